@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: GB/s ingested by the hash+compress hot path (Skein-512 + LZ4, 64 KiB blocks).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline figure needs and nothing else: it generates the headline leg's input, runs W warm-up and K timed
+steps, writes the last step's outputs when --dump-outputs is given (dump_outputs()) and prints the result line.  Everything the rest
+of this text describes beyond that -- the oracle parity and device round trip, the CPU baselines, the standalone kernels, the further
+legs, the host-buffer path and the {"leg_detail": ...} records -- runs only with --full.
 
 One "step" is one pass of the hot path (compress every block, then hash every block -- ProcessBlock,
 src/hashandcompress/HashAndCompress.cpp:231-261) over this rank's blocks, which are generated on the device
@@ -68,6 +73,12 @@ def parse():
     ap.add_argument("--hash", default="skein512", choices=list(HASH_IDS))
     ap.add_argument("--comp", default="lz4", choices=list(COMP_IDS))
     ap.add_argument("--data", default="random", choices=["random", "mixed", "corpus"], help="input of the headline leg")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write what the last step computed as DIR/<name>.npy (float32/float64, seeded samples, "
+                         "under 64 MB in all); see dump_outputs()")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: parity against the CPU oracle, device round trip, CPU "
+                         "baselines, the extra legs and the host-buffer path (the options below act only with --full)")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=10.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-legs", action="store_true", help="headline leg only")
@@ -79,7 +90,12 @@ def parse():
     ap.add_argument("--dry-run-cpu", action="store_true",
                     help="rehearsal of the N > 1 control flow without a GPU: gloo, CPU tensors, the oracle standing in for the device "
                          "on a few small blocks (tests/test_bench_dryrun.py); prints a line marked dry_run, never a benchmark number")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.standalone and not args.full:
+        ap.error("--standalone needs --full")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -276,8 +292,42 @@ def full_parity(torch, name, hash_name, comp_name, bs, nb, kind, first_block, sr
 # ---------------------------------------------------------------------------------------------------------------
 # one timed leg
 # ---------------------------------------------------------------------------------------------------------------
+def dump_outputs(dirname, torch, all_digests, all_totals, dst, stride, sizes, nb):
+    """--dump-outputs: what a caller of the hot path holds after the last timed step, as .npy files that two builds can be compared
+    by.  Byte arrays are stored as float32 (exact), counts as float64; where an output is larger than the budget, a fixed sample of
+    its rows (seeded, sorted, saved as <name>_rows.npy) stands in for it.  At most ~47 MB in all.
+      digests   [rows, digest bytes] digests of all ranks in global block order (the gathered result)
+      sizes     [rows] compressed size of each of this rank's blocks (0 = LZF stored the block raw)
+      payload   [rows, min(stride, 1 MiB)] compressed bytes of sampled slots of this rank, zero past each block's size
+      totals    [2] compressed bytes out over all ranks, blocks stored raw"""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+
+    def rows(name, n, k, salt):
+        if n <= k:
+            return np.arange(n)
+        r = np.sort(np.random.default_rng([SEED, salt]).choice(n, k, replace=False))
+        np.save(os.path.join(dirname, name + "_rows.npy"), r.astype(np.float64))
+        return r
+
+    def save(name, arr):
+        np.save(os.path.join(dirname, name + ".npy"), arr)
+
+    d_rows = rows("digests", all_digests.shape[0], 1 << 16, 1)
+    save("digests", all_digests[torch.from_numpy(d_rows).to(all_digests.device)].cpu().numpy().astype(np.float32))
+    hsz = sizes.cpu().numpy()
+    s_rows = rows("sizes", nb, 1 << 20, 2)
+    save("sizes", hsz[s_rows].astype(np.float32))
+    width = min(stride, 1 << 20)
+    p_rows = rows("payload", nb, max(1, (4 << 20) // width), 3)
+    slots = dst.view(nb, stride)[torch.from_numpy(p_rows).to(dst.device), :width].cpu().numpy()
+    slots[np.arange(width)[None, :] >= hsz[p_rows].astype(np.int64)[:, None]] = 0   # past the block's size the slot holds no output
+    save("payload", slots.astype(np.float32))
+    save("totals", all_totals.cpu().numpy().astype(np.float64))
+
+
 def run_leg(cw, torch, args, name, hash_name, comp_name, bs, nb, kind, steps, warmup, world, rank, local_rank, first_block,
-            baseline_s, standalone=False):
+            baseline_s, standalone=False, dump_dir=None):
     from compute_war_amd.shard import gather_results
     db = cw.digest_bytes(hash_name)
     stride = (cw.compress_bound(comp_name, bs) + 15) // 16 * 16
@@ -331,6 +381,8 @@ def run_leg(cw, torch, args, name, hash_name, comp_name, bs, nb, kind, steps, wa
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, torch, all_digests, all_totals, dst, stride, sizes, nb)
     prof = cw.profile_read(reset=True)
     names = cw.profile_kernels()   # what the library launched, from the library
     k_ms = {"comp": prof["codec"][0] / max(prof["codec"][1], 1), "hash": prof["hash"][0] / max(prof["hash"][1], 1)}
@@ -357,8 +409,8 @@ def run_leg(cw, torch, args, name, hash_name, comp_name, bs, nb, kind, steps, wa
 
     # parity at the leg's own scale (outside the timed region): every block against the CPU oracle where the input is periodic,
     # 4,096 regenerated blocks otherwise
-    spot, sample, per_corpus = "skipped", None, None
-    if rank == 0:
+    spot, sample, per_corpus = "skipped" if args.full else "not run (--full checks it)", None, None
+    if rank == 0 and args.full:
         import numpy as np
         spot = full_parity(torch, name, hash_name, comp_name, bs, nb, kind, first_block, src, dst, stride, sizes, digests)
         hz = sizes.cpu().numpy()
@@ -381,7 +433,7 @@ def run_leg(cw, torch, args, name, hash_name, comp_name, bs, nb, kind, steps, wa
     # full-size round trip (outside the timed region): every block this rank compressed is decoded on the device and compared
     # with its input -- a check that does not depend on the oracle and covers all of the leg's blocks, not a sample
     roundtrip = None
-    if not args.no_roundtrip:
+    if args.full and not args.no_roundtrip:
         t_rt = time.perf_counter()
         chunk = max(1, min(nb, (2 << 30) // bs))
         back = torch.empty(chunk * bs, dtype=torch.uint8, device="cuda")
@@ -407,7 +459,7 @@ def run_leg(cw, torch, args, name, hash_name, comp_name, bs, nb, kind, steps, wa
     # (tools/lz_probe_count.py, a pure-Python walk of the parser) over a few sampled blocks.
     line_roof = None
     rl = os.path.join(ROOT, "profiles", "random_line.json")
-    if rank == 0 and comp_name == "lz4" and bs > 4096 and kind != "random" and "lanes" in names["codec"] and os.path.exists(rl):
+    if args.full and rank == 0 and comp_name == "lz4" and bs > 4096 and kind != "random" and "lanes" in names["codec"] and os.path.exists(rl):
         import importlib.util
         spec = importlib.util.spec_from_file_location("lz_probe_count", os.path.join(ROOT, "tools", "lz_probe_count.py"))
         lpc = importlib.util.module_from_spec(spec)
@@ -625,7 +677,8 @@ def main():
     first, last = shard_range(nb * world, rank, world)
     assert last - first == nb
     head, sample = run_leg(cw, torch, args, "headline", args.hash, args.comp, bs, nb, args.data, args.steps, args.warmup, world, rank, local_rank,
-                           first, 0.0 if (args.no_cpu_baseline or world > 1) else args.cpu_baseline_seconds, standalone=args.standalone)
+                           first, 0.0 if (not args.full or args.no_cpu_baseline or world > 1) else args.cpu_baseline_seconds,
+                           standalone=args.standalone, dump_dir=args.dump_outputs)
     if rank != 0:
         return
     detail_path = os.path.join(ROOT, "gpurun_out", "bench_detail.json")
@@ -640,7 +693,8 @@ def main():
         except OSError:
             pass
 
-    emit_detail(head)
+    if args.full:
+        emit_detail(head)
     rf = head["roofline"]
     out = {
         "metric": "GB/s ingested (Skein-512 + LZ4, 64 KiB blocks)" if (args.hash, args.comp, bs) == ("skein512", "lz4", 65536)
@@ -678,7 +732,7 @@ def main():
         detail["cpu_baseline_reference_style"] = ref
         cb["pinned14"] = {k: v["value"] for k, v in ref.items() if isinstance(v, dict)}
         out["cpu_baseline"] = cb
-    if world == 1 and not args.no_legs:
+    if args.full and world == 1 and not args.no_legs:
         lb = args.leg_bytes
         bsec = 0.0 if args.no_cpu_baseline else 4.0
         # (leg, hash, codec, block bytes, input, blocks, steps, the reference's published MB/s for the pair at 14 threads -- its own host,

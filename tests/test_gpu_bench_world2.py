@@ -28,7 +28,7 @@ def _line(r):
 
 def test_bench_two_ranks_on_one_gpu_equal_one_rank():
     nb = 4096   # per rank: enough for the sliced Skein launches and the span scan (256 MiB of input per rank)
-    common = ["--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--no-legs"]
+    common = ["--steps", "3", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-legs"]   # --full: parity and round trip
     env = dict(os.environ, CW_BENCH_REHEARSE="gloo-one-gpu", HSA_ENABLE_IPC_MODE_LEGACY="0")
     two = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
                           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--blocks-per-gpu", str(nb)] + common,

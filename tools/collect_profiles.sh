@@ -14,21 +14,21 @@ LEGS=("mixed skein512 lz4 65536 mixed 65536" "corpus_skein512_lz4 skein512 lz4 6
       "corpus_skein512_lz4_51728 skein512 lz4 4096 corpus 51728" "corpus_skein256_lz4_4k skein lz4 4096 corpus 1048576"
       "corpus_sha256_lzf_4k sha256mb lzf 4096 corpus 1048576" "corpus_sha256_lzf_64k sha256mb lzf 65536 corpus 65536" "corpus_sha256_lzf_64k_16g sha256mb lzf 65536 corpus 262144")
 if [ "$PART" != pmc ]; then
-python bench.py > $O/bench_default.json 2> $O/bench_default.err || { tail -20 $O/bench_default.err; exit 1; }
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err || { tail -20 $O/bench_default.err; exit 1; }
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --stats -d $O/prof_headline -o p -f csv -- python3 bench.py --no-legs --no-cpu-baseline > $O/prof_headline.json 2> $O/prof_headline.err
+rocprofv3 --kernel-trace --stats -d $O/prof_headline -o p -f csv -- python3 bench.py --full --no-legs --no-cpu-baseline > $O/prof_headline.json 2> $O/prof_headline.err
 for leg in "${LEGS[@]}"; do
   set -- $leg
-  rocprofv3 --kernel-trace --stats -d $O/prof_$1 -o p -f csv -- python3 bench.py --no-legs --no-cpu-baseline --hash $2 --comp $3 --block-bytes $4 --data $5 --blocks-per-gpu $6 --steps 3 --warmup 1 > $O/prof_$1.json 2> $O/prof_$1.err
+  rocprofv3 --kernel-trace --stats -d $O/prof_$1 -o p -f csv -- python3 bench.py --full --no-legs --no-cpu-baseline --hash $2 --comp $3 --block-bytes $4 --data $5 --blocks-per-gpu $6 --steps 3 --warmup 1 > $O/prof_$1.json 2> $O/prof_$1.err
 done
 fi
 if [ "$PART" = stats ]; then echo collected: $(ls $O | wc -l) entries in $O; exit 0; fi
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --kernel-trace -d $O/pmc_headline_$c -o p -f csv -- python3 bench.py --no-legs --no-cpu-baseline --no-roundtrip --steps 1 --warmup 0 > $O/pmc_headline_$c.log 2>&1
+  rocprofv3 --pmc $c --kernel-trace -d $O/pmc_headline_$c -o p -f csv -- python3 bench.py --full --no-legs --no-cpu-baseline --no-roundtrip --steps 1 --warmup 0 > $O/pmc_headline_$c.log 2>&1
   for leg in "${LEGS[@]}"; do
     set -- $leg
-    rocprofv3 --pmc $c --kernel-trace -d $O/pmc_$1_$c -o p -f csv -- python3 bench.py --no-legs --no-cpu-baseline --hash $2 --comp $3 --block-bytes $4 --data $5 --blocks-per-gpu $6 --steps 1 --warmup 0 > $O/pmc_$1_$c.log 2>&1
+    rocprofv3 --pmc $c --kernel-trace -d $O/pmc_$1_$c -o p -f csv -- python3 bench.py --full --no-legs --no-cpu-baseline --hash $2 --comp $3 --block-bytes $4 --data $5 --blocks-per-gpu $6 --steps 1 --warmup 0 > $O/pmc_$1_$c.log 2>&1
   done
 done
 echo collected: $(ls $O | wc -l) entries in $O

@@ -11,6 +11,10 @@ What it writes (all DATA -- inputs and expected outputs, no reference source tex
                                 Skein-256-128 (a variant no KAT covers) computed by oracle/_ref =
                                 the reference's Optimized_64bit/skein.c + skein_block.c compiled
                                 where they lie (oracle/Makefile target `ref`).
+* skein_ref_live.json        -- oracle/_ref's digests of the fresh inputs of
+                                tests/test_oracle_skein.py::test_live_reference_build_when_present
+                                (Skein-512-512/-256/-160, Skein-256-128), so that the test also runs
+                                where oracle/_ref cannot be built (`--live` writes only this file).
 * survey_anchors.json        -- the reference outputs SURVEY.md 8(c) / BASELINE.md section 2 recorded
                                 (LZ4 1.8.2 / liblzf sizes, SHA-256 of outputs, corpus ratios).
 * corpus/canterbury/*        -- the reference's dataset/canterbury files (data the reference's own
@@ -205,6 +209,21 @@ def main():
     print("golden fixtures written to", OUT)
 
 
+LIVE_SIZES = (0, 1, 31, 32, 33, 63, 64, 65, 127, 128, 129, 4096, 65536, 70001)
+
+
+def ref_live():
+    assert O.ref_available(), "build oracle/_ref first (make -C oracle ref)"
+    recs = []
+    for n in LIVE_SIZES:
+        d = seeded_block(n + 7, n, "random")
+        recs.append({"n": n, "kind": "random", "seed": n + 7,
+                     **{f"skein512_{bits}": O.ref_skein512(d, bits).hex() for bits in (512, 256, 160)},
+                     "skein256_128": O.ref_skein256(d, 128).hex()})
+    return {"source": "oracle/_ref/libskein_ref.so (see skein_ref_blocks.json); inputs regenerated by tools/make_golden.py:seeded_block",
+            "blocks": recs}
+
+
 def skein_internals():
     """Round-by-round Threefish states of the reference's skein_golden_kat_short_internals.txt (generated by the reference's
     SKEIN_DEBUG build, skein.h:246-254): every Threefish-256 / -512 call record of the file = tweak, key words, input block
@@ -237,5 +256,10 @@ if __name__ == "__main__":
         with open(f"{OUT}/skein_internals.json", "w") as f:
             json.dump(skein_internals(), f)
         print("wrote skein_internals.json")
+    elif "--live" in sys.argv:      # only the live-input fixture
+        O.build()
+        with open(f"{OUT}/skein_ref_live.json", "w") as f:
+            json.dump(ref_live(), f, indent=0)
+        print("wrote skein_ref_live.json")
     else:
         main()
