@@ -25,6 +25,7 @@ ABI_SYMBOLS = [
     "cw_offload_create", "cw_offload_destroy", "cw_offload_reset", "cw_offload_enqueue", "cw_offload_start",
     "cw_offload_complete", "cw_offload_completed", "cw_offload_state", "cw_offload_error", "cw_offload_do",
     "cw_offload_thread_start", "cw_offload_submit", "cw_offload_thread_stop",
+    "cw_dedupe_create", "cw_dedupe_destroy", "cw_dedupe_count", "cw_dev_dedupe", "cw_dev_hash_dedupe_compress",
     "cw_shard_range", "cw_mgpu_create", "cw_mgpu_destroy", "cw_mgpu_ndev", "cw_mgpu_device", "cw_mgpu_last_error", "cw_mgpu_gather",
 ]
 
@@ -119,6 +120,10 @@ def lib() -> C.CDLL:
         "cw_offload_state": ([vp], C.c_int), "cw_offload_error": ([vp], C.c_int), "cw_offload_do": ([vp], C.c_int),
         "cw_offload_thread_start": ([], C.c_int), "cw_offload_submit": ([vp], C.c_int),
         "cw_offload_thread_stop": ([], None),
+        "cw_dedupe_create": ([C.c_int, sz], vp), "cw_dedupe_destroy": ([vp], None),
+        "cw_dedupe_count": ([vp, vp], C.c_int),
+        "cw_dev_dedupe": ([vp, vp, sz, C.c_uint64, vp, vp, vp, vp], C.c_int),
+        "cw_dev_hash_dedupe_compress": ([vp, C.c_int, vp, sz, sz, sz, C.c_uint64, vp, vp, vp, vp, sz, u32p, vp, vp], C.c_int),
         "cw_shard_range": ([sz, C.c_int, C.c_int, vp, vp], None),
         "cw_mgpu_create": ([vp, C.c_int], vp), "cw_mgpu_destroy": ([vp], None), "cw_mgpu_ndev": ([vp], C.c_int),
         "cw_mgpu_device": ([vp, C.c_int], C.c_int), "cw_mgpu_last_error": ([], C.c_char_p),

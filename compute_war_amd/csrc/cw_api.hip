@@ -1190,6 +1190,205 @@ unsigned cw_decompress_lzf(const void *src, unsigned csize, void *dst, unsigned 
     return st == 0 ? (unsigned)bb : 0;
 }
 
+// ---- dedupe index (kernels and protocol: dedupe_kernels.hip) -------------------------------------------------------
+struct cw_dedupe {
+    int device = -1, hash_alg = 0;
+    unsigned words = 0;              // u64 words per digest
+    size_t max_entries = 0;
+    uint64_t cap = 0;                // slots: a power of two >= 2 x max_entries
+    void *table = nullptr;           // one allocation: state | value | key | min_idx | ctrl
+    uint64_t *state = nullptr, *value = nullptr, *key = nullptr;
+    uint32_t *min_idx = nullptr;
+    uint64_t *ctrl = nullptr;        // [0] count, [1] a probe reached its bound, [2] n_new of the fused call
+    uint64_t *h_ctrl = nullptr;      // pinned: the fused call's copy of ctrl[1..2]
+    DevBuf rec, flags, offs, gather; // per-call scratch, shared by the calls because they are serialised
+    hipEvent_t last = nullptr;       // the last call's work: the next call's stream waits for it
+    uint64_t count_bound = 0;        // upper bound on ctrl[0] (every block of every call counted)
+    std::mutex lock;                 // guards `last`, the scratch and count_bound
+};
+
+namespace {
+// block indices are u32 on the device, and a launch of one lane per block must stay below 2^32 work-items
+constexpr size_t kMaxDedupeBlocks = ((size_t)1 << 32) - 256;
+
+// checks shared by the dedupe calls
+int dedupe_args(cw_dedupe *x, size_t nblocks, uint64_t base)
+{
+    int rc = ensure_init();
+    if (rc != CW_OK) return rc;
+    if (!x) return fail(CW_ERR_BAD_ARG, "NULL dedupe index");
+    if (current_device() != x->device) return fail(CW_ERR_BAD_ARG, "dedupe index of device %d used on device %d", x->device, current_device());
+    if (nblocks > kMaxDedupeBlocks) return fail(CW_ERR_BAD_ARG, "nblocks %zu > 2^32 - 256", nblocks);
+    if (base > UINT64_MAX - nblocks) return fail(CW_ERR_BAD_ARG, "base + nblocks wraps");
+    return CW_OK;
+}
+
+// x->lock held: refuse a call that could overflow the table.  The host bound only grows, so only when it would refuse is the
+// exact count read (after the last call has finished).
+int dedupe_admit(cw_dedupe *x, size_t n)
+{
+    if (x->count_bound + n <= x->max_entries) return CW_OK;
+    HIP_TRY(hipEventSynchronize(x->last));
+    uint64_t c[2];
+    HIP_TRY(hipMemcpy(c, x->ctrl, sizeof c, hipMemcpyDeviceToHost));
+    if (c[1]) return fail(CW_ERR_HIP, "dedupe index: a probe reached its bound (the table is inconsistent)");
+    x->count_bound = c[0];
+    if (c[0] + n > x->max_entries)
+        return fail(CW_ERR_NOMEM, "dedupe index full: %llu entries + %zu blocks > max_entries %zu", (unsigned long long)c[0], n, x->max_entries);
+    return CW_OK;
+}
+
+// x->lock held, admitted: probe, resolve, index-only pack scan of the new flags, scatter -- queued on s
+int dedupe_enqueue(cw_dedupe *x, const uint64_t *dig, uint32_t n, uint64_t base, uint64_t *ref, uint32_t *new_idx, uint64_t *d_n_new,
+                   hipStream_t s)
+{
+    int rc;
+    if (x->rec.cap < (size_t)n * 8 || x->offs.cap < ((size_t)n + 1) * 8) // growing frees scratch the last call may still use
+        HIP_TRY(hipEventSynchronize(x->last));
+    if ((rc = x->rec.reserve((size_t)n * 8)) != CW_OK || (rc = x->flags.reserve((size_t)n * 4)) != CW_OK ||
+        (rc = x->offs.reserve(((size_t)n + 1) * 8)) != CW_OK)
+        return rc;
+    uint64_t *rec = (uint64_t *)x->rec.p, *off = (uint64_t *)x->offs.p;
+    uint32_t *flags = (uint32_t *)x->flags.p;
+    x->count_bound += n; // from the first launch on, the table may change
+    hipError_t e = cw::dedupe_probe_launch(x->words, dig, n, x->state, x->min_idx, x->value, x->key, x->cap - 1, rec, ref,
+                                           reinterpret_cast<unsigned long long *>(x->ctrl + 1), s);
+    if (e == hipSuccess)
+        e = cw::dedupe_resolve_launch(x->words, dig, n, base, x->min_idx, x->state, x->value, x->key, rec, ref, flags, s);
+    if (e == hipSuccess) e = cw::pack_launch(nullptr, 0, flags, n, nullptr, off, s);
+    if (e == hipSuccess) e = cw::dedupe_scatter_launch(flags, off, n, rec, x->min_idx, new_idx, d_n_new, x->ctrl, s);
+    if (e != hipSuccess) return fail(CW_ERR_HIP, "dedupe launch: %s", hipGetErrorString(e));
+    return CW_OK;
+}
+} // namespace
+
+cw_dedupe_t *cw_dedupe_create(int hash_alg, size_t max_entries)
+{
+    if (ensure_init() != CW_OK) return nullptr;
+    const size_t db = cw_digest_bytes(hash_alg);
+    if (db == 0 || max_entries == 0 || max_entries > ((size_t)1 << 40)) {
+        fail(CW_ERR_BAD_ARG, "cw_dedupe_create: hash algorithm %d / max_entries %zu not usable", hash_alg, max_entries);
+        return nullptr;
+    }
+    cw_dedupe *x = new cw_dedupe;
+    x->device = current_device();
+    x->hash_alg = hash_alg;
+    x->words = (unsigned)(db / 8);
+    x->max_entries = max_entries;
+    x->cap = 2;
+    while (x->cap < 2 * (uint64_t)max_entries) x->cap <<= 1;
+    const size_t cap = x->cap, bytes = cap * (20 + db) + 4 * sizeof(uint64_t);
+    hipError_t e = hipMalloc(&x->table, bytes);
+    if (e == hipSuccess) {
+        uint8_t *p = (uint8_t *)x->table;
+        x->state = (uint64_t *)p;
+        x->value = (uint64_t *)(p + cap * 8);
+        x->key = (uint64_t *)(p + cap * 16);
+        x->min_idx = (uint32_t *)(p + cap * (16 + db));
+        x->ctrl = (uint64_t *)(p + cap * (20 + db)); // cap is even: 8-byte aligned
+        e = hipMemset(x->state, 0, cap * 8);
+        if (e == hipSuccess) e = hipMemset(x->min_idx, 0xFF, cap * 4);
+        if (e == hipSuccess) e = hipMemset(x->ctrl, 0, 4 * sizeof(uint64_t));
+        if (e == hipSuccess) e = hipDeviceSynchronize(); // the calls come on other streams
+    }
+    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&x->h_ctrl), 2 * sizeof(uint64_t), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&x->last, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        fail(e == hipErrorOutOfMemory ? CW_ERR_NOMEM : CW_ERR_HIP, "cw_dedupe_create(%zu entries, %zu bytes): %s", max_entries, bytes,
+             hipGetErrorString(e));
+        cw_dedupe_destroy(x);
+        return nullptr;
+    }
+    return x;
+}
+
+void cw_dedupe_destroy(cw_dedupe_t *x)
+{
+    if (!x) return;
+    (void)hipSetDevice(x->device);
+    if (x->last) { (void)hipEventSynchronize(x->last); (void)hipEventDestroy(x->last); }
+    x->rec.release(); x->flags.release(); x->offs.release(); x->gather.release();
+    if (x->table) (void)hipFree(x->table);
+    if (x->h_ctrl) (void)hipHostFree(x->h_ctrl);
+    delete x;
+}
+
+int cw_dedupe_count(cw_dedupe_t *x, uint64_t *count)
+{
+    int rc = dedupe_args(x, 0, 0);
+    if (rc != CW_OK) return rc;
+    if (!count) return fail(CW_ERR_BAD_ARG, "NULL count");
+    std::lock_guard<std::mutex> g(x->lock);
+    HIP_TRY(hipEventSynchronize(x->last));
+    uint64_t c[2];
+    HIP_TRY(hipMemcpy(c, x->ctrl, sizeof c, hipMemcpyDeviceToHost));
+    if (c[1]) return fail(CW_ERR_HIP, "dedupe index: a probe reached its bound (the table is inconsistent)");
+    x->count_bound = c[0];
+    *count = c[0];
+    return CW_OK;
+}
+
+int cw_dev_dedupe(cw_dedupe_t *x, const void *d_digests, size_t nblocks, uint64_t base, uint64_t *d_ref, uint32_t *d_new_idx,
+                  uint64_t *d_n_new, void *stream)
+{
+    int rc = dedupe_args(x, nblocks, base);
+    if (rc != CW_OK || nblocks == 0) return rc;
+    if (!d_digests || !d_ref || !d_new_idx || !d_n_new) return fail(CW_ERR_BAD_ARG, "NULL device pointer");
+    if ((uintptr_t)d_digests % 8) return fail(CW_ERR_BAD_ARG, "d_digests must be 8-byte aligned");
+    const hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::mutex> g(x->lock);
+    if ((rc = dedupe_admit(x, nblocks)) != CW_OK) return rc;
+    HIP_TRY(hipStreamWaitEvent(s, x->last, 0));
+    rc = dedupe_enqueue(x, (const uint64_t *)d_digests, (uint32_t)nblocks, base, d_ref, d_new_idx, d_n_new, s);
+    HIP_TRY(hipEventRecord(x->last, s));
+    return rc;
+}
+
+// hash -> dedupe -> one 16-byte copy back + a synchronise -> the codec over the new blocks only.  The codec cannot start before
+// the dedupe result, so hash and codec do not overlap as in dev_fused.
+int cw_dev_hash_dedupe_compress(cw_dedupe_t *x, int comp_alg, const void *d_src, size_t block_bytes, size_t src_stride, size_t nblocks,
+                                uint64_t base, void *d_digests, uint64_t *d_ref, uint32_t *d_new_idx, void *d_dst, size_t dst_stride,
+                                uint32_t *d_sizes, size_t *n_new, void *stream)
+{
+    if (n_new) *n_new = 0;
+    int rc = dedupe_args(x, nblocks, base);
+    if (rc != CW_OK) return rc;
+    if (!n_new) return fail(CW_ERR_BAD_ARG, "NULL n_new");
+    if (comp_alg != CW_COMP_LZ4 && comp_alg != CW_COMP_LZF) return fail(CW_ERR_BAD_ARG, "unknown compression algorithm %d", comp_alg);
+    if (nblocks == 0) return CW_OK;
+    if (!d_src || !d_digests || !d_ref || !d_new_idx || !d_dst || !d_sizes) return fail(CW_ERR_BAD_ARG, "NULL device pointer");
+    if ((uintptr_t)d_digests % 8) return fail(CW_ERR_BAD_ARG, "d_digests must be 8-byte aligned");
+    if (block_bytes == 0 || (rc = check_block(block_bytes)) != CW_OK) return rc ? rc : fail(CW_ERR_BAD_ARG, "block_bytes == 0");
+    if (src_stride < block_bytes) return fail(CW_ERR_BAD_ARG, "src_stride < block_bytes");
+    if (dst_stride < cw_compress_bound(comp_alg, block_bytes))
+        return fail(CW_ERR_BAD_ARG, "dst_stride %zu < bound %zu", dst_stride, cw_compress_bound(comp_alg, block_bytes));
+    const hipStream_t s = (hipStream_t)stream;
+    const uint8_t *src = (const uint8_t *)d_src;
+    std::lock_guard<std::mutex> g(x->lock); // held to the end: the gather buffer is the index's
+    if ((rc = dedupe_admit(x, nblocks)) != CW_OK) return rc;
+    HIP_TRY(hipStreamWaitEvent(s, x->last, 0));
+    rc = dev_hash(x->hash_alg, src, block_bytes, src_stride, nblocks, (uint8_t *)d_digests, s, false, true);
+    if (rc == CW_OK) rc = dedupe_enqueue(x, (const uint64_t *)d_digests, (uint32_t)nblocks, base, d_ref, d_new_idx, x->ctrl + 2, s);
+    if (rc == CW_OK) {
+        HIP_TRY(hipMemcpyAsync(x->h_ctrl, x->ctrl + 1, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (x->h_ctrl[0]) rc = fail(CW_ERR_HIP, "dedupe index: a probe reached its bound (the table is inconsistent)");
+    }
+    const size_t k = rc == CW_OK ? (size_t)x->h_ctrl[1] : 0;
+    if (rc == CW_OK && k == nblocks) { // all new: the codec on the caller's blocks, slots as cw_dev_hash_and_compress
+        rc = dev_compress(comp_alg, src, block_bytes, src_stride, nblocks, (uint8_t *)d_dst, dst_stride, d_sizes, s);
+    } else if (rc == CW_OK && k) { // (the stream is idle here, and it waited for the last call: nothing uses the old buffer)
+        rc = x->gather.reserve(k * block_bytes);
+        hipError_t e = rc == CW_OK ? cw::dedupe_gather_launch(src, block_bytes, src_stride, d_new_idx, k, (uint8_t *)x->gather.p, s) : hipSuccess;
+        if (e != hipSuccess) rc = fail(CW_ERR_HIP, "gather launch: %s", hipGetErrorString(e));
+        if (rc == CW_OK)
+            rc = dev_compress(comp_alg, (const uint8_t *)x->gather.p, block_bytes, block_bytes, k, (uint8_t *)d_dst, dst_stride, d_sizes, s);
+    }
+    HIP_TRY(hipEventRecord(x->last, s));
+    if (rc == CW_OK) *n_new = k;
+    return rc;
+}
+
 // ---- HashOffload -------------------------------------------------------------------------------------------------
 struct cw_offload {
     int hash_alg;

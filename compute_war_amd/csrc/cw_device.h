@@ -118,6 +118,17 @@ void skein_release_stream(hipStream_t stream);
 void lz4_release_stream(hipStream_t stream);
 void lzf_release_stream(hipStream_t stream);
 void pack_release_stream(hipStream_t stream);
+// fingerprint index (dedupe_kernels.hip): words = u64 words per digest (2 / 4 / 8); mask = slots - 1; rec / flags = per-block
+// scratch of the call; off = exclusive scan of flags (pack_launch, index only); err |= 1 if a probe reached the bound
+hipError_t dedupe_probe_launch(unsigned words, const uint64_t *dig, uint32_t n, uint64_t *state, uint32_t *min_idx, const uint64_t *value,
+                               const uint64_t *key, uint64_t mask, uint64_t *rec, uint64_t *ref, unsigned long long *err, hipStream_t s);
+hipError_t dedupe_resolve_launch(unsigned words, const uint64_t *dig, uint32_t n, uint64_t base, const uint32_t *min_idx, uint64_t *state,
+                                 uint64_t *value, uint64_t *key, const uint64_t *rec, uint64_t *ref, uint32_t *flags, hipStream_t s);
+hipError_t dedupe_scatter_launch(const uint32_t *flags, const uint64_t *off, uint32_t n, const uint64_t *rec, uint32_t *min_idx,
+                                 uint32_t *new_idx, uint64_t *n_new, uint64_t *count, hipStream_t s);
+// block new_idx[j] (src_stride apart in src) -> dst + j * block_bytes, for j < n_new
+hipError_t dedupe_gather_launch(const uint8_t *src, size_t block_bytes, size_t src_stride, const uint32_t *new_idx, size_t n_new,
+                                uint8_t *dst, hipStream_t s);
 hipError_t sum_sizes_launch(const uint32_t *sizes, size_t n, uint32_t raw_bytes, uint64_t *totals, hipStream_t stream);
 hipError_t gen_random_launch(uint64_t seed, uint64_t first_block, size_t nblocks, size_t block_bytes, uint8_t *dst,
                              hipStream_t stream);

@@ -287,6 +287,67 @@ def profile_kernels() -> dict:
     return out
 
 
+# ---- dedupe index -------------------------------------------------------------------------------------
+class DedupeIndex:
+    """Device-resident fingerprint index of one hash algorithm (cw_dedupe_*): full digests, each with a 64-bit value.
+
+    ``dev_dedupe`` is the batched lookup-or-insert, ``dev_hash_dedupe_compress`` hashes, dedupes and compresses only the
+    new blocks.  Both take raw device pointers and a stream handle like the other ``dev_*`` functions; a full index raises
+    ``CwError`` with code ``CW_ERR_NOMEM`` (-5) and is left unchanged."""
+
+    def __init__(self, hash_alg, max_entries: int):
+        self.hash_alg = _hash_id(hash_alg)
+        self._h = lib().cw_dedupe_create(self.hash_alg, max_entries)
+        if not self._h:
+            err = lib().cw_last_error().decode(errors="replace")
+            raise _lib.CwError(-1 if "no HIP device" in err else -5 if "out of memory" in err else -2, err)
+        self.max_entries = max_entries
+
+    def _x(self):
+        if not self._h:
+            raise _lib.CwError(-4, "DedupeIndex is closed")
+        return self._h
+
+    def dev_dedupe(self, d_digests: int, nblocks: int, base: int, d_ref: int, d_new_idx: int, d_n_new: int, stream: int = 0) -> None:
+        """ref[i] = value of block i's first occurrence (an earlier call's, else base + the lowest j of this call with the same
+        digest); new_idx[0..n_new) = the new blocks in ascending order, inserted with value base + i; *d_n_new = n_new (u64)."""
+        check(lib().cw_dev_dedupe(self._x(), d_digests, nblocks, base, d_ref, d_new_idx, d_n_new, stream))
+
+    def dev_hash_dedupe_compress(self, comp_alg, d_src: int, block_bytes: int, nblocks: int, base: int, d_digests: int, d_ref: int,
+                                 d_new_idx: int, d_dst: int, dst_stride: int, d_sizes: int, stream: int = 0,
+                                 src_stride: int | None = None) -> int:
+        """Digests of every block, dedupe, then the codec over the new blocks only: slot j of d_dst holds block new_idx[j].
+        Synchronises the stream once; returns n_new."""
+        n_new = C.c_size_t(0)
+        check(lib().cw_dev_hash_dedupe_compress(self._x(), _comp_id(comp_alg), d_src, block_bytes, src_stride or block_bytes, nblocks,
+                                                base, d_digests, d_ref, d_new_idx, d_dst, dst_stride, d_sizes, C.byref(n_new), stream))
+        return int(n_new.value)
+
+    def count(self) -> int:
+        """Entries in the index (waits for the index's last call)."""
+        n = C.c_uint64(0)
+        check(lib().cw_dedupe_count(self._x(), C.byref(n)))
+        return int(n.value)
+
+    def close(self) -> None:
+        if self._h:
+            lib().cw_dedupe_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ---- HashOffload ------------------------------------------------------------------------------------
 class HashOffload:
     """HashOffload.h:13-64: Reset(data, results, onComplete) -> Enqueue() -> Start() -> Complete()."""

@@ -183,6 +183,36 @@ int cw_dev_gen_mixed(uint64_t seed, uint64_t first_block, size_t nblocks, size_t
 int cw_dev_sum_sizes(const uint32_t *d_sizes, size_t nblocks, uint32_t raw_bytes, uint64_t *d_totals,
                      void *stream);
 
+/* ---- dedupe index: a device-resident fingerprint index next to the fingerprint engine ------------
+ * The reference has no counterpart: HashAndCompress.cpp computes each block's digest and discards it (:257).
+ * An index belongs to one hash algorithm and stores FULL digests, each with a 64-bit value.  Open addressing with
+ * linear probing over a power of two >= 2 * max_entries slots, allocated once on the calling thread's device:
+ * 20 + digest bytes per slot (Skein-512 84 B, SHA-256 52 B, Skein-256-128 36 B; 16 Mi Skein-512 entries = 2.7 GiB),
+ * plus per-call scratch of 20 B per block (and the fused call's gather buffer, n_new * block_bytes).
+ * Calls on one index are serialised on the device whatever stream they come on (each waits for the previous call). */
+typedef struct cw_dedupe cw_dedupe_t;
+cw_dedupe_t *cw_dedupe_create(int hash_alg, size_t max_entries);   /* NULL + cw_last_error() on failure / no device */
+void         cw_dedupe_destroy(cw_dedupe_t *x);                    /* waits for the index's last call */
+int          cw_dedupe_count(cw_dedupe_t *x, uint64_t *count);    /* entries; synchronises on the index's last call */
+/* Lookup-or-insert of nblocks digests (d_digests 8-byte aligned, cw_digest_bytes() each); block i has the value base + i.
+ * d_ref[i] = value of the block's first occurrence: the stored value if an earlier call inserted the digest, else base + j
+ * for the lowest j of this call with the same digest.  Block i is new iff j == i; d_new_idx[0..n_new) lists the new blocks
+ * in ascending order, *d_n_new = n_new, and they are inserted with base + i.  Deterministic: what a sequential loop over the
+ * batch gives.  CW_ERR_NOMEM (index unchanged, nothing launched) when count + nblocks > max_entries; CW_ERR_BAD_ARG when
+ * nblocks > 2^32 - 256 (indices are u32 on the device) or base + nblocks wraps.  All pointers device memory; queued on `stream`, not synchronised.
+ * d_ref[nblocks] u64, d_new_idx[nblocks] u32 (first n_new valid), *d_n_new u64.                                        */
+int cw_dev_dedupe(cw_dedupe_t *x, const void *d_digests, size_t nblocks, uint64_t base,
+                  uint64_t *d_ref, uint32_t *d_new_idx, uint64_t *d_n_new, void *stream);
+/* hash every block (d_digests) -> dedupe -> compress ONLY the new blocks: compressed block new_idx[j] in slot j of
+ * d_dst, its size in d_sizes[j] (0 = did not fit, as cw_dev_compress), so cw_dev_pack over (d_dst, d_sizes, n_new) gives
+ * the stream of new blocks.  Synchronises the stream once, after the dedupe step (the codecs' launch policy needs the
+ * block count on the host); *n_new returns that count.  Duplicates are never compressed.  Hash and codec run one after
+ * the other here (cw_dev_hash_and_compress runs them side by side).                                                  */
+int cw_dev_hash_dedupe_compress(cw_dedupe_t *x, int comp_alg, const void *d_src, size_t block_bytes,
+                                size_t src_stride, size_t nblocks, uint64_t base, void *d_digests,
+                                uint64_t *d_ref, uint32_t *d_new_idx, void *d_dst, size_t dst_stride,
+                                uint32_t *d_sizes, size_t *n_new, void *stream);
+
 /* plain device memory on the calling thread's device, for C callers of cw_dev_* (the host programs link no HIP runtime) */
 void *cw_dev_alloc(size_t bytes);                                   /* NULL on failure */
 void  cw_dev_free(void *d_p);
