@@ -464,11 +464,112 @@ lz4_scan_stream_kernel(const uint8_t *__restrict__ src, uint32_t n, size_t src_s
 // Step i: store chunk i-1 (speculatively, as before), load chunk i+2 into the registers that frees, finish the
 // previous block if chunk i starts a new one, stage chunk i in the LDS ring, probe the positions below it.
 // ---------------------------------------------------------------------------------------------------
+// The span scan's probe schedule.  Which probes fall below a chunk boundary depends only on n, so lane c of kend holds the number of
+// probes at positions < c * 4 KiB (computed once per wavefront by a binary search) and a chunk runs exactly kend[c] - knext probes in
+// batches of 64, the last one partial.  A batch's verdicts are wave masks (the v_cmp results themselves), so that the judge costs a few
+// scalar ANDs/ORs instead of per-lane booleans under exec-mask branches.
+__device__ __forceinline__ uint32_t probe_pos(uint32_t k) // 1 + probe_delta(k): with q = (k + 62) >> 6 it is q * (k + 31 - 32 q) + 2
+{
+    const uint32_t q = (k + 62) >> 6;
+    return q * (k + 31 - 32 * q) + 1 + (uint32_t)(k != 0); // k = 0 (q = 0) is position 1
+}
+
+__device__ __forceinline__ uint32_t probe_kend(uint32_t end, uint32_t nprobes) // probes at positions < end
+{
+    uint32_t lo = 0, hi = nprobes;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (probe_pos(mid) < end) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// NG batches of 64 probes from k = kb (PART: only the first rem of them are real).  All ring reads, then all table exchanges, then all
+// verdicts, then the rare settling of fingerprint hits.  Returns whether the block has a match.  The semantics are those of scan_issue /
+// scan_judge / scan_settle, with the epoch test written on the whole word: entries never carry a later epoch than the current one, so
+// "same epoch" is old >= tag and "same epoch and cand >= pos" is old >= tag | pos << 12.  Every verdict is the ballot of ONE compare,
+// i.e. the v_cmp's own mask, combined with scalar ANDs/ORs.
+template <int NG, bool PART>
+__device__ __forceinline__ bool probe_batches(uint32_t kb, uint32_t rem, uint32_t *tab, const uint32_t *ring32, uint32_t tag, uint32_t v0,
+                                              const uint8_t *g, uint32_t lane)
+{
+    uint32_t pos[NG], v[NG], tp[NG], fp[NG], old[NG];
+    unsigned long long actm[NG];
+#pragma unroll
+    for (int j = 0; j < NG; j++) {
+        pos[j] = probe_pos(kb + 64 * j + lane);
+        // the probe's 4 bytes: two aligned ring dwords (the second may wrap) + byte align (v_alignbyte_b32 uses the low 2 bits)
+        const uint8_t *r8 = reinterpret_cast<const uint8_t *>(ring32);
+        const uint32_t lo = *reinterpret_cast<const uint32_t *>(r8 + (pos[j] & (kRing - 4)));
+        const uint32_t hi = *reinterpret_cast<const uint32_t *>(r8 + ((pos[j] + 4) & (kRing - 4)));
+        v[j] = __builtin_amdgcn_alignbyte(hi, lo, pos[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < NG; j++) {
+        const bool act = !PART || 64 * j + lane < rem;
+        actm[j] = PART ? __ballot(act) : ~0ull;
+        const uint32_t h = v[j] * 2654435761u;
+        fp[j] = (h >> 7) & 0xFFFu;
+        tp[j] = tag | (pos[j] << 12);
+        old[j] = atomicMax(&tab[act ? h >> 19 : 0u], act ? tp[j] | fp[j] : 0u); // an inactive lane: max(tab[0], 0) changes nothing
+    }
+    unsigned long long hit = 0, maybe = 0;
+#pragma unroll
+    for (int j = 0; j < NG; j++) {
+        // an empty slot (earlier epoch) means candidate 0; a candidate >= pos means the atomics ran out of lane order
+        const unsigned long long empty = __ballot(old[j] < tag);
+        hit |= (__ballot(old[j] >= tp[j]) | (empty & __ballot(v[j] == v0))) & actm[j];
+        const unsigned long long fm = __ballot(((old[j] ^ fp[j]) & 0xFFFu) == 0) & ~empty & actm[j];
+        hit |= fm & maybe; // a second fingerprint hit before settling: let the parser decide
+        maybe |= fm;
+    }
+    if (maybe) { // rare: settle the fingerprint hit on the candidate's actual bytes
+        uint32_t mcand = 0, mv = 0;
+#pragma unroll
+        for (int j = 0; j < NG; j++) {
+            const bool f = (((PART ? actm[j] : ~0ull) >> lane) & 1u) && old[j] >= tag && ((old[j] ^ fp[j]) & 0xFFFu) == 0;
+            mcand = f ? (old[j] >> 12) & 0xFFFFu : mcand;
+            mv = f ? v[j] : mv;
+        }
+        const bool mine = (maybe >> lane) & 1u;
+        hit |= __ballot(mine && ld32g(g + mcand) == mv);
+    }
+    return hit != 0;
+}
+
+// one aligned 16-byte nontemporal store (global_store_dwordx4 ... nt)
+__device__ __forceinline__ void store16_nt(uint8_t *p, uint32_t x, uint32_t y, uint32_t z, uint32_t w)
+{
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    u32x4 v = {x, y, z, w};
+    __builtin_nontemporal_store(v, reinterpret_cast<u32x4 *>(p));
+}
+
+// the probes [w.knext, ke) of the block
+__device__ __forceinline__ void probe_range(Walk &w, uint32_t ke, uint32_t *tab, const uint32_t *ring32, uint32_t tag, const uint8_t *g,
+                                            uint32_t lane)
+{
+    uint32_t kb = w.knext;
+    for (; kb + 128 <= ke; kb += 128)
+        if (probe_batches<2, false>(kb, 0, tab, ring32, tag, w.v0, g, lane)) { w.marked = true; return; }
+    const uint32_t rem = ke - kb;
+    if (rem > 64) w.marked = probe_batches<2, true>(kb, rem, tab, ring32, tag, w.v0, g, lane);
+    else if (rem) w.marked = probe_batches<1, true>(kb, rem, tab, ring32, tag, w.v0, g, lane);
+    w.knext = ke;
+}
+
 #ifdef CW_CLOCK_STAMP
 __device__ unsigned long long g_clock_scan[4 * kClockSlots];
 hipError_t lz4_clock_read(unsigned long long *out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_clock_scan), sizeof g_clock_scan); }
 #endif
 
+// ALIGNED (dst and dst_stride multiples of 16): the literal run goes out as aligned 16-byte lines.  For every power-of-two n from 4 KiB
+// to 64 KiB the header is hdr = 2 + (n - 15) / 255 bytes with hdr - 2 a multiple of 16, so byte x of the block lands 2 bytes into line
+// (x + 2) / 16 counted from out + hdr - 2: a lane's line is the last 2 bytes of the piece in front of its own (one ring dword, the
+// previous chunk's last for lane 0 of piece 0, the header's last two bytes at a block's first chunk) and the first 14 of its own; the
+// block's last 2 bytes are one 2-byte store.  The header's first hdr - 2 bytes (0xF0, then 0xFF) go out as aligned lines too.
+template <bool ALIGNED>
 __global__ void __launch_bounds__(64)
 lz4_scan_span_kernel(const uint8_t *__restrict__ src, uint32_t n, size_t src_stride, uint32_t nspans, uint8_t *__restrict__ dst,
                      size_t dst_stride, uint32_t *__restrict__ sizes, uint32_t nprobes, uint32_t *__restrict__ queue,
@@ -484,6 +585,9 @@ lz4_scan_span_kernel(const uint8_t *__restrict__ src, uint32_t n, size_t src_str
     const uint32_t cmask = (1u << lg) - 1, run = 16u >> lg; // chunks per block - 1, blocks per span
     const uint32_t hdr = 1 + (n - 15) / 255 + 1;            // token + length bytes of the single literal run (n >= 4096)
     const uint32_t lane16 = lane * 16;
+    const uint32_t kend = probe_kend(lane * kChunk, nprobes); // lane c: probes below chunk c of a block (lane >= 16: all)
+    // the header's last two bytes (0xFF, (n - 15) % 255) as the high half of the dword in front of a block's first line
+    const uint32_t hdrw = (0xFFu << 16) | (((n - 15) % 255) << 24);
 
     for (;;) {
         __syncthreads();
@@ -494,7 +598,7 @@ lz4_scan_span_kernel(const uint8_t *__restrict__ src, uint32_t n, size_t src_str
         __syncthreads(); // the mailbox word is ring memory
         const size_t first = (size_t)span * run;
         const uint8_t *gs = src + first * src_stride;
-        uint8_t *os = dst + first * dst_stride + hdr;
+        uint8_t *os = dst + first * dst_stride + (ALIGNED ? hdr - 2 : hdr);
 
         Walk w;
         size_t blk = first;
@@ -506,24 +610,45 @@ lz4_scan_span_kernel(const uint8_t *__restrict__ src, uint32_t n, size_t src_str
             const uint8_t *p_ = gs + (size_t)(i_ >> lg) * src_stride + ((i_ & cmask) << 12) + lane16;        \
             _Pragma("unroll") for (uint32_t j = 0; j < kPieces; j++) R.p[j] = *reinterpret_cast<const uint4 *>(p_ + j * 1024); \
         } while (0)
+        // chunk I of the span, still in the ring (and in R): its literal bytes to the slot
 #define CW_ST(R, I)                                                                                          \
         do {                                                                                                 \
-            const uint32_t i_ = (I);                                                                         \
-            uint8_t *p_ = os + (size_t)(i_ >> lg) * dst_stride + ((i_ & cmask) << 12) + lane16;              \
-            _Pragma("unroll") for (uint32_t j = 0; j < kPieces; j++) {                                       \
-                uint32_t *q = reinterpret_cast<uint32_t *>(p_ + j * 1024); /* 2-byte-misaligned: 4 dword stores, merged by hipcc */ \
-                __builtin_nontemporal_store(R.p[j].x, q);     __builtin_nontemporal_store(R.p[j].y, q + 1);  \
-                __builtin_nontemporal_store(R.p[j].z, q + 2); __builtin_nontemporal_store(R.p[j].w, q + 3);  \
+            const uint32_t i_ = (I), c_ = i_ & cmask;                                                        \
+            uint8_t *p_ = os + (size_t)(i_ >> lg) * dst_stride + (c_ << 12) + lane16;                        \
+            if constexpr (ALIGNED) {                                                                         \
+                const uint32_t b_ = ((c_ & 1u) << 12) + lane16; /* the chunk's ring half; wraps for lane 0 of piece 0 */ \
+                uint32_t pw_[kPieces];                                                                       \
+                _Pragma("unroll") for (uint32_t j = 0; j < kPieces; j++) pw_[j] = ring32[((b_ + j * 1024 - 4) & (kRing - 4)) / 4]; \
+                if (c_ == 0 && lane == 0) pw_[0] = hdrw;                                                     \
+                _Pragma("unroll") for (uint32_t j = 0; j < kPieces; j++) {                                   \
+                    store16_nt(p_ + j * 1024, __builtin_amdgcn_alignbyte(R.p[j].x, pw_[j], 2),               \
+                               __builtin_amdgcn_alignbyte(R.p[j].y, R.p[j].x, 2),                            \
+                               __builtin_amdgcn_alignbyte(R.p[j].z, R.p[j].y, 2),                            \
+                               __builtin_amdgcn_alignbyte(R.p[j].w, R.p[j].z, 2));                           \
+                }                                                                                            \
+                if (c_ == cmask && lane == 63) /* the block's last 2 bytes */                                \
+                    *reinterpret_cast<uint16_t *>(p_ + (kPieces - 1) * 1024 + 16) = (uint16_t)(R.p[kPieces - 1].w >> 16); \
+            } else {                                                                                         \
+                _Pragma("unroll") for (uint32_t j = 0; j < kPieces; j++) {                                   \
+                    uint32_t *q = reinterpret_cast<uint32_t *>(p_ + j * 1024); /* misaligned: 4 dword stores, merged by hipcc */ \
+                    __builtin_nontemporal_store(R.p[j].x, q);     __builtin_nontemporal_store(R.p[j].y, q + 1); \
+                    __builtin_nontemporal_store(R.p[j].z, q + 2); __builtin_nontemporal_store(R.p[j].w, q + 3); \
+                }                                                                                            \
             }                                                                                                \
         } while (0)
 #define CW_FINISH()                                                                                          \
         do { /* the block's last probes (nothing straddles its end), then its verdict */                     \
-            if (!w.marked) probe_upto(w, n, tab, ring32, tag, epoch, nprobes, src + blk * src_stride, lane); \
+            if (!w.marked) probe_range(w, nprobes, tab, ring32, tag, src + blk * src_stride, lane);          \
             if (w.marked) marks |= 1u << (uint32_t)(blk - first); /* queued at the end of the span */        \
             else {                                                                                           \
                 uint8_t *out = dst + blk * dst_stride;                                                       \
-                if (lane == 0) out[0] = 15u << 4;                                                            \
-                put_len(out + 1, n - 15, lane);                                                              \
+                if constexpr (ALIGNED) {                                                                     \
+                    if (lane < (hdr - 2) / 16)                                                               \
+                        store16_nt(out + lane16, lane ? ~0u : 0xFFFFFFF0u, ~0u, ~0u, ~0u);                   \
+                } else {                                                                                     \
+                    if (lane == 0) out[0] = 15u << 4;                                                        \
+                    put_len(out + 1, n - 15, lane);                                                          \
+                }                                                                                            \
                 if (lane == 0) sizes[blk] = hdr + n;                                                         \
             }                                                                                                \
         } while (0)
@@ -548,7 +673,7 @@ lz4_scan_span_kernel(const uint8_t *__restrict__ src, uint32_t n, size_t src_str
                     atomicMax(&tab[h0 >> 19], tag | ((h0 >> 7) & 0xFFFu)); /* position 0 */                  \
                 }                                                                                            \
             } else if (!w.marked) {                                                                          \
-                probe_upto(w, (C) * kChunk, tab, ring32, tag, epoch, nprobes, src + blk * src_stride, lane); \
+                probe_range(w, __builtin_amdgcn_readlane(kend, (C)), tab, ring32, tag, src + blk * src_stride, lane); \
             }                                                                                                \
         } while (0)
 #define CW_STEP(PREV, CUR, I)                                                                                \
@@ -2153,9 +2278,17 @@ hipError_t lz4_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
         const size_t nspans = pow2 ? nblocks / run : 0, done = nspans * run;
         if (nspans) {
             const size_t g = nspans < 256 * wpc ? nspans : 256 * wpc; // 40 KiB of LDS each -> at most 4 per CU
-            hipLaunchKernelGGL(lz4_scan_span_kernel, dim3((unsigned)g), dim3(64), 0, stream, src, n, src_stride, (uint32_t)nspans, dst,
-                               dst_stride, sizes, scan_probes(n), queue, counters, lg);
-            note("cw::lz4_scan_span_kernel");
+            // 16-byte aligned slots: the literal runs go out as aligned lines (any other slot alignment: misaligned 16-byte stores)
+            const bool aligned = ((reinterpret_cast<uintptr_t>(dst) | dst_stride) & 15) == 0;
+            if (aligned) {
+                hipLaunchKernelGGL(lz4_scan_span_kernel<true>, dim3((unsigned)g), dim3(64), 0, stream, src, n, src_stride, (uint32_t)nspans,
+                                   dst, dst_stride, sizes, scan_probes(n), queue, counters, lg);
+                note("cw::lz4_scan_span_kernel<true>");
+            } else {
+                hipLaunchKernelGGL(lz4_scan_span_kernel<false>, dim3((unsigned)g), dim3(64), 0, stream, src, n, src_stride, (uint32_t)nspans,
+                                   dst, dst_stride, sizes, scan_probes(n), queue, counters, lg);
+                note("cw::lz4_scan_span_kernel<false>");
+            }
         }
         if (done < nblocks) {
             const size_t rest = nblocks - done;
