@@ -20,7 +20,6 @@
 #include <cstring>
 #include <deque>
 #include <memory>
-#include <map>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -248,8 +247,8 @@ int dev_hash(int alg, const uint8_t *d_src, size_t bb, size_t stride, size_t n, 
 {
     hipError_t e;
     ProfScope prof(PROF_HASH, s);
-    const char *slice_env = cw::tune("CW_SKEIN_SLICED"); // CW_SKEIN_SLICED=0: always the one-launch hash kernel (profiling knob)
-    if (sliced && !(slice_env && slice_env[0] == '0') && (alg == CW_HASH_SKEIN512 || alg == CW_HASH_SKEIN256_128)) {
+    // CW_SKEIN_SLICED=0: always the one-launch hash kernel (profiling knob)
+    if (sliced && cw::knobs().skein_sliced && (alg == CW_HASH_SKEIN512 || alg == CW_HASH_SKEIN256_128)) {
         const int nw = alg == CW_HASH_SKEIN512 ? 8 : 4;
         if (cw::skein_sliced_applies(nw, d_src, bb, stride, n, d_dig)) {
             e = cw::skein_sliced_launch(nw, d_src, bb, stride, n, nw == 8 ? g_iv512_512 : g_iv256_128, d_dig, nw == 8 ? 64 : 16, s);
@@ -294,25 +293,82 @@ thread_local char t_kernels[2][320] = {"", ""};
 
 } // namespace
 
-// Tuning and test knobs.  A knob's value is what cw_tune_set gave it, else the environment variable of the same name (read once),
-// else unset.  Every launch function asks per call, so a test can run two settings in one process.
+// Tuning and test knobs (cw::Knobs).  This table is the only code that knows their names and how their values read; an unset knob
+// keeps the field's initial value.  A knob's value is what cw_tune_set gave it, else the environment variable of the same name (read
+// once, for the whole table, on first use).
 namespace {
+using cw::Knobs;
+void positive(int &f, const char *v) { if (atoi(v) > 0) f = atoi(v); }
+void positive(long &f, const char *v) { if (atol(v) > 0) f = atol(v); }
+
+struct KnobDef { const char *name; void (*decode)(Knobs &k, const char *v); };
+const KnobDef kKnobTable[] = {
+    {"CW_SKEIN_SLICED", [](Knobs &k, const char *v) { k.skein_sliced = v[0] != '0'; }},
+    {"CW_LZ4_LANES_FP", [](Knobs &k, const char *v) { k.lz4_lanes_fp = v[0] != '0'; }},
+    {"CW_LZF_STHREAD", [](Knobs &k, const char *v) { k.lzf_sthread = v[0] != '0'; }},
+    {"CW_SERIAL", [](Knobs &k, const char *v) { k.serial = v[0] == '1'; }},
+    {"CW_DEBUG_HOST", [](Knobs &k, const char *v) { k.debug_host = v[0] == '1'; }},
+    {"CW_PREPARE_COLD", [](Knobs &k, const char *v) { k.prepare_cold = v[0] == '1'; }},
+    {"CW_FUSED_GATE", [](Knobs &k, const char *v) { k.fused_gate = v[0] == '1'; }},
+    {"CW_HOST_SHARED_STREAMS", [](Knobs &k, const char *v) { k.host_shared_streams = v[0] == '1'; }},
+    {"CW_LANES_CONCURRENT", [](Knobs &k, const char *v) { k.lanes_concurrent = v[0] != '0'; }},
+    {"CW_SIDE_PRIO", [](Knobs &k, const char *v) { k.side_prio = v[0] == '0' ? cw::SidePrio::none : v[0] == '2' ? cw::SidePrio::both : cw::SidePrio::lanes; }},
+    {"CW_LZ4_MODE", [](Knobs &k, const char *v) {
+         k.lz4_mode = !strcmp(v, "scan") ? cw::Lz4Mode::scan : !strcmp(v, "generic") ? cw::Lz4Mode::generic
+                    : !strcmp(v, "stream") ? cw::Lz4Mode::stream : !strcmp(v, "cut") ? cw::Lz4Mode::cut : cw::Lz4Mode::normal; }},
+    {"CW_LZF_MODE", [](Knobs &k, const char *v) { k.lzf_mode = !strcmp(v, "cut") ? cw::LzfMode::cut : !strcmp(v, "table") ? cw::LzfMode::table : cw::LzfMode::normal; }},
+    {"CW_SKEIN_MODE", [](Knobs &k, const char *v) { k.skein_mode = !strcmp(v, "steps") ? cw::SkeinMode::steps : cw::SkeinMode::lines; }},
+    {"CW_LZ4_PARSE", [](Knobs &k, const char *v) { k.lz4_parse_fp = !strcmp(v, "fp"); }},
+    {"CW_DEBUG_LZF", [](Knobs &k, const char *) { k.debug_lzf = true; }},
+    {"CW_SCAN_WPC", [](Knobs &k, const char *v) { positive(k.scan_wpc, v); }},
+    {"CW_PARSE_WPC", [](Knobs &k, const char *v) { positive(k.parse_wpc, v); }},
+    {"CW_LANES_WPC", [](Knobs &k, const char *v) { positive(k.lanes_wpc, v); }},
+    {"CW_LANES_RESERVE", [](Knobs &k, const char *v) { positive(k.lanes_reserve, v); }},
+    {"CW_VTAB_WPC", [](Knobs &k, const char *v) { positive(k.vtab_wpc, v); }},
+    {"CW_LZF_ST_WPC", [](Knobs &k, const char *v) { positive(k.lzf_st_wpc, v); }},
+    {"CW_LZF_ROUND", [](Knobs &k, const char *v) { positive(k.lzf_round, v); }},
+    {"CW_LZF_LDS_MAX", [](Knobs &k, const char *v) { positive(k.lzf_lds_max, v); }},
+    {"CW_SKEIN_NSLICES", [](Knobs &k, const char *v) { positive(k.skein_nslices, v); }},
+    {"CW_HOST_CHUNK_MB", [](Knobs &k, const char *v) { positive(k.host_chunk_mb, v); }},
+    {"CW_HOST_BIG_CHUNK_MB", [](Knobs &k, const char *v) { positive(k.host_big_chunk_mb, v); }},
+    {"CW_LZ_FORCE_REDO", [](Knobs &k, const char *v) { k.force_redo = atoi(v) > 0; }},
+    {"CW_LZF_SHARE_GIVE_UP", [](Knobs &k, const char *v) { k.lzf_share_give_up = atoi(v) > 0; }},
+    {"CW_LZ4_LANES", [](Knobs &k, const char *v) { k.lz4_lanes = atoi(v); }},
+    {"CW_LZF_LANES", [](Knobs &k, const char *v) { k.lzf_lanes = atoi(v); }},
+    {"CW_DECODE_LANES", [](Knobs &k, const char *v) { k.decode_lanes = atoi(v); }},
+    {"CW_LANES_LEAVE", [](Knobs &k, const char *v) { k.lanes_leave = atoi(v); }},
+    {"CW_VTAB_MIN", [](Knobs &k, const char *v) { k.vtab_min = atoi(v); }},
+    {"CW_VTAB_MAX", [](Knobs &k, const char *v) { k.vtab_max = atoi(v); }},
+    {"CW_VTAB_RESERVE", [](Knobs &k, const char *v) { k.vtab_reserve = atoi(v); }},
+    {"CW_LZ4_VTAB", [](Knobs &k, const char *v) { k.lz4_vtab = atoi(v); }},
+    {"CW_LZ4_LANES_RING", [](Knobs &k, const char *v) { k.lz4_lanes_ring = atoi(v); }},
+    {"CW_LZ4_HEADW", [](Knobs &k, const char *v) { k.lz4_headw = atoi(v); }},
+    {"CW_LZ4_LTAB", [](Knobs &k, const char *v) { k.lz4_ltab = atoi(v); }},
+    {"CW_VTAB_GEN", [](Knobs &k, const char *v) { k.vtab_gen = atoi(v); }},
+    {"CW_LZ4_STAGE_MAX", [](Knobs &k, const char *v) { if (atoi(v) >= 0) k.lz4_stage_max = atoi(v); }},
+};
+constexpr size_t kKnobs = sizeof kKnobTable / sizeof kKnobTable[0];
+
+struct KnobValue { bool set = false; std::string value; };
 std::mutex tune_lock;
-std::map<std::string, std::string> tune_over;                 // cw_tune_set
-std::map<std::string, std::pair<bool, std::string>> tune_env; // getenv, cached (present?, value)
+KnobValue tune_over[kKnobs], tune_env[kKnobs]; // cw_tune_set; the environment
+bool tune_env_read = false;
 } // namespace
 
-const char *cw::tune(const char *key)
+cw::Knobs cw::knobs()
 {
+    Knobs k;
     std::lock_guard<std::mutex> g(tune_lock);
-    auto o = tune_over.find(key);
-    if (o != tune_over.end()) return o->second.c_str();
-    auto e = tune_env.find(key);
-    if (e == tune_env.end()) {
-        const char *v = getenv(key);
-        e = tune_env.emplace(key, std::make_pair(v != nullptr, std::string(v ? v : ""))).first;
+    if (!tune_env_read) {
+        for (size_t i = 0; i < kKnobs; i++)
+            if (const char *v = getenv(kKnobTable[i].name)) tune_env[i] = {true, v};
+        tune_env_read = true;
     }
-    return e->second.first ? e->second.second.c_str() : nullptr;
+    for (size_t i = 0; i < kKnobs; i++) {
+        const KnobValue &v = tune_over[i].set ? tune_over[i] : tune_env[i];
+        if (v.set) kKnobTable[i].decode(k, v.value.c_str());
+    }
+    return k;
 }
 
 void cw::release_stream_workspaces(hipStream_t stream)
@@ -336,16 +392,18 @@ extern "C" {
 // ---- knobs (CW_TESTING section of the header) -------------------------------------------------------
 int cw_tune_set(const char *key, const char *value)
 {
-    if (!key || strncmp(key, "CW_", 3) != 0) return fail(CW_ERR_BAD_ARG, "knob names start with CW_");
-    std::lock_guard<std::mutex> g(tune_lock);
-    if (value) tune_over[key] = value;
-    else tune_over.erase(key);
-    return CW_OK;
+    for (size_t i = 0; key && i < kKnobs; i++) {
+        if (strcmp(kKnobTable[i].name, key) != 0) continue;
+        std::lock_guard<std::mutex> g(tune_lock);
+        tune_over[i] = value ? KnobValue{true, value} : KnobValue{};
+        return CW_OK;
+    }
+    return fail(CW_ERR_BAD_ARG, "unknown knob %s", key ? key : "(null)");
 }
 void cw_tune_reset(void)
 {
     std::lock_guard<std::mutex> g(tune_lock);
-    tune_over.clear();
+    for (KnobValue &o : tune_over) o = KnobValue{};
 }
 
 // ---- lifecycle ------------------------------------------------------------------------------------
@@ -462,8 +520,8 @@ static int dev_fused(hipStream_t side, hipEvent_t fork, hipEvent_t join, int has
                      uint8_t *d_digests, uint8_t *d_dst, size_t dst_stride, uint32_t *d_sizes, hipStream_t main_s)
 {
     int rc;
-    const char *serial = cw::tune("CW_SERIAL"); // CW_SERIAL=1: both kernels on the caller's stream (profiling knob)
-    if (serial && serial[0] == '1') {
+    const cw::Knobs kn = cw::knobs();
+    if (kn.serial) { // CW_SERIAL=1: both kernels on the caller's stream (profiling knob)
         rc = dev_compress(comp_alg, d_src, block_bytes, src_stride, nblocks, d_dst, dst_stride, d_sizes, main_s);
         return rc == CW_OK ? dev_hash(hash_alg, d_src, block_bytes, src_stride, nblocks, d_digests, main_s, false, true) : rc;
     }
@@ -496,8 +554,8 @@ static int dev_fused(hipStream_t side, hipEvent_t fork, hipEvent_t join, int has
         if (hint->blocks_of_copy) hint->queued_share = (float)*hint->h_queued / (float)hint->blocks_of_copy;
     }
     (void)hipGetLastError(); // (hipErrorNotReady of the query is not an error)
-    const char *gate_env = cw::tune("CW_FUSED_GATE"); // 0 = never, 1 = always (profiling knob)
-    const bool gated = hint && (gate_env ? gate_env[0] == '1' : block_bytes <= 4096 && nblocks >= 16384 && hint->queued_share >= 0.25f);
+    // CW_FUSED_GATE: 0 = never, 1 = always (profiling knob)
+    const bool gated = hint && (kn.fused_gate ? *kn.fused_gate : block_bytes <= 4096 && nblocks >= 16384 && hint->queued_share >= 0.25f);
     rc = dev_compress(comp_alg, d_src, block_bytes, src_stride, nblocks, d_dst, dst_stride, d_sizes, main_s, gated ? &hook : nullptr);
     if (gate.called && gate.rc != CW_OK) return gate.rc;
     if (rc == CW_OK && !gate.called) rc = dev_hash(hash_alg, d_src, block_bytes, src_stride, nblocks, d_digests, side, false, true);
@@ -724,17 +782,16 @@ int slot_reserve(HostJob &j, Slot &s, size_t n, bool stage_src, bool stage_pack,
 // cw_hash_and_compress_packed, own streams -> shared: corpus, Skein-512 + LZ4, 64 KiB 24.1 -> 26.0 GB/s; Skein-256 + LZ4, 4 KiB 22.6 -> 33.4;
 // SHA-256 + LZ4, 4 KiB 23.0 -> 33.5; noise 41.4 -> 43.6; SHA-256 + LZF, 4 KiB 25.5 -> 25.6, 64 KiB 17.6 -> 15.9 (its rounds of link and parse
 // kernels do overlap across chunks).
-const Slot *shared_lender(ThreadCtx &c, const HostJob &j, const Slot &s)
+const Slot *shared_lender(const cw::Knobs &kn, ThreadCtx &c, const HostJob &j, const Slot &s)
 {
-    const char *sh_env = cw::tune("CW_HOST_SHARED_STREAMS");
-    const bool share = sh_env ? sh_env[0] == '1' : j.comp_alg != CW_COMP_LZF;
+    const bool share = kn.host_shared_streams ? *kn.host_shared_streams : j.comp_alg != CW_COMP_LZF;
     if (!share || &s == &c.slot[0]) return nullptr;
     return c.slot[0].open() == CW_OK ? &c.slot[0] : nullptr;
 }
 
-int pipe_issue(ThreadCtx &c, HostJob &j, Slot &s, size_t first, size_t n)
+int pipe_issue(const cw::Knobs &kn, ThreadCtx &c, HostJob &j, Slot &s, size_t first, size_t n)
 {
-    int rc = slot_reserve(j, s, n, !j.src_pinned, !(j.packed && j.packed_pinned), shared_lender(c, j, s));
+    int rc = slot_reserve(j, s, n, !j.src_pinned, !(j.packed && j.packed_pinned), shared_lender(kn, c, j, s));
     if (rc != CW_OK) return rc;
     s.first = first; s.n = n; s.total = 0;
     const size_t bytes = n * j.bb;
@@ -831,13 +888,12 @@ void pipe_drain(ThreadCtx &c)
 // behind its own host->device copy: 64 / 128 / 256 / 512 MiB measured 21.7 / 27.8 / 28.0 / 45.7 GB/s on random 64 KiB blocks
 // (the last is the link's duplex rate).  Three slots x (input + slots + packed stream) = 4.6 GiB of device memory per calling
 // thread at 512 MiB.  CW_HOST_CHUNK_MB overrides.
-size_t pipeline_chunk(size_t bb, size_t nblocks)
+size_t pipeline_chunk(const cw::Knobs &kn, size_t bb, size_t nblocks)
 {
-    const char *ck_env = cw::tune("CW_HOST_CHUNK_MB");
     // 512 MiB: the chunk's kernels cost 8-10 ms whatever its size and do not overlap across chunks, and a chunk of 4 KiB blocks has
     // to be large enough for the lane parsers to run beside the LDS-resident ones (8 GiB of 4 KiB corpus blocks, Skein-256 + LZ4 /
     // SHA-256 + LZF: chunks of 64 MiB 29.5 / 18.8 GB/s, 512 MiB 38.6 / 27.2, 1 GiB 40.0 / 20.8; random data 47 -> 45-47 GB/s)
-    size_t chunk_bytes = ck_env && atol(ck_env) > 0 ? (size_t)atol(ck_env) << 20 : (size_t)512 << 20;
+    size_t chunk_bytes = kn.host_chunk_mb ? (size_t)kn.host_chunk_mb << 20 : (size_t)512 << 20;
     size_t chunk = chunk_bytes / (bb ? bb : 1);
     if (chunk == 0) chunk = 1;
     if (chunk > nblocks) chunk = nblocks;
@@ -870,13 +926,11 @@ int slot_reserve(HostJob &j, Slot &s, size_t n, bool stage_src, bool stage_pack,
 constexpr size_t kBigChunkBytes = (size_t)2 << 30;
 
 // blocks of a grown chunk, or 0 when chunks of this job never grow
-size_t grown_chunk(const HostJob &j, size_t chunk, bool pinned_io)
+size_t grown_chunk(const cw::Knobs &kn, const HostJob &j, size_t chunk, bool pinned_io)
 {
-    const char *ck_env = cw::tune("CW_HOST_CHUNK_MB");
-    const char *bk_env = cw::tune("CW_HOST_BIG_CHUNK_MB"); // test knob: the grown chunk's size (and growth although CW_HOST_CHUNK_MB is set)
-    const bool bk_set = bk_env && atol(bk_env) > 0;
-    const size_t big = (bk_set ? (size_t)atol(bk_env) << 20 : kBigChunkBytes) / (j.bb ? j.bb : 1);
-    const bool may = (bk_set || !(ck_env && atol(ck_env) > 0)) && j.do_comp && j.bb > 4096 && pinned_io && big > chunk;
+    // CW_HOST_BIG_CHUNK_MB (test knob): the grown chunk's size, and growth although CW_HOST_CHUNK_MB is set
+    const size_t big = (kn.host_big_chunk_mb ? (size_t)kn.host_big_chunk_mb << 20 : kBigChunkBytes) / (j.bb ? j.bb : 1);
+    const bool may = (kn.host_big_chunk_mb || !kn.host_chunk_mb) && j.do_comp && j.bb > 4096 && pinned_io && big > chunk;
     return may ? big : 0;
 }
 
@@ -901,11 +955,12 @@ int host_pipeline(HostJob &j)
     if (rc != CW_OK) return rc;
     ThreadCtx &c = *cp;
     if (j.nblocks == 0 || (!j.do_hash && !j.do_comp)) { if (j.offsets) j.offsets[0] = 0; return CW_OK; }
-    const size_t chunk = pipeline_chunk(j.bb, j.nblocks);
+    const cw::Knobs kn = cw::knobs();
+    const size_t chunk = pipeline_chunk(kn, j.bb, j.nblocks);
     j.src_pinned = is_pinned(j.src);
     j.packed_pinned = j.packed && is_pinned(j.packed);
     j.packed_off = 0;
-    const size_t big = grown_chunk(j, chunk, j.src_pinned && j.packed_pinned);
+    const size_t big = grown_chunk(kn, j, chunk, j.src_pinned && j.packed_pinned);
     const bool may_grow = big != 0 && j.nblocks > 2 * chunk && room_to_grow(c, j, big);
     size_t next = 0, issued = 0, seen_in = 0, seen_out = 0; // blocks handed out; chunks issued; bytes in / out of the chunks reaped so far
     for (size_t k = 0; rc == CW_OK && (next < j.nblocks || k < issued + 2); k++) {
@@ -914,9 +969,8 @@ int host_pipeline(HostJob &j)
             size_t n = left < chunk ? left : chunk;
             if (may_grow && seen_in && seen_in / 10 * 9 >= seen_out && left > chunk) // compressible so far (>= 10 % saved)
                 n = left >= 2 * big ? big : left > big ? (left + 1) / 2 : left;
-            const char *dbg_env = cw::tune("CW_DEBUG_HOST"); // prints the chunks of a call (tests)
-            if (dbg_env && dbg_env[0] == '1') fprintf(stderr, "cw host pipeline: chunk %zu = %zu blocks of %zu B\n", issued, n, j.bb);
-            rc = pipe_issue(c, j, c.slot[k % kSlots], next, n);
+            if (kn.debug_host) fprintf(stderr, "cw host pipeline: chunk %zu = %zu blocks of %zu B\n", issued, n, j.bb); // (tests)
+            rc = pipe_issue(kn, c, j, c.slot[k % kSlots], next, n);
             next += n;
             issued++;
         }
@@ -994,19 +1048,19 @@ int cw_prepare(int hash_alg, int comp_alg, size_t block_bytes, size_t nblocks, i
     int dummy = 0;
     if ((rc = host_job_init(j, hash_alg, comp_alg, &dummy, block_bytes, nblocks, &dummy, true)) != CW_OK) return rc;
     if (!j.do_hash && !j.do_comp) return CW_OK; // (CW_HASH_NONE, CW_COMP_NONE): nothing a batch would allocate
-    size_t chunk = pipeline_chunk(block_bytes, nblocks);
+    const cw::Knobs kn = cw::knobs();
+    size_t chunk = pipeline_chunk(kn, block_bytes, nblocks);
     // a batch whose chunks may grow (host_pipeline): buffers, workspaces and lane tables for the grown chunk, so that the growth costs
     // no allocation inside a timed window (18.5 GiB of device memory per calling thread)
-    const size_t big = grown_chunk(j, chunk, pinned_io != 0);
+    const size_t big = grown_chunk(kn, j, chunk, pinned_io != 0);
     if (big && nblocks > 2 * chunk && room_to_grow(*c, j, big)) chunk = nblocks - 2 * chunk < big ? nblocks - 2 * chunk : big;
     for (Slot &s : c->slot)
-        if ((rc = slot_reserve(j, s, chunk, !pinned_io, !pinned_io, shared_lender(*c, j, s))) != CW_OK) return rc;
+        if ((rc = slot_reserve(j, s, chunk, !pinned_io, !pinned_io, shared_lender(kn, *c, j, s))) != CW_OK) return rc;
     // One chunk's kernels on every slot (over whatever its device buffers hold): the codecs' per-stream workspaces -- queues, link
     // arrays, the lane parsers' tables -- are allocated here instead of inside the first timed batch, and the device leaves its
     // idle clocks.  Then a few copies each way to wake the link (the first pass after idle ran at 25-29 GB/s against 45.7).
     // CW_PREPARE_COLD=1 skips both.
-    const char *cold = cw::tune("CW_PREPARE_COLD");
-    if (cold && cold[0] == '1') return CW_OK;
+    if (kn.prepare_cold) return CW_OK;
     for (Slot &s : c->slot) { // the same predicates as pipe_issue: a hash-only job has no slots, sizes or packed stream to touch
         if (j.do_comp && j.do_hash)
             rc = dev_fused(s.side, s.fork, s.join, hash_alg, comp_alg, (const uint8_t *)s.src.p, block_bytes, block_bytes, chunk, (uint8_t *)s.dig.p,

@@ -2223,9 +2223,10 @@ hipError_t lz4_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
     if (nblocks == 0) return hipSuccess;
     if (block_bytes == 0 || block_bytes > 65536 || nblocks > 0xFFFFFFFFull) return hipErrorInvalidValue;
     const uint32_t n = (uint32_t)block_bytes;
-    const char *sm_env = tune("CW_LZ4_STAGE_MAX"); // profiling knob: largest block parsed from an LDS copy
+    const Knobs kn = knobs();
+    // CW_LZ4_STAGE_MAX (profiling knob): largest block parsed from an LDS copy
     // measured on text: 4 KiB 26.0 (staged) vs 22.4 GB/s (global); 8 KiB 18.1 vs 20.6; 16 KiB 11.5 vs 18.7 -- blocks per CU win
-    const uint32_t stage_max = sm_env && atoi(sm_env) >= 0 ? (uint32_t)atoi(sm_env) : 4096u;
+    const uint32_t stage_max = kn.lz4_stage_max ? (uint32_t)*kn.lz4_stage_max : 4096u;
     const bool staged = n <= (stage_max < kStageMax ? stage_max : kStageMax);
     // staged bytes are read as aligned dwords: a size that is not a multiple of 4 gets 16 bytes of slack behind it
     uint32_t lds = kTabBytes + (staged ? ((n + 15u) & ~15u) + (n % 4 ? 16u : 0u) : 0u);
@@ -2260,18 +2261,16 @@ hipError_t lz4_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
     };
 
     if ((e = hipMemsetAsync(counters, 0, 8 * sizeof(uint32_t), stream)) != hipSuccess) return e;
-    // CW_LZ4_MODE=scan stops after the scan kernel (queued blocks keep sizes[i] = 0xFFFFFFFF): a profiling knob
-    const char *mode = tune("CW_LZ4_MODE");
     // scan: one wavefront per workgroup, 32 KiB of LDS each -> 5 per CU; the grid-stride loop walks the rest
     const size_t scan_grid = nblocks < 256 * 5 ? nblocks : 256 * 5;
     // CW_LZ4_MODE=generic forces the gather-based scan (profiling knob)
-    const bool streamable = ((reinterpret_cast<uintptr_t>(src) | src_stride | n) & 15) == 0 && !(mode && strcmp(mode, "generic") == 0);
+    const bool streamable = ((reinterpret_cast<uintptr_t>(src) | src_stride | n) & 15) == 0 && kn.lz4_mode != Lz4Mode::generic;
     if (streamable) {
-        const char *wpc_env = tune("CW_SCAN_WPC"); // scan wavefronts per CU (profiling knob; 4 = all that fit)
-        const size_t wpc = wpc_env && atoi(wpc_env) > 0 ? (size_t)atoi(wpc_env) : 4;
+        // CW_SCAN_WPC: scan wavefronts per CU (profiling knob; 4 = all that fit)
+        const size_t wpc = kn.scan_wpc ? (size_t)kn.scan_wpc : 4;
         // power-of-two sizes 4 KiB .. 64 KiB go through the span kernel, 64 KiB of whole blocks per pull; what does not
         // fill a span (and every other size) through the per-block streaming kernel.  CW_LZ4_MODE=stream: the latter only.
-        const bool pow2 = n >= kChunk && (n & (n - 1)) == 0 && !(mode && strcmp(mode, "stream") == 0);
+        const bool pow2 = n >= kChunk && (n & (n - 1)) == 0 && kn.lz4_mode != Lz4Mode::stream;
         uint32_t lg = 0;
         while (pow2 && (kChunk << lg) < n) lg++;
         const size_t run = pow2 ? (size_t)(16u >> lg) : 1;
@@ -2305,16 +2304,15 @@ hipError_t lz4_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
     if ((e = hipGetLastError()) != hipSuccess) return e;
     // the fused call's hook (cw_api.hip, dev_fused): what it enqueues here runs beside the scan, and the parsers below wait for it
     if (after_scan && (e = after_scan->fn(after_scan->ctx)) != hipSuccess) return e;
-    if (mode && strcmp(mode, "scan") == 0) { note_kernels(0, launched); return hipSuccess; }
+    // CW_LZ4_MODE=scan stops after the scan kernel (queued blocks keep sizes[i] = 0xFFFFFFFF): a profiling knob
+    if (kn.lz4_mode == Lz4Mode::scan) { note_kernels(0, launched); return hipSuccess; }
     // parse: queued blocks only; LDS admits 160 KiB / lds workgroups per CU
     // CW_LZ4_PARSE=fp: blocks read from global memory go through the fingerprint parser (20 KiB of LDS, 8 blocks per CU).
     // Measured on text at 64 KiB: 11.9 GB/s against 14.2 GB/s for the second generation with its 10 blocks per CU -- both
     // are bound by the instruction latency of one sequence's serial chain (tools/parse_stamp.hip), not by candidate
     // traffic, so the extra blocks win; the second generation stays the default.
-    const char *gen_env = tune("CW_LZ4_PARSE");
-    const bool use_fp = !staged && gen_env && strcmp(gen_env, "fp") == 0;
-    const char *hw_env = tune("CW_LZ4_HEADW"); // head batch width of the fingerprint parser (profiling knob: 8, 16, 32)
-    const int headw = hw_env ? atoi(hw_env) : 16;
+    const bool use_fp = !staged && kn.lz4_parse_fp;
+    const int headw = kn.lz4_headw.value_or(16); // CW_LZ4_HEADW: head batch width of the fingerprint parser (profiling knob: 8, 16, 32)
     if (use_fp) lds = kTabBytes + kFpBytes;
     const size_t per_cu = (160u * 1024u) / lds ? (160u * 1024u) / lds : 1;
     // Large batches: the lane-per-block parser.  Two regimes:
@@ -2327,17 +2325,14 @@ hipError_t lz4_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
     // The kernel looks at the queue length on the device and leaves everything to the wavefront parser below the threshold.
     // CW_LZ4_LANES=0 switches it off, =N sets the threshold (1: every queued block, in the tests); CW_LANES_WPC = its
     // wavefronts per CU, CW_LANES_CONCURRENT=0|1 forces the regime, CW_LANES_RESERVE the blocks left to the wavefronts.
-    const char *lanes_env = tune("CW_LZ4_LANES");
     // measured break-even with the wavefront parser on text (GB/s, wavefront parser / lanes): 64 KiB 16 Ki blocks 14.2 / 20.9; 16 KiB 16 Ki
     // blocks 18.3 / 17.4, 24 Ki 18.3 / 20.7; 8 KiB 24 Ki blocks 20.9 / 18.5, 32 Ki 20.4 / 22.7 (on small blocks the wavefront parser
     // is faster and a lane slower per byte: every block starts on an empty table, and has one to zero)
-    const uint32_t lane_min = lanes_env ? (uint32_t)atoi(lanes_env)
+    const uint32_t lane_min = kn.lz4_lanes ? (uint32_t)*kn.lz4_lanes
                               : staged ? kLaneMinSmall : n > 32768 ? kLaneMidBlocks : n > 16384 ? 40960u : n > 8192 ? 61440u : 98304u;
     // (16 KiB blocks: the register-table + wavefront parsers 25.7 / 27.9 / 29.3 GB/s at 16 Ki / 32 Ki / 64 Ki blocks against the lanes' 19.5 / 25.0 / 30.1;
     //  8 KiB blocks: 25.5 / 28.8 / 30.0 at 16 Ki / 48 Ki / 96 Ki blocks against 21.4 / 21.3 / 30.3)
     bool lanes_used = false, lanes_beside = false;
-    const char *lf_env = tune("CW_LZ4_LANES_FP"); // profiling knob: 0 = 16-bit table entries without fingerprints for blocks > 4 KiB
-    const bool lanes_fp = !(lf_env && lf_env[0] == '0');
     // CW_LZ4_LANES_RING: 0 = input from global memory (lz4_lanes_kernel); 1, 2, 4, 8 = the ring form with that many positions per
     // iteration whatever the queue's length.  Unset: the ring form, K chosen ON THE DEVICE by the queue's length -- two launches,
     // each of which returns at once unless the length lies in its range:
@@ -2348,18 +2343,18 @@ hipError_t lz4_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
     //   [kLaneWideBlocks, ...)             K = 1.  Enough chains to be bound by the memory system's random lines, where the
     //       lines of the speculative second position only cost (64 Ki blocks: 38.3 against 35.6 GB/s).
     //   K = 4 / 8 are never better (16 Ki blocks: 20.0 / 16.4 GB/s): each position adds instructions to every iteration.
-    const char *lr_env = tune("CW_LZ4_LANES_RING");
-    const int lanes_ring = lr_env ? atoi(lr_env) : -1; // -1: by queue length
+    const int lanes_ring = kn.lz4_lanes_ring.value_or(-1); // -1: by queue length
+    // CW_LANES_CONCURRENT=0: one after the other on the caller's stream (the lanes take the whole queue); default: side by side
+    const bool lanes_concurrent = kn.lanes_concurrent.value_or(true);
     if (!use_fp && lane_min && nblocks >= lane_min && n >= 64) {
-        const char *lw_env = tune("CW_LANES_WPC");
-        const size_t lwpc = lw_env && atoi(lw_env) > 0 ? (size_t)atoi(lw_env) : 8;
+        const size_t lwpc = kn.lanes_wpc ? (size_t)kn.lanes_wpc : 8;
         size_t lgrid = (nblocks + 63) / 64, lcap = 256 * lwpc;
         uint32_t lane_leave = 0;
         // LDS-staged blocks, lanes beside the wavefront parser: lanes for about half of the blocks (2 .. 8 wavefronts per CU).  With
         // fewer lanes each is faster (less traffic per probe in flight), and a batch of 64 Ki .. 256 Ki blocks is over before a lane
         // has parsed more than two or three (text, 4 KiB, 80 Ki / 128 Ki / 256 Ki blocks: 2 wavefronts per CU 34.4 / 33.6 / 35.6 GB/s,
         // 4: 27.7 / 39.6 / 36.5, 8: 24.9 / 26.0 / 39.0-41.0; the wavefront parser alone 25.8)
-        if (staged && !(lw_env && atoi(lw_env) > 0)) lcap = nblocks / 128 < 512 ? 512 : nblocks / 128 > 2048 ? 2048 : nblocks / 128;
+        if (staged && !kn.lanes_wpc) lcap = nblocks / 128 < 512 ? 512 : nblocks / 128 > 2048 ? 2048 : nblocks / 128;
         if (lgrid > lcap) lgrid = lcap;
         // blocks > 4 KiB, lanes beside the on-chip parsers, calls below kLaneWideBlocks (every lane gets ONE block and the call lasts as long as a lane
         // needs for it, 60-110 ms depending on how many lanes run): no lanes for the ~18 Ki blocks the two on-chip parsers get through in that time.
@@ -2369,9 +2364,9 @@ hipError_t lz4_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
         // 48 Ki 42.5 / 43.2 / 44.1 / 46.8 / 39.2, 64 Ki 41.1 / 42.9 / 47.3 / 45.2 / 42.1 (best: all but 16-19 Ki blocks); 128 Ki and 256 Ki blocks
         // (lanes take several blocks each, the reserve works): 47.8 / 42.6 / 46.5 / 44.6 / 44.7 and 47.6-49.1, no trend.
         // (the kernel applies the same rule to the queue's length, which may be shorter than the call: blocks the scan has dealt with are not queued)
-        const char *ll_env = tune("CW_LANES_LEAVE"); // blocks of such a call that get no lane (profiling knob; 0 = a lane for every block)
-        const size_t leave = ll_env ? (size_t)atoi(ll_env) : kLaneLeave;
-        if (!staged && leave && !(tune("CW_LANES_CONCURRENT") && tune("CW_LANES_CONCURRENT")[0] == '0') && lane_min > 1) {
+        // CW_LANES_LEAVE: blocks of such a call that get no lane (profiling knob; 0 = a lane for every block)
+        const size_t leave = kn.lanes_leave ? (size_t)*kn.lanes_leave : kLaneLeave;
+        if (!staged && leave && lanes_concurrent && lane_min > 1) {
             lane_leave = (uint32_t)leave;
             const size_t want = nblocks > leave + 4096 ? (nblocks - leave + 63) / 64 : 64;
             if (nblocks < kLaneWideBlocks && lgrid > want) lgrid = want;
@@ -2389,10 +2384,7 @@ hipError_t lz4_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
             }
         }
         if (lgrid) {
-        // CW_LANES_CONCURRENT=0: one after the other on the caller's stream (the lanes take the whole queue); default: side by side
-        const char *cc_env = tune("CW_LANES_CONCURRENT");
-        const char *rs_env = tune("CW_LANES_RESERVE");
-        lanes_beside = cc_env ? cc_env[0] != '0' : true;
+        lanes_beside = lanes_concurrent;
         uint32_t reserve = 0, reserve_wide = 0, lmin = lane_min;
         if (lanes_beside) {
             if (!wsp.side) {
@@ -2403,10 +2395,9 @@ hipError_t lz4_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
                     // kernels starting the moment ITS OWN lanes kernel had ended, 108 ms late.  With the side streams in another pool a chunk's kernels
                     // no longer share a queue with each other: host path over the corpus 20.5-21.0 -> 24.0-24.3 GB/s (GPU_MAX_HW_QUEUES=8 on top: 24.7-24.9);
                     // the device-resident legs and the headline are unchanged (16 GiB corpus leg 44-48 -> 49.6).
-                    const char *sp_env = tune("CW_SIDE_PRIO");
                     int least = 0, greatest = 0;
                     if ((e = hipDeviceGetStreamPriorityRange(&least, &greatest)) != hipSuccess) return e;
-                    e = !(sp_env && sp_env[0] == '0') ? hipStreamCreateWithPriority(&wsp.side, hipStreamNonBlocking, greatest)
+                    e = kn.side_prio != SidePrio::none ? hipStreamCreateWithPriority(&wsp.side, hipStreamNonBlocking, greatest)
                                                    : hipStreamCreateWithFlags(&wsp.side, hipStreamNonBlocking);
                     if (e != hipSuccess) return e;
                 }
@@ -2417,9 +2408,9 @@ hipError_t lz4_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
             // 256 Ki blocks: 16 Ki / 28 Ki / 40 Ki 37.4 / 39.0 / 41.0
             // blocks > 4 KiB (round 3; corpus, 64 KiB, lanes alone -> lanes beside the other two, GB/s): two positions per iteration, 32 Ki blocks
             // 29.4 -> 31.0 (reserve 24 Ki), 48 Ki 34.0 -> 40.7 (16-24 Ki), 64 Ki 37.2 -> 40.6 (32 Ki); one position: 128 Ki 44.9 -> 48.3 (32 Ki), 256 Ki 42.8 -> 46.7
-            reserve = rs_env && atoi(rs_env) > 0 ? (uint32_t)atoi(rs_env) : (staged ? 32768u : kLaneShare);
-            if (!staged && !(rs_env && atoi(rs_env) > 0) && reserve > nblocks / 3 * 2) reserve = (uint32_t)(nblocks / 3 * 2);
-            reserve_wide = rs_env && atoi(rs_env) > 0 ? (uint32_t)atoi(rs_env) : kLaneShareWide;
+            reserve = kn.lanes_reserve ? (uint32_t)kn.lanes_reserve : (staged ? 32768u : kLaneShare);
+            if (!staged && !kn.lanes_reserve && reserve > nblocks / 3 * 2) reserve = (uint32_t)(nblocks / 3 * 2);
+            reserve_wide = kn.lanes_reserve ? (uint32_t)kn.lanes_reserve : kLaneShareWide;
             if (lane_min > 1 && lmin < reserve + reserve / 4) lmin = reserve + reserve / 4; // (CW_LZ4_LANES=1 in the tests: no reserve)
             if (lane_min == 1) reserve = reserve_wide = 0;
             if ((e = hipEventRecord(wsp.fork, stream)) != hipSuccess) return e;
@@ -2451,7 +2442,7 @@ hipError_t lz4_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
         else if (lanes_ring == 4) CW_RING(4, lmin, no_max);
         else if (lanes_ring == 8) CW_RING(8, lmin, no_max);
 #undef CW_RING
-        else if (lanes_fp) {
+        else if (kn.lz4_lanes_fp) { // CW_LZ4_LANES_FP=0 (profiling knob): 16-bit table entries without fingerprints for blocks > 4 KiB
             hipLaunchKernelGGL(lz4_lanes_kernel<kLaneFp>, dim3((unsigned)lgrid), dim3(64), 0, ls, src, n, src_stride, dst, dst_stride, sizes, queue,
                                counters, wsp.lane_tabs, lmin, reserve);
             note("cw::lz4_lanes_kernel<2> (queue >= %u)%s", lmin, side_tag);
@@ -2471,26 +2462,24 @@ hipError_t lz4_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
     // candidate fetches wait).  CW_LZ4_VTAB: 0 = off, 1 = on the caller's stream AHEAD of the wavefront parser (it takes the whole
     // queue: tests), 2 = beside (default); CW_VTAB_MIN / CW_VTAB_MAX = queue lengths between which it runs (checked on the device),
     // CW_VTAB_RESERVE = blocks it leaves to the others, CW_VTAB_WPC = its wavefronts per CU (at most 16), CW_VTAB_GEN = kernel generation.
-    const char *vt_env = tune("CW_LZ4_VTAB");
-    const int vt_mode = vt_env ? atoi(vt_env) : 2;
-    const bool cut_first = mode && strcmp(mode, "cut") == 0; // (CW_LZ4_MODE=cut: the first-generation parser only)
+    const int vt_mode = kn.lz4_vtab.value_or(2);
+    // CW_LZ4_MODE=cut parses with the first-generation (write/read-back) kernel only (profiling knob)
+    const bool cut_only = kn.lz4_mode == Lz4Mode::cut;
     bool vtab_used = false, vtab_beside = false;
-    if (vt_mode > 0 && !use_fp && !cut_first && n >= 64 && nblocks >= 64 && ((reinterpret_cast<uintptr_t>(src) | src_stride) & 3) == 0) {
-        const char *vm_env = tune("CW_VTAB_MIN"), *vx_env = tune("CW_VTAB_MAX"), *vr_env = tune("CW_VTAB_RESERVE"), *vw_env = tune("CW_VTAB_WPC");
+    if (vt_mode > 0 && !use_fp && !cut_only && n >= 64 && nblocks >= 64 && ((reinterpret_cast<uintptr_t>(src) | src_stride) & 3) == 0) {
         // LDS-staged blocks: a small queue is the LDS-resident parser's (4 Ki blocks of 4 KiB: 19.4 GB/s alone against 14.5 with the register-table
         // parser's 4,096 wavefronts taking a block each; 16 Ki blocks 23.8 -> 24.5, 32 Ki 25.1 -> 28.0, 51,728 25.6 -> 29.5)
-        const uint32_t vmin = vm_env ? (uint32_t)atoi(vm_env) : staged ? 12288u : 1u, vres = vr_env ? (uint32_t)atoi(vr_env) : 0u;
+        const uint32_t vmin = kn.vtab_min ? (uint32_t)*kn.vtab_min : staged ? 12288u : 1u, vres = kn.vtab_reserve ? (uint32_t)*kn.vtab_reserve : 0u;
         // lanes that take the whole queue (blocks > 4 KiB) start at lane_min queued blocks: the register-table parser stays below
-        const uint32_t vmax = vx_env ? (uint32_t)atoi(vx_env) : (lanes_used && !lanes_beside ? lane_min : 0xFFFFFFFFu);
-        const unsigned vwpc = vw_env && atoi(vw_env) > 0 ? (unsigned)atoi(vw_env) : 16u;
+        const uint32_t vmax = kn.vtab_max ? (uint32_t)*kn.vtab_max : (lanes_used && !lanes_beside ? lane_min : 0xFFFFFFFFu);
+        const unsigned vwpc = kn.vtab_wpc ? (unsigned)kn.vtab_wpc : 16u;
         hipStream_t vs = stream;
         if (vt_mode == 2) {
             if (!wsp.side2) {
                 {
-                    const char *sp_env = tune("CW_SIDE_PRIO");
                     int least = 0, greatest = 0;
                     if ((e = hipDeviceGetStreamPriorityRange(&least, &greatest)) != hipSuccess) return e;
-                    e = !(sp_env && sp_env[0] != '2') ? hipStreamCreateWithPriority(&wsp.side2, hipStreamNonBlocking, greatest)
+                    e = kn.side_prio == SidePrio::both ? hipStreamCreateWithPriority(&wsp.side2, hipStreamNonBlocking, greatest)
                                                    : hipStreamCreateWithFlags(&wsp.side2, hipStreamNonBlocking);
                     if (e != hipSuccess) return e;
                 }
@@ -2503,26 +2492,22 @@ hipError_t lz4_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
             vtab_beside = true;
         }
         const char *vname = nullptr;
-        if ((e = lz4_vtab_launch(src, n, src_stride, nblocks, dst, dst_stride, sizes, queue, counters, vmin, vmax, vres, vwpc, vs, &vname)) != hipSuccess) return e;
+        const int gen = kn.vtab_gen.value_or(0);
+        if ((e = lz4_vtab_launch(src, n, src_stride, nblocks, dst, dst_stride, sizes, queue, counters, vmin, vmax, vres, vwpc, gen, vs, &vname)) != hipSuccess) return e;
         if (vmax != 0xFFFFFFFFu) note("%s (queue < %u)%s", vname, vmax, vtab_beside ? " [side stream]" : "");
         else note("%s%s", vname, vtab_beside ? " [side stream]" : "");
         vtab_used = true;
     }
-    const char *pwpc_env = tune("CW_PARSE_WPC"); // parse wavefronts per CU (profiling knob; default: all the LDS admits)
-    const size_t pwpc = pwpc_env && atoi(pwpc_env) > 0 ? (size_t)atoi(pwpc_env) : 10;
+    const size_t pwpc = kn.parse_wpc ? (size_t)kn.parse_wpc : 10; // CW_PARSE_WPC: parse wavefronts per CU (profiling knob; default: all the LDS admits)
     const size_t want = 256 * (per_cu > pwpc ? pwpc : per_cu);
     const size_t grid = nblocks < want ? nblocks : want;
-    // CW_LZ4_MODE=cut parses with the first-generation (write/read-back) kernel only (profiling knob)
-    const bool cut_only = mode && strcmp(mode, "cut") == 0;
     // CW_LZ_FORCE_REDO=1: the exchange kernel hands every block back, as if its lane-order check had failed (test knob)
-    const char *redo_env = tune("CW_LZ_FORCE_REDO");
-    const uint32_t force_redo = redo_env && atoi(redo_env) > 0 ? 1u : 0u;
+    const uint32_t force_redo = kn.force_redo ? 1u : 0u;
     if (!cut_only) {
         // blocks read from global memory: the scalar-thread parser with its table in LDS (lz4_vtab3_kernel<true>) in the place of the round-2
         // wavefront parser; CW_LZ4_LTAB=0 keeps the latter (and the forced-redo test knob and unaligned sources need it)
-        const char *lt_env = tune("CW_LZ4_LTAB");
         const bool use_ltab = !staged && !use_fp && !force_redo && n >= 64 && ((reinterpret_cast<uintptr_t>(src) | src_stride) & 3) == 0 &&
-                              (lt_env ? atoi(lt_env) != 0 : kLtabDefault);
+                              (kn.lz4_ltab ? *kn.lz4_ltab != 0 : kLtabDefault);
         if (use_ltab) {
             note("cw::lz4_vtab3_kernel<true>");
             if ((e = lz4_ltab_launch(src, n, src_stride, nblocks, dst, dst_stride, sizes, queue, counters, (unsigned)pwpc, stream)) != hipSuccess) return e;

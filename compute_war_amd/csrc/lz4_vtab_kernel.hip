@@ -742,13 +742,12 @@ lz4_vtab3_kernel(const uint8_t *__restrict__ src, uint32_t n, size_t src_stride,
 // grid: as many single-wavefront workgroups as the register file admits (128 VGPRs -> 4 per SIMD, 16 per CU), at most one per queued block
 hipError_t lz4_vtab_launch(const uint8_t *src, uint32_t n, size_t src_stride, size_t nblocks, uint8_t *dst, size_t dst_stride, uint32_t *sizes,
                            const uint32_t *queue, uint32_t *counters, uint32_t min_queued, uint32_t max_queued, uint32_t reserve,
-                           unsigned waves_per_cu, hipStream_t stream, const char **kernel_name)
+                           unsigned waves_per_cu, int gen, hipStream_t stream, const char **kernel_name)
 {
-    // CW_VTAB_GEN: 2 = batches of four items (vector loads), 3 = the scalar chain with the VALU's help.  Default by measurement (GB/s alone,
+    // gen (CW_VTAB_GEN): 2 = batches of four items (vector loads), 3 = the scalar chain with the VALU's help.  Default by measurement (GB/s alone,
     // 16 wavefronts per CU; (1) = the all-scalar first form, removed): text, 64 KiB blocks, 8 Ki blocks 18.4 (1) / 13.7 (2) / 20.8 (3),
     // 3,233 blocks 13.6 / 11.3 / 17.1; corpus, 4 KiB blocks 15.4-16.0 (1) against 17.8-17.9 (2)
-    const char *gen_env = tune("CW_VTAB_GEN");
-    const int gen = gen_env && atoi(gen_env) == 2 ? 2 : gen_env && atoi(gen_env) == 3 ? 3 : n <= 4096 ? 2 : 3;
+    if (gen != 2 && gen != 3) gen = n <= 4096 ? 2 : 3;
     if ((reinterpret_cast<uintptr_t>(src) | src_stride) & 3) return hipErrorInvalidValue; // the scalar loads are dword loads
     size_t grid = 256 * (size_t)(waves_per_cu ? waves_per_cu : 16);
     if (grid > nblocks) grid = nblocks;

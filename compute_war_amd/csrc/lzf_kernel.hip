@@ -1381,35 +1381,30 @@ hipError_t lzf_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
         attr_set = true;
     }
     const size_t grid = nblocks < 256 ? nblocks : 256; // the 128 KiB table admits one workgroup per CU
+    const Knobs kn = knobs();
     // CW_LZF_MODE=cut: write/read-back kernel only; =table: exchange kernel with the 128 KiB table also for small blocks
-    const char *mode = tune("CW_LZF_MODE");
-    const bool cut_only = mode && strcmp(mode, "cut") == 0, table_only = mode && strcmp(mode, "table") == 0;
-    const char *redo_env = tune("CW_LZ_FORCE_REDO"); // test knob, see lz4_kernel.hip
-    const uint32_t force_redo = redo_env && atoi(redo_env) > 0 ? 1u : 0u;
+    const bool cut_only = kn.lzf_mode == LzfMode::cut, table_only = kn.lzf_mode == LzfMode::table;
+    const uint32_t force_redo = kn.force_redo ? 1u : 0u; // CW_LZ_FORCE_REDO: test knob, see lz4_kernel.hip
     if (!cut_only && !table_only && n >= 16) {
         // links for a round of blocks, then the chain parser over that round
-        const char *lm_env = tune("CW_LZF_LDS_MAX"); // profiling knob: largest block parsed from LDS-resident links
+        // CW_LZF_LDS_MAX (profiling knob): largest block parsed from LDS-resident links
         // measured (text): 4 KiB 13.2 (LDS) vs 12.4 GB/s (global links); 8 KiB 7.2 vs 10.6; 16 KiB 3.7 vs 9.3 -- blocks per CU win
-        const uint32_t lds_max = lm_env && atoi(lm_env) > 0 ? (uint32_t)atoi(lm_env) : 4096u;
+        const uint32_t lds_max = kn.lzf_lds_max ? (uint32_t)kn.lzf_lds_max : 4096u;
         const bool big = n > (lds_max < kChainMax ? lds_max : kChainMax);
         const uint32_t n2 = (n + 63u) & ~63u;
         const size_t ws_bytes = big ? (size_t)1 << 30 : (size_t)256 << 20; // links per round
-        const char *round_env = tune("CW_LZF_ROUND"); // test knob: blocks per round (many rounds on small data)
-        const char *lanes_env = tune("CW_LZF_LANES");
         // (blocks of 4-8 KiB: the chain kernels win up to ~18 Ki blocks -- text, 8 KiB, 16 Ki blocks 11.0 against 10.6 GB/s, 24 Ki 11.3 / 13.0)
-        const size_t lane_min = lanes_env ? (size_t)atoi(lanes_env) : (big ? (n > 8192 ? kLzfLaneMinBlocks : 18432u) : kLzfLaneMinSmall);
-        const char *cc_env = tune("CW_LANES_CONCURRENT");
+        const size_t lane_min = kn.lzf_lanes ? (size_t)*kn.lzf_lanes : (big ? (n > 8192 ? kLzfLaneMinBlocks : 18432u) : kLzfLaneMinSmall);
         bool use_lanes = lane_min && nblocks >= lane_min;
         // blocks > 4 KiB: the scalar-thread form of the chain parser (CW_LZF_STHREAD=0: the wavefront-wide one); needs dword-aligned blocks
-        const char *st_env = tune("CW_LZF_STHREAD");
-        const char *stw_env = tune("CW_LZF_ST_WPC");
-        const size_t st_wpc = stw_env && atoi(stw_env) > 0 ? (size_t)atoi(stw_env) : 20;
-        const bool sthread = big && (st_env ? st_env[0] != '0' : true) && ((reinterpret_cast<uintptr_t>(src) | src_stride) & 3) == 0;
+        const size_t st_wpc = kn.lzf_st_wpc ? (size_t)kn.lzf_st_wpc : 20;
+        const bool sthread = big && kn.lzf_sthread && ((reinterpret_cast<uintptr_t>(src) | src_stride) & 3) == 0;
         // lanes BESIDE the rounds: blocks <= 4 KiB always; larger blocks from kLzfBigBesideMin blocks on, and only with the scalar-thread
         // parser in the rounds (with the wavefront-wide chain kernel in the rounds: 256 Ki blocks 27.7 -> 27.7 GB/s)
         const bool big_beside = sthread && n > 16384 && nblocks >= kLzfBigBesideMin;
-        bool beside = use_lanes && (cc_env ? cc_env[0] != '0' : !big || big_beside);
-        const size_t chunk_cap = round_env && atoi(round_env) > 0 ? (size_t)atoi(round_env) : beside ? (big ? (nblocks < kLzfBigBesideWide ? kLzfBigBesideRoundMid : kLzfBigBesideRound) : kLzfBesideRound) : ws_bytes / (2 * (size_t)n2);
+        bool beside = use_lanes && kn.lanes_concurrent.value_or(!big || big_beside);
+        // CW_LZF_ROUND (test knob): blocks per round (many rounds on small data)
+        const size_t chunk_cap = kn.lzf_round ? (size_t)kn.lzf_round : beside ? (big ? (nblocks < kLzfBigBesideWide ? kLzfBigBesideRoundMid : kLzfBigBesideRound) : kLzfBesideRound) : ws_bytes / (2 * (size_t)n2);
         const size_t chunk_max = chunk_cap < ws_bytes / (2 * (size_t)n2) ? chunk_cap : ws_bytes / (2 * (size_t)n2);
         const size_t chunk = nblocks < chunk_max ? nblocks : chunk_max;
         LinkSpace ls;
@@ -1424,6 +1419,7 @@ hipError_t lzf_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
         // LDS-resident chain parser, from kLzfLaneMinSmall on: the lanes run BESIDE the link/chain rounds on a second stream,
         // pulling from the top of the batch while the rounds climb from the bottom (LaneShare) -- one side is bound by LDS
         // capacity and chain latency, the other by random memory accesses.
+        const size_t want_reserve = kn.lanes_reserve ? (size_t)kn.lanes_reserve : big ? (nblocks < kLzfBigBesideWide ? kLzfBigBesideReserveMid : kLzfBigBesideRound) : nblocks < 49152 ? kLzfBesideReserveFew : kLzfBesideReserve;
         uint32_t lane_reserve = 0;
         const size_t round_max = ws_bytes / (2 * (size_t)n2); // blocks per round that the link workspace admits
         const size_t hb_chunk = nblocks < round_max ? nblocks : round_max; // rounds of the hand-back pass
@@ -1442,12 +1438,9 @@ hipError_t lzf_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
         }
         size_t lgrid = 0; // workgroups of the lane-per-block kernel
         if (use_lanes) {
-            const char *lw_env = tune("CW_LANES_WPC");
-            const size_t lwpc = lw_env && atoi(lw_env) > 0 ? (size_t)atoi(lw_env) : 4;
+            const size_t lwpc = kn.lanes_wpc ? (size_t)kn.lanes_wpc : 4;
             lgrid = (nblocks + 63) / 64;
             if (lgrid > 256 * lwpc) lgrid = 256 * lwpc;
-            const char *rs0_env = tune("CW_LANES_RESERVE");
-            const size_t want_reserve = rs0_env && atoi(rs0_env) > 0 ? (size_t)atoi(rs0_env) : big ? (nblocks < kLzfBigBesideWide ? kLzfBigBesideReserveMid : kLzfBigBesideRound) : nblocks < 49152 ? kLzfBesideReserveFew : kLzfBesideReserve;
             if (beside && lgrid * 64 + want_reserve > nblocks) lgrid = nblocks > want_reserve + 64 ? (nblocks - want_reserve) / 64 : 1; // (no lane without a block)
             LinkSpace &w = entry->s;
             if (w.lane_cap < lgrid * 64) {
@@ -1480,8 +1473,7 @@ hipError_t lzf_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
                     if ((e = hipEventCreateWithFlags(&w.fork, hipEventDisableTiming)) != hipSuccess) return e;
                     if ((e = hipEventCreateWithFlags(&w.join, hipEventDisableTiming)) != hipSuccess) return e;
                 }
-                const char *rs_env = tune("CW_LANES_RESERVE");
-                lane_reserve = rs_env && atoi(rs_env) > 0 ? (uint32_t)atoi(rs_env) : big ? (nblocks < kLzfBigBesideWide ? kLzfBigBesideReserveMid : kLzfBigBesideRound) : nblocks < 49152 ? kLzfBesideReserveFew : kLzfBesideReserve;
+                lane_reserve = (uint32_t)want_reserve;
                 if (lane_reserve < 1) lane_reserve = 1; // (0 means "on their own" to the kernel; the protocol itself needs no reserve)
                 if ((e = hipEventRecord(w.fork, stream)) != hipSuccess) return e;
                 if ((e = hipStreamWaitEvent(w.side, w.fork, 0)) != hipSuccess) return e;
@@ -1513,8 +1505,8 @@ hipError_t lzf_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
         if (per_cu > (big ? 20u : 16u)) per_cu = big ? 20 : 16;
         // one round of the link + chain kernels: blocks [first, first + nb) of the batch, or entries [first, first + nb) of the
         // hand-back list (as far as the lanes filled it: the kernels read its length on the device and return at once beyond it)
-        const char *gu_env = tune("CW_LZF_SHARE_GIVE_UP"); // test knob: every workgroup but a round's claimant gives up at once
-        const uint32_t spin_cap = gu_env && atoi(gu_env) > 0 ? 0u : kShareSpinCap;
+        // CW_LZF_SHARE_GIVE_UP (test knob): every workgroup but a round's claimant gives up at once
+        const uint32_t spin_cap = kn.lzf_share_give_up ? 0u : kShareSpinCap;
         auto round = [&](size_t first, size_t nb, bool listed) -> hipError_t {
             hipError_t r = hipMemsetAsync(ls.counter, 0, sizeof(uint32_t), stream);
             if (r != hipSuccess) return r;
@@ -1549,7 +1541,7 @@ hipError_t lzf_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
             if (e == hipSuccess) e = hipStreamWaitEvent(stream, ls.join, 0);
             if (e != hipSuccess) return e;
         }
-        if (use_lanes && tune("CW_DEBUG_LZF")) {
+        if (use_lanes && kn.debug_lzf) {
             uint32_t h[kCtrBytes / 4];
             (void)hipStreamSynchronize(stream);
             (void)hipMemcpy(h, ls.counter, kCtrBytes, hipMemcpyDeviceToHost);

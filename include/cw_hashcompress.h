@@ -230,10 +230,11 @@ int  cw_profile_kernels(int kind, char *buf, size_t cap);
 
 /* ---- CW_TESTING: tuning and test knobs -----------------------------------------------------------------------------
  * Every knob the launch policy reads (thresholds such as CW_LZ4_LANES / CW_LZF_LANES / CW_LZ4_VTAB, CW_LANES_*, CW_LZF_ROUND,
- * CW_LZ_FORCE_REDO, CW_DECODE_LANES, CW_HOST_*CHUNK_MB, ...; DESIGN.md lists them) is looked up PER CALL: the value given
- * here wins, the environment variable of the same name is the default.  value = NULL removes an override.  Not part of the
- * reference's interface (it has no tunables beyond its CLI); meant for tests and profiling, and not to be changed while
- * other threads are inside compute calls.                                                                             */
+ * CW_LZ_FORCE_REDO, CW_DECODE_LANES, CW_HOST_*CHUNK_MB, ...; README.md lists them) is read PER CALL: the value given
+ * here wins, the environment variable of the same name is the default.  value = NULL removes an override; a name the
+ * library does not read is refused with CW_ERR_BAD_ARG.  A launch sees the knobs as they were when it started, so setting
+ * them while other threads compute is safe.  Not part of the reference's interface (it has no tunables beyond its CLI);
+ * meant for tests and profiling.                                                                                      */
 int  cw_tune_set(const char *key, const char *value);
 void cw_tune_reset(void);
 

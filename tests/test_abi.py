@@ -123,3 +123,43 @@ def test_multi_device_entry_points_fail_cleanly_without_gpu(cwlib):
     subprocess.run(["make", "-C", os.path.dirname(exe)], capture_output=True, text=True, check=True)
     r = subprocess.run([exe, "--devices", "2"], capture_output=True, text=True)
     assert r.returncode == 2 and "0 usable" in r.stderr
+
+
+CW_ERR_BAD_ARG = -2  # include/cw_hashcompress.h
+
+
+def _knob_table():
+    """The knob names of the one table in cw_api.hip that decodes them (kKnobTable), with the table's line span."""
+    lines = open(os.path.join(ROOT, "compute_war_amd", "csrc", "cw_api.hip")).read().split("\n")
+    first = next(i for i, l in enumerate(lines) if "kKnobTable[] = {" in l)
+    last = next(i for i in range(first, len(lines)) if lines[i] == "};")
+    names = re.findall(r'^\s*\{"(CW_[A-Z0-9_]+)"', "\n".join(lines[first:last]), flags=re.M)
+    return names, (first + 1, last + 1)
+
+
+def test_knob_table_is_the_only_list_of_knobs(cwlib):
+    """Every knob the library reads is in the table: cw_tune_set accepts it and the README's knob paragraph names it; other names
+    are refused, and no other code in the library looks a knob up by name."""
+    names, (first, last) = _knob_table()
+    assert len(names) >= 40 and len(set(names)) == len(names), names
+    readme = open(os.path.join(ROOT, "README.md")).read()
+    para = readme[readme.index("Profiling / test knobs"):].split("\n\n")[0]
+    L = cwlib.lib()
+    try:
+        for n in names:
+            assert L.cw_tune_set(n.encode(), b"0") == 0, n
+            assert L.cw_tune_set(n.encode(), None) == 0, n
+            assert re.search(r"`%s[=`]" % n, para), f"{n} is missing from the README's knob paragraph"
+        assert L.cw_tune_set(b"CW_NO_SUCH_KNOB", b"1") == CW_ERR_BAD_ARG
+        assert L.cw_tune_set(b"CW_NO_SUCH_KNOB", None) == CW_ERR_BAD_ARG
+    finally:
+        cwlib.tune_reset()
+    csrc = os.path.join(ROOT, "compute_war_amd", "csrc")
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".h")):
+            continue
+        for i, line in enumerate(open(os.path.join(csrc, f)).read().split("\n"), 1):
+            code = line.split("//")[0]
+            assert "tune(" not in code or "cw_tune" in code, (f, i, line)
+            assert '"CW_' not in code or (f == "cw_api.hip" and first <= i <= last), (f, i, line)
+            assert "getenv(" not in code or "getenv(kKnobTable[i].name)" in code, (f, i, line)

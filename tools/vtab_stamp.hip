@@ -6,8 +6,6 @@
 #include <stdio.h>
 #include <vector>
 
-const char *cw::tune(const char *) { return nullptr; }
-
 int main(int argc, char **argv)
 {
     const char *path = argc > 1 ? argv[1] : "tests/golden/corpus/canterbury/lcet10.txt";
