@@ -26,6 +26,7 @@ ABI_SYMBOLS = [
     "cw_offload_complete", "cw_offload_completed", "cw_offload_state", "cw_offload_error", "cw_offload_do",
     "cw_offload_thread_start", "cw_offload_submit", "cw_offload_thread_stop",
     "cw_dedupe_create", "cw_dedupe_destroy", "cw_dedupe_count", "cw_dev_dedupe", "cw_dev_hash_dedupe_compress",
+    "cw_cdc_default_params", "cw_dev_cdc", "cw_dev_hash_chunks", "cw_cdc_hash",
     "cw_shard_range", "cw_mgpu_create", "cw_mgpu_destroy", "cw_mgpu_ndev", "cw_mgpu_device", "cw_mgpu_last_error", "cw_mgpu_gather",
 ]
 
@@ -124,6 +125,10 @@ def lib() -> C.CDLL:
         "cw_dedupe_count": ([vp, vp], C.c_int),
         "cw_dev_dedupe": ([vp, vp, sz, C.c_uint64, vp, vp, vp, vp], C.c_int),
         "cw_dev_hash_dedupe_compress": ([vp, C.c_int, vp, sz, sz, sz, C.c_uint64, vp, vp, vp, vp, sz, u32p, vp, vp], C.c_int),
+        "cw_cdc_default_params": ([vp, C.c_uint32], None),
+        "cw_dev_cdc": ([vp, vp, sz, C.c_int, vp, sz, vp, vp], C.c_int),
+        "cw_dev_hash_chunks": ([C.c_int, vp, sz, vp, vp, sz, vp, vp], C.c_int),
+        "cw_cdc_hash": ([vp, C.c_int, vp, sz, vp, sz, vp, vp], C.c_int),
         "cw_shard_range": ([sz, C.c_int, C.c_int, vp, vp], None),
         "cw_mgpu_create": ([vp, C.c_int], vp), "cw_mgpu_destroy": ([vp], None), "cw_mgpu_ndev": ([vp], C.c_int),
         "cw_mgpu_device": ([vp, C.c_int], C.c_int), "cw_mgpu_last_error": ([], C.c_char_p),

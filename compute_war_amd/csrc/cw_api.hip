@@ -331,6 +331,7 @@ const KnobDef kKnobTable[] = {
     {"CW_SKEIN_NSLICES", [](Knobs &k, const char *v) { positive(k.skein_nslices, v); }},
     {"CW_HOST_CHUNK_MB", [](Knobs &k, const char *v) { positive(k.host_chunk_mb, v); }},
     {"CW_HOST_BIG_CHUNK_MB", [](Knobs &k, const char *v) { positive(k.host_big_chunk_mb, v); }},
+    {"CW_CDC_SEGMENT", [](Knobs &k, const char *v) { positive(k.cdc_segment, v); }},
     {"CW_LZ_FORCE_REDO", [](Knobs &k, const char *v) { k.force_redo = atoi(v) > 0; }},
     {"CW_LZF_SHARE_GIVE_UP", [](Knobs &k, const char *v) { k.lzf_share_give_up = atoi(v) > 0; }},
     {"CW_LZ4_LANES", [](Knobs &k, const char *v) { k.lz4_lanes = atoi(v); }},
@@ -378,6 +379,7 @@ void cw::release_stream_workspaces(hipStream_t stream)
     cw::lzf_release_stream(stream);
     cw::pack_release_stream(stream);
     cw::skein_release_stream(stream);
+    cw::cdc_release_stream(stream);
 }
 
 void cw::note_kernels(int kind, const char *names)
@@ -456,6 +458,7 @@ void cw_shutdown(void)
     cw::lz4_release_workspaces();
     cw::lzf_release_workspaces();
     cw::pack_release_workspaces();
+    cw::cdc_release_workspaces();
     g_mask.store(0);
     g_default.store(-1);
     t_device = -1;
@@ -1243,6 +1246,170 @@ unsigned cw_decompress_lzf(const void *src, unsigned csize, void *dst, unsigned 
     if (cw_decompress_blocks(CW_COMP_LZF, src, sz, &sz, 1, dst, bb, &st) != CW_OK) die("cw_decompress_lzf");
     return st == 0 ? (unsigned)bb : 0;
 }
+
+// ---- content-defined chunking (kernels: cdc_kernels.hip; semantics: the header) ------------------------------------------
+namespace {
+
+uint64_t splitmix64_host(uint64_t x)
+{
+    uint64_t z = x + 0x9E3779B97F4A7C15ULL;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    return z ^ (z >> 31);
+}
+
+struct DefaultGear {
+    uint64_t g[256];
+    DefaultGear() { for (int v = 0; v < 256; v++) g[v] = splitmix64_host((uint64_t)v); }
+};
+const DefaultGear kDefaultGear;
+
+int cdc_params(const cw_cdc_params *p, cw::CdcParams *out)
+{
+    if (!p) return fail(CW_ERR_BAD_ARG, "NULL cdc params");
+    if (p->reserved != 0) return fail(CW_ERR_BAD_ARG, "cdc params: reserved must be 0");
+    if (!(64 <= p->min_size && p->min_size <= p->normal_size && p->normal_size <= p->max_size && p->max_size <= (1u << 24)))
+        return fail(CW_ERR_BAD_ARG, "cdc params: need 64 <= min %u <= normal %u <= max %u <= 2^24", p->min_size, p->normal_size, p->max_size);
+    *out = cw::CdcParams{p->min_size, p->normal_size, p->max_size, p->mask_s, p->mask_l, p->gear ? p->gear : kDefaultGear.g};
+    return CW_OK;
+}
+
+int dev_cdc(const cw::CdcParams &p, const uint8_t *d_src, size_t nbytes, int final_, uint64_t *d_offsets, size_t max_offsets,
+            uint64_t *d_nchunks, hipStream_t s)
+{
+    const uint64_t seg = cw::cdc_segment_bytes(p.max_size, cw::knobs().cdc_segment);
+    ProfScope prof(PROF_HASH, s);
+    hipError_t e = cw::cdc_launch(p, d_src, nbytes, final_, d_offsets, max_offsets, d_nchunks, seg, s);
+    if (e == hipErrorOutOfMemory) return fail(CW_ERR_NOMEM, "cdc workspace (%zu bytes): %s", cw::cdc_workspace_bytes(nbytes, p.min_size, seg),
+                                              hipGetErrorString(e));
+    if (e != hipSuccess) return fail(CW_ERR_HIP, "cdc launch: %s", hipGetErrorString(e));
+    return CW_OK;
+}
+
+int dev_hash_chunks(int alg, const uint8_t *d_src, size_t src_bytes, const uint64_t *d_offsets, const uint64_t *d_nchunks, size_t max_chunks,
+                    uint8_t *d_dig, hipStream_t s)
+{
+    if (alg == CW_HASH_NONE) return CW_OK;
+    if (alg != CW_HASH_SKEIN512 && alg != CW_HASH_SKEIN256_128 && alg != CW_HASH_SHA256) return fail(CW_ERR_BAD_ARG, "unknown hash algorithm %d", alg);
+    if (max_chunks > 0xFFFFFF00u) return fail(CW_ERR_BAD_ARG, "max_chunks %zu > 2^32 - 256", max_chunks);
+    if (max_chunks == 0) return CW_OK;
+    ProfScope prof(PROF_HASH, s);
+    struct Call { int alg; const uint8_t *src; size_t src_bytes; const uint64_t *off, *n; size_t max; uint8_t *dig; hipStream_t s; };
+    Call call{alg, d_src, src_bytes, d_offsets, d_nchunks, max_chunks, d_dig, s};
+    const cw::ChunkHash hash{[](void *ctx, const uint32_t *perm) {
+                                 const Call &k = *static_cast<const Call *>(ctx);
+                                 if (k.alg == CW_HASH_SHA256) return cw::sha256_chunks_launch(k.src, k.src_bytes, k.off, perm, k.n, k.max, k.dig, k.s);
+                                 if (k.alg == CW_HASH_SKEIN512)
+                                     return cw::skein_chunks_launch(8, k.src, k.src_bytes, k.off, perm, k.n, k.max, g_iv512_512, k.dig, 64, k.s);
+                                 return cw::skein_chunks_launch(4, k.src, k.src_bytes, k.off, perm, k.n, k.max, g_iv256_128, k.dig, 16, k.s);
+                             },
+                             &call};
+    // the step counts the sort orders by: 64-byte steps (Skein-512, SHA-256) or 32-byte steps (Skein-256)
+    const hipError_t e = cw::chunk_hash_launch(d_offsets, d_nchunks, max_chunks, src_bytes, alg == CW_HASH_SKEIN256_128 ? 5 : 6, hash, s);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? CW_ERR_NOMEM : CW_ERR_HIP, "hash chunks launch: %s", hipGetErrorString(e));
+    return CW_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+void cw_cdc_default_params(cw_cdc_params *p, uint32_t normal_size)
+{
+    if (!p) return;
+    // normal_size is clamped to [256, 2^21] and rounded down to a power of two, so every field is defined and valid
+    unsigned lg = 8;
+    while (lg < 21 && (1u << (lg + 1)) <= normal_size) lg++;
+    const uint32_t normal = 1u << lg;
+    p->min_size = normal / 4;
+    p->normal_size = normal;
+    p->max_size = normal * 8;
+    p->reserved = 0;
+    p->mask_s = ~0ull << (64 - (lg + 2));
+    p->mask_l = ~0ull << (64 - (lg - 2));
+    p->gear = NULL;
+}
+
+int cw_dev_cdc(const cw_cdc_params *p, const void *d_src, size_t nbytes, int final, uint64_t *d_offsets, size_t max_offsets,
+               uint64_t *d_nchunks, void *stream)
+{
+    cw::CdcParams cp;
+    int rc = cdc_params(p, &cp);
+    if (rc != CW_OK) return rc;
+    if (!d_offsets || !d_nchunks || (nbytes && !d_src)) return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    if (max_offsets < nbytes / cp.min_size + 2)
+        return fail(CW_ERR_BAD_ARG, "max_offsets %zu < nbytes / min_size + 2 = %zu", max_offsets, nbytes / cp.min_size + 2);
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    return dev_cdc(cp, (const uint8_t *)d_src, nbytes, final ? 1 : 0, d_offsets, max_offsets, d_nchunks, (hipStream_t)stream);
+}
+
+int cw_dev_hash_chunks(int hash_alg, const void *d_src, size_t src_bytes, const uint64_t *d_offsets, const uint64_t *d_nchunks,
+                       size_t max_chunks, void *d_digests, void *stream)
+{
+    if (hash_alg < 0 || hash_alg > CW_HASH_NONE) return fail(CW_ERR_BAD_ARG, "unknown hash algorithm %d", hash_alg);
+    if (hash_alg != CW_HASH_NONE && max_chunks && (!d_offsets || !d_nchunks || !d_digests || (src_bytes && !d_src)))
+        return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    int rc = ensure_init();
+    if (rc != CW_OK) return rc;
+    return dev_hash_chunks(hash_alg, (const uint8_t *)d_src, src_bytes, d_offsets, d_nchunks, max_chunks, (uint8_t *)d_digests,
+                           (hipStream_t)stream);
+}
+
+// Pieces of at most kMaxChunkBytes: each piece is chunked with final = 0 (the last with final = 1); the bytes after the last
+// cut of a piece -- fewer than max_size -- are copied to the front of the next piece's buffer.
+int cw_cdc_hash(const cw_cdc_params *p, int hash_alg, const void *src, size_t nbytes, uint64_t *offsets, size_t max_offsets,
+                size_t *nchunks, void *digests)
+{
+    cw::CdcParams cp;
+    int rc = cdc_params(p, &cp);
+    if (rc != CW_OK) return rc;
+    if (hash_alg < 0 || hash_alg > CW_HASH_NONE) return fail(CW_ERR_BAD_ARG, "unknown hash algorithm %d", hash_alg);
+    if (!offsets || !nchunks || (nbytes && !src) || (hash_alg != CW_HASH_NONE && !digests)) return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    if (max_offsets < nbytes / cp.min_size + 2)
+        return fail(CW_ERR_BAD_ARG, "max_offsets %zu < nbytes / min_size + 2 = %zu", max_offsets, nbytes / cp.min_size + 2);
+    ThreadCtx *c;
+    if ((rc = thread_ctx(&c)) != CW_OK) return rc;
+    const hipStream_t s = c->stream;
+    const size_t piece = kMaxChunkBytes, dbytes = cw_digest_bytes(hash_alg);
+    const size_t cap = (piece + cp.max_size) / cp.min_size + 2; // offsets of one piece
+    if ((rc = c->src.reserve(piece + cp.max_size)) != CW_OK) return rc;
+    if ((rc = c->sizes.reserve(cap * 8 + 64)) != CW_OK) return rc;
+    if (hash_alg != CW_HASH_NONE && (rc = c->dig.reserve(cap * dbytes)) != CW_OK) return rc;
+    uint8_t *d_buf = (uint8_t *)c->src.p;
+    uint64_t *d_off = (uint64_t *)c->sizes.p, *d_k = d_off + cap;
+    size_t done = 0, carry = 0, k_total = 0; // done: stream bytes consumed; carry: bytes at the front of d_buf
+    offsets[0] = 0;
+    for (;;) {
+        const size_t take = nbytes - done - carry < piece ? nbytes - done - carry : piece;
+        const int fin = done + carry + take == nbytes;
+        HIP_TRY(hipMemcpyAsync(d_buf + carry, (const uint8_t *)src + done + carry, take, hipMemcpyHostToDevice, s));
+        const size_t len = carry + take;
+        if ((rc = dev_cdc(cp, d_buf, len, fin, d_off, cap, d_k, s)) != CW_OK) return rc;
+        if (hash_alg != CW_HASH_NONE && (rc = dev_hash_chunks(hash_alg, d_buf, len, d_off, d_k, cap, (uint8_t *)c->dig.p, s)) != CW_OK)
+            return rc;
+        uint64_t k = 0;
+        HIP_TRY(hipMemcpyAsync(&k, d_k, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (k_total + k + 1 > max_offsets) return fail(CW_ERR_BAD_ARG, "max_offsets %zu too small", max_offsets);
+        std::vector<uint64_t> h(k + 1);
+        HIP_TRY(hipMemcpyAsync(h.data(), d_off, (k + 1) * 8, hipMemcpyDeviceToHost, s));
+        if (hash_alg != CW_HASH_NONE && k)
+            HIP_TRY(hipMemcpyAsync((uint8_t *)digests + k_total * dbytes, c->dig.p, k * dbytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        for (uint64_t i = 1; i <= k; i++) offsets[k_total + i] = done + h[i];
+        k_total += k;
+        const size_t used = h[k];
+        if (fin) break;
+        // the tail after the last cut (< max_size bytes) moves to the front of the buffer
+        carry = len - used;
+        if (carry) HIP_TRY(hipMemcpyAsync(d_buf, d_buf + used, carry, hipMemcpyDeviceToDevice, s));
+        done += used;
+    }
+    *nchunks = k_total;
+    return CW_OK;
+}
+
+} // extern "C"
 
 // ---- dedupe index (kernels and protocol: dedupe_kernels.hip) -------------------------------------------------------
 struct cw_dedupe {

@@ -88,7 +88,7 @@ struct Knobs {
     // > 0
     int scan_wpc = 0, parse_wpc = 0, lanes_wpc = 0, lanes_reserve = 0, vtab_wpc = 0, lzf_st_wpc = 0, lzf_round = 0, lzf_lds_max = 0,
         skein_nslices = 0;
-    long host_chunk_mb = 0, host_big_chunk_mb = 0;
+    long host_chunk_mb = 0, host_big_chunk_mb = 0, cdc_segment = 0;
     bool force_redo = false, lzf_share_give_up = false; // CW_LZ_FORCE_REDO, CW_LZF_SHARE_GIVE_UP
     // set: atoi of the value ("" = 0)
     std::optional<int> lz4_lanes, lzf_lanes, decode_lanes, lanes_leave, vtab_min, vtab_max, vtab_reserve, lz4_vtab, lz4_lanes_ring,
@@ -162,6 +162,59 @@ hipError_t dedupe_scatter_launch(const uint32_t *flags, const uint64_t *off, uin
 // block new_idx[j] (src_stride apart in src) -> dst + j * block_bytes, for j < n_new
 hipError_t dedupe_gather_launch(const uint8_t *src, size_t block_bytes, size_t src_stride, const uint32_t *new_idx, size_t n_new,
                                 uint8_t *dst, hipStream_t s);
+// content-defined chunking (cdc_kernels.hip): gear = 256 entries in HOST memory (copied into the stream's workspace)
+struct CdcParams { uint32_t min_size, normal_size, max_size; uint64_t mask_s, mask_l; const uint64_t *gear; };
+// the resolve's segment: CW_CDC_SEGMENT bytes (>= max_size), by default 256 KiB rounded up to a multiple of max_size
+uint64_t cdc_segment_bytes(uint32_t max_size, long knob);
+size_t cdc_workspace_bytes(size_t nbytes, uint32_t min_size, uint64_t seg);
+// offsets[0..K] and *nchunks = K on the device; at most nbytes / min_size + 2 offsets are written
+hipError_t cdc_launch(const CdcParams &p, const uint8_t *src, size_t nbytes, int final_, uint64_t *offsets, size_t max_offsets,
+                      uint64_t *nchunks, uint64_t seg, hipStream_t stream);
+// orders the chunks i < min(*d_n, max_chunks) by (length >> step_shift), longest first, into a permutation in the stream's
+// workspace, and calls hash.fn(hash.ctx, perm) to queue the hash that reads it -- both under the workspace's launch lock
+struct ChunkHash { hipError_t (*fn)(void *ctx, const uint32_t *perm); void *ctx; };
+hipError_t chunk_hash_launch(const uint64_t *offsets, const uint64_t *d_n, size_t max_chunks, size_t src_bytes, unsigned step_shift,
+                             const ChunkHash &hash, hipStream_t stream);
+// digest of chunk perm[j] = [offsets[i], offsets[i + 1]) clamped to [0, src_bytes), for j < min(*d_n, max_chunks), at digests + i * digest_bytes
+hipError_t skein_chunks_launch(int state_words, const uint8_t *src, size_t src_bytes, const uint64_t *offsets, const uint32_t *perm,
+                               const uint64_t *d_n, size_t max_chunks, const SkeinIV &iv, uint8_t *digests, unsigned digest_bytes,
+                               hipStream_t stream);
+hipError_t sha256_chunks_launch(const uint8_t *src, size_t src_bytes, const uint64_t *offsets, const uint32_t *perm, const uint64_t *d_n,
+                                size_t max_chunks, uint8_t *digests, hipStream_t stream);
+void cdc_release_workspaces();
+void cdc_release_stream(hipStream_t stream);
+
+// Message bytes of a chunk that starts at any byte: the NG aligned 16-byte granules from a16, each clamped to `last` (the last
+// granule that holds a byte of the source), then shifted down by sh = 0..15 bytes with v_alignbyte_b32 -- 4 * (NG - 1) dwords.
+template <int NG>
+__device__ __forceinline__ void chunk_granules(uint32_t (&d)[4 * NG], const uint8_t *a16, const uint8_t *last)
+{
+#pragma unroll
+    for (int g = 0; g < NG; g++) {
+        const uint8_t *q = a16 + 16 * g;
+        const uint4 v = *reinterpret_cast<const uint4 *>(q < last ? q : last);
+        d[4 * g] = v.x; d[4 * g + 1] = v.y; d[4 * g + 2] = v.z; d[4 * g + 3] = v.w;
+    }
+}
+template <int NG>
+__device__ __forceinline__ void chunk_shift(uint32_t (&out)[4 * (NG - 1)], const uint32_t (&d)[4 * NG], unsigned sh)
+{
+    const unsigned ds = sh >> 2, bs = sh & 3;
+    uint32_t sel[4 * (NG - 1) + 1];
+#pragma unroll
+    for (int k = 0; k <= 4 * (NG - 1); k++) {
+        const uint32_t a0 = d[k], a1 = d[k + 1 < 4 * NG ? k + 1 : k], a2 = d[k + 2 < 4 * NG ? k + 2 : k], a3 = d[k + 3 < 4 * NG ? k + 3 : k];
+        sel[k] = ds == 0 ? a0 : ds == 1 ? a1 : ds == 2 ? a2 : a3;
+    }
+#pragma unroll
+    for (int k = 0; k < 4 * (NG - 1); k++) out[k] = __builtin_amdgcn_alignbyte(sel[k + 1], sel[k], bs);
+}
+// keeps the bytes of dword k (at source position pos + 4k) that lie before end
+__device__ __forceinline__ uint32_t chunk_keep(uint32_t v, int64_t valid)
+{
+    return valid >= 4 ? v : valid <= 0 ? 0u : v & ((1u << (8 * (unsigned)valid)) - 1u);
+}
+
 hipError_t sum_sizes_launch(const uint32_t *sizes, size_t n, uint32_t raw_bytes, uint64_t *totals, hipStream_t stream);
 hipError_t gen_random_launch(uint64_t seed, uint64_t first_block, size_t nblocks, size_t block_bytes, uint8_t *dst,
                              hipStream_t stream);

@@ -161,6 +161,79 @@ sha256_blocks_kernel(const uint8_t *__restrict__ src, size_t block_bytes, size_t
     }
 }
 
+// Variable-length chunks (cw_dev_hash_chunks): lane j hashes chunk perm[j], starting at any byte.  Each 64-byte step comes from
+// five aligned granules shifted by the chunk's misalignment; the bytes past the chunk, the 0x80 terminator and the length are
+// applied only on the steps that reach the chunk's end.
+__global__ void __launch_bounds__(CW_SKEIN_THREADS)
+sha256_chunks_kernel(const uint8_t *__restrict__ src, size_t src_bytes, const uint64_t *__restrict__ offsets, const uint32_t *__restrict__ perm,
+                     const uint64_t *__restrict__ d_n, size_t max_chunks, uint8_t *__restrict__ digests)
+{
+    const size_t k = *d_n < max_chunks ? *d_n : max_chunks;
+    const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= k) return;
+    const uint32_t ci = perm[gid];
+    uint64_t s = offsets[ci], e = offsets[ci + 1];
+    s = s < src_bytes ? s : src_bytes;
+    e = e < src_bytes ? e : src_bytes;
+    if (e < s) e = s;
+    const uint64_t len = e - s;
+    const size_t nsteps = len / 64 + 1 + ((len % 64) >= 56 ? 1 : 0);
+    const uint64_t bits = len * 8;
+    const unsigned sh = (unsigned)(reinterpret_cast<uintptr_t>(src + s) & 15);
+    const uint8_t *a0 = src + s - sh;
+    const uint8_t *last = reinterpret_cast<const uint8_t *>(reinterpret_cast<uintptr_t>(src + (e ? e - 1 : 0)) & ~(uintptr_t)15);
+
+    uint32_t h[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
+    auto message = [&](uint32_t (&w)[16], const uint32_t (&raw)[20], size_t st) __attribute__((always_inline)) {
+        uint32_t d[16];
+        chunk_shift<5>(d, raw, sh);
+        const int64_t left = (int64_t)len - (int64_t)(st * 64);
+        if (left < 64) {
+#pragma unroll
+            for (int j = 0; j < 16; j++) {
+                const int64_t v = left - 4 * j;
+                d[j] = chunk_keep(d[j], v) | (v >= 0 && v < 4 ? 0x80u << (8 * (unsigned)v) : 0u);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 16; j++) w[j] = __builtin_bswap32(d[j]);
+        if (st + 1 == nsteps) { w[14] = (uint32_t)(bits >> 32); w[15] = (uint32_t)bits; }
+    };
+    uint32_t raw[20], w[16];
+    if (src_bytes) chunk_granules<5>(raw, a0, last);
+    else {
+#pragma unroll
+        for (int j = 0; j < 20; j++) raw[j] = 0;
+    }
+    message(w, raw, 0);
+#pragma unroll 1
+    for (size_t st = 0; st < nsteps; st++) {
+        if (src_bytes) chunk_granules<5>(raw, a0 + (st + 1) * 64, last);
+        sha256_compress(h, w);
+        if (st + 1 < nsteps) message(w, raw, st + 1);
+    }
+
+    uint8_t *o = digests + (size_t)ci * 32;
+    if ((reinterpret_cast<uintptr_t>(o) & 15) == 0) {
+        uint4 *out = reinterpret_cast<uint4 *>(o);
+        out[0] = make_uint4(__builtin_bswap32(h[0]), __builtin_bswap32(h[1]), __builtin_bswap32(h[2]), __builtin_bswap32(h[3]));
+        out[1] = make_uint4(__builtin_bswap32(h[4]), __builtin_bswap32(h[5]), __builtin_bswap32(h[6]), __builtin_bswap32(h[7]));
+    } else {
+#pragma unroll
+        for (int j = 0; j < 32; j++) o[j] = (uint8_t)(h[j >> 2] >> (24 - 8 * (j & 3)));
+    }
+}
+
+hipError_t sha256_chunks_launch(const uint8_t *src, size_t src_bytes, const uint64_t *offsets, const uint32_t *perm, const uint64_t *d_n,
+                                size_t max_chunks, uint8_t *digests, hipStream_t stream)
+{
+    if (max_chunks == 0) return hipSuccess;
+    const dim3 grid((unsigned)((max_chunks + CW_SKEIN_THREADS - 1) / CW_SKEIN_THREADS)), block(CW_SKEIN_THREADS);
+    hipLaunchKernelGGL(sha256_chunks_kernel, grid, block, 0, stream, src, src_bytes, offsets, perm, d_n, max_chunks, digests);
+    note_kernels(1, "cw::sha256_chunks_kernel");
+    return hipGetLastError();
+}
+
 hipError_t sha256_launch(const uint8_t *src, size_t block_bytes, size_t src_stride, size_t nblocks, uint8_t *digests,
                          hipStream_t stream)
 {

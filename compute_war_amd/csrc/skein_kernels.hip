@@ -696,6 +696,98 @@ hipError_t skein256_launch(const uint8_t *src, size_t block_bytes, size_t src_st
     return launch_skein<4>(src, block_bytes, src_stride, nblocks, iv, digests, digest_bytes, stream, lean);
 }
 
+// ---- variable-length chunks (cw_dev_hash_chunks): lane j hashes chunk perm[j] of any length at any byte -----------------
+// The tweak words are per lane (each lane is at its own step kind); the message of a step comes from NW / 2 + 1 aligned
+// granules shifted by the chunk's misalignment (chunk_shift), so a chunk starting at any byte costs the same loads as an
+// aligned one.  The chunk sort orders lanes by step count, so the lanes of a wavefront leave the loop close together.
+template <int NW>
+__global__ void __launch_bounds__(CW_SKEIN_THREADS)
+skein_chunks_kernel(const uint8_t *__restrict__ src, size_t src_bytes, const uint64_t *__restrict__ offsets, const uint32_t *__restrict__ perm,
+                    const uint64_t *__restrict__ d_n, size_t max_chunks, SkeinIV iv, uint8_t *__restrict__ digests, unsigned digest_bytes)
+{
+    constexpr unsigned BB = NW * 8, NG = NW / 2 + 1;
+    const size_t k = *d_n < max_chunks ? *d_n : max_chunks;
+    const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= k) return;
+    const uint32_t ci = perm[gid];
+    uint64_t s = offsets[ci], e = offsets[ci + 1];
+    s = s < src_bytes ? s : src_bytes;
+    e = e < src_bytes ? e : src_bytes;
+    if (e < s) e = s;
+    const uint64_t len = e - s;
+    const uint64_t nfull = len ? (len - 1) / BB : 0;
+    const size_t nsteps = nfull + 2; // + Final() + output transform
+    const unsigned sh = (unsigned)(reinterpret_cast<uintptr_t>(src + s) & 15);
+    const uint8_t *a0 = src + s - sh;
+    const uint8_t *last = reinterpret_cast<const uint8_t *>(reinterpret_cast<uintptr_t>(src + (e ? e - 1 : 0)) & ~(uintptr_t)15);
+
+    uint64_t X[NW], w[NW];
+#pragma unroll
+    for (int i = 0; i < NW; i++) X[i] = iv.w[i];
+    // message words of step st: the bytes [s + st * BB, +BB) that lie before e, zero padded
+    auto message = [&](uint64_t (&dst)[NW], const uint32_t (&raw)[4 * NG], uint64_t st) __attribute__((always_inline)) {
+        uint32_t d[2 * NW];
+        chunk_shift<NG>(d, raw, sh);
+        const int64_t left = (int64_t)len - (int64_t)(st * BB);
+        if (left < (int64_t)BB) {
+#pragma unroll
+            for (int j = 0; j < 2 * NW; j++) d[j] = chunk_keep(d[j], left - 4 * j);
+        }
+#pragma unroll
+        for (int j = 0; j < NW; j++) dst[j] = (uint64_t)d[2 * j] | ((uint64_t)d[2 * j + 1] << 32);
+    };
+    uint32_t raw[4 * NG];
+    if (src_bytes) chunk_granules<NG>(raw, a0, last);
+    else {
+#pragma unroll
+        for (int j = 0; j < 4 * NG; j++) raw[j] = 0;
+    }
+    message(w, raw, 0);
+#pragma unroll 1
+    for (size_t st = 0; st < nsteps; st++) {
+        // the next step's granules go out before this step's rounds (the shift and mask run after them)
+        if (src_bytes) chunk_granules<NG>(raw, a0 + (st + 1) * BB, last);
+        uint64_t t0, t1;
+        if (st < nfull) { t0 = (st + 1) * BB; t1 = T1_MSG; }
+        else if (st == nfull) { t0 = len; t1 = T1_MSG | T1_FINAL; }
+        else { t0 = 8; t1 = T1_FIRST | T1_FINAL | T1_OUT; }
+        if (st == 0) t1 |= T1_FIRST;
+        Ubi<NW>::run(X, w, t0, t1);
+        if (st + 1 <= nfull) message(w, raw, st + 1);
+        else {
+#pragma unroll
+            for (int j = 0; j < NW; j++) w[j] = 0; // output block: counter 0
+        }
+    }
+
+    uint8_t *out = digests + (size_t)ci * digest_bytes;
+    if (((digest_bytes | (unsigned)reinterpret_cast<uintptr_t>(out)) & 15) == 0) {
+        uint4 *o4 = reinterpret_cast<uint4 *>(out);
+#pragma unroll
+        for (int j = 0; j < NW / 2; j++)
+            if ((unsigned)(16 * j) < digest_bytes)
+                o4[j] = make_uint4((uint32_t)X[2 * j], (uint32_t)(X[2 * j] >> 32), (uint32_t)X[2 * j + 1], (uint32_t)(X[2 * j + 1] >> 32));
+    } else {
+        for (unsigned j = 0; j < digest_bytes; j++) out[j] = (uint8_t)(X[j >> 3] >> (8 * (j & 7)));
+    }
+}
+
+hipError_t skein_chunks_launch(int nw, const uint8_t *src, size_t src_bytes, const uint64_t *offsets, const uint32_t *perm,
+                               const uint64_t *d_n, size_t max_chunks, const SkeinIV &iv, uint8_t *digests, unsigned digest_bytes,
+                               hipStream_t stream)
+{
+    if (max_chunks == 0) return hipSuccess;
+    const dim3 grid((unsigned)((max_chunks + CW_SKEIN_THREADS - 1) / CW_SKEIN_THREADS)), block(CW_SKEIN_THREADS);
+    if (nw == 8) {
+        hipLaunchKernelGGL((skein_chunks_kernel<8>), grid, block, 0, stream, src, src_bytes, offsets, perm, d_n, max_chunks, iv, digests, digest_bytes);
+        note_kernels(1, "cw::skein_chunks_kernel<8>");
+    } else {
+        hipLaunchKernelGGL((skein_chunks_kernel<4>), grid, block, 0, stream, src, src_bytes, offsets, perm, d_n, max_chunks, iv, digests, digest_bytes);
+        note_kernels(1, "cw::skein_chunks_kernel<4>");
+    }
+    return hipGetLastError();
+}
+
 // ---- host-side config-block UBI (Skein_*_Init's "no precomputed IV" path, skein.c:245-259) ----
 static uint64_t h_rotl(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
 

@@ -404,3 +404,67 @@ class HashOffload:
             self.close()
         except Exception:
             pass
+
+
+# ---- content-defined chunking (cw_cdc_*) --------------------------------------------------------
+class CdcParams(C.Structure):
+    """cw_cdc_params: min / normal / max chunk sizes, the two masks and an optional 256-entry gear table (None = default)."""
+    _fields_ = [("min_size", C.c_uint32), ("normal_size", C.c_uint32), ("max_size", C.c_uint32), ("reserved", C.c_uint32),
+                ("mask_s", C.c_uint64), ("mask_l", C.c_uint64), ("gear", C.POINTER(C.c_uint64))]
+
+    def __init__(self, min_size: int | None = None, normal_size: int = 8192, max_size: int | None = None, mask_s: int | None = None,
+                 mask_l: int | None = None, gear=None):
+        """A field left at None takes the value cw_cdc_default_params gives for normal_size: CdcParams() is the 8 KiB default."""
+        lg = normal_size.bit_length() - 1
+
+        def top(k):
+            return ((1 << 64) - 1) ^ ((1 << (64 - k)) - 1) if k > 0 else 0
+
+        super().__init__(normal_size // 4 if min_size is None else min_size, normal_size, normal_size * 8 if max_size is None else max_size,
+                         0, top(lg + 2) if mask_s is None else mask_s, top(lg - 2) if mask_l is None else mask_l, None)
+        self.set_gear(gear)
+
+    def set_gear(self, gear) -> None:
+        if gear is None:
+            self._gear = None
+            self.gear = C.POINTER(C.c_uint64)()
+        else:
+            self._gear = np.ascontiguousarray(np.asarray(gear, dtype=np.uint64).reshape(256))
+            self.gear = self._gear.ctypes.data_as(C.POINTER(C.c_uint64))
+
+    @classmethod
+    def default(cls, normal_size: int) -> "CdcParams":
+        p = cls()
+        lib().cw_cdc_default_params(C.byref(p), normal_size)
+        p._gear = None
+        return p
+
+    def max_offsets(self, nbytes: int) -> int:
+        return nbytes // self.min_size + 2
+
+
+def dev_cdc(params: CdcParams, d_src: int, nbytes: int, final: bool, d_offsets: int, max_offsets: int, d_nchunks: int,
+            stream: int = 0) -> None:
+    """Cuts of d_src[0..nbytes): d_offsets[0..K] (u64) and *d_nchunks = K, on the device, queued on `stream`."""
+    check(lib().cw_dev_cdc(C.byref(params), d_src, nbytes, 1 if final else 0, d_offsets, max_offsets, d_nchunks, stream))
+
+
+def dev_hash_chunks(hash_alg, d_src: int, src_bytes: int, d_offsets: int, d_nchunks: int, max_chunks: int, d_digests: int,
+                    stream: int = 0) -> None:
+    """Digest of every chunk [offsets[i], offsets[i+1]) for i < min(*d_nchunks, max_chunks), at d_digests + i * digest size."""
+    check(lib().cw_dev_hash_chunks(_hash_id(hash_alg), d_src, src_bytes, d_offsets, d_nchunks, max_chunks, d_digests, stream))
+
+
+def cdc_hash(params: CdcParams, data, hash_alg=None):
+    """Host form: (offsets u64 array of K + 1 cuts, digests as a (K, digest bytes) uint8 array, or None without hash_alg)."""
+    a = _np_u8(data)
+    hid = HASH_NONE if hash_alg is None else _hash_id(hash_alg)
+    cap = params.max_offsets(a.size)
+    offs = np.zeros(cap, dtype=np.uint64)
+    db = digest_bytes(hid) if hid != HASH_NONE else 0
+    dig = np.zeros((cap, max(db, 1)), dtype=np.uint8)
+    k = C.c_size_t(0)
+    check(lib().cw_cdc_hash(C.byref(params), hid, a.ctypes.data, a.size, offs.ctypes.data, cap, C.byref(k),
+                            dig.ctypes.data if db else None))
+    k = int(k.value)
+    return offs[:k + 1].copy(), (dig[:k, :db].copy() if db else None)

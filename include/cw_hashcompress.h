@@ -213,6 +213,53 @@ int cw_dev_hash_dedupe_compress(cw_dedupe_t *x, int comp_alg, const void *d_src,
                                 uint64_t *d_ref, uint32_t *d_new_idx, void *d_dst, size_t dst_stride,
                                 uint32_t *d_sizes, size_t *n_new, void *stream);
 
+/* ---- content-defined chunking ---------------------------------------------------------------
+ * Cuts a byte stream where its content says, so that an insertion or a deletion moves only the cuts near it and the
+ * chunks after it keep their digests (fixed blocks all shift).  Parameters m = min_size, a = normal_size, M = max_size,
+ * mask_s, mask_l, gear[256]; 64 <= m <= a <= M <= 2^24, else CW_ERR_BAD_ARG.
+ *   H(-1) = 0, H(i) = 2 H(i-1) + gear[b[i]] mod 2^64: the sum over k < 64 of gear[b[i-k]] << k, a function of the 64
+ *   bytes ending at i.  Cuts: c_0 = 0; from a cut c < n with r = n - c: r <= m -> the next cut is n; else with
+ *   e = c + min(M, r), z = c + min(a, r) the next cut is the smallest x in [c+m, z) with H(x-1) & mask_s == 0, else the
+ *   smallest x in [z, e) with H(x-1) & mask_l == 0, else e.
+ *   final = 0 (streaming): the chain stops at the first cut c with c + M > n, and c is the number of bytes consumed; pass
+ *   b[c..) plus the data that follows to the next call.  Because m >= 64, every test reads only bytes of its own chunk,
+ *   so pieces chunked this way give exactly the cuts of one final = 1 call over the whole stream.
+ * This is FastCDC's normalized chunking with one deliberate difference: FastCDC restarts its fingerprint at c + m for
+ * every chunk, so its first ~64 tests depend on where the chunk starts.  Here H runs over the stream and is never reset,
+ * so every position's candidate bits are computed in parallel with no knowledge of the cuts.                          */
+typedef struct cw_cdc_params {
+    uint32_t min_size, normal_size, max_size, reserved;   /* reserved = 0 */
+    uint64_t mask_s, mask_l;
+    const uint64_t *gear;                                 /* 256 entries in host memory; NULL = the default table */
+} cw_cdc_params;
+/* normal a power of two in [256, 2^21]: min = normal / 4, max = normal * 8, mask_s = the top log2(normal) + 2 bits,
+ * mask_l = the top log2(normal) - 2 bits, gear = NULL (gear[v] = splitmix64(v), the generator of cw_dev_gen_random).
+ * Another normal_size is clamped to [256, 2^21] and rounded down to a power of two.  Host only, needs no device.      */
+void cw_cdc_default_params(cw_cdc_params *p, uint32_t normal_size);
+/* d_offsets[0..K] = c_0..c_K and *d_nchunks = K (u64), device memory.  max_offsets >= nbytes / min_size + 2, checked on
+ * the host, so the device can never overflow.  final = 0: c_K = bytes consumed.  Queued on `stream`, not synchronised.
+ * Scratch: a workspace per stream in device memory (freed by cw_shutdown and when the library releases the stream),
+ * about nbytes / 4 for the candidate bitmaps plus 16 * nbytes / min_size for the cut lists of the resolve's segments
+ * (CW_CDC_SEGMENT bytes each, >= max_size; default 256 KiB rounded up to a multiple of max_size).  d_src may have any
+ * alignment; the scan loads the 16-byte-aligned granules that overlap d_src[0..nbytes), and no byte outside that range
+ * enters a result.                                                                                                   */
+int cw_dev_cdc(const cw_cdc_params *p, const void *d_src, size_t nbytes, int final,
+               uint64_t *d_offsets, size_t max_offsets, uint64_t *d_nchunks, void *stream);
+/* digest of every chunk [d_offsets[i], d_offsets[i+1]) for i < min(*d_nchunks, max_chunks), each the digest cw_dev_hash
+ * gives for that message (Skein-512-512, Skein-256-128, SHA-256), at d_digests + i * cw_digest_bytes(hash_alg).  The count
+ * is read on the DEVICE, so cdc -> hash_chunks -> (one synchronise) -> cw_dev_dedupe needs no host round trip in between.
+ * Offsets are clamped to [0, src_bytes] and a decreasing pair hashes as empty: only 16-byte-aligned granules that overlap
+ * d_src[0..src_bytes) are loaded, and no byte outside it enters a digest.  Digests past the count are not written.
+ * max_chunks <= 2^32 - 256.  Scratch: a per-stream workspace of 16 KiB + 4 * max_chunks bytes (the chunk order: chunks
+ * are hashed longest first so that the lanes of a wavefront finish together), freed like cw_dev_cdc's.               */
+int cw_dev_hash_chunks(int hash_alg, const void *d_src, size_t src_bytes, const uint64_t *d_offsets,
+                       const uint64_t *d_nchunks, size_t max_chunks, void *d_digests, void *stream);
+/* host buffers, synchronous: chunks (and hashes, unless hash_alg == CW_HASH_NONE) any nbytes through pieces of at most
+ * 256 MiB on the device, using the final = 0 contract between pieces; offsets[0..*nchunks] (max_offsets >= nbytes /
+ * min_size + 2), digests[*nchunks].  Uses the calling thread's staging buffers and the workspaces of its stream.      */
+int cw_cdc_hash(const cw_cdc_params *p, int hash_alg, const void *src, size_t nbytes,
+                uint64_t *offsets, size_t max_offsets, size_t *nchunks, void *digests);
+
 /* plain device memory on the calling thread's device, for C callers of cw_dev_* (the host programs link no HIP runtime) */
 void *cw_dev_alloc(size_t bytes);                                   /* NULL on failure */
 void  cw_dev_free(void *d_p);
