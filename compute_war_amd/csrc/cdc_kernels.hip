@@ -21,10 +21,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <mutex>
-#include <unordered_map>
-
 #include "cw_device.h"
+#include "stream_scratch.h"
 
 namespace cw {
 
@@ -495,28 +493,9 @@ chunk_scatter_kernel(const uint64_t *__restrict__ offsets, const uint64_t *__res
 }
 
 // ---- per-stream workspace -----------------------------------------------------------------------------------------------
-struct Workspace { void *p = nullptr; size_t cap = 0; std::mutex launch; };
-std::mutex ws_lock;
-std::unordered_map<uint64_t, Workspace> ws_map; // references stay valid across inserts
-std::unordered_map<uint64_t, Workspace> ws_sort;
-
-Workspace *workspace(std::unordered_map<uint64_t, Workspace> &map, hipStream_t stream)
-{
-    std::lock_guard<std::mutex> g(ws_lock);
-    return &map[ws_key(stream)];
-}
-
-hipError_t reserve(Workspace &w, size_t bytes)
-{
-    if (w.cap >= bytes) return hipSuccess;
-    if (w.p) { hipError_t e = hipFree(w.p); if (e != hipSuccess) return e; }
-    w.p = nullptr; w.cap = 0;
-    const size_t cap = bytes < ((size_t)1 << 20) ? ((size_t)1 << 20) : bytes;
-    hipError_t e = hipMalloc(&w.p, cap);
-    if (e != hipSuccess) return e;
-    w.cap = cap;
-    return hipSuccess;
-}
+// two registries: chunk_hash_launch holds its entry's launch lock while the hash it calls queues on the same stream
+StreamScratch<DeviceBuf> scan_space, sort_space;
+constexpr size_t kFloor = (size_t)1 << 20;
 
 size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
@@ -538,26 +517,6 @@ size_t cdc_workspace_bytes(size_t nbytes, uint32_t min_size, uint64_t seg)
            up256(2 * nseg * cap * 8 + 2 * nseg * 8 + (nseg + 63) / 64 * 8 + 3 * nseg * 4) + up256(nseg * 4) + up256((nseg + 1) * 8);
 }
 
-void cdc_release_workspaces()
-{
-    std::lock_guard<std::mutex> g(ws_lock);
-    for (auto *m : {&ws_map, &ws_sort}) {
-        for (auto &kv : *m) if (kv.second.p) (void)hipFree(kv.second.p);
-        m->clear();
-    }
-}
-
-void cdc_release_stream(hipStream_t stream)
-{
-    std::lock_guard<std::mutex> g(ws_lock);
-    for (auto *m : {&ws_map, &ws_sort}) {
-        auto it = m->find(ws_key(stream));
-        if (it == m->end()) continue;
-        if (it->second.p) (void)hipFree(it->second.p);
-        m->erase(it);
-    }
-}
-
 hipError_t cdc_launch(const CdcParams &p, const uint8_t *src, size_t nbytes, int final_, uint64_t *offsets, size_t max_offsets,
                       uint64_t *nchunks, uint64_t seg, hipStream_t stream)
 {
@@ -569,11 +528,11 @@ hipError_t cdc_launch(const CdcParams &p, const uint8_t *src, size_t nbytes, int
     const uint8_t *base = src - off;
     const uint64_t nv = nbytes + off, nwords = (nv + 63) / 64, n1 = (nwords + 63) / 64, n2 = (n1 + 63) / 64, n3 = (n2 + 63) / 64;
     const uint64_t nseg = nbytes / seg + 1, cap = seg / p.min_size + 2;
-    Workspace *wsp = workspace(ws_map, stream);
-    std::lock_guard<std::mutex> sequence(wsp->launch); // the scratch is shared by the launches below
-    hipError_t e = reserve(*wsp, cdc_workspace_bytes(nbytes, p.min_size, seg));
+    auto &space = scan_space.at(stream);
+    LaunchLock sequence(space.launch); // the scratch is shared by the launches below
+    hipError_t e = space.reserve(cdc_workspace_bytes(nbytes, p.min_size, seg), kFloor);
     if (e != hipSuccess) return e;
-    uint8_t *w = static_cast<uint8_t *>(wsp->p);
+    uint8_t *w = space.as<uint8_t>();
     auto take = [&](size_t bytes) { uint8_t *r = w; w += up256(bytes); return r; };
     uint64_t *gear = reinterpret_cast<uint64_t *>(take(2048));
     uint64_t *l0 = reinterpret_cast<uint64_t *>(take(2 * nwords * 8));
@@ -619,13 +578,13 @@ hipError_t cdc_launch(const CdcParams &p, const uint8_t *src, size_t nbytes, int
 hipError_t chunk_hash_launch(const uint64_t *offsets, const uint64_t *d_n, size_t max_chunks, size_t src_bytes, unsigned step_shift,
                              const ChunkHash &hash, hipStream_t stream)
 {
-    Workspace *wsp = workspace(ws_sort, stream);
+    auto &space = sort_space.at(stream);
     // the sort and the hash that reads its permutation are queued under one lock: another thread's call on the same stream
     // cannot rewrite (or reallocate) the permutation in between
-    std::lock_guard<std::mutex> sequence(wsp->launch);
-    hipError_t e = reserve(*wsp, kBuckets * 4 + max_chunks * 4);
+    LaunchLock sequence(space.launch);
+    hipError_t e = space.reserve(kBuckets * 4 + max_chunks * 4, kFloor);
     if (e != hipSuccess) return e;
-    uint32_t *hist = static_cast<uint32_t *>(wsp->p), *perm = hist + kBuckets;
+    uint32_t *hist = space.as<uint32_t>(), *perm = hist + kBuckets;
     e = hipMemsetAsync(hist, 0, kBuckets * 4, stream);
     if (e != hipSuccess) return e;
     const unsigned grid = (unsigned)umin((max_chunks + 255) / 256, 2048);

@@ -27,6 +27,7 @@
 
 #include "../../include/cw_hashcompress.h"
 #include "cw_device.h"
+#include "stream_scratch.h"
 
 namespace {
 
@@ -97,21 +98,16 @@ int ensure_init()
 }
 
 // ---- per-(thread, device) context ---------------------------------------------------------------------
-struct DevBuf {
+struct DevBuf { // cw::DeviceBuf with a floor of 1 MiB and the library's error codes; p = the buffer, for the many places that pass it on
+    cw::DeviceBuf buf;
     void *p = nullptr;
-    size_t cap = 0;
     int reserve(size_t n)
     {
-        if (n <= cap) return CW_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        size_t want = n < (1u << 20) ? (1u << 20) : n;
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) return fail(CW_ERR_NOMEM, "hipMalloc(%zu): %s", want, hipGetErrorString(e));
-        cap = want;
-        return CW_OK;
+        const hipError_t e = buf.reserve(n, (size_t)1 << 20);
+        p = buf.as<void>();
+        return e == hipSuccess ? CW_OK : fail(CW_ERR_NOMEM, "hipMalloc(%zu): %s", n < (1u << 20) ? (size_t)1 << 20 : n, hipGetErrorString(e));
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    void release() { (void)buf.release(); p = nullptr; }
 };
 struct PinnedBuf { // page-locked host staging: the only kind of host memory a copy engine reads or writes at bus speed
     void *p = nullptr;
@@ -135,25 +131,21 @@ constexpr int kSlots = 3;
 struct Slot {
     DevBuf src, dst, pack, sizes, offs, dig;
     PinnedBuf h_src, h_meta, h_pack;
-    hipStream_t stream = nullptr, side = nullptr; // this chunk's kernels: codec on `stream`, hash beside it on `side`
-    hipEvent_t fork = nullptr, join = nullptr;
+    hipStream_t stream = nullptr; // this chunk's kernels: codec on `stream`, hash beside it on `side`
+    cw::SideStream side;
     hipEvent_t ev_h2d = nullptr, ev_meta = nullptr, ev_payload = nullptr;
     size_t first = 0, n = 0;
     uint64_t total = 0;
-    bool borrowed = false; // stream and side belong to the thread's first slot (CW_HOST_SHARED_STREAMS)
+    bool borrowed = false; // stream and side's stream belong to the thread's first slot (CW_HOST_SHARED_STREAMS)
     int open(const Slot *lender = nullptr)
     {
         if (ev_h2d) return CW_OK;
-        int least = 0, greatest = 0;
-        HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
         if (lender && lender->stream) {
-            stream = lender->stream; side = lender->side; borrowed = true;
+            stream = lender->stream; borrowed = true;
         } else {
             HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-            HIP_TRY(hipStreamCreateWithPriority(&side, hipStreamNonBlocking, least));
         }
-        HIP_TRY(hipEventCreateWithFlags(&fork, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&join, hipEventDisableTiming));
+        HIP_TRY(side.open(cw::SideStream::least, borrowed ? lender->side.stream : nullptr));
         HIP_TRY(hipEventCreateWithFlags(&ev_meta, hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&ev_payload, hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&ev_h2d, hipEventDisableTiming));
@@ -164,14 +156,13 @@ struct Slot {
         src.release(); dst.release(); pack.release(); sizes.release(); offs.release(); dig.release();
         h_src.release(); h_meta.release(); h_pack.release();
         if (stream && !borrowed) { cw::release_stream_workspaces(stream); (void)hipStreamDestroy(stream); }
-        if (side && !borrowed) { cw::release_stream_workspaces(side); (void)hipStreamDestroy(side); }
+        if (side.stream && !side.borrowed) cw::release_stream_workspaces(side.stream);
+        side.release();
         borrowed = false;
-        if (fork) (void)hipEventDestroy(fork);
-        if (join) (void)hipEventDestroy(join);
         if (ev_meta) (void)hipEventDestroy(ev_meta);
         if (ev_payload) (void)hipEventDestroy(ev_payload);
         if (ev_h2d) (void)hipEventDestroy(ev_h2d);
-        stream = side = nullptr; fork = join = ev_meta = ev_payload = ev_h2d = nullptr;
+        stream = nullptr; ev_meta = ev_payload = ev_h2d = nullptr;
     }
 };
 
@@ -185,8 +176,7 @@ struct ThreadCtx {
     hipStream_t stream = nullptr;            // kernels of the host-buffer entry points
     hipStream_t s_h2d = nullptr, s_d2h = nullptr; // the two copy directions of the pipelined batch path
     // fork/join for the fused call: the hash runs on `side` beside the codec on the caller's stream
-    hipStream_t side = nullptr;
-    hipEvent_t fork = nullptr, join = nullptr;
+    cw::SideStream side;
     DevBuf src, dst, dig, sizes;             // unpipelined helpers (decompress, tree hash)
     Slot slot[kSlots];
     int open(int dev)
@@ -197,11 +187,7 @@ struct ThreadCtx {
         HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         HIP_TRY(hipStreamCreateWithFlags(&s_h2d, hipStreamNonBlocking));
         HIP_TRY(hipStreamCreateWithFlags(&s_d2h, hipStreamNonBlocking));
-        int least = 0, greatest = 0; // the hash is the long, ALU-bound kernel: it yields dispatch slots to the codec
-        HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIP_TRY(hipStreamCreateWithPriority(&side, hipStreamNonBlocking, least));
-        HIP_TRY(hipEventCreateWithFlags(&fork, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&join, hipEventDisableTiming));
+        HIP_TRY(side.open(cw::SideStream::least)); // the hash is the long, ALU-bound kernel: it yields dispatch slots to the codec
         return CW_OK;
     }
     ~ThreadCtx()
@@ -210,11 +196,11 @@ struct ThreadCtx {
         (void)hipSetDevice(device);
         src.release(); dst.release(); dig.release(); sizes.release();
         for (Slot &s : slot) s.release();
-        (void)hipEventDestroy(fork); (void)hipEventDestroy(join);
         if (hint.ev) (void)hipEventDestroy(hint.ev);
         if (hint.h_queued) (void)hipHostFree(hint.h_queued);
-        cw::release_stream_workspaces(side); cw::release_stream_workspaces(stream);
-        (void)hipStreamDestroy(side); (void)hipStreamDestroy(s_h2d); (void)hipStreamDestroy(s_d2h); (void)hipStreamDestroy(stream);
+        cw::release_stream_workspaces(side.stream); cw::release_stream_workspaces(stream);
+        side.release();
+        (void)hipStreamDestroy(s_h2d); (void)hipStreamDestroy(s_d2h); (void)hipStreamDestroy(stream);
     }
 };
 struct ThreadCtxSet { std::unique_ptr<ThreadCtx> of[kMaxDevices]; };
@@ -375,11 +361,12 @@ cw::Knobs cw::knobs()
 void cw::release_stream_workspaces(hipStream_t stream)
 {
     (void)hipStreamSynchronize(stream); // nothing of the stream's may still use what is freed here
-    cw::lz4_release_stream(stream);
-    cw::lzf_release_stream(stream);
-    cw::pack_release_stream(stream);
-    cw::skein_release_stream(stream);
-    cw::cdc_release_stream(stream);
+    for (cw::ScratchRegistry *r = cw::ScratchRegistry::head(); r; r = r->next) r->release(stream);
+}
+
+void cw::release_all_workspaces()
+{
+    for (cw::ScratchRegistry *r = cw::ScratchRegistry::head(); r; r = r->next) r->release_all();
 }
 
 void cw::note_kernels(int kind, const char *names)
@@ -454,11 +441,7 @@ void cw_shutdown(void)
             (void)hipSetDevice(d);
             (void)hipDeviceSynchronize();
         }
-    cw::skein_release_workspaces();
-    cw::lz4_release_workspaces();
-    cw::lzf_release_workspaces();
-    cw::pack_release_workspaces();
-    cw::cdc_release_workspaces();
+    cw::release_all_workspaces();
     g_mask.store(0);
     g_default.store(-1);
     t_device = -1;
@@ -519,7 +502,7 @@ int cw_dev_compress(int comp_alg, const void *d_src, size_t block_bytes, size_t 
 // side: the codec (latency/memory bound, few issue slots, persistent grid) goes first on the caller's stream so its
 // workgroups are resident before the hash (pure integer VALU, one long-lived wavefront per 64 blocks) fills the rest of
 // every CU from the context's low-priority side stream; the side stream is joined before the call's work counts as done.
-static int dev_fused(hipStream_t side, hipEvent_t fork, hipEvent_t join, int hash_alg, int comp_alg, const uint8_t *d_src, size_t block_bytes, size_t src_stride, size_t nblocks,
+static int dev_fused(cw::SideStream &side_s, int hash_alg, int comp_alg, const uint8_t *d_src, size_t block_bytes, size_t src_stride, size_t nblocks,
                      uint8_t *d_digests, uint8_t *d_dst, size_t dst_stride, uint32_t *d_sizes, hipStream_t main_s)
 {
     int rc;
@@ -528,8 +511,9 @@ static int dev_fused(hipStream_t side, hipEvent_t fork, hipEvent_t join, int has
         rc = dev_compress(comp_alg, d_src, block_bytes, src_stride, nblocks, d_dst, dst_stride, d_sizes, main_s);
         return rc == CW_OK ? dev_hash(hash_alg, d_src, block_bytes, src_stride, nblocks, d_digests, main_s, false, true) : rc;
     }
-    HIP_TRY(hipEventRecord(fork, main_s));
-    HIP_TRY(hipStreamWaitEvent(side, fork, 0));
+    cw::SideStream::Fork fork(side_s, main_s); // (a return before the join below still joins)
+    HIP_TRY(fork.err);
+    const hipStream_t side = side_s.stream;
     // Side by side pays when the codec is light -- incompressible input, where it is the scan alone (the headline: 61.7 ms against 72.9 one after
     // the other).  On compressible input the parsers fill every CU with wavefronts that stay until the queue is empty; a hash kernel that arrives
     // beside them trickles in behind, ends with the call and costs the parsers more than it takes alone (Skein-256 over 1 Mi blocks of 4 KiB:
@@ -540,30 +524,31 @@ static int dev_fused(hipStream_t side, hipEvent_t fork, hipEvent_t join, int has
     // Skein-256 + LZ4, 1 Mi blocks of 4 KiB 93.3 / 104.2 ms, SHA-256 + LZ4 92.2 / 101.6, 51,728 blocks 7.15 / 7.55; blocks of 64 KiB, where the
     // scalar-thread parsers leave the vector ALUs to the hash: 64 Ki blocks 94.8 / 91.1 ms, the mix 43.4 / 42.2, 256 Ki blocks 370.6 / 372.0 -- so
     // those stay side by side.  (Always gating costs the headline 2.7 ms: its empty-queue parser and redo launches then run behind the hash.)
-    struct Gate { int hash_alg; const uint8_t *src; size_t bb, stride, n; uint8_t *dig; hipStream_t side, main_s; hipEvent_t join; int rc; bool called; };
-    Gate gate = {hash_alg, d_src, block_bytes, src_stride, nblocks, d_digests, side, main_s, join, CW_OK, false};
+    struct Gate { int hash_alg; const uint8_t *src; size_t bb, stride, n; uint8_t *dig; hipStream_t side; cw::SideStream::Fork *fork; int rc; bool called; };
+    Gate gate = {hash_alg, d_src, block_bytes, src_stride, nblocks, d_digests, side, &fork, CW_OK, false};
     const cw::AfterScan hook = {[](void *p) -> hipError_t {
                                     Gate *g = static_cast<Gate *>(p);
                                     g->called = true;
                                     g->rc = dev_hash(g->hash_alg, g->src, g->bb, g->stride, g->n, g->dig, g->side, false, true);
-                                    if (g->rc != CW_OK) return hipErrorUnknown;
-                                    hipError_t e = hipEventRecord(g->join, g->side);
-                                    return e == hipSuccess ? hipStreamWaitEvent(g->main_s, g->join, 0) : e;
+                                    return g->rc != CW_OK ? hipErrorUnknown : g->fork->join();
                                 }, &gate};
     ThreadCtx *tc = nullptr;
     FusedHint *hint = comp_alg == CW_COMP_LZ4 && thread_ctx(&tc) == CW_OK ? &tc->hint : nullptr;
-    if (hint && hint->pending && hipEventQuery(hint->ev) == hipSuccess) {
-        hint->pending = false;
-        if (hint->blocks_of_copy) hint->queued_share = (float)*hint->h_queued / (float)hint->blocks_of_copy;
+    if (hint && hint->pending) {
+        const hipError_t q = hipEventQuery(hint->ev);
+        if (q == hipSuccess) {
+            hint->pending = false;
+            if (hint->blocks_of_copy) hint->queued_share = (float)*hint->h_queued / (float)hint->blocks_of_copy;
+        } else if (q == hipErrorNotReady) {
+            (void)hipGetLastError(); // (not an error; any other pending error stays for whoever asks next)
+        }
     }
-    (void)hipGetLastError(); // (hipErrorNotReady of the query is not an error)
     // CW_FUSED_GATE: 0 = never, 1 = always (profiling knob)
     const bool gated = hint && (kn.fused_gate ? *kn.fused_gate : block_bytes <= 4096 && nblocks >= 16384 && hint->queued_share >= 0.25f);
     rc = dev_compress(comp_alg, d_src, block_bytes, src_stride, nblocks, d_dst, dst_stride, d_sizes, main_s, gated ? &hook : nullptr);
     if (gate.called && gate.rc != CW_OK) return gate.rc;
     if (rc == CW_OK && !gate.called) rc = dev_hash(hash_alg, d_src, block_bytes, src_stride, nblocks, d_digests, side, false, true);
-    HIP_TRY(hipEventRecord(join, side));
-    HIP_TRY(hipStreamWaitEvent(main_s, join, 0));
+    HIP_TRY(fork.join());
     if (rc == CW_OK && hint && !hint->pending) { // this call's queued share, for the next call
         const uint32_t *word = cw::lz4_queued_blocks_word(main_s);
         if (word) {
@@ -591,7 +576,7 @@ int cw_dev_hash_and_compress(int hash_alg, int comp_alg, const void *d_src, size
     if (!d_src || !d_dst || !d_sizes || !d_digests) return fail(CW_ERR_BAD_ARG, "NULL device pointer");
     if ((rc = check_block(block_bytes)) != CW_OK) return rc;
     if (src_stride < block_bytes) return fail(CW_ERR_BAD_ARG, "src_stride < block_bytes");
-    return dev_fused(c->side, c->fork, c->join, hash_alg, comp_alg, (const uint8_t *)d_src, block_bytes, src_stride, nblocks, (uint8_t *)d_digests, (uint8_t *)d_dst,
+    return dev_fused(c->side, hash_alg, comp_alg, (const uint8_t *)d_src, block_bytes, src_stride, nblocks, (uint8_t *)d_digests, (uint8_t *)d_dst,
                      dst_stride, d_sizes, (hipStream_t)stream);
 }
 
@@ -808,7 +793,7 @@ int pipe_issue(const cw::Knobs &kn, ThreadCtx &c, HostJob &j, Slot &s, size_t fi
     HIP_TRY(hipStreamWaitEvent(s.stream, s.ev_h2d, 0));
     uint8_t *meta = (uint8_t *)s.h_meta.p;
     if (j.do_comp && j.do_hash)
-        rc = dev_fused(s.side, s.fork, s.join, j.hash_alg, j.comp_alg, (const uint8_t *)s.src.p, j.bb, j.bb, n, (uint8_t *)s.dig.p, (uint8_t *)s.dst.p,
+        rc = dev_fused(s.side, j.hash_alg, j.comp_alg, (const uint8_t *)s.src.p, j.bb, j.bb, n, (uint8_t *)s.dig.p, (uint8_t *)s.dst.p,
                        j.d_stride, (uint32_t *)s.sizes.p, s.stream);
     else if (j.do_comp)
         rc = dev_compress(j.comp_alg, (const uint8_t *)s.src.p, j.bb, j.bb, n, (uint8_t *)s.dst.p, j.d_stride, (uint32_t *)s.sizes.p, s.stream);
@@ -880,7 +865,7 @@ int pipe_finish(HostJob &j, Slot &s)
 void pipe_drain(ThreadCtx &c)
 {
     (void)hipStreamSynchronize(c.s_h2d);
-    for (Slot &s : c.slot) { if (s.stream) { (void)hipStreamSynchronize(s.stream); (void)hipStreamSynchronize(s.side); } }
+    for (Slot &s : c.slot) { if (s.stream) { (void)hipStreamSynchronize(s.stream); (void)hipStreamSynchronize(s.side.stream); } }
     (void)hipStreamSynchronize(c.s_d2h);
 }
 
@@ -941,7 +926,7 @@ size_t grown_chunk(const cw::Knobs &kn, const HostJob &j, size_t chunk, bool pin
 // (many host threads on one device each run a pipeline of their own)
 bool room_to_grow(const ThreadCtx &c, const HostJob &j, size_t big)
 {
-    if (c.slot[0].src.cap >= big * j.bb && c.slot[kSlots - 1].src.cap >= big * j.bb) return true; // grown before
+    if (c.slot[0].src.buf.bytes() >= big * j.bb && c.slot[kSlots - 1].src.buf.bytes() >= big * j.bb) return true; // grown before
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return false; }
     // + the lane parsers' tables on each slot stream (LZ4 4 GiB, LZF 8 GiB at most; lz4_kernel.hip / lzf_kernel.hip allocate them on the first
@@ -1066,7 +1051,7 @@ int cw_prepare(int hash_alg, int comp_alg, size_t block_bytes, size_t nblocks, i
     if (kn.prepare_cold) return CW_OK;
     for (Slot &s : c->slot) { // the same predicates as pipe_issue: a hash-only job has no slots, sizes or packed stream to touch
         if (j.do_comp && j.do_hash)
-            rc = dev_fused(s.side, s.fork, s.join, hash_alg, comp_alg, (const uint8_t *)s.src.p, block_bytes, block_bytes, chunk, (uint8_t *)s.dig.p,
+            rc = dev_fused(s.side, hash_alg, comp_alg, (const uint8_t *)s.src.p, block_bytes, block_bytes, chunk, (uint8_t *)s.dig.p,
                            (uint8_t *)s.dst.p, j.d_stride, (uint32_t *)s.sizes.p, s.stream);
         else if (j.do_comp)
             rc = dev_compress(comp_alg, (const uint8_t *)s.src.p, block_bytes, block_bytes, chunk, (uint8_t *)s.dst.p, j.d_stride, (uint32_t *)s.sizes.p, s.stream);
@@ -1464,7 +1449,7 @@ int dedupe_enqueue(cw_dedupe *x, const uint64_t *dig, uint32_t n, uint64_t base,
                    hipStream_t s)
 {
     int rc;
-    if (x->rec.cap < (size_t)n * 8 || x->offs.cap < ((size_t)n + 1) * 8) // growing frees scratch the last call may still use
+    if (x->rec.buf.bytes() < (size_t)n * 8 || x->offs.buf.bytes() < ((size_t)n + 1) * 8) // growing frees scratch the last call may still use
         HIP_TRY(hipEventSynchronize(x->last));
     if ((rc = x->rec.reserve((size_t)n * 8)) != CW_OK || (rc = x->flags.reserve((size_t)n * 4)) != CW_OK ||
         (rc = x->offs.reserve(((size_t)n + 1) * 8)) != CW_OK)

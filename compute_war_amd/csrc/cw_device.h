@@ -48,17 +48,6 @@ hipError_t lz4_clock_read(unsigned long long *out);
 #define CW_CLOCK_SCOPE_KEYED(buf, key) do { } while (0)
 #endif
 
-// Key of the per-(device, stream) scratch the launch sequences keep (the NULL stream exists once per device).  Every
-// entry also holds a launch mutex: a sequence of launches that shares scratch -- memset counters, scan, parse, redo; the
-// chained slices of one hash -- is queued under it, so that two host threads using the same stream cannot interleave
-// their sequences (stream order then keeps each sequence atomic).
-static inline uint64_t ws_key(hipStream_t s)
-{
-    int d = 0;
-    (void)hipGetDevice(&d);
-    return ((uint64_t)reinterpret_cast<uintptr_t>(s) << 4) | (uint64_t)(d & 15);
-}
-
 struct SkeinIV { uint64_t w[8]; };
 
 // The launch functions note which kernels they used, per calling thread (kind 0 = codec, 1 = hash): cw_profile_kernels
@@ -139,18 +128,12 @@ hipError_t decompress_launch(int alg, const uint8_t *comp, size_t comp_stride, c
 // packed stream: offsets[i] = sum sizes[0..i) (nblocks + 1 entries); slot i copied to packed + offsets[i] (packed may be NULL)
 hipError_t pack_launch(const uint8_t *slots, size_t slot_stride, const uint32_t *sizes, size_t nblocks, uint8_t *packed,
                        uint64_t *offsets, hipStream_t stream);
-// per-stream scratch of the codec / pack launches (queues, link arrays, scan partials): freed by cw_shutdown
-void skein_release_workspaces();
-void lz4_release_workspaces();
-void lzf_release_workspaces();
-void pack_release_workspaces();
-// the same for ONE stream of the current device: called by whoever owns the stream before destroying it, so that a short-lived
-// calling thread does not leave gigabytes of lane tables behind and a recycled stream handle does not inherit a stale entry
+// Per-stream scratch of the launch sequences (queues, link arrays, scan partials, side streams: stream_scratch.h), in every
+// registry of the library.  For ONE stream of the current device: called by whoever owns the stream before destroying it, so
+// that a short-lived calling thread does not leave gigabytes of lane tables behind and a recycled stream handle does not
+// inherit a stale entry.  All of it: cw_shutdown.
 void release_stream_workspaces(hipStream_t stream);
-void skein_release_stream(hipStream_t stream);
-void lz4_release_stream(hipStream_t stream);
-void lzf_release_stream(hipStream_t stream);
-void pack_release_stream(hipStream_t stream);
+void release_all_workspaces();
 // fingerprint index (dedupe_kernels.hip): words = u64 words per digest (2 / 4 / 8); mask = slots - 1; rec / flags = per-block
 // scratch of the call; off = exclusive scan of flags (pack_launch, index only); err |= 1 if a probe reached the bound
 hipError_t dedupe_probe_launch(unsigned words, const uint64_t *dig, uint32_t n, uint64_t *state, uint32_t *min_idx, const uint64_t *value,
@@ -181,8 +164,6 @@ hipError_t skein_chunks_launch(int state_words, const uint8_t *src, size_t src_b
                                hipStream_t stream);
 hipError_t sha256_chunks_launch(const uint8_t *src, size_t src_bytes, const uint64_t *offsets, const uint32_t *perm, const uint64_t *d_n,
                                 size_t max_chunks, uint8_t *digests, hipStream_t stream);
-void cdc_release_workspaces();
-void cdc_release_stream(hipStream_t stream);
 
 // Message bytes of a chunk that starts at any byte: the NG aligned 16-byte granules from a16, each clamped to `last` (the last
 // granule that holds a byte of the source), then shifted down by sh = 0..15 bytes with v_alignbyte_b32 -- 4 * (NG - 1) dwords.

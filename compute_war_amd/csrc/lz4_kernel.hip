@@ -39,12 +39,11 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <mutex>
 #include <type_traits>
-#include <unordered_map>
 
 #include "cw_device.h"
 #include "lz_device.h"
+#include "stream_scratch.h"
 
 #ifndef HEADW_GLOBAL
 #define HEADW_GLOBAL 16
@@ -2152,69 +2151,20 @@ lz4_lanes_ring_auto_kernel(const uint8_t *__restrict__ src, uint32_t n, size_t s
 // per-stream workspace: counters[8] (parse queue head, tail; scan feed; -; second queue head, tail) + two queues
 namespace {
 struct Workspace {
-    uint32_t *p = nullptr; size_t cap = 0;
-    uint16_t *lane_tabs = nullptr; size_t lane_cap = 0; // tables of the lane-per-block parser: 16 KiB per lane
-    hipStream_t side = nullptr; hipEvent_t fork = nullptr, join = nullptr; // the lane parser's stream beside the caller's
-    hipStream_t side2 = nullptr; hipEvent_t fork2 = nullptr, join2 = nullptr; // the register-table parser's
-    std::mutex launch;
+    DeviceBuf queues;    // counters[8] + two queues of as many entries as the largest call had blocks (at least 4096)
+    DeviceBuf lane_tabs; // tables of the lane-per-block parser: 16 KiB per lane
+    SideStream lanes;    // the lane parser's stream beside the caller's
+    SideStream vtab;     // the register-table parser's
+    void release() { (void)queues.release(); (void)lane_tabs.release(); lanes.release(); vtab.release(); }
 };
-std::mutex ws_lock;
-std::unordered_map<uint64_t, Workspace> ws_map; // references stay valid across inserts
-
-Workspace &find_workspace(hipStream_t stream)
-{
-    std::lock_guard<std::mutex> g(ws_lock);
-    return ws_map[ws_key(stream)];
-}
-
-// caller holds w.launch
-hipError_t grow_workspace(Workspace &w, size_t nblocks, uint32_t **out, size_t *cap_out)
-{
-    if (w.cap < nblocks) { // only ever on the first (or a larger) call on this stream
-        if (w.p) { hipError_t e = hipFree(w.p); if (e != hipSuccess) return e; }
-        w.p = nullptr; w.cap = 0;
-        size_t cap = nblocks < 4096 ? 4096 : nblocks;
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&w.p), (2 * cap + 8) * sizeof(uint32_t));
-        if (e != hipSuccess) return e;
-        w.cap = cap;
-    }
-    *out = w.p;
-    *cap_out = w.cap;
-    return hipSuccess;
-}
+StreamScratch<Workspace> workspaces;
 } // namespace
 
 // device address of the word that holds the number of blocks the last call's scan queued for the parsers on this stream (nullptr: no call yet)
 const uint32_t *lz4_queued_blocks_word(hipStream_t stream)
 {
-    std::lock_guard<std::mutex> g(ws_lock);
-    auto it = ws_map.find(ws_key(stream));
-    return it == ws_map.end() || !it->second.p ? nullptr : it->second.p + 1;
-}
-
-void lz4_release_workspaces()
-{
-    std::lock_guard<std::mutex> g(ws_lock);
-    for (auto &kv : ws_map) {
-        if (kv.second.p) (void)hipFree(kv.second.p);
-        if (kv.second.lane_tabs) (void)hipFree(kv.second.lane_tabs);
-        if (kv.second.side) { (void)hipStreamDestroy(kv.second.side); (void)hipEventDestroy(kv.second.fork); (void)hipEventDestroy(kv.second.join); }
-        if (kv.second.side2) { (void)hipStreamDestroy(kv.second.side2); (void)hipEventDestroy(kv.second.fork2); (void)hipEventDestroy(kv.second.join2); }
-    }
-    ws_map.clear();
-}
-
-void lz4_release_stream(hipStream_t stream)
-{
-    std::lock_guard<std::mutex> g(ws_lock);
-    auto it = ws_map.find(ws_key(stream));
-    if (it == ws_map.end()) return;
-    Workspace &w = it->second;
-    if (w.p) (void)hipFree(w.p);
-    if (w.lane_tabs) (void)hipFree(w.lane_tabs);
-    if (w.side) { (void)hipStreamDestroy(w.side); (void)hipEventDestroy(w.fork); (void)hipEventDestroy(w.join); }
-    if (w.side2) { (void)hipStreamDestroy(w.side2); (void)hipEventDestroy(w.fork2); (void)hipEventDestroy(w.join2); }
-    ws_map.erase(it);
+    const auto *w = workspaces.find(stream);
+    return !w || !w->queues.bytes() ? nullptr : w->queues.as<uint32_t>() + 1;
 }
 
 hipError_t lz4_launch(const uint8_t *src, size_t block_bytes, size_t src_stride, size_t nblocks, uint8_t *dst,
@@ -2240,13 +2190,15 @@ hipError_t lz4_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
         if (e != hipSuccess) return e;
         attr_set = true;
     }
-    uint32_t *ws = nullptr;
-    size_t cap = 0;
-    Workspace &wsp = find_workspace(stream);
-    std::lock_guard<std::mutex> sequence(wsp.launch); // counters/queues are shared by every launch below
-    hipError_t e = grow_workspace(wsp, nblocks, &ws, &cap);
+    auto &wsp = workspaces.at(stream);
+    LaunchLock sequence(wsp.launch); // counters/queues are shared by every launch below
+    // (only ever allocates on the first, or a larger, call on this stream)
+    hipError_t e = wsp.queues.reserve((2 * nblocks + 8) * sizeof(uint32_t), (2 * 4096 + 8) * sizeof(uint32_t));
     if (e != hipSuccess) return e;
-    uint32_t *counters = ws, *queue = ws + 8, *queue2 = ws + 8 + cap;
+    const size_t cap = (wsp.queues.bytes() / sizeof(uint32_t) - 8) / 2;
+    uint32_t *counters = wsp.queues.as<uint32_t>(), *queue = counters + 8, *queue2 = queue + cap;
+    // the forks onto the two side streams: a return before the joins below still joins them (lanes last, as below)
+    std::optional<SideStream::Fork> lanes_fork, vtab_fork;
     // what this call launches, noted in the branch that launches it (cw_profile_kernels): names as rocprofv3 prints them; a kernel that
     // decides on the device whether the queue's length is in its range carries the range
     char launched[320] = "";
@@ -2371,39 +2323,24 @@ hipError_t lz4_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
             const size_t want = nblocks > leave + 4096 ? (nblocks - leave + 63) / 64 : 64;
             if (nblocks < kLaneWideBlocks && lgrid > want) lgrid = want;
         }
-        if (wsp.lane_cap < lgrid * 64) {
-            if (wsp.lane_tabs) { e = hipFree(wsp.lane_tabs); if (e != hipSuccess) return e; }
-            wsp.lane_tabs = nullptr; wsp.lane_cap = 0;
-            e = hipMalloc(reinterpret_cast<void **>(&wsp.lane_tabs), lgrid * 64 * (size_t)kTabBytes * 2); // (entries of 4 bytes for blocks > 4 KiB)
-            if (e != hipSuccess) { // up to 4 GiB: a nearly full device does without the lanes instead of failing the call
-                (void)hipGetLastError();
-                wsp.lane_tabs = nullptr;
-                lgrid = 0;
-            } else {
-                wsp.lane_cap = lgrid * 64;
-            }
+        // (entries of 4 bytes for blocks > 4 KiB); up to 4 GiB: a nearly full device does without the lanes instead of failing the call
+        if (wsp.lane_tabs.reserve(lgrid * 64 * (size_t)kTabBytes * 2) != hipSuccess) {
+            (void)hipGetLastError();
+            lgrid = 0;
         }
+        uint16_t *const lane_tabs = wsp.lane_tabs.as<uint16_t>();
         if (lgrid) {
         lanes_beside = lanes_concurrent;
         uint32_t reserve = 0, reserve_wide = 0, lmin = lane_min;
         if (lanes_beside) {
-            if (!wsp.side) {
-                {   // The lanes' and the register-table parser's streams come from the HIGH-PRIORITY pool of hardware queues (CW_SIDE_PRIO=0: the normal one,
-                    // =1: the lanes' only).  HIP multiplexes its streams onto four hardware queues per priority level, and kernels of different streams
-                    // that land on one queue run one after the other.  A device-resident call has four streams and is not affected; the host pipeline has
-                    // three slots with four streams each plus two for copies, and its timeline (rocprofv3 --kernel-trace) showed a chunk's two scalar-thread
-                    // kernels starting the moment ITS OWN lanes kernel had ended, 108 ms late.  With the side streams in another pool a chunk's kernels
-                    // no longer share a queue with each other: host path over the corpus 20.5-21.0 -> 24.0-24.3 GB/s (GPU_MAX_HW_QUEUES=8 on top: 24.7-24.9);
-                    // the device-resident legs and the headline are unchanged (16 GiB corpus leg 44-48 -> 49.6).
-                    int least = 0, greatest = 0;
-                    if ((e = hipDeviceGetStreamPriorityRange(&least, &greatest)) != hipSuccess) return e;
-                    e = kn.side_prio != SidePrio::none ? hipStreamCreateWithPriority(&wsp.side, hipStreamNonBlocking, greatest)
-                                                   : hipStreamCreateWithFlags(&wsp.side, hipStreamNonBlocking);
-                    if (e != hipSuccess) return e;
-                }
-                if ((e = hipEventCreateWithFlags(&wsp.fork, hipEventDisableTiming)) != hipSuccess) return e;
-                if ((e = hipEventCreateWithFlags(&wsp.join, hipEventDisableTiming)) != hipSuccess) return e;
-            }
+            // The lanes' and the register-table parser's streams come from the HIGH-PRIORITY pool of hardware queues (CW_SIDE_PRIO=0: the normal one,
+            // =1: the lanes' only).  HIP multiplexes its streams onto four hardware queues per priority level, and kernels of different streams
+            // that land on one queue run one after the other.  A device-resident call has four streams and is not affected; the host pipeline has
+            // three slots with four streams each plus two for copies, and its timeline (rocprofv3 --kernel-trace) showed a chunk's two scalar-thread
+            // kernels starting the moment ITS OWN lanes kernel had ended, 108 ms late.  With the side streams in another pool a chunk's kernels
+            // no longer share a queue with each other: host path over the corpus 20.5-21.0 -> 24.0-24.3 GB/s (GPU_MAX_HW_QUEUES=8 on top: 24.7-24.9);
+            // the device-resident legs and the headline are unchanged (16 GiB corpus leg 44-48 -> 49.6).
+            if ((e = wsp.lanes.open(kn.side_prio != SidePrio::none ? SideStream::greatest : SideStream::normal)) != hipSuccess) return e;
             // what the wavefront parser gets through while a lane parses its last block: 4 KiB text, 1 Mi blocks: 8 Ki..40 Ki 40-43 GB/s, 48 Ki 39.8;
             // 256 Ki blocks: 16 Ki / 28 Ki / 40 Ki 37.4 / 39.0 / 41.0
             // blocks > 4 KiB (round 3; corpus, 64 KiB, lanes alone -> lanes beside the other two, GB/s): two positions per iteration, 32 Ki blocks
@@ -2413,28 +2350,27 @@ hipError_t lz4_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
             reserve_wide = kn.lanes_reserve ? (uint32_t)kn.lanes_reserve : kLaneShareWide;
             if (lane_min > 1 && lmin < reserve + reserve / 4) lmin = reserve + reserve / 4; // (CW_LZ4_LANES=1 in the tests: no reserve)
             if (lane_min == 1) reserve = reserve_wide = 0;
-            if ((e = hipEventRecord(wsp.fork, stream)) != hipSuccess) return e;
-            if ((e = hipStreamWaitEvent(wsp.side, wsp.fork, 0)) != hipSuccess) return e;
+            if ((e = lanes_fork.emplace(wsp.lanes, stream).err) != hipSuccess) return e;
         }
-        hipStream_t ls = lanes_beside ? wsp.side : stream;
+        hipStream_t ls = lanes_beside ? wsp.lanes.stream : stream;
         const uint32_t no_max = 0xFFFFFFFFu;
         const char *side_tag = lanes_beside ? " [side stream]" : "";
 #define CW_RING(K, LO, HI) do { \
             const uint32_t lo_ = (LO), hi_ = (HI); \
             hipLaunchKernelGGL(lz4_lanes_ring_kernel<K>, dim3((unsigned)lgrid), dim3(64), 0, ls, src, n, src_stride, dst, dst_stride, sizes, queue, counters, \
-                               wsp.lane_tabs, lo_, hi_ == no_max && lanes_ring < 0 ? reserve_wide : reserve, hi_); \
+                               lane_tabs, lo_, hi_ == no_max && lanes_ring < 0 ? reserve_wide : reserve, hi_); \
             if (hi_ == no_max) note("cw::lz4_lanes_ring_kernel<" #K "> (queue >= %u)%s", lo_, side_tag); \
             else note("cw::lz4_lanes_ring_kernel<" #K "> (queue in [%u, %u))%s", lo_, hi_, side_tag); } while (0)
         if (n <= 4096)
         {
             hipLaunchKernelGGL(lz4_lanes_kernel<kLaneTagged>, dim3((unsigned)lgrid), dim3(64), 0, ls, src, n, src_stride, dst, dst_stride, sizes, queue,
-                               counters, wsp.lane_tabs, lmin, reserve);
+                               counters, lane_tabs, lmin, reserve);
             note("cw::lz4_lanes_kernel<1> (queue >= %u)%s", lmin, side_tag);
         }
         else if (lanes_ring < 0) {
             const uint32_t wide_from = lmin < kLaneWideBlocks ? kLaneWideBlocks : lmin;
             hipLaunchKernelGGL(lz4_lanes_ring_auto_kernel, dim3((unsigned)lgrid), dim3(64), 0, ls, src, n, src_stride, dst, dst_stride, sizes, queue, counters,
-                               wsp.lane_tabs, lmin, reserve, wide_from, reserve_wide, lane_leave);
+                               lane_tabs, lmin, reserve, wide_from, reserve_wide, lane_leave);
             note("cw::lz4_lanes_ring_auto_kernel (queue >= %u: two positions per iteration, >= %u: one)%s", lmin, wide_from, side_tag);
         }
         else if (lanes_ring == 1) CW_RING(1, lmin, no_max);
@@ -2444,11 +2380,11 @@ hipError_t lz4_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
 #undef CW_RING
         else if (kn.lz4_lanes_fp) { // CW_LZ4_LANES_FP=0 (profiling knob): 16-bit table entries without fingerprints for blocks > 4 KiB
             hipLaunchKernelGGL(lz4_lanes_kernel<kLaneFp>, dim3((unsigned)lgrid), dim3(64), 0, ls, src, n, src_stride, dst, dst_stride, sizes, queue,
-                               counters, wsp.lane_tabs, lmin, reserve);
+                               counters, lane_tabs, lmin, reserve);
             note("cw::lz4_lanes_kernel<2> (queue >= %u)%s", lmin, side_tag);
         } else {
             hipLaunchKernelGGL(lz4_lanes_kernel<kLanePlain>, dim3((unsigned)lgrid), dim3(64), 0, ls, src, n, src_stride, dst, dst_stride, sizes, queue,
-                               counters, wsp.lane_tabs, lmin, reserve);
+                               counters, lane_tabs, lmin, reserve);
             note("cw::lz4_lanes_kernel<0> (queue >= %u)%s", lmin, side_tag);
         }
         if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -2465,7 +2401,7 @@ hipError_t lz4_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
     const int vt_mode = kn.lz4_vtab.value_or(2);
     // CW_LZ4_MODE=cut parses with the first-generation (write/read-back) kernel only (profiling knob)
     const bool cut_only = kn.lz4_mode == Lz4Mode::cut;
-    bool vtab_used = false, vtab_beside = false;
+    bool vtab_beside = false;
     if (vt_mode > 0 && !use_fp && !cut_only && n >= 64 && nblocks >= 64 && ((reinterpret_cast<uintptr_t>(src) | src_stride) & 3) == 0) {
         // LDS-staged blocks: a small queue is the LDS-resident parser's (4 Ki blocks of 4 KiB: 19.4 GB/s alone against 14.5 with the register-table
         // parser's 4,096 wavefronts taking a block each; 16 Ki blocks 23.8 -> 24.5, 32 Ki 25.1 -> 28.0, 51,728 25.6 -> 29.5)
@@ -2475,20 +2411,9 @@ hipError_t lz4_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
         const unsigned vwpc = kn.vtab_wpc ? (unsigned)kn.vtab_wpc : 16u;
         hipStream_t vs = stream;
         if (vt_mode == 2) {
-            if (!wsp.side2) {
-                {
-                    int least = 0, greatest = 0;
-                    if ((e = hipDeviceGetStreamPriorityRange(&least, &greatest)) != hipSuccess) return e;
-                    e = kn.side_prio == SidePrio::both ? hipStreamCreateWithPriority(&wsp.side2, hipStreamNonBlocking, greatest)
-                                                   : hipStreamCreateWithFlags(&wsp.side2, hipStreamNonBlocking);
-                    if (e != hipSuccess) return e;
-                }
-                if ((e = hipEventCreateWithFlags(&wsp.fork2, hipEventDisableTiming)) != hipSuccess) return e;
-                if ((e = hipEventCreateWithFlags(&wsp.join2, hipEventDisableTiming)) != hipSuccess) return e;
-            }
-            if ((e = hipEventRecord(wsp.fork2, stream)) != hipSuccess) return e;
-            if ((e = hipStreamWaitEvent(wsp.side2, wsp.fork2, 0)) != hipSuccess) return e;
-            vs = wsp.side2;
+            if ((e = wsp.vtab.open(kn.side_prio == SidePrio::both ? SideStream::greatest : SideStream::normal)) != hipSuccess) return e;
+            if ((e = vtab_fork.emplace(wsp.vtab, stream).err) != hipSuccess) return e;
+            vs = wsp.vtab.stream;
             vtab_beside = true;
         }
         const char *vname = nullptr;
@@ -2496,7 +2421,6 @@ hipError_t lz4_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
         if ((e = lz4_vtab_launch(src, n, src_stride, nblocks, dst, dst_stride, sizes, queue, counters, vmin, vmax, vres, vwpc, gen, vs, &vname)) != hipSuccess) return e;
         if (vmax != 0xFFFFFFFFu) note("%s (queue < %u)%s", vname, vmax, vtab_beside ? " [side stream]" : "");
         else note("%s%s", vname, vtab_beside ? " [side stream]" : "");
-        vtab_used = true;
     }
     const size_t pwpc = kn.parse_wpc ? (size_t)kn.parse_wpc : 10; // CW_PARSE_WPC: parse wavefronts per CU (profiling knob; default: all the LDS admits)
     const size_t want = 256 * (per_cu > pwpc ? pwpc : per_cu);
@@ -2531,14 +2455,8 @@ hipError_t lz4_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
         if ((e = hipGetLastError()) != hipSuccess) return e;
         }
     }
-    if (vtab_used && vtab_beside) {
-        if ((e = hipEventRecord(wsp.join2, wsp.side2)) != hipSuccess) return e;
-        if ((e = hipStreamWaitEvent(stream, wsp.join2, 0)) != hipSuccess) return e;
-    }
-    if (lanes_used && lanes_beside) { // the redo pass and the caller's later work wait for the lanes too
-        if ((e = hipEventRecord(wsp.join, wsp.side)) != hipSuccess) return e;
-        if ((e = hipStreamWaitEvent(stream, wsp.join, 0)) != hipSuccess) return e;
-    }
+    if (vtab_fork && (e = vtab_fork->join()) != hipSuccess) return e;
+    if (lanes_fork && (e = lanes_fork->join()) != hipSuccess) return e; // the redo pass and the caller's later work wait for the lanes too
     if (cut_only) note(staged ? "cw::lz4_blocks_kernel<true>" : "cw::lz4_blocks_kernel<false>");
     note_kernels(0, launched); // (the redo pass below finds an empty list unless the LDS ever applied an exchange's lanes out of order)
     // blocks the exchange-based parser handed back (none, unless the LDS ever applies lanes out of order)

@@ -35,12 +35,10 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <mutex>
-#include <unordered_map>
-
 #include "cw_device.h"
 #include "lz_device.h"
 #include "scalar_thread.h"
+#include "stream_scratch.h"
 
 namespace cw {
 
@@ -1317,41 +1315,13 @@ lzf_lanes_kernel(const uint8_t *__restrict__ src, uint32_t n, size_t src_stride,
 
 namespace {
 struct LinkSpace {
-    uint16_t *p = nullptr; size_t cap = 0; uint32_t *counter = nullptr;
-    uint16_t *lane_tabs = nullptr; size_t lane_cap = 0; // tables of the lane-per-block parser: 128 KiB per lane
-    uint32_t *handback = nullptr; size_t hb_cap = 0;    // blocks the lanes passed on to the link/chain kernels
-    hipStream_t side = nullptr; hipEvent_t fork = nullptr, join = nullptr; // the lane parser's stream beside the rounds
+    DeviceBuf links, counter;
+    DeviceBuf lane_tabs; // tables of the lane-per-block parser: 128 KiB per lane
+    DeviceBuf handback;  // blocks the lanes passed on to the link/chain kernels
+    SideStream lanes;    // the lane parser's stream beside the rounds
+    void release() { (void)links.release(); (void)counter.release(); (void)lane_tabs.release(); (void)handback.release(); lanes.release(); }
 };
-struct LinkEntry { LinkSpace s; std::mutex launch; };
-std::mutex link_lock;
-std::unordered_map<uint64_t, LinkEntry> link_map; // references stay valid across inserts
-}
-
-void lzf_release_workspaces()
-{
-    std::lock_guard<std::mutex> g(link_lock);
-    for (auto &kv : link_map) {
-        if (kv.second.s.p) (void)hipFree(kv.second.s.p);
-        if (kv.second.s.counter) (void)hipFree(kv.second.s.counter);
-        if (kv.second.s.lane_tabs) (void)hipFree(kv.second.s.lane_tabs);
-        if (kv.second.s.handback) (void)hipFree(kv.second.s.handback);
-        if (kv.second.s.side) { (void)hipStreamDestroy(kv.second.s.side); (void)hipEventDestroy(kv.second.s.fork); (void)hipEventDestroy(kv.second.s.join); }
-    }
-    link_map.clear();
-}
-
-void lzf_release_stream(hipStream_t stream)
-{
-    std::lock_guard<std::mutex> g(link_lock);
-    auto it = link_map.find(ws_key(stream));
-    if (it == link_map.end()) return;
-    auto &w = it->second.s;
-    if (w.p) (void)hipFree(w.p);
-    if (w.counter) (void)hipFree(w.counter);
-    if (w.lane_tabs) (void)hipFree(w.lane_tabs);
-    if (w.handback) (void)hipFree(w.handback);
-    if (w.side) { (void)hipStreamDestroy(w.side); (void)hipEventDestroy(w.fork); (void)hipEventDestroy(w.join); }
-    link_map.erase(it);
+StreamScratch<LinkSpace> link_spaces;
 }
 
 hipError_t lzf_launch(const uint8_t *src, size_t block_bytes, size_t src_stride, size_t nblocks, uint8_t *dst,
@@ -1407,13 +1377,9 @@ hipError_t lzf_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
         const size_t chunk_cap = kn.lzf_round ? (size_t)kn.lzf_round : beside ? (big ? (nblocks < kLzfBigBesideWide ? kLzfBigBesideRoundMid : kLzfBigBesideRound) : kLzfBesideRound) : ws_bytes / (2 * (size_t)n2);
         const size_t chunk_max = chunk_cap < ws_bytes / (2 * (size_t)n2) ? chunk_cap : ws_bytes / (2 * (size_t)n2);
         const size_t chunk = nblocks < chunk_max ? nblocks : chunk_max;
-        LinkSpace ls;
-        LinkEntry *entry;
-        {
-            std::lock_guard<std::mutex> g(link_lock);
-            entry = &link_map[ws_key(stream)];
-        }
-        std::lock_guard<std::mutex> sequence(entry->launch); // the link array and the counter are shared by the launches below
+        auto &w = link_spaces.at(stream);
+        LaunchLock sequence(w.launch); // the link array and the counter are shared by the launches below
+        std::optional<SideStream::Fork> lanes_fork; // (a return before the join below still joins)
         // Large batches: the lane-per-block parser (CW_LZF_LANES=0 off, =N threshold, 1 = every block, in the tests; CW_LANES_WPC
         // wavefronts per CU).  Blocks > 4 KiB from kLzfLaneMinBlocks on: the lanes take the whole batch.  Blocks that fit the
         // LDS-resident chain parser, from kLzfLaneMinSmall on: the lanes run BESIDE the link/chain rounds on a second stream,
@@ -1424,72 +1390,44 @@ hipError_t lzf_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
         const size_t round_max = ws_bytes / (2 * (size_t)n2); // blocks per round that the link workspace admits
         const size_t hb_chunk = nblocks < round_max ? nblocks : round_max; // rounds of the hand-back pass
         hipError_t e;
-        {
-            LinkSpace &w = entry->s;
-            const size_t need = use_lanes && hb_chunk > chunk ? hb_chunk : chunk;
-            if (w.cap < need * n2) {
-                if (w.p) { e = hipFree(w.p); if (e != hipSuccess) return e; }
-                w.p = nullptr; w.cap = 0;
-                e = hipMalloc(reinterpret_cast<void **>(&w.p), need * n2 * sizeof(uint16_t));
-                if (e != hipSuccess) return e;
-                w.cap = need * n2;
-            }
-            if (!w.counter && (e = hipMalloc(reinterpret_cast<void **>(&w.counter), kCtrBytes)) != hipSuccess) return e;
-        }
+        const size_t need = use_lanes && hb_chunk > chunk ? hb_chunk : chunk;
+        if ((e = w.links.reserve(need * n2 * sizeof(uint16_t))) != hipSuccess) return e;
+        if ((e = w.counter.reserve(kCtrBytes)) != hipSuccess) return e;
+        uint16_t *const links = w.links.as<uint16_t>();
+        uint32_t *const counter = w.counter.as<uint32_t>();
         size_t lgrid = 0; // workgroups of the lane-per-block kernel
         if (use_lanes) {
             const size_t lwpc = kn.lanes_wpc ? (size_t)kn.lanes_wpc : 4;
             lgrid = (nblocks + 63) / 64;
             if (lgrid > 256 * lwpc) lgrid = 256 * lwpc;
             if (beside && lgrid * 64 + want_reserve > nblocks) lgrid = nblocks > want_reserve + 64 ? (nblocks - want_reserve) / 64 : 1; // (no lane without a block)
-            LinkSpace &w = entry->s;
-            if (w.lane_cap < lgrid * 64) {
-                if (w.lane_tabs) { e = hipFree(w.lane_tabs); if (e != hipSuccess) return e; }
-                w.lane_tabs = nullptr; w.lane_cap = 0;
-                e = hipMalloc(reinterpret_cast<void **>(&w.lane_tabs), lgrid * 64 * (size_t)kLzfTabBytes);
-                if (e != hipSuccess) { // up to 8 GiB: a nearly full device does without the lanes instead of failing the call
-                    (void)hipGetLastError();
-                    w.lane_tabs = nullptr;
-                    use_lanes = beside = false;
-                } else {
-                    w.lane_cap = lgrid * 64;
-                }
+            // up to 8 GiB: a nearly full device does without the lanes instead of failing the call
+            if (w.lane_tabs.reserve(lgrid * 64 * (size_t)kLzfTabBytes) != hipSuccess) {
+                (void)hipGetLastError();
+                use_lanes = beside = false;
             }
         }
         if (use_lanes) {
-            LinkSpace &w = entry->s;
-            if (w.hb_cap < nblocks) { // a block is handed back once at most
-                if (w.handback) { e = hipFree(w.handback); if (e != hipSuccess) return e; }
-                w.handback = nullptr; w.hb_cap = 0;
-                e = hipMalloc(reinterpret_cast<void **>(&w.handback), nblocks * sizeof(uint32_t));
-                if (e != hipSuccess) return e;
-                w.hb_cap = nblocks;
-            }
-            if ((e = hipMemsetAsync(w.counter, 0, kCtrBytes, stream)) != hipSuccess) return e;
+            if ((e = w.handback.reserve(nblocks * sizeof(uint32_t))) != hipSuccess) return e; // a block is handed back once at most
+            if ((e = hipMemsetAsync(counter, 0, kCtrBytes, stream)) != hipSuccess) return e;
             hipStream_t lstream = stream;
             if (beside) {
-                if (!w.side) {
-                    if ((e = hipStreamCreateWithFlags(&w.side, hipStreamNonBlocking)) != hipSuccess) return e;
-                    if ((e = hipEventCreateWithFlags(&w.fork, hipEventDisableTiming)) != hipSuccess) return e;
-                    if ((e = hipEventCreateWithFlags(&w.join, hipEventDisableTiming)) != hipSuccess) return e;
-                }
+                if ((e = w.lanes.open(SideStream::normal)) != hipSuccess) return e;
                 lane_reserve = (uint32_t)want_reserve;
                 if (lane_reserve < 1) lane_reserve = 1; // (0 means "on their own" to the kernel; the protocol itself needs no reserve)
-                if ((e = hipEventRecord(w.fork, stream)) != hipSuccess) return e;
-                if ((e = hipStreamWaitEvent(w.side, w.fork, 0)) != hipSuccess) return e;
-                lstream = w.side;
+                if ((e = lanes_fork.emplace(w.lanes, stream).err) != hipSuccess) return e;
+                lstream = w.lanes.stream;
             }
             if (n <= 4096)
                 { note(beside ? "cw::lzf_lanes_kernel<true> [side stream]" : "cw::lzf_lanes_kernel<true>");
                 hipLaunchKernelGGL(lzf_lanes_kernel<true>, dim3((unsigned)lgrid), dim3(64), 0, lstream, src, n, src_stride, nblocks, dst, dst_stride,
-                                   sizes, w.lane_tabs, w.counter, lane_reserve, w.handback); }
+                                   sizes, w.lane_tabs.as<uint16_t>(), counter, lane_reserve, w.handback.as<uint32_t>()); }
             else
                 { note(beside ? "cw::lzf_lanes_kernel<false> [side stream]" : "cw::lzf_lanes_kernel<false>");
                 hipLaunchKernelGGL(lzf_lanes_kernel<false>, dim3((unsigned)lgrid), dim3(64), 0, lstream, src, n, src_stride, nblocks, dst, dst_stride,
-                                   sizes, w.lane_tabs, w.counter, lane_reserve, w.handback); }
+                                   sizes, w.lane_tabs.as<uint16_t>(), counter, lane_reserve, w.handback.as<uint32_t>()); }
             if ((e = hipGetLastError()) != hipSuccess) return e;
         }
-        ls = entry->s;
         static bool chain_attr = false;
         if (!chain_attr) {
             e = hipFuncSetAttribute(reinterpret_cast<const void *>(lzf_links_kernel),
@@ -1508,15 +1446,15 @@ hipError_t lzf_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
         // CW_LZF_SHARE_GIVE_UP (test knob): every workgroup but a round's claimant gives up at once
         const uint32_t spin_cap = kn.lzf_share_give_up ? 0u : kShareSpinCap;
         auto round = [&](size_t first, size_t nb, bool listed) -> hipError_t {
-            hipError_t r = hipMemsetAsync(ls.counter, 0, sizeof(uint32_t), stream);
+            hipError_t r = hipMemsetAsync(counter, 0, sizeof(uint32_t), stream);
             if (r != hipSuccess) return r;
-            const LaneShare share = {beside && !listed ? ls.counter : nullptr, first, nblocks, (uint32_t)(first / chunk + 1), spin_cap};
-            const BlockList list = {listed ? ls.handback : nullptr, listed ? ls.counter + kCtrHanded : nullptr, (uint32_t)first};
+            const LaneShare share = {beside && !listed ? counter : nullptr, first, nblocks, (uint32_t)(first / chunk + 1), spin_cap};
+            const BlockList list = {listed ? w.handback.as<uint32_t>() : nullptr, listed ? counter + kCtrHanded : nullptr, (uint32_t)first};
             const size_t off = listed ? 0 : first; // listed blocks are addressed through the list, from the batch's base
             note(listed ? "cw::lzf_links_kernel (handed-back blocks)" : "cw::lzf_links_kernel");
             note(sthread ? "cw::lzf_sthread_kernel" : big ? "cw::lzf_chain_kernel<true>" : "cw::lzf_chain_kernel<false>");
             hipLaunchKernelGGL(lzf_links_kernel, dim3((unsigned)(nb < 256 ? nb : 256)), dim3(64), links_lds, stream, src + off * src_stride, n,
-                               src_stride, nb, ls.p, n2, sizes + off, force_redo, share, list);
+                               src_stride, nb, links, n2, sizes + off, force_redo, share, list);
             size_t cgrid = nb < 256 * per_cu ? nb : 256 * per_cu;
             if (sthread) { // (n2 / 8 bytes of LDS per workgroup: 20 per CU at 64 KiB; smaller blocks: as many wavefronts as measured to pay)
                 const size_t st_cu = (160u * 1024u) / (n2 / 8) < st_wpc ? (160u * 1024u) / (n2 / 8) : st_wpc;
@@ -1524,27 +1462,25 @@ hipError_t lzf_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
             }
             if (sthread)
                 hipLaunchKernelGGL(lzf_sthread_kernel, dim3((unsigned)cgrid), dim3(64), n2 / 8, stream, src + off * src_stride, n, src_stride, nb,
-                                   dst + off * dst_stride, dst_stride, sizes + off, ls.p, n2, ls.counter, share, list);
+                                   dst + off * dst_stride, dst_stride, sizes + off, links, n2, counter, share, list);
             else if (big)
                 hipLaunchKernelGGL(lzf_chain_kernel<true>, dim3((unsigned)cgrid), dim3(64), chain_lds, stream, src + off * src_stride, n, src_stride,
-                                   nb, dst + off * dst_stride, dst_stride, sizes + off, ls.p, n2, ls.counter, share, list);
+                                   nb, dst + off * dst_stride, dst_stride, sizes + off, links, n2, counter, share, list);
             else
                 hipLaunchKernelGGL(lzf_chain_kernel<false>, dim3((unsigned)cgrid), dim3(64), chain_lds, stream, src + off * src_stride, n, src_stride,
-                                   nb, dst + off * dst_stride, dst_stride, sizes + off, ls.p, n2, ls.counter, share, list);
+                                   nb, dst + off * dst_stride, dst_stride, sizes + off, links, n2, counter, share, list);
             return hipGetLastError();
         };
         if (!use_lanes || beside)
             for (size_t first = 0; first < nblocks; first += chunk)
                 if ((e = round(first, nblocks - first < chunk ? nblocks - first : chunk, false)) != hipSuccess) return e;
         if (beside) { // the hand-back pass, the redo pass and the caller's later work wait for the lanes
-            e = hipEventRecord(ls.join, ls.side);
-            if (e == hipSuccess) e = hipStreamWaitEvent(stream, ls.join, 0);
-            if (e != hipSuccess) return e;
+            if ((e = lanes_fork->join()) != hipSuccess) return e;
         }
         if (use_lanes && kn.debug_lzf) {
             uint32_t h[kCtrBytes / 4];
             (void)hipStreamSynchronize(stream);
-            (void)hipMemcpy(h, ls.counter, kCtrBytes, hipMemcpyDeviceToHost);
+            (void)hipMemcpy(h, counter, kCtrBytes, hipMemcpyDeviceToHost);
             fprintf(stderr, "lzf lanes: taken %u claimed %u poor %u fine %u handed back %u of %zu; claim ticket %u, gave up %u\n", h[kCtrWord],
                     h[kCtrWord + 1], h[kCtrPoor], h[kCtrFine], h[kCtrHanded], nblocks, h[kCtrTicket], h[kCtrFailed]);
         }
@@ -1552,7 +1488,7 @@ hipError_t lzf_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
             for (size_t first = 0; first < nblocks; first += hb_chunk)
                 if ((e = round(first, nblocks - first < hb_chunk ? nblocks - first : hb_chunk, true)) != hipSuccess) return e;
         hipLaunchKernelGGL(lzf_blocks_kernel, dim3((unsigned)grid), dim3(64), lds, stream, src, n, src_stride, nblocks, dst,
-                           dst_stride, sizes, in_lds, 1u, beside ? ls.counter + kCtrFailed : nullptr);
+                           dst_stride, sizes, in_lds, 1u, beside ? counter + kCtrFailed : nullptr);
         note_kernels(0, launched);
         return hipGetLastError();
     }

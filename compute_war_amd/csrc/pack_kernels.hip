@@ -11,11 +11,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <mutex>
-#include <unordered_map>
-
 #include "cw_device.h"
 #include "lz_device.h"
+#include "stream_scratch.h"
 
 namespace cw {
 
@@ -108,52 +106,20 @@ pack_copy_kernel(const uint8_t *__restrict__ slots, size_t slot_stride, const ui
     }
 }
 
-struct Workspace { unsigned long long *p = nullptr; size_t cap = 0; std::mutex launch; };
-std::mutex ws_lock;
-std::unordered_map<uint64_t, Workspace> ws_map; // references stay valid across inserts
+StreamScratch<DeviceBuf> partials; // per stream: the tile sums
 
 } // namespace
-
-void pack_release_workspaces()
-{
-    std::lock_guard<std::mutex> g(ws_lock);
-    for (auto &kv : ws_map) if (kv.second.p) (void)hipFree(kv.second.p);
-    ws_map.clear();
-}
-
-void pack_release_stream(hipStream_t stream)
-{
-    std::lock_guard<std::mutex> g(ws_lock);
-    auto it = ws_map.find(ws_key(stream));
-    if (it == ws_map.end()) return;
-    if (it->second.p) (void)hipFree(it->second.p);
-    ws_map.erase(it);
-}
 
 hipError_t pack_launch(const uint8_t *slots, size_t slot_stride, const uint32_t *sizes, size_t nblocks, uint8_t *packed,
                        uint64_t *offsets, hipStream_t stream)
 {
     if (nblocks == 0) return hipMemsetAsync(offsets, 0, sizeof(uint64_t), stream);
     const size_t ntiles = (nblocks + kTile - 1) / kTile;
-    unsigned long long *partial = nullptr;
-    Workspace *wsp;
-    {
-        std::lock_guard<std::mutex> g(ws_lock);
-        wsp = &ws_map[ws_key(stream)];
-    }
-    std::lock_guard<std::mutex> sequence(wsp->launch); // the tile partials are shared by the launches below
-    {
-        Workspace &w = *wsp;
-        if (w.cap < ntiles) { // first (or a larger) call on this stream
-            if (w.p) { hipError_t e = hipFree(w.p); if (e != hipSuccess) return e; }
-            w.p = nullptr; w.cap = 0;
-            const size_t cap = ntiles < 1024 ? 1024 : ntiles;
-            hipError_t e = hipMalloc(reinterpret_cast<void **>(&w.p), cap * sizeof(unsigned long long));
-            if (e != hipSuccess) return e;
-            w.cap = cap;
-        }
-        partial = w.p;
-    }
+    auto &w = partials.at(stream);
+    LaunchLock sequence(w.launch); // the tile partials are shared by the launches below
+    const hipError_t e = w.reserve(ntiles * sizeof(unsigned long long), 1024 * sizeof(unsigned long long));
+    if (e != hipSuccess) return e;
+    unsigned long long *partial = w.as<unsigned long long>();
     unsigned long long *off = reinterpret_cast<unsigned long long *>(offsets);
     hipLaunchKernelGGL(tile_sums_kernel, dim3((unsigned)ntiles), dim3(kThreads), 0, stream, sizes, nblocks, partial);
     hipLaunchKernelGGL(scan_partials_kernel, dim3(1), dim3(kThreads), 0, stream, partial, ntiles);

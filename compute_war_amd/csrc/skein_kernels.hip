@@ -21,10 +21,8 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <mutex>
-#include <unordered_map>
-
 #include "cw_device.h"
+#include "stream_scratch.h"
 
 namespace cw {
 
@@ -470,25 +468,7 @@ skein_slice_kernel(const uint8_t *__restrict__ src, size_t block_bytes, size_t s
 }
 
 namespace {
-struct SliceSpace { uint64_t *p = nullptr; size_t cap = 0; std::mutex launch; };
-std::mutex slice_lock;
-std::unordered_map<uint64_t, SliceSpace> slice_map; // references stay valid across inserts
-}
-
-void skein_release_workspaces()
-{
-    std::lock_guard<std::mutex> g(slice_lock);
-    for (auto &kv : slice_map) if (kv.second.p) (void)hipFree(kv.second.p);
-    slice_map.clear();
-}
-
-void skein_release_stream(hipStream_t stream)
-{
-    std::lock_guard<std::mutex> g(slice_lock);
-    auto it = slice_map.find(ws_key(stream));
-    if (it == slice_map.end()) return;
-    if (it->second.p) (void)hipFree(it->second.p);
-    slice_map.erase(it);
+StreamScratch<DeviceBuf> slices; // per stream: the chaining values between the slices of one hash
 }
 
 bool skein_sliced_applies(int nw, const uint8_t *src, size_t block_bytes, size_t src_stride, size_t nblocks, const uint8_t *digests)
@@ -506,24 +486,11 @@ hipError_t skein_sliced_launch(int nw, const uint8_t *src, size_t block_bytes, s
     const size_t nsl = kn.skein_nslices ? (size_t)kn.skein_nslices : kSkeinSlices; // CW_SKEIN_NSLICES: profiling knob
     size_t slice_steps = (total + nsl - 1) / nsl;
     slice_steps = (slice_steps + spl - 1) / spl * spl;
-    uint64_t *state = nullptr;
-    SliceSpace *wsp;
-    {
-        std::lock_guard<std::mutex> g(slice_lock);
-        wsp = &slice_map[ws_key(stream)];
-    }
-    std::lock_guard<std::mutex> sequence(wsp->launch); // the slices hand their chaining values on through w.p
-    {
-        SliceSpace &w = *wsp;
-        if (w.cap < nblocks * (size_t)nw) {
-            if (w.p) { hipError_t e = hipFree(w.p); if (e != hipSuccess) return e; }
-            w.p = nullptr; w.cap = 0;
-            hipError_t e = hipMalloc(reinterpret_cast<void **>(&w.p), nblocks * (size_t)nw * sizeof(uint64_t));
-            if (e != hipSuccess) return e;
-            w.cap = nblocks * (size_t)nw;
-        }
-        state = w.p;
-    }
+    auto &w = slices.at(stream);
+    LaunchLock sequence(w.launch); // the slices hand their chaining values on through the entry's buffer
+    const hipError_t err = w.reserve(nblocks * (size_t)nw * sizeof(uint64_t));
+    if (err != hipSuccess) return err;
+    uint64_t *state = w.as<uint64_t>();
     const dim3 grid((unsigned)((nblocks + CW_SKEIN_THREADS - 1) / CW_SKEIN_THREADS)), block(CW_SKEIN_THREADS);
     for (size_t b = 0; b < total; b += slice_steps) {
         const size_t e = b + slice_steps < total ? b + slice_steps : total;

@@ -163,3 +163,22 @@ def test_knob_table_is_the_only_list_of_knobs(cwlib):
             assert "tune(" not in code or "cw_tune" in code, (f, i, line)
             assert '"CW_' not in code or (f == "cw_api.hip" and first <= i <= last), (f, i, line)
             assert "getenv(" not in code or "getenv(kKnobTable[i].name)" in code, (f, i, line)
+
+
+def test_stream_scratch_is_the_only_per_stream_registry():
+    """The kernel files keep their per-(device, stream) scratch through stream_scratch.h alone: none of them declares a map or a
+    mutex of its own, or allocates device memory, streams or events itself; and the key of an entry is computed in one place."""
+    csrc = os.path.join(ROOT, "compute_war_amd", "csrc")
+    banned = ("std::unordered_map", "std::mutex", "hipMalloc", "hipFree", "hipStreamCreate", "hipStreamDestroy", "hipEventCreate",
+              "hipEventDestroy")
+    kernel_files = [f for f in sorted(os.listdir(csrc)) if f.endswith(("_kernel.hip", "_kernels.hip"))]
+    assert len(kernel_files) >= 10, kernel_files
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".h")):
+            continue
+        for i, line in enumerate(open(os.path.join(csrc, f)).read().split("\n"), 1):
+            code = line.split("//")[0]
+            if f in kernel_files:
+                for token in banned:
+                    assert token not in code, (f, i, token, line)
+            assert "ws_key(" not in code or f == "stream_scratch.h", (f, i, line)

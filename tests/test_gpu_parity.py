@@ -1,11 +1,14 @@
 """GPU parity tests proper: the HIP path (through the C ABI) against the CPU oracle and the committed
 golden fixtures.  Bit-exact everywhere (integer / byte work)."""
 import hashlib
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
 
-from conftest import (anchor_input, corpus_file, corpus_large_file, corpus_large_names, corpus_names, load_golden,
+from conftest import (ROOT, anchor_input, corpus_file, corpus_large_file, corpus_large_names, corpus_names, load_golden,
                       seeded_block)
 
 pytestmark = pytest.mark.gpu
@@ -552,3 +555,72 @@ def test_fused_call_sliced_hash_equals_whole_block_hash(cw, oracle, alg, db, bs)
     hd = fused.cpu().numpy()
     for i in (0, 1, 63, 64, nb // 2 - 1, nb // 2, nb // 2 + 1, nb - 2, nb - 1):
         assert hd[i * db:(i + 1) * db].tobytes() == _oracle_hash(oracle, alg, host[i * bs:(i + 1) * bs].tobytes()), i
+
+
+# ---------------------------------------------------------------- cw_shutdown
+def _shutdown_data():
+    text = corpus_file("lcet10.txt") + corpus_file("kennedy.xls")[:300000] + corpus_file("ptt5")[:200000]
+    return (text * (4096 * 4096 // len(text) + 1))[:4096 * 4096]
+
+
+def test_shutdown_releases_every_stream_scratch_subprocess(oracle):
+    """cw_shutdown gives back the per-stream scratch of every registry, and the library works again after cw_init.  In a process of its
+    own (the session's library state is not torn down under the other tests): a fused Skein-512 + LZ4 call and an LZF call over 4096
+    blocks of 4 KiB with the lane parsers on (CW_LZ4_LANES=1: 128 MiB of lane tables, both side streams; CW_LZF_LANES=1: 32 MiB of
+    links, lane tables, hand-back list, side stream), then cw_shutdown: device memory in use is back within 64 MiB of what it was
+    before the calls (the bound of test_short_lived_calling_threads_leave_no_device_memory_behind), while after the calls it was
+    more than 64 MiB above it (128 MiB of lane tables alone).  The first pass runs unmeasured, so that what the runtime allocates
+    once per process is there already; the calling thread's own context outlives cw_shutdown, so the baseline is taken when it exists."""
+    prog = (
+        "import sys, hashlib; sys.path.insert(0, %r); sys.path.insert(0, %r + '/tests')\n"
+        "import numpy as np, torch, compute_war_amd as cw\n"
+        "from test_gpu_parity import _shutdown_data\n"
+        "bs, nb = 4096, 4096\n"
+        "cw.init(0)\n"
+        "s = torch.cuda.current_stream().cuda_stream\n"
+        "src = torch.frombuffer(bytearray(_shutdown_data()), dtype=torch.uint8).cuda()\n"
+        "stride = (max(cw.compress_bound('lz4', bs), cw.compress_bound('lzf', bs)) + 15) // 16 * 16\n"
+        "dig = torch.zeros((nb, 64), dtype=torch.uint8, device='cuda')\n"
+        "dst = torch.zeros(nb * stride, dtype=torch.uint8, device='cuda')\n"
+        "sizes = torch.zeros(nb, dtype=torch.int32, device='cuda')\n"
+        "def run(comp, n=nb):\n"
+        "    dig.zero_(); dst.zero_(); sizes.zero_()\n"
+        "    if comp == 'lz4': cw.dev_hash_and_compress('skein512', comp, src.data_ptr(), bs, n, dig.data_ptr(), dst.data_ptr(), stride, sizes.data_ptr(), s)\n"
+        "    else: cw.dev_compress(comp, src.data_ptr(), bs, n, dst.data_ptr(), stride, sizes.data_ptr(), s)\n"
+        "    torch.cuda.synchronize()\n"
+        "    z, d = sizes.cpu().numpy().astype(np.uint32), dst.cpu().numpy().reshape(nb, stride)\n"
+        "    h = hashlib.sha256(dig.cpu().numpy().tobytes() + z.tobytes())\n"
+        "    for i in range(n): h.update(d[i, :z[i]].tobytes())\n"
+        "    return h.hexdigest()\n"
+        "def used():\n"
+        "    torch.cuda.synchronize()\n"
+        "    free, total = torch.cuda.mem_get_info()\n"
+        "    return total - free\n"
+        "with cw.tuned(CW_LZ4_LANES=1, CW_LZF_LANES=1):\n"
+        "    run('lz4'); run('lzf'); cw.shutdown(); cw.init(0)   # unmeasured: first use may allocate process-wide state\n"
+        "    run('lz4', 64)                                       # the thread's context exists\n"
+        "    before = used()\n"
+        "    print('lz4', run('lz4')); print('lzf', run('lzf'))\n"
+        "    held = used()\n"
+        "    cw.shutdown()\n"
+        "    after = used()\n"
+        "    print('mem', before, held, after)\n"
+        "    cw.init(0)\n"
+        "    print('lz4', run('lz4'))\n" % (ROOT, ROOT))
+    r = subprocess.run([sys.executable, "-c", prog], capture_output=True, text=True, timeout=600, env=dict(os.environ))
+    assert r.returncode == 0, r.stderr[-3000:]
+    data, bs, nb = _shutdown_data(), 4096, 4096
+    blocks = [data[i * bs:(i + 1) * bs] for i in range(nb)]
+    want = {}
+    for comp, cfn in (("lz4", oracle.lz4_compress), ("lzf", oracle.lzf_compress)):
+        outs = [cfn(b) for b in blocks]
+        digs = b"".join(oracle.skein512(b, 512) for b in blocks) if comp == "lz4" else bytes(nb * 64)
+        want[comp] = hashlib.sha256(digs + np.array([len(o) for o in outs], dtype=np.uint32).tobytes() + b"".join(outs)).hexdigest()
+    lines = [ln.split() for ln in r.stdout.strip().splitlines()]
+    print(r.stdout)
+    assert [ln[0] for ln in lines] == ["lz4", "lzf", "mem", "lz4"], r.stdout
+    assert lines[0][1] == want["lz4"] and lines[1][1] == want["lzf"]
+    before, held, after = (int(v) for v in lines[2][1:])
+    assert held - before > (64 << 20), (before, held, after)    # the calls did allocate scratch a leak of which would show
+    assert after - before < (64 << 20), (before, held, after)   # ... and cw_shutdown gave it back
+    assert lines[3][1] == want["lz4"]                           # the library works again after cw_init
