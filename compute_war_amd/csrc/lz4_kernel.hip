@@ -461,53 +461,64 @@ lz4_scan_stream_kernel(const uint8_t *__restrict__ src, uint32_t n, size_t src_s
 // span re-read its last chunk), the chunk pipeline runs across the block boundaries inside a span (so 4 KiB blocks
 // are pipelined at all), and the waits come out as vmcnt(N) with the next chunks still in flight.
 // Step i: store chunk i-1 (speculatively, as before), load chunk i+2 into the registers that frees, finish the
-// previous block if chunk i starts a new one, stage chunk i in the LDS ring, probe the positions below it.
+// previous block if chunk i starts a new one, stage chunk i in the LDS ring, run the probe groups that end in or before it.
 // ---------------------------------------------------------------------------------------------------
-// The span scan's probe schedule.  Which probes fall below a chunk boundary depends only on n, so lane c of kend holds the number of
-// probes at positions < c * 4 KiB (computed once per wavefront by a binary search) and a chunk runs exactly kend[c] - knext probes in
-// batches of 64, the last one partial.  A batch's verdicts are wave masks (the v_cmp results themselves), so that the judge costs a few
-// scalar ANDs/ORs instead of per-lane booleans under exec-mask branches.
-__device__ __forceinline__ uint32_t probe_pos(uint32_t k) // 1 + probe_delta(k): with q = (k + 62) >> 6 it is q * (k + 31 - 32 q) + 2
+// The span scan's probe schedule.  With q = (k + 62) >> 6 the probes k = 64 q - 62 .. 64 q + 1 form GROUP q: 64 probes whose positions
+// are an arithmetic progression with stride q, pos = q * (k + 31 - 32 q) + 2 (probe_pos below is the serial statement).  A batch is one
+// group, lane L its probe k = 64 q - 62 + L at group_base(q) + q * L: base and stride are wave-uniform and only a block's first group
+// (k = 0, 1 in lanes 62, 63; k = 0 sits at position 1, off the progression) and its last one are partial.  The widest group of a 64 KiB
+// block spans 45 * 63 bytes, less than a chunk, so after chunk c has been staged (ring = chunks c - 1 and c) every group not yet run
+// whose last position + 4 lies at or below the end of chunk c runs: its first position is still in the ring, none of its probes
+// straddles into chunk c + 1, and none runs later than under the rule "positions below chunk c".  Which groups those are depends only
+// on n: lane c of gend holds their number (group_end, once per wavefront).  A batch's verdicts are wave masks (the v_cmp results
+// themselves), so that the judge costs a few scalar ANDs/ORs instead of per-lane booleans under exec-mask branches.
+__device__ __forceinline__ uint32_t probe_pos(uint32_t k) // 1 + probe_delta(k)
 {
     const uint32_t q = (k + 62) >> 6;
     return q * (k + 31 - 32 * q) + 1 + (uint32_t)(k != 0); // k = 0 (q = 0) is position 1
 }
 
-__device__ __forceinline__ uint32_t probe_kend(uint32_t end, uint32_t nprobes) // probes at positions < end
+__device__ __forceinline__ uint32_t group_base(uint32_t q) { return q * (32 * q - 31) + 2; } // probe_pos(64 q - 62), q >= 1
+
+// number of groups q < qlast whose last position + 4 = group_base(q) + 63 q + 4 lies at or below end
+__device__ __forceinline__ uint32_t group_end(uint32_t end, uint32_t qlast)
 {
-    uint32_t lo = 0, hi = nprobes;
+    uint32_t lo = 0, hi = qlast;
     while (lo < hi) {
         const uint32_t mid = (lo + hi) >> 1;
-        if (probe_pos(mid) < end) lo = mid + 1;
+        if (32 * mid * mid + 32 * mid + 6 <= end) lo = mid + 1;
         else hi = mid;
     }
     return lo;
 }
 
-// NG batches of 64 probes from k = kb (PART: only the first rem of them are real).  All ring reads, then all table exchanges, then all
-// verdicts, then the rare settling of fingerprint hits.  Returns whether the block has a match.  The semantics are those of scan_issue /
-// scan_judge / scan_settle, with the epoch test written on the whole word: entries never carry a later epoch than the current one, so
-// "same epoch" is old >= tag and "same epoch and cand >= pos" is old >= tag | pos << 12.  Every verdict is the ballot of ONE compare,
-// i.e. the v_cmp's own mask, combined with scalar ANDs/ORs.
+struct SpanWalk { // progress of one block's no-match walk in the span scan
+    uint32_t qnext = 0, v0 = 0; // first group that has not run yet; bytes 0..3 of the block
+    bool marked = false;
+};
+
+// NG batches: lane L of batch j probes position pos[j] (PART: only lanes lo <= L < hi are real).  All ring reads, then all table
+// exchanges, then all verdicts, then the rare settling of fingerprint hits.  Returns whether the block has a match.  The semantics are
+// those of scan_issue / scan_judge / scan_settle, with the epoch test written on the whole word: entries never carry a later epoch than
+// the current one, so "same epoch" is old >= tag and "same epoch and cand >= pos" is old >= tag | pos << 12.  Every verdict is the
+// ballot of ONE compare, i.e. the v_cmp's own mask, combined with scalar ANDs/ORs.
 template <int NG, bool PART>
-__device__ __forceinline__ bool probe_batches(uint32_t kb, uint32_t rem, uint32_t *tab, const uint32_t *ring32, uint32_t tag, uint32_t v0,
-                                              const uint8_t *g, uint32_t lane)
+__device__ __forceinline__ bool probe_batches(const uint32_t (&pos)[NG], uint32_t lo, uint32_t hi, uint32_t *tab, const uint32_t *ring32,
+                                              uint32_t tag, uint32_t v0, const uint8_t *g, uint32_t lane)
 {
-    uint32_t pos[NG], v[NG], tp[NG], fp[NG], old[NG];
-    unsigned long long actm[NG];
+    uint32_t v[NG], tp[NG], fp[NG], old[NG];
+    const bool act = !PART || (lane >= lo && lane < hi);
+    const unsigned long long actm = PART ? __ballot(act) : ~0ull;
 #pragma unroll
     for (int j = 0; j < NG; j++) {
-        pos[j] = probe_pos(kb + 64 * j + lane);
         // the probe's 4 bytes: two aligned ring dwords (the second may wrap) + byte align (v_alignbyte_b32 uses the low 2 bits)
         const uint8_t *r8 = reinterpret_cast<const uint8_t *>(ring32);
-        const uint32_t lo = *reinterpret_cast<const uint32_t *>(r8 + (pos[j] & (kRing - 4)));
-        const uint32_t hi = *reinterpret_cast<const uint32_t *>(r8 + ((pos[j] + 4) & (kRing - 4)));
-        v[j] = __builtin_amdgcn_alignbyte(hi, lo, pos[j]);
+        const uint32_t wlo = *reinterpret_cast<const uint32_t *>(r8 + (pos[j] & (kRing - 4)));
+        const uint32_t whi = *reinterpret_cast<const uint32_t *>(r8 + ((pos[j] + 4) & (kRing - 4)));
+        v[j] = __builtin_amdgcn_alignbyte(whi, wlo, pos[j]);
     }
 #pragma unroll
     for (int j = 0; j < NG; j++) {
-        const bool act = !PART || 64 * j + lane < rem;
-        actm[j] = PART ? __ballot(act) : ~0ull;
         const uint32_t h = v[j] * 2654435761u;
         fp[j] = (h >> 7) & 0xFFFu;
         tp[j] = tag | (pos[j] << 12);
@@ -518,8 +529,8 @@ __device__ __forceinline__ bool probe_batches(uint32_t kb, uint32_t rem, uint32_
     for (int j = 0; j < NG; j++) {
         // an empty slot (earlier epoch) means candidate 0; a candidate >= pos means the atomics ran out of lane order
         const unsigned long long empty = __ballot(old[j] < tag);
-        hit |= (__ballot(old[j] >= tp[j]) | (empty & __ballot(v[j] == v0))) & actm[j];
-        const unsigned long long fm = __ballot(((old[j] ^ fp[j]) & 0xFFFu) == 0) & ~empty & actm[j];
+        hit |= (__ballot(old[j] >= tp[j]) | (empty & __ballot(v[j] == v0))) & actm;
+        const unsigned long long fm = __ballot(((old[j] ^ fp[j]) & 0xFFFu) == 0) & ~empty & actm;
         hit |= fm & maybe; // a second fingerprint hit before settling: let the parser decide
         maybe |= fm;
     }
@@ -527,7 +538,7 @@ __device__ __forceinline__ bool probe_batches(uint32_t kb, uint32_t rem, uint32_
         uint32_t mcand = 0, mv = 0;
 #pragma unroll
         for (int j = 0; j < NG; j++) {
-            const bool f = (((PART ? actm[j] : ~0ull) >> lane) & 1u) && old[j] >= tag && ((old[j] ^ fp[j]) & 0xFFFu) == 0;
+            const bool f = act && old[j] >= tag && ((old[j] ^ fp[j]) & 0xFFFu) == 0;
             mcand = f ? (old[j] >> 12) & 0xFFFFu : mcand;
             mv = f ? v[j] : mv;
         }
@@ -545,17 +556,35 @@ __device__ __forceinline__ void store16_nt(uint8_t *p, uint32_t x, uint32_t y, u
     __builtin_nontemporal_store(v, reinterpret_cast<u32x4 *>(p));
 }
 
-// the probes [w.knext, ke) of the block
-__device__ __forceinline__ void probe_range(Walk &w, uint32_t ke, uint32_t *tab, const uint32_t *ring32, uint32_t tag, const uint8_t *g,
+// the partial group q of the block (its first, q = 0: probes 0 and 1 at positions 1 and 2 in lanes 62 and 63; or its last)
+__device__ __forceinline__ void probe_partial(SpanWalk &w, uint32_t q, uint32_t nprobes, uint32_t *tab, const uint32_t *ring32, uint32_t tag,
+                                              const uint8_t *g, uint32_t lane)
+{
+    // these positions are the same for every block: computed where they are used, they do not hold registers across the span loop
+    asm volatile("" : "+v"(lane));
+    const uint32_t pos[1] = {q ? __umul24(q, lane) + group_base(q) : lane - 61};
+    const uint32_t left = nprobes + 62 - 64 * q; // lanes up to the block's last probe
+    w.marked = probe_batches<1, true>(pos, q ? 0u : 62u, left < 64 ? left : 64u, tab, ring32, tag, w.v0, g, lane);
+    w.qnext = q + 1;
+}
+
+// the full groups [w.qnext, qe) of the block, two at a time.  From group q to q + 1 a lane's position grows by
+// group_base(q + 1) - group_base(q) + lane = 64 q + 1 + lane.
+__device__ __forceinline__ void probe_range(SpanWalk &w, uint32_t qe, uint32_t *tab, const uint32_t *ring32, uint32_t tag, const uint8_t *g,
                                             uint32_t lane)
 {
-    uint32_t kb = w.knext;
-    for (; kb + 128 <= ke; kb += 128)
-        if (probe_batches<2, false>(kb, 0, tab, ring32, tag, w.v0, g, lane)) { w.marked = true; return; }
-    const uint32_t rem = ke - kb;
-    if (rem > 64) w.marked = probe_batches<2, true>(kb, rem, tab, ring32, tag, w.v0, g, lane);
-    else if (rem) w.marked = probe_batches<1, true>(kb, rem, tab, ring32, tag, w.v0, g, lane);
-    w.knext = ke;
+    uint32_t q = w.qnext;
+    w.qnext = qe;
+    uint32_t p = __umul24(q, lane) + group_base(q);
+    for (; q + 2 <= qe; q += 2) {
+        const uint32_t pos[2] = {p, p + lane + (64 * q + 1)};
+        if (probe_batches<2, false>(pos, 0, 64, tab, ring32, tag, w.v0, g, lane)) { w.marked = true; return; }
+        p = pos[1] + lane + (64 * q + 65);
+    }
+    if (q < qe) {
+        const uint32_t pos[1] = {p};
+        w.marked = probe_batches<1, false>(pos, 0, 64, tab, ring32, tag, w.v0, g, lane);
+    }
 }
 
 #ifdef CW_CLOCK_STAMP
@@ -584,7 +613,9 @@ lz4_scan_span_kernel(const uint8_t *__restrict__ src, uint32_t n, size_t src_str
     const uint32_t cmask = (1u << lg) - 1, run = 16u >> lg; // chunks per block - 1, blocks per span
     const uint32_t hdr = 1 + (n - 15) / 255 + 1;            // token + length bytes of the single literal run (n >= 4096)
     const uint32_t lane16 = lane * 16;
-    const uint32_t kend = probe_kend(lane * kChunk, nprobes); // lane c: probes below chunk c of a block (lane >= 16: all)
+    const uint32_t qlast = (nprobes + 61) >> 6; // the block's last group, the one that holds probe nprobes - 1
+    // lane c: the groups that run once chunk c of a block has been staged; its last chunk (and any lane behind) gives qlast
+    const uint32_t gend = group_end((lane + 1) * kChunk < n ? (lane + 1) * kChunk : n, qlast);
     // the header's last two bytes (0xFF, (n - 15) % 255) as the high half of the dword in front of a block's first line
     const uint32_t hdrw = (0xFFu << 16) | (((n - 15) % 255) << 24);
 
@@ -599,7 +630,7 @@ lz4_scan_span_kernel(const uint8_t *__restrict__ src, uint32_t n, size_t src_str
         const uint8_t *gs = src + first * src_stride;
         uint8_t *os = dst + first * dst_stride + (ALIGNED ? hdr - 2 : hdr);
 
-        Walk w;
+        SpanWalk w;
         size_t blk = first;
         uint32_t tag = 0, marks = 0; // marks: bit b = block first + b of the span has a match
         Chunk r0, r1, r2;
@@ -636,8 +667,8 @@ lz4_scan_span_kernel(const uint8_t *__restrict__ src, uint32_t n, size_t src_str
             }                                                                                                \
         } while (0)
 #define CW_FINISH()                                                                                          \
-        do { /* the block's last probes (nothing straddles its end), then its verdict */                     \
-            if (!w.marked) probe_range(w, nprobes, tab, ring32, tag, src + blk * src_stride, lane);          \
+        do { /* the block's last group (every group in front of it ran when the last chunk was staged), then its verdict */ \
+            if (nprobes && !w.marked) probe_partial(w, qlast, nprobes, tab, ring32, tag, src + blk * src_stride, lane); \
             if (w.marked) marks |= 1u << (uint32_t)(blk - first); /* queued at the end of the span */        \
             else {                                                                                           \
                 uint8_t *out = dst + blk * dst_stride;                                                       \
@@ -656,7 +687,7 @@ lz4_scan_span_kernel(const uint8_t *__restrict__ src, uint32_t n, size_t src_str
             blk = first + ((I) >> lg);                                                                       \
             scan_begin_block(tab, epoch, lane);                                                              \
             tag = epoch << 28;                                                                               \
-            w = Walk();                                                                                      \
+            w = SpanWalk();                                                                                  \
         } while (0)
 #define CW_STAGE_IN(R, C)                                                                                    \
         do {                                                                                                 \
@@ -671,9 +702,9 @@ lz4_scan_span_kernel(const uint8_t *__restrict__ src, uint32_t n, size_t src_str
                     const uint32_t h0 = w.v0 * 2654435761u;                                                  \
                     atomicMax(&tab[h0 >> 19], tag | ((h0 >> 7) & 0xFFFu)); /* position 0 */                  \
                 }                                                                                            \
-            } else if (!w.marked) {                                                                          \
-                probe_range(w, __builtin_amdgcn_readlane(kend, (C)), tab, ring32, tag, src + blk * src_stride, lane); \
+                if (qlast) probe_partial(w, 0u, nprobes, tab, ring32, tag, src + blk * src_stride, lane);    \
             }                                                                                                \
+            if (!w.marked) probe_range(w, __builtin_amdgcn_readlane(gend, (C)), tab, ring32, tag, src + blk * src_stride, lane); \
         } while (0)
 #define CW_STEP(PREV, CUR, I)                                                                                \
         do {                                                                                                 \

@@ -376,6 +376,10 @@ skein_lines_kernel(const uint8_t *__restrict__ src, size_t block_bytes, size_t s
 // hash is as fast as the one-launch line kernel (46.6 ms per Mi blocks, a little ahead on small batches), so it is used
 // there too; the line kernel serves batches below 4,096 blocks and short messages.
 // ---------------------------------------------------------------------------------------------------
+// INTERIOR: a slice whose steps and prefetches all lie inside the message (the launch guarantees s_end - s_begin a multiple of the steps
+// per line and s_end + one line <= the message steps): every step is a plain message step and no prefetched line needs the "past the
+// message" mask or the clamped address, i.e. 32 v_cndmask_b32 + the compares per loop iteration less.  All but a hash's last slice are
+// launched so; the two instantiations never run in the same launch, so the instruction cache holds one loop body at a time as before.
 constexpr uint32_t kSkeinSlices = 8;
 
 #ifdef CW_CLOCK_STAMP
@@ -383,7 +387,7 @@ __device__ unsigned long long g_clock_skein[4 * kClockSlots];
 hipError_t skein_clock_read(unsigned long long *out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_clock_skein), sizeof g_clock_skein); }
 #endif
 
-template <int NW, bool ALIGNED16>
+template <int NW, bool ALIGNED16, bool INTERIOR>
 __global__ void __launch_bounds__(CW_SKEIN_THREADS)
 skein_slice_kernel(const uint8_t *__restrict__ src, size_t block_bytes, size_t src_stride, size_t nblocks, SkeinIV iv,
                    uint8_t *__restrict__ digests, unsigned digest_bytes, uint64_t *__restrict__ state, size_t s_begin, size_t s_end)
@@ -411,17 +415,25 @@ skein_slice_kernel(const uint8_t *__restrict__ src, size_t block_bytes, size_t s
 #pragma unroll
         for (unsigned j = 0; j < HS; j++) {
             const size_t s = first + j;
-            const uint64_t keep = s < nmsg ? ~0ull : 0ull; // wave-uniform
-            load_words<NW, ALIGNED16>(dst[j], p + (s < nmsg ? s : nmsg - 1) * BB);
+            if constexpr (INTERIOR) {
+                load_words<NW, ALIGNED16>(dst[j], p + s * BB);
+            } else {
+                const uint64_t keep = s < nmsg ? ~0ull : 0ull; // wave-uniform
+                load_words<NW, ALIGNED16>(dst[j], p + (s < nmsg ? s : nmsg - 1) * BB);
 #pragma unroll
-            for (int k = 0; k < NW; k++) dst[j][k] &= keep;
+                for (int k = 0; k < NW; k++) dst[j][k] &= keep;
+            }
         }
     };
     auto run_half = [&](uint64_t (&buf)[HS][NW], size_t first) {
 #pragma unroll
         for (unsigned j = 0; j < HS; j++) {
             const size_t s = first + j;
-            if (s < s_end) {
+            if constexpr (INTERIOR) {
+                t0 += BB;
+                Ubi<NW>::run(X, buf[j], t0, t1);
+                t1 &= ~T1_FIRST;
+            } else if (s < s_end) {
                 if (s + 1 < nmsg) {
                     t0 += BB;
                 } else if (s + 1 == nmsg) {
@@ -441,8 +453,12 @@ skein_slice_kernel(const uint8_t *__restrict__ src, size_t block_bytes, size_t s
 #pragma unroll 1
     for (size_t first = s_begin; first < s_end; first += SPL) {
         run_half(A, first);
+        // without the masks nothing ties the spare half's loads to this place: the scheduler sinks them behind the rounds of B (loading
+        // straight into B's registers) or hoists them to the loop top, and either way the line is requested in two parts.  Hence the fences.
+        if constexpr (INTERIOR) __builtin_amdgcn_sched_barrier(0);
         fetch_half(A, first + SPL);
         fetch_half(S, first + SPL + HS);
+        if constexpr (INTERIOR) __builtin_amdgcn_sched_barrier(0);
         run_half(B, first + HS);
 #pragma unroll
         for (unsigned j = 0; j < HS; j++)
@@ -450,7 +466,7 @@ skein_slice_kernel(const uint8_t *__restrict__ src, size_t block_bytes, size_t s
             for (int k = 0; k < NW; k++) B[j][k] = S[j][k];
     }
 
-    if (s_end < total) {
+    if (INTERIOR || s_end < total) {
 #pragma unroll
         for (int i = 0; i < NW; i++) st[i] = X[i];
         return;
@@ -492,16 +508,25 @@ hipError_t skein_sliced_launch(int nw, const uint8_t *src, size_t block_bytes, s
     if (err != hipSuccess) return err;
     uint64_t *state = w.as<uint64_t>();
     const dim3 grid((unsigned)((nblocks + CW_SKEIN_THREADS - 1) / CW_SKEIN_THREADS)), block(CW_SKEIN_THREADS);
+    bool interior_used = false;
     for (size_t b = 0; b < total; b += slice_steps) {
         const size_t e = b + slice_steps < total ? b + slice_steps : total;
-        if (nw == 8)
-            hipLaunchKernelGGL((skein_slice_kernel<8, true>), grid, block, 0, stream, src, block_bytes, src_stride, nblocks, iv, digests,
+        // 8 words only: for 4 words hipcc moves a quarter of the mask-free line request to the loop top
+        const bool interior = nw == 8 && (e - b) % spl == 0 && e + spl <= total - 1; // the slice and its prefetches stay inside the message
+        interior_used |= interior;
+        if (interior)
+            hipLaunchKernelGGL((skein_slice_kernel<8, true, true>), grid, block, 0, stream, src, block_bytes, src_stride, nblocks, iv, digests,
+                               digest_bytes, state, b, e);
+        else if (nw == 8)
+            hipLaunchKernelGGL((skein_slice_kernel<8, true, false>), grid, block, 0, stream, src, block_bytes, src_stride, nblocks, iv, digests,
                                digest_bytes, state, b, e);
         else
-            hipLaunchKernelGGL((skein_slice_kernel<4, true>), grid, block, 0, stream, src, block_bytes, src_stride, nblocks, iv, digests,
+            hipLaunchKernelGGL((skein_slice_kernel<4, true, false>), grid, block, 0, stream, src, block_bytes, src_stride, nblocks, iv, digests,
                                digest_bytes, state, b, e);
     }
-    note_kernels(1, nw == 8 ? "cw::skein_slice_kernel<8, true>" : "cw::skein_slice_kernel<4, true>");
+    note_kernels(1, interior_used ? "cw::skein_slice_kernel<8, true, true> + cw::skein_slice_kernel<8, true, false>"
+                    : nw == 8     ? "cw::skein_slice_kernel<8, true, false>"
+                                  : "cw::skein_slice_kernel<4, true, false>");
     return hipGetLastError();
 }
 

@@ -3,7 +3,7 @@
 
   peak = SIMDs x bytes per wavefront-call / sum over the kernel's VALU opcodes of (count per Threefish call x measured issue cost)
 
-  counts  from the ISA hipcc emits for cw::skein_slice_kernel<8, true> (csrc/skein_kernels.hip; two Threefish bodies per loop)
+  counts  from the ISA hipcc emits for cw::skein_slice_kernel<8, true, false> (csrc/skein_kernels.hip; two Threefish bodies per loop)
   costs   from tools/ubench.hip run on the MI355X: profiles/r02_ubench_valu_issue.txt (ns per wavefront-instruction per SIMD
           at 8 wavefronts per SIMD, whole chip, wall clock)
 """
@@ -34,7 +34,7 @@ def counts():
         subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-S", "--cuda-device-only",
                         os.path.join(ROOT, "compute_war_amd", "csrc", "skein_kernels.hip"), "-o", s], check=True, capture_output=True)
         text = open(s).read()
-    m = re.search(r"^(_ZN2cw18skein_slice_kernelILi8ELb1EEE\w*):.*?s_endpgm", text, re.S | re.M)
+    m = re.search(r"^(_ZN2cw18skein_slice_kernelILi8ELb1ELb0EEE\w*):.*?s_endpgm", text, re.S | re.M)
     body = m.group(0)
     c = {op: len(re.findall(r"^\s+" + op + r"(?:_e32|_e64)?\s", body, re.M)) for op in OPS}
     total_valu = len(re.findall(r"^\s+v_\w+", body, re.M))
@@ -49,7 +49,7 @@ def main():
     simds, bytes_per_call = 256 * 4, 64 * 64   # 64 lanes x 64 message bytes
     peak = simds * bytes_per_call / ns          # bytes per ns = GB/s
     out = {
-        "kernel": "cw::skein_slice_kernel<8, true>", "symbol": sym,
+        "kernel": "cw::skein_slice_kernel<8, true, false>", "symbol": sym,
         "instr_per_threefish_call": per_call, "all_valu_in_kernel": total_valu,
         "ns_per_wave_instr_per_simd": {op: cost[OPS[op]] for op in OPS},
         "ns_per_wave_call_per_simd": round(ns, 1), "simds": simds, "bytes_per_wave_call": bytes_per_call,
