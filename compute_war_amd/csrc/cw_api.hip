@@ -1295,6 +1295,36 @@ int dev_hash_chunks(int alg, const uint8_t *d_src, size_t src_bytes, const uint6
     return CW_OK;
 }
 
+// chunk indices are u32 on the device (the order, d_sel), as the dedupe's block indices are
+constexpr size_t kMaxChunks = ((size_t)1 << 32) - 256;
+
+// everything cw_dev_compress_chunks refuses, none of it needing a device
+int compress_chunks_args(int comp_alg, const void *d_src, size_t src_bytes, const uint64_t *d_offsets, const uint64_t *d_nchunks,
+                         size_t max_chunks, const uint32_t *d_sel, const uint64_t *d_nsel, const void *d_dst, size_t dst_bytes,
+                         const uint32_t *d_sizes)
+{
+    if (comp_alg != CW_COMP_LZ4 && comp_alg != CW_COMP_LZF) return fail(CW_ERR_BAD_ARG, "unknown compression algorithm %d", comp_alg);
+    if (max_chunks > kMaxChunks) return fail(CW_ERR_BAD_ARG, "max_chunks %zu > 2^32 - 256", max_chunks);
+    if (src_bytes > ((size_t)1 << 62)) return fail(CW_ERR_BAD_ARG, "src_bytes %zu not usable", src_bytes);
+    if (!d_offsets || !d_nchunks || !d_dst || !d_sizes || (src_bytes && !d_src) || (d_sel && !d_nsel)) return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    const size_t need = (size_t)cw::chunk_slot_offset(comp_alg == CW_COMP_LZ4, src_bytes, max_chunks) + 16;
+    if (dst_bytes < need) return fail(CW_ERR_BAD_ARG, "dst_bytes %zu < cw_chunk_slots_bytes = %zu", dst_bytes, need);
+    return CW_OK;
+}
+
+int dev_compress_chunks(int comp_alg, const uint8_t *d_src, size_t src_bytes, const uint64_t *d_offsets, const uint64_t *d_nchunks,
+                        size_t max_chunks, const uint32_t *d_sel, const uint64_t *d_nsel, uint8_t *d_dst, uint32_t *d_sizes, hipStream_t s)
+{
+    ProfScope prof(PROF_CODEC, s);
+    const hipError_t e = cw::chunk_compress_launch(comp_alg == CW_COMP_LZF, d_src, src_bytes, d_offsets, d_nchunks, max_chunks, d_sel, d_nsel,
+                                                   d_dst, d_sizes, s);
+    if (e == hipErrorOutOfMemory)
+        return fail(CW_ERR_NOMEM, "chunk parser workspace (order %zu bytes, lane tables of %zu bytes each): %s", (2048 + max_chunks) * 4,
+                    cw::chunk_lane_table_bytes(comp_alg == CW_COMP_LZF), hipGetErrorString(e));
+    if (e != hipSuccess) return fail(CW_ERR_HIP, "compress chunks launch: %s", hipGetErrorString(e));
+    return CW_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -1338,6 +1368,54 @@ int cw_dev_hash_chunks(int hash_alg, const void *d_src, size_t src_bytes, const 
     if (rc != CW_OK) return rc;
     return dev_hash_chunks(hash_alg, (const uint8_t *)d_src, src_bytes, d_offsets, d_nchunks, max_chunks, (uint8_t *)d_digests,
                            (hipStream_t)stream);
+}
+
+uint64_t cw_chunk_slot_offset(int comp_alg, uint64_t o, uint64_t i) { return cw::chunk_slot_offset(comp_alg != CW_COMP_LZF, o, i); }
+size_t cw_chunk_slots_bytes(int comp_alg, size_t src_bytes, size_t max_chunks)
+{
+    return (size_t)cw_chunk_slot_offset(comp_alg, src_bytes, max_chunks) + 16;
+}
+
+int cw_dev_compress_chunks(int comp_alg, const void *d_src, size_t src_bytes, const uint64_t *d_offsets, const uint64_t *d_nchunks,
+                           size_t max_chunks, const uint32_t *d_sel, const uint64_t *d_nsel, void *d_dst, size_t dst_bytes,
+                           uint32_t *d_sizes, void *stream)
+{
+    int rc = compress_chunks_args(comp_alg, d_src, src_bytes, d_offsets, d_nchunks, max_chunks, d_sel, d_nsel, d_dst, dst_bytes, d_sizes);
+    if (rc != CW_OK) return rc;
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    return dev_compress_chunks(comp_alg, (const uint8_t *)d_src, src_bytes, d_offsets, d_nchunks, max_chunks, d_sel, d_nsel, (uint8_t *)d_dst,
+                               d_sizes, (hipStream_t)stream);
+}
+
+int cw_dev_pack_chunks(int comp_alg, const void *d_slots, const uint64_t *d_offsets, const uint32_t *d_sel, const uint64_t *d_count,
+                       size_t max_count, const uint32_t *d_sizes, void *d_packed, uint64_t *d_packed_offsets, void *stream)
+{
+    if (comp_alg != CW_COMP_LZ4 && comp_alg != CW_COMP_LZF) return fail(CW_ERR_BAD_ARG, "unknown compression algorithm %d", comp_alg);
+    if (max_count > kMaxChunks) return fail(CW_ERR_BAD_ARG, "max_count %zu > 2^32 - 256", max_count);
+    if (!d_packed_offsets || (max_count && (!d_count || !d_sizes || (d_packed && (!d_slots || !d_offsets)))))
+        return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    int rc = ensure_init();
+    if (rc != CW_OK) return rc;
+    const hipError_t e = cw::chunk_pack_launch(comp_alg == CW_COMP_LZF, (const uint8_t *)d_slots, d_offsets, d_sel, d_count, max_count, d_sizes,
+                                               (uint8_t *)d_packed, d_packed_offsets, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? CW_ERR_NOMEM : CW_ERR_HIP, "pack chunks launch: %s", hipGetErrorString(e));
+    return CW_OK;
+}
+
+int cw_dev_decompress_chunks(int comp_alg, const void *d_comp, const uint64_t *d_comp_offsets, const uint64_t *d_raw_offsets,
+                             const uint64_t *d_count, size_t max_count, void *d_dst, size_t dst_bytes, uint32_t *d_status, void *stream)
+{
+    if (comp_alg != CW_COMP_LZ4 && comp_alg != CW_COMP_LZF) return fail(CW_ERR_BAD_ARG, "unknown compression algorithm %d", comp_alg);
+    if (max_count > kMaxChunks) return fail(CW_ERR_BAD_ARG, "max_count %zu > 2^32 - 256", max_count);
+    if (max_count && (!d_comp || !d_comp_offsets || !d_raw_offsets || !d_count || !d_status || (dst_bytes && !d_dst)))
+        return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    int rc = ensure_init();
+    if (rc != CW_OK) return rc;
+    ProfScope prof(PROF_CODEC, (hipStream_t)stream);
+    const hipError_t e = cw::chunk_decompress_launch(comp_alg == CW_COMP_LZF, (const uint8_t *)d_comp, d_comp_offsets, d_raw_offsets, d_count,
+                                                     max_count, (uint8_t *)d_dst, dst_bytes, d_status, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(CW_ERR_HIP, "decompress chunks launch: %s", hipGetErrorString(e));
+    return CW_OK;
 }
 
 // Pieces of at most kMaxChunkBytes: each piece is chunked with final = 0 (the last with final = 1); the bytes after the last
@@ -1592,6 +1670,50 @@ int cw_dev_hash_dedupe_compress(cw_dedupe_t *x, int comp_alg, const void *d_src,
     }
     HIP_TRY(hipEventRecord(x->last, s));
     if (rc == CW_OK) *n_new = k;
+    return rc;
+}
+
+// cdc -> hash of every chunk -> one 8-byte copy back + a synchronise (the dedupe's admit check and launch need the count on the
+// host) -> dedupe -> the chunk codec over the new chunks, selected on the device: n_new never comes back to the host.
+int cw_dev_cdc_dedupe_compress(cw_dedupe_t *x, const cw_cdc_params *p, int comp_alg, const void *d_src, size_t nbytes, int final,
+                               uint64_t base, uint64_t *d_offsets, size_t max_offsets, uint64_t *d_nchunks, void *d_digests, uint64_t *d_ref,
+                               uint32_t *d_new_idx, uint64_t *d_n_new, void *d_dst, size_t dst_bytes, uint32_t *d_sizes, size_t *nchunks,
+                               void *stream)
+{
+    if (nchunks) *nchunks = 0;
+    cw::CdcParams cp;
+    int rc = cdc_params(p, &cp);
+    if (rc != CW_OK) return rc;
+    if (!nchunks) return fail(CW_ERR_BAD_ARG, "NULL nchunks");
+    if (!d_offsets || !d_nchunks || !d_digests || !d_ref || !d_new_idx || !d_n_new || (nbytes && !d_src)) return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    if (max_offsets < nbytes / cp.min_size + 2)
+        return fail(CW_ERR_BAD_ARG, "max_offsets %zu < nbytes / min_size + 2 = %zu", max_offsets, nbytes / cp.min_size + 2);
+    if ((uintptr_t)d_digests % 8) return fail(CW_ERR_BAD_ARG, "d_digests must be 8-byte aligned");
+    const size_t max_chunks = max_offsets - 1;
+    if ((rc = compress_chunks_args(comp_alg, d_src, nbytes, d_offsets, d_nchunks, max_chunks, d_new_idx, d_n_new, d_dst, dst_bytes, d_sizes)) != CW_OK)
+        return rc;
+    if ((rc = dedupe_args(x, 0, base)) != CW_OK) return rc; // (base + the chunk count: checked when the count is known, as cw_dev_dedupe would)
+    const hipStream_t s = (hipStream_t)stream;
+    const uint8_t *src = (const uint8_t *)d_src;
+    std::lock_guard<std::mutex> g(x->lock);
+    HIP_TRY(hipStreamWaitEvent(s, x->last, 0));
+    rc = dev_cdc(cp, src, nbytes, final ? 1 : 0, d_offsets, max_offsets, d_nchunks, s);
+    if (rc == CW_OK) rc = dev_hash_chunks(x->hash_alg, src, nbytes, d_offsets, d_nchunks, max_chunks, (uint8_t *)d_digests, s);
+    if (rc != CW_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(x->h_ctrl, d_nchunks, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const size_t k = (size_t)x->h_ctrl[0];
+    *nchunks = k;
+    if (k == 0) { // (an empty input: cw_dev_dedupe would launch nothing)
+        HIP_TRY(hipMemsetAsync(d_n_new, 0, sizeof(uint64_t), s));
+        return CW_OK;
+    }
+    if (base > UINT64_MAX - k) return fail(CW_ERR_BAD_ARG, "base + nchunks wraps");
+    if ((rc = dedupe_admit(x, k)) != CW_OK) return rc; // offsets and digests are written; nothing inserted, nothing compressed
+    rc = dedupe_enqueue(x, (const uint64_t *)d_digests, (uint32_t)k, base, d_ref, d_new_idx, d_n_new, s);
+    if (rc == CW_OK)
+        rc = dev_compress_chunks(comp_alg, src, nbytes, d_offsets, d_nchunks, max_chunks, d_new_idx, d_n_new, (uint8_t *)d_dst, d_sizes, s);
+    HIP_TRY(hipEventRecord(x->last, s));
     return rc;
 }
 

@@ -196,6 +196,25 @@ __device__ __forceinline__ uint32_t chunk_keep(uint32_t v, int64_t valid)
     return valid >= 4 ? v : valid <= 0 ? 0u : v & ((1u << (8 * (unsigned)valid)) - 1u);
 }
 
+// ---- codecs over chunks (chunk_codec_kernels.hip, pack_kernels.hip; semantics: the public header) ------------------------
+// where compressed chunk i, at input offset o, goes in the slot buffer (cw_chunk_slot_offset)
+__host__ __device__ inline uint64_t chunk_slot_offset(bool lz4, uint64_t o, uint64_t i)
+{
+    return lz4 ? (o + o / 255 + 32 * i) & ~(uint64_t)15 : o;
+}
+// bytes of table per lane of the chunk parsers (the workspace holds up to 131,072 / 65,536 of them, LZ4 / LZF)
+size_t chunk_lane_table_bytes(int lzf);
+// sel == NULL: every chunk i < min(*d_nchunks, max_chunks); else the chunks sel[j], j < min(*d_nsel, max_chunks); sizes per position
+hipError_t chunk_compress_launch(int lzf, const uint8_t *src, size_t src_bytes, const uint64_t *offsets, const uint64_t *d_nchunks,
+                                 size_t max_chunks, const uint32_t *sel, const uint64_t *d_nsel, uint8_t *dst, uint32_t *sizes,
+                                 hipStream_t stream);
+hipError_t chunk_decompress_launch(int lzf, const uint8_t *comp, const uint64_t *comp_offsets, const uint64_t *raw_offsets,
+                                   const uint64_t *d_count, size_t max_count, uint8_t *dst, size_t dst_bytes, uint32_t *status,
+                                   hipStream_t stream);
+// pack_launch for chunk slots and a count on the device: packed_offsets[0..n], n = min(*d_count, max_count)
+hipError_t chunk_pack_launch(int lzf, const uint8_t *slots, const uint64_t *offsets, const uint32_t *sel, const uint64_t *d_count,
+                             size_t max_count, const uint32_t *sizes, uint8_t *packed, uint64_t *packed_offsets, hipStream_t stream);
+
 hipError_t sum_sizes_launch(const uint32_t *sizes, size_t n, uint32_t raw_bytes, uint64_t *totals, hipStream_t stream);
 hipError_t gen_random_launch(uint64_t seed, uint64_t first_block, size_t nblocks, size_t block_bytes, uint8_t *dst,
                              hipStream_t stream);

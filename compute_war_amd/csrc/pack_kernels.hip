@@ -7,6 +7,9 @@
 // Three small kernels for the exclusive scan (tile sums, scan of the tile sums by one workgroup, tile offsets) and
 // one copy kernel: a wavefront per slot, 16-byte aligned stores fed by unaligned loads.  The host batch API uses
 // the packed stream to bring a whole batch back in ONE device-to-host copy instead of one per block.
+//
+// cw_dev_pack_chunks is the same scan and copy for the chunk codecs' slots (chunk_codec_kernels.hip): the count is read on the device
+// and a position's slot is found through cw_chunk_slot_offset instead of a stride.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -27,8 +30,7 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
     return v;
 }
 
-__global__ void __launch_bounds__(kThreads)
-tile_sums_kernel(const uint32_t *__restrict__ sizes, size_t n, unsigned long long *__restrict__ partial)
+__device__ __forceinline__ void tile_sums(const uint32_t *__restrict__ sizes, size_t n, unsigned long long *__restrict__ partial)
 {
     __shared__ unsigned long long wsum[kThreads / 64];
     const size_t base = (size_t)blockIdx.x * kTile;
@@ -41,6 +43,12 @@ tile_sums_kernel(const uint32_t *__restrict__ sizes, size_t n, unsigned long lon
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) partial[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+__global__ void __launch_bounds__(kThreads)
+tile_sums_kernel(const uint32_t *__restrict__ sizes, size_t n, unsigned long long *__restrict__ partial)
+{
+    tile_sums(sizes, n, partial);
 }
 
 // one workgroup: exclusive scan of the tile sums in place
@@ -66,9 +74,8 @@ scan_partials_kernel(unsigned long long *__restrict__ partial, size_t ntiles)
     }
 }
 
-__global__ void __launch_bounds__(kThreads)
-tile_offsets_kernel(const uint32_t *__restrict__ sizes, size_t n, const unsigned long long *__restrict__ partial,
-                    unsigned long long *__restrict__ offsets)
+__device__ __forceinline__ void tile_offsets(const uint32_t *__restrict__ sizes, size_t n, const unsigned long long *__restrict__ partial,
+                                             unsigned long long *__restrict__ offsets)
 {
     __shared__ unsigned long long buf[kThreads];
     // thread t owns kPerThread consecutive entries of the tile
@@ -95,6 +102,13 @@ tile_offsets_kernel(const uint32_t *__restrict__ sizes, size_t n, const unsigned
     }
 }
 
+__global__ void __launch_bounds__(kThreads)
+tile_offsets_kernel(const uint32_t *__restrict__ sizes, size_t n, const unsigned long long *__restrict__ partial,
+                    unsigned long long *__restrict__ offsets)
+{
+    tile_offsets(sizes, n, partial, offsets);
+}
+
 __global__ void __launch_bounds__(64)
 pack_copy_kernel(const uint8_t *__restrict__ slots, size_t slot_stride, const uint32_t *__restrict__ sizes,
                  const unsigned long long *__restrict__ offsets, size_t n, uint8_t *__restrict__ out)
@@ -103,6 +117,41 @@ pack_copy_kernel(const uint8_t *__restrict__ slots, size_t slot_stride, const ui
     for (size_t i = blockIdx.x; i < n; i += gridDim.x) {
         const uint32_t len = sizes[i];
         if (len) lz::copy_g2g(out + offsets[i], slots + i * slot_stride, len, lane);
+    }
+}
+
+// ---- the same for chunk slots (cw_dev_pack_chunks): the count n = min(*d_count, max_count) is read on the device, the grids are
+// sized from max_count, sizes behind n count as 0 (tiles behind n sum to 0) and offsets behind entry n are not written ----
+__global__ void __launch_bounds__(kThreads)
+chunk_tile_sums_kernel(const uint32_t *__restrict__ sizes, const uint64_t *__restrict__ d_count, size_t max_count,
+                       unsigned long long *__restrict__ partial)
+{
+    const size_t n = *d_count < max_count ? (size_t)*d_count : max_count;
+    tile_sums(sizes, n, partial);
+}
+
+__global__ void __launch_bounds__(kThreads)
+chunk_tile_offsets_kernel(const uint32_t *__restrict__ sizes, const uint64_t *__restrict__ d_count, size_t max_count,
+                          const unsigned long long *__restrict__ partial, unsigned long long *__restrict__ offsets)
+{
+    const size_t n = *d_count < max_count ? (size_t)*d_count : max_count;
+    if (n == 0 && blockIdx.x == 0 && threadIdx.x == 0) offsets[0] = 0;
+    tile_offsets(sizes, n, partial, offsets);
+}
+
+// position i's bytes are in the slot of chunk sel[i] (chunk i without a selection); a position of size 0 has no slot to look at
+__global__ void __launch_bounds__(64)
+chunk_pack_copy_kernel(const uint8_t *__restrict__ slots, bool lz4, const uint64_t *__restrict__ chunk_offsets, const uint32_t *__restrict__ sel,
+                       const uint32_t *__restrict__ sizes, const unsigned long long *__restrict__ offsets, const uint64_t *__restrict__ d_count,
+                       size_t max_count, uint8_t *__restrict__ out)
+{
+    const size_t n = *d_count < max_count ? (size_t)*d_count : max_count;
+    const uint32_t lane = threadIdx.x;
+    for (size_t i = blockIdx.x; i < n; i += gridDim.x) {
+        const uint32_t len = sizes[i];
+        if (len == 0) continue;
+        const uint64_t c = sel ? sel[i] : i;
+        lz::copy_g2g(out + offsets[i], slots + chunk_slot_offset(lz4, chunk_offsets[c], c), len, lane);
     }
 }
 
@@ -127,6 +176,28 @@ hipError_t pack_launch(const uint8_t *slots, size_t slot_stride, const uint32_t 
     if (packed) {
         const size_t grid = nblocks < 256 * 32 ? nblocks : 256 * 32;
         hipLaunchKernelGGL(pack_copy_kernel, dim3((unsigned)grid), dim3(64), 0, stream, slots, slot_stride, sizes, off, nblocks, packed);
+    }
+    return hipGetLastError();
+}
+
+hipError_t chunk_pack_launch(int lzf, const uint8_t *slots, const uint64_t *chunk_offsets, const uint32_t *sel, const uint64_t *d_count,
+                             size_t max_count, const uint32_t *sizes, uint8_t *packed, uint64_t *offsets, hipStream_t stream)
+{
+    if (max_count == 0) return hipMemsetAsync(offsets, 0, sizeof(uint64_t), stream);
+    const size_t ntiles = (max_count + kTile - 1) / kTile;
+    auto &w = partials.at(stream);
+    LaunchLock sequence(w.launch); // the tile partials are shared by the launches below
+    const hipError_t e = w.reserve(ntiles * sizeof(unsigned long long), 1024 * sizeof(unsigned long long));
+    if (e != hipSuccess) return e;
+    unsigned long long *partial = w.as<unsigned long long>();
+    unsigned long long *off = reinterpret_cast<unsigned long long *>(offsets);
+    hipLaunchKernelGGL(chunk_tile_sums_kernel, dim3((unsigned)ntiles), dim3(kThreads), 0, stream, sizes, d_count, max_count, partial);
+    hipLaunchKernelGGL(scan_partials_kernel, dim3(1), dim3(kThreads), 0, stream, partial, ntiles);
+    hipLaunchKernelGGL(chunk_tile_offsets_kernel, dim3((unsigned)ntiles), dim3(kThreads), 0, stream, sizes, d_count, max_count, partial, off);
+    if (packed) {
+        const size_t grid = max_count < 256 * 32 ? max_count : 256 * 32;
+        hipLaunchKernelGGL(chunk_pack_copy_kernel, dim3((unsigned)grid), dim3(64), 0, stream, slots, lzf == 0, chunk_offsets, sel, sizes, off,
+                           d_count, max_count, packed);
     }
     return hipGetLastError();
 }

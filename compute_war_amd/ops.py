@@ -323,6 +323,22 @@ class DedupeIndex:
                                                 base, d_digests, d_ref, d_new_idx, d_dst, dst_stride, d_sizes, C.byref(n_new), stream))
         return int(n_new.value)
 
+    def dev_cdc_dedupe_compress(self, params: "CdcParams", comp_alg, d_src: int, nbytes: int, final: bool, base: int, d_offsets: int,
+                                max_offsets: int, d_nchunks: int, d_digests: int, d_ref: int, d_new_idx: int, d_n_new: int, d_dst: int,
+                                dst_bytes: int, d_sizes: int, stream: int = 0) -> int:
+        """Chunk, hash and dedupe d_src[0..nbytes), then compress only the new chunks into their slots (chunk_slot_offset); d_sizes[j]
+        belongs to chunk new_idx[j].  Synchronises the stream once, for the chunk count it returns; n_new stays on the device.  A full
+        index raises CwError -5 with ``e.nchunks`` set."""
+        k = C.c_size_t(0)
+        rc = lib().cw_dev_cdc_dedupe_compress(self._x(), C.byref(params), _comp_id(comp_alg), d_src, nbytes, 1 if final else 0, base,
+                                              d_offsets, max_offsets, d_nchunks, d_digests, d_ref, d_new_idx, d_n_new, d_dst, dst_bytes,
+                                              d_sizes, C.byref(k), stream)
+        if rc != 0:
+            err = _lib.CwError(rc, lib().cw_last_error().decode(errors="replace"))
+            err.nchunks = int(k.value)
+            raise err
+        return int(k.value)
+
     def count(self) -> int:
         """Entries in the index (waits for the index's last call)."""
         n = C.c_uint64(0)
@@ -468,3 +484,36 @@ def cdc_hash(params: CdcParams, data, hash_alg=None):
                             dig.ctypes.data if db else None))
     k = int(k.value)
     return offs[:k + 1].copy(), (dig[:k, :db].copy() if db else None)
+
+
+# ---- codecs over chunks (cw_dev_*_chunks) --------------------------------------------------------
+def chunk_slot_offset(comp_alg, o: int, i: int) -> int:
+    """Where compressed chunk i of input offset o lies in the slot buffer: LZ4 (o + o // 255 + 32 * i) & ~15, LZF o."""
+    return o if _comp_id(comp_alg) == COMP_LZF else (o + o // 255 + 32 * i) & ~15
+
+
+def chunk_slots_bytes(comp_alg, src_bytes: int, max_chunks: int) -> int:
+    """Bytes of slot buffer dev_compress_chunks needs for src_bytes of input in at most max_chunks chunks."""
+    return chunk_slot_offset(comp_alg, src_bytes, max_chunks) + 16
+
+
+def dev_compress_chunks(comp_alg, d_src: int, src_bytes: int, d_offsets: int, d_nchunks: int, max_chunks: int, d_dst: int, dst_bytes: int,
+                        d_sizes: int, stream: int = 0, d_sel: int = 0, d_nsel: int = 0) -> None:
+    """Compress chunk i = [offsets[i], offsets[i+1]) into its slot for every i < min(*d_nchunks, max_chunks), or for the chunks
+    d_sel[j], j < min(*d_nsel, max_chunks); d_sizes[j] is the size of position j (0: LZF did not fit, or out of contract)."""
+    check(lib().cw_dev_compress_chunks(_comp_id(comp_alg), d_src, src_bytes, d_offsets, d_nchunks, max_chunks, d_sel or None,
+                                       d_nsel or None, d_dst, dst_bytes, d_sizes, stream))
+
+
+def dev_pack_chunks(comp_alg, d_slots: int, d_offsets: int, d_count: int, max_count: int, d_sizes: int, d_packed: int,
+                    d_packed_offsets: int, stream: int = 0, d_sel: int = 0) -> None:
+    """Packed stream of the positions j < min(*d_count, max_count): d_packed_offsets[0..n] and, unless d_packed is 0, the bytes."""
+    check(lib().cw_dev_pack_chunks(_comp_id(comp_alg), d_slots, d_offsets, d_sel or None, d_count, max_count, d_sizes, d_packed or None,
+                                   d_packed_offsets, stream))
+
+
+def dev_decompress_chunks(comp_alg, d_comp: int, d_comp_offsets: int, d_raw_offsets: int, d_count: int, max_count: int, d_dst: int,
+                          dst_bytes: int, d_status: int, stream: int = 0) -> None:
+    """Decode position j's compressed extent into its raw extent of d_dst; d_status[j] = 0 iff well formed and exactly that long."""
+    check(lib().cw_dev_decompress_chunks(_comp_id(comp_alg), d_comp, d_comp_offsets, d_raw_offsets, d_count, max_count, d_dst, dst_bytes,
+                                         d_status, stream))

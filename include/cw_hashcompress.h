@@ -260,6 +260,75 @@ int cw_dev_hash_chunks(int hash_alg, const void *d_src, size_t src_bytes, const 
 int cw_cdc_hash(const cw_cdc_params *p, int hash_alg, const void *src, size_t nbytes,
                 uint64_t *offsets, size_t max_offsets, size_t *nchunks, void *digests);
 
+/* ---- codecs over chunks ----------------------------------------------------------------------
+ * The codec calls above take one block size per call; these take an offset list as cw_dev_cdc writes it, every chunk
+ * [d_offsets[i], d_offsets[i+1]) with a length of its own, 1 .. 65536 = CW_MAX_BLOCK_BYTES bytes (the range of
+ * cw_cdc_default_params(p, 8192) and below).  Formats and parsers are those of cw_dev_compress: LZ4 output is byte for
+ * byte LZ4_compress_default(chunk, dst, l, bound(l)) of v1.8.2 (l < 13: literals only), LZF output lzf_compress(chunk, l,
+ * dst, l - 1) with size 0 = did not fit.
+ *
+ * Slots.  Compressed chunk i of input offset o = d_offsets[i] is written at d_dst + cw_chunk_slot_offset(comp_alg, o, i):
+ *     LZ4: (o + o / 255 + 32 * i) & ~15          LZF: o
+ * a position known before the parse.  floor((o + l) / 255) - floor(o / 255) >= floor(l / 255), so consecutive LZ4 slots
+ * of ascending, non-overlapping chunks are at least l + l / 255 + 16 = cw_compress_bound(LZ4, l) apart and 16-byte aligned
+ * relative to d_dst; an LZF chunk's output is shorter than l.  cw_chunk_slots_bytes(comp_alg, src_bytes, max_chunks) =
+ * cw_chunk_slot_offset(comp_alg, src_bytes, max_chunks) + 16 bytes hold every slot: about 1.004 * src_bytes + 32 *
+ * max_chunks.  Both are host functions, need no device, and are normative: callers compute slot positions with them.    */
+uint64_t cw_chunk_slot_offset(int comp_alg, uint64_t o, uint64_t i);
+size_t   cw_chunk_slots_bytes(int comp_alg, size_t src_bytes, size_t max_chunks);
+/* Compresses the chunks of positions j: d_sel == NULL -> position j is chunk i = j, for j < min(*d_nchunks, max_chunks);
+ * else chunk i = d_sel[j] for j < min(*d_nsel, max_chunks) (u32 indices and a u64 count: cw_dev_dedupe's d_new_idx and
+ * d_n_new; entries are expected to be distinct -- two positions naming one chunk write the same bytes to the same slot).
+ * Both counts are read on the DEVICE; nothing synchronises.  The output goes to the CHUNK's slot (above), its size to the
+ * POSITION: d_sizes[j].  Out of contract, and given d_sizes[j] = 0 with nothing loaded and nothing stored: a chunk index
+ * >= min(*d_nchunks, max_chunks), a length of 0 or above 65536, a decreasing pair, an offset past src_bytes -- also a
+ * chunk that only ENDS past src_bytes: it is refused whole, where cw_dev_hash_chunks clamps it and hashes the part inside.  Slots of
+ * chunks that are not selected and d_sizes past the count are not touched; only bytes [0, d_sizes[j]) of a slot (LZF
+ * that did not fit: [0, l)) are written.  Slots are disjoint when the in-contract chunks ascend without overlap (what
+ * cw_dev_cdc writes); for any other list they may overlap and only memory safety holds: no load outside
+ * d_src[0..src_bytes), no store outside d_dst[0..dst_bytes), since slot(o, i) + bound(l) <= slot(o + l, i + 1) <=
+ * slot(src_bytes, max_chunks).  CW_ERR_BAD_ARG, before anything is launched: dst_bytes < cw_chunk_slots_bytes(comp_alg,
+ * src_bytes, max_chunks), max_chunks > 2^32 - 256, an unknown codec, NULL pointers (d_sel may be NULL; d_nsel then too).
+ * Scratch, per stream, freed like cw_dev_cdc's: 8 KiB + 4 * max_chunks bytes for the order (chunks are parsed longest
+ * first, one chunk per lane) and one hash table per lane, 32 KiB (LZ4) / 256 KiB (LZF) each, for min(max_chunks, one per 4 KiB
+ * of src_bytes, 131,072 (LZ4) / 65,536 (LZF)) lanes, rounded up to 64: 8 / 64 bytes of table per source byte of the largest call
+ * on the stream, 4 GiB / 16 GiB at most; fewer lanes if that cannot be had (the stream then keeps to that number).          */
+int cw_dev_compress_chunks(int comp_alg, const void *d_src, size_t src_bytes,
+                           const uint64_t *d_offsets, const uint64_t *d_nchunks, size_t max_chunks,
+                           const uint32_t *d_sel, const uint64_t *d_nsel,
+                           void *d_dst, size_t dst_bytes, uint32_t *d_sizes, void *stream);
+/* cw_dev_pack for those slots, the count read on the device: with n = min(*d_count, max_count), d_packed_offsets[j] = sum
+ * of d_sizes[0..j) for j <= n (entry n = the total; entries behind it are not written), and the slot of chunk d_sel[j]
+ * (chunk j if d_sel == NULL) is copied to d_packed + d_packed_offsets[j].  d_packed == NULL: the index only.  d_offsets:
+ * the chunk offsets the slots were computed from.  max_count <= 2^32 - 256.                                           */
+int cw_dev_pack_chunks(int comp_alg, const void *d_slots, const uint64_t *d_offsets,
+                       const uint32_t *d_sel, const uint64_t *d_count, size_t max_count,
+                       const uint32_t *d_sizes, void *d_packed, uint64_t *d_packed_offsets, void *stream);
+/* Position j < min(*d_count, max_count) decodes d_comp[d_comp_offsets[j] .. d_comp_offsets[j+1]) into
+ * d_dst[d_raw_offsets[j] .. d_raw_offsets[j+1]).  d_status[j] = 0 iff the input is well formed and yields exactly that
+ * many bytes (the rules of cw_dev_decompress; an empty compressed extent gives 1, so an LZF chunk that did not fit does).
+ * A raw extent that is longer than 65536, decreasing, or reaches past dst_bytes is skipped with status 1.  No store leaves
+ * a position's raw extent, no load its compressed extent; the bytes of a raw extent with status 1 are unspecified, except
+ * that a skipped or empty-input position writes nothing.  One chunk per lane; no scratch.                             */
+int cw_dev_decompress_chunks(int comp_alg, const void *d_comp, const uint64_t *d_comp_offsets,
+                             const uint64_t *d_raw_offsets, const uint64_t *d_count, size_t max_count,
+                             void *d_dst, size_t dst_bytes, uint32_t *d_status, void *stream);
+/* cw_dev_cdc -> cw_dev_hash_chunks (the index's algorithm) -> ONE synchronise of the stream that reads the chunk count
+ * (cw_dev_dedupe needs it on the host) -> cw_dev_dedupe with value base + i for chunk i -> cw_dev_compress_chunks with
+ * d_sel = d_new_idx, d_nsel = d_n_new and max_chunks = max_offsets - 1: only the new chunks are compressed, and n_new
+ * stays on the device, so cw_dev_pack_chunks(comp_alg, d_dst, d_offsets, d_new_idx, d_n_new, ...) can be queued behind it
+ * without another synchronise.  Every output equals what those five calls give.  *nchunks = the chunk count (final = 0:
+ * d_offsets[*nchunks] = bytes consumed).  dst_bytes >= cw_chunk_slots_bytes(comp_alg, nbytes, max_offsets - 1).
+ * CW_ERR_NOMEM when count + *nchunks > max_entries: offsets and digests are written and *nchunks is returned (retry with
+ * a larger index), nothing is inserted, nothing compressed.  CW_ERR_BAD_ARG, at the same point, when base + *nchunks wraps.
+ * Calls on one index are serialised as cw_dev_dedupe's.                                                               */
+int cw_dev_cdc_dedupe_compress(cw_dedupe_t *x, const cw_cdc_params *p, int comp_alg,
+                               const void *d_src, size_t nbytes, int final, uint64_t base,
+                               uint64_t *d_offsets, size_t max_offsets, uint64_t *d_nchunks,
+                               void *d_digests, uint64_t *d_ref, uint32_t *d_new_idx, uint64_t *d_n_new,
+                               void *d_dst, size_t dst_bytes, uint32_t *d_sizes,
+                               size_t *nchunks, void *stream);
+
 /* plain device memory on the calling thread's device, for C callers of cw_dev_* (the host programs link no HIP runtime) */
 void *cw_dev_alloc(size_t bytes);                                   /* NULL on failure */
 void  cw_dev_free(void *d_p);
