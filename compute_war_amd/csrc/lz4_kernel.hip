@@ -42,6 +42,7 @@
 #include <type_traits>
 
 #include "cw_device.h"
+#include "lane_codec.h"
 #include "lz_device.h"
 #include "stream_scratch.h"
 
@@ -60,6 +61,7 @@ using lz::copy_g2g;
 using lz::rd32;
 using lz::rd32x;
 using lz::tab_exchange;
+using namespace lane; // kMinMatch / kLastLiterals / kMFLimit, hash13, ld16g and the lane parser's loop (lane_codec.h)
 
 namespace {
 
@@ -67,10 +69,8 @@ constexpr uint32_t kTabBytes = (1u << 13) * 2; // 8192 x u16
 constexpr uint32_t kStageMax = 16384;          // parse kernel: blocks up to this size are staged in LDS
 constexpr uint32_t kNeedsParse = 0xFFFFFFFFu;  // sizes[] marker: scan kernel -> parse kernel
 constexpr int kScanGroup = 16;                 // probe batches in flight per wavefront in the generic scan kernel
-constexpr uint32_t kMinMatch = 4, kLastLiterals = 5, kMFLimit = 12;
 
 __device__ __forceinline__ uint32_t uni(uint32_t x) { return __builtin_amdgcn_readfirstlane(x); }
-__device__ __forceinline__ uint32_t hash13(uint32_t v) { return (v * 2654435761u) >> 19; }
 __device__ __forceinline__ uint32_t ctz64(unsigned long long m) { return m ? (uint32_t)__builtin_ctzll(m) : 64u; }
 
 // offset of the k-th probe of a search from its first probe: the parser advances by
@@ -1245,12 +1245,6 @@ __device__ __forceinline__ unsigned long long stamp_now()
 #endif
 
 __device__ __forceinline__ uint32_t fp4(uint32_t v) { return ((v * 2654435761u) >> 15) & 0xFu; }
-__device__ __forceinline__ uint4 ld16g(const uint8_t *p)
-{
-    uint4 v;
-    __builtin_memcpy(&v, p, 16); // unaligned global_load_dwordx4
-    return v;
-}
 
 // any batch of items (positions ascending with the lane): run_batch<false> + fingerprint upkeep.  Used for the first
 // search of a block and for searches that outlast their head batch; the loads are per field, as in the second generation.
@@ -1560,12 +1554,8 @@ lz4_parse_fp_kernel(const uint8_t *__restrict__ src, uint32_t n, size_t src_stri
 // chip, bound by how many random table / candidate accesses the memory system retires, not by any one chain's latency.
 // It only pays when there are that many blocks: lz4_launch uses it from kLaneMidBlocks queued blocks on.
 //
-// Every lane is in one of the states below; an iteration of the wavefront's loop runs one step of every lane:
-//   PROBE   the parser's search loop body, or the re-test right after a match (same table traffic, different follow-up)
-//   EMIT    a match was found: catch-up, literals, offset, match length; then PROBE (as a re-test) or TAIL
-//   TAIL    last literals, size; then NEXT
-//   NEXT    pull the next queued block, zero the table
-// Per iteration a lane's dependent memory chain is: its 16 bytes around ip -> table slot -> the candidate's 16 bytes.
+// The loop itself (the lanes' states, the window requested a step ahead, every bound) is lz4_lane_run in lane_codec.h, shared
+// with the parser over content-defined chunks; this file supplies the queue the blocks come from and the table's entry formats.
 // ---------------------------------------------------------------------------------------------------
 // blocks > 4 KiB: below kLaneMidBlocks queued blocks the wavefront-per-block parser's 13-14 GB/s win; [mid, wide): lanes with two
 // positions per iteration (every lane holds one block: latency regime), from kLaneWideBlocks on one (random-line regime); lz4_launch
@@ -1581,20 +1571,6 @@ constexpr uint32_t kLaneShare = 24576, kLaneShareWide = 32768;     // blocks of 
                                                                    // 64 KiB, 20 Ki / 24 Ki / 28 Ki blocks without lanes 29.0 / 29.4 / 29.8 GB/s, with 28.2 / 31.7 / 35.3 (16 Ki left);
                                                                    // 56 Ki / 72 Ki blocks with 16 Ki left 39.9-43.9 / 43.2-48.1, with 24 Ki 47.1 / 48.2-48.7
 constexpr uint32_t kLaneMinSmall = 61440;  // LDS-staged blocks: lanes beside the LDS-resident parser from 60 Ki blocks on (64 Ki blocks of text: 28.5 against 25.7 GB/s)
-enum : uint32_t { LS_NEXT = 0, LS_PROBE = 1, LS_EMIT = 2, LS_TAIL = 3, LS_EXIT = 4 };
-
-__device__ __forceinline__ void lane_put_len(uint8_t *__restrict__ out, uint32_t &op, uint32_t extra)
-{
-    while (extra >= 255) { out[op++] = 255; extra -= 255; }
-    out[op++] = (uint8_t)extra;
-}
-
-// 4 bytes at byte offset s (4 <= s <= 12) of a 16-byte window held in (x, y, z, w)
-__device__ __forceinline__ uint32_t win_at(const uint4 &q, uint32_t s)
-{
-    return s < 8 ? __builtin_amdgcn_alignbyte(q.z, q.y, s & 3u) : s < 12 ? __builtin_amdgcn_alignbyte(q.w, q.z, s & 3u) : q.w;
-}
-
 // Table entries:
 //   kLaneTagged (blocks <= 4 KiB)  u16 epoch:4 | position:12; an entry of another epoch reads as empty (= position 0, as in the
 //                                  parser's zeroed table) and the table is zeroed once per 15 blocks instead of per block
@@ -1605,6 +1581,55 @@ __device__ __forceinline__ uint32_t win_at(const uint4 &q, uint32_t s)
 //   kLanePlain                     u16 position (profiling: CW_LZ4_LANES_FP=0)
 enum : int { kLanePlain = 0, kLaneTagged = 1, kLaneFp = 2 };
 __device__ __forceinline__ uint32_t fp16(uint32_t v) { return ((v * 2654435761u) >> 3) & 0xFFFFu; }
+
+template <int MODE>
+struct LaneTab {
+    static constexpr bool TAGGED = MODE == kLaneTagged, FP = MODE == kLaneFp;
+    static constexpr bool kNameFirst = FP;
+    using Entry = typename std::conditional<FP, uint32_t, uint16_t>::type;
+    Entry *tab;
+    uint32_t epoch = 15; // TAGGED: forces a clean table before the first block
+    __device__ __forceinline__ uint32_t get(uint32_t h, uint32_t v, bool &maybe) const
+    {
+        const uint32_t e = tab[h];
+        maybe = true;
+        if (FP) { maybe = (e >> 16) == fp16(v); return e & 0xFFFFu; }
+        return TAGGED ? ((e >> 12) == epoch ? e & 0xFFFu : 0u) : e;
+    }
+    __device__ __forceinline__ void put(uint32_t h, uint32_t v, uint32_t pos) const
+    {
+        tab[h] = (Entry)(FP ? (fp16(v) << 16) | pos : TAGGED ? (epoch << 12) | pos : pos);
+    }
+    __device__ __forceinline__ void begin()
+    {
+        if (!TAGGED || ++epoch == 16) {
+            uint4 *t4 = reinterpret_cast<uint4 *>(tab);
+            for (uint32_t i = 0; i < (1u << 13) * sizeof(Entry) / 16; i++) t4[i] = make_uint4(0, 0, 0, 0);
+            epoch = 1;
+        }
+    }
+};
+
+// the queued blocks of a launch; n and its limits are the launch's (scalar registers: take() never writes them)
+struct LaneQueue {
+    static constexpr bool kShort = false;
+    const uint8_t *const src; const size_t src_stride;
+    uint8_t *const dst; const size_t dst_stride;
+    uint32_t *const sizes; const uint32_t *const queue; uint32_t *const counters;
+    const uint32_t qcount, reserve, n, mflimit, matchlimit;
+    const uint8_t *g; uint8_t *out; uint32_t blk;
+    __device__ __forceinline__ Take take()
+    {
+        uint32_t qi = qcount;
+        if (!reserve || __hip_atomic_load(&counters[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + reserve < qcount)
+            qi = atomicAdd(&counters[0], 1u);
+        if (qi >= qcount) return Take::kDone;
+        blk = queue[qi];
+        g = src + (size_t)blk * src_stride;
+        out = dst + (size_t)blk * dst_stride;
+        return Take::kTaken;
+    }
+};
 
 template <int MODE>
 __global__ void __launch_bounds__(64)
@@ -1621,211 +1646,10 @@ lz4_lanes_kernel(const uint8_t *__restrict__ src, uint32_t n, size_t src_stride,
     // is bound by LDS capacity and its own latency, this kernel by random memory accesses: the rates add).  A block takes a lane
     // ~100 ms and a wavefront ~10 ms, so the lanes stop pulling while `reserve` blocks are left: the wavefronts finish those in
     // about the time the lanes need for the blocks they hold.
-    constexpr bool TAGGED = MODE == kLaneTagged, FP = MODE == kLaneFp;
-    using Entry = typename std::conditional<FP, uint32_t, uint16_t>::type;
-    Entry *tab = reinterpret_cast<Entry *>(tables) + ((size_t)blockIdx.x * 64 + threadIdx.x) * (1u << 13);
-    const uint32_t mflimit = n - kMFLimit, matchlimit = n - kLastLiterals; // n >= 13: a queued block had a match
-    uint32_t epoch = 15; // TAGGED: forces a clean table before the first block
-    // the slot's position, and whether the bytes there can be the 4 bytes v at all
-    auto tab_get = [&](uint32_t h, uint32_t v, bool &maybe) -> uint32_t {
-        const uint32_t e = tab[h];
-        maybe = true;
-        if (FP) { maybe = (e >> 16) == fp16(v); return e & 0xFFFFu; }
-        return TAGGED ? ((e >> 12) == epoch ? e & 0xFFFu : 0u) : e;
-    };
-    auto tab_put = [&](uint32_t h, uint32_t v, uint32_t pos) {
-        tab[h] = (Entry)(FP ? (fp16(v) << 16) | pos : TAGGED ? (epoch << 12) | pos : pos);
-    };
-
-    uint32_t state = LS_NEXT;
-    const uint8_t *g = src;
-    uint8_t *out = dst;
-    uint32_t blk = 0, ip = 0, anchor = 0, op = 0, step = 1, nb = 64, match = 0, first_lo = 0, first_hi = 0;
-    bool retest = false;
-    // own = the 16 bytes [ip-4, ip+12), requested one iteration ahead; vcur = the 4 bytes at ip, cut out of the previous
-    // window when it reached that far (have_v), so that the table lookup never waits for the request
-    uint4 own = make_uint4(0, 0, 0, 0), cd = make_uint4(0, 0, 0, 0);
-    uint32_t vcur = 0, v2cur = 0;
-    bool have_v = false;
-    // literals of the last sequence on their way from memory: stored one iteration later (their load is then long done)
-    uint64_t pend_a = 0, pend_b = 0;
-    uint8_t *pend_dst = nullptr;
-    uint32_t pend_n = 0;
-
-    while (__ballot(state != LS_EXIT)) {
-        // everything requested during the previous iteration is waited for here, once
-        if (pend_n) { // exactly pend_n (1..16) bytes: what follows them in the slot is already written
-            uint64_t lo = pend_a;
-            uint8_t *p = pend_dst;
-            if (pend_n & 16) { __builtin_memcpy(p, &lo, 8); __builtin_memcpy(p + 8, &pend_b, 8); }
-            else {
-                if (pend_n & 8) { __builtin_memcpy(p, &lo, 8); lo = pend_b; p += 8; }
-                if (pend_n & 4) { const uint32_t t = (uint32_t)lo; __builtin_memcpy(p, &t, 4); lo >>= 32; p += 4; }
-                if (pend_n & 2) { const uint16_t t = (uint16_t)lo; __builtin_memcpy(p, &t, 2); lo >>= 16; p += 2; }
-                if (pend_n & 1) *p = (uint8_t)lo;
-            }
-            pend_n = 0;
-        }
-        if (state == LS_NEXT) {
-            uint32_t qi = qcount;
-            if (!reserve || __hip_atomic_load(&counters[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + reserve < qcount)
-                qi = atomicAdd(&counters[0], 1u);
-            if (qi >= qcount) {
-                state = LS_EXIT;
-            } else {
-                blk = queue[qi];
-                g = src + (size_t)blk * src_stride;
-                out = dst + (size_t)blk * dst_stride;
-                if (!TAGGED || ++epoch == 16) {
-                    uint4 *t4 = reinterpret_cast<uint4 *>(tab);
-                    for (uint32_t i = 0; i < (1u << 13) * sizeof(Entry) / 16; i++) t4[i] = make_uint4(0, 0, 0, 0);
-                    epoch = 1;
-                }
-                first_lo = rd32(g, 0); first_hi = rd32(g, 4);
-                // tab[hash(first 4 bytes)] = 0 is what an empty table already says; with fingerprints the entry says whose 0 it is
-                if (FP) tab_put(hash13(first_lo), first_lo, 0);
-                ip = 1; anchor = 0; op = 0; step = 1; nb = 64; retest = false;
-                own.x = 0; own.y = rd32(g, 1); own.z = rd32(g, 5); own.w = rd32(g, 9); // no "before" at the block's start
-                have_v = false;
-                state = LS_PROBE;
-            }
-        }
-
-        if (state == LS_PROBE) {
-            const uint32_t next = ip + step;
-            if (!retest && next > mflimit + 1) {
-                state = LS_TAIL;
-            } else {
-                const uint32_t v = have_v ? vcur : own.y;
-                if (retest) { // LZ4_putPosition(ip - 2) in front of the re-test
-                    const uint32_t v2 = have_v ? v2cur : (own.x >> 16) | (own.y << 16);
-                    tab_put(hash13(v2), v2, ip - 2);
-                }
-                const uint32_t h = hash13(v);
-                bool maybe;
-                match = tab_get(h, v, maybe);
-                tab_put(h, v, ip);
-                uint32_t cat = ~v;
-                if (maybe) {
-                    if (match >= 4) { cd = ld16g(g + match - 4); cat = cd.y; }
-                    else cat = __builtin_amdgcn_alignbyte(first_hi, first_lo, match);
-                }
-                if (cat == v) {
-                    state = LS_EMIT; // (own was requested for this ip an iteration ago: it is here by now)
-                } else {
-                    uint32_t nip;
-                    if (retest) { nip = ip + 1; step = 1; nb = 64; retest = false; }
-                    else { nip = next; step = nb >> 6; nb++; }
-                    // the next position's 4 bytes, from the window if it reaches (it is the window of `ip` only if that
-                    // has arrived, which it has unless this iteration ran on vcur: then the request is still the one for ip)
-                    const uint32_t s = nip - ip + 4;
-                    have_v = s <= 12 && ip >= 4;
-                    if (have_v) vcur = win_at(own, s);
-                    ip = nip;
-                    // (ip = mflimit + 1 is never probed, the next iteration sends it to TAIL: keep its request inside the block)
-                    const uint32_t rp = ip <= mflimit ? ip : mflimit;
-                    own = ld16g(g + rp - (rp >= 4 ? 4 : 0));
-                    if (rp < 4) { own.w = own.z; own.z = own.y; own.y = own.x; own.x = 0; have_v = false; }
-                }
-            }
-        }
-
-        if (state == LS_EMIT) {
-            // own = [ip-4, ip+12) and cd = [match-4, match+12) (match >= 4), both as found by the probe
-            const uint32_t ip0 = ip;
-            const bool windows = ip >= 4 && match >= 4;
-            uint32_t nf = 0; // equal bytes behind the 4 that matched
-            bool nf_open = true;
-            if (windows) {
-                const uint64_t x = ((uint64_t)own.w << 32 | own.z) ^ ((uint64_t)cd.w << 32 | cd.z);
-                nf = x ? (uint32_t)__builtin_ctzll(x) >> 3 : 8u;
-                nf_open = nf == 8;
-                const uint32_t lim = matchlimit - (ip0 + kMinMatch);
-                if (nf >= lim) { nf = lim; nf_open = false; }
-            }
-            // ---- catch-up over the pending literals (a re-test has none: anchor == ip) ----
-            if (!retest) {
-                if (windows) {
-                    const uint32_t room = ip - anchor < match ? ip - anchor : match;
-                    const uint32_t y = own.x ^ cd.x;
-                    uint32_t back = y ? (uint32_t)__builtin_clz(y) >> 3 : 4u;
-                    if (back > room) back = room;
-                    ip -= back; match -= back;
-                    if (back == 4) while (ip > anchor && match > 0 && g[ip - 1] == g[match - 1]) { ip--; match--; }
-                } else {
-                    while (ip > anchor && match > 0 && g[ip - 1] == g[match - 1]) { ip--; match--; }
-                }
-            }
-            // ---- literals: 8 or 16 bytes requested now and stored next iteration; longer runs copied here ----
-            const uint32_t lit = ip - anchor, tok = op++;
-            uint32_t token;
-            if (lit >= 15) { token = 15u << 4; lane_put_len(out, op, lit - 15); }
-            else token = lit << 4;
-            if (lit) {
-                // (8 bytes from anchor stay inside the block: anchor + 8 <= ip + 7 <= n - 5; 16 only for runs of 9 and more)
-                __builtin_memcpy(&pend_a, g + anchor, 8);
-                if (lit > 8) __builtin_memcpy(&pend_b, g + anchor + 8, 8);
-                pend_dst = out + op;
-                pend_n = lit < 16 ? lit : 16;
-                for (uint32_t k = 16; k < lit; k += 8) { // runs beyond 16 (0.3 % on text): 8 bytes at a time, the overshoot (< 8
-                    uint64_t q;                          // bytes) lands where the offset and what follows are written next
-                    __builtin_memcpy(&q, g + anchor + k, 8);
-                    __builtin_memcpy(out + op + k, &q, 8);
-                }
-            }
-            op += lit;
-            // ---- offset, match length ----
-            const uint32_t off = ip - match;
-            out[op] = (uint8_t)off; out[op + 1] = (uint8_t)(off >> 8);
-            op += 2;
-            // the bytes taken back, the 4 that matched and the nf behind them are one run: mc = (ip0 - ip) + nf (+ what memory adds)
-            uint32_t mc = ip0 - ip + nf;
-            if (nf_open) {
-                const uint32_t a = ip + kMinMatch, b = match + kMinMatch;
-                while (a + mc + 8 <= matchlimit) {
-                    uint64_t x, y;
-                    __builtin_memcpy(&x, g + a + mc, 8);
-                    __builtin_memcpy(&y, g + b + mc, 8);
-                    const uint64_t d = x ^ y;
-                    if (d) { mc += (uint32_t)__builtin_ctzll(d) >> 3; break; }
-                    mc += 8;
-                }
-                if (a + mc + 8 > matchlimit) while (a + mc < matchlimit && g[a + mc] == g[b + mc]) mc++;
-            }
-            if (mc >= 15) { token += 15; lane_put_len(out, op, mc - 15); }
-            else token += mc;
-            out[tok] = (uint8_t)token;
-            ip += kMinMatch + mc;
-            anchor = ip;
-            if (ip > mflimit) {
-                state = LS_TAIL;
-            } else {
-                // the re-test's values out of the old window when the match was short enough (mend + 4 <= ip0 + 12)
-                const uint32_t s = ip - ip0 + 4;
-                have_v = windows && s <= 12;
-                if (have_v) { vcur = win_at(own, s); v2cur = win_at(own, s - 2); }
-                own = ld16g(g + ip - 4); // ip >= 5
-                retest = true;
-                state = LS_PROBE;
-            }
-        }
-
-        if (state == LS_TAIL) {
-            const uint32_t run = n - anchor;
-            if (run >= 15) { out[op++] = 15u << 4; lane_put_len(out, op, run - 15); }
-            else out[op++] = (uint8_t)(run << 4);
-            uint32_t k = 0;
-            for (; k + 16 <= run; k += 16) {
-                uint4 q;
-                __builtin_memcpy(&q, g + anchor + k, 16);
-                __builtin_memcpy(out + op + k, &q, 16);
-            }
-            for (; k < run; k++) out[op + k] = g[anchor + k];
-            op += run;
-            sizes[blk] = op;
-            state = LS_NEXT;
-        }
-    }
+    LaneQueue s{src, src_stride, dst, dst_stride, sizes, queue, counters, qcount, reserve, n, n - kMFLimit, n - kLastLiterals, // n >= 13: a queued
+                src, dst, 0};                                                                                                   // block had a match
+    LaneTab<MODE> t{reinterpret_cast<typename LaneTab<MODE>::Entry *>(tables) + ((size_t)blockIdx.x * 64 + threadIdx.x) * (1u << 13)};
+    lz4_lane_run(s, t);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1854,16 +1678,6 @@ lz4_lanes_kernel(const uint8_t *__restrict__ src, uint32_t n, size_t src_stride,
 // ---------------------------------------------------------------------------------------------------
 constexpr uint32_t kRingBytes = 256, kRingPiece = 64;
 enum : uint32_t { LB_NEXT = 0, LB_PROBE = 1, LB_EXTEND = 2, LB_TAIL = 3, LB_EXIT = 4 };
-
-// stores exactly cnt (1..16) bytes of (a, b)
-__device__ __forceinline__ void lane_store_upto16(uint8_t *p, uint64_t a, uint64_t b, uint32_t cnt)
-{
-    if (cnt & 16) { __builtin_memcpy(p, &a, 8); __builtin_memcpy(p + 8, &b, 8); return; }
-    if (cnt & 8) { __builtin_memcpy(p, &a, 8); a = b; p += 8; }
-    if (cnt & 4) { const uint32_t t = (uint32_t)a; __builtin_memcpy(p, &t, 4); a >>= 32; p += 4; }
-    if (cnt & 2) { const uint16_t t = (uint16_t)a; __builtin_memcpy(p, &t, 2); a >>= 16; p += 2; }
-    if (cnt & 1) *p = (uint8_t)a;
-}
 
 // (the body of the two kernels below; ring: the workgroup's (kRingBytes / 4) * 64 dwords of LDS, dword d of lane l's ring at [d * 64 + l]: a lane only
 // touches its column; qcount: the queue's length)
@@ -2070,7 +1884,7 @@ lz4_lanes_ring_body(uint32_t *__restrict__ ring, const uint32_t qcount, const ui
                 if (anchor >= rb) { // out of the ring (ip <= re: the run's bytes are all there)
                     for (uint32_t k = 0; k < lit; k += 16) {
                         const uint4 q = ring16(anchor + k);
-                        lane_store_upto16(out + op + k, (uint64_t)q.y << 32 | q.x, (uint64_t)q.w << 32 | q.z, lit - k < 16 ? lit - k : 16);
+                        store_upto16(out + op + k, (uint64_t)q.y << 32 | q.x, (uint64_t)q.w << 32 | q.z, lit - k < 16 ? lit - k : 16);
                     }
                 } else { // a run longer than the ring remembers
                     uint32_t k = 0;

@@ -36,16 +36,18 @@
 #include <string.h>
 
 #include "cw_device.h"
+#include "lane_codec.h"
 #include "lz_device.h"
 #include "scalar_thread.h"
 #include "stream_scratch.h"
 
 namespace cw {
 
+using namespace lane; // kMaxOff / kMaxRef / kMaxLit, lzf_slot and the lane parser's loop (lane_codec.h)
+
 namespace {
 
 constexpr uint32_t kLzfSlots = 1u << 16, kLzfTabBytes = kLzfSlots * 2;
-constexpr uint32_t kMaxOff = 1u << 13, kMaxRef = (1u << 8) + (1u << 3), kMaxLit = 32;
 constexpr uint32_t kInLdsMax = 16384; // blocks up to this size are staged in LDS next to the table
 constexpr uint32_t kRedo = 0xFFFFFFFFu; // sizes[] marker: exchange kernel -> write/read-back kernel
 
@@ -124,11 +126,6 @@ struct BlockList {
 };
 
 __device__ __forceinline__ uint32_t ctz64(unsigned long long m) { return m ? (uint32_t)__builtin_ctzll(m) : 64u; }
-__device__ __forceinline__ uint32_t lzf_slot(uint32_t b0, uint32_t b1, uint32_t b2)
-{
-    // IDX(hval) = ((hval >> 8) - hval*5) & 0xFFFF with hval = b0<<16 | b1<<8 | b2 (VERY_FAST, HLOG 16)
-    return (((b0 << 8) | b1) - (((b1 << 8) | b2) * 5u)) & 0xFFFFu;
-}
 
 // m literals starting at in[ip]: bytes and completed-run control bytes; updates (op, lit)
 __device__ __forceinline__ void put_literals(uint8_t *__restrict__ out, const uint8_t *in, uint32_t ip, uint32_t m,
@@ -1098,10 +1095,9 @@ lzf_sthread_kernel(const uint8_t *__restrict__ src, uint32_t n, size_t src_strid
 
 // ---------------------------------------------------------------------------------------------------
 // Lane-per-block parser for large batches of blocks that do not fit the LDS-resident scheme (> 4 KiB): the counterpart
-// of lz4_lanes_kernel (lz4_kernel.hip has the reasoning).  A lane runs liblzf's loop as it stands -- one position per
-// iteration: hash the next three bytes, exchange the table slot, test the reference, emit a literal or a match -- with its
-// 65,536 x u16 table in global memory (128 KiB per lane, zeroed by the lane when it takes a block).  No links, no skip
-// flags, no lane-order assumption: the parse is the serial one.
+// of lz4_lanes_kernel (lz4_kernel.hip has the reasoning).  A lane runs liblzf's loop as it stands (lzf_lane_run in lane_codec.h,
+// shared with the parser over content-defined chunks) with its 65,536 x u16 table in global memory (128 KiB per lane, zeroed by
+// the lane when it takes a block).  This file supplies where the blocks come from and the table's entry formats.
 // ---------------------------------------------------------------------------------------------------
 // A lane needs ~66 ms for a 64 KiB block of text however few lanes there are, the link/chain kernels run at 8.5 GB/s: the lanes win
 // from ~9 Ki compressible blocks on (text, 64 KiB, 12 Ki / 16 Ki / 20 Ki / 24 Ki blocks: 13.2 / 16.3 / 13.6 / 15.2 GB/s against 8.5; the dip
@@ -1128,19 +1124,96 @@ __device__ __forceinline__ uint32_t lzf_rd(const uint8_t *g, uint32_t ip, uint32
 // table is zeroed once per 15 blocks instead of per block -- a 4 KiB block is ~1,300 parse iterations, zeroing its table 8,192
 // store iterations that the whole wavefront sits through whenever one of its lanes takes a new block.
 template <bool TAGGED>
+struct LzfLaneTab {
+    uint16_t *tab;
+    uint32_t epoch = 15; // TAGGED: forces a clean table before the first block
+    __device__ __forceinline__ uint32_t get(uint32_t slot) const
+    {
+        const uint32_t e = tab[slot];
+        return TAGGED ? ((e >> 12) == epoch ? e & 0xFFFu : 0u) : e;
+    }
+    __device__ __forceinline__ void put(uint32_t slot, uint32_t pos) const { tab[slot] = (uint16_t)(TAGGED ? (epoch << 12) | pos : pos); }
+    __device__ __forceinline__ void begin()
+    {
+        if (!TAGGED || ++epoch == 16) {
+            uint4 *t4 = reinterpret_cast<uint4 *>(tab);
+            for (uint32_t i = 0; i < kLzfTabBytes / 16; i++) t4[i] = make_uint4(0, 0, 0, 0);
+            epoch = 1;
+        }
+    }
+};
+
+// The blocks of a launch; n and what derives from it are the launch's (scalar registers: take() never writes them).
+// Blocks that do not compress are the lanes' worst case and the chain parser's best (a noise block is a serial walk of all
+// its positions here -- 61 -> 18 GB/s on random 64 KiB blocks when the lanes took them all -- and a 60 GB/s bail-out there).
+// So a lane looks at its block once, after `check_at` positions (keep): less than 1/32 saved so far => the block goes to the
+// hand-back list (counter[kCtrHanded] entries), which the link/chain kernels parse after the lanes are done; and once more than a
+// third of the blocks looked at were such (counter[kCtrPoor], counter[kCtrFine]), the lanes stop parsing: beside the rounds they
+// take no more blocks, on their own they pass what is left straight to the list.
+// reserve == 0: the lanes take every block, pulled upwards from counter[0].  reserve > 0: beside the link/chain rounds --
+// blocks are taken from the top downwards while more than `reserve` unclaimed blocks are left (LaneShare)
+struct LzfLaneBlocks {
+    static constexpr bool kShort = false; // n >= 16 here
+    const uint8_t *const src; const size_t src_stride, nblocks;
+    uint8_t *const dst; const size_t dst_stride;
+    uint32_t *const sizes, *const counter, *const handback;
+    const uint32_t reserve, n, check_at;
+    const uint8_t *g; uint8_t *out; size_t blk;
+    bool checked;
+    __device__ __forceinline__ Take take()
+    {
+        const uint32_t poor = __hip_atomic_load(&counter[kCtrPoor], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint32_t fine = __hip_atomic_load(&counter[kCtrFine], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // (beside the rounds the lanes also slow THEM down, so they give up sooner: a fifth of noise against a third)
+        const bool noisy = reserve ? poor > 64 + fine / 4 : poor > 32 + fine / 2;
+        if (reserve && noisy) {
+            blk = nblocks; // the rounds take the rest
+        } else if (reserve) { // the wavefront's idle lanes ask together (LaneShare): one compare-and-swap for all of them
+            const unsigned long long idle = __ballot(true);
+            const uint32_t m = (uint32_t)__builtin_popcountll(idle), leader = (uint32_t)__builtin_ctzll(idle);
+            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+            uint32_t first = 0, claimed = 0;
+            if (threadIdx.x == leader) share_take(counter, m, nblocks, reserve, first, claimed);
+            first = __builtin_amdgcn_readlane(first, leader);
+            claimed = __builtin_amdgcn_readlane(claimed, leader);
+            const size_t k = (size_t)first + rank; // my rank, if any: block nblocks-1-k, mine if it lay above `claimed` at the draw
+            blk = k < nblocks && nblocks - 1 - k >= claimed ? nblocks - 1 - k : nblocks;
+        } else {
+            blk = atomicAdd(counter, 1u);
+            while (noisy && blk < nblocks) { // unparsed, to the list
+                handback[atomicAdd(&counter[kCtrHanded], 1u)] = (uint32_t)blk;
+                blk = atomicAdd(counter, 1u);
+            }
+        }
+        if (blk >= nblocks) return Take::kDone;
+        checked = false;
+        g = src + blk * src_stride;
+        out = dst + blk * dst_stride;
+        return Take::kTaken;
+    }
+    __device__ __forceinline__ uint32_t rd(uint32_t ip) const { return lzf_rd(g, ip, n); }
+    // the one look at the block: false = handed back (what the lane wrote so far is overwritten by the chain parser)
+    __device__ __forceinline__ bool keep(uint32_t ip, uint32_t op)
+    {
+        if (__builtin_expect(!checked && ip >= check_at, false)) { // (once per block)
+            checked = true;
+            if (op + (ip >> 5) >= ip) {
+                atomicAdd(&counter[kCtrPoor], 1u);
+                handback[atomicAdd(&counter[kCtrHanded], 1u)] = (uint32_t)blk;
+                return false;
+            }
+            atomicAdd(&counter[kCtrFine], 1u);
+        }
+        return true;
+    }
+};
+
+template <bool TAGGED>
 __global__ void __launch_bounds__(64)
 lzf_lanes_kernel(const uint8_t *__restrict__ src, uint32_t n, size_t src_stride, size_t nblocks, uint8_t *__restrict__ dst, size_t dst_stride,
                  uint32_t *__restrict__ sizes, uint16_t *__restrict__ tables, uint32_t *__restrict__ counter, uint32_t reserve,
                  uint32_t *__restrict__ handback)
 {
-    // Blocks that do not compress are the lanes' worst case and the chain parser's best (a noise block is a serial walk of all
-    // its positions here -- 61 -> 18 GB/s on random 64 KiB blocks when the lanes took them all -- and a 60 GB/s bail-out there).
-    // So a lane looks at its block once, after `check_at` positions: less than 1/32 saved so far => the block goes to the
-    // hand-back list (counter[kCtrHanded] entries), which the link/chain kernels parse after the lanes are done; and once more than a
-    // third of the blocks looked at were such (counter[kCtrPoor], counter[kCtrFine]), the lanes stop parsing: beside the rounds they
-    // take no more blocks, on their own they pass what is left straight to the list.
-    const uint32_t check_at = n >= 2048 ? 512u : n / 4 < 128 ? 128u : n / 4;
-    bool checked = false;
     // Slow start: the first 128 workgroups sample the batch; the others wait (bounded: ~3 ms) until 512 blocks have been looked at
     // and then start -- or, on noise, leave at once.  (Random 4 KiB blocks beside the rounds: 65,536 first looks cost 11 ms.)
     if (blockIdx.x >= 128) {
@@ -1151,166 +1224,10 @@ lzf_lanes_kernel(const uint8_t *__restrict__ src, uint32_t n, size_t src_stride,
             __builtin_amdgcn_s_sleep(32);
         }
     }
-    uint32_t epoch = 15; // TAGGED: forces a clean table before the first block
-    auto tab_get = [&](uint16_t *t, uint32_t slot) -> uint32_t {
-        const uint32_t e = t[slot];
-        return TAGGED ? ((e >> 12) == epoch ? e & 0xFFFu : 0u) : e;
-    };
-    auto tab_put = [&](uint16_t *t, uint32_t slot, uint32_t pos) { t[slot] = (uint16_t)(TAGGED ? (epoch << 12) | pos : pos); };
-    // reserve == 0: the lanes take every block, pulled upwards from counter[0].  reserve > 0: beside the link/chain rounds --
-    // blocks are taken from the top downwards while more than `reserve` unclaimed blocks are left (LaneShare)
-    uint16_t *tab = tables + ((size_t)blockIdx.x * 64 + threadIdx.x) * kLzfSlots;
-    const uint32_t cap = n - 1; // out_len of the reference's call (n >= 16 here)
-    enum : uint32_t { NEXT = 0, STEP = 1, TAIL = 2, EXIT = 3 };
-    uint32_t state = NEXT, ip = 0, op = 0, lit = 0, v = 0;
-    size_t blk = 0;
-    const uint8_t *g = src;
-    uint8_t *out = dst;
-    bool fail = false;
-
-    while (__ballot(state != EXIT)) {
-        if (state == NEXT) {
-            const uint32_t poor = __hip_atomic_load(&counter[kCtrPoor], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const uint32_t fine = __hip_atomic_load(&counter[kCtrFine], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            // (beside the rounds the lanes also slow THEM down, so they give up sooner: a fifth of noise against a third)
-            const bool noisy = reserve ? poor > 64 + fine / 4 : poor > 32 + fine / 2;
-            if (reserve && noisy) {
-                blk = nblocks; // the rounds take the rest
-            } else if (reserve) { // the wavefront's idle lanes ask together (LaneShare): one compare-and-swap for all of them
-                const unsigned long long idle = __ballot(true);
-                const uint32_t m = (uint32_t)__builtin_popcountll(idle), leader = (uint32_t)__builtin_ctzll(idle);
-                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
-                uint32_t first = 0, claimed = 0;
-                if (threadIdx.x == leader) share_take(counter, m, nblocks, reserve, first, claimed);
-                first = __builtin_amdgcn_readlane(first, leader);
-                claimed = __builtin_amdgcn_readlane(claimed, leader);
-                const size_t k = (size_t)first + rank; // my rank, if any: block nblocks-1-k, mine if it lay above `claimed` at the draw
-                blk = k < nblocks && nblocks - 1 - k >= claimed ? nblocks - 1 - k : nblocks;
-            } else {
-                blk = atomicAdd(counter, 1u);
-                while (noisy && blk < nblocks) { // unparsed, to the list
-                    handback[atomicAdd(&counter[kCtrHanded], 1u)] = (uint32_t)blk;
-                    blk = atomicAdd(counter, 1u);
-                }
-            }
-            if (blk >= nblocks) {
-                state = EXIT;
-            } else {
-                checked = false;
-                g = src + blk * src_stride;
-                out = dst + blk * dst_stride;
-                if (!TAGGED || ++epoch == 16) {
-                    uint4 *t4 = reinterpret_cast<uint4 *>(tab);
-                    for (uint32_t i = 0; i < kLzfTabBytes / 16; i++) t4[i] = make_uint4(0, 0, 0, 0);
-                    epoch = 1;
-                }
-                ip = 0; op = 1; lit = 0; fail = false; // op = 1: the first literal run's control byte is reserved
-                v = lzf_rd(g, 0, n);
-                state = STEP;
-            }
-        }
-
-        if (state == STEP && !checked && ip >= check_at) {
-            checked = true;
-            if (op + (ip >> 5) >= ip) { // (what the lane wrote so far is overwritten by the chain parser)
-                atomicAdd(&counter[kCtrPoor], 1u);
-                handback[atomicAdd(&counter[kCtrHanded], 1u)] = (uint32_t)blk;
-                state = NEXT;
-            } else {
-                atomicAdd(&counter[kCtrFine], 1u);
-            }
-        }
-
-        if (state == STEP) {
-            // v = the 4 bytes at ip (requested an iteration ago)
-            const uint32_t b0 = v & 0xFFu, b1 = (v >> 8) & 0xFFu, b2 = (v >> 16) & 0xFFu;
-            const uint32_t slot = lzf_slot(b0, b1, b2);
-            const uint32_t ref = tab_get(tab, slot);
-            tab_put(tab, slot, ip);
-            bool is_match = false;
-            if (ref > 0 && ip - ref - 1 < kMaxOff) is_match = ((lz::rd32(g, ref) ^ v) & 0xFFFFFFu) == 0; // ref + 4 <= ip + 3 <= n
-            if (is_match) {
-                uint32_t maxlen = n - ip - 2;
-                if (maxlen > kMaxRef) maxlen = kMaxRef;
-                if (op + 4 >= cap && op - (lit == 0) + 4 >= cap) {
-                    fail = true; state = TAIL;
-                } else {
-                    if (lit) out[op - lit - 1] = (uint8_t)(lit - 1);
-                    else op -= 1;
-                    // equal bytes from index 3 on, as far as the reference's loops can look
-                    const uint32_t room = (n - ip < kMaxRef + 2 ? n - ip : kMaxRef + 2) - 3;
-                    uint32_t eq = 0;
-                    while (eq + 8 <= room) {
-                        uint64_t x, y;
-                        __builtin_memcpy(&x, g + ref + 3 + eq, 8);
-                        __builtin_memcpy(&y, g + ip + 3 + eq, 8);
-                        const uint64_t d = x ^ y;
-                        if (d) { eq += (uint32_t)__builtin_ctzll(d) >> 3; break; }
-                        eq += 8;
-                    }
-                    if (eq + 8 > room) while (eq < room && g[ref + 3 + eq] == g[ip + 3 + eq]) eq++;
-                    uint32_t len;
-                    if (maxlen > 16) { // 16 unrolled compares without a bound, then the bounded loop
-                        if (eq < 16) len = 3 + eq;
-                        else { len = 3 + eq < maxlen ? 3 + eq : maxlen; if (len < 19) len = 19; }
-                    } else {
-                        len = 3 + eq < maxlen ? 3 + eq : maxlen;
-                        if (len < 3) len = 3;
-                    }
-                    const uint32_t off = ip - ref - 1, l2 = len - 2;
-                    if (l2 < 7) {
-                        out[op] = (uint8_t)((off >> 8) + (l2 << 5));
-                        out[op + 1] = (uint8_t)off;
-                        op += 2;
-                    } else {
-                        out[op] = (uint8_t)((off >> 8) + (7u << 5));
-                        out[op + 1] = (uint8_t)(l2 - 7);
-                        out[op + 2] = (uint8_t)off;
-                        op += 3;
-                    }
-                    lit = 0; op += 1;
-                    ip += len;
-                    if (ip + 2 >= n) {
-                        state = TAIL;
-                    } else { // VERY_FAST: only the last two positions of the match are inserted
-                        const uint32_t w = lz::rd32(g, ip - 2); // bytes ip-2 .. ip+1
-                        tab_put(tab, lzf_slot(w & 0xFFu, (w >> 8) & 0xFFu, (w >> 16) & 0xFFu), ip - 2);
-                        tab_put(tab, lzf_slot((w >> 8) & 0xFFu, (w >> 16) & 0xFFu, w >> 24), ip - 1);
-                        v = lzf_rd(g, ip, n);
-                    }
-                }
-            } else {
-                if (op >= cap) {
-                    fail = true; state = TAIL;
-                } else {
-                    lit++;
-                    out[op++] = (uint8_t)b0;
-                    if (lit == kMaxLit) { out[op - lit - 1] = (uint8_t)(kMaxLit - 1); lit = 0; op++; }
-                    ip++;
-                    if (ip + 2 < n) v = (v >> 8) | ((uint32_t)(ip + 3 < n ? g[ip + 3] : 0u) << 24);
-                    else state = TAIL;
-                }
-            }
-        }
-
-        if (state == TAIL) {
-            if (!fail) {
-                if (op + 3 > cap) {
-                    fail = true;
-                } else {
-                    while (ip < n) {
-                        lit++;
-                        out[op++] = g[ip++];
-                        if (lit == kMaxLit) { out[op - lit - 1] = (uint8_t)(kMaxLit - 1); lit = 0; op++; }
-                    }
-                    if (lit) out[op - lit - 1] = (uint8_t)(lit - 1);
-                    else op -= 1;
-                }
-            }
-            sizes[blk] = fail ? 0u : op;
-            state = NEXT;
-        }
-    }
+    LzfLaneBlocks s{src, src_stride, nblocks, dst, dst_stride, sizes, counter, handback, reserve, n,
+                    n >= 2048 ? 512u : n / 4 < 128 ? 128u : n / 4, src, dst, 0, false};
+    LzfLaneTab<TAGGED> t{tables + ((size_t)blockIdx.x * 64 + threadIdx.x) * kLzfSlots};
+    lzf_lane_run(s, t);
 }
 
 namespace {

@@ -392,6 +392,115 @@ def test_corrupted_packed_input_gets_the_oracles_verdict(cw, O, alg):
     assert bool((out[:GUARD + 60000] == FILL).all()) and bool((out[GUARD + 61000:] == FILL).all())
 
 
+# ---- the fixed-size path and the chunk path run one loop ---------------------------------------------------------------------------
+def _decode_through_both_decoders(cw, alg, payloads, data, bs):
+    """One compressed result (payloads[i] = block i's bytes, b"" = LZF did not fit), laid out as fixed-stride slots for
+    cw_dev_decompress (lane decoders forced) and as a packed stream for cw_dev_decompress_chunks: status 0 and the input's bytes
+    for every block that has a compressed form, status 1 and nothing written for the others."""
+    import torch
+    nb = len(payloads)
+    sizes = np.array([len(p) for p in payloads], np.int64)
+    stride = (cw.compress_bound(alg, bs) + 15) // 16 * 16
+    slots = np.full((nb, stride), FILL, np.uint8)
+    for i, p in enumerate(payloads):
+        slots[i, :len(p)] = np.frombuffer(p, np.uint8)
+    d_slots = torch.from_numpy(slots).cuda()
+    d_sizes = torch.from_numpy(sizes.astype(np.int32)).cuda()
+    d_packed = torch.from_numpy(np.frombuffer(b"".join(payloads) + bytes(16), np.uint8).copy()).cuda()
+    d_poff, d_raw, d_count = _dev_u64(np.concatenate([[0], sizes.cumsum()])), _dev_u64(np.arange(nb + 1) * bs), _dev_u64([nb])
+    outs = []
+    for door in ("blocks", "chunks"):
+        out = torch.full((nb * bs + GUARD,), FILL, dtype=torch.uint8, device="cuda")
+        status = torch.full((nb,), -1, dtype=torch.int32, device="cuda")
+        if door == "blocks":
+            with cw.tuned(CW_DECODE_LANES=1):
+                cw.dev_decompress(alg, d_slots.data_ptr(), stride, d_sizes.data_ptr(), nb, out.data_ptr(), bs, status.data_ptr(), _stream())
+        else:
+            cw.dev_decompress_chunks(alg, d_packed.data_ptr(), d_poff.data_ptr(), d_raw.data_ptr(), d_count.data_ptr(), nb, out.data_ptr(),
+                                     nb * bs, status.data_ptr(), _stream())
+        torch.cuda.synchronize()
+        assert status.cpu().numpy().tolist() == (sizes == 0).astype(int).tolist(), (alg, bs, door)
+        outs.append(out.cpu().numpy())
+    want = np.concatenate([data, np.full(GUARD, FILL, np.uint8)])
+    for i in np.nonzero(sizes == 0)[0]:
+        want[i * bs:(i + 1) * bs] = FILL
+    for door, o in zip(("blocks", "chunks"), outs):
+        assert np.array_equal(o, want), (alg, bs, door)
+
+
+@pytest.mark.parametrize("bs", [70, 4093, 5001, 65536])
+def test_one_codec_through_both_doors(cw, O, bs):
+    """192 blocks (three wavefronts of lanes) of the Canterbury corpus, compressed once by cw_dev_compress with the lane-per-block
+    parsers forced and once by cw_dev_compress_chunks over the offsets 0, bs, 2 bs, ...: the same loop behind both, so the same
+    sizes and bytes, which are the oracle's; and both results decode to the input through the lane decoders of both paths.
+    (The corpus is 2.8 MB: it is repeated to fill 192 blocks of 64 KiB; its length is no multiple of the block size, so the
+    blocks still differ.  An LZF block that does not fit n - 1 bytes has no compressed form on either path: size 0, status 1.)"""
+    import torch
+    nb = 192
+    corpus = b"".join(corpus_file(n) for n in corpus_names())
+    data = np.frombuffer((corpus * (nb * bs // len(corpus) + 1))[:nb * bs], np.uint8)
+    src = torch.from_numpy(data.copy()).cuda()
+    cuts = [i * bs for i in range(nb + 1)]
+    lz4_lanes = dict(CW_LZ4_LANES=1, CW_LZ4_LANES_RING=0, CW_LZ4_VTAB=0, CW_LANES_CONCURRENT=0)
+    for alg, knob_sets in (("lz4", [lz4_lanes, dict(lz4_lanes, CW_LZ4_LANES_FP=0)]), ("lzf", [dict(CW_LZF_LANES=1)])):
+        fn, scratch = _oracle_fn(O, alg), np.zeros(2 * 65536 + 64, np.uint8)
+        want = []
+        for i in range(nb):
+            c = fn(data.ctypes.data + i * bs, bs, scratch.ctypes.data)
+            want.append(scratch[:c].tobytes())
+        results = []
+        stride = (cw.compress_bound(alg, bs) + 15) // 16 * 16
+        for knobs in knob_sets:
+            dst = torch.full((nb * stride,), FILL, dtype=torch.uint8, device="cuda")
+            sizes = torch.full((nb,), -1, dtype=torch.int32, device="cuda")
+            with cw.tuned(**knobs):
+                cw.dev_compress(alg, src.data_ptr(), bs, nb, dst.data_ptr(), stride, sizes.data_ptr(), _stream())
+                torch.cuda.synchronize()
+                assert alg + "_lanes_kernel" in cw.profile_kernels()["codec"], (knobs, cw.profile_kernels())
+            hs, hd = sizes.cpu().numpy(), dst.cpu().numpy()
+            results.append(("blocks %s" % knobs, [hd[i * stride:i * stride + hs[i]].tobytes() for i in range(nb)]))
+        r = Run(cw, alg, data, cuts=cuts).fetch()
+        assert alg + "_chunks_kernel" in cw.profile_kernels()["codec"] and r.guards_ok
+        slot = [cw.chunk_slot_offset(alg, i * bs, i) for i in range(nb)]
+        results.append(("chunks", [r.image[slot[i]:slot[i] + r.sizes[i]].tobytes() for i in range(nb)]))
+        for door, got in results:
+            bad = [i for i in range(nb) if got[i] != want[i]]
+            assert not bad, (alg, bs, door, "block", bad[0], len(got[bad[0]]), len(want[bad[0]]), len(bad))
+        for door, got in (results[0], results[-1]):
+            _decode_through_both_decoders(cw, alg, got, data, bs)
+
+
+def test_lz4_chunk_table_epoch_wraps(cw, O):
+    """The LZ4 chunk table's epoch has 8 bits: after 255 parses a lane zeroes its table and starts again at 1.  Just under 256 KiB
+    of input get one workgroup of 64 lanes, the input is cut into over 6,500 chunks of 20 .. 40 bytes, and the same call is made
+    six times on one stream, where the lanes' epochs persist: every lane passes its 256th parse, most of them more than once.  The
+    text repeats at distances inside a chunk, so an entry left by an earlier parse that were taken for one of this parse would be
+    a match the reference does not find.  Every call's sizes and bytes are the oracle's.
+    (The LZF table's epoch has 16 bits: wrapping it takes 65,536 chunks per lane, which no test of this size can supply.)"""
+    rng = np.random.default_rng(47)
+    text = corpus_file("alice29.txt")
+    pieces, total, k = [], 0, 0
+    while total < (256 << 10):  # every piece of 5 .. 11 bytes two or three times in a row
+        piece = text[5 * k:5 * k + 5 + k % 7] * (2 + k % 2)
+        pieces.append(piece); total += len(piece); k += 1
+    lens = rng.integers(20, 41, (256 << 10) // 40).tolist()  # (fits whatever is drawn)
+    while sum(lens) + 40 < (256 << 10):
+        lens.append(int(rng.integers(20, 41)))
+    cuts = np.concatenate([[0], np.cumsum(lens)]).tolist()
+    data = np.frombuffer(b"".join(pieces)[:cuts[-1]], np.uint8)
+    assert len(data) < (256 << 10) and len(lens) >= 6500 and 64 * 256 * 2 < 6 * len(lens)
+    want_sizes = want_img = None
+    for call in range(6):
+        r = Run(cw, "lz4", data, cuts=cuts).fetch()
+        if want_sizes is None:
+            want_sizes, want_img = oracle_image(cw, O, "lz4", data, cuts, range(len(lens)), r.total)
+            assert (want_sizes < np.array(lens)).sum() > len(lens) // 2  # most chunks have matches
+        bad = np.nonzero(r.sizes[:len(lens)] != want_sizes)[0]
+        assert len(bad) == 0, (call, "chunk", int(bad[0]), int(r.sizes[bad[0]]), int(want_sizes[bad[0]]), len(bad))
+        diff = np.nonzero(r.image != want_img)[0]
+        assert len(diff) == 0 and r.guards_ok, (call, "slot image differs at", int(diff[0]) if len(diff) else None, len(diff))
+
+
 # ---- a large batch ----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("alg", ALGS)
 def test_one_gib_of_tiled_corpus(cw, O, alg):
