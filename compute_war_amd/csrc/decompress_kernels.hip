@@ -8,10 +8,15 @@
 // out-of-bounds access -- a size that exceeds the slot (comp_stride) is malformed too, and every length is checked
 // against what is left before it is added, so no sum can wrap.
 //
-// A wavefront first copies its compressed block into LDS (coalesced; parsing token by token from global memory costs
-// a dependent ~1 us round trip per token), decodes it into a second LDS buffer (sequences are serial, their byte copies
-// are 64 lanes wide; an overlapping match -- offset < length -- is copied in rounds of `offset` bytes) and then streams
-// the block out.
+// Three kernels decode the same formats (the wavefront decoder with the slot staged in LDS, the same reading the slot from
+// global memory, and the lane-per-block decoder); which one a batch is routed to depends on its size and the block size, the
+// verdict on a slot does not: status 0 iff the stream is well formed, lies inside its slot and yields exactly block_bytes.
+// A valid stream may be longer than its block (LZF: 32-byte literal runs give bs + bs/32, 1-byte runs 2*bs).
+//
+// A wavefront first copies its compressed block into LDS if it fits the staging buffer (coalesced; parsing token by token
+// from global memory costs a dependent ~1 us round trip per token), decodes it into a second LDS buffer (sequences are
+// serial, their byte copies are 64 lanes wide; an overlapping match -- offset < length -- is copied in rounds of `offset`
+// bytes) and then streams the block out.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -39,6 +44,64 @@ __device__ __forceinline__ void copy_match(uint8_t *out, uint32_t op, uint32_t o
         __syncthreads();
     }
 }
+// One block's sequences, the whole wavefront in step: in[0, n) -> out[0, raw_bytes) (LDS).  Returns bad; op = bytes produced.
+// Inlined once per address space of `in` (the staged slot in LDS, the slot itself in global memory).
+template <int ALG>
+__device__ __forceinline__ bool wave_decode(const uint8_t *in, uint32_t n, uint8_t *out, uint32_t raw_bytes, uint32_t lane, bool bad,
+                                            uint32_t &op_out)
+{
+    uint32_t ip = 0, op = 0;
+    if (ALG == 0) {
+        while (!bad) {
+            if (ip >= n) { bad = true; break; }
+            const uint32_t tok = bcast(in[ip]); ip++;
+            uint32_t lit = tok >> 4;
+            if (lit == 15) {
+                uint32_t c;
+                do { if (ip >= n) { bad = true; break; } c = bcast(in[ip]); ip++; lit += c; } while (c == 255);
+                if (bad) break;
+            }
+            if (lit > n - ip || lit > raw_bytes - op) { bad = true; break; } // ip <= n, op <= raw_bytes: no wrap
+            for (uint32_t i = lane; i < lit; i += 64) out[op + i] = in[ip + i];
+            ip += lit; op += lit;
+            if (ip == n) break; // last sequence: literals only
+            if (n - ip < 2) { bad = true; break; }
+            const uint32_t off = bcast((uint32_t)in[ip] | ((uint32_t)in[ip + 1] << 8)); ip += 2;
+            if (off == 0 || off > op) { bad = true; break; }
+            uint32_t ml = tok & 15;
+            if (ml == 15) {
+                uint32_t c;
+                do { if (ip >= n) { bad = true; break; } c = bcast(in[ip]); ip++; ml += c; } while (c == 255);
+                if (bad) break;
+            }
+            if (ml > raw_bytes || ml + 4 > raw_bytes - op) { bad = true; break; }
+            ml += 4;
+            copy_match(out, op, off, ml, lane);
+            op += ml;
+        }
+    } else {
+        while (!bad && ip < n) {
+            const uint32_t ctrl = bcast(in[ip]); ip++;
+            if (ctrl < 32) {
+                const uint32_t run = ctrl + 1;
+                if (run > n - ip || run > raw_bytes - op) { bad = true; break; }
+                if (lane < run) out[op + lane] = in[ip + lane];
+                ip += run; op += run;
+            } else {
+                uint32_t len = ctrl >> 5;
+                if (ip >= n) { bad = true; break; }
+                if (len == 7) { len += bcast(in[ip]); ip++; if (ip >= n) { bad = true; break; } }
+                const uint32_t off = (((ctrl & 0x1f) << 8) | bcast(in[ip])) + 1; ip++;
+                len += 2;
+                if (off > op || len > raw_bytes - op) { bad = true; break; }
+                copy_match(out, op, off, len, lane);
+                op += len;
+            }
+        }
+    }
+    op_out = op;
+    return bad;
+}
 } // namespace
 
 // status[i]: 0 = ok and exactly block_bytes produced, 1 = malformed / wrong size (including sizes[i] == 0, LZF's "did not
@@ -54,11 +117,14 @@ decompress_kernel(const uint8_t *__restrict__ comp, size_t comp_stride, const ui
     for (size_t blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
         const uint8_t *gin = comp + blk * comp_stride;
         const uint32_t n = sizes[blk];
-        uint32_t ip = 0, op = 0;
-        // inside the slot; a valid slot never exceeds the codec's bound (~66 KB), and below 2^24 bytes no run of 255s can wrap a length
-        bool bad = n == 0 || n > comp_stride || n > (1u << 24) || (STAGE_IN && n > in_cap);
+        uint32_t op = 0;
+        // inside the slot; below 2^24 bytes no run of 255s can wrap a length
+        bool bad = n == 0 || n > comp_stride || n > (1u << 24);
+        // A slot longer than the staging buffer is decoded from where it lies: the verdict never depends on in_cap.  (A valid LZF
+        // stream can be longer than its block, up to twice with 1-byte literal runs; the staging buffer holds block_bytes.)
+        const bool staged = STAGE_IN && n <= in_cap;
         __syncthreads();
-        if (STAGE_IN && !bad) {
+        if (staged && !bad) {
             if ((reinterpret_cast<uintptr_t>(gin) & 15) == 0) {
                 for (uint32_t i = lane; i < n / 16; i += 64) reinterpret_cast<uint4 *>(cin)[i] = reinterpret_cast<const uint4 *>(gin)[i];
                 for (uint32_t i = (n & ~15u) + lane; i < n; i += 64) cin[i] = gin[i]; // never read past the slot's bytes
@@ -67,55 +133,8 @@ decompress_kernel(const uint8_t *__restrict__ comp, size_t comp_stride, const ui
             }
         }
         __syncthreads();
-        const uint8_t *in = STAGE_IN ? cin : gin;
-        if (ALG == 0) {
-            while (!bad) {
-                if (ip >= n) { bad = true; break; }
-                const uint32_t tok = bcast(in[ip]); ip++;
-                uint32_t lit = tok >> 4;
-                if (lit == 15) {
-                    uint32_t c;
-                    do { if (ip >= n) { bad = true; break; } c = bcast(in[ip]); ip++; lit += c; } while (c == 255);
-                    if (bad) break;
-                }
-                if (lit > n - ip || lit > block_bytes - op) { bad = true; break; } // ip <= n, op <= block_bytes: no wrap
-                for (uint32_t i = lane; i < lit; i += 64) out[op + i] = in[ip + i];
-                ip += lit; op += lit;
-                if (ip == n) break; // last sequence: literals only
-                if (n - ip < 2) { bad = true; break; }
-                const uint32_t off = bcast((uint32_t)in[ip] | ((uint32_t)in[ip + 1] << 8)); ip += 2;
-                if (off == 0 || off > op) { bad = true; break; }
-                uint32_t ml = tok & 15;
-                if (ml == 15) {
-                    uint32_t c;
-                    do { if (ip >= n) { bad = true; break; } c = bcast(in[ip]); ip++; ml += c; } while (c == 255);
-                    if (bad) break;
-                }
-                if (ml > block_bytes || ml + 4 > block_bytes - op) { bad = true; break; }
-                ml += 4;
-                copy_match(out, op, off, ml, lane);
-                op += ml;
-            }
-        } else {
-            while (!bad && ip < n) {
-                const uint32_t ctrl = bcast(in[ip]); ip++;
-                if (ctrl < 32) {
-                    const uint32_t run = ctrl + 1;
-                    if (run > n - ip || run > block_bytes - op) { bad = true; break; }
-                    if (lane < run) out[op + lane] = in[ip + lane];
-                    ip += run; op += run;
-                } else {
-                    uint32_t len = ctrl >> 5;
-                    if (ip >= n) { bad = true; break; }
-                    if (len == 7) { len += bcast(in[ip]); ip++; if (ip >= n) { bad = true; break; } }
-                    const uint32_t off = (((ctrl & 0x1f) << 8) | bcast(in[ip])) + 1; ip++;
-                    len += 2;
-                    if (off > op || len > block_bytes - op) { bad = true; break; }
-                    copy_match(out, op, off, len, lane);
-                    op += len;
-                }
-            }
-        }
+        if (__builtin_expect(staged, STAGE_IN)) bad = wave_decode<ALG>(cin, n, out, block_bytes, lane, bad, op);
+        else bad = wave_decode<ALG>(gin, n, out, block_bytes, lane, bad, op);
         __syncthreads();
         if (op != block_bytes) bad = true;
         if (!bad) {

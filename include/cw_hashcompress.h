@@ -154,7 +154,12 @@ int cw_dev_hash_and_compress(int hash_alg, int comp_alg, const void *d_src, size
 /* Decoders (the reference calls LZ4_decompress_safe / lzf_decompress only to time them,
  * src/compression_perf/src/experiment.cpp:118,256): decode nblocks compressed slots (comp_stride apart, d_sizes[i]
  * bytes each) into nblocks * block_bytes at d_dst; d_status[i] = 0 iff slot i is well formed and yields exactly
- * block_bytes.  Used as the reference-independent round-trip verifier of the compressors.                     */
+ * block_bytes.  Used as the reference-independent round-trip verifier of the compressors.
+ * The verdict is a property of the slot alone: it does not depend on nblocks, block_bytes' size class or any knob
+ * that routes a batch to one decoder kernel or another.  A valid stream may be longer than block_bytes (LZF: up to
+ * 2 * block_bytes with 1-byte literal runs); it is valid if it fits the slot, d_sizes[i] <= comp_stride.  A size of 0
+ * or beyond comp_stride gives status 1 and nothing is read or written.  The bytes of a block with status 1 are
+ * unspecified; nothing outside a slot's block_bytes of d_dst is ever written.                                     */
 int cw_dev_decompress(int comp_alg, const void *d_comp, size_t comp_stride, const uint32_t *d_sizes, size_t nblocks,
                       void *d_dst, size_t block_bytes, uint32_t *d_status, void *stream);
 /* Skein tree hashing of every block (the reference's Skein_TreeHash,
