@@ -27,6 +27,7 @@
 
 #include "../../include/cw_hashcompress.h"
 #include "cw_device.h"
+#include "launch_plan.h"
 #include "stream_scratch.h"
 
 namespace {
@@ -393,6 +394,22 @@ void cw_tune_reset(void)
 {
     std::lock_guard<std::mutex> g(tune_lock);
     for (KnobValue &o : tune_over) o = KnobValue{};
+}
+
+int cw_plan_describe(int comp_alg, size_t block_bytes, size_t nblocks, unsigned src_misalign, unsigned dst_misalign, char *buf, size_t cap)
+{
+    if (comp_alg != CW_COMP_LZ4 && comp_alg != CW_COMP_LZF) return fail(CW_ERR_BAD_ARG, "unknown compression algorithm %d", comp_alg);
+    if (!(comp_alg == CW_COMP_LZ4 ? cw::lz4_call_valid(block_bytes, nblocks) : cw::lzf_call_valid(block_bytes, nblocks)))
+        return fail(CW_ERR_BAD_ARG, "cw_plan_describe: %zu blocks of %zu bytes is not a call the codec accepts", nblocks, block_bytes);
+    const cw::CodecCall call = {(uint32_t)block_bytes, nblocks, (unsigned)((src_misalign | block_bytes) & 15), (unsigned)((src_misalign | block_bytes) & 3), dst_misalign & 15};
+    const cw::Knobs kn = cw::knobs();
+    std::string text;
+    if (nblocks == 0) text = "\n"; // (such a call launches nothing)
+    else if (comp_alg == CW_COMP_LZ4) { const cw::Lz4Plan p = cw::lz4_plan(call, kn); text = std::string(cw::describe(p).text) + "\n" + cw::dump(p); }
+    else { const cw::LzfPlan p = cw::lzf_plan(call, kn); text = std::string(cw::describe(p).text) + "\n" + cw::dump(p); }
+    if (!buf || cap <= text.size()) return fail(CW_ERR_BAD_ARG, "cw_plan_describe: the text needs a buffer of %zu bytes", text.size() + 1);
+    memcpy(buf, text.c_str(), text.size() + 1);
+    return CW_OK;
 }
 
 // ---- lifecycle ------------------------------------------------------------------------------------

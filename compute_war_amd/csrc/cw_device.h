@@ -6,7 +6,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include <optional>
+#include "knobs.h"
 
 #ifndef CW_SKEIN_THREADS
 #define CW_SKEIN_THREADS 64 // one wavefront per workgroup: lanes never communicate, small groups spread evenly
@@ -53,40 +53,6 @@ struct SkeinIV { uint64_t w[8]; };
 // The launch functions note which kernels they used, per calling thread (kind 0 = codec, 1 = hash): cw_profile_kernels
 // hands the names to the caller so that a benchmark reports what ran instead of guessing it from its arguments.
 void note_kernels(int kind, const char *names);
-// The tuning / test knobs (CW_TESTING in the public header), decoded.  A knob's value is what cw_tune_set gave it, else the
-// environment variable of the same name; the table in cw_api.hip is the only code that knows their names and formats.  Knobs
-// marked "> 0" hold the value only when it is a positive number and 0 otherwise; std::nullopt = unset.  Defaults that depend on
-// the call stay where the call decides.
-enum class Lz4Mode : uint8_t { normal, scan, generic, stream, cut }; // CW_LZ4_MODE (other values: normal)
-enum class LzfMode : uint8_t { normal, cut, table };                // CW_LZF_MODE (other values: normal)
-enum class SkeinMode : uint8_t { by_lean, steps, lines };           // CW_SKEIN_MODE: unset / "steps" / any other value
-enum class SidePrio : uint8_t { both, lanes, none };                // CW_SIDE_PRIO: unset or 2... / other / 0...: streams on the high-priority pool
-struct Knobs {
-    // first character
-    bool skein_sliced = true, lz4_lanes_fp = true, lzf_sthread = true; // off iff it starts with '0'
-    bool serial = false, debug_host = false, prepare_cold = false;     // on iff it starts with '1'
-    std::optional<bool> fused_gate, host_shared_streams;               // set: starts with '1'
-    std::optional<bool> lanes_concurrent;                              // set: does not start with '0'
-    SidePrio side_prio = SidePrio::both;
-    // strings, presence
-    Lz4Mode lz4_mode = Lz4Mode::normal;
-    LzfMode lzf_mode = LzfMode::normal;
-    SkeinMode skein_mode = SkeinMode::by_lean;
-    bool lz4_parse_fp = false; // CW_LZ4_PARSE == "fp"
-    bool debug_lzf = false;    // set, to any value
-    // > 0
-    int scan_wpc = 0, parse_wpc = 0, lanes_wpc = 0, lanes_reserve = 0, vtab_wpc = 0, lzf_st_wpc = 0, lzf_round = 0, lzf_lds_max = 0,
-        skein_nslices = 0;
-    long host_chunk_mb = 0, host_big_chunk_mb = 0, cdc_segment = 0;
-    bool force_redo = false, lzf_share_give_up = false; // CW_LZ_FORCE_REDO, CW_LZF_SHARE_GIVE_UP
-    // set: atoi of the value ("" = 0)
-    std::optional<int> lz4_lanes, lzf_lanes, decode_lanes, lanes_leave, vtab_min, vtab_max, vtab_reserve, lz4_vtab, lz4_lanes_ring,
-        lz4_headw, lz4_ltab, vtab_gen;
-    std::optional<int> lz4_stage_max; // set: atoi of the value if it is >= 0
-};
-// The knobs as they are now: each launch function takes one snapshot when it starts, so tests sweep settings in one process.
-Knobs knobs();
-
 // host: chaining value after the configuration block (Skein_*_Init)
 void skein_compute_iv(int state_words, unsigned hash_bits, SkeinIV *iv, uint64_t tree_info = 0);
 // sliced Skein for the fused call: the steps of every block in 8 launches (see skein_kernels.hip)
@@ -114,15 +80,13 @@ hipError_t lz4_launch(const uint8_t *src, size_t block_bytes, size_t src_stride,
 const uint32_t *lz4_queued_blocks_word(hipStream_t stream);
 hipError_t lzf_launch(const uint8_t *src, size_t block_bytes, size_t src_stride, size_t nblocks, uint8_t *dst,
                       size_t dst_stride, uint32_t *sizes, hipStream_t stream);
-// LZ4 parser with the table in vector registers (lz4_vtab_kernel.hip): parses blocks of the scan's queue (counters[0] = head,
-// counters[1] = length) while more than `reserve` are left, if the queue's length lies in [min_queued, max_queued); gen = kernel generation
-// (2 or 3; any other value: chosen by block size)
-hipError_t lz4_vtab_launch(const uint8_t *src, uint32_t n, size_t src_stride, size_t nblocks, uint8_t *dst, size_t dst_stride, uint32_t *sizes,
-                           const uint32_t *queue, uint32_t *counters, uint32_t min_queued, uint32_t max_queued, uint32_t reserve,
-                           unsigned waves_per_cu, int gen, hipStream_t stream, const char **kernel_name);
-// the same scalar-thread parser with its table in LDS (ten wavefronts per CU): takes what is left of the queue
-hipError_t lz4_ltab_launch(const uint8_t *src, uint32_t n, size_t src_stride, size_t nblocks, uint8_t *dst, size_t dst_stride, uint32_t *sizes,
-                           const uint32_t *queue, uint32_t *counters, unsigned waves_per_cu, hipStream_t stream);
+enum class Lz4Vtab : uint8_t; // (launch_plan.h)
+// LZ4 scalar-thread parsers (lz4_vtab_kernel.hip; the plan chooses the member, the grid and the LDS bytes): they parse blocks of the
+// scan's queue (counters[0] = head, counters[1] = length) while more than `reserve` are left, if the queue's length lies in
+// [min_queued, max_queued)
+hipError_t lz4_vtab_launch(Lz4Vtab kernel, uint32_t grid, uint32_t lds, hipStream_t stream, const uint8_t *src, uint32_t n, size_t src_stride, uint8_t *dst,
+                           size_t dst_stride, uint32_t *sizes, const uint32_t *queue, uint32_t *counters, uint32_t min_queued, uint32_t max_queued,
+                           uint32_t reserve);
 hipError_t decompress_launch(int alg, const uint8_t *comp, size_t comp_stride, const uint32_t *sizes, size_t nblocks, uint8_t *dst,
                              size_t block_bytes, uint32_t *status, hipStream_t stream);
 // packed stream: offsets[i] = sum sizes[0..i) (nblocks + 1 entries); slot i copied to packed + offsets[i] (packed may be NULL)

@@ -39,10 +39,12 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <optional>
 #include <type_traits>
 
 #include "cw_device.h"
 #include "lane_codec.h"
+#include "launch_plan.h"
 #include "lz_device.h"
 #include "stream_scratch.h"
 
@@ -65,8 +67,7 @@ using namespace lane; // kMinMatch / kLastLiterals / kMFLimit, hash13, ld16g and
 
 namespace {
 
-constexpr uint32_t kTabBytes = (1u << 13) * 2; // 8192 x u16
-constexpr uint32_t kStageMax = 16384;          // parse kernel: blocks up to this size are staged in LDS
+// (kTabBytes, kStageMax, kFpBytes, kChunk: launch_plan.h, shared with the launch policy)
 constexpr uint32_t kNeedsParse = 0xFFFFFFFFu;  // sizes[] marker: scan kernel -> parse kernel
 constexpr int kScanGroup = 16;                 // probe batches in flight per wavefront in the generic scan kernel
 
@@ -285,7 +286,7 @@ lz4_scan_kernel(const uint8_t *__restrict__ src, uint32_t n, size_t src_stride, 
 // hit, so compressible data costs a chunk or two of reads and at most one chunk of wasted stores here.
 // LDS: 32 KiB table + 8 KiB ring = 40 KiB -> 4 wavefronts per CU.
 // ---------------------------------------------------------------------------------------------------
-constexpr uint32_t kChunk = 4096, kPieces = kChunk / 1024, kRing = 2 * kChunk, kStreamGroup = 2;
+constexpr uint32_t kPieces = kChunk / 1024, kRing = 2 * kChunk, kStreamGroup = 2;
 
 struct Chunk { uint4 p[kPieces]; }; // 4 KiB of the block across the wavefront: piece j, lane L = bytes [j*1024 + L*16, +16)
 
@@ -1221,7 +1222,6 @@ lz4_parse_kernel(const uint8_t *__restrict__ src, uint32_t n, size_t src_stride,
 // The fingerprint exchange relies on the same lane order as the position exchange; it is checked the same way: a
 // lane whose candidate was inserted by an earlier lane of the same batch must have received that lane's fingerprint.
 // ---------------------------------------------------------------------------------------------------
-constexpr uint32_t kFpBytes = (1u << 13) / 2; // 4-bit fingerprint per table slot
 
 // Diagnostic build only (-DCW_STAMP, tools/parse_stamp.hip): where a sequence's cycles go.  A stamp is s_memtime behind a
 // drained LDS/scalar queue; the differences are summed per phase in scalar registers and added to g_stamp once per block.
@@ -1552,25 +1552,12 @@ lz4_parse_fp_kernel(const uint8_t *__restrict__ src, uint32_t n, size_t src_stri
 // owns a block and runs the serial parser as it stands (the oracle's loop, one probe per iteration), its table in global
 // memory (16 KiB per lane, zeroed by the lane when it takes a block): 64 chains per wavefront, tens of thousands per
 // chip, bound by how many random table / candidate accesses the memory system retires, not by any one chain's latency.
-// It only pays when there are that many blocks: lz4_launch uses it from kLaneMidBlocks queued blocks on.
+// It only pays when there are that many blocks: lz4_plan (launch_plan.cpp) uses it from kLaneMidBlocks queued blocks on.
 //
 // The loop itself (the lanes' states, the window requested a step ahead, every bound) is lz4_lane_run in lane_codec.h, shared
 // with the parser over content-defined chunks; this file supplies the queue the blocks come from and the table's entry formats.
 // ---------------------------------------------------------------------------------------------------
-// blocks > 4 KiB: below kLaneMidBlocks queued blocks the wavefront-per-block parser's 13-14 GB/s win; [mid, wide): lanes with two
-// positions per iteration (every lane holds one block: latency regime), from kLaneWideBlocks on one (random-line regime); lz4_launch
-// Round 3: below kLaneMidBlocks the two scalar-thread parsers (table in vector registers / in LDS, lz4_vtab_kernel.hip) win (corpus, 64 KiB: 12 Ki /
-// 16 Ki / 20 Ki blocks 23.9 / 27.3 / 29.0 GB/s against the lanes' 15.4 / 19.5 / ~22), so the lanes start later than in round 2 (10,240), and from there on
-// they run BESIDE those two: in the one-block-per-lane regime there are no lanes for kLaneLeave blocks of the queue and the lanes leave kLaneShare
-// blocks (two thirds of a small call) alone; from kLaneWideBlocks on they leave kLaneShareWide.  One launch for both regimes (lz4_lanes_ring_auto_kernel).
-constexpr uint32_t kLaneMidBlocks = 22528, kLaneWideBlocks = 98304; // (blocks <= 32 KiB: higher lower thresholds, lz4_launch)
-constexpr bool kLtabDefault = true; // corpus, 64 KiB, alone on the queue: 8 Ki / 16 Ki / 48 Ki blocks 16.1 / 17.5 / 18.6 GB/s against the wavefront parser's 14.6 / 15.8 / 16.6; beside the register form 23.3 / 26.7 against 22.2 / 25.4
-constexpr size_t kLaneLeave = 18432;   // blocks > 4 KiB, calls below kLaneWideBlocks: this many blocks get no lane (lz4_launch has the measurements)
-constexpr uint32_t kLaneShare = 24576, kLaneShareWide = 32768;     // blocks of the queue the lanes leave to the other parsers (K = 2 / K = 1 regime); K = 2: at most two thirds of
-                                                                   // the call -- since the lanes no longer take the whole queue at once (kLaneLeave) they pay from 22 Ki blocks on: corpus,
-                                                                   // 64 KiB, 20 Ki / 24 Ki / 28 Ki blocks without lanes 29.0 / 29.4 / 29.8 GB/s, with 28.2 / 31.7 / 35.3 (16 Ki left);
-                                                                   // 56 Ki / 72 Ki blocks with 16 Ki left 39.9-43.9 / 43.2-48.1, with 24 Ki 47.1 / 48.2-48.7
-constexpr uint32_t kLaneMinSmall = 61440;  // LDS-staged blocks: lanes beside the LDS-resident parser from 60 Ki blocks on (64 Ki blocks of text: 28.5 against 25.7 GB/s)
+// (when the lanes run, beside what, and what they leave to the others: lz4_plan in launch_plan.cpp, with the measurements)
 // Table entries:
 //   kLaneTagged (blocks <= 4 KiB)  u16 epoch:4 | position:12; an entry of another epoch reads as empty (= position 0, as in the
 //                                  parser's zeroed table) and the table is zeroed once per 15 blocks instead of per block
@@ -1970,7 +1957,7 @@ lz4_lanes_ring_kernel(const uint8_t *__restrict__ src, uint32_t n, size_t src_st
 }
 
 // The launch policy's form: ONE launch, the number of positions per iteration chosen on the device by the queue's length (two below wide_from,
-// one from there on; see lz4_launch).  Until round 3 these were two launches on one stream, each returning at once outside its range -- and from
+// one from there on; see lz4_plan).  Until round 3 these were two launches on one stream, each returning at once outside its range -- and from
 // kLaneWideBlocks queued blocks on the second one lost the race for the CUs: while the first launch's workgroups came and went, the register-table
 // and LDS-table parsers of the other streams had filled every CU (the register-table parser alone takes a CU's whole vector register file), and the
 // lanes only started when those ran out of queue: corpus, 64 KiB, 128 Ki / 256 Ki blocks 30.3 / 31.5 GB/s instead of 47.2 / 49.0.
@@ -1987,7 +1974,7 @@ lz4_lanes_ring_auto_kernel(const uint8_t *__restrict__ src, uint32_t n, size_t s
     if (qcount >= wide_from) {
         lz4_lanes_ring_body<1>(ring, qcount, src, n, src_stride, dst, dst_stride, sizes, queue, counters, tables, reserve_wide);
     } else {
-        // below wide_from every lane gets one block: no lanes for the leave_mid blocks the on-chip parsers get through meanwhile (lz4_launch)
+        // below wide_from every lane gets one block: no lanes for the leave_mid blocks the on-chip parsers get through meanwhile (lz4_plan)
         if ((size_t)blockIdx.x * 64 + leave_mid >= qcount && blockIdx.x > 0) return;
         lz4_lanes_ring_body<2>(ring, qcount, src, n, src_stride, dst, dst_stride, sizes, queue, counters, tables, reserve_mid);
     }
@@ -2012,308 +1999,133 @@ const uint32_t *lz4_queued_blocks_word(hipStream_t stream)
     return !w || !w->queues.bytes() ? nullptr : w->queues.as<uint32_t>() + 1;
 }
 
+// ---- the kernel families of the launch (launch_plan.h): member, name as rocprofv3 prints it, kernel ------------------------------
+namespace {
+const KernelRow<Lz4ScanSpan, decltype(lz4_scan_span_kernel<true>)> kScanSpanKernels[] = {
+    {Lz4ScanSpan::unaligned, "cw::lz4_scan_span_kernel<false>", lz4_scan_span_kernel<false>},
+    {Lz4ScanSpan::aligned, "cw::lz4_scan_span_kernel<true>", lz4_scan_span_kernel<true>},
+};
+const KernelRow<Lz4Parse, decltype(lz4_parse_kernel<true>)> kParseKernels[] = {
+    {Lz4Parse::global, "cw::lz4_parse_kernel<false>", lz4_parse_kernel<false>},
+    {Lz4Parse::staged, "cw::lz4_parse_kernel<true>", lz4_parse_kernel<true>},
+    {Lz4Parse::fp8, "cw::lz4_parse_fp_kernel<8>", lz4_parse_fp_kernel<8>},
+    {Lz4Parse::fp16, "cw::lz4_parse_fp_kernel<16>", lz4_parse_fp_kernel<16>},
+    {Lz4Parse::fp32, "cw::lz4_parse_fp_kernel<32>", lz4_parse_fp_kernel<32>},
+};
+const KernelRow<Lz4Lanes, decltype(lz4_lanes_kernel<kLanePlain>)> kLanesKernels[] = {
+    {Lz4Lanes::plain, "cw::lz4_lanes_kernel<0>", lz4_lanes_kernel<kLanePlain>},
+    {Lz4Lanes::tagged, "cw::lz4_lanes_kernel<1>", lz4_lanes_kernel<kLaneTagged>},
+    {Lz4Lanes::fp, "cw::lz4_lanes_kernel<2>", lz4_lanes_kernel<kLaneFp>},
+};
+const KernelRow<Lz4Ring, decltype(lz4_lanes_ring_kernel<1>)> kRingKernels[] = {
+    {Lz4Ring::k1, "cw::lz4_lanes_ring_kernel<1>", lz4_lanes_ring_kernel<1>},
+    {Lz4Ring::k2, "cw::lz4_lanes_ring_kernel<2>", lz4_lanes_ring_kernel<2>},
+    {Lz4Ring::k4, "cw::lz4_lanes_ring_kernel<4>", lz4_lanes_ring_kernel<4>},
+    {Lz4Ring::k8, "cw::lz4_lanes_ring_kernel<8>", lz4_lanes_ring_kernel<8>},
+};
+const KernelRow<Lz4Blocks, decltype(lz4_blocks_kernel<true>)> kBlocksKernels[] = {
+    {Lz4Blocks::global, "cw::lz4_blocks_kernel<false>", lz4_blocks_kernel<false>},
+    {Lz4Blocks::staged, "cw::lz4_blocks_kernel<true>", lz4_blocks_kernel<true>},
+};
+
+// (dynamic-LDS limits: stream_scratch.h)
+hipError_t lz4_set_attributes()
+{
+    static std::atomic<bool> done{false};
+    return set_lds_limits_once(done, {{reinterpret_cast<const void *>(lz4_blocks_kernel<true>), kStageMax + kTabBytes + 16},
+                                      {reinterpret_cast<const void *>(lz4_parse_kernel<true>), kStageMax + kTabBytes + 16}});
+}
+} // namespace
+const char *kernel_name(Lz4ScanSpan k) { return kernel_row(kScanSpanKernels, k).name; }
+const char *kernel_name(Lz4Parse k) { return kernel_row(kParseKernels, k).name; }
+const char *kernel_name(Lz4Lanes k) { return kernel_row(kLanesKernels, k).name; }
+const char *kernel_name(Lz4Ring k) { return kernel_row(kRingKernels, k).name; }
+const char *kernel_name(Lz4Blocks k) { return kernel_row(kBlocksKernels, k).name; }
+
+// plan (launch_plan.cpp: every decision), reserve, enqueue
 hipError_t lz4_launch(const uint8_t *src, size_t block_bytes, size_t src_stride, size_t nblocks, uint8_t *dst,
                       size_t dst_stride, uint32_t *sizes, hipStream_t stream, const AfterScan *after_scan)
 {
     if (nblocks == 0) return hipSuccess;
-    if (block_bytes == 0 || block_bytes > 65536 || nblocks > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    if (!lz4_call_valid(block_bytes, nblocks)) return hipErrorInvalidValue;
     const uint32_t n = (uint32_t)block_bytes;
     const Knobs kn = knobs();
-    // CW_LZ4_STAGE_MAX (profiling knob): largest block parsed from an LDS copy
-    // measured on text: 4 KiB 26.0 (staged) vs 22.4 GB/s (global); 8 KiB 18.1 vs 20.6; 16 KiB 11.5 vs 18.7 -- blocks per CU win
-    const uint32_t stage_max = kn.lz4_stage_max ? (uint32_t)*kn.lz4_stage_max : 4096u;
-    const bool staged = n <= (stage_max < kStageMax ? stage_max : kStageMax);
-    // staged bytes are read as aligned dwords: a size that is not a multiple of 4 gets 16 bytes of slack behind it
-    uint32_t lds = kTabBytes + (staged ? ((n + 15u) & ~15u) + (n % 4 ? 16u : 0u) : 0u);
-    static bool attr_set = false; // benign race: idempotent
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(lz4_blocks_kernel<true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, kStageMax + kTabBytes + 16);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(lz4_parse_kernel<true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kStageMax + kTabBytes + 16);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
+    const CodecCall call = codec_call(src, block_bytes, src_stride, nblocks, dst, dst_stride);
+    Lz4Plan p = lz4_plan(call, kn);
+    hipError_t e = lz4_set_attributes();
+    if (e != hipSuccess) return e;
     auto &wsp = workspaces.at(stream);
     LaunchLock sequence(wsp.launch); // counters/queues are shared by every launch below
     // (only ever allocates on the first, or a larger, call on this stream)
-    hipError_t e = wsp.queues.reserve((2 * nblocks + 8) * sizeof(uint32_t), (2 * 4096 + 8) * sizeof(uint32_t));
-    if (e != hipSuccess) return e;
+    if ((e = wsp.queues.reserve(p.queue_bytes, p.queue_min_bytes)) != hipSuccess) return e;
+    // a nearly full device does without the lanes instead of failing the call
+    if (p.lanes.on && wsp.lane_tabs.reserve(p.lane_tab_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        p = lz4_plan(call, kn, false);
+    }
     const size_t cap = (wsp.queues.bytes() / sizeof(uint32_t) - 8) / 2;
     uint32_t *counters = wsp.queues.as<uint32_t>(), *queue = counters + 8, *queue2 = queue + cap;
+    uint16_t *const lane_tabs = wsp.lane_tabs.as<uint16_t>();
     // the forks onto the two side streams: a return before the joins below still joins them (lanes last, as below)
     std::optional<SideStream::Fork> lanes_fork, vtab_fork;
-    // what this call launches, noted in the branch that launches it (cw_profile_kernels): names as rocprofv3 prints them; a kernel that
-    // decides on the device whether the queue's length is in its range carries the range
-    char launched[320] = "";
-    auto note = [&](const char *fmt, auto... a) __attribute__((format(printf, 2, 0))) {
-        const size_t used = strlen(launched);
-        if (used && used + 3 < sizeof launched) strcat(launched, " + ");
-        const size_t at = strlen(launched);
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wformat-security"
-        snprintf(launched + at, sizeof launched - at, fmt, a...);
-#pragma clang diagnostic pop
-    };
+    auto on = [&](const Stage &s) { return s.stream == Target::lanes_side ? wsp.lanes.stream : s.stream == Target::vtab_side ? wsp.vtab.stream : stream; };
+    auto pool = [](SidePool sp) { return sp == SidePool::greatest ? SideStream::greatest : SideStream::normal; };
 
     if ((e = hipMemsetAsync(counters, 0, 8 * sizeof(uint32_t), stream)) != hipSuccess) return e;
-    // scan: one wavefront per workgroup, 32 KiB of LDS each -> 5 per CU; the grid-stride loop walks the rest
-    const size_t scan_grid = nblocks < 256 * 5 ? nblocks : 256 * 5;
-    // CW_LZ4_MODE=generic forces the gather-based scan (profiling knob)
-    const bool streamable = ((reinterpret_cast<uintptr_t>(src) | src_stride | n) & 15) == 0 && kn.lz4_mode != Lz4Mode::generic;
-    if (streamable) {
-        // CW_SCAN_WPC: scan wavefronts per CU (profiling knob; 4 = all that fit)
-        const size_t wpc = kn.scan_wpc ? (size_t)kn.scan_wpc : 4;
-        // power-of-two sizes 4 KiB .. 64 KiB go through the span kernel, 64 KiB of whole blocks per pull; what does not
-        // fill a span (and every other size) through the per-block streaming kernel.  CW_LZ4_MODE=stream: the latter only.
-        const bool pow2 = n >= kChunk && (n & (n - 1)) == 0 && kn.lz4_mode != Lz4Mode::stream;
-        uint32_t lg = 0;
-        while (pow2 && (kChunk << lg) < n) lg++;
-        const size_t run = pow2 ? (size_t)(16u >> lg) : 1;
-        const size_t nspans = pow2 ? nblocks / run : 0, done = nspans * run;
-        if (nspans) {
-            const size_t g = nspans < 256 * wpc ? nspans : 256 * wpc; // 40 KiB of LDS each -> at most 4 per CU
-            // 16-byte aligned slots: the literal runs go out as aligned lines (any other slot alignment: misaligned 16-byte stores)
-            const bool aligned = ((reinterpret_cast<uintptr_t>(dst) | dst_stride) & 15) == 0;
-            if (aligned) {
-                hipLaunchKernelGGL(lz4_scan_span_kernel<true>, dim3((unsigned)g), dim3(64), 0, stream, src, n, src_stride, (uint32_t)nspans,
-                                   dst, dst_stride, sizes, scan_probes(n), queue, counters, lg);
-                note("cw::lz4_scan_span_kernel<true>");
-            } else {
-                hipLaunchKernelGGL(lz4_scan_span_kernel<false>, dim3((unsigned)g), dim3(64), 0, stream, src, n, src_stride, (uint32_t)nspans,
-                                   dst, dst_stride, sizes, scan_probes(n), queue, counters, lg);
-                note("cw::lz4_scan_span_kernel<false>");
-            }
-        }
-        if (done < nblocks) {
-            const size_t rest = nblocks - done;
-            const size_t sgrid = rest < 256 * wpc ? rest : 256 * wpc;
-            hipLaunchKernelGGL(lz4_scan_stream_kernel, dim3((unsigned)sgrid), dim3(64), 0, stream, src, n, src_stride, nblocks, dst,
-                               dst_stride, sizes, scan_probes(n), queue, counters, done, 3u);
-            note("cw::lz4_scan_stream_kernel");
-        }
-    } else {
-        hipLaunchKernelGGL(lz4_scan_kernel, dim3((unsigned)scan_grid), dim3(64), 0, stream, src, n, src_stride, nblocks, dst,
+    if (p.scan_span.on)
+        hipLaunchKernelGGL(kernel_row(kScanSpanKernels, p.scan_span_kernel).fn, dim3(p.scan_span.grid), dim3(64), 0, stream, src, n, src_stride, p.nspans,
+                           dst, dst_stride, sizes, scan_probes(n), queue, counters, p.lg);
+    if (p.scan_stream.on)
+        hipLaunchKernelGGL(lz4_scan_stream_kernel, dim3(p.scan_stream.grid), dim3(64), 0, stream, src, n, src_stride, nblocks, dst,
+                           dst_stride, sizes, scan_probes(n), queue, counters, p.done, 3u);
+    if (p.scan_generic.on)
+        hipLaunchKernelGGL(lz4_scan_kernel, dim3(p.scan_generic.grid), dim3(64), 0, stream, src, n, src_stride, nblocks, dst,
                            dst_stride, sizes, scan_probes(n), queue, counters);
-        note("cw::lz4_scan_kernel");
-    }
     if ((e = hipGetLastError()) != hipSuccess) return e;
     // the fused call's hook (cw_api.hip, dev_fused): what it enqueues here runs beside the scan, and the parsers below wait for it
     if (after_scan && (e = after_scan->fn(after_scan->ctx)) != hipSuccess) return e;
-    // CW_LZ4_MODE=scan stops after the scan kernel (queued blocks keep sizes[i] = 0xFFFFFFFF): a profiling knob
-    if (kn.lz4_mode == Lz4Mode::scan) { note_kernels(0, launched); return hipSuccess; }
-    // parse: queued blocks only; LDS admits 160 KiB / lds workgroups per CU
-    // CW_LZ4_PARSE=fp: blocks read from global memory go through the fingerprint parser (20 KiB of LDS, 8 blocks per CU).
-    // Measured on text at 64 KiB: 11.9 GB/s against 14.2 GB/s for the second generation with its 10 blocks per CU -- both
-    // are bound by the instruction latency of one sequence's serial chain (tools/parse_stamp.hip), not by candidate
-    // traffic, so the extra blocks win; the second generation stays the default.
-    const bool use_fp = !staged && kn.lz4_parse_fp;
-    const int headw = kn.lz4_headw.value_or(16); // CW_LZ4_HEADW: head batch width of the fingerprint parser (profiling knob: 8, 16, 32)
-    if (use_fp) lds = kTabBytes + kFpBytes;
-    const size_t per_cu = (160u * 1024u) / lds ? (160u * 1024u) / lds : 1;
-    // Large batches: the lane-per-block parser.  Two regimes:
-    //  * blocks read from global memory (> 4 KiB), from kLaneMidBlocks queued blocks on: the lanes take the whole queue, the
-    //    wavefront-per-block parser only what they leave (running it beside the lanes gains nothing there: both end up waiting
-    //    for the same memory system -- 33.1 vs 34.2 GB/s);
-    //  * LDS-staged blocks (<= 4 KiB), from kLaneMinSmall blocks on: the lanes run BESIDE the LDS-resident parser on a second
-    //    stream, both pulling from the scan's queue -- one is bound by LDS capacity and its chain latency, the other by random
-    //    memory accesses, and the rates add (4 KiB text: 26.2 -> 40.1 GB/s).
-    // The kernel looks at the queue length on the device and leaves everything to the wavefront parser below the threshold.
-    // CW_LZ4_LANES=0 switches it off, =N sets the threshold (1: every queued block, in the tests); CW_LANES_WPC = its
-    // wavefronts per CU, CW_LANES_CONCURRENT=0|1 forces the regime, CW_LANES_RESERVE the blocks left to the wavefronts.
-    // measured break-even with the wavefront parser on text (GB/s, wavefront parser / lanes): 64 KiB 16 Ki blocks 14.2 / 20.9; 16 KiB 16 Ki
-    // blocks 18.3 / 17.4, 24 Ki 18.3 / 20.7; 8 KiB 24 Ki blocks 20.9 / 18.5, 32 Ki 20.4 / 22.7 (on small blocks the wavefront parser
-    // is faster and a lane slower per byte: every block starts on an empty table, and has one to zero)
-    const uint32_t lane_min = kn.lz4_lanes ? (uint32_t)*kn.lz4_lanes
-                              : staged ? kLaneMinSmall : n > 32768 ? kLaneMidBlocks : n > 16384 ? 40960u : n > 8192 ? 61440u : 98304u;
-    // (16 KiB blocks: the register-table + wavefront parsers 25.7 / 27.9 / 29.3 GB/s at 16 Ki / 32 Ki / 64 Ki blocks against the lanes' 19.5 / 25.0 / 30.1;
-    //  8 KiB blocks: 25.5 / 28.8 / 30.0 at 16 Ki / 48 Ki / 96 Ki blocks against 21.4 / 21.3 / 30.3)
-    bool lanes_used = false, lanes_beside = false;
-    // CW_LZ4_LANES_RING: 0 = input from global memory (lz4_lanes_kernel); 1, 2, 4, 8 = the ring form with that many positions per
-    // iteration whatever the queue's length.  Unset: the ring form, K chosen ON THE DEVICE by the queue's length -- two launches,
-    // each of which returns at once unless the length lies in its range:
-    //   [kLaneMidBlocks, kLaneWideBlocks)  K = 2.  Every lane holds one block and the call lasts as long as one lane needs for
-    //       one block: latency, not lines, so the second position's table entry and candidate requested together with the
-    //       first's pay (text, 64 KiB, 16 Ki / 24 Ki / 32 Ki blocks: 21.1 / 26.0 / 29.9 GB/s against 16.4 / 21.0 / 27.0 with K = 1
-    //       and 14.2 for the wavefront parser, which keeps everything below ~10 Ki blocks: 8 Ki blocks 13.5 against 11.8);
-    //   [kLaneWideBlocks, ...)             K = 1.  Enough chains to be bound by the memory system's random lines, where the
-    //       lines of the speculative second position only cost (64 Ki blocks: 38.3 against 35.6 GB/s).
-    //   K = 4 / 8 are never better (16 Ki blocks: 20.0 / 16.4 GB/s): each position adds instructions to every iteration.
-    const int lanes_ring = kn.lz4_lanes_ring.value_or(-1); // -1: by queue length
-    // CW_LANES_CONCURRENT=0: one after the other on the caller's stream (the lanes take the whole queue); default: side by side
-    const bool lanes_concurrent = kn.lanes_concurrent.value_or(true);
-    if (!use_fp && lane_min && nblocks >= lane_min && n >= 64) {
-        const size_t lwpc = kn.lanes_wpc ? (size_t)kn.lanes_wpc : 8;
-        size_t lgrid = (nblocks + 63) / 64, lcap = 256 * lwpc;
-        uint32_t lane_leave = 0;
-        // LDS-staged blocks, lanes beside the wavefront parser: lanes for about half of the blocks (2 .. 8 wavefronts per CU).  With
-        // fewer lanes each is faster (less traffic per probe in flight), and a batch of 64 Ki .. 256 Ki blocks is over before a lane
-        // has parsed more than two or three (text, 4 KiB, 80 Ki / 128 Ki / 256 Ki blocks: 2 wavefronts per CU 34.4 / 33.6 / 35.6 GB/s,
-        // 4: 27.7 / 39.6 / 36.5, 8: 24.9 / 26.0 / 39.0-41.0; the wavefront parser alone 25.8)
-        if (staged && !kn.lanes_wpc) lcap = nblocks / 128 < 512 ? 512 : nblocks / 128 > 2048 ? 2048 : nblocks / 128;
-        if (lgrid > lcap) lgrid = lcap;
-        // blocks > 4 KiB, lanes beside the on-chip parsers, calls below kLaneWideBlocks (every lane gets ONE block and the call lasts as long as a lane
-        // needs for it, 60-110 ms depending on how many lanes run): no lanes for the ~18 Ki blocks the two on-chip parsers get through in that time.
-        // A grid with a lane for every block takes the whole queue in its first microseconds (every lane passes the "leave `reserve` blocks" check
-        // before any has drawn) and the on-chip parsers get nothing: 64 Ki blocks, the lanes' kernel 110 ms, the two scalar-thread kernels beside
-        // it 15 ms each.  Corpus, 64 KiB, share of the blocks with a lane 100 / 85 / 72 / 60 / 50 %, GB/s: 32 Ki blocks 32.5 / 33.5 / 33.0 / 35.2 / 37.6,
-        // 48 Ki 42.5 / 43.2 / 44.1 / 46.8 / 39.2, 64 Ki 41.1 / 42.9 / 47.3 / 45.2 / 42.1 (best: all but 16-19 Ki blocks); 128 Ki and 256 Ki blocks
-        // (lanes take several blocks each, the reserve works): 47.8 / 42.6 / 46.5 / 44.6 / 44.7 and 47.6-49.1, no trend.
-        // (the kernel applies the same rule to the queue's length, which may be shorter than the call: blocks the scan has dealt with are not queued)
-        // CW_LANES_LEAVE: blocks of such a call that get no lane (profiling knob; 0 = a lane for every block)
-        const size_t leave = kn.lanes_leave ? (size_t)*kn.lanes_leave : kLaneLeave;
-        if (!staged && leave && lanes_concurrent && lane_min > 1) {
-            lane_leave = (uint32_t)leave;
-            const size_t want = nblocks > leave + 4096 ? (nblocks - leave + 63) / 64 : 64;
-            if (nblocks < kLaneWideBlocks && lgrid > want) lgrid = want;
-        }
-        // (entries of 4 bytes for blocks > 4 KiB); up to 4 GiB: a nearly full device does without the lanes instead of failing the call
-        if (wsp.lane_tabs.reserve(lgrid * 64 * (size_t)kTabBytes * 2) != hipSuccess) {
-            (void)hipGetLastError();
-            lgrid = 0;
-        }
-        uint16_t *const lane_tabs = wsp.lane_tabs.as<uint16_t>();
-        if (lgrid) {
-        lanes_beside = lanes_concurrent;
-        uint32_t reserve = 0, reserve_wide = 0, lmin = lane_min;
-        if (lanes_beside) {
-            // The lanes' and the register-table parser's streams come from the HIGH-PRIORITY pool of hardware queues (CW_SIDE_PRIO=0: the normal one,
-            // =1: the lanes' only).  HIP multiplexes its streams onto four hardware queues per priority level, and kernels of different streams
-            // that land on one queue run one after the other.  A device-resident call has four streams and is not affected; the host pipeline has
-            // three slots with four streams each plus two for copies, and its timeline (rocprofv3 --kernel-trace) showed a chunk's two scalar-thread
-            // kernels starting the moment ITS OWN lanes kernel had ended, 108 ms late.  With the side streams in another pool a chunk's kernels
-            // no longer share a queue with each other: host path over the corpus 20.5-21.0 -> 24.0-24.3 GB/s (GPU_MAX_HW_QUEUES=8 on top: 24.7-24.9);
-            // the device-resident legs and the headline are unchanged (16 GiB corpus leg 44-48 -> 49.6).
-            if ((e = wsp.lanes.open(kn.side_prio != SidePrio::none ? SideStream::greatest : SideStream::normal)) != hipSuccess) return e;
-            // what the wavefront parser gets through while a lane parses its last block: 4 KiB text, 1 Mi blocks: 8 Ki..40 Ki 40-43 GB/s, 48 Ki 39.8;
-            // 256 Ki blocks: 16 Ki / 28 Ki / 40 Ki 37.4 / 39.0 / 41.0
-            // blocks > 4 KiB (round 3; corpus, 64 KiB, lanes alone -> lanes beside the other two, GB/s): two positions per iteration, 32 Ki blocks
-            // 29.4 -> 31.0 (reserve 24 Ki), 48 Ki 34.0 -> 40.7 (16-24 Ki), 64 Ki 37.2 -> 40.6 (32 Ki); one position: 128 Ki 44.9 -> 48.3 (32 Ki), 256 Ki 42.8 -> 46.7
-            reserve = kn.lanes_reserve ? (uint32_t)kn.lanes_reserve : (staged ? 32768u : kLaneShare);
-            if (!staged && !kn.lanes_reserve && reserve > nblocks / 3 * 2) reserve = (uint32_t)(nblocks / 3 * 2);
-            reserve_wide = kn.lanes_reserve ? (uint32_t)kn.lanes_reserve : kLaneShareWide;
-            if (lane_min > 1 && lmin < reserve + reserve / 4) lmin = reserve + reserve / 4; // (CW_LZ4_LANES=1 in the tests: no reserve)
-            if (lane_min == 1) reserve = reserve_wide = 0;
+    if (p.stop_after_scan) { note_kernels(0, describe(p).text); return hipSuccess; }
+    if (p.lanes.on) {
+        if (p.lanes.stream == Target::lanes_side) {
+            if ((e = wsp.lanes.open(pool(p.lanes_pool))) != hipSuccess) return e;
             if ((e = lanes_fork.emplace(wsp.lanes, stream).err) != hipSuccess) return e;
         }
-        hipStream_t ls = lanes_beside ? wsp.lanes.stream : stream;
-        const uint32_t no_max = 0xFFFFFFFFu;
-        const char *side_tag = lanes_beside ? " [side stream]" : "";
-#define CW_RING(K, LO, HI) do { \
-            const uint32_t lo_ = (LO), hi_ = (HI); \
-            hipLaunchKernelGGL(lz4_lanes_ring_kernel<K>, dim3((unsigned)lgrid), dim3(64), 0, ls, src, n, src_stride, dst, dst_stride, sizes, queue, counters, \
-                               lane_tabs, lo_, hi_ == no_max && lanes_ring < 0 ? reserve_wide : reserve, hi_); \
-            if (hi_ == no_max) note("cw::lz4_lanes_ring_kernel<" #K "> (queue >= %u)%s", lo_, side_tag); \
-            else note("cw::lz4_lanes_ring_kernel<" #K "> (queue in [%u, %u))%s", lo_, hi_, side_tag); } while (0)
-        if (n <= 4096)
-        {
-            hipLaunchKernelGGL(lz4_lanes_kernel<kLaneTagged>, dim3((unsigned)lgrid), dim3(64), 0, ls, src, n, src_stride, dst, dst_stride, sizes, queue,
-                               counters, lane_tabs, lmin, reserve);
-            note("cw::lz4_lanes_kernel<1> (queue >= %u)%s", lmin, side_tag);
-        }
-        else if (lanes_ring < 0) {
-            const uint32_t wide_from = lmin < kLaneWideBlocks ? kLaneWideBlocks : lmin;
-            hipLaunchKernelGGL(lz4_lanes_ring_auto_kernel, dim3((unsigned)lgrid), dim3(64), 0, ls, src, n, src_stride, dst, dst_stride, sizes, queue, counters,
-                               lane_tabs, lmin, reserve, wide_from, reserve_wide, lane_leave);
-            note("cw::lz4_lanes_ring_auto_kernel (queue >= %u: two positions per iteration, >= %u: one)%s", lmin, wide_from, side_tag);
-        }
-        else if (lanes_ring == 1) CW_RING(1, lmin, no_max);
-        else if (lanes_ring == 2) CW_RING(2, lmin, no_max);
-        else if (lanes_ring == 4) CW_RING(4, lmin, no_max);
-        else if (lanes_ring == 8) CW_RING(8, lmin, no_max);
-#undef CW_RING
-        else if (kn.lz4_lanes_fp) { // CW_LZ4_LANES_FP=0 (profiling knob): 16-bit table entries without fingerprints for blocks > 4 KiB
-            hipLaunchKernelGGL(lz4_lanes_kernel<kLaneFp>, dim3((unsigned)lgrid), dim3(64), 0, ls, src, n, src_stride, dst, dst_stride, sizes, queue,
-                               counters, lane_tabs, lmin, reserve);
-            note("cw::lz4_lanes_kernel<2> (queue >= %u)%s", lmin, side_tag);
-        } else {
-            hipLaunchKernelGGL(lz4_lanes_kernel<kLanePlain>, dim3((unsigned)lgrid), dim3(64), 0, ls, src, n, src_stride, dst, dst_stride, sizes, queue,
-                               counters, lane_tabs, lmin, reserve);
-            note("cw::lz4_lanes_kernel<0> (queue >= %u)%s", lmin, side_tag);
-        }
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        lanes_used = true;
-        }
-    }
-    // The register-table parser (lz4_vtab_kernel.hip): 16 more chains per CU than the LDS admits, no table traffic.  It runs BESIDE the
-    // wavefront parser on a second stream, both pulling from the scan's queue, whenever the lanes do not take the whole queue
-    // (text, 64 KiB blocks, wavefront parser alone -> both: 3,233 blocks 11.8 -> 15.7 GB/s, 8 Ki 13.3 -> 21.6, 16 Ki 24.5 against the
-    // lanes' 19.5; beside the lanes in their random-line regime it gains nothing -- they keep the memory system busy and its
-    // candidate fetches wait).  CW_LZ4_VTAB: 0 = off, 1 = on the caller's stream AHEAD of the wavefront parser (it takes the whole
-    // queue: tests), 2 = beside (default); CW_VTAB_MIN / CW_VTAB_MAX = queue lengths between which it runs (checked on the device),
-    // CW_VTAB_RESERVE = blocks it leaves to the others, CW_VTAB_WPC = its wavefronts per CU (at most 16), CW_VTAB_GEN = kernel generation.
-    const int vt_mode = kn.lz4_vtab.value_or(2);
-    // CW_LZ4_MODE=cut parses with the first-generation (write/read-back) kernel only (profiling knob)
-    const bool cut_only = kn.lz4_mode == Lz4Mode::cut;
-    bool vtab_beside = false;
-    if (vt_mode > 0 && !use_fp && !cut_only && n >= 64 && nblocks >= 64 && ((reinterpret_cast<uintptr_t>(src) | src_stride) & 3) == 0) {
-        // LDS-staged blocks: a small queue is the LDS-resident parser's (4 Ki blocks of 4 KiB: 19.4 GB/s alone against 14.5 with the register-table
-        // parser's 4,096 wavefronts taking a block each; 16 Ki blocks 23.8 -> 24.5, 32 Ki 25.1 -> 28.0, 51,728 25.6 -> 29.5)
-        const uint32_t vmin = kn.vtab_min ? (uint32_t)*kn.vtab_min : staged ? 12288u : 1u, vres = kn.vtab_reserve ? (uint32_t)*kn.vtab_reserve : 0u;
-        // lanes that take the whole queue (blocks > 4 KiB) start at lane_min queued blocks: the register-table parser stays below
-        const uint32_t vmax = kn.vtab_max ? (uint32_t)*kn.vtab_max : (lanes_used && !lanes_beside ? lane_min : 0xFFFFFFFFu);
-        const unsigned vwpc = kn.vtab_wpc ? (unsigned)kn.vtab_wpc : 16u;
-        hipStream_t vs = stream;
-        if (vt_mode == 2) {
-            if ((e = wsp.vtab.open(kn.side_prio == SidePrio::both ? SideStream::greatest : SideStream::normal)) != hipSuccess) return e;
-            if ((e = vtab_fork.emplace(wsp.vtab, stream).err) != hipSuccess) return e;
-            vs = wsp.vtab.stream;
-            vtab_beside = true;
-        }
-        const char *vname = nullptr;
-        const int gen = kn.vtab_gen.value_or(0);
-        if ((e = lz4_vtab_launch(src, n, src_stride, nblocks, dst, dst_stride, sizes, queue, counters, vmin, vmax, vres, vwpc, gen, vs, &vname)) != hipSuccess) return e;
-        if (vmax != 0xFFFFFFFFu) note("%s (queue < %u)%s", vname, vmax, vtab_beside ? " [side stream]" : "");
-        else note("%s%s", vname, vtab_beside ? " [side stream]" : "");
-    }
-    const size_t pwpc = kn.parse_wpc ? (size_t)kn.parse_wpc : 10; // CW_PARSE_WPC: parse wavefronts per CU (profiling knob; default: all the LDS admits)
-    const size_t want = 256 * (per_cu > pwpc ? pwpc : per_cu);
-    const size_t grid = nblocks < want ? nblocks : want;
-    // CW_LZ_FORCE_REDO=1: the exchange kernel hands every block back, as if its lane-order check had failed (test knob)
-    const uint32_t force_redo = kn.force_redo ? 1u : 0u;
-    if (!cut_only) {
-        // blocks read from global memory: the scalar-thread parser with its table in LDS (lz4_vtab3_kernel<true>) in the place of the round-2
-        // wavefront parser; CW_LZ4_LTAB=0 keeps the latter (and the forced-redo test knob and unaligned sources need it)
-        const bool use_ltab = !staged && !use_fp && !force_redo && n >= 64 && ((reinterpret_cast<uintptr_t>(src) | src_stride) & 3) == 0 &&
-                              (kn.lz4_ltab ? *kn.lz4_ltab != 0 : kLtabDefault);
-        if (use_ltab) {
-            note("cw::lz4_vtab3_kernel<true>");
-            if ((e = lz4_ltab_launch(src, n, src_stride, nblocks, dst, dst_stride, sizes, queue, counters, (unsigned)pwpc, stream)) != hipSuccess) return e;
-        } else {
-        note(staged ? "cw::lz4_parse_kernel<true>" : use_fp ? "cw::lz4_parse_fp_kernel<%d>" : "cw::lz4_parse_kernel<false>", headw == 32 || headw == 8 ? headw : 16);
-        if (staged)
-            hipLaunchKernelGGL(lz4_parse_kernel<true>, dim3((unsigned)grid), dim3(64), lds, stream, src, n, src_stride, nblocks, dst,
-                               dst_stride, sizes, queue, counters, queue2, force_redo);
-        else if (use_fp && headw == 32)
-            hipLaunchKernelGGL(lz4_parse_fp_kernel<32>, dim3((unsigned)grid), dim3(64), lds, stream, src, n, src_stride, nblocks, dst,
-                               dst_stride, sizes, queue, counters, queue2, force_redo);
-        else if (use_fp && headw == 8)
-            hipLaunchKernelGGL(lz4_parse_fp_kernel<8>, dim3((unsigned)grid), dim3(64), lds, stream, src, n, src_stride, nblocks, dst,
-                               dst_stride, sizes, queue, counters, queue2, force_redo);
-        else if (use_fp)
-            hipLaunchKernelGGL(lz4_parse_fp_kernel<16>, dim3((unsigned)grid), dim3(64), lds, stream, src, n, src_stride, nblocks, dst,
-                               dst_stride, sizes, queue, counters, queue2, force_redo);
+        const dim3 lgrid(p.lanes.grid);
+        if (p.lanes_form == Lz4Plan::LanesForm::ring_auto)
+            hipLaunchKernelGGL(lz4_lanes_ring_auto_kernel, lgrid, dim3(64), 0, on(p.lanes), src, n, src_stride, dst, dst_stride, sizes, queue, counters,
+                               lane_tabs, p.lmin, p.reserve, p.wide_from, p.reserve_wide, p.lane_leave);
+        else if (p.lanes_form == Lz4Plan::LanesForm::ring)
+            hipLaunchKernelGGL(kernel_row(kRingKernels, p.ring_kernel).fn, lgrid, dim3(64), 0, on(p.lanes), src, n, src_stride, dst, dst_stride, sizes, queue,
+                               counters, lane_tabs, p.lmin, p.reserve, kNoMax);
         else
-            hipLaunchKernelGGL(lz4_parse_kernel<false>, dim3((unsigned)grid), dim3(64), lds, stream, src, n, src_stride, nblocks, dst,
-                               dst_stride, sizes, queue, counters, queue2, force_redo);
+            hipLaunchKernelGGL(kernel_row(kLanesKernels, p.lanes_kernel).fn, lgrid, dim3(64), 0, on(p.lanes), src, n, src_stride, dst, dst_stride, sizes, queue,
+                               counters, lane_tabs, p.lmin, p.reserve);
         if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    if (p.vtab.on) {
+        if (p.vtab.stream == Target::vtab_side) {
+            if ((e = wsp.vtab.open(pool(p.vtab_pool))) != hipSuccess) return e;
+            if ((e = vtab_fork.emplace(wsp.vtab, stream).err) != hipSuccess) return e;
         }
+        if ((e = lz4_vtab_launch(p.vtab_kernel, p.vtab.grid, p.vtab.lds, on(p.vtab), src, n, src_stride, dst, dst_stride, sizes, queue, counters, p.vmin, p.vmax,
+                                 p.vres)) != hipSuccess) return e;
+    }
+    // the scalar-thread parser with its table in LDS takes what is left of the queue
+    if (p.ltab.on && (e = lz4_vtab_launch(Lz4Vtab::lds_table, p.ltab.grid, p.ltab.lds, stream, src, n, src_stride, dst, dst_stride, sizes, queue, counters, 0u,
+                                          kNoMax, 0u)) != hipSuccess) return e;
+    if (p.parse.on) {
+        hipLaunchKernelGGL(kernel_row(kParseKernels, p.parse_kernel).fn, dim3(p.parse.grid), dim3(64), p.parse.lds, stream, src, n, src_stride, nblocks, dst,
+                           dst_stride, sizes, queue, counters, queue2, p.force_redo);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     if (vtab_fork && (e = vtab_fork->join()) != hipSuccess) return e;
     if (lanes_fork && (e = lanes_fork->join()) != hipSuccess) return e; // the redo pass and the caller's later work wait for the lanes too
-    if (cut_only) note(staged ? "cw::lz4_blocks_kernel<true>" : "cw::lz4_blocks_kernel<false>");
-    note_kernels(0, launched); // (the redo pass below finds an empty list unless the LDS ever applied an exchange's lanes out of order)
-    // blocks the exchange-based parser handed back (none, unless the LDS ever applies lanes out of order)
-    const uint32_t *q = cut_only ? queue : queue2;
-    uint32_t *c = cut_only ? counters : counters + 4;
-    if (staged)
-        hipLaunchKernelGGL(lz4_blocks_kernel<true>, dim3((unsigned)grid), dim3(64), lds, stream, src, n, src_stride, nblocks, dst,
-                           dst_stride, sizes, q, c);
-    else
-        hipLaunchKernelGGL(lz4_blocks_kernel<false>, dim3((unsigned)grid), dim3(64), lds, stream, src, n, src_stride, nblocks, dst,
-                           dst_stride, sizes, q, c);
-    return hipGetLastError();
+    // blocks the exchange-based parser handed back (none, unless the LDS ever applies lanes out of order); CW_LZ4_MODE=cut: the scan's queue
+    hipLaunchKernelGGL(kernel_row(kBlocksKernels, p.redo_kernel).fn, dim3(p.redo.grid), dim3(64), p.redo.lds, stream, src, n, src_stride, nblocks, dst,
+                       dst_stride, sizes, p.cut_only ? queue : queue2, p.cut_only ? counters : counters + 4);
+    e = hipGetLastError();
+    note_kernels(0, describe(p).text);
+    return e;
 }
 
 } // namespace cw

@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include "cw_device.h"
+#include "launch_plan.h"
 #include "lz_device.h"
 #include "scalar_thread.h"
 
@@ -739,39 +740,22 @@ lz4_vtab3_kernel(const uint8_t *__restrict__ src, uint32_t n, size_t src_stride,
     }
 }
 
-// grid: as many single-wavefront workgroups as the register file admits (128 VGPRs -> 4 per SIMD, 16 per CU), at most one per queued block
-hipError_t lz4_vtab_launch(const uint8_t *src, uint32_t n, size_t src_stride, size_t nblocks, uint8_t *dst, size_t dst_stride, uint32_t *sizes,
-                           const uint32_t *queue, uint32_t *counters, uint32_t min_queued, uint32_t max_queued, uint32_t reserve,
-                           unsigned waves_per_cu, int gen, hipStream_t stream, const char **kernel_name)
-{
-    // gen (CW_VTAB_GEN): 2 = batches of four items (vector loads), 3 = the scalar chain with the VALU's help.  Default by measurement (GB/s alone,
-    // 16 wavefronts per CU; (1) = the all-scalar first form, removed): text, 64 KiB blocks, 8 Ki blocks 18.4 (1) / 13.7 (2) / 20.8 (3),
-    // 3,233 blocks 13.6 / 11.3 / 17.1; corpus, 4 KiB blocks 15.4-16.0 (1) against 17.8-17.9 (2)
-    if (gen != 2 && gen != 3) gen = n <= 4096 ? 2 : 3;
-    if ((reinterpret_cast<uintptr_t>(src) | src_stride) & 3) return hipErrorInvalidValue; // the scalar loads are dword loads
-    size_t grid = 256 * (size_t)(waves_per_cu ? waves_per_cu : 16);
-    if (grid > nblocks) grid = nblocks;
-    if (grid == 0) return hipSuccess;
-    if (kernel_name) *kernel_name = gen == 3 ? "cw::lz4_vtab3_kernel<false>" : "cw::lz4_vtab2_kernel";
-    if (gen == 3)
-        hipLaunchKernelGGL(lz4_vtab3_kernel<false>, dim3((unsigned)grid), dim3(64), 0, stream, src, n, src_stride, dst, dst_stride, sizes, queue, counters,
-                           min_queued, max_queued, reserve);
-    else
-        hipLaunchKernelGGL(lz4_vtab2_kernel, dim3((unsigned)grid), dim3(64), 0, stream, src, n, src_stride, dst, dst_stride, sizes, queue, counters,
-                           min_queued, max_queued, reserve);
-    return hipGetLastError();
-}
+// the family (launch_plan.h): member, name as rocprofv3 prints it, kernel.  lds_table is the same scalar-thread parser with its table in LDS.
+static const KernelRow<Lz4Vtab, decltype(lz4_vtab2_kernel)> kVtabKernels[] = {
+    {Lz4Vtab::gen2, "cw::lz4_vtab2_kernel", lz4_vtab2_kernel},
+    {Lz4Vtab::gen3, "cw::lz4_vtab3_kernel<false>", lz4_vtab3_kernel<false>},
+    {Lz4Vtab::lds_table, "cw::lz4_vtab3_kernel<true>", lz4_vtab3_kernel<true>},
+};
+const char *kernel_name(Lz4Vtab k) { return kernel_row(kVtabKernels, k).name; }
 
-// the scalar-thread parser with its table in LDS: ten single-wavefront workgroups per CU at most (16 KiB of LDS each)
-hipError_t lz4_ltab_launch(const uint8_t *src, uint32_t n, size_t src_stride, size_t nblocks, uint8_t *dst, size_t dst_stride, uint32_t *sizes,
-                           const uint32_t *queue, uint32_t *counters, unsigned waves_per_cu, hipStream_t stream)
+hipError_t lz4_vtab_launch(Lz4Vtab kernel, uint32_t grid, uint32_t lds, hipStream_t stream, const uint8_t *src, uint32_t n, size_t src_stride, uint8_t *dst,
+                           size_t dst_stride, uint32_t *sizes, const uint32_t *queue, uint32_t *counters, uint32_t min_queued, uint32_t max_queued,
+                           uint32_t reserve)
 {
-    if ((reinterpret_cast<uintptr_t>(src) | src_stride) & 3) return hipErrorInvalidValue;
-    size_t grid = 256 * (size_t)(waves_per_cu && waves_per_cu < 10 ? waves_per_cu : 10);
-    if (grid > nblocks) grid = nblocks;
+    if ((reinterpret_cast<uintptr_t>(src) | src_stride) & 3) return hipErrorInvalidValue; // the scalar loads are dword loads
     if (grid == 0) return hipSuccess;
-    hipLaunchKernelGGL(lz4_vtab3_kernel<true>, dim3((unsigned)grid), dim3(64), (1u << 13) * 2u, stream, src, n, src_stride, dst, dst_stride, sizes, queue,
-                       counters, 0u, 0xFFFFFFFFu, 0u);
+    hipLaunchKernelGGL(kernel_row(kVtabKernels, kernel).fn, dim3(grid), dim3(64), lds, stream, src, n, src_stride, dst, dst_stride, sizes, queue, counters,
+                       min_queued, max_queued, reserve);
     return hipGetLastError();
 }
 

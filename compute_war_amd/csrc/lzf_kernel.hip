@@ -35,8 +35,11 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <optional>
+
 #include "cw_device.h"
 #include "lane_codec.h"
+#include "launch_plan.h"
 #include "lz_device.h"
 #include "scalar_thread.h"
 #include "stream_scratch.h"
@@ -47,8 +50,8 @@ using namespace lane; // kMaxOff / kMaxRef / kMaxLit, lzf_slot and the lane pars
 
 namespace {
 
-constexpr uint32_t kLzfSlots = 1u << 16, kLzfTabBytes = kLzfSlots * 2;
-constexpr uint32_t kInLdsMax = 16384; // blocks up to this size are staged in LDS next to the table
+constexpr uint32_t kLzfSlots = kLzfTabBytes / 2;
+// (kLzfTabBytes, kInLdsMax, kChainMax, kShareSpinCap: launch_plan.h, shared with the launch policy)
 constexpr uint32_t kRedo = 0xFFFFFFFFu; // sizes[] marker: exchange kernel -> write/read-back kernel
 
 // Small blocks, large batches: the lane-per-block parser runs BESIDE the link/chain rounds (second stream).  The rounds walk
@@ -73,7 +76,6 @@ constexpr uint32_t kRedo = 0xFFFFFFFFu; // sizes[] marker: exchange kernel -> wr
 // [99] failed
 constexpr uint32_t kCtrWord = 32, kCtrPoor = 64, kCtrFine = 65, kCtrHanded = 66, kCtrPublished = 96, kCtrTicket = 98, kCtrFailed = 99, kCtrBytes = 512;
 constexpr uint32_t kShareGaveUp = 0xFFFFFFFFu; // share_round_taken: the published number never came (see there)
-constexpr uint32_t kShareSpinCap = 1u << 20;   // polls of ~64 cycles: tens of milliseconds, against the microsecond a claim takes
 struct LaneShare { uint32_t *ctr; size_t round_first, total; uint32_t seq, spin_cap; };
 __device__ __forceinline__ unsigned long long *share_word(uint32_t *ctr) { return reinterpret_cast<unsigned long long *>(ctr + kCtrWord); }
 __device__ __forceinline__ unsigned long long *share_published(uint32_t *ctr) { return reinterpret_cast<unsigned long long *>(ctr + kCtrPublished); }
@@ -478,7 +480,7 @@ lzf_parse_kernel(const uint8_t *__restrict__ src, uint32_t n, size_t src_stride,
 // The lane-order check sits in lzf_links_kernel (a link >= its own position); a failing block is marked and parsed
 // by lzf_blocks_kernel like everywhere else.
 // ---------------------------------------------------------------------------------------------------
-constexpr uint32_t kChainMax = 16384, kChainHead = 8, kSkipFlag = 0x8000u;
+constexpr uint32_t kChainHead = 8, kSkipFlag = 0x8000u;
 
 // 3 bytes at pos (as the low 24 bits) from global memory without reading past the block
 __device__ __forceinline__ uint32_t load3(const uint8_t *g, uint32_t n, uint32_t pos, bool ok)
@@ -1099,19 +1101,7 @@ lzf_sthread_kernel(const uint8_t *__restrict__ src, uint32_t n, size_t src_strid
 // shared with the parser over content-defined chunks) with its 65,536 x u16 table in global memory (128 KiB per lane, zeroed by
 // the lane when it takes a block).  This file supplies where the blocks come from and the table's entry formats.
 // ---------------------------------------------------------------------------------------------------
-// A lane needs ~66 ms for a 64 KiB block of text however few lanes there are, the link/chain kernels run at 8.5 GB/s: the lanes win
-// from ~9 Ki compressible blocks on (text, 64 KiB, 12 Ki / 16 Ki / 20 Ki / 24 Ki blocks: 13.2 / 16.3 / 13.6 / 15.2 GB/s against 8.5; the dip
-// is the second wavefront on some CUs' SIMDs).  A batch that is a third noise or more goes back to the chain kernels anyway.
-constexpr uint32_t kLzfLaneMinBlocks = 12288;
-constexpr uint32_t kLzfLaneMinSmall = 28672;  // blocks <= 4 KiB: lanes beside the rounds from 28 Ki blocks on (text, 32 Ki / 40 Ki / 64 Ki blocks: 16.1 / 19.5 / 21 against 13.5 GB/s)
-constexpr size_t kLzfBesideRound = 16384;     // ... in rounds of 16 Ki blocks, the last 16 Ki unclaimed blocks left to the rounds.  4 KiB blocks, text /
-                                              // 50 % noise / noise, GB/s -- 1 Mi blocks: rounds of 8 Ki 29.8 / 24.7 / 52.9, 16 Ki 33.1 / 29.0 / 57.7,
-                                              // 32 Ki 32.6 / 30.9 / 59.2; 96 Ki blocks: 25.6 / 36.3 / 50.5, 26.2 / 39.3 / 53.6, 23.1 / 36.4 / 55.0
-// blocks > 16 KiB: lanes beside the scalar-thread rounds from 52 Ki blocks on; from 96 Ki blocks on rounds of 8 Ki blocks and as many left to the rounds, below
-// (every lane gets one block; the rounds get what they manage in that time) rounds of 4 Ki and 12 Ki blocks left.  Corpus, 64 KiB, lanes alone -> beside:
-// 48 Ki blocks 27.0 -> 26.3-27.6 (not used), 56 Ki 27.0 -> 29.1, 64 Ki 27.3 -> 29.0, 80 Ki 26.4 -> 34.8, 128 Ki 27.3 -> 31.0, 256 Ki 29.4 -> 35.2 GB/s
-constexpr size_t kLzfBigBesideMin = 53248, kLzfBigBesideWide = 98304, kLzfBigBesideRound = 8192, kLzfBigBesideRoundMid = 4096, kLzfBigBesideReserveMid = 12288;
-constexpr uint32_t kLzfBesideReserve = 16384, kLzfBesideReserveFew = 8192; // blocks left to the rounds; below 48 Ki blocks (32 Ki blocks: 16.1 against 13.2 GB/s with 16 Ki)
+// (when the lanes run, alone or beside the rounds, and the rounds' sizes: lzf_plan in launch_plan.cpp, with the measurements)
 
 // 4 bytes at ip (ip + 2 < n): the last position of a block is read one byte early and shifted (no read past the block)
 __device__ __forceinline__ uint32_t lzf_rd(const uint8_t *g, uint32_t ip, uint32_t n)
@@ -1241,191 +1231,128 @@ struct LinkSpace {
 StreamScratch<LinkSpace> link_spaces;
 }
 
+// ---- the kernel families of the launch (launch_plan.h): member, name as rocprofv3 prints it, kernel ------------------------------
+namespace {
+const KernelRow<LzfLanes, decltype(lzf_lanes_kernel<true>)> kLzfLanesKernels[] = {
+    {LzfLanes::plain, "cw::lzf_lanes_kernel<false>", lzf_lanes_kernel<false>},
+    {LzfLanes::tagged, "cw::lzf_lanes_kernel<true>", lzf_lanes_kernel<true>},
+};
+const KernelRow<LzfChain, decltype(lzf_sthread_kernel)> kLzfChainKernels[] = {
+    {LzfChain::small, "cw::lzf_chain_kernel<false>", lzf_chain_kernel<false>},
+    {LzfChain::big, "cw::lzf_chain_kernel<true>", lzf_chain_kernel<true>},
+    {LzfChain::sthread, "cw::lzf_sthread_kernel", lzf_sthread_kernel},
+};
+const KernelRow<LzfParse, decltype(lzf_parse_kernel<true>)> kLzfParseKernels[] = {
+    {LzfParse::global, "cw::lzf_parse_kernel<false>", lzf_parse_kernel<false>},
+    {LzfParse::staged, "cw::lzf_parse_kernel<true>", lzf_parse_kernel<true>},
+};
+
+// (dynamic-LDS limits: stream_scratch.h)
+hipError_t lzf_set_table_attributes()
+{
+    static std::atomic<bool> done{false};
+    return set_lds_limits_once(done, {{reinterpret_cast<const void *>(lzf_blocks_kernel), kLzfTabBytes + kInLdsMax + 16},
+                                 {reinterpret_cast<const void *>(lzf_parse_kernel<true>), kLzfTabBytes + kInLdsMax + 16},
+                                 {reinterpret_cast<const void *>(lzf_parse_kernel<false>), kLzfTabBytes}});
+}
+hipError_t lzf_set_chain_attributes()
+{
+    static std::atomic<bool> done{false};
+    return set_lds_limits_once(done, {{reinterpret_cast<const void *>(lzf_links_kernel), kLzfTabBytes + kChainMax + 48},
+                                 {reinterpret_cast<const void *>(lzf_chain_kernel<false>), 3 * kChainMax + 256}});
+}
+} // namespace
+const char *kernel_name(LzfLanes k) { return kernel_row(kLzfLanesKernels, k).name; }
+const char *kernel_name(LzfChain k) { return kernel_row(kLzfChainKernels, k).name; }
+const char *kernel_name(LzfParse k) { return kernel_row(kLzfParseKernels, k).name; }
+
+// the end of every call: the table parser where the plan has one, the final pass over what is still marked for it, the description
+static hipError_t lzf_enqueue_tail(const LzfPlan &p, const uint32_t *gave_up, const uint8_t *src, uint32_t n, size_t src_stride, size_t nblocks, uint8_t *dst,
+                                   size_t dst_stride, uint32_t *sizes, hipStream_t stream)
+{
+    if (p.parse.on) {
+        hipLaunchKernelGGL(kernel_row(kLzfParseKernels, p.parse_kernel).fn, dim3(p.parse.grid), dim3(64), p.parse.lds, stream, src, n, src_stride, nblocks,
+                           dst, dst_stride, sizes, p.force_redo);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(lzf_blocks_kernel, dim3(p.blocks.grid), dim3(64), p.blocks.lds, stream, src, n, src_stride, nblocks, dst,
+                       dst_stride, sizes, p.in_lds, p.blocks_pass, gave_up);
+    note_kernels(0, describe(p).text);
+    return hipGetLastError();
+}
+
+// plan (launch_plan.cpp: every decision), reserve, enqueue
 hipError_t lzf_launch(const uint8_t *src, size_t block_bytes, size_t src_stride, size_t nblocks, uint8_t *dst,
                       size_t dst_stride, uint32_t *sizes, hipStream_t stream)
 {
-    // what this call launches, noted where it is launched (cw_profile_kernels); names as rocprofv3 prints them
-    char launched[320] = "";
-    auto note = [&](const char *name) {
-        if (strstr(launched, name)) return; // (rounds repeat their kernels)
-        const size_t used = strlen(launched);
-        if (used + strlen(name) + 4 < sizeof launched) { if (used) strcat(launched, " + "); strcat(launched, name); }
-    };
     if (nblocks == 0) return hipSuccess;
-    if (block_bytes == 0 || block_bytes > 65536) return hipErrorInvalidValue;
+    if (!lzf_call_valid(block_bytes, nblocks)) return hipErrorInvalidValue;
     const uint32_t n = (uint32_t)block_bytes;
-    const uint32_t in_lds = n <= kInLdsMax ? 1u : 0u;
-    const uint32_t lds = kLzfTabBytes + (in_lds ? ((n + 15u) & ~15u) + 16u : 0u); // 16 bytes of slack for dword reads
-    static bool attr_set = false; // benign race: idempotent
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(lzf_blocks_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, kLzfTabBytes + kInLdsMax + 16);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(lzf_parse_kernel<true>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, kLzfTabBytes + kInLdsMax + 16);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(lzf_parse_kernel<false>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, kLzfTabBytes);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
-    const size_t grid = nblocks < 256 ? nblocks : 256; // the 128 KiB table admits one workgroup per CU
     const Knobs kn = knobs();
-    // CW_LZF_MODE=cut: write/read-back kernel only; =table: exchange kernel with the 128 KiB table also for small blocks
-    const bool cut_only = kn.lzf_mode == LzfMode::cut, table_only = kn.lzf_mode == LzfMode::table;
-    const uint32_t force_redo = kn.force_redo ? 1u : 0u; // CW_LZ_FORCE_REDO: test knob, see lz4_kernel.hip
-    if (!cut_only && !table_only && n >= 16) {
-        // links for a round of blocks, then the chain parser over that round
-        // CW_LZF_LDS_MAX (profiling knob): largest block parsed from LDS-resident links
-        // measured (text): 4 KiB 13.2 (LDS) vs 12.4 GB/s (global links); 8 KiB 7.2 vs 10.6; 16 KiB 3.7 vs 9.3 -- blocks per CU win
-        const uint32_t lds_max = kn.lzf_lds_max ? (uint32_t)kn.lzf_lds_max : 4096u;
-        const bool big = n > (lds_max < kChainMax ? lds_max : kChainMax);
-        const uint32_t n2 = (n + 63u) & ~63u;
-        const size_t ws_bytes = big ? (size_t)1 << 30 : (size_t)256 << 20; // links per round
-        // (blocks of 4-8 KiB: the chain kernels win up to ~18 Ki blocks -- text, 8 KiB, 16 Ki blocks 11.0 against 10.6 GB/s, 24 Ki 11.3 / 13.0)
-        const size_t lane_min = kn.lzf_lanes ? (size_t)*kn.lzf_lanes : (big ? (n > 8192 ? kLzfLaneMinBlocks : 18432u) : kLzfLaneMinSmall);
-        bool use_lanes = lane_min && nblocks >= lane_min;
-        // blocks > 4 KiB: the scalar-thread form of the chain parser (CW_LZF_STHREAD=0: the wavefront-wide one); needs dword-aligned blocks
-        const size_t st_wpc = kn.lzf_st_wpc ? (size_t)kn.lzf_st_wpc : 20;
-        const bool sthread = big && kn.lzf_sthread && ((reinterpret_cast<uintptr_t>(src) | src_stride) & 3) == 0;
-        // lanes BESIDE the rounds: blocks <= 4 KiB always; larger blocks from kLzfBigBesideMin blocks on, and only with the scalar-thread
-        // parser in the rounds (with the wavefront-wide chain kernel in the rounds: 256 Ki blocks 27.7 -> 27.7 GB/s)
-        const bool big_beside = sthread && n > 16384 && nblocks >= kLzfBigBesideMin;
-        bool beside = use_lanes && kn.lanes_concurrent.value_or(!big || big_beside);
-        // CW_LZF_ROUND (test knob): blocks per round (many rounds on small data)
-        const size_t chunk_cap = kn.lzf_round ? (size_t)kn.lzf_round : beside ? (big ? (nblocks < kLzfBigBesideWide ? kLzfBigBesideRoundMid : kLzfBigBesideRound) : kLzfBesideRound) : ws_bytes / (2 * (size_t)n2);
-        const size_t chunk_max = chunk_cap < ws_bytes / (2 * (size_t)n2) ? chunk_cap : ws_bytes / (2 * (size_t)n2);
-        const size_t chunk = nblocks < chunk_max ? nblocks : chunk_max;
-        auto &w = link_spaces.at(stream);
-        LaunchLock sequence(w.launch); // the link array and the counter are shared by the launches below
-        std::optional<SideStream::Fork> lanes_fork; // (a return before the join below still joins)
-        // Large batches: the lane-per-block parser (CW_LZF_LANES=0 off, =N threshold, 1 = every block, in the tests; CW_LANES_WPC
-        // wavefronts per CU).  Blocks > 4 KiB from kLzfLaneMinBlocks on: the lanes take the whole batch.  Blocks that fit the
-        // LDS-resident chain parser, from kLzfLaneMinSmall on: the lanes run BESIDE the link/chain rounds on a second stream,
-        // pulling from the top of the batch while the rounds climb from the bottom (LaneShare) -- one side is bound by LDS
-        // capacity and chain latency, the other by random memory accesses.
-        const size_t want_reserve = kn.lanes_reserve ? (size_t)kn.lanes_reserve : big ? (nblocks < kLzfBigBesideWide ? kLzfBigBesideReserveMid : kLzfBigBesideRound) : nblocks < 49152 ? kLzfBesideReserveFew : kLzfBesideReserve;
-        uint32_t lane_reserve = 0;
-        const size_t round_max = ws_bytes / (2 * (size_t)n2); // blocks per round that the link workspace admits
-        const size_t hb_chunk = nblocks < round_max ? nblocks : round_max; // rounds of the hand-back pass
-        hipError_t e;
-        const size_t need = use_lanes && hb_chunk > chunk ? hb_chunk : chunk;
-        if ((e = w.links.reserve(need * n2 * sizeof(uint16_t))) != hipSuccess) return e;
-        if ((e = w.counter.reserve(kCtrBytes)) != hipSuccess) return e;
-        uint16_t *const links = w.links.as<uint16_t>();
-        uint32_t *const counter = w.counter.as<uint32_t>();
-        size_t lgrid = 0; // workgroups of the lane-per-block kernel
-        if (use_lanes) {
-            const size_t lwpc = kn.lanes_wpc ? (size_t)kn.lanes_wpc : 4;
-            lgrid = (nblocks + 63) / 64;
-            if (lgrid > 256 * lwpc) lgrid = 256 * lwpc;
-            if (beside && lgrid * 64 + want_reserve > nblocks) lgrid = nblocks > want_reserve + 64 ? (nblocks - want_reserve) / 64 : 1; // (no lane without a block)
-            // up to 8 GiB: a nearly full device does without the lanes instead of failing the call
-            if (w.lane_tabs.reserve(lgrid * 64 * (size_t)kLzfTabBytes) != hipSuccess) {
-                (void)hipGetLastError();
-                use_lanes = beside = false;
-            }
+    const CodecCall call = codec_call(src, block_bytes, src_stride, nblocks, dst, dst_stride);
+    LzfPlan p = lzf_plan(call, kn);
+    hipError_t e = lzf_set_table_attributes();
+    if (e != hipSuccess) return e;
+    if (p.path != LzfPlan::Path::rounds) return lzf_enqueue_tail(p, nullptr, src, n, src_stride, nblocks, dst, dst_stride, sizes, stream);
+    auto &w = link_spaces.at(stream);
+    LaunchLock sequence(w.launch); // the link array and the counter are shared by the launches below
+    std::optional<SideStream::Fork> lanes_fork; // (a return before the join below still joins)
+    if ((e = w.links.reserve(p.links_bytes)) != hipSuccess) return e;
+    if ((e = w.counter.reserve(kCtrBytes)) != hipSuccess) return e;
+    // a nearly full device does without the lanes instead of failing the call: the rounds stay as they were sized
+    if (p.lanes.on && w.lane_tabs.reserve(p.lane_tab_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        p = lzf_plan(call, kn, false);
+    }
+    uint16_t *const links = w.links.as<uint16_t>();
+    uint32_t *const counter = w.counter.as<uint32_t>();
+    if (p.lanes.on) {
+        if ((e = w.handback.reserve(p.handback_bytes)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(counter, 0, kCtrBytes, stream)) != hipSuccess) return e;
+        hipStream_t lstream = stream;
+        if (p.lanes.stream == Target::lanes_side) {
+            if ((e = w.lanes.open(p.lanes_pool == SidePool::greatest ? SideStream::greatest : SideStream::normal)) != hipSuccess) return e;
+            if ((e = lanes_fork.emplace(w.lanes, stream).err) != hipSuccess) return e;
+            lstream = w.lanes.stream;
         }
-        if (use_lanes) {
-            if ((e = w.handback.reserve(nblocks * sizeof(uint32_t))) != hipSuccess) return e; // a block is handed back once at most
-            if ((e = hipMemsetAsync(counter, 0, kCtrBytes, stream)) != hipSuccess) return e;
-            hipStream_t lstream = stream;
-            if (beside) {
-                if ((e = w.lanes.open(SideStream::normal)) != hipSuccess) return e;
-                lane_reserve = (uint32_t)want_reserve;
-                if (lane_reserve < 1) lane_reserve = 1; // (0 means "on their own" to the kernel; the protocol itself needs no reserve)
-                if ((e = lanes_fork.emplace(w.lanes, stream).err) != hipSuccess) return e;
-                lstream = w.lanes.stream;
-            }
-            if (n <= 4096)
-                { note(beside ? "cw::lzf_lanes_kernel<true> [side stream]" : "cw::lzf_lanes_kernel<true>");
-                hipLaunchKernelGGL(lzf_lanes_kernel<true>, dim3((unsigned)lgrid), dim3(64), 0, lstream, src, n, src_stride, nblocks, dst, dst_stride,
-                                   sizes, w.lane_tabs.as<uint16_t>(), counter, lane_reserve, w.handback.as<uint32_t>()); }
-            else
-                { note(beside ? "cw::lzf_lanes_kernel<false> [side stream]" : "cw::lzf_lanes_kernel<false>");
-                hipLaunchKernelGGL(lzf_lanes_kernel<false>, dim3((unsigned)lgrid), dim3(64), 0, lstream, src, n, src_stride, nblocks, dst, dst_stride,
-                                   sizes, w.lane_tabs.as<uint16_t>(), counter, lane_reserve, w.handback.as<uint32_t>()); }
-            if ((e = hipGetLastError()) != hipSuccess) return e;
-        }
-        static bool chain_attr = false;
-        if (!chain_attr) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(lzf_links_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, kLzfTabBytes + kChainMax + 48);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(lzf_chain_kernel<false>),
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, 3 * kChainMax + 256);
-            if (e != hipSuccess) return e;
-            chain_attr = true;
-        }
-        const uint32_t links_lds = kLzfTabBytes + ((big ? kChainMax + 16 : n) + 15u) / 16u * 16u + 32u;
-        const uint32_t chain_lds = big ? n2 / 8 + 16u : 2 * n2 + ((n + 15u) & ~15u) + 16u;
-        size_t per_cu = (160u * 1024u) / (chain_lds + 64);
-        if (per_cu > (big ? 20u : 16u)) per_cu = big ? 20 : 16;
-        // one round of the link + chain kernels: blocks [first, first + nb) of the batch, or entries [first, first + nb) of the
-        // hand-back list (as far as the lanes filled it: the kernels read its length on the device and return at once beyond it)
-        // CW_LZF_SHARE_GIVE_UP (test knob): every workgroup but a round's claimant gives up at once
-        const uint32_t spin_cap = kn.lzf_share_give_up ? 0u : kShareSpinCap;
-        auto round = [&](size_t first, size_t nb, bool listed) -> hipError_t {
-            hipError_t r = hipMemsetAsync(counter, 0, sizeof(uint32_t), stream);
-            if (r != hipSuccess) return r;
-            const LaneShare share = {beside && !listed ? counter : nullptr, first, nblocks, (uint32_t)(first / chunk + 1), spin_cap};
-            const BlockList list = {listed ? w.handback.as<uint32_t>() : nullptr, listed ? counter + kCtrHanded : nullptr, (uint32_t)first};
-            const size_t off = listed ? 0 : first; // listed blocks are addressed through the list, from the batch's base
-            note(listed ? "cw::lzf_links_kernel (handed-back blocks)" : "cw::lzf_links_kernel");
-            note(sthread ? "cw::lzf_sthread_kernel" : big ? "cw::lzf_chain_kernel<true>" : "cw::lzf_chain_kernel<false>");
-            hipLaunchKernelGGL(lzf_links_kernel, dim3((unsigned)(nb < 256 ? nb : 256)), dim3(64), links_lds, stream, src + off * src_stride, n,
-                               src_stride, nb, links, n2, sizes + off, force_redo, share, list);
-            size_t cgrid = nb < 256 * per_cu ? nb : 256 * per_cu;
-            if (sthread) { // (n2 / 8 bytes of LDS per workgroup: 20 per CU at 64 KiB; smaller blocks: as many wavefronts as measured to pay)
-                const size_t st_cu = (160u * 1024u) / (n2 / 8) < st_wpc ? (160u * 1024u) / (n2 / 8) : st_wpc;
-                cgrid = nb < 256 * st_cu ? nb : 256 * st_cu;
-            }
-            if (sthread)
-                hipLaunchKernelGGL(lzf_sthread_kernel, dim3((unsigned)cgrid), dim3(64), n2 / 8, stream, src + off * src_stride, n, src_stride, nb,
-                                   dst + off * dst_stride, dst_stride, sizes + off, links, n2, counter, share, list);
-            else if (big)
-                hipLaunchKernelGGL(lzf_chain_kernel<true>, dim3((unsigned)cgrid), dim3(64), chain_lds, stream, src + off * src_stride, n, src_stride,
-                                   nb, dst + off * dst_stride, dst_stride, sizes + off, links, n2, counter, share, list);
-            else
-                hipLaunchKernelGGL(lzf_chain_kernel<false>, dim3((unsigned)cgrid), dim3(64), chain_lds, stream, src + off * src_stride, n, src_stride,
-                                   nb, dst + off * dst_stride, dst_stride, sizes + off, links, n2, counter, share, list);
-            return hipGetLastError();
-        };
-        if (!use_lanes || beside)
-            for (size_t first = 0; first < nblocks; first += chunk)
-                if ((e = round(first, nblocks - first < chunk ? nblocks - first : chunk, false)) != hipSuccess) return e;
-        if (beside) { // the hand-back pass, the redo pass and the caller's later work wait for the lanes
-            if ((e = lanes_fork->join()) != hipSuccess) return e;
-        }
-        if (use_lanes && kn.debug_lzf) {
-            uint32_t h[kCtrBytes / 4];
-            (void)hipStreamSynchronize(stream);
-            (void)hipMemcpy(h, counter, kCtrBytes, hipMemcpyDeviceToHost);
-            fprintf(stderr, "lzf lanes: taken %u claimed %u poor %u fine %u handed back %u of %zu; claim ticket %u, gave up %u\n", h[kCtrWord],
-                    h[kCtrWord + 1], h[kCtrPoor], h[kCtrFine], h[kCtrHanded], nblocks, h[kCtrTicket], h[kCtrFailed]);
-        }
-        if (use_lanes)
-            for (size_t first = 0; first < nblocks; first += hb_chunk)
-                if ((e = round(first, nblocks - first < hb_chunk ? nblocks - first : hb_chunk, true)) != hipSuccess) return e;
-        hipLaunchKernelGGL(lzf_blocks_kernel, dim3((unsigned)grid), dim3(64), lds, stream, src, n, src_stride, nblocks, dst,
-                           dst_stride, sizes, in_lds, 1u, beside ? counter + kCtrFailed : nullptr);
-        note_kernels(0, launched);
+        hipLaunchKernelGGL(kernel_row(kLzfLanesKernels, p.lanes_kernel).fn, dim3(p.lanes.grid), dim3(64), 0, lstream, src, n, src_stride, nblocks, dst,
+                           dst_stride, sizes, w.lane_tabs.as<uint16_t>(), counter, p.lane_reserve, w.handback.as<uint32_t>());
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    if ((e = lzf_set_chain_attributes()) != hipSuccess) return e;
+    // one round of the link + chain kernels: blocks [first, first + nb) of the batch, or entries [first, first + nb) of the
+    // hand-back list (as far as the lanes filled it: the kernels read its length on the device and return at once beyond it)
+    const size_t chain_per_cu = p.chain_kernel == LzfChain::sthread ? p.st_cu : p.per_cu;
+    auto round = [&](size_t first, size_t nb, bool listed) -> hipError_t {
+        hipError_t r = hipMemsetAsync(counter, 0, sizeof(uint32_t), stream);
+        if (r != hipSuccess) return r;
+        const LaneShare share = {p.beside && !listed ? counter : nullptr, first, nblocks, (uint32_t)(first / p.chunk + 1), p.spin_cap};
+        const BlockList list = {listed ? w.handback.as<uint32_t>() : nullptr, listed ? counter + kCtrHanded : nullptr, (uint32_t)first};
+        const size_t off = listed ? 0 : first; // listed blocks are addressed through the list, from the batch's base
+        hipLaunchKernelGGL(lzf_links_kernel, dim3((unsigned)(nb < 256 ? nb : 256)), dim3(64), p.links_lds, stream, src + off * src_stride, n,
+                           src_stride, nb, links, p.n2, sizes + off, p.force_redo, share, list);
+        const size_t cgrid = nb < 256 * chain_per_cu ? nb : 256 * chain_per_cu;
+        hipLaunchKernelGGL(kernel_row(kLzfChainKernels, p.chain_kernel).fn, dim3((unsigned)cgrid), dim3(64), p.chain_lds, stream, src + off * src_stride, n,
+                           src_stride, nb, dst + off * dst_stride, dst_stride, sizes + off, links, p.n2, counter, share, list);
         return hipGetLastError();
+    };
+    if (p.rounds_over_batch)
+        for (size_t first = 0; first < nblocks; first += p.chunk)
+            if ((e = round(first, nblocks - first < p.chunk ? nblocks - first : p.chunk, false)) != hipSuccess) return e;
+    // the hand-back pass, the redo pass and the caller's later work wait for the lanes
+    if (lanes_fork && (e = lanes_fork->join()) != hipSuccess) return e;
+    if (p.lanes.on && kn.debug_lzf) {
+        uint32_t h[kCtrBytes / 4];
+        (void)hipStreamSynchronize(stream);
+        (void)hipMemcpy(h, counter, kCtrBytes, hipMemcpyDeviceToHost);
+        fprintf(stderr, "lzf lanes: taken %u claimed %u poor %u fine %u handed back %u of %zu; claim ticket %u, gave up %u\n", h[kCtrWord],
+                h[kCtrWord + 1], h[kCtrPoor], h[kCtrFine], h[kCtrHanded], nblocks, h[kCtrTicket], h[kCtrFailed]);
     }
-    if (!cut_only) {
-        if (in_lds)
-            { note("cw::lzf_parse_kernel<true>");
-            hipLaunchKernelGGL(lzf_parse_kernel<true>, dim3((unsigned)grid), dim3(64), lds, stream, src, n, src_stride, nblocks, dst,
-                               dst_stride, sizes, force_redo); }
-        else
-            { note("cw::lzf_parse_kernel<false>");
-            hipLaunchKernelGGL(lzf_parse_kernel<false>, dim3((unsigned)grid), dim3(64), lds, stream, src, n, src_stride, nblocks, dst,
-                               dst_stride, sizes, force_redo); }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(lzf_blocks_kernel, dim3((unsigned)grid), dim3(64), lds, stream, src, n, src_stride, nblocks, dst,
-                       dst_stride, sizes, in_lds, cut_only ? 0u : 1u, static_cast<const uint32_t *>(nullptr));
-    if (cut_only) note("cw::lzf_blocks_kernel");
-    note_kernels(0, launched);
-    return hipGetLastError();
+    if (p.rounds_over_handback)
+        for (size_t first = 0; first < nblocks; first += p.hb_chunk)
+            if ((e = round(first, nblocks - first < p.hb_chunk ? nblocks - first : p.hb_chunk, true)) != hipSuccess) return e;
+    return lzf_enqueue_tail(p, p.beside ? counter + kCtrFailed : nullptr, src, n, src_stride, nblocks, dst, dst_stride, sizes, stream);
 }
 
 } // namespace cw

@@ -7,8 +7,11 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <initializer_list>
+#include <atomic>
 #include <mutex>
 #include <unordered_map>
+#include <utility>
 
 namespace cw {
 
@@ -126,6 +129,21 @@ protected:
 };
 
 using LaunchLock = std::lock_guard<std::mutex>;
+
+// The dynamic-LDS limits of a launch function's kernels (`done`: that function's own flag): each set is made once per process; a
+// failure is the call's, and the next call tries again.  Once a set is made, a call only reads the flag.
+inline hipError_t set_lds_limits_once(std::atomic<bool> &done, std::initializer_list<std::pair<const void *, uint32_t>> limits)
+{
+    if (done.load(std::memory_order_acquire)) return hipSuccess;
+    static std::mutex lock;
+    std::lock_guard<std::mutex> g(lock);
+    for (auto it = limits.begin(); !done.load(std::memory_order_relaxed) && it != limits.end(); ++it) {
+        const hipError_t e = hipFuncSetAttribute(it->first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)it->second);
+        if (e != hipSuccess) return e;
+    }
+    done.store(true, std::memory_order_release);
+    return hipSuccess;
+}
 
 // One T per (device, stream), each with the launch mutex of ws_key()'s comment.  There is one mutex per (registry, stream)
 // and not one per stream, because launch functions nest on a stream: chunk_hash_launch calls the hash's launch function

@@ -277,6 +277,14 @@ class tuned:
         return False
 
 
+def plan_describe(alg, block_bytes: int, nblocks: int, src_misalign: int = 0, dst_misalign: int = 0) -> str:
+    """cw_plan_describe: what dev_compress would launch under the knobs as they are now -- line 1 as profile_kernels()["codec"]
+    reports it afterwards, then one key=value line per field of the launch plan.  Needs no device."""
+    buf = C.create_string_buffer(8192)
+    check(lib().cw_plan_describe(_comp_id(alg), block_bytes, nblocks, src_misalign, dst_misalign, buf, 8192))
+    return buf.value.decode()
+
+
 def profile_kernels() -> dict:
     """Names of the kernels the calling thread's latest codec / hash launch used (as rocprofv3 prints them)."""
     out = {}

@@ -358,6 +358,13 @@ int  cw_profile_kernels(int kind, char *buf, size_t cap);
  * meant for tests and profiling.                                                                                      */
 int  cw_tune_set(const char *key, const char *value);
 void cw_tune_reset(void);
+/* What cw_dev_compress would launch for nblocks blocks of block_bytes under the knobs as they are now, without a device:
+ * line 1 = the kernels as cw_profile_kernels reports them after such a call; then one `key=value` line per field of the launch
+ * plan (kernels, grids, LDS bytes, streams, thresholds, reserves, workspace bytes), in a fixed order.  src_misalign stands for
+ * (src | src_stride) & 15, dst_misalign for (dst | dst_stride) & 15.  CW_ERR_BAD_ARG: sizes the call would refuse, or a buffer
+ * that is too small.                                                                                                     */
+int  cw_plan_describe(int comp_alg, size_t block_bytes, size_t nblocks, unsigned src_misalign, unsigned dst_misalign, char *buf,
+                      size_t cap);
 
 /* ---- HashOffload (HashOffload.h:13-64): batch object + the offload thread that drains it -------
  * Lifecycle  hInit --Enqueue--> hQueued --Start--> hOffloaded --Complete--> hComplete.
