@@ -26,6 +26,8 @@ ABI_SYMBOLS = [
     "cw_offload_complete", "cw_offload_completed", "cw_offload_state", "cw_offload_error", "cw_offload_do",
     "cw_offload_thread_start", "cw_offload_submit", "cw_offload_thread_stop",
     "cw_dedupe_create", "cw_dedupe_destroy", "cw_dedupe_count", "cw_dev_dedupe", "cw_dev_hash_dedupe_compress",
+    "cw_dev_dedupe_lookup", "cw_dev_dedupe_insert", "cw_dev_dedupe_export", "cw_dedupe_export", "cw_dedupe_import",
+    "cw_dedupe_set_stage_entries", "cw_dedupe_resize", "cw_dedupe_max_entries",
     "cw_cdc_default_params", "cw_dev_cdc", "cw_dev_hash_chunks", "cw_cdc_hash",
     "cw_chunk_slot_offset", "cw_chunk_slots_bytes", "cw_dev_compress_chunks", "cw_dev_pack_chunks", "cw_dev_decompress_chunks",
     "cw_dev_cdc_dedupe_compress",
@@ -128,6 +130,12 @@ def lib() -> C.CDLL:
         "cw_dedupe_count": ([vp, vp], C.c_int),
         "cw_dev_dedupe": ([vp, vp, sz, C.c_uint64, vp, vp, vp, vp], C.c_int),
         "cw_dev_hash_dedupe_compress": ([vp, C.c_int, vp, sz, sz, sz, C.c_uint64, vp, vp, vp, vp, sz, u32p, vp, vp], C.c_int),
+        "cw_dev_dedupe_lookup": ([vp, vp, sz, vp, vp, vp], C.c_int),
+        "cw_dev_dedupe_insert": ([vp, vp, vp, sz, vp, vp, vp, vp], C.c_int),
+        "cw_dev_dedupe_export": ([vp, vp, vp, sz, vp, vp], C.c_int),
+        "cw_dedupe_export": ([vp, vp, vp, sz, vp], C.c_int), "cw_dedupe_import": ([vp, vp, vp, sz, vp], C.c_int),
+        "cw_dedupe_set_stage_entries": ([vp, sz], C.c_int),
+        "cw_dedupe_resize": ([vp, sz], C.c_int), "cw_dedupe_max_entries": ([vp, vp], C.c_int),
         "cw_cdc_default_params": ([vp, C.c_uint32], None),
         "cw_dev_cdc": ([vp, vp, sz, C.c_int, vp, sz, vp, vp], C.c_int),
         "cw_dev_hash_chunks": ([C.c_int, vp, sz, vp, vp, sz, vp, vp], C.c_int),

@@ -1500,9 +1500,11 @@ struct cw_dedupe {
     void *table = nullptr;           // one allocation: state | value | key | min_idx | ctrl
     uint64_t *state = nullptr, *value = nullptr, *key = nullptr;
     uint32_t *min_idx = nullptr;
-    uint64_t *ctrl = nullptr;        // [0] count, [1] a probe reached its bound, [2] n_new of the fused call
+    uint64_t *ctrl = nullptr;        // [0] count, [1] a probe / lookup / rehash walk reached its bound, [2] n_new of the fused call
     uint64_t *h_ctrl = nullptr;      // pinned: the fused call's copy of ctrl[1..2]
     DevBuf rec, flags, offs, gather; // per-call scratch, shared by the calls because they are serialised
+    DevBuf stage_dig, stage_val, stage_out; // the host forms' pieces: digests | values | ref, new_idx, n_new of an import piece
+    size_t stage_entries = (size_t)1 << 20; // pairs per piece (cw_dedupe_set_stage_entries)
     hipEvent_t last = nullptr;       // the last call's work: the next call's stream waits for it
     uint64_t count_bound = 0;        // upper bound on ctrl[0] (every block of every call counted)
     std::mutex lock;                 // guards `last`, the scratch and count_bound
@@ -1539,15 +1541,32 @@ int dedupe_admit(cw_dedupe *x, size_t n)
     return CW_OK;
 }
 
-// x->lock held, admitted: probe, resolve, index-only pack scan of the new flags, scatter -- queued on s
-int dedupe_enqueue(cw_dedupe *x, const uint64_t *dig, uint32_t n, uint64_t base, uint64_t *ref, uint32_t *new_idx, uint64_t *d_n_new,
-                   hipStream_t s)
+// x->lock held: the shared "index is inconsistent" check of a copy of ctrl[0..1]
+int dedupe_read_count(cw_dedupe *x, uint64_t *count)
+{
+    HIP_TRY(hipEventSynchronize(x->last));
+    uint64_t c[2];
+    HIP_TRY(hipMemcpy(c, x->ctrl, sizeof c, hipMemcpyDeviceToHost));
+    if (c[1]) return fail(CW_ERR_HIP, "dedupe index: a probe reached its bound (the table is inconsistent)");
+    x->count_bound = *count = c[0];
+    return CW_OK;
+}
+
+// x->lock held: index-owned scratch of at least `bytes`; growing frees a buffer the last call may still use
+int dedupe_scratch(cw_dedupe *x, DevBuf &b, size_t bytes)
+{
+    if (b.buf.bytes() < bytes) HIP_TRY(hipEventSynchronize(x->last));
+    return b.reserve(bytes);
+}
+
+// x->lock held, admitted: probe, resolve, index-only pack scan of the new flags, scatter -- queued on s.  values != NULL: block i
+// carries values[i] instead of base + i.
+int dedupe_enqueue(cw_dedupe *x, const uint64_t *dig, uint32_t n, uint64_t base, const uint64_t *values, uint64_t *ref, uint32_t *new_idx,
+                   uint64_t *d_n_new, hipStream_t s)
 {
     int rc;
-    if (x->rec.buf.bytes() < (size_t)n * 8 || x->offs.buf.bytes() < ((size_t)n + 1) * 8) // growing frees scratch the last call may still use
-        HIP_TRY(hipEventSynchronize(x->last));
-    if ((rc = x->rec.reserve((size_t)n * 8)) != CW_OK || (rc = x->flags.reserve((size_t)n * 4)) != CW_OK ||
-        (rc = x->offs.reserve(((size_t)n + 1) * 8)) != CW_OK)
+    if ((rc = dedupe_scratch(x, x->rec, (size_t)n * 8)) != CW_OK || (rc = dedupe_scratch(x, x->flags, (size_t)n * 4)) != CW_OK ||
+        (rc = dedupe_scratch(x, x->offs, ((size_t)n + 1) * 8)) != CW_OK)
         return rc;
     uint64_t *rec = (uint64_t *)x->rec.p, *off = (uint64_t *)x->offs.p;
     uint32_t *flags = (uint32_t *)x->flags.p;
@@ -1555,11 +1574,50 @@ int dedupe_enqueue(cw_dedupe *x, const uint64_t *dig, uint32_t n, uint64_t base,
     hipError_t e = cw::dedupe_probe_launch(x->words, dig, n, x->state, x->min_idx, x->value, x->key, x->cap - 1, rec, ref,
                                            reinterpret_cast<unsigned long long *>(x->ctrl + 1), s);
     if (e == hipSuccess)
-        e = cw::dedupe_resolve_launch(x->words, dig, n, base, x->min_idx, x->state, x->value, x->key, rec, ref, flags, s);
+        e = cw::dedupe_resolve_launch(x->words, dig, n, base, values, x->min_idx, x->state, x->value, x->key, rec, ref, flags, s);
     if (e == hipSuccess) e = cw::pack_launch(nullptr, 0, flags, n, nullptr, off, s);
     if (e == hipSuccess) e = cw::dedupe_scatter_launch(flags, off, n, rec, x->min_idx, new_idx, d_n_new, x->ctrl, s);
     if (e != hipSuccess) return fail(CW_ERR_HIP, "dedupe launch: %s", hipGetErrorString(e));
     return CW_OK;
+}
+} // namespace
+
+namespace {
+// the table of an index: one allocation, state | value | key | min_idx | ctrl
+struct DedupeTable {
+    void *mem = nullptr;
+    uint64_t *state = nullptr, *value = nullptr, *key = nullptr, *ctrl = nullptr;
+    uint32_t *min_idx = nullptr;
+};
+uint64_t dedupe_cap(size_t max_entries)
+{
+    uint64_t cap = 2;
+    while (cap < 2 * (uint64_t)max_entries) cap <<= 1;
+    return cap;
+}
+size_t dedupe_table_bytes(uint64_t cap, size_t db) { return cap * (20 + db) + 4 * sizeof(uint64_t); }
+// allocated and emptied (state EMPTY, min_idx UINT32_MAX, ctrl 0) on stream s, not synchronised; on failure nothing is held
+hipError_t dedupe_table_alloc(uint64_t cap, size_t db, hipStream_t s, DedupeTable *t)
+{
+    hipError_t e = hipMalloc(&t->mem, dedupe_table_bytes(cap, db));
+    if (e != hipSuccess) { t->mem = nullptr; return e; }
+    uint8_t *p = (uint8_t *)t->mem;
+    t->state = (uint64_t *)p;
+    t->value = (uint64_t *)(p + cap * 8);
+    t->key = (uint64_t *)(p + cap * 16);
+    t->min_idx = (uint32_t *)(p + cap * (16 + db));
+    t->ctrl = (uint64_t *)(p + cap * (20 + db)); // cap is even: 8-byte aligned
+    e = hipMemsetAsync(t->state, 0, cap * 8, s);
+    if (e == hipSuccess) e = hipMemsetAsync(t->min_idx, 0xFF, cap * 4, s);
+    if (e == hipSuccess) e = hipMemsetAsync(t->ctrl, 0, 4 * sizeof(uint64_t), s);
+    if (e != hipSuccess) { (void)hipFree(t->mem); t->mem = nullptr; }
+    return e;
+}
+void dedupe_table_adopt(cw_dedupe *x, const DedupeTable &t, uint64_t cap, size_t max_entries)
+{
+    x->table = t.mem; x->state = t.state; x->value = t.value; x->key = t.key; x->min_idx = t.min_idx; x->ctrl = t.ctrl;
+    x->cap = cap;
+    x->max_entries = max_entries;
 }
 } // namespace
 
@@ -1575,22 +1633,13 @@ cw_dedupe_t *cw_dedupe_create(int hash_alg, size_t max_entries)
     x->device = current_device();
     x->hash_alg = hash_alg;
     x->words = (unsigned)(db / 8);
-    x->max_entries = max_entries;
-    x->cap = 2;
-    while (x->cap < 2 * (uint64_t)max_entries) x->cap <<= 1;
-    const size_t cap = x->cap, bytes = cap * (20 + db) + 4 * sizeof(uint64_t);
-    hipError_t e = hipMalloc(&x->table, bytes);
+    const uint64_t cap = dedupe_cap(max_entries);
+    const size_t bytes = dedupe_table_bytes(cap, db);
+    DedupeTable t;
+    hipError_t e = dedupe_table_alloc(cap, db, nullptr, &t);
     if (e == hipSuccess) {
-        uint8_t *p = (uint8_t *)x->table;
-        x->state = (uint64_t *)p;
-        x->value = (uint64_t *)(p + cap * 8);
-        x->key = (uint64_t *)(p + cap * 16);
-        x->min_idx = (uint32_t *)(p + cap * (16 + db));
-        x->ctrl = (uint64_t *)(p + cap * (20 + db)); // cap is even: 8-byte aligned
-        e = hipMemset(x->state, 0, cap * 8);
-        if (e == hipSuccess) e = hipMemset(x->min_idx, 0xFF, cap * 4);
-        if (e == hipSuccess) e = hipMemset(x->ctrl, 0, 4 * sizeof(uint64_t));
-        if (e == hipSuccess) e = hipDeviceSynchronize(); // the calls come on other streams
+        dedupe_table_adopt(x, t, cap, max_entries);
+        e = hipDeviceSynchronize(); // the calls come on other streams
     }
     if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&x->h_ctrl), 2 * sizeof(uint64_t), hipHostMallocDefault);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&x->last, hipEventDisableTiming);
@@ -1609,6 +1658,7 @@ void cw_dedupe_destroy(cw_dedupe_t *x)
     (void)hipSetDevice(x->device);
     if (x->last) { (void)hipEventSynchronize(x->last); (void)hipEventDestroy(x->last); }
     x->rec.release(); x->flags.release(); x->offs.release(); x->gather.release();
+    x->stage_dig.release(); x->stage_val.release(); x->stage_out.release();
     if (x->table) (void)hipFree(x->table);
     if (x->h_ctrl) (void)hipHostFree(x->h_ctrl);
     delete x;
@@ -1620,12 +1670,23 @@ int cw_dedupe_count(cw_dedupe_t *x, uint64_t *count)
     if (rc != CW_OK) return rc;
     if (!count) return fail(CW_ERR_BAD_ARG, "NULL count");
     std::lock_guard<std::mutex> g(x->lock);
-    HIP_TRY(hipEventSynchronize(x->last));
-    uint64_t c[2];
-    HIP_TRY(hipMemcpy(c, x->ctrl, sizeof c, hipMemcpyDeviceToHost));
-    if (c[1]) return fail(CW_ERR_HIP, "dedupe index: a probe reached its bound (the table is inconsistent)");
-    x->count_bound = c[0];
-    *count = c[0];
+    return dedupe_read_count(x, count);
+}
+
+int cw_dedupe_max_entries(cw_dedupe_t *x, size_t *max_entries)
+{
+    if (!x || !max_entries) return fail(CW_ERR_BAD_ARG, "NULL %s", x ? "max_entries" : "dedupe index");
+    std::lock_guard<std::mutex> g(x->lock);
+    *max_entries = x->max_entries;
+    return CW_OK;
+}
+
+int cw_dedupe_set_stage_entries(cw_dedupe_t *x, size_t entries)
+{
+    if (!x) return fail(CW_ERR_BAD_ARG, "NULL dedupe index");
+    if (entries > kMaxDedupeBlocks) return fail(CW_ERR_BAD_ARG, "stage entries %zu > 2^32 - 256", entries);
+    std::lock_guard<std::mutex> g(x->lock);
+    x->stage_entries = entries ? entries : (size_t)1 << 20;
     return CW_OK;
 }
 
@@ -1640,9 +1701,180 @@ int cw_dev_dedupe(cw_dedupe_t *x, const void *d_digests, size_t nblocks, uint64_
     std::lock_guard<std::mutex> g(x->lock);
     if ((rc = dedupe_admit(x, nblocks)) != CW_OK) return rc;
     HIP_TRY(hipStreamWaitEvent(s, x->last, 0));
-    rc = dedupe_enqueue(x, (const uint64_t *)d_digests, (uint32_t)nblocks, base, d_ref, d_new_idx, d_n_new, s);
+    rc = dedupe_enqueue(x, (const uint64_t *)d_digests, (uint32_t)nblocks, base, nullptr, d_ref, d_new_idx, d_n_new, s);
     HIP_TRY(hipEventRecord(x->last, s));
     return rc;
+}
+
+int cw_dev_dedupe_insert(cw_dedupe_t *x, const void *d_digests, const uint64_t *d_values, size_t n, uint64_t *d_ref, uint32_t *d_new_idx,
+                         uint64_t *d_n_new, void *stream)
+{
+    int rc = dedupe_args(x, n, 0);
+    if (rc != CW_OK || n == 0) return rc;
+    if (!d_digests || !d_values || !d_ref || !d_new_idx || !d_n_new) return fail(CW_ERR_BAD_ARG, "NULL device pointer");
+    if ((uintptr_t)d_digests % 8) return fail(CW_ERR_BAD_ARG, "d_digests must be 8-byte aligned");
+    const hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::mutex> g(x->lock);
+    if ((rc = dedupe_admit(x, n)) != CW_OK) return rc;
+    HIP_TRY(hipStreamWaitEvent(s, x->last, 0));
+    rc = dedupe_enqueue(x, (const uint64_t *)d_digests, (uint32_t)n, 0, d_values, d_ref, d_new_idx, d_n_new, s);
+    HIP_TRY(hipEventRecord(x->last, s));
+    return rc;
+}
+
+int cw_dev_dedupe_lookup(cw_dedupe_t *x, const void *d_digests, size_t n, uint64_t *d_ref, uint64_t *d_n_found, void *stream)
+{
+    int rc = dedupe_args(x, n, 0);
+    if (rc != CW_OK || n == 0) return rc;
+    if (!d_digests || !d_ref || !d_n_found) return fail(CW_ERR_BAD_ARG, "NULL device pointer");
+    if ((uintptr_t)d_digests % 8) return fail(CW_ERR_BAD_ARG, "d_digests must be 8-byte aligned");
+    const hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::mutex> g(x->lock);
+    HIP_TRY(hipStreamWaitEvent(s, x->last, 0));
+    const hipError_t e = cw::dedupe_lookup_launch(x->words, (const uint64_t *)d_digests, (uint32_t)n, x->state, x->value, x->key, x->cap - 1, d_ref,
+                                                  d_n_found, reinterpret_cast<unsigned long long *>(x->ctrl + 1), s);
+    HIP_TRY(hipEventRecord(x->last, s));
+    return e == hipSuccess ? CW_OK : fail(CW_ERR_HIP, "dedupe lookup launch: %s", hipGetErrorString(e));
+}
+
+namespace {
+// x->lock held, s waits for x->last: tile counts and their scan into the index's scratch (flags = counts, offs)
+int dedupe_export_scan(cw_dedupe *x, hipStream_t s)
+{
+    const uint64_t ntiles = cw::dedupe_export_tiles(x->cap);
+    int rc;
+    if ((rc = dedupe_scratch(x, x->flags, ntiles * 4)) != CW_OK || (rc = dedupe_scratch(x, x->offs, (ntiles + 1) * 8)) != CW_OK) return rc;
+    const hipError_t e = cw::dedupe_export_scan_launch(x->state, x->cap, (uint32_t *)x->flags.p, (uint64_t *)x->offs.p, s);
+    return e == hipSuccess ? CW_OK : fail(CW_ERR_HIP, "dedupe export scan launch: %s", hipGetErrorString(e));
+}
+int dedupe_export_scatter(cw_dedupe *x, uint64_t first, uint64_t max_out, void *d_digests, uint64_t *d_values, uint64_t *d_n, hipStream_t s)
+{
+    const hipError_t e = cw::dedupe_export_scatter_launch(x->words, x->state, x->value, x->key, x->cap, (const uint64_t *)x->offs.p, first, max_out,
+                                                          (uint64_t *)d_digests, d_values, d_n, s);
+    return e == hipSuccess ? CW_OK : fail(CW_ERR_HIP, "dedupe export launch: %s", hipGetErrorString(e));
+}
+} // namespace
+
+int cw_dev_dedupe_export(cw_dedupe_t *x, void *d_digests, uint64_t *d_values, size_t max_out, uint64_t *d_n, void *stream)
+{
+    int rc = dedupe_args(x, 0, 0);
+    if (rc != CW_OK) return rc;
+    if (!d_n || (max_out && (!d_digests || !d_values))) return fail(CW_ERR_BAD_ARG, "NULL device pointer");
+    if ((uintptr_t)d_digests % 8) return fail(CW_ERR_BAD_ARG, "d_digests must be 8-byte aligned");
+    const hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::mutex> g(x->lock);
+    HIP_TRY(hipStreamWaitEvent(s, x->last, 0));
+    if ((rc = dedupe_export_scan(x, s)) == CW_OK) rc = dedupe_export_scatter(x, 0, max_out, d_digests, d_values, d_n, s);
+    HIP_TRY(hipEventRecord(x->last, s));
+    return rc;
+}
+
+int cw_dedupe_export(cw_dedupe_t *x, void *digests, uint64_t *values, size_t max_out, size_t *n)
+{
+    int rc = dedupe_args(x, 0, 0);
+    if (rc != CW_OK) return rc;
+    if (!n || (max_out && (!digests || !values))) return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    ThreadCtx *c;
+    if ((rc = thread_ctx(&c)) != CW_OK) return rc;
+    const hipStream_t s = c->stream;
+    const size_t db = (size_t)x->words * 8;
+    std::lock_guard<std::mutex> g(x->lock);
+    HIP_TRY(hipStreamWaitEvent(s, x->last, 0));
+    if ((rc = dedupe_export_scan(x, s)) != CW_OK) return rc;
+    uint64_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, (const uint64_t *)x->offs.p + cw::dedupe_export_tiles(x->cap), sizeof total, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const size_t want = total < max_out ? (size_t)total : max_out, piece = x->stage_entries < want ? x->stage_entries : want;
+    if (piece && ((rc = dedupe_scratch(x, x->stage_dig, piece * db)) != CW_OK || (rc = dedupe_scratch(x, x->stage_val, piece * 8)) != CW_OK)) return rc;
+    for (size_t first = 0; first < want && rc == CW_OK; first += piece) {
+        const size_t k = want - first < piece ? want - first : piece;
+        if ((rc = dedupe_export_scatter(x, first, k, x->stage_dig.p, (uint64_t *)x->stage_val.p, nullptr, s)) != CW_OK) break;
+        HIP_TRY(hipMemcpyAsync((uint8_t *)digests + first * db, x->stage_dig.p, k * db, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(values + first, x->stage_val.p, k * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s)); // the next piece overwrites the staging buffers
+    }
+    HIP_TRY(hipEventRecord(x->last, s));
+    if (rc == CW_OK) *n = (size_t)total;
+    return rc;
+}
+
+int cw_dedupe_import(cw_dedupe_t *x, const void *digests, const uint64_t *values, size_t n, size_t *n_inserted)
+{
+    if (n_inserted) *n_inserted = 0;
+    int rc = dedupe_args(x, 0, 0);
+    if (rc != CW_OK) return rc;
+    if (!n_inserted || (n && (!digests || !values))) return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    if (n == 0) return CW_OK;
+    ThreadCtx *c;
+    if ((rc = thread_ctx(&c)) != CW_OK) return rc;
+    const hipStream_t s = c->stream;
+    const size_t db = (size_t)x->words * 8;
+    std::lock_guard<std::mutex> g(x->lock);
+    if ((rc = dedupe_admit(x, n)) != CW_OK) return rc; // the whole import: count only grows by what the pieces insert, so no piece can overflow
+    const size_t piece = x->stage_entries < n ? x->stage_entries : n;
+    if ((rc = dedupe_scratch(x, x->stage_dig, piece * db)) != CW_OK || (rc = dedupe_scratch(x, x->stage_val, piece * 8)) != CW_OK ||
+        (rc = dedupe_scratch(x, x->stage_out, piece * 12 + 16)) != CW_OK)
+        return rc;
+    uint64_t *d_ref = (uint64_t *)x->stage_out.p, *d_k = d_ref + piece;
+    uint32_t *d_new = (uint32_t *)(d_k + 1);
+    HIP_TRY(hipStreamWaitEvent(s, x->last, 0));
+    size_t inserted = 0;
+    for (size_t first = 0; first < n && rc == CW_OK; first += piece) {
+        const size_t k = n - first < piece ? n - first : piece;
+        uint64_t k_new = 0;
+        HIP_TRY(hipMemcpyAsync(x->stage_dig.p, (const uint8_t *)digests + first * db, k * db, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(x->stage_val.p, values + first, k * 8, hipMemcpyHostToDevice, s));
+        rc = dedupe_enqueue(x, (const uint64_t *)x->stage_dig.p, (uint32_t)k, 0, (const uint64_t *)x->stage_val.p, d_ref, d_new, d_k, s);
+        HIP_TRY(hipEventRecord(x->last, s));
+        if (rc != CW_OK) break;
+        HIP_TRY(hipMemcpyAsync(&k_new, d_k, sizeof k_new, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s)); // the next piece overwrites the staging buffers
+        inserted += (size_t)k_new;
+    }
+    if (rc == CW_OK) *n_inserted = inserted;
+    return rc;
+}
+
+int cw_dedupe_resize(cw_dedupe_t *x, size_t new_max_entries)
+{
+    int rc = dedupe_args(x, 0, 0);
+    if (rc != CW_OK) return rc;
+    std::lock_guard<std::mutex> g(x->lock);
+    uint64_t count = 0;
+    if ((rc = dedupe_read_count(x, &count)) != CW_OK) return rc;
+    if (new_max_entries == 0 || new_max_entries > ((size_t)1 << 40) || new_max_entries < count)
+        return fail(CW_ERR_BAD_ARG, "cw_dedupe_resize: max_entries %zu not in [max(1, count = %llu), 2^40]", new_max_entries, (unsigned long long)count);
+    const uint64_t cap = dedupe_cap(new_max_entries);
+    if (cap == x->cap) { // the same table serves
+        x->max_entries = new_max_entries;
+        return CW_OK;
+    }
+    const size_t db = (size_t)x->words * 8;
+    DedupeTable t;
+    hipError_t e = dedupe_table_alloc(cap, db, nullptr, &t);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(e == hipErrorOutOfMemory ? CW_ERR_NOMEM : CW_ERR_HIP, "cw_dedupe_resize(%zu entries, %zu bytes beside the old table): %s", new_max_entries,
+                    dedupe_table_bytes(cap, db), hipGetErrorString(e));
+    }
+    // the old table is idle (the last call has finished, the lock keeps new ones out): rehash and carry ctrl over on the NULL stream
+    uint64_t err = 0;
+    e = cw::dedupe_rehash_launch(x->words, x->state, x->value, x->key, x->cap, t.state, t.value, t.key, cap - 1,
+                                 reinterpret_cast<unsigned long long *>(t.ctrl + 1), nullptr);
+    if (e == hipSuccess) e = hipMemcpyAsync(&err, t.ctrl + 1, sizeof err, hipMemcpyDeviceToHost, nullptr);
+    if (e == hipSuccess) e = hipMemcpyAsync(t.ctrl, x->ctrl, 4 * sizeof(uint64_t), hipMemcpyDeviceToDevice, nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess || err) {
+        (void)hipFree(t.mem);
+        return e != hipSuccess ? fail(CW_ERR_HIP, "cw_dedupe_resize: %s", hipGetErrorString(e))
+                               : fail(CW_ERR_HIP, "cw_dedupe_resize: an entry found no slot in the new table (the index is unchanged)");
+    }
+    void *old = x->table;
+    dedupe_table_adopt(x, t, cap, new_max_entries);
+    x->count_bound = count;
+    HIP_TRY(hipEventRecord(x->last, nullptr));
+    HIP_TRY(hipFree(old));
+    return CW_OK;
 }
 
 // hash -> dedupe -> one 16-byte copy back + a synchronise -> the codec over the new blocks only.  The codec cannot start before
@@ -1669,7 +1901,7 @@ int cw_dev_hash_dedupe_compress(cw_dedupe_t *x, int comp_alg, const void *d_src,
     if ((rc = dedupe_admit(x, nblocks)) != CW_OK) return rc;
     HIP_TRY(hipStreamWaitEvent(s, x->last, 0));
     rc = dev_hash(x->hash_alg, src, block_bytes, src_stride, nblocks, (uint8_t *)d_digests, s, false, true);
-    if (rc == CW_OK) rc = dedupe_enqueue(x, (const uint64_t *)d_digests, (uint32_t)nblocks, base, d_ref, d_new_idx, x->ctrl + 2, s);
+    if (rc == CW_OK) rc = dedupe_enqueue(x, (const uint64_t *)d_digests, (uint32_t)nblocks, base, nullptr, d_ref, d_new_idx, x->ctrl + 2, s);
     if (rc == CW_OK) {
         HIP_TRY(hipMemcpyAsync(x->h_ctrl, x->ctrl + 1, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -1727,7 +1959,7 @@ int cw_dev_cdc_dedupe_compress(cw_dedupe_t *x, const cw_cdc_params *p, int comp_
     }
     if (base > UINT64_MAX - k) return fail(CW_ERR_BAD_ARG, "base + nchunks wraps");
     if ((rc = dedupe_admit(x, k)) != CW_OK) return rc; // offsets and digests are written; nothing inserted, nothing compressed
-    rc = dedupe_enqueue(x, (const uint64_t *)d_digests, (uint32_t)k, base, d_ref, d_new_idx, d_n_new, s);
+    rc = dedupe_enqueue(x, (const uint64_t *)d_digests, (uint32_t)k, base, nullptr, d_ref, d_new_idx, d_n_new, s);
     if (rc == CW_OK)
         rc = dev_compress_chunks(comp_alg, src, nbytes, d_offsets, d_nchunks, max_chunks, d_new_idx, d_n_new, (uint8_t *)d_dst, d_sizes, s);
     HIP_TRY(hipEventRecord(x->last, s));

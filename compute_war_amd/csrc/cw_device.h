@@ -102,10 +102,24 @@ void release_all_workspaces();
 // scratch of the call; off = exclusive scan of flags (pack_launch, index only); err |= 1 if a probe reached the bound
 hipError_t dedupe_probe_launch(unsigned words, const uint64_t *dig, uint32_t n, uint64_t *state, uint32_t *min_idx, const uint64_t *value,
                                const uint64_t *key, uint64_t mask, uint64_t *rec, uint64_t *ref, unsigned long long *err, hipStream_t s);
-hipError_t dedupe_resolve_launch(unsigned words, const uint64_t *dig, uint32_t n, uint64_t base, const uint32_t *min_idx, uint64_t *state,
-                                 uint64_t *value, uint64_t *key, const uint64_t *rec, uint64_t *ref, uint32_t *flags, hipStream_t s);
+// values != NULL: block j carries values[j] instead of base + j (cw_dev_dedupe_insert)
+hipError_t dedupe_resolve_launch(unsigned words, const uint64_t *dig, uint32_t n, uint64_t base, const uint64_t *values, const uint32_t *min_idx,
+                                 uint64_t *state, uint64_t *value, uint64_t *key, const uint64_t *rec, uint64_t *ref, uint32_t *flags, hipStream_t s);
 hipError_t dedupe_scatter_launch(const uint32_t *flags, const uint64_t *off, uint32_t n, const uint64_t *rec, uint32_t *min_idx,
                                  uint32_t *new_idx, uint64_t *n_new, uint64_t *count, hipStream_t s);
+// read-only: ref[i] = the stored value or UINT64_MAX, *n_found = hits (zeroed on the stream first); err = 1 if a walk found no EMPTY slot
+hipError_t dedupe_lookup_launch(unsigned words, const uint64_t *dig, uint32_t n, const uint64_t *state, const uint64_t *value, const uint64_t *key,
+                                uint64_t mask, uint64_t *ref, uint64_t *n_found, unsigned long long *err, hipStream_t s);
+// export = compaction of the committed slots in slot order, in tiles of 256 slots: counts[tiles] (u32) and offs[tiles + 1] are the
+// caller's scratch; the scatter writes pairs [first, first + max_out) of that order and the entry count to *d_n (may be NULL)
+uint64_t dedupe_export_tiles(uint64_t cap);
+hipError_t dedupe_export_scan_launch(const uint64_t *state, uint64_t cap, uint32_t *counts, uint64_t *offs, hipStream_t s);
+hipError_t dedupe_export_scatter_launch(unsigned words, const uint64_t *state, const uint64_t *value, const uint64_t *key, uint64_t cap,
+                                        const uint64_t *offs, uint64_t first, uint64_t max_out, uint64_t *out_dig, uint64_t *out_val, uint64_t *d_n,
+                                        hipStream_t s);
+// every committed entry of the old table into the (empty) new one; err = 1 if an entry found no slot
+hipError_t dedupe_rehash_launch(unsigned words, const uint64_t *old_state, const uint64_t *old_value, const uint64_t *old_key, uint64_t old_cap,
+                                uint64_t *state, uint64_t *value, uint64_t *key, uint64_t mask, unsigned long long *err, hipStream_t s);
 // block new_idx[j] (src_stride apart in src) -> dst + j * block_bytes, for j < n_new
 hipError_t dedupe_gather_launch(const uint8_t *src, size_t block_bytes, size_t src_stride, const uint32_t *new_idx, size_t n_new,
                                 uint8_t *dst, hipStream_t s);

@@ -1,20 +1,21 @@
-// dedupe_kernels.hip -- device-resident fingerprint index (cw_dedupe_*, cw_dev_dedupe): batched lookup-or-insert of full
-// digests in an open-addressed table with linear probing, on gfx950.  The reference has no counterpart: HashAndCompress.cpp
-// computes the digests and drops them (:257).
+// dedupe_kernels.hip -- device-resident fingerprint index (cw_dedupe_*, cw_dev_dedupe*): batched lookup-or-insert of full
+// digests in an open-addressed table with linear probing, on gfx950, and the index's lifecycle: read-only lookup, export and the
+// rehash of cw_dedupe_resize.  The reference has no counterpart: HashAndCompress.cpp computes the digests and drops them (:257,
+// SURVEY.md D3).
 //
-// Table (allocated once by cw_dedupe_create; capacity a power of two >= 2 x max_entries, so the load stays <= 0.5):
+// Table (allocated by cw_dedupe_create and again by cw_dedupe_resize; capacity a power of two >= 2 x max_entries, so the load stays <= 0.5):
 //   state[cap]   u64   EMPTY, PENDING(owner block of the running call) or COMMITTED
 //   min_idx[cap] u32   lowest block index of the running call that reached the slot (UINT32_MAX between calls)
-//   value[cap]   u64   value of the committed digest (base + i of the block that inserted it)
+//   value[cap]   u64   value of the committed digest (base + i, or values[i], of the block that inserted it)
 //   key[cap][W]  u64   the committed digest, all of it (W = 2 / 4 / 8 words)
 //
-// One call is three kernels plus the index-only pack scan (pack_kernels.hip) for the compaction:
+// One inserting call is three kernels plus the index-only pack scan (pack_kernels.hip) for the compaction:
 //   probe    one lane per block.  Lanes of a wavefront with equal digests elect the lowest lane; only these leaders touch
 //            the table.  Each probe step is ONE agent-scope 64-bit CAS EMPTY -> PENDING(leader); what it returns is the only
 //            read of `state` (per-XCD L2s are not coherent, MI355X_MICROARCH.md).  EMPTY: claimed; PENDING(k): compare with
 //            the batch's digest k; COMMITTED: compare with key[slot], a match is a hit on an earlier call's entry.  A claim or
 //            a PENDING match does atomicMin(min_idx[slot], leader); followers copy the leader's record.
-//   resolve  one lane per block, after the kernel boundary: ref = stored value (hit) or base + min_idx[slot]; the block with
+//   resolve  one lane per block, after the kernel boundary: ref = stored value (hit) or the value of block min_idx[slot]; the block with
 //            min_idx[slot] == i is new and commits the slot (key, value, then state).  Nothing else here reads state, key
 //            or value, so the commits race with nothing.
 //   scatter  new_idx[off[i]] = i for the new blocks, min_idx of their slots back to UINT32_MAX (here and not in resolve,
@@ -113,11 +114,12 @@ dedupe_probe_kernel(const uint64_t *__restrict__ dig, uint32_t n, uint64_t *__re
     if (rv & kHit) ref[i] = hv;
 }
 
-template <int W>
+// kValues: block j carries values[j] (cw_dev_dedupe_insert) instead of base + j
+template <int W, bool kValues>
 __global__ void __launch_bounds__(kThreads)
-dedupe_resolve_kernel(const uint64_t *__restrict__ dig, uint32_t n, uint64_t base, const uint32_t *__restrict__ min_idx,
-                      uint64_t *__restrict__ state, uint64_t *__restrict__ value, uint64_t *__restrict__ key,
-                      const uint64_t *__restrict__ rec, uint64_t *__restrict__ ref, uint32_t *__restrict__ flags)
+dedupe_resolve_kernel(const uint64_t *__restrict__ dig, uint32_t n, uint64_t base, const uint64_t *__restrict__ values,
+                      const uint32_t *__restrict__ min_idx, uint64_t *__restrict__ state, uint64_t *__restrict__ value,
+                      uint64_t *__restrict__ key, const uint64_t *__restrict__ rec, uint64_t *__restrict__ ref, uint32_t *__restrict__ flags)
 {
     const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
     if (i >= n) return;
@@ -129,11 +131,12 @@ dedupe_resolve_kernel(const uint64_t *__restrict__ dig, uint32_t n, uint64_t bas
     }
     const uint64_t slot = rv & kSlotMask;
     const uint32_t m = __hip_atomic_load(min_idx + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    ref[i] = base + m;
+    const uint64_t v = kValues ? values[m] : base + m;
+    ref[i] = v;
     flags[i] = m == i;
     if (m != i) return;
     for (int w = 0; w < W; w++) key[slot * W + w] = dig[(size_t)i * W + w];
-    value[slot] = base + i;
+    value[slot] = v;
     __hip_atomic_store(state + slot, kCommitted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
@@ -172,7 +175,136 @@ dedupe_gather_kernel(const uint8_t *__restrict__ src, size_t bb, size_t stride, 
     }
 }
 
+// ---- lifecycle: read-only lookup, export, rehash (protocol notes: the head of this file) ----------
+
+// Read-only query, one lane per digest: the probe's fold and bounded walk with PLAIN loads of state.  Calls on an index are
+// serialised and a dependent kernel boundary lies between this kernel and every earlier commit, so nothing changes the table
+// while it runs (inside the inserting probe that does not hold).  EMPTY ends the walk as a miss; between calls no slot is PENDING.
+// The only atomic is the hit count: ballot + population count per wavefront, the workgroup's four counts added up through LDS, then
+// one atomic per workgroup (16,384 same-address atomics, one per wavefront of a 2^20 batch, cost more than the walks: DESIGN.md
+// section 10).  The error word only ever holds 0 or 1: a plain store sets it.
+template <int W>
+__global__ void __launch_bounds__(kThreads)
+dedupe_lookup_kernel(const uint64_t *__restrict__ dig, uint32_t n, const uint64_t *__restrict__ state, const uint64_t *__restrict__ value,
+                     const uint64_t *__restrict__ key, uint64_t mask, uint64_t *__restrict__ ref, unsigned long long *__restrict__ n_found,
+                     unsigned long long *__restrict__ err)
+{
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    const bool valid = i < n;
+    bool hit = false;
+    if (valid) {
+        uint64_t d[W];
+        for (int w = 0; w < W; w++) d[w] = dig[(size_t)i * W + w];
+        uint64_t slot = fold(d) & mask, out = UINT64_MAX, step = 0;
+        for (; step <= mask; step++, slot = (slot + 1) & mask) {
+            const uint64_t st = state[slot];
+            if (st == kEmpty) break;
+            if (st == kCommitted && same<W>(key + slot * W, d)) { out = value[slot]; hit = true; break; }
+        }
+        if (step > mask) *err = 1ull; // no EMPTY slot in the whole table: it is inconsistent (the load is <= 0.5)
+        ref[i] = out;
+    }
+    __shared__ uint32_t whits[kThreads / 64];
+    const unsigned long long hits = __ballot(hit);
+    if ((threadIdx.x & 63u) == 0) whits[threadIdx.x >> 6] = (uint32_t)__builtin_popcountll(hits);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t all = 0;
+        for (uint32_t w = 0; w < kThreads / 64; w++) all += whits[w];
+        if (all) __hip_atomic_fetch_add(n_found, (unsigned long long)all, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// Export is a stream compaction over state[cap] in tiles of kThreads slots: committed slots per tile, the index-only pack scan
+// over the tile counts (offs[ntiles + 1]), then a pass that finds each committed slot's place inside its tile again with ballots.
+__device__ __forceinline__ uint64_t tile_rank(bool c, uint32_t *wcount, uint32_t *total)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const unsigned long long b = __ballot(c);
+    if (lane == 0) wcount[wave] = (uint32_t)__builtin_popcountll(b);
+    __syncthreads();
+    uint32_t before = (uint32_t)__builtin_popcountll(b & ((1ull << lane) - 1ull)), all = 0;
+    for (uint32_t w = 0; w < kThreads / 64; w++) {
+        if (w < wave) before += wcount[w];
+        all += wcount[w];
+    }
+    __syncthreads(); // the next tile writes wcount again
+    *total = all;
+    return before;
+}
+
+__global__ void __launch_bounds__(kThreads)
+dedupe_export_count_kernel(const uint64_t *__restrict__ state, uint64_t cap, uint64_t ntiles, uint32_t *__restrict__ counts)
+{
+    __shared__ uint32_t wcount[kThreads / 64];
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const uint64_t slot = tile * kThreads + threadIdx.x;
+        uint32_t total;
+        (void)tile_rank(slot < cap && state[slot] == kCommitted, wcount, &total);
+        if (threadIdx.x == 0) counts[tile] = total;
+    }
+}
+
+// pairs [first, first + max_out) of the slot order go to out_dig / out_val [0, max_out); *d_n = the entry count (d_n may be NULL)
+template <int W>
+__global__ void __launch_bounds__(kThreads)
+dedupe_export_scatter_kernel(const uint64_t *__restrict__ state, const uint64_t *__restrict__ value, const uint64_t *__restrict__ key,
+                             uint64_t cap, uint64_t ntiles, const unsigned long long *__restrict__ offs, uint64_t first, uint64_t max_out,
+                             uint64_t *__restrict__ out_dig, uint64_t *__restrict__ out_val, uint64_t *__restrict__ d_n, bool vec)
+{
+    __shared__ uint32_t wcount[kThreads / 64];
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const uint64_t t0 = offs[tile], t1 = offs[tile + 1];
+        if (t1 <= first || (t0 >= first && t0 - first >= max_out)) continue; // the same for every lane of the workgroup
+        const uint64_t slot = tile * kThreads + threadIdx.x;
+        const bool c = slot < cap && state[slot] == kCommitted;
+        uint32_t total;
+        const uint64_t pos = t0 + tile_rank(c, wcount, &total);
+        if (!c || pos < first || pos - first >= max_out) continue;
+        const uint64_t j = pos - first;
+        const uint4 *k = reinterpret_cast<const uint4 *>(key + slot * W); // the key array is 16-byte aligned, W is even
+        if (vec) {
+            for (int q = 0; q < W / 2; q++) reinterpret_cast<uint4 *>(out_dig + j * W)[q] = k[q];
+        } else {
+            for (int q = 0; q < W / 2; q++) {
+                const uint4 v = k[q];
+                out_dig[j * W + 2 * q] = (uint64_t)v.x | (uint64_t)v.y << 32;
+                out_dig[j * W + 2 * q + 1] = (uint64_t)v.z | (uint64_t)v.w << 32;
+            }
+        }
+        out_val[j] = value[slot];
+    }
+    if (d_n && blockIdx.x == 0 && threadIdx.x == 0) *d_n = offs[ntiles];
+}
+
+// Rehash into an empty table (cw_dedupe_resize): one lane per old slot.  All keys are distinct and nothing reads keys while this
+// runs, so a committed entry walks from its new home slot with one agent-scope CAS EMPTY -> COMMITTED per step until it claims a
+// slot, then stores key and value: no PENDING phase, no key compares.  Bounded by the new table's size.
+template <int W>
+__global__ void __launch_bounds__(kThreads)
+dedupe_rehash_kernel(const uint64_t *__restrict__ old_state, const uint64_t *__restrict__ old_value, const uint64_t *__restrict__ old_key,
+                     uint64_t old_cap, uint64_t *__restrict__ state, uint64_t *__restrict__ value, uint64_t *__restrict__ key, uint64_t mask,
+                     unsigned long long *__restrict__ err)
+{
+    for (uint64_t o = (uint64_t)blockIdx.x * kThreads + threadIdx.x; o < old_cap; o += (uint64_t)gridDim.x * kThreads) {
+        if (old_state[o] != kCommitted) continue;
+        uint64_t d[W];
+        for (int w = 0; w < W; w++) d[w] = old_key[o * W + w];
+        uint64_t slot = fold(d) & mask, step = 0;
+        for (; step <= mask; step++, slot = (slot + 1) & mask) {
+            uint64_t old = kEmpty;
+            __hip_atomic_compare_exchange_strong(state + slot, &old, kCommitted, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (old == kEmpty) break;
+        }
+        if (step > mask) { *err = 1ull; continue; }
+        for (int w = 0; w < W; w++) key[slot * W + w] = d[w];
+        value[slot] = old_value[o];
+    }
+}
+
 unsigned grid_of(uint32_t n) { return (n + kThreads - 1) / kThreads; }
+// grid-stride kernels over `tiles` tiles of kThreads slots
+unsigned grid_stride_of(uint64_t tiles) { return (unsigned)(tiles < (1u << 20) ? tiles : (1u << 20)); }
 
 } // namespace
 
@@ -189,16 +321,18 @@ hipError_t dedupe_probe_launch(unsigned words, const uint64_t *dig, uint32_t n, 
     return hipGetLastError();
 }
 
-hipError_t dedupe_resolve_launch(unsigned words, const uint64_t *dig, uint32_t n, uint64_t base, const uint32_t *min_idx, uint64_t *state,
-                                 uint64_t *value, uint64_t *key, const uint64_t *rec, uint64_t *ref, uint32_t *flags, hipStream_t s)
+hipError_t dedupe_resolve_launch(unsigned words, const uint64_t *dig, uint32_t n, uint64_t base, const uint64_t *values, const uint32_t *min_idx,
+                                 uint64_t *state, uint64_t *value, uint64_t *key, const uint64_t *rec, uint64_t *ref, uint32_t *flags, hipStream_t s)
 {
     const dim3 g(grid_of(n)), b(kThreads);
+#define CW_RESOLVE(W, V) hipLaunchKernelGGL((dedupe_resolve_kernel<W, V>), g, b, 0, s, dig, n, base, values, min_idx, state, value, key, rec, ref, flags)
     switch (words) {
-    case 2: hipLaunchKernelGGL(dedupe_resolve_kernel<2>, g, b, 0, s, dig, n, base, min_idx, state, value, key, rec, ref, flags); break;
-    case 4: hipLaunchKernelGGL(dedupe_resolve_kernel<4>, g, b, 0, s, dig, n, base, min_idx, state, value, key, rec, ref, flags); break;
-    case 8: hipLaunchKernelGGL(dedupe_resolve_kernel<8>, g, b, 0, s, dig, n, base, min_idx, state, value, key, rec, ref, flags); break;
+    case 2: if (values) CW_RESOLVE(2, true); else CW_RESOLVE(2, false); break;
+    case 4: if (values) CW_RESOLVE(4, true); else CW_RESOLVE(4, false); break;
+    case 8: if (values) CW_RESOLVE(8, true); else CW_RESOLVE(8, false); break;
     default: return hipErrorInvalidValue;
     }
+#undef CW_RESOLVE
     return hipGetLastError();
 }
 
@@ -218,6 +352,62 @@ hipError_t dedupe_gather_launch(const uint8_t *src, size_t block_bytes, size_t s
     const size_t grid = n_new < 65536 ? n_new : 65536;
     hipLaunchKernelGGL(dedupe_gather_kernel, dim3((unsigned)grid), dim3(kThreads), 0, s, src, block_bytes, src_stride, new_idx, n_new,
                        dst, vec);
+    return hipGetLastError();
+}
+
+hipError_t dedupe_lookup_launch(unsigned words, const uint64_t *dig, uint32_t n, const uint64_t *state, const uint64_t *value, const uint64_t *key,
+                                uint64_t mask, uint64_t *ref, uint64_t *n_found, unsigned long long *err, hipStream_t s)
+{
+    hipError_t e = hipMemsetAsync(n_found, 0, sizeof(uint64_t), s);
+    if (e != hipSuccess) return e;
+    const dim3 g(grid_of(n)), b(kThreads);
+    unsigned long long *nf = reinterpret_cast<unsigned long long *>(n_found);
+    switch (words) {
+    case 2: hipLaunchKernelGGL(dedupe_lookup_kernel<2>, g, b, 0, s, dig, n, state, value, key, mask, ref, nf, err); break;
+    case 4: hipLaunchKernelGGL(dedupe_lookup_kernel<4>, g, b, 0, s, dig, n, state, value, key, mask, ref, nf, err); break;
+    case 8: hipLaunchKernelGGL(dedupe_lookup_kernel<8>, g, b, 0, s, dig, n, state, value, key, mask, ref, nf, err); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+uint64_t dedupe_export_tiles(uint64_t cap) { return (cap + kThreads - 1) / kThreads; }
+
+hipError_t dedupe_export_scan_launch(const uint64_t *state, uint64_t cap, uint32_t *counts, uint64_t *offs, hipStream_t s)
+{
+    const uint64_t ntiles = dedupe_export_tiles(cap);
+    hipLaunchKernelGGL(dedupe_export_count_kernel, dim3(grid_stride_of(ntiles)), dim3(kThreads), 0, s, state, cap, ntiles, counts);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? pack_launch(nullptr, 0, counts, ntiles, nullptr, offs, s) : e;
+}
+
+hipError_t dedupe_export_scatter_launch(unsigned words, const uint64_t *state, const uint64_t *value, const uint64_t *key, uint64_t cap,
+                                        const uint64_t *offs, uint64_t first, uint64_t max_out, uint64_t *out_dig, uint64_t *out_val, uint64_t *d_n,
+                                        hipStream_t s)
+{
+    const uint64_t ntiles = dedupe_export_tiles(cap);
+    const dim3 g(grid_stride_of(ntiles)), b(kThreads);
+    const unsigned long long *off = reinterpret_cast<const unsigned long long *>(offs);
+    const bool vec = (reinterpret_cast<uintptr_t>(out_dig) & 15) == 0;
+    switch (words) {
+    case 2: hipLaunchKernelGGL(dedupe_export_scatter_kernel<2>, g, b, 0, s, state, value, key, cap, ntiles, off, first, max_out, out_dig, out_val, d_n, vec); break;
+    case 4: hipLaunchKernelGGL(dedupe_export_scatter_kernel<4>, g, b, 0, s, state, value, key, cap, ntiles, off, first, max_out, out_dig, out_val, d_n, vec); break;
+    case 8: hipLaunchKernelGGL(dedupe_export_scatter_kernel<8>, g, b, 0, s, state, value, key, cap, ntiles, off, first, max_out, out_dig, out_val, d_n, vec); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t dedupe_rehash_launch(unsigned words, const uint64_t *old_state, const uint64_t *old_value, const uint64_t *old_key, uint64_t old_cap,
+                                uint64_t *state, uint64_t *value, uint64_t *key, uint64_t mask, unsigned long long *err, hipStream_t s)
+{
+    const dim3 g(grid_stride_of(dedupe_export_tiles(old_cap))), b(kThreads);
+    switch (words) {
+    case 2: hipLaunchKernelGGL(dedupe_rehash_kernel<2>, g, b, 0, s, old_state, old_value, old_key, old_cap, state, value, key, mask, err); break;
+    case 4: hipLaunchKernelGGL(dedupe_rehash_kernel<4>, g, b, 0, s, old_state, old_value, old_key, old_cap, state, value, key, mask, err); break;
+    case 8: hipLaunchKernelGGL(dedupe_rehash_kernel<8>, g, b, 0, s, old_state, old_value, old_key, old_cap, state, value, key, mask, err); break;
+    default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

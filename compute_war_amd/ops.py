@@ -301,7 +301,11 @@ class DedupeIndex:
 
     ``dev_dedupe`` is the batched lookup-or-insert, ``dev_hash_dedupe_compress`` hashes, dedupes and compresses only the
     new blocks.  Both take raw device pointers and a stream handle like the other ``dev_*`` functions; a full index raises
-    ``CwError`` with code ``CW_ERR_NOMEM`` (-5) and is left unchanged."""
+    ``CwError`` with code ``CW_ERR_NOMEM`` (-5) and is left unchanged: ``resize`` it and repeat the call.  ``dev_lookup`` only
+    reads, ``dev_insert`` carries explicit values, ``dev_export`` / ``export`` / ``import_`` / ``save`` / ``load`` move the
+    (digest, value) pairs out and in."""
+
+    MISS = 2 ** 64 - 1  # CW_DEDUPE_MISS
 
     def __init__(self, hash_alg, max_entries: int):
         self.hash_alg = _hash_id(hash_alg)
@@ -346,6 +350,74 @@ class DedupeIndex:
             err.nchunks = int(k.value)
             raise err
         return int(k.value)
+
+    def dev_lookup(self, d_digests: int, n: int, d_ref: int, d_n_found: int, stream: int = 0) -> None:
+        """Read-only: ref[i] = the stored value of digest i or ``MISS``; *d_n_found = hits (u64).  The index is unchanged."""
+        check(lib().cw_dev_dedupe_lookup(self._x(), d_digests, n, d_ref, d_n_found, stream))
+
+    def dev_insert(self, d_digests: int, d_values: int, n: int, d_ref: int, d_new_idx: int, d_n_new: int, stream: int = 0) -> None:
+        """``dev_dedupe`` with explicit values: block i carries values[i] (u64); the lowest index of a digest wins, stored entries keep
+        their value."""
+        check(lib().cw_dev_dedupe_insert(self._x(), d_digests, d_values, n, d_ref, d_new_idx, d_n_new, stream))
+
+    def dev_export(self, d_digests: int, d_values: int, max_out: int, d_n: int, stream: int = 0) -> None:
+        """The entries as parallel device arrays: *d_n = the entry count (u64), min(*d_n, max_out) pairs written."""
+        check(lib().cw_dev_dedupe_export(self._x(), d_digests, d_values, max_out, d_n, stream))
+
+    def resize(self, max_entries: int) -> None:
+        """Rebuild the table for ``max_entries`` (synchronous; at least ``count()``).  Every lookup answers as before."""
+        check(lib().cw_dedupe_resize(self._x(), max_entries))
+        n = C.c_size_t(0)
+        check(lib().cw_dedupe_max_entries(self._x(), C.byref(n)))
+        self.max_entries = int(n.value)
+
+    def set_stage_entries(self, entries: int) -> None:
+        """Pairs per piece of ``export`` / ``import_`` (0 = the default); for tests."""
+        check(lib().cw_dedupe_set_stage_entries(self._x(), entries))
+
+    def export(self):
+        """Every entry on the host: (digests uint8[n, digest_bytes], values uint64[n]), in an unspecified order."""
+        db = digest_bytes(self.hash_alg)
+        n = self.count()
+        while True:
+            dig, val, got = np.empty((n, db), np.uint8), np.empty(n, np.uint64), C.c_size_t(0)
+            check(lib().cw_dedupe_export(self._x(), dig.ctypes.data, val.ctypes.data, n, C.byref(got)))
+            if got.value <= n:  # (another thread may have inserted in between)
+                return dig[:got.value], val[:got.value]
+            n = int(got.value)
+
+    def import_(self, digests, values) -> int:
+        """Insert the pairs in order (entries already stored keep their value); returns how many were new."""
+        db = digest_bytes(self.hash_alg)
+        dig = np.ascontiguousarray(digests, dtype=np.uint8).reshape(-1, db)
+        val = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1)
+        if len(dig) != len(val):
+            raise ValueError(f"{len(dig)} digests, {len(val)} values")
+        k = C.c_size_t(0)
+        check(lib().cw_dedupe_import(self._x(), dig.ctypes.data, val.ctypes.data, len(val), C.byref(k)))
+        return int(k.value)
+
+    def save(self, path) -> None:
+        """Snapshot to ``path`` (numpy.savez): hash algorithm id, max_entries, digests, values."""
+        dig, val = self.export()
+        with open(path, "wb") as f:
+            np.savez(f, hash_alg=np.int64(self.hash_alg), max_entries=np.int64(self.max_entries), digests=dig, values=val)
+
+    @classmethod
+    def load(cls, path, max_entries: int | None = None) -> "DedupeIndex":
+        """A new index from a snapshot; ``max_entries`` defaults to the saved one and must hold every saved entry."""
+        with np.load(path) as z:
+            alg, saved, dig, val = int(z["hash_alg"]), int(z["max_entries"]), z["digests"], z["values"]
+        want = saved if max_entries is None else max_entries
+        if want < len(val):
+            raise _lib.CwError(-2, f"max_entries {want} < {len(val)} saved entries")
+        idx = cls(alg, want)
+        try:
+            idx.import_(dig, val)
+        except Exception:
+            idx.close()
+            raise
+        return idx
 
     def count(self) -> int:
         """Entries in the index (waits for the index's last call)."""

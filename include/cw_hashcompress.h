@@ -191,8 +191,8 @@ int cw_dev_sum_sizes(const uint32_t *d_sizes, size_t nblocks, uint32_t raw_bytes
 /* ---- dedupe index: a device-resident fingerprint index next to the fingerprint engine ------------
  * The reference has no counterpart: HashAndCompress.cpp computes each block's digest and discards it (:257).
  * An index belongs to one hash algorithm and stores FULL digests, each with a 64-bit value.  Open addressing with
- * linear probing over a power of two >= 2 * max_entries slots, allocated once on the calling thread's device:
- * 20 + digest bytes per slot (Skein-512 84 B, SHA-256 52 B, Skein-256-128 36 B; 16 Mi Skein-512 entries = 2.7 GiB),
+ * linear probing over a power of two >= 2 * max_entries slots, allocated on the calling thread's device (once, unless
+ * cw_dedupe_resize rebuilds it): 20 + digest bytes per slot (Skein-512 84 B, SHA-256 52 B, Skein-256-128 36 B; 16 Mi Skein-512 entries = 2.7 GiB),
  * plus per-call scratch of 20 B per block (and the fused call's gather buffer, n_new * block_bytes).
  * Calls on one index are serialised on the device whatever stream they come on (each waits for the previous call). */
 typedef struct cw_dedupe cw_dedupe_t;
@@ -217,6 +217,48 @@ int cw_dev_hash_dedupe_compress(cw_dedupe_t *x, int comp_alg, const void *d_src,
                                 size_t src_stride, size_t nblocks, uint64_t base, void *d_digests,
                                 uint64_t *d_ref, uint32_t *d_new_idx, void *d_dst, size_t dst_stride,
                                 uint32_t *d_sizes, size_t *n_new, void *stream);
+
+/* ---- the index's lifecycle: read-only lookup, explicit values, export / import, resize ----
+ * The cw_dev_* calls below follow cw_dev_dedupe's rules: all pointers device memory, queued on `stream` and not
+ * synchronised, serialised with every other call on the index; a wrong device, a NULL pointer, a d_digests that is not
+ * 8-byte aligned or n > 2^32 - 256 gives CW_ERR_BAD_ARG with nothing launched; n == 0 is a no-op.                    */
+#define CW_DEDUPE_MISS UINT64_MAX
+/* Read-only query: d_ref[i] = the stored value of digest i, or CW_DEDUPE_MISS when the index does not hold it;
+ * *d_n_found (u64) = the number of hits.  The index is unchanged and nothing is counted against max_entries, so it works
+ * on a full index.                                                                                                    */
+int cw_dev_dedupe_lookup(cw_dedupe_t *x, const void *d_digests, size_t n, uint64_t *d_ref,
+                         uint64_t *d_n_found, void *stream);
+/* cw_dev_dedupe with explicit values: block i carries d_values[i] instead of base + i.  A digest that an earlier call
+ * inserted keeps its stored value; within the batch the lowest index j with that digest wins, d_ref[i] = the winning
+ * value, d_new_idx lists the inserted blocks in ascending order.  Deterministic.  CW_ERR_NOMEM (index unchanged) when
+ * count + n > max_entries.  The value UINT64_MAX is reserved: an entry stored with it cannot be told from a miss by
+ * cw_dev_dedupe_lookup.                                                                                               */
+int cw_dev_dedupe_insert(cw_dedupe_t *x, const void *d_digests, const uint64_t *d_values, size_t n,
+                         uint64_t *d_ref, uint32_t *d_new_idx, uint64_t *d_n_new, void *stream);
+/* The entries as parallel arrays: d_digests[j] (cw_digest_bytes() each) with d_values[j].  *d_n (u64) = the entry count of
+ * the index; exactly min(*d_n, max_out) pairs are written and nothing beyond them, so *d_n > max_out means truncated
+ * (max_out == 0 just counts; the arrays may be NULL then).  The order is unspecified, but two exports of an unchanged
+ * index give the same bytes.  16-byte stores when d_digests is 16-byte aligned.  Scratch of the index: 12 B per 256
+ * slots.                                                                                                              */
+int cw_dev_dedupe_export(cw_dedupe_t *x, void *d_digests, uint64_t *d_values, size_t max_out, uint64_t *d_n,
+                         void *stream);
+/* Host forms, synchronous, host buffers: staged through device buffers of the index in pieces of 2^20 pairs.
+ * export: *n = the entry count, min(*n, max_out) pairs written.  import: cw_dev_dedupe_insert of the n pairs in order,
+ * *n_inserted = how many were new; the whole n is admitted up front, CW_ERR_NOMEM (index unchanged) when
+ * count + n > max_entries.  n may exceed 2^32 - 256.                                                                   */
+int cw_dedupe_export(cw_dedupe_t *x, void *digests, uint64_t *values, size_t max_out, size_t *n);
+int cw_dedupe_import(cw_dedupe_t *x, const void *digests, const uint64_t *values, size_t n, size_t *n_inserted);
+/* CW_TESTING: pairs per piece of the two host forms (0 = the default, 2^20; at most 2^32 - 256) */
+int cw_dedupe_set_stage_entries(cw_dedupe_t *x, size_t entries);
+/* Synchronous: waits for the index's last call, allocates a table for new_max_entries (slots as cw_dedupe_create
+ * computes them), rehashes every entry into it on the device and frees the old table; the handle stays the same.  Old and
+ * new table are live at once during the call: (20 + digest bytes) x (old slots + new slots).  When the slot count does not
+ * change only max_entries does.  CW_ERR_BAD_ARG when new_max_entries is 0, above 2^40 or below the entry count;
+ * CW_ERR_NOMEM when the new table cannot be allocated -- the index is then unchanged and usable.  Every lookup answers as
+ * before; the order of cw_dev_dedupe_export may differ.  The pattern for a full index: on CW_ERR_NOMEM from an inserting
+ * call, resize, then repeat the call.                                                                                 */
+int cw_dedupe_resize(cw_dedupe_t *x, size_t new_max_entries);
+int cw_dedupe_max_entries(cw_dedupe_t *x, size_t *max_entries);
 
 /* ---- content-defined chunking ---------------------------------------------------------------
  * Cuts a byte stream where its content says, so that an insertion or a deletion moves only the cuts near it and the
@@ -324,8 +366,8 @@ int cw_dev_decompress_chunks(int comp_alg, const void *d_comp, const uint64_t *d
  * stays on the device, so cw_dev_pack_chunks(comp_alg, d_dst, d_offsets, d_new_idx, d_n_new, ...) can be queued behind it
  * without another synchronise.  Every output equals what those five calls give.  *nchunks = the chunk count (final = 0:
  * d_offsets[*nchunks] = bytes consumed).  dst_bytes >= cw_chunk_slots_bytes(comp_alg, nbytes, max_offsets - 1).
- * CW_ERR_NOMEM when count + *nchunks > max_entries: offsets and digests are written and *nchunks is returned (retry with
- * a larger index), nothing is inserted, nothing compressed.  CW_ERR_BAD_ARG, at the same point, when base + *nchunks wraps.
+ * CW_ERR_NOMEM when count + *nchunks > max_entries: offsets and digests are written and *nchunks is returned (cw_dedupe_resize,
+ * then call again), nothing is inserted, nothing compressed.  CW_ERR_BAD_ARG, at the same point, when base + *nchunks wraps.
  * Calls on one index are serialised as cw_dev_dedupe's.                                                               */
 int cw_dev_cdc_dedupe_compress(cw_dedupe_t *x, const cw_cdc_params *p, int comp_alg,
                                const void *d_src, size_t nbytes, int final, uint64_t base,
