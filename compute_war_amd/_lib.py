@@ -30,7 +30,7 @@ ABI_SYMBOLS = [
     "cw_dedupe_set_stage_entries", "cw_dedupe_resize", "cw_dedupe_max_entries",
     "cw_cdc_default_params", "cw_dev_cdc", "cw_dev_hash_chunks", "cw_cdc_hash",
     "cw_chunk_slot_offset", "cw_chunk_slots_bytes", "cw_dev_compress_chunks", "cw_dev_pack_chunks", "cw_dev_decompress_chunks",
-    "cw_dev_cdc_dedupe_compress",
+    "cw_dev_cdc_dedupe_compress", "cw_dev_store_chunks", "cw_dev_restore_chunks",
     "cw_shard_range", "cw_mgpu_create", "cw_mgpu_destroy", "cw_mgpu_ndev", "cw_mgpu_device", "cw_mgpu_last_error", "cw_mgpu_gather",
 ]
 
@@ -147,6 +147,8 @@ def lib() -> C.CDLL:
         "cw_dev_decompress_chunks": ([C.c_int, vp, vp, vp, vp, sz, vp, sz, u32p, vp], C.c_int),
         "cw_dev_cdc_dedupe_compress": ([vp, vp, C.c_int, vp, sz, C.c_int, C.c_uint64, vp, sz, vp, vp, vp, vp, vp, vp, sz, u32p, vp, vp],
                                        C.c_int),
+        "cw_dev_store_chunks": ([C.c_int, vp, sz, vp, vp, sz, vp, vp, vp, u32p, C.c_uint64, vp, sz, vp, vp, C.c_uint64, sz, vp, vp], C.c_int),
+        "cw_dev_restore_chunks": ([C.c_int, vp, sz, vp, C.c_uint64, sz, vp, vp, vp, sz, vp, sz, u32p, vp], C.c_int),
         "cw_shard_range": ([sz, C.c_int, C.c_int, vp, vp], None),
         "cw_mgpu_create": ([vp, C.c_int], vp), "cw_mgpu_destroy": ([vp], None), "cw_mgpu_ndev": ([vp], C.c_int),
         "cw_mgpu_device": ([vp, C.c_int], C.c_int), "cw_mgpu_last_error": ([], C.c_char_p),

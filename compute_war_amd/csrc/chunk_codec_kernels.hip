@@ -27,32 +27,10 @@ namespace {
 
 using namespace lane;
 
-constexpr uint32_t kMaxChunk = 65536;
+constexpr uint32_t kMaxChunk = kMaxChunkBytes;
 constexpr uint32_t kLz4Slots = 1u << 13, kLzfSlots = 1u << 16; // u32 entries: 32 KiB / 256 KiB per lane
 
-__device__ __forceinline__ uint64_t umin64(uint64_t a, uint64_t b) { return a < b ? a : b; }
-
-// ---- the positions of a call and the chunk behind each -------------------------------------------------------------------
-struct ChunkList {
-    const uint64_t *offsets, *d_nchunks;
-    const uint32_t *sel;      // NULL: position j is chunk j
-    const uint64_t *d_nsel;
-    uint64_t max_chunks, src_bytes;
-
-    __device__ __forceinline__ uint64_t nchunks() const { return umin64(*d_nchunks, max_chunks); }
-    __device__ __forceinline__ uint64_t npos() const { return sel ? umin64(*d_nsel, max_chunks) : nchunks(); }
-    // chunk of position j and its length; 0 = out of contract (then nothing of it may be loaded or stored)
-    __device__ __forceinline__ uint32_t chunk(uint64_t j, uint64_t count, uint64_t &i, uint64_t &start) const
-    {
-        i = sel ? sel[j] : j;
-        start = 0;
-        if (i >= count) return 0;
-        const uint64_t s = offsets[i], e = offsets[i + 1];
-        if (!(s < e && e <= src_bytes && e - s <= kMaxChunk)) return 0;
-        start = s;
-        return (uint32_t)(e - s);
-    }
-};
+// (the positions of a call and the chunk behind each: ChunkList, cw_device.h)
 
 // ---- order: positions by length, longest first (counting sort over 64-byte classes; out-of-contract chunks last) -----------
 constexpr unsigned kBuckets = 1025, kSortThreads = 256, kSortPer = 8, kSortTile = kSortThreads * kSortPer;

@@ -1435,6 +1435,50 @@ int cw_dev_decompress_chunks(int comp_alg, const void *d_comp, const uint64_t *d
     return CW_OK;
 }
 
+// ---- the chunk store (kernels: restore_kernels.hip; semantics: the header) -------------------------------------------------
+static_assert(sizeof(cw_chunk_loc) == 16, "cw_chunk_loc is one 16-byte store");
+
+int cw_dev_store_chunks(int comp_alg, const void *d_src, size_t src_bytes, const uint64_t *d_offsets, const uint64_t *d_nchunks,
+                        size_t max_chunks, const uint32_t *d_sel, const uint64_t *d_nsel, const void *d_slots, const uint32_t *d_sizes,
+                        uint64_t base, void *d_store, size_t store_bytes, uint64_t *d_used, cw_chunk_loc *d_dir, uint64_t dir_base,
+                        size_t dir_entries, uint64_t *d_result, void *stream)
+{
+    if (comp_alg != CW_COMP_LZ4 && comp_alg != CW_COMP_LZF) return fail(CW_ERR_BAD_ARG, "unknown compression algorithm %d", comp_alg);
+    if (max_chunks > kMaxChunks) return fail(CW_ERR_BAD_ARG, "max_chunks %zu > 2^32 - 256", max_chunks);
+    if (!d_offsets || !d_nchunks || !d_slots || !d_sizes || !d_used || !d_dir || !d_result || (src_bytes && !d_src) || (store_bytes && !d_store) ||
+        !d_sel != !d_nsel)
+        return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    if (dir_entries == 0) return fail(CW_ERR_BAD_ARG, "dir_entries is 0");
+    if ((uintptr_t)d_dir & 15) return fail(CW_ERR_BAD_ARG, "d_dir is not 16-byte aligned");
+    if (((uintptr_t)d_used | (uintptr_t)d_result) & 7) return fail(CW_ERR_BAD_ARG, "d_used / d_result not 8-byte aligned");
+    int rc = ensure_init();
+    if (rc != CW_OK) return rc;
+    const hipError_t e = cw::chunk_store_launch(comp_alg == CW_COMP_LZF, (const uint8_t *)d_src, src_bytes, d_offsets, d_nchunks, max_chunks, d_sel,
+                                                d_nsel, (const uint8_t *)d_slots, d_sizes, base, (uint8_t *)d_store, store_bytes, d_used, d_dir,
+                                                dir_base, dir_entries, d_result, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? CW_ERR_NOMEM : CW_ERR_HIP, "store chunks launch: %s", hipGetErrorString(e));
+    return CW_OK;
+}
+
+int cw_dev_restore_chunks(int comp_alg, const void *d_store, size_t store_bytes, const cw_chunk_loc *d_dir, uint64_t dir_base,
+                          size_t dir_entries, const uint64_t *d_ref, const uint64_t *d_raw_offsets, const uint64_t *d_count, size_t max_count,
+                          void *d_dst, size_t dst_bytes, uint32_t *d_status, void *stream)
+{
+    if (comp_alg != CW_COMP_LZ4 && comp_alg != CW_COMP_LZF) return fail(CW_ERR_BAD_ARG, "unknown compression algorithm %d", comp_alg);
+    if (max_count > kMaxChunks) return fail(CW_ERR_BAD_ARG, "max_count %zu > 2^32 - 256", max_count);
+    if (!d_dir || !d_ref || !d_raw_offsets || !d_count || !d_status || (store_bytes && !d_store) || (dst_bytes && !d_dst))
+        return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    if (dir_entries == 0) return fail(CW_ERR_BAD_ARG, "dir_entries is 0");
+    if ((uintptr_t)d_dir & 15) return fail(CW_ERR_BAD_ARG, "d_dir is not 16-byte aligned");
+    int rc = ensure_init();
+    if (rc != CW_OK) return rc;
+    ProfScope prof(PROF_CODEC, (hipStream_t)stream);
+    const hipError_t e = cw::chunk_restore_launch(comp_alg == CW_COMP_LZF, (const uint8_t *)d_store, store_bytes, d_dir, dir_base, dir_entries, d_ref,
+                                                  d_raw_offsets, d_count, max_count, (uint8_t *)d_dst, dst_bytes, d_status, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(CW_ERR_HIP, "restore chunks launch: %s", hipGetErrorString(e));
+    return CW_OK;
+}
+
 // Pieces of at most kMaxChunkBytes: each piece is chunked with final = 0 (the last with final = 1); the bytes after the last
 // cut of a piece -- fewer than max_size -- are copied to the front of the next piece's buffer.
 int cw_cdc_hash(const cw_cdc_params *p, int hash_alg, const void *src, size_t nbytes, uint64_t *offsets, size_t max_offsets,

@@ -180,6 +180,30 @@ __host__ __device__ inline uint64_t chunk_slot_offset(bool lz4, uint64_t o, uint
 {
     return lz4 ? (o + o / 255 + 32 * i) & ~(uint64_t)15 : o;
 }
+__device__ __forceinline__ uint64_t umin64(uint64_t a, uint64_t b) { return a < b ? a : b; }
+constexpr uint32_t kMaxChunkBytes = 65536; // CW_MAX_BLOCK_BYTES
+// The positions of a call over chunks and the chunk behind each (cw_dev_compress_chunks' arguments; cw_dev_store_chunks reads the
+// same list behind it).
+struct ChunkList {
+    const uint64_t *offsets, *d_nchunks;
+    const uint32_t *sel;      // NULL: position j is chunk j
+    const uint64_t *d_nsel;
+    uint64_t max_chunks, src_bytes;
+
+    __device__ __forceinline__ uint64_t nchunks() const { return umin64(*d_nchunks, max_chunks); }
+    __device__ __forceinline__ uint64_t npos() const { return sel ? umin64(*d_nsel, max_chunks) : nchunks(); }
+    // chunk of position j and its length; 0 = out of contract (then nothing of it may be loaded or stored)
+    __device__ __forceinline__ uint32_t chunk(uint64_t j, uint64_t count, uint64_t &i, uint64_t &start) const
+    {
+        i = sel ? sel[j] : j;
+        start = 0;
+        if (i >= count) return 0;
+        const uint64_t s = offsets[i], e = offsets[i + 1];
+        if (!(s < e && e <= src_bytes && e - s <= kMaxChunkBytes)) return 0;
+        start = s;
+        return (uint32_t)(e - s);
+    }
+};
 // bytes of table per lane of the chunk parsers (the workspace holds up to 131,072 / 65,536 of them, LZ4 / LZF)
 size_t chunk_lane_table_bytes(int lzf);
 // sel == NULL: every chunk i < min(*d_nchunks, max_chunks); else the chunks sel[j], j < min(*d_nsel, max_chunks); sizes per position
@@ -192,6 +216,15 @@ hipError_t chunk_decompress_launch(int lzf, const uint8_t *comp, const uint64_t 
 // pack_launch for chunk slots and a count on the device: packed_offsets[0..n], n = min(*d_count, max_count)
 hipError_t chunk_pack_launch(int lzf, const uint8_t *slots, const uint64_t *offsets, const uint32_t *sel, const uint64_t *d_count,
                              size_t max_count, const uint32_t *sizes, uint8_t *packed, uint64_t *packed_offsets, hipStream_t stream);
+
+// the chunk store (restore_kernels.hip; semantics: the public header).  dir: cw_chunk_loc entries, 16-byte aligned
+hipError_t chunk_store_launch(int lzf, const uint8_t *src, size_t src_bytes, const uint64_t *offsets, const uint64_t *d_nchunks, size_t max_chunks,
+                              const uint32_t *sel, const uint64_t *d_nsel, const uint8_t *slots, const uint32_t *sizes, uint64_t base,
+                              uint8_t *store, size_t store_bytes, uint64_t *d_used, void *dir, uint64_t dir_base, size_t dir_entries,
+                              uint64_t *result, hipStream_t stream);
+hipError_t chunk_restore_launch(int lzf, const uint8_t *store, size_t store_bytes, const void *dir, uint64_t dir_base, size_t dir_entries,
+                                const uint64_t *ref, const uint64_t *raw_offsets, const uint64_t *d_count, size_t max_count, uint8_t *dst,
+                                size_t dst_bytes, uint32_t *status, hipStream_t stream);
 
 hipError_t sum_sizes_launch(const uint32_t *sizes, size_t n, uint32_t raw_bytes, uint64_t *totals, hipStream_t stream);
 hipError_t gen_random_launch(uint64_t seed, uint64_t first_block, size_t nblocks, size_t block_bytes, uint8_t *dst,

@@ -597,3 +597,166 @@ def dev_decompress_chunks(comp_alg, d_comp: int, d_comp_offsets: int, d_raw_offs
     """Decode position j's compressed extent into its raw extent of d_dst; d_status[j] = 0 iff well formed and exactly that long."""
     check(lib().cw_dev_decompress_chunks(_comp_id(comp_alg), d_comp, d_comp_offsets, d_raw_offsets, d_count, max_count, d_dst, dst_bytes,
                                          d_status, stream))
+
+
+# ---- the chunk store (cw_dev_store_chunks / cw_dev_restore_chunks, DESIGN.md section 14) ---------------------------------
+class ChunkLoc(C.Structure):
+    """cw_chunk_loc: where a chunk lies in the store.  All zero = no such chunk."""
+    _fields_ = [("pos", C.c_uint64), ("stored", C.c_uint32), ("raw", C.c_uint32)]
+    RAW = 0x80000000  # CW_CHUNK_RAW: stored uncompressed; bits 0..16 of ``raw`` are the chunk's length
+
+
+def dev_store_chunks(comp_alg, d_src: int, src_bytes: int, d_offsets: int, d_nchunks: int, max_chunks: int, d_slots: int, d_sizes: int,
+                     base: int, d_store: int, store_bytes: int, d_used: int, d_dir: int, dir_base: int, dir_entries: int, d_result: int,
+                     stream: int = 0, d_sel: int = 0, d_nsel: int = 0) -> None:
+    """Append the chunks of one dev_compress_chunks / dev_cdc_dedupe_compress call (same arguments, d_slots = its d_dst) to the
+    store (d_store, *d_used, d_dir); chunk i gets the entry d_dir[base + i - dir_base].  d_result[0] = 0, or 1 (does not fit) /
+    2 (an entry outside the directory) with nothing changed; d_result[1] = the bytes the call needs.  Not synchronised."""
+    check(lib().cw_dev_store_chunks(_comp_id(comp_alg), d_src or None, src_bytes, d_offsets, d_nchunks, max_chunks, d_sel or None,
+                                    d_nsel or None, d_slots, d_sizes, base, d_store or None, store_bytes, d_used, d_dir, dir_base,
+                                    dir_entries, d_result, stream))
+
+
+def dev_restore_chunks(comp_alg, d_store: int, store_bytes: int, d_dir: int, dir_base: int, dir_entries: int, d_ref: int,
+                       d_raw_offsets: int, d_count: int, max_count: int, d_dst: int, dst_bytes: int, d_status: int, stream: int = 0) -> None:
+    """Position j < min(*d_count, max_count): the chunk of value d_ref[j] into d_dst[raw_offsets[j] .. raw_offsets[j+1]);
+    d_status[j] = 0 restored, 1 stored bytes malformed, 2 refused (no such entry, or it does not match the extent or the store)."""
+    check(lib().cw_dev_restore_chunks(_comp_id(comp_alg), d_store or None, store_bytes, d_dir, dir_base, dir_entries, d_ref,
+                                      d_raw_offsets, d_count, max_count, d_dst or None, dst_bytes, d_status, stream))
+
+
+class Recipe:
+    """What restores one ingested stream: refs[j] = the value of chunk j's first occurrence, offsets[0..k] = its cuts."""
+
+    def __init__(self, refs, offsets):
+        self.refs = np.ascontiguousarray(refs, dtype=np.uint64)
+        self.offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if len(self.offsets) != len(self.refs) + 1:
+            raise ValueError(f"{len(self.refs)} refs need {len(self.refs) + 1} offsets, not {len(self.offsets)}")
+
+    @property
+    def nbytes(self) -> int:
+        return int(self.offsets[-1] - self.offsets[0])
+
+
+class ChunkStore:
+    """A dedupe index with the bytes behind it: ``ingest`` chunks, dedupes and compresses a buffer and appends its new chunks to a
+    device-resident store, ``restore`` turns a recipe back into bytes.  The store is three torch buffers this object owns (bytes,
+    cursor, directory: the caller-owned triple of cw_dev_store_chunks); chunk values count up from ``dir_base`` over the ingests.
+    One device call per ingest: the whole buffer has to fit on the device next to its slots."""
+
+    def __init__(self, index: DedupeIndex, comp_alg, params: CdcParams, store_bytes: int, dir_entries: int, dir_base: int = 0):
+        import torch
+        self.index, self.comp_alg, self.params = index, _comp_id(comp_alg), params
+        self.store_bytes, self.dir_entries, self.dir_base = store_bytes, dir_entries, dir_base
+        self.base = dir_base
+        self.d_store = torch.zeros(max(store_bytes, 1), dtype=torch.uint8, device="cuda")
+        self.d_used = torch.zeros(1, dtype=torch.int64, device="cuda")
+        self.d_dir = torch.zeros(dir_entries * 2, dtype=torch.int64, device="cuda")  # 16 bytes per entry
+        torch.cuda.synchronize()
+
+    @staticmethod
+    def _stream() -> int:
+        import torch
+        return torch.cuda.current_stream().cuda_stream
+
+    def used(self) -> int:
+        return int(self.d_used.item())
+
+    def ingest(self, data) -> Recipe:
+        """Chunk, hash, dedupe and compress ``data`` in one device call, then append its new chunks.  Raises CwError (-5) when the
+        store or the directory cannot take them (``e.needed`` = the bytes the call wanted); the store is then unchanged."""
+        import torch
+        a = _np_u8(data)
+        n, s = a.size, self._stream()
+        src = torch.from_numpy(a.copy() if n else np.zeros(1, np.uint8)).cuda()
+        cap = self.params.max_offsets(n)
+        total = chunk_slots_bytes(self.comp_alg, n, cap - 1)
+        z = lambda k, dt: torch.zeros(k, dtype=dt, device="cuda")  # noqa: E731
+        off, k_dev, dig = z(cap, torch.int64), z(1, torch.int64), z(cap * digest_bytes(self.index.hash_alg), torch.uint8)
+        ref, new_idx, n_new = z(cap, torch.int64), z(cap, torch.int32), z(1, torch.int64)
+        slots, sizes, result = torch.empty(total, dtype=torch.uint8, device="cuda"), z(cap, torch.int32), z(2, torch.int64)
+        torch.cuda.synchronize()
+        k = self.index.dev_cdc_dedupe_compress(self.params, self.comp_alg, src.data_ptr(), n, True, self.base, off.data_ptr(), cap,
+                                               k_dev.data_ptr(), dig.data_ptr(), ref.data_ptr(), new_idx.data_ptr(), n_new.data_ptr(),
+                                               slots.data_ptr(), total, sizes.data_ptr(), s)
+        dev_store_chunks(self.comp_alg, src.data_ptr(), n, off.data_ptr(), k_dev.data_ptr(), cap - 1, slots.data_ptr(), sizes.data_ptr(),
+                         self.base, self.d_store.data_ptr(), self.store_bytes, self.d_used.data_ptr(), self.d_dir.data_ptr(), self.dir_base,
+                         self.dir_entries, result.data_ptr(), s, new_idx.data_ptr(), n_new.data_ptr())
+        torch.cuda.synchronize()
+        verdict, needed = (int(v) for v in result.cpu().numpy().view(np.uint64))
+        if verdict:
+            # the index holds the call's new chunks already, the store does not: the caller starts over or grows the store
+            err = _lib.CwError(-5, f"chunk store: {needed} bytes do not fit behind {self.used()} of {self.store_bytes}" if verdict == 1 else
+                               f"chunk store: values {self.base} .. {self.base + k} leave the directory [{self.dir_base}, "
+                               f"{self.dir_base + self.dir_entries})")
+            err.needed = needed
+            raise err
+        self.base += k
+        return Recipe(ref.cpu().numpy().view(np.uint64)[:k], off.cpu().numpy().view(np.uint64)[:k + 1])
+
+    def restore(self, recipe: Recipe, verify: bool = False) -> bytes:
+        """The bytes of an ingested stream.  Raises CwError (-2) unless every position restores.  verify: the restored chunks are
+        hashed again and looked up in the index, and every answer has to be the recipe's ref."""
+        import torch
+        k, n, s = len(recipe.refs), recipe.nbytes, self._stream()
+        raw = recipe.offsets - recipe.offsets[0]
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64).copy()).cuda()  # noqa: E731
+        d_ref, d_raw, d_count = up(recipe.refs if k else [0]), up(raw), up([k])
+        out = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
+        status = torch.zeros(max(k, 1), dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        dev_restore_chunks(self.comp_alg, self.d_store.data_ptr(), self.store_bytes, self.d_dir.data_ptr(), self.dir_base, self.dir_entries,
+                           d_ref.data_ptr(), d_raw.data_ptr(), d_count.data_ptr(), k, out.data_ptr(), n, status.data_ptr(), s)
+        if verify and k:
+            dig = torch.zeros(k * digest_bytes(self.index.hash_alg), dtype=torch.uint8, device="cuda")
+            found, n_found = torch.zeros(k, dtype=torch.int64, device="cuda"), torch.zeros(1, dtype=torch.int64, device="cuda")
+            torch.cuda.synchronize()  # (torch zeroed them on its own stream)
+            dev_hash_chunks(self.index.hash_alg, out.data_ptr(), n, d_raw.data_ptr(), d_count.data_ptr(), k, dig.data_ptr(), s)
+            self.index.dev_lookup(dig.data_ptr(), k, found.data_ptr(), n_found.data_ptr(), s)
+        torch.cuda.synchronize()
+        st = status.cpu().numpy()[:k]
+        if st.any():
+            j = int(np.nonzero(st)[0][0])
+            raise _lib.CwError(-2, f"chunk store: {int((st != 0).sum())} of {k} positions not restored; position {j} (ref "
+                                   f"{int(recipe.refs[j])}) has status {int(st[j])}")
+        if verify and k:
+            got = found.cpu().numpy().view(np.uint64)
+            bad = np.nonzero(got != recipe.refs)[0]
+            if len(bad):
+                raise _lib.CwError(-2, f"chunk store: verify failed at position {int(bad[0])}: the index answers {int(got[bad[0]])}, "
+                                       f"the recipe says {int(recipe.refs[bad[0]])} ({len(bad)} positions differ)")
+        return out.cpu().numpy()[:n].tobytes()
+
+    def save(self, path) -> None:
+        """One ``.npz``: the index's export, the store bytes [0, used), the directory, base and the parameters."""
+        dig, val = self.index.export()
+        p = self.params
+        gear = p._gear if getattr(p, "_gear", None) is not None else np.zeros(0, np.uint64)
+        with open(path, "wb") as f:
+            np.savez(f, hash_alg=np.int64(self.index.hash_alg), max_entries=np.int64(self.index.max_entries), digests=dig, values=val,
+                     comp_alg=np.int64(self.comp_alg), store=self.d_store[:self.used()].cpu().numpy(), store_bytes=np.int64(self.store_bytes),
+                     directory=self.d_dir.cpu().numpy(), dir_base=np.uint64(self.dir_base), base=np.uint64(self.base),
+                     cdc=np.array([p.min_size, p.normal_size, p.max_size, p.mask_s, p.mask_l], np.uint64), gear=gear)
+
+    @classmethod
+    def load(cls, path) -> "ChunkStore":
+        """A new index and fresh device buffers from a snapshot."""
+        import torch
+        with np.load(path) as z:
+            cdc, gear = [int(v) for v in z["cdc"]], z["gear"]
+            params = CdcParams(cdc[0], cdc[1], cdc[2], cdc[3], cdc[4], gear if len(gear) else None)
+            index = DedupeIndex(int(z["hash_alg"]), int(z["max_entries"]))
+            try:
+                index.import_(z["digests"], z["values"])
+                directory, store = z["directory"], z["store"]
+                cs = cls(index, int(z["comp_alg"]), params, int(z["store_bytes"]), len(directory) // 2, int(z["dir_base"]))
+                cs.base = int(z["base"])
+                cs.d_store[:len(store)] = torch.from_numpy(store).cuda()
+                cs.d_dir.copy_(torch.from_numpy(directory).cuda())
+                cs.d_used.fill_(len(store))
+                torch.cuda.synchronize()
+            except Exception:
+                index.close()
+                raise
+        return cs

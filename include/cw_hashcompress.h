@@ -376,6 +376,62 @@ int cw_dev_cdc_dedupe_compress(cw_dedupe_t *x, const cw_cdc_params *p, int comp_
                                void *d_dst, size_t dst_bytes, uint32_t *d_sizes,
                                size_t *nchunks, void *stream);
 
+/* ---- chunk store: keep the new chunks, restore deduplicated streams ---------------------------------
+ * The read side of the dedupe path.  The library keeps no state: the CALLER owns three plain device buffers, and all three
+ * zeroed are an empty store:
+ *     d_store[store_bytes]     the stored bytes, appended without padding
+ *     *d_used (u64)            the append cursor: bytes of d_store in use
+ *     d_dir[dir_entries]       where each chunk lies, indexed by value - dir_base; value = what the index stores for the chunk
+ *                              (base + i), so restoring needs no hash lookup.  16-byte aligned; 16 B per ingested chunk.
+ * One store is used from one stream at a time (the calls read and write *d_used and the directory in stream order and do
+ * not serialise against other streams); different stores may be used from different streams and threads.              */
+typedef struct cw_chunk_loc {   /* 16 bytes; all zero = no such chunk */
+    uint64_t pos;               /* first byte in the store */
+    uint32_t stored;            /* bytes stored there */
+    uint32_t raw;               /* bits 0..16: the chunk's length, 1..65536; bit 31: stored uncompressed; bits 17..30: 0 */
+} cw_chunk_loc;
+#define CW_CHUNK_RAW 0x80000000u
+/* Appends the chunks of one cw_dev_compress_chunks / cw_dev_cdc_dedupe_compress call: comp_alg, d_src, src_bytes, d_offsets,
+ * d_nchunks, max_chunks, d_sel / d_nsel (that call's selection: cw_dev_dedupe's d_new_idx / d_n_new; NULL / NULL = every chunk),
+ * d_slots (its d_dst) and d_sizes exactly as that call got and left them.  With n = min(*d_nsel, max_chunks) (no selection:
+ * min(*d_nchunks, max_chunks)), position j < n, chunk i = d_sel[j], l its length and s = d_sizes[j]:
+ *   stored form   0 < s < l: the s compressed bytes of the chunk's slot; otherwise the l bytes of d_src, with CW_CHUNK_RAW set --
+ *                 one rule for both codecs: an LZF chunk that did not fit and an LZ4 chunk that grew are kept, and restored by a copy.
+ *   placement     position j at *d_used + the stored bytes of the positions before it; d_dir[base + i - dir_base] = {pos, stored,
+ *                 l | flag}; then *d_used grows by the total.
+ *   out of contract (as cw_dev_compress_chunks defines it: index >= the chunk count, length 0 or above 65536, a decreasing pair,
+ *                 an end past src_bytes): stores nothing, gets no entry.
+ * All or nothing, decided on the device: d_result[1] = the total either way; d_result[0] = 1 when *d_used + total > store_bytes,
+ * else 2 when an in-contract chunk's base + i - dir_base lies outside [0, dir_entries) (or base + i wraps), else 0.  When it is
+ * not 0, no store byte, no directory entry and not *d_used change.  Nothing synchronises: the call can be queued directly behind
+ * the compressing call.  Two positions naming one chunk store it twice; either entry stays.
+ * CW_ERR_BAD_ARG before anything is launched: a NULL pointer (d_sel and d_nsel may be NULL together; d_src when src_bytes is 0;
+ * d_store when store_bytes is 0), an unknown codec, max_chunks > 2^32 - 256, dir_entries == 0, a d_dir that is not 16-byte
+ * aligned, a d_used or d_result that is not 8-byte aligned.  Scratch, per stream: 72 + 12 * max_chunks bytes.                */
+int cw_dev_store_chunks(int comp_alg, const void *d_src, size_t src_bytes, const uint64_t *d_offsets,
+                        const uint64_t *d_nchunks, size_t max_chunks, const uint32_t *d_sel, const uint64_t *d_nsel,
+                        const void *d_slots, const uint32_t *d_sizes, uint64_t base,
+                        void *d_store, size_t store_bytes, uint64_t *d_used,
+                        cw_chunk_loc *d_dir, uint64_t dir_base, size_t dir_entries,
+                        uint64_t *d_result, void *stream);
+/* Rebuilds a stream from its recipe: position j < min(*d_count, max_count) is the chunk of value d_ref[j] (as cw_dev_dedupe
+ * wrote it) and goes to d_dst[d_raw_offsets[j] .. d_raw_offsets[j+1]).  d_status[j] =
+ *   0  the entry exists, its length is the raw extent's, and the decoder (or the copy) produced exactly that many bytes;
+ *   1  the stored bytes are malformed: cw_dev_decompress_chunks' verdict on the same bytes (the extent's bytes are unspecified);
+ *   2  refused, nothing loaded from the store and nothing written: d_ref[j] outside [dir_base, dir_base + dir_entries) (so
+ *      CW_DEDUPE_MISS), an entry with length 0 or above 65536 or with bits 17..30 set (so an all-zero entry), a length that is
+ *      not the raw extent's, stored == 0, a raw entry with stored != length, pos + stored > store_bytes, a raw extent that is
+ *      decreasing, longer than 65536 or past dst_bytes.
+ * No load leaves d_store[0..store_bytes), d_dir[0..dir_entries) or the recipe, no store position j's raw extent, whatever the
+ * store and the directory hold; positions behind the count are not touched.  A chunk named twice is decoded twice.  Compressed
+ * entries are decoded one per lane, raw entries copied by the whole wavefront; no scratch.  CW_ERR_BAD_ARG: a NULL pointer
+ * (d_dst when dst_bytes is 0 and d_store when store_bytes is 0 may be), an unknown codec, max_count > 2^32 - 256,
+ * dir_entries == 0, a d_dir that is not 16-byte aligned.  Not synchronised.                                                 */
+int cw_dev_restore_chunks(int comp_alg, const void *d_store, size_t store_bytes, const cw_chunk_loc *d_dir,
+                          uint64_t dir_base, size_t dir_entries, const uint64_t *d_ref, const uint64_t *d_raw_offsets,
+                          const uint64_t *d_count, size_t max_count, void *d_dst, size_t dst_bytes,
+                          uint32_t *d_status, void *stream);
+
 /* plain device memory on the calling thread's device, for C callers of cw_dev_* (the host programs link no HIP runtime) */
 void *cw_dev_alloc(size_t bytes);                                   /* NULL on failure */
 void  cw_dev_free(void *d_p);
