@@ -954,7 +954,11 @@ lzf_sthread_kernel(const uint8_t *__restrict__ src, uint32_t n, size_t src_strid
         const uint8_t *g = src + gb * src_stride;
         uint8_t *out = dst + gb * dst_stride;
         uint16_t *lk = links + blk * (size_t)n2;
-        const u32x4 rs = sc_descriptor(g, n), rl = sc_descriptor(lk, n2 * 2u);
+        // the range check of a scalar buffer load works on whole dwords: with n as the range the last n & 3 bytes of a block read as
+        // zero, and a match that reaches them (LZF matches run to the block's last byte) came out short.  The block and its stride are
+        // dword-aligned here (lzf_plan), so the dword that holds byte n - 1 is the block's own; what it holds behind n - 1 is never
+        // counted (`room` below, ip + 2 < n for the three bytes that are hashed).
+        const u32x4 rs = sc_descriptor(g, (n + 3u) & ~3u), rl = sc_descriptor(lk, n2 * 2u);
         for (uint32_t i = lane; i < n2 / 32; i += 64) skipmap[i] = 0;
         asm volatile("" ::: "memory");
 
@@ -1029,7 +1033,7 @@ lzf_sthread_kernel(const uint8_t *__restrict__ src, uint32_t n, size_t src_strid
                 }
                 uint32_t eq = __builtin_amdgcn_readfirstlane(T) - 3u;
                 {
-                    const uint32_t room = (n - ip < kMaxRef + 2 ? n - ip : kMaxRef + 2) - 3u; // (windows read zeros beyond the block)
+                    const uint32_t room = (n - ip < kMaxRef + 2 ? n - ip : kMaxRef + 2) - 3u; // (the windows reach beyond the block)
                     if (eq > room) eq = room;
                 }
                 uint32_t maxlen = n - ip - 2u, len;

@@ -72,6 +72,62 @@ def lz4_counts(b):
     return probes, seqs, out
 
 
+def lz4_walk(b):
+    """The same walk with its positions kept (tests/lz_inputs.py checks its built inputs against them): returns
+    (probes, seqs).  probes: every position the search loop or the re-test looked up, in order.  seqs: one
+    (found_at, back, start, literals, offset, match_len) per match: the probe that found it, the bytes the catch-up stepped
+    back, where the match starts; the last sequence is (None, 0, n, literals, None, None).  Follows oracle/lz4_oracle.c
+    (search ends when the next probe would lie beyond n - 11)."""
+    n = len(b)
+    probes, seqs = [], []
+    if n < 13:
+        return probes, [(None, 0, n, n, None, None)]
+    mflimit, matchlimit = n - 12, n - 5
+    tab = {}
+    h = lambda p: ((struct.unpack_from("<I", b, p)[0] * 2654435761) & 0xFFFFFFFF) >> 19
+    tab[h(0)] = 0
+    anchor, ip = 0, 1
+    while True:
+        fwd, step, nb, m = ip, 1, 64, None
+        while True:
+            ip = fwd
+            fwd += step
+            step = nb >> 6
+            nb += 1
+            if fwd > mflimit + 1:
+                seqs.append((None, 0, n, n - anchor, None, None))
+                return probes, seqs
+            hv = h(ip)
+            m = tab.get(hv, 0)
+            probes.append(ip)
+            tab[hv] = ip
+            if b[m:m + 4] == b[ip:ip + 4]:
+                break
+        found = ip
+        while ip > anchor and m > 0 and b[ip - 1] == b[m - 1]:
+            ip -= 1
+            m -= 1
+        while True:
+            ml = 4
+            while ip + ml < matchlimit and b[ip + ml] == b[m + ml]:
+                ml += 1
+            seqs.append((found, found - ip, ip, ip - anchor, ip - m, ml))
+            ip += ml
+            anchor = ip
+            if ip > mflimit:
+                seqs.append((None, 0, n, n - anchor, None, None))
+                return probes, seqs
+            tab[h(ip - 2)] = ip - 2
+            hv = h(ip)
+            m = tab.get(hv, 0)
+            probes.append(ip)
+            tab[hv] = ip
+            if b[m:m + 4] != b[ip:ip + 4]:
+                break
+            found = ip
+        ip += 1
+
+
 def main():
     path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "tests/golden/corpus/canterbury/lcet10.txt")
     bs = int(sys.argv[2]) if len(sys.argv) > 2 else 65536
