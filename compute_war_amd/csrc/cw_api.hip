@@ -1479,6 +1479,48 @@ int cw_dev_restore_chunks(int comp_alg, const void *d_store, size_t store_bytes,
     return CW_OK;
 }
 
+// ---- the chunk store forgets: mark and compact (kernels: store_gc_kernels.hip; semantics: the header) ------------------------
+// [a, a + an) and [b, b + bn) share a byte
+static bool ranges_overlap(const void *a, size_t an, const void *b, size_t bn)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return an && bn && x < y + bn && y < x + an;
+}
+
+int cw_dev_store_mark(const uint64_t *d_ref, const uint64_t *d_count, size_t max_count, uint64_t dir_base, size_t dir_entries, uint32_t *d_live,
+                      uint64_t *d_n_outside, void *stream)
+{
+    if (max_count > kMaxChunks) return fail(CW_ERR_BAD_ARG, "max_count %zu > 2^32 - 256", max_count);
+    if (!d_ref || !d_count || !d_live || !d_n_outside) return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    if (dir_entries == 0) return fail(CW_ERR_BAD_ARG, "dir_entries is 0");
+    if ((uintptr_t)d_n_outside & 7) return fail(CW_ERR_BAD_ARG, "d_n_outside not 8-byte aligned");
+    int rc = ensure_init();
+    if (rc != CW_OK) return rc;
+    const hipError_t e = cw::store_mark_launch(d_ref, d_count, max_count, dir_base, dir_entries, d_live, d_n_outside, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(CW_ERR_HIP, "store mark launch: %s", hipGetErrorString(e));
+    return CW_OK;
+}
+
+int cw_dev_store_compact(const void *d_store, size_t store_bytes, const cw_chunk_loc *d_dir, size_t dir_entries, const uint32_t *d_live,
+                         void *d_new_store, size_t new_store_bytes, uint64_t *d_new_used, cw_chunk_loc *d_new_dir, uint64_t *d_result,
+                         void *stream)
+{
+    if (!d_dir || !d_live || !d_new_used || !d_new_dir || !d_result || (store_bytes && !d_store) || (new_store_bytes && !d_new_store))
+        return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    if (dir_entries == 0) return fail(CW_ERR_BAD_ARG, "dir_entries is 0");
+    if (((uintptr_t)d_dir | (uintptr_t)d_new_dir) & 15) return fail(CW_ERR_BAD_ARG, "d_dir / d_new_dir is not 16-byte aligned");
+    if (((uintptr_t)d_new_used | (uintptr_t)d_result) & 7) return fail(CW_ERR_BAD_ARG, "d_new_used / d_result not 8-byte aligned");
+    if (ranges_overlap(d_store, store_bytes, d_new_store, new_store_bytes)) return fail(CW_ERR_BAD_ARG, "d_new_store overlaps d_store");
+    if (d_new_dir != d_dir && ranges_overlap(d_dir, dir_entries * sizeof(cw_chunk_loc), d_new_dir, dir_entries * sizeof(cw_chunk_loc)))
+        return fail(CW_ERR_BAD_ARG, "d_new_dir overlaps d_dir without being d_dir");
+    int rc = ensure_init();
+    if (rc != CW_OK) return rc;
+    const hipError_t e = cw::store_compact_launch((const uint8_t *)d_store, store_bytes, d_dir, dir_entries, d_live, (uint8_t *)d_new_store,
+                                                  new_store_bytes, d_new_used, d_new_dir, d_result, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? CW_ERR_NOMEM : CW_ERR_HIP, "store compact launch: %s", hipGetErrorString(e));
+    return CW_OK;
+}
+
 // Pieces of at most kMaxChunkBytes: each piece is chunked with final = 0 (the last with final = 1); the bytes after the last
 // cut of a piece -- fewer than max_size -- are copied to the front of the next piece's buffer.
 int cw_cdc_hash(const cw_cdc_params *p, int hash_alg, const void *src, size_t nbytes, uint64_t *offsets, size_t max_offsets,
@@ -1916,6 +1958,64 @@ int cw_dedupe_resize(cw_dedupe_t *x, size_t new_max_entries)
     void *old = x->table;
     dedupe_table_adopt(x, t, cap, new_max_entries);
     x->count_bound = count;
+    HIP_TRY(hipEventRecord(x->last, nullptr));
+    HIP_TRY(hipFree(old));
+    return CW_OK;
+}
+
+// cw_dedupe_resize with a filter (the keep rule: dedupe_retain_kernel).  When the new table could not hold every entry of the old one
+// (new_max_entries below the old count) the kept entries are counted first, by the same kernel without a table: rehashing more
+// entries than the table has slots would walk the whole table once per entry that finds none.
+int cw_dedupe_retain(cw_dedupe_t *x, const uint32_t *d_live, uint64_t dir_base, size_t dir_entries, size_t new_max_entries, uint64_t *n_removed)
+{
+    if (!x || !d_live) return fail(CW_ERR_BAD_ARG, "cw_dedupe_retain: NULL %s", x ? "d_live" : "dedupe index");
+    if (dir_entries == 0) return fail(CW_ERR_BAD_ARG, "cw_dedupe_retain: dir_entries is 0");
+    if (new_max_entries > ((size_t)1 << 40)) return fail(CW_ERR_BAD_ARG, "cw_dedupe_retain: max_entries %zu > 2^40", new_max_entries);
+    int rc = dedupe_args(x, 0, 0);
+    if (rc != CW_OK) return rc;
+    std::lock_guard<std::mutex> g(x->lock);
+    uint64_t count = 0;
+    if ((rc = dedupe_read_count(x, &count)) != CW_OK) return rc;
+    const size_t want = new_max_entries ? new_max_entries : x->max_entries;
+    const uint64_t cap = dedupe_cap(want);
+    const size_t db = (size_t)x->words * 8;
+    DedupeTable t;
+    hipError_t e = dedupe_table_alloc(cap, db, nullptr, &t);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(e == hipErrorOutOfMemory ? CW_ERR_NOMEM : CW_ERR_HIP, "cw_dedupe_retain(%zu entries, %zu bytes beside the old table): %s", want,
+                    dedupe_table_bytes(cap, db), hipGetErrorString(e));
+    }
+    // the old table is idle (the last call has finished, the lock keeps new ones out): everything below is on the NULL stream.
+    // t.ctrl[0] counts the kept entries, t.ctrl[1] takes the walks' error word
+    unsigned long long *kept_d = reinterpret_cast<unsigned long long *>(t.ctrl), *err_d = kept_d + 1;
+    uint64_t c[2] = {0, 0}; // kept, err
+    if (want < count) {
+        e = cw::dedupe_retain_launch(x->words, x->state, x->value, x->key, x->cap, d_live, dir_base, dir_entries, nullptr, nullptr, nullptr, 0, kept_d,
+                                     err_d, nullptr);
+        if (e == hipSuccess) e = hipMemcpyAsync(c, t.ctrl, sizeof c, hipMemcpyDeviceToHost, nullptr);
+        if (e == hipSuccess) e = hipMemsetAsync(t.ctrl, 0, sizeof c, nullptr);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    }
+    if (e == hipSuccess && c[0] <= want) {
+        e = cw::dedupe_retain_launch(x->words, x->state, x->value, x->key, x->cap, d_live, dir_base, dir_entries, t.state, t.value, t.key, cap - 1,
+                                     kept_d, err_d, nullptr);
+        if (e == hipSuccess) e = hipMemcpyAsync(c, t.ctrl, sizeof c, hipMemcpyDeviceToHost, nullptr);
+        if (e == hipSuccess) e = hipMemcpyAsync(t.ctrl + 2, x->ctrl + 2, 2 * sizeof(uint64_t), hipMemcpyDeviceToDevice, nullptr);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    }
+    if (e != hipSuccess || c[1] || c[0] > want) {
+        (void)hipFree(t.mem);
+        if (e != hipSuccess) return fail(CW_ERR_HIP, "cw_dedupe_retain: %s", hipGetErrorString(e));
+        if (c[0] > want)
+            return fail(CW_ERR_BAD_ARG, "cw_dedupe_retain: max_entries %zu below the %llu kept entries (the index is unchanged)", want,
+                        (unsigned long long)c[0]);
+        return fail(CW_ERR_HIP, "cw_dedupe_retain: an entry found no slot in the new table (the index is unchanged)");
+    }
+    void *old = x->table;
+    dedupe_table_adopt(x, t, cap, want);
+    x->count_bound = c[0];
+    if (n_removed) *n_removed = count - c[0];
     HIP_TRY(hipEventRecord(x->last, nullptr));
     HIP_TRY(hipFree(old));
     return CW_OK;

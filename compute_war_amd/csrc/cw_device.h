@@ -120,6 +120,11 @@ hipError_t dedupe_export_scatter_launch(unsigned words, const uint64_t *state, c
 // every committed entry of the old table into the (empty) new one; err = 1 if an entry found no slot
 hipError_t dedupe_rehash_launch(unsigned words, const uint64_t *old_state, const uint64_t *old_value, const uint64_t *old_key, uint64_t old_cap,
                                 uint64_t *state, uint64_t *value, uint64_t *key, uint64_t mask, unsigned long long *err, hipStream_t s);
+// the rehash of the entries whose value names no entry of [dir_base, dir_base + dir_entries) or a flagged one (live[v - dir_base] != 0);
+// *n_kept += their number.  state == NULL: only counts
+hipError_t dedupe_retain_launch(unsigned words, const uint64_t *old_state, const uint64_t *old_value, const uint64_t *old_key, uint64_t old_cap,
+                                const uint32_t *live, uint64_t dir_base, uint64_t dir_entries, uint64_t *state, uint64_t *value, uint64_t *key,
+                                uint64_t mask, unsigned long long *n_kept, unsigned long long *err, hipStream_t s);
 // block new_idx[j] (src_stride apart in src) -> dst + j * block_bytes, for j < n_new
 hipError_t dedupe_gather_launch(const uint8_t *src, size_t block_bytes, size_t src_stride, const uint32_t *new_idx, size_t n_new,
                                 uint8_t *dst, hipStream_t s);
@@ -225,6 +230,13 @@ hipError_t chunk_store_launch(int lzf, const uint8_t *src, size_t src_bytes, con
 hipError_t chunk_restore_launch(int lzf, const uint8_t *store, size_t store_bytes, const void *dir, uint64_t dir_base, size_t dir_entries,
                                 const uint64_t *ref, const uint64_t *raw_offsets, const uint64_t *d_count, size_t max_count, uint8_t *dst,
                                 size_t dst_bytes, uint32_t *status, hipStream_t stream);
+
+// mark and compact (store_gc_kernels.hip; semantics: the public header).  new_dir may be dir itself
+hipError_t store_mark_launch(const uint64_t *ref, const uint64_t *d_count, size_t max_count, uint64_t dir_base, size_t dir_entries,
+                             uint32_t *live, uint64_t *n_outside, hipStream_t stream);
+hipError_t store_compact_launch(const uint8_t *store, size_t store_bytes, const void *dir, size_t dir_entries, const uint32_t *live,
+                                uint8_t *new_store, size_t new_store_bytes, uint64_t *new_used, void *new_dir, uint64_t *result,
+                                hipStream_t stream);
 
 hipError_t sum_sizes_launch(const uint32_t *sizes, size_t n, uint32_t raw_bytes, uint64_t *totals, hipStream_t stream);
 hipError_t gen_random_launch(uint64_t seed, uint64_t first_block, size_t nblocks, size_t block_bytes, uint8_t *dst,

@@ -1,6 +1,6 @@
 // dedupe_kernels.hip -- device-resident fingerprint index (cw_dedupe_*, cw_dev_dedupe*): batched lookup-or-insert of full
-// digests in an open-addressed table with linear probing, on gfx950, and the index's lifecycle: read-only lookup, export and the
-// rehash of cw_dedupe_resize.  The reference has no counterpart: HashAndCompress.cpp computes the digests and drops them (:257,
+// digests in an open-addressed table with linear probing, on gfx950, and the index's lifecycle: read-only lookup, export, the
+// rehash of cw_dedupe_resize and the filtered rehash of cw_dedupe_retain.  The reference has no counterpart: HashAndCompress.cpp computes the digests and drops them (:257,
 // SURVEY.md D3).
 //
 // Table (allocated by cw_dedupe_create and again by cw_dedupe_resize; capacity a power of two >= 2 x max_entries, so the load stays <= 0.5):
@@ -279,7 +279,20 @@ dedupe_export_scatter_kernel(const uint64_t *__restrict__ state, const uint64_t 
 
 // Rehash into an empty table (cw_dedupe_resize): one lane per old slot.  All keys are distinct and nothing reads keys while this
 // runs, so a committed entry walks from its new home slot with one agent-scope CAS EMPTY -> COMMITTED per step until it claims a
-// slot, then stores key and value: no PENDING phase, no key compares.  Bounded by the new table's size.
+// slot, then stores key and value: no PENDING phase, no key compares.  Bounded by the new table's size.  The claim walk (shared with
+// the retain below) returns the slot it claimed for digest d, or kNoSlot when it reached the bound.
+template <int W>
+__device__ __forceinline__ uint64_t claim_committed(uint64_t *__restrict__ state, const uint64_t (&d)[W], uint64_t mask)
+{
+    uint64_t slot = fold(d) & mask;
+    for (uint64_t step = 0; step <= mask; step++, slot = (slot + 1) & mask) {
+        uint64_t old = kEmpty;
+        __hip_atomic_compare_exchange_strong(state + slot, &old, kCommitted, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (old == kEmpty) return slot;
+    }
+    return kNoSlot;
+}
+
 template <int W>
 __global__ void __launch_bounds__(kThreads)
 dedupe_rehash_kernel(const uint64_t *__restrict__ old_state, const uint64_t *__restrict__ old_value, const uint64_t *__restrict__ old_key,
@@ -290,15 +303,47 @@ dedupe_rehash_kernel(const uint64_t *__restrict__ old_state, const uint64_t *__r
         if (old_state[o] != kCommitted) continue;
         uint64_t d[W];
         for (int w = 0; w < W; w++) d[w] = old_key[o * W + w];
-        uint64_t slot = fold(d) & mask, step = 0;
-        for (; step <= mask; step++, slot = (slot + 1) & mask) {
-            uint64_t old = kEmpty;
-            __hip_atomic_compare_exchange_strong(state + slot, &old, kCommitted, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (old == kEmpty) break;
-        }
-        if (step > mask) { *err = 1ull; continue; }
+        const uint64_t slot = claim_committed(state, d, mask);
+        if (slot == kNoSlot) { *err = 1ull; continue; }
         for (int w = 0; w < W; w++) key[slot * W + w] = d[w];
         value[slot] = old_value[o];
+    }
+}
+
+// Retain (cw_dedupe_retain): the rehash with a filter.  A committed entry with value v is kept when v names no entry of the directory
+// (v - dir_base >= dir_entries in u64) or that entry's flag is set; only kept entries are rehashed, so the new table is what inserting
+// them into an empty one gives and no slot ever had to be emptied.  live is complete before the launch (a kernel boundary behind the
+// marks).  The kept entries are counted whether or not they found a slot: each lane's count summed per wavefront, then through
+// LDS, then one atomic per workgroup, for the reason the lookup counts its hits that way.  state == NULL only counts.
+template <int W>
+__global__ void __launch_bounds__(kThreads)
+dedupe_retain_kernel(const uint64_t *__restrict__ old_state, const uint64_t *__restrict__ old_value, const uint64_t *__restrict__ old_key,
+                     uint64_t old_cap, const uint32_t *__restrict__ live, uint64_t dir_base, uint64_t dir_entries, uint64_t *__restrict__ state,
+                     uint64_t *__restrict__ value, uint64_t *__restrict__ key, uint64_t mask, unsigned long long *__restrict__ n_kept,
+                     unsigned long long *__restrict__ err)
+{
+    uint32_t mine = 0; // (a lane sees at most old_cap / (gridDim.x * kThreads) + 1 < 2^32 slots)
+    for (uint64_t o = (uint64_t)blockIdx.x * kThreads + threadIdx.x; o < old_cap; o += (uint64_t)gridDim.x * kThreads) {
+        if (old_state[o] != kCommitted) continue;
+        const uint64_t v = old_value[o], idx = v - dir_base;
+        if (idx < dir_entries && live[idx] == 0) continue;
+        mine++;
+        if (!state) continue;
+        uint64_t d[W];
+        for (int w = 0; w < W; w++) d[w] = old_key[o * W + w];
+        const uint64_t slot = claim_committed(state, d, mask);
+        if (slot == kNoSlot) { *err = 1ull; continue; }
+        for (int w = 0; w < W; w++) key[slot * W + w] = d[w];
+        value[slot] = v;
+    }
+    __shared__ uint32_t wkept[kThreads / 64];
+    for (int off = 32; off > 0; off >>= 1) mine += __shfl_down(mine, off, 64);
+    if ((threadIdx.x & 63u) == 0) wkept[threadIdx.x >> 6] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t all = 0;
+        for (uint32_t w = 0; w < kThreads / 64; w++) all += wkept[w];
+        if (all) __hip_atomic_fetch_add(n_kept, (unsigned long long)all, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
@@ -408,6 +453,23 @@ hipError_t dedupe_rehash_launch(unsigned words, const uint64_t *old_state, const
     case 8: hipLaunchKernelGGL(dedupe_rehash_kernel<8>, g, b, 0, s, old_state, old_value, old_key, old_cap, state, value, key, mask, err); break;
     default: return hipErrorInvalidValue;
     }
+    return hipGetLastError();
+}
+
+// state == NULL: *n_kept += the entries the keep rule keeps, nothing is written; else they are rehashed as well
+hipError_t dedupe_retain_launch(unsigned words, const uint64_t *old_state, const uint64_t *old_value, const uint64_t *old_key, uint64_t old_cap,
+                                const uint32_t *live, uint64_t dir_base, uint64_t dir_entries, uint64_t *state, uint64_t *value, uint64_t *key,
+                                uint64_t mask, unsigned long long *n_kept, unsigned long long *err, hipStream_t s)
+{
+    const dim3 g(grid_stride_of(dedupe_export_tiles(old_cap))), b(kThreads);
+#define CW_RETAIN(W) hipLaunchKernelGGL(dedupe_retain_kernel<W>, g, b, 0, s, old_state, old_value, old_key, old_cap, live, dir_base, dir_entries, state, value, key, mask, n_kept, err)
+    switch (words) {
+    case 2: CW_RETAIN(2); break;
+    case 4: CW_RETAIN(4); break;
+    case 8: CW_RETAIN(8); break;
+    default: return hipErrorInvalidValue;
+    }
+#undef CW_RETAIN
     return hipGetLastError();
 }
 

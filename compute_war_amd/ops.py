@@ -371,6 +371,17 @@ class DedupeIndex:
         check(lib().cw_dedupe_max_entries(self._x(), C.byref(n)))
         self.max_entries = int(n.value)
 
+    def retain(self, d_live: int, dir_base: int, dir_entries: int, max_entries: int | None = None) -> int:
+        """Rebuild the table with only the entries whose value names no entry of [dir_base, dir_base + dir_entries) or one whose
+        flag d_live[value - dir_base] (u32, device memory, complete when the call is made) is set; returns how many were removed.
+        Synchronous; ``max_entries`` (default: as it is) must hold the kept entries, else CwError -2 and the index is unchanged."""
+        removed = C.c_uint64(0)
+        check(lib().cw_dedupe_retain(self._x(), d_live, dir_base, dir_entries, max_entries or 0, C.byref(removed)))
+        n = C.c_size_t(0)
+        check(lib().cw_dedupe_max_entries(self._x(), C.byref(n)))
+        self.max_entries = int(n.value)
+        return int(removed.value)
+
     def set_stage_entries(self, entries: int) -> None:
         """Pairs per piece of ``export`` / ``import_`` (0 = the default); for tests."""
         check(lib().cw_dedupe_set_stage_entries(self._x(), entries))
@@ -625,6 +636,22 @@ def dev_restore_chunks(comp_alg, d_store: int, store_bytes: int, d_dir: int, dir
                                       d_raw_offsets, d_count, max_count, d_dst or None, dst_bytes, d_status, stream))
 
 
+def dev_store_mark(d_ref: int, d_count: int, max_count: int, dir_base: int, dir_entries: int, d_live: int, d_n_outside: int,
+                   stream: int = 0) -> None:
+    """d_live[d_ref[j] - dir_base] = 1 (u32) for every position j < min(*d_count, max_count) that names a directory entry;
+    *d_n_outside (u64) += the positions that name none.  The caller zeroes both first.  Not synchronised."""
+    check(lib().cw_dev_store_mark(d_ref, d_count, max_count, dir_base, dir_entries, d_live, d_n_outside, stream))
+
+
+def dev_store_compact(d_store: int, store_bytes: int, d_dir: int, dir_entries: int, d_live: int, d_new_store: int, new_store_bytes: int,
+                      d_new_used: int, d_new_dir: int, d_result: int, stream: int = 0) -> None:
+    """The flagged, non-zero entries' stored bytes back to back into d_new_store, their new places into d_new_dir (which may be
+    d_dir), the total into *d_new_used.  d_result[0..4) = verdict (1: does not fit, 2: a kept entry is unsound; nothing changed
+    then), kept bytes, kept entries, dropped entries.  d_new_store = 0 with new_store_bytes = 0 is a dry run.  Not synchronised."""
+    check(lib().cw_dev_store_compact(d_store or None, store_bytes, d_dir, dir_entries, d_live, d_new_store or None, new_store_bytes,
+                                     d_new_used, d_new_dir, d_result, stream))
+
+
 class Recipe:
     """What restores one ingested stream: refs[j] = the value of chunk j's first occurrence, offsets[0..k] = its cuts."""
 
@@ -641,8 +668,9 @@ class Recipe:
 
 class ChunkStore:
     """A dedupe index with the bytes behind it: ``ingest`` chunks, dedupes and compresses a buffer and appends its new chunks to a
-    device-resident store, ``restore`` turns a recipe back into bytes.  The store is three torch buffers this object owns (bytes,
-    cursor, directory: the caller-owned triple of cw_dev_store_chunks); chunk values count up from ``dir_base`` over the ingests.
+    device-resident store, ``restore`` turns a recipe back into bytes, ``compact`` forgets every stream but the ones named.
+    The store is three torch buffers this object owns (bytes, cursor, directory: the caller-owned triple of cw_dev_store_chunks);
+    chunk values count up from ``dir_base`` over the ingests.
     One device call per ingest: the whole buffer has to fit on the device next to its slots."""
 
     def __init__(self, index: DedupeIndex, comp_alg, params: CdcParams, store_bytes: int, dir_entries: int, dir_base: int = 0):
@@ -727,6 +755,55 @@ class ChunkStore:
                 raise _lib.CwError(-2, f"chunk store: verify failed at position {int(bad[0])}: the index answers {int(got[bad[0]])}, "
                                        f"the recipe says {int(recipe.refs[bad[0]])} ({len(bad)} positions differ)")
         return out.cpu().numpy()[:n].tobytes()
+
+    def compact(self, keep, store_bytes: int | None = None) -> dict:
+        """Forget every stream but the recipes in ``keep``: mark their chunks, move the marked chunks' stored bytes into a new store
+        of ``store_bytes`` (default: as large as the old one, after a dry run) with a new directory, and drop the other chunks' digests
+        from the index.  Values are not renumbered.  Returns dict(kept, dropped, bytes_before, bytes_after, removed).  Raises CwError
+        with ``e.needed`` (the bytes the kept chunks take) when the new store is too small (-5) or a kept chunk's entry is damaged
+        (-2), and CwError -2 when a recipe names a value outside the directory; the store and the index are then unchanged, as they
+        are when the index's retain fails."""
+        import torch
+        s, n = self._stream(), self.dir_entries
+        live, n_out = torch.zeros(n, dtype=torch.int32, device="cuda"), torch.zeros(1, dtype=torch.int64, device="cuda")
+        new_dir, new_used = torch.zeros(n * 2, dtype=torch.int64, device="cuda"), torch.zeros(1, dtype=torch.int64, device="cuda")
+        result = torch.zeros(4, dtype=torch.int64, device="cuda")
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64).copy()).cuda()  # noqa: E731
+        recipes = [(up(r.refs), up([len(r.refs)]), len(r.refs)) for r in keep if len(r.refs)]
+        torch.cuda.synchronize()  # (torch zeroed and copied on its own stream)
+        for d_ref, d_count, k in recipes:
+            dev_store_mark(d_ref.data_ptr(), d_count.data_ptr(), k, self.dir_base, n, live.data_ptr(), n_out.data_ptr(), s)
+
+        def run(d_new_store: int, new_bytes: int):
+            dev_store_compact(self.d_store.data_ptr(), self.store_bytes, self.d_dir.data_ptr(), n, live.data_ptr(), d_new_store, new_bytes,
+                              new_used.data_ptr(), new_dir.data_ptr(), result.data_ptr(), s)
+            torch.cuda.synchronize()
+            verdict, needed, kept, dropped = (int(v) for v in result.cpu().numpy().view(np.uint64))
+            if verdict:
+                err = _lib.CwError(-5 if verdict == 1 else -2, f"chunk store: the kept chunks' {needed} bytes do not fit into {new_bytes}"
+                                   if verdict == 1 else "chunk store: a kept chunk's directory entry is damaged")
+                err.needed = needed
+                raise err
+            return needed, kept, dropped
+
+        if store_bytes is None:
+            try:
+                run(0, 0)  # the dry run: verdict 1 with the bytes needed, unless nothing is kept
+            except _lib.CwError as e:
+                if e.code != -5:
+                    raise
+            store_bytes = self.store_bytes
+        outside = int(n_out.item())
+        if outside:
+            raise _lib.CwError(-2, f"chunk store: {outside} positions of the kept recipes name no entry of the directory [{self.dir_base}, "
+                                   f"{self.dir_base + n})")
+        new_store = torch.zeros(max(store_bytes, 1), dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        bytes_before = self.used()
+        needed, kept, dropped = run(new_store.data_ptr(), store_bytes)
+        removed = self.index.retain(live.data_ptr(), self.dir_base, n)
+        self.d_store, self.d_used, self.d_dir, self.store_bytes = new_store, new_used, new_dir, store_bytes
+        return dict(kept=kept, dropped=dropped, bytes_before=bytes_before, bytes_after=needed, removed=removed)
 
     def save(self, path) -> None:
         """One ``.npz``: the index's export, the store bytes [0, used), the directory, base and the parameters."""

@@ -432,6 +432,53 @@ int cw_dev_restore_chunks(int comp_alg, const void *d_store, size_t store_bytes,
                           const uint64_t *d_count, size_t max_count, void *d_dst, size_t dst_bytes,
                           uint32_t *d_status, void *stream);
 
+/* ---- the store forgets: mark, compact, and the index's retain ----------------------------------------
+ * Mark and sweep over the same caller-owned buffers, plus one more the caller owns: d_live[dir_entries] (u32), a flag per
+ * directory entry.  To drop streams: zero d_live and *d_n_outside, mark every recipe that stays, compact, retain.  Marking is
+ * idempotent and needs no atomics on the flags; no call keeps state, every decision is made on the device, every call is all or
+ * nothing.  Values are not renumbered: a dropped chunk's directory entry stays zero (16 B), and base keeps counting upward.   */
+/* With n = min(*d_count, max_count), read on the device: for each position j < n, idx = d_ref[j] - dir_base in u64 (a value
+ * below the base wraps out of range); idx < dir_entries sets d_live[idx] = 1 (a plain store), any other position -- CW_DEDUPE_MISS
+ * always -- is counted: *d_n_outside (u64) += their number, so several marks accumulate.  Positions behind n are not read.
+ * CW_ERR_BAD_ARG before anything is launched: a NULL pointer, max_count > 2^32 - 256, dir_entries == 0, a d_n_outside that is
+ * not 8-byte aligned.  No scratch.  Not synchronised.                                                                         */
+int cw_dev_store_mark(const uint64_t *d_ref, const uint64_t *d_count, size_t max_count,
+                      uint64_t dir_base, size_t dir_entries, uint32_t *d_live,
+                      uint64_t *d_n_outside, void *stream);
+/* Moves the kept entries' stored bytes into a new store.  No codec: extents move as they are.
+ *   kept          entry idx is kept iff d_live[idx] != 0 and the entry is not all zero (a flag on an all-zero entry -- what a
+ *                 failed append leaves -- keeps nothing).  A kept entry must be sound by cw_dev_restore_chunks' entry checks:
+ *                 length 1..65536, bits 17..30 zero, stored != 0, a raw entry has stored == length, pos + stored <= store_bytes.
+ *   placement     kept entries back to back from byte 0 of d_new_store in ascending idx, without padding;
+ *                 d_new_dir[idx] = {new pos, stored, raw}, every other entry of d_new_dir all zero; *d_new_used = the total.
+ *   d_result[4]   {verdict, the kept entries' stored bytes summed, the kept count, the count of non-zero entries not kept}; the
+ *                 last three are written whatever the verdict is.
+ *   verdict       2 when a kept entry is unsound, else 1 when the total > new_store_bytes, else 0.  When it is not 0, no byte of
+ *                 d_new_store, no entry of d_new_dir and not *d_new_used change: new_store_bytes == 0 with d_new_store == NULL is
+ *                 a dry run, and d_result[1] says how much room to provide.  An unsound entry that is not kept is dropped like
+ *                 any other.
+ * d_new_dir may be d_dir itself (the directory is compacted in place; the old store's bytes stay, only the directory forgets) or
+ * must not overlap it.  The old store and its directory are never written unless d_new_dir == d_dir.  No load leaves
+ * d_store[0..store_bytes), d_dir[0..dir_entries) or d_live[0..dir_entries) whatever they hold; no store leaves the new buffers.
+ * CW_ERR_BAD_ARG before anything is launched: a NULL pointer (d_store when store_bytes is 0 and d_new_store when new_store_bytes
+ * is 0 may be), dir_entries == 0, a directory that is not 16-byte aligned, a d_new_used or d_result that is not 8-byte aligned,
+ * [d_new_store, +new_store_bytes) overlapping [d_store, +store_bytes), a d_new_dir that overlaps d_dir without being equal to it.
+ * Scratch, per stream: 72 + 12 * dir_entries bytes.  Not synchronised.                                                        */
+int cw_dev_store_compact(const void *d_store, size_t store_bytes, const cw_chunk_loc *d_dir, size_t dir_entries,
+                         const uint32_t *d_live,
+                         void *d_new_store, size_t new_store_bytes, uint64_t *d_new_used, cw_chunk_loc *d_new_dir,
+                         uint64_t *d_result /* [4] */, void *stream);
+/* The index's side, synchronous like cw_dedupe_resize: waits for the index's last call, always allocates and clears a fresh table
+ * for new_max_entries (0 = as it is), and rehashes on the device every entry whose value v it keeps: v - dir_base >= dir_entries
+ * (in u64: the value belongs to no entry of this directory) or d_live[v - dir_base] != 0.  The other entries are gone; a digest
+ * that was dropped can be inserted again.  d_live (device memory) must be complete when the call is made: synchronise the stream
+ * that marked.  *n_removed (may be NULL) = the old count - the kept count.  A rebuild, so the table is what inserting the kept
+ * entries into an empty index gives: slots only ever fill within a table's life.  CW_ERR_BAD_ARG: a NULL d_live,
+ * dir_entries == 0, new_max_entries above 2^40, or -- found out on the device, the index unchanged -- below the kept count;
+ * CW_ERR_NOMEM (index unchanged) when the new table cannot be allocated.  Old and new table are live at once during the call. */
+int cw_dedupe_retain(cw_dedupe_t *x, const uint32_t *d_live, uint64_t dir_base, size_t dir_entries,
+                     size_t new_max_entries /* 0 = as it is */, uint64_t *n_removed);
+
 /* plain device memory on the calling thread's device, for C callers of cw_dev_* (the host programs link no HIP runtime) */
 void *cw_dev_alloc(size_t bytes);                                   /* NULL on failure */
 void  cw_dev_free(void *d_p);
