@@ -1,40 +1,42 @@
-// cw_api.hip -- host side of libcwhc.so: the C ABI of include/cw_hashcompress.h over the HIP kernels.
+// cw_api.hip -- the core of the host side of libcwhc.so (the C ABI of include/cw_hashcompress.h over the HIP kernels): errors, devices and
+// per-thread contexts, the knob table, the fixed-block device API, profiling, the pipelined host batch path and the reference's slots.
+// What the other host files share is declared in cw_host.h and defined here: cw_chunks.hip (content-defined chunks and the chunk store),
+// cw_dedupe.hip (the dedupe index and the calls fused with it) and cw_offload.hip (the HashOffload object and its thread).
 //
 // Structure: a set of initialised devices (cw_init = the reference's empty initializeGpu(),
 // src/hashandcompress/HashAndCompress.cpp:95-98) with one "current device" per calling host thread (cw_set_device;
 // threads that never choose use the first initialised device), one lazily created context per (thread, device) --
 // own HIP streams + growable device/pinned staging buffers, because the reference invokes its slots from --c-threads
-// workers with no locking, :398-402 --, the pipelined host batch path (what HashOffload::Start()/Complete() were meant
-// to be, HashOffload.h:26-40), the HashOffload batch object itself (HashOffload.h:13-64) and the single consumer
-// thread that drains it (hashing_offload_entry_point, :160-183).
+// workers with no locking, :398-402 --, and the pipelined host batch path (what HashOffload::Start()/Complete() were meant
+// to be, HashOffload.h:26-40).
 //
 // No CPU fallback exists: every compute path ends in a kernel launch or an error.
 
-#include <hip/hip_runtime.h>
-
 #include <atomic>
-#include <condition_variable>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <deque>
 #include <memory>
 #include <mutex>
 #include <string>
-#include <thread>
 #include <vector>
 
-#include "../../include/cw_hashcompress.h"
-#include "cw_device.h"
+#include "cw_host.h"
 #include "launch_plan.h"
-#include "stream_scratch.h"
+
+using namespace cw::host;
 
 namespace {
-
 thread_local char t_err[512] = "";
 
-int fail(int code, const char *fmt, ...)
+// ---- optional per-thread kernel timing (cw_profile_*): HIP events on the stream each kernel is launched on ----
+struct ProfSpan { int kind; hipEvent_t a, b; };
+thread_local bool t_prof_on = false;
+thread_local std::vector<ProfSpan> t_prof;
+} // namespace
+
+int cw::host::fail(int code, const char *fmt, ...)
 {
     va_list ap;
     va_start(ap, fmt);
@@ -43,34 +45,26 @@ int fail(int code, const char *fmt, ...)
     return code;
 }
 
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return fail(CW_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));     \
-    } while (0)
+int cw::host::launched(hipError_t e, const char *what) { return e == hipSuccess ? CW_OK : fail(CW_ERR_HIP, "%s: %s", what, hipGetErrorString(e)); }
+int cw::host::launched_nomem(hipError_t e, const char *what)
+{
+    return e == hipErrorOutOfMemory ? fail(CW_ERR_NOMEM, "%s: %s", what, hipGetErrorString(e)) : launched(e, what);
+}
 
-// ---- optional per-thread kernel timing (cw_profile_*): HIP events on the stream each kernel is launched on ----
-enum { PROF_CODEC = 0, PROF_HASH = 1, PROF_OTHER = 2, PROF_KINDS = 3 };
-struct ProfSpan { int kind; hipEvent_t a, b; };
-thread_local bool t_prof_on = false;
-thread_local std::vector<ProfSpan> t_prof;
-
-struct ProfScope { // brackets the launches made during its lifetime on `stream`
-    int kind; hipStream_t stream; hipEvent_t a = nullptr;
-    ProfScope(int k, hipStream_t s) : kind(k), stream(s)
-    {
-        if (t_prof_on && hipEventCreate(&a) == hipSuccess) (void)hipEventRecord(a, stream);
-    }
-    ~ProfScope()
-    {
-        if (!a) return;
-        hipEvent_t b = nullptr;
-        if (hipEventCreate(&b) == hipSuccess) { (void)hipEventRecord(b, stream); t_prof.push_back({kind, a, b}); }
-        else (void)hipEventDestroy(a);
-    }
-};
+cw::host::ProfScope::ProfScope(int k, hipStream_t s) : kind(k), stream(s)
+{
+    if (t_prof_on && hipEventCreate(&a) == hipSuccess) (void)hipEventRecord(a, stream);
+}
+cw::host::ProfScope::~ProfScope()
+{
+    if (!a) return;
+    hipEvent_t b = nullptr;
+    if (hipEventCreate(&b) == hipSuccess) { (void)hipEventRecord(b, stream); t_prof.push_back({kind, a, b}); }
+    else (void)hipEventDestroy(a);
+}
 
 // ---- devices ----------------------------------------------------------------------------------------
+namespace {
 constexpr int kMaxDevices = 16;
 std::mutex g_lock;
 std::atomic<int> g_default{-1};        // first initialised device: what threads use that never chose one
@@ -78,15 +72,15 @@ std::atomic<uint32_t> g_mask{0};       // initialised devices
 thread_local int t_device = -1;        // the calling thread's device (cw_init / cw_set_device), -1 = g_default
 cw::SkeinIV g_iv512_512, g_iv256_128;  // host-computed, device independent
 std::atomic<size_t> g_block_size{4096}; // the reference's global blockSize (:89)
+} // namespace
 
-int current_device()
+int cw::host::current_device()
 {
     const int d = t_device;
     return d >= 0 && ((g_mask.load(std::memory_order_acquire) >> d) & 1u) ? d : g_default.load(std::memory_order_acquire);
 }
 
-// every entry point: initialise on first use and make the library's device the calling thread's HIP device
-int ensure_init()
+int cw::host::ensure_init()
 {
     int d = current_device();
     if (d < 0) {
@@ -98,18 +92,10 @@ int ensure_init()
     return CW_OK;
 }
 
+const cw::SkeinIV &cw::host::skein_iv(int nw) { return nw == 8 ? g_iv512_512 : g_iv256_128; }
+
 // ---- per-(thread, device) context ---------------------------------------------------------------------
-struct DevBuf { // cw::DeviceBuf with a floor of 1 MiB and the library's error codes; p = the buffer, for the many places that pass it on
-    cw::DeviceBuf buf;
-    void *p = nullptr;
-    int reserve(size_t n)
-    {
-        const hipError_t e = buf.reserve(n, (size_t)1 << 20);
-        p = buf.as<void>();
-        return e == hipSuccess ? CW_OK : fail(CW_ERR_NOMEM, "hipMalloc(%zu): %s", n < (1u << 20) ? (size_t)1 << 20 : n, hipGetErrorString(e));
-    }
-    void release() { (void)buf.release(); p = nullptr; }
-};
+namespace {
 struct PinnedBuf { // page-locked host staging: the only kind of host memory a copy engine reads or writes at bus speed
     void *p = nullptr;
     size_t cap = 0;
@@ -221,27 +207,39 @@ int thread_ctx(ThreadCtx **out)
 }
 
 const size_t kMaxChunkBytes = (size_t)256 << 20; // host-API staging granularity
+} // namespace
 
-int check_block(size_t block_bytes)
+int cw::host::ctx_stream(hipStream_t *s)
+{
+    ThreadCtx *c;
+    const int rc = thread_ctx(&c);
+    if (rc == CW_OK) *s = c->stream;
+    return rc;
+}
+
+int cw::host::check_block(size_t block_bytes)
 {
     if (block_bytes > CW_MAX_BLOCK_BYTES) return fail(CW_ERR_BAD_ARG, "block_bytes %zu > %u", block_bytes, CW_MAX_BLOCK_BYTES);
     return CW_OK;
 }
+int cw::host::check_codec(int comp_alg)
+{
+    return comp_alg == CW_COMP_LZ4 || comp_alg == CW_COMP_LZF ? CW_OK : fail(CW_ERR_BAD_ARG, "unknown compression algorithm %d", comp_alg);
+}
+int cw::host::check_count(const char *name, size_t n)
+{
+    return n <= ((size_t)1 << 32) - 256 ? CW_OK : fail(CW_ERR_BAD_ARG, "%s %zu > 2^32 - 256", name, n);
+}
 
-// sliced: long Skein messages (>= 256 steps, >= 4096 blocks) are hashed in several launches of short-lived wavefronts
-int dev_hash(int alg, const uint8_t *d_src, size_t bb, size_t stride, size_t n, uint8_t *d_dig, hipStream_t s, bool lean = false,
-             bool sliced = false)
+int cw::host::dev_hash(int alg, const uint8_t *d_src, size_t bb, size_t stride, size_t n, uint8_t *d_dig, hipStream_t s, bool lean, bool sliced)
 {
     hipError_t e;
     ProfScope prof(PROF_HASH, s);
     // CW_SKEIN_SLICED=0: always the one-launch hash kernel (profiling knob)
     if (sliced && cw::knobs().skein_sliced && (alg == CW_HASH_SKEIN512 || alg == CW_HASH_SKEIN256_128)) {
         const int nw = alg == CW_HASH_SKEIN512 ? 8 : 4;
-        if (cw::skein_sliced_applies(nw, d_src, bb, stride, n, d_dig)) {
-            e = cw::skein_sliced_launch(nw, d_src, bb, stride, n, nw == 8 ? g_iv512_512 : g_iv256_128, d_dig, nw == 8 ? 64 : 16, s);
-            if (e != hipSuccess) return fail(CW_ERR_HIP, "hash launch: %s", hipGetErrorString(e));
-            return CW_OK;
-        }
+        if (cw::skein_sliced_applies(nw, d_src, bb, stride, n, d_dig))
+            return launched(cw::skein_sliced_launch(nw, d_src, bb, stride, n, skein_iv(nw), d_dig, nw == 8 ? 64 : 16, s), "hash launch");
     }
     switch (alg) {
     case CW_HASH_SKEIN512: e = cw::skein512_launch(d_src, bb, stride, n, g_iv512_512, d_dig, 64, s, lean); break;
@@ -250,26 +248,24 @@ int dev_hash(int alg, const uint8_t *d_src, size_t bb, size_t stride, size_t n, 
     case CW_HASH_NONE: return CW_OK;
     default: return fail(CW_ERR_BAD_ARG, "unknown hash algorithm %d", alg);
     }
-    if (e != hipSuccess) return fail(CW_ERR_HIP, "hash launch: %s", hipGetErrorString(e));
-    return CW_OK;
+    return launched(e, "hash launch");
 }
 
-int dev_compress(int alg, const uint8_t *d_src, size_t bb, size_t stride, size_t n, uint8_t *d_dst, size_t dst_stride,
-                 uint32_t *d_sizes, hipStream_t s, const cw::AfterScan *after_scan = nullptr)
+int cw::host::dev_compress(int alg, const uint8_t *d_src, size_t bb, size_t stride, size_t n, uint8_t *d_dst, size_t dst_stride,
+                           uint32_t *d_sizes, hipStream_t s, const cw::AfterScan *after_scan)
 {
-    hipError_t e;
     if (alg == CW_COMP_NONE) return CW_OK;
-    if (alg != CW_COMP_LZ4 && alg != CW_COMP_LZF) return fail(CW_ERR_BAD_ARG, "unknown compression algorithm %d", alg);
+    if (int rc = check_codec(alg)) return rc;
     if (bb == 0) return fail(CW_ERR_BAD_ARG, "compression needs block_bytes > 0");
     if (dst_stride < cw_compress_bound(alg, bb))
         return fail(CW_ERR_BAD_ARG, "dst_stride %zu < bound %zu", dst_stride, cw_compress_bound(alg, bb));
     ProfScope prof(PROF_CODEC, s);
-    e = alg == CW_COMP_LZ4 ? cw::lz4_launch(d_src, bb, stride, n, d_dst, dst_stride, d_sizes, s, after_scan)
-                           : cw::lzf_launch(d_src, bb, stride, n, d_dst, dst_stride, d_sizes, s);
-    if (e != hipSuccess) return fail(CW_ERR_HIP, "compress launch: %s", hipGetErrorString(e));
-    return CW_OK;
+    return launched(alg == CW_COMP_LZ4 ? cw::lz4_launch(d_src, bb, stride, n, d_dst, dst_stride, d_sizes, s, after_scan)
+                                       : cw::lzf_launch(d_src, bb, stride, n, d_dst, dst_stride, d_sizes, s),
+                    "compress launch");
 }
 
+namespace {
 thread_local char t_kernels[2][320] = {"", ""};
 
 [[noreturn]] void die(const char *what)
@@ -398,7 +394,7 @@ void cw_tune_reset(void)
 
 int cw_plan_describe(int comp_alg, size_t block_bytes, size_t nblocks, unsigned src_misalign, unsigned dst_misalign, char *buf, size_t cap)
 {
-    if (comp_alg != CW_COMP_LZ4 && comp_alg != CW_COMP_LZF) return fail(CW_ERR_BAD_ARG, "unknown compression algorithm %d", comp_alg);
+    if (int bad = check_codec(comp_alg)) return bad;
     if (!(comp_alg == CW_COMP_LZ4 ? cw::lz4_call_valid(block_bytes, nblocks) : cw::lzf_call_valid(block_bytes, nblocks)))
         return fail(CW_ERR_BAD_ARG, "cw_plan_describe: %zu blocks of %zu bytes is not a call the codec accepts", nblocks, block_bytes);
     const cw::CodecCall call = {(uint32_t)block_bytes, nblocks, (unsigned)((src_misalign | block_bytes) & 15), (unsigned)((src_misalign | block_bytes) & 3), dst_misalign & 15};
@@ -604,12 +600,10 @@ int cw_dev_decompress(int comp_alg, const void *d_comp, size_t comp_stride, cons
     if (rc != CW_OK) return rc;
     if (nblocks == 0) return CW_OK;
     if (!d_comp || !d_sizes || !d_dst || !d_status) return fail(CW_ERR_BAD_ARG, "NULL device pointer");
-    if (comp_alg != CW_COMP_LZ4 && comp_alg != CW_COMP_LZF) return fail(CW_ERR_BAD_ARG, "unknown compression algorithm %d", comp_alg);
+    if (int bad = check_codec(comp_alg)) return bad;
     if (block_bytes == 0 || (rc = check_block(block_bytes)) != CW_OK) return rc ? rc : fail(CW_ERR_BAD_ARG, "block_bytes == 0");
-    hipError_t e = cw::decompress_launch(comp_alg == CW_COMP_LZ4 ? 0 : 1, (const uint8_t *)d_comp, comp_stride, d_sizes, nblocks,
-                                         (uint8_t *)d_dst, block_bytes, d_status, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(CW_ERR_HIP, "decompress launch: %s", hipGetErrorString(e));
-    return CW_OK;
+    return launched(cw::decompress_launch(comp_alg == CW_COMP_LZ4 ? 0 : 1, (const uint8_t *)d_comp, comp_stride, d_sizes, nblocks,
+                                         (uint8_t *)d_dst, block_bytes, d_status, (hipStream_t)stream), "decompress launch");
 }
 
 int cw_dev_hash_tree(int hash_alg, const void *d_src, size_t block_bytes, size_t src_stride, size_t nblocks, unsigned leaf, unsigned node,
@@ -625,8 +619,7 @@ int cw_dev_hash_tree(int hash_alg, const void *d_src, size_t block_bytes, size_t
                                          src_stride ? src_stride : block_bytes, nblocks, hash_alg == CW_HASH_SKEIN512 ? 512u : 128u, leaf,
                                          node, max_level, (uint8_t *)d_digests, (hipStream_t)stream);
     if (e == hipErrorInvalidValue) return fail(CW_ERR_BAD_ARG, "tree parameters leaf=%u node=%u maxLevel=%u not usable for %zu-byte blocks", leaf, node, max_level, block_bytes);
-    if (e != hipSuccess) return fail(CW_ERR_HIP, "tree hash launch: %s", hipGetErrorString(e));
-    return CW_OK;
+    return launched(e, "tree hash launch");
 }
 
 int cw_dev_pack(const void *d_slots, size_t slot_stride, const uint32_t *d_sizes, size_t nblocks, void *d_packed, uint64_t *d_offsets,
@@ -635,32 +628,26 @@ int cw_dev_pack(const void *d_slots, size_t slot_stride, const uint32_t *d_sizes
     int rc = ensure_init();
     if (rc != CW_OK) return rc;
     if (!d_offsets || (nblocks && (!d_sizes || (d_packed && !d_slots)))) return fail(CW_ERR_BAD_ARG, "NULL device pointer");
-    hipError_t e = cw::pack_launch((const uint8_t *)d_slots, slot_stride, d_sizes, nblocks, (uint8_t *)d_packed, d_offsets,
-                                   (hipStream_t)stream);
-    if (e != hipSuccess) return fail(CW_ERR_HIP, "pack launch: %s", hipGetErrorString(e));
-    return CW_OK;
+    return launched(cw::pack_launch((const uint8_t *)d_slots, slot_stride, d_sizes, nblocks, (uint8_t *)d_packed, d_offsets,
+                                   (hipStream_t)stream), "pack launch");
 }
 
+static int dev_gen(bool mixed, uint64_t seed, uint64_t first_block, size_t nblocks, size_t block_bytes, void *d_dst, hipStream_t s)
+{
+    if (int rc = ensure_init()) return rc;
+    if (!d_dst) return fail(CW_ERR_BAD_ARG, "NULL device pointer");
+    if (block_bytes % 16 || block_bytes > CW_MAX_BLOCK_BYTES) return fail(CW_ERR_BAD_ARG, "block_bytes must be a multiple of 16, <= 65536");
+    return launched(mixed ? cw::gen_mixed_launch(seed, first_block, nblocks, block_bytes, (uint8_t *)d_dst, s)
+                          : cw::gen_random_launch(seed, first_block, nblocks, block_bytes, (uint8_t *)d_dst, s),
+                    "gen launch");
+}
 int cw_dev_gen_random(uint64_t seed, uint64_t first_block, size_t nblocks, size_t block_bytes, void *d_dst, void *stream)
 {
-    int rc = ensure_init();
-    if (rc != CW_OK) return rc;
-    if (!d_dst) return fail(CW_ERR_BAD_ARG, "NULL device pointer");
-    if (block_bytes % 16 || block_bytes > CW_MAX_BLOCK_BYTES) return fail(CW_ERR_BAD_ARG, "block_bytes must be a multiple of 16, <= 65536");
-    hipError_t e = cw::gen_random_launch(seed, first_block, nblocks, block_bytes, (uint8_t *)d_dst, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(CW_ERR_HIP, "gen launch: %s", hipGetErrorString(e));
-    return CW_OK;
+    return dev_gen(false, seed, first_block, nblocks, block_bytes, d_dst, (hipStream_t)stream);
 }
-
 int cw_dev_gen_mixed(uint64_t seed, uint64_t first_block, size_t nblocks, size_t block_bytes, void *d_dst, void *stream)
 {
-    int rc = ensure_init();
-    if (rc != CW_OK) return rc;
-    if (!d_dst) return fail(CW_ERR_BAD_ARG, "NULL device pointer");
-    if (block_bytes % 16 || block_bytes > CW_MAX_BLOCK_BYTES) return fail(CW_ERR_BAD_ARG, "block_bytes must be a multiple of 16, <= 65536");
-    hipError_t e = cw::gen_mixed_launch(seed, first_block, nblocks, block_bytes, (uint8_t *)d_dst, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(CW_ERR_HIP, "gen launch: %s", hipGetErrorString(e));
-    return CW_OK;
+    return dev_gen(true, seed, first_block, nblocks, block_bytes, d_dst, (hipStream_t)stream);
 }
 
 int cw_dev_sum_sizes(const uint32_t *d_sizes, size_t nblocks, uint32_t raw_bytes, uint64_t *d_totals, void *stream)
@@ -668,9 +655,7 @@ int cw_dev_sum_sizes(const uint32_t *d_sizes, size_t nblocks, uint32_t raw_bytes
     int rc = ensure_init();
     if (rc != CW_OK) return rc;
     if (!d_sizes || !d_totals) return fail(CW_ERR_BAD_ARG, "NULL device pointer");
-    hipError_t e = cw::sum_sizes_launch(d_sizes, nblocks, raw_bytes, d_totals, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(CW_ERR_HIP, "sum launch: %s", hipGetErrorString(e));
-    return CW_OK;
+    return launched(cw::sum_sizes_launch(d_sizes, nblocks, raw_bytes, d_totals, (hipStream_t)stream), "sum launch");
 }
 
 // plain device memory for C callers of the cw_dev_* functions (the host programs link no HIP runtime themselves)
@@ -794,6 +779,23 @@ const Slot *shared_lender(const cw::Knobs &kn, ThreadCtx &c, const HostJob &j, c
     return c.slot[0].open() == CW_OK ? &c.slot[0] : nullptr;
 }
 
+// the kernels of a chunk of n blocks in the slot's device buffers: codec and hash, then the pack of the slots (a hash-only job has no
+// slots, sizes or packed stream to touch)
+int slot_kernels(const HostJob &j, Slot &s, size_t n)
+{
+    int rc;
+    if (j.do_comp && j.do_hash)
+        rc = dev_fused(s.side, j.hash_alg, j.comp_alg, (const uint8_t *)s.src.p, j.bb, j.bb, n, (uint8_t *)s.dig.p, (uint8_t *)s.dst.p,
+                       j.d_stride, (uint32_t *)s.sizes.p, s.stream);
+    else if (j.do_comp)
+        rc = dev_compress(j.comp_alg, (const uint8_t *)s.src.p, j.bb, j.bb, n, (uint8_t *)s.dst.p, j.d_stride, (uint32_t *)s.sizes.p, s.stream);
+    else
+        rc = dev_hash(j.hash_alg, (const uint8_t *)s.src.p, j.bb, j.bb, n, (uint8_t *)s.dig.p, s.stream, false, true);
+    if (rc != CW_OK || !j.do_comp) return rc;
+    return launched(cw::pack_launch((const uint8_t *)s.dst.p, j.d_stride, (const uint32_t *)s.sizes.p, n, (uint8_t *)s.pack.p, (uint64_t *)s.offs.p, s.stream),
+                    "pack launch");
+}
+
 int pipe_issue(const cw::Knobs &kn, ThreadCtx &c, HostJob &j, Slot &s, size_t first, size_t n)
 {
     int rc = slot_reserve(j, s, n, !j.src_pinned, !(j.packed && j.packed_pinned), shared_lender(kn, c, j, s));
@@ -809,18 +811,8 @@ int pipe_issue(const cw::Knobs &kn, ThreadCtx &c, HostJob &j, Slot &s, size_t fi
     HIP_TRY(hipEventRecord(s.ev_h2d, c.s_h2d));
     HIP_TRY(hipStreamWaitEvent(s.stream, s.ev_h2d, 0));
     uint8_t *meta = (uint8_t *)s.h_meta.p;
-    if (j.do_comp && j.do_hash)
-        rc = dev_fused(s.side, j.hash_alg, j.comp_alg, (const uint8_t *)s.src.p, j.bb, j.bb, n, (uint8_t *)s.dig.p, (uint8_t *)s.dst.p,
-                       j.d_stride, (uint32_t *)s.sizes.p, s.stream);
-    else if (j.do_comp)
-        rc = dev_compress(j.comp_alg, (const uint8_t *)s.src.p, j.bb, j.bb, n, (uint8_t *)s.dst.p, j.d_stride, (uint32_t *)s.sizes.p, s.stream);
-    else
-        rc = dev_hash(j.hash_alg, (const uint8_t *)s.src.p, j.bb, j.bb, n, (uint8_t *)s.dig.p, s.stream, false, true);
-    if (rc != CW_OK) return rc;
+    if ((rc = slot_kernels(j, s, n)) != CW_OK) return rc;
     if (j.do_comp) {
-        hipError_t pe = cw::pack_launch((const uint8_t *)s.dst.p, j.d_stride, (const uint32_t *)s.sizes.p, n, (uint8_t *)s.pack.p, (uint64_t *)s.offs.p,
-                                        s.stream);
-        if (pe != hipSuccess) return fail(CW_ERR_HIP, "pack launch: %s", hipGetErrorString(pe));
         HIP_TRY(hipMemcpyAsync(meta, s.sizes.p, n * 4, hipMemcpyDeviceToHost, s.stream));
         HIP_TRY(hipMemcpyAsync(meta + meta_off_total(n), (const uint64_t *)s.offs.p + n, 8, hipMemcpyDeviceToHost, s.stream));
     }
@@ -1033,7 +1025,7 @@ int cw_hash_and_compress_blocks(int hash_alg, int comp_alg, const void *src, siz
 int cw_hash_and_compress_packed(int hash_alg, int comp_alg, const void *src, size_t block_bytes, size_t nblocks, void *digests,
                                 void *packed, size_t packed_cap, uint64_t *offsets, uint32_t *sizes)
 {
-    if (comp_alg != CW_COMP_LZ4 && comp_alg != CW_COMP_LZF) return fail(CW_ERR_BAD_ARG, "unknown compression algorithm %d", comp_alg);
+    if (int bad = check_codec(comp_alg)) return bad;
     if (nblocks && (!packed || !offsets || !sizes)) return fail(CW_ERR_BAD_ARG, "NULL packed/offsets/sizes");
     HostJob j;
     int rc = host_job_init(j, hash_alg, comp_alg, src, block_bytes, nblocks, digests, true);
@@ -1066,21 +1058,8 @@ int cw_prepare(int hash_alg, int comp_alg, size_t block_bytes, size_t nblocks, i
     // idle clocks.  Then a few copies each way to wake the link (the first pass after idle ran at 25-29 GB/s against 45.7).
     // CW_PREPARE_COLD=1 skips both.
     if (kn.prepare_cold) return CW_OK;
-    for (Slot &s : c->slot) { // the same predicates as pipe_issue: a hash-only job has no slots, sizes or packed stream to touch
-        if (j.do_comp && j.do_hash)
-            rc = dev_fused(s.side, hash_alg, comp_alg, (const uint8_t *)s.src.p, block_bytes, block_bytes, chunk, (uint8_t *)s.dig.p,
-                           (uint8_t *)s.dst.p, j.d_stride, (uint32_t *)s.sizes.p, s.stream);
-        else if (j.do_comp)
-            rc = dev_compress(comp_alg, (const uint8_t *)s.src.p, block_bytes, block_bytes, chunk, (uint8_t *)s.dst.p, j.d_stride, (uint32_t *)s.sizes.p, s.stream);
-        else
-            rc = dev_hash(hash_alg, (const uint8_t *)s.src.p, block_bytes, block_bytes, chunk, (uint8_t *)s.dig.p, s.stream, false, true);
-        if (rc != CW_OK) return rc;
-        if (j.do_comp) {
-            hipError_t pe = cw::pack_launch((const uint8_t *)s.dst.p, j.d_stride, (const uint32_t *)s.sizes.p, chunk, (uint8_t *)s.pack.p, (uint64_t *)s.offs.p,
-                                            s.stream);
-            if (pe != hipSuccess) return fail(CW_ERR_HIP, "pack launch: %s", hipGetErrorString(pe));
-        }
-    }
+    for (Slot &s : c->slot)
+        if ((rc = slot_kernels(j, s, chunk)) != CW_OK) return rc;
     void *h = nullptr;
     const size_t wb = (size_t)64 << 20 < chunk * block_bytes ? (size_t)64 << 20 : chunk * block_bytes;
     if (hipHostMalloc(&h, 2 * wb, hipHostMallocPortable) == hipSuccess) {
@@ -1155,7 +1134,7 @@ int cw_compress_blocks(int comp_alg, const void *src, size_t block_bytes, size_t
                        uint32_t *sizes)
 {
     if ((!dst || !sizes) && nblocks) return fail(CW_ERR_BAD_ARG, "NULL dst/sizes");
-    if (comp_alg != CW_COMP_LZ4 && comp_alg != CW_COMP_LZF) return fail(CW_ERR_BAD_ARG, "unknown compression algorithm %d", comp_alg);
+    if (int bad = check_codec(comp_alg)) return bad;
     return cw_hash_and_compress_blocks(CW_HASH_NONE, comp_alg, src, block_bytes, nblocks, nullptr, dst, dst_stride, sizes);
 }
 
@@ -1168,7 +1147,7 @@ int cw_decompress_blocks(int comp_alg, const void *comp, size_t comp_stride, con
     ThreadCtx &c = *cp;
     if (nblocks == 0) return CW_OK;
     if (!comp || !sizes || !dst || !status) return fail(CW_ERR_BAD_ARG, "NULL pointer");
-    if (comp_alg != CW_COMP_LZ4 && comp_alg != CW_COMP_LZF) return fail(CW_ERR_BAD_ARG, "unknown compression algorithm %d", comp_alg);
+    if (int bad = check_codec(comp_alg)) return bad;
     if (block_bytes == 0 || (rc = check_block(block_bytes)) != CW_OK) return rc ? rc : fail(CW_ERR_BAD_ARG, "block_bytes == 0");
     const size_t d_stride = (comp_stride + 15) & ~(size_t)15;
     size_t chunk = kMaxChunkBytes / (d_stride + block_bytes + 8);
@@ -1249,278 +1228,6 @@ unsigned cw_decompress_lzf(const void *src, unsigned csize, void *dst, unsigned 
     return st == 0 ? (unsigned)bb : 0;
 }
 
-// ---- content-defined chunking (kernels: cdc_kernels.hip; semantics: the header) ------------------------------------------
-namespace {
-
-uint64_t splitmix64_host(uint64_t x)
-{
-    uint64_t z = x + 0x9E3779B97F4A7C15ULL;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
-struct DefaultGear {
-    uint64_t g[256];
-    DefaultGear() { for (int v = 0; v < 256; v++) g[v] = splitmix64_host((uint64_t)v); }
-};
-const DefaultGear kDefaultGear;
-
-int cdc_params(const cw_cdc_params *p, cw::CdcParams *out)
-{
-    if (!p) return fail(CW_ERR_BAD_ARG, "NULL cdc params");
-    if (p->reserved != 0) return fail(CW_ERR_BAD_ARG, "cdc params: reserved must be 0");
-    if (!(64 <= p->min_size && p->min_size <= p->normal_size && p->normal_size <= p->max_size && p->max_size <= (1u << 24)))
-        return fail(CW_ERR_BAD_ARG, "cdc params: need 64 <= min %u <= normal %u <= max %u <= 2^24", p->min_size, p->normal_size, p->max_size);
-    *out = cw::CdcParams{p->min_size, p->normal_size, p->max_size, p->mask_s, p->mask_l, p->gear ? p->gear : kDefaultGear.g};
-    return CW_OK;
-}
-
-int dev_cdc(const cw::CdcParams &p, const uint8_t *d_src, size_t nbytes, int final_, uint64_t *d_offsets, size_t max_offsets,
-            uint64_t *d_nchunks, hipStream_t s)
-{
-    const uint64_t seg = cw::cdc_segment_bytes(p.max_size, cw::knobs().cdc_segment);
-    ProfScope prof(PROF_HASH, s);
-    hipError_t e = cw::cdc_launch(p, d_src, nbytes, final_, d_offsets, max_offsets, d_nchunks, seg, s);
-    if (e == hipErrorOutOfMemory) return fail(CW_ERR_NOMEM, "cdc workspace (%zu bytes): %s", cw::cdc_workspace_bytes(nbytes, p.min_size, seg),
-                                              hipGetErrorString(e));
-    if (e != hipSuccess) return fail(CW_ERR_HIP, "cdc launch: %s", hipGetErrorString(e));
-    return CW_OK;
-}
-
-int dev_hash_chunks(int alg, const uint8_t *d_src, size_t src_bytes, const uint64_t *d_offsets, const uint64_t *d_nchunks, size_t max_chunks,
-                    uint8_t *d_dig, hipStream_t s)
-{
-    if (alg == CW_HASH_NONE) return CW_OK;
-    if (alg != CW_HASH_SKEIN512 && alg != CW_HASH_SKEIN256_128 && alg != CW_HASH_SHA256) return fail(CW_ERR_BAD_ARG, "unknown hash algorithm %d", alg);
-    if (max_chunks > 0xFFFFFF00u) return fail(CW_ERR_BAD_ARG, "max_chunks %zu > 2^32 - 256", max_chunks);
-    if (max_chunks == 0) return CW_OK;
-    ProfScope prof(PROF_HASH, s);
-    struct Call { int alg; const uint8_t *src; size_t src_bytes; const uint64_t *off, *n; size_t max; uint8_t *dig; hipStream_t s; };
-    Call call{alg, d_src, src_bytes, d_offsets, d_nchunks, max_chunks, d_dig, s};
-    const cw::ChunkHash hash{[](void *ctx, const uint32_t *perm) {
-                                 const Call &k = *static_cast<const Call *>(ctx);
-                                 if (k.alg == CW_HASH_SHA256) return cw::sha256_chunks_launch(k.src, k.src_bytes, k.off, perm, k.n, k.max, k.dig, k.s);
-                                 if (k.alg == CW_HASH_SKEIN512)
-                                     return cw::skein_chunks_launch(8, k.src, k.src_bytes, k.off, perm, k.n, k.max, g_iv512_512, k.dig, 64, k.s);
-                                 return cw::skein_chunks_launch(4, k.src, k.src_bytes, k.off, perm, k.n, k.max, g_iv256_128, k.dig, 16, k.s);
-                             },
-                             &call};
-    // the step counts the sort orders by: 64-byte steps (Skein-512, SHA-256) or 32-byte steps (Skein-256)
-    const hipError_t e = cw::chunk_hash_launch(d_offsets, d_nchunks, max_chunks, src_bytes, alg == CW_HASH_SKEIN256_128 ? 5 : 6, hash, s);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? CW_ERR_NOMEM : CW_ERR_HIP, "hash chunks launch: %s", hipGetErrorString(e));
-    return CW_OK;
-}
-
-// chunk indices are u32 on the device (the order, d_sel), as the dedupe's block indices are
-constexpr size_t kMaxChunks = ((size_t)1 << 32) - 256;
-
-// everything cw_dev_compress_chunks refuses, none of it needing a device
-int compress_chunks_args(int comp_alg, const void *d_src, size_t src_bytes, const uint64_t *d_offsets, const uint64_t *d_nchunks,
-                         size_t max_chunks, const uint32_t *d_sel, const uint64_t *d_nsel, const void *d_dst, size_t dst_bytes,
-                         const uint32_t *d_sizes)
-{
-    if (comp_alg != CW_COMP_LZ4 && comp_alg != CW_COMP_LZF) return fail(CW_ERR_BAD_ARG, "unknown compression algorithm %d", comp_alg);
-    if (max_chunks > kMaxChunks) return fail(CW_ERR_BAD_ARG, "max_chunks %zu > 2^32 - 256", max_chunks);
-    if (src_bytes > ((size_t)1 << 62)) return fail(CW_ERR_BAD_ARG, "src_bytes %zu not usable", src_bytes);
-    if (!d_offsets || !d_nchunks || !d_dst || !d_sizes || (src_bytes && !d_src) || (d_sel && !d_nsel)) return fail(CW_ERR_BAD_ARG, "NULL pointer");
-    const size_t need = (size_t)cw::chunk_slot_offset(comp_alg == CW_COMP_LZ4, src_bytes, max_chunks) + 16;
-    if (dst_bytes < need) return fail(CW_ERR_BAD_ARG, "dst_bytes %zu < cw_chunk_slots_bytes = %zu", dst_bytes, need);
-    return CW_OK;
-}
-
-int dev_compress_chunks(int comp_alg, const uint8_t *d_src, size_t src_bytes, const uint64_t *d_offsets, const uint64_t *d_nchunks,
-                        size_t max_chunks, const uint32_t *d_sel, const uint64_t *d_nsel, uint8_t *d_dst, uint32_t *d_sizes, hipStream_t s)
-{
-    ProfScope prof(PROF_CODEC, s);
-    const hipError_t e = cw::chunk_compress_launch(comp_alg == CW_COMP_LZF, d_src, src_bytes, d_offsets, d_nchunks, max_chunks, d_sel, d_nsel,
-                                                   d_dst, d_sizes, s);
-    if (e == hipErrorOutOfMemory)
-        return fail(CW_ERR_NOMEM, "chunk parser workspace (order %zu bytes, lane tables of %zu bytes each): %s", (2048 + max_chunks) * 4,
-                    cw::chunk_lane_table_bytes(comp_alg == CW_COMP_LZF), hipGetErrorString(e));
-    if (e != hipSuccess) return fail(CW_ERR_HIP, "compress chunks launch: %s", hipGetErrorString(e));
-    return CW_OK;
-}
-
-} // namespace
-
-extern "C" {
-
-void cw_cdc_default_params(cw_cdc_params *p, uint32_t normal_size)
-{
-    if (!p) return;
-    // normal_size is clamped to [256, 2^21] and rounded down to a power of two, so every field is defined and valid
-    unsigned lg = 8;
-    while (lg < 21 && (1u << (lg + 1)) <= normal_size) lg++;
-    const uint32_t normal = 1u << lg;
-    p->min_size = normal / 4;
-    p->normal_size = normal;
-    p->max_size = normal * 8;
-    p->reserved = 0;
-    p->mask_s = ~0ull << (64 - (lg + 2));
-    p->mask_l = ~0ull << (64 - (lg - 2));
-    p->gear = NULL;
-}
-
-int cw_dev_cdc(const cw_cdc_params *p, const void *d_src, size_t nbytes, int final, uint64_t *d_offsets, size_t max_offsets,
-               uint64_t *d_nchunks, void *stream)
-{
-    cw::CdcParams cp;
-    int rc = cdc_params(p, &cp);
-    if (rc != CW_OK) return rc;
-    if (!d_offsets || !d_nchunks || (nbytes && !d_src)) return fail(CW_ERR_BAD_ARG, "NULL pointer");
-    if (max_offsets < nbytes / cp.min_size + 2)
-        return fail(CW_ERR_BAD_ARG, "max_offsets %zu < nbytes / min_size + 2 = %zu", max_offsets, nbytes / cp.min_size + 2);
-    if ((rc = ensure_init()) != CW_OK) return rc;
-    return dev_cdc(cp, (const uint8_t *)d_src, nbytes, final ? 1 : 0, d_offsets, max_offsets, d_nchunks, (hipStream_t)stream);
-}
-
-int cw_dev_hash_chunks(int hash_alg, const void *d_src, size_t src_bytes, const uint64_t *d_offsets, const uint64_t *d_nchunks,
-                       size_t max_chunks, void *d_digests, void *stream)
-{
-    if (hash_alg < 0 || hash_alg > CW_HASH_NONE) return fail(CW_ERR_BAD_ARG, "unknown hash algorithm %d", hash_alg);
-    if (hash_alg != CW_HASH_NONE && max_chunks && (!d_offsets || !d_nchunks || !d_digests || (src_bytes && !d_src)))
-        return fail(CW_ERR_BAD_ARG, "NULL pointer");
-    int rc = ensure_init();
-    if (rc != CW_OK) return rc;
-    return dev_hash_chunks(hash_alg, (const uint8_t *)d_src, src_bytes, d_offsets, d_nchunks, max_chunks, (uint8_t *)d_digests,
-                           (hipStream_t)stream);
-}
-
-uint64_t cw_chunk_slot_offset(int comp_alg, uint64_t o, uint64_t i) { return cw::chunk_slot_offset(comp_alg != CW_COMP_LZF, o, i); }
-size_t cw_chunk_slots_bytes(int comp_alg, size_t src_bytes, size_t max_chunks)
-{
-    return (size_t)cw_chunk_slot_offset(comp_alg, src_bytes, max_chunks) + 16;
-}
-
-int cw_dev_compress_chunks(int comp_alg, const void *d_src, size_t src_bytes, const uint64_t *d_offsets, const uint64_t *d_nchunks,
-                           size_t max_chunks, const uint32_t *d_sel, const uint64_t *d_nsel, void *d_dst, size_t dst_bytes,
-                           uint32_t *d_sizes, void *stream)
-{
-    int rc = compress_chunks_args(comp_alg, d_src, src_bytes, d_offsets, d_nchunks, max_chunks, d_sel, d_nsel, d_dst, dst_bytes, d_sizes);
-    if (rc != CW_OK) return rc;
-    if ((rc = ensure_init()) != CW_OK) return rc;
-    return dev_compress_chunks(comp_alg, (const uint8_t *)d_src, src_bytes, d_offsets, d_nchunks, max_chunks, d_sel, d_nsel, (uint8_t *)d_dst,
-                               d_sizes, (hipStream_t)stream);
-}
-
-int cw_dev_pack_chunks(int comp_alg, const void *d_slots, const uint64_t *d_offsets, const uint32_t *d_sel, const uint64_t *d_count,
-                       size_t max_count, const uint32_t *d_sizes, void *d_packed, uint64_t *d_packed_offsets, void *stream)
-{
-    if (comp_alg != CW_COMP_LZ4 && comp_alg != CW_COMP_LZF) return fail(CW_ERR_BAD_ARG, "unknown compression algorithm %d", comp_alg);
-    if (max_count > kMaxChunks) return fail(CW_ERR_BAD_ARG, "max_count %zu > 2^32 - 256", max_count);
-    if (!d_packed_offsets || (max_count && (!d_count || !d_sizes || (d_packed && (!d_slots || !d_offsets)))))
-        return fail(CW_ERR_BAD_ARG, "NULL pointer");
-    int rc = ensure_init();
-    if (rc != CW_OK) return rc;
-    const hipError_t e = cw::chunk_pack_launch(comp_alg == CW_COMP_LZF, (const uint8_t *)d_slots, d_offsets, d_sel, d_count, max_count, d_sizes,
-                                               (uint8_t *)d_packed, d_packed_offsets, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? CW_ERR_NOMEM : CW_ERR_HIP, "pack chunks launch: %s", hipGetErrorString(e));
-    return CW_OK;
-}
-
-int cw_dev_decompress_chunks(int comp_alg, const void *d_comp, const uint64_t *d_comp_offsets, const uint64_t *d_raw_offsets,
-                             const uint64_t *d_count, size_t max_count, void *d_dst, size_t dst_bytes, uint32_t *d_status, void *stream)
-{
-    if (comp_alg != CW_COMP_LZ4 && comp_alg != CW_COMP_LZF) return fail(CW_ERR_BAD_ARG, "unknown compression algorithm %d", comp_alg);
-    if (max_count > kMaxChunks) return fail(CW_ERR_BAD_ARG, "max_count %zu > 2^32 - 256", max_count);
-    if (max_count && (!d_comp || !d_comp_offsets || !d_raw_offsets || !d_count || !d_status || (dst_bytes && !d_dst)))
-        return fail(CW_ERR_BAD_ARG, "NULL pointer");
-    int rc = ensure_init();
-    if (rc != CW_OK) return rc;
-    ProfScope prof(PROF_CODEC, (hipStream_t)stream);
-    const hipError_t e = cw::chunk_decompress_launch(comp_alg == CW_COMP_LZF, (const uint8_t *)d_comp, d_comp_offsets, d_raw_offsets, d_count,
-                                                     max_count, (uint8_t *)d_dst, dst_bytes, d_status, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(CW_ERR_HIP, "decompress chunks launch: %s", hipGetErrorString(e));
-    return CW_OK;
-}
-
-// ---- the chunk store (kernels: restore_kernels.hip; semantics: the header) -------------------------------------------------
-static_assert(sizeof(cw_chunk_loc) == 16, "cw_chunk_loc is one 16-byte store");
-
-int cw_dev_store_chunks(int comp_alg, const void *d_src, size_t src_bytes, const uint64_t *d_offsets, const uint64_t *d_nchunks,
-                        size_t max_chunks, const uint32_t *d_sel, const uint64_t *d_nsel, const void *d_slots, const uint32_t *d_sizes,
-                        uint64_t base, void *d_store, size_t store_bytes, uint64_t *d_used, cw_chunk_loc *d_dir, uint64_t dir_base,
-                        size_t dir_entries, uint64_t *d_result, void *stream)
-{
-    if (comp_alg != CW_COMP_LZ4 && comp_alg != CW_COMP_LZF) return fail(CW_ERR_BAD_ARG, "unknown compression algorithm %d", comp_alg);
-    if (max_chunks > kMaxChunks) return fail(CW_ERR_BAD_ARG, "max_chunks %zu > 2^32 - 256", max_chunks);
-    if (!d_offsets || !d_nchunks || !d_slots || !d_sizes || !d_used || !d_dir || !d_result || (src_bytes && !d_src) || (store_bytes && !d_store) ||
-        !d_sel != !d_nsel)
-        return fail(CW_ERR_BAD_ARG, "NULL pointer");
-    if (dir_entries == 0) return fail(CW_ERR_BAD_ARG, "dir_entries is 0");
-    if ((uintptr_t)d_dir & 15) return fail(CW_ERR_BAD_ARG, "d_dir is not 16-byte aligned");
-    if (((uintptr_t)d_used | (uintptr_t)d_result) & 7) return fail(CW_ERR_BAD_ARG, "d_used / d_result not 8-byte aligned");
-    int rc = ensure_init();
-    if (rc != CW_OK) return rc;
-    const hipError_t e = cw::chunk_store_launch(comp_alg == CW_COMP_LZF, (const uint8_t *)d_src, src_bytes, d_offsets, d_nchunks, max_chunks, d_sel,
-                                                d_nsel, (const uint8_t *)d_slots, d_sizes, base, (uint8_t *)d_store, store_bytes, d_used, d_dir,
-                                                dir_base, dir_entries, d_result, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? CW_ERR_NOMEM : CW_ERR_HIP, "store chunks launch: %s", hipGetErrorString(e));
-    return CW_OK;
-}
-
-int cw_dev_restore_chunks(int comp_alg, const void *d_store, size_t store_bytes, const cw_chunk_loc *d_dir, uint64_t dir_base,
-                          size_t dir_entries, const uint64_t *d_ref, const uint64_t *d_raw_offsets, const uint64_t *d_count, size_t max_count,
-                          void *d_dst, size_t dst_bytes, uint32_t *d_status, void *stream)
-{
-    if (comp_alg != CW_COMP_LZ4 && comp_alg != CW_COMP_LZF) return fail(CW_ERR_BAD_ARG, "unknown compression algorithm %d", comp_alg);
-    if (max_count > kMaxChunks) return fail(CW_ERR_BAD_ARG, "max_count %zu > 2^32 - 256", max_count);
-    if (!d_dir || !d_ref || !d_raw_offsets || !d_count || !d_status || (store_bytes && !d_store) || (dst_bytes && !d_dst))
-        return fail(CW_ERR_BAD_ARG, "NULL pointer");
-    if (dir_entries == 0) return fail(CW_ERR_BAD_ARG, "dir_entries is 0");
-    if ((uintptr_t)d_dir & 15) return fail(CW_ERR_BAD_ARG, "d_dir is not 16-byte aligned");
-    int rc = ensure_init();
-    if (rc != CW_OK) return rc;
-    ProfScope prof(PROF_CODEC, (hipStream_t)stream);
-    const hipError_t e = cw::chunk_restore_launch(comp_alg == CW_COMP_LZF, (const uint8_t *)d_store, store_bytes, d_dir, dir_base, dir_entries, d_ref,
-                                                  d_raw_offsets, d_count, max_count, (uint8_t *)d_dst, dst_bytes, d_status, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(CW_ERR_HIP, "restore chunks launch: %s", hipGetErrorString(e));
-    return CW_OK;
-}
-
-// ---- the chunk store forgets: mark and compact (kernels: store_gc_kernels.hip; semantics: the header) ------------------------
-// [a, a + an) and [b, b + bn) share a byte
-static bool ranges_overlap(const void *a, size_t an, const void *b, size_t bn)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return an && bn && x < y + bn && y < x + an;
-}
-
-int cw_dev_store_mark(const uint64_t *d_ref, const uint64_t *d_count, size_t max_count, uint64_t dir_base, size_t dir_entries, uint32_t *d_live,
-                      uint64_t *d_n_outside, void *stream)
-{
-    if (max_count > kMaxChunks) return fail(CW_ERR_BAD_ARG, "max_count %zu > 2^32 - 256", max_count);
-    if (!d_ref || !d_count || !d_live || !d_n_outside) return fail(CW_ERR_BAD_ARG, "NULL pointer");
-    if (dir_entries == 0) return fail(CW_ERR_BAD_ARG, "dir_entries is 0");
-    if ((uintptr_t)d_n_outside & 7) return fail(CW_ERR_BAD_ARG, "d_n_outside not 8-byte aligned");
-    int rc = ensure_init();
-    if (rc != CW_OK) return rc;
-    const hipError_t e = cw::store_mark_launch(d_ref, d_count, max_count, dir_base, dir_entries, d_live, d_n_outside, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(CW_ERR_HIP, "store mark launch: %s", hipGetErrorString(e));
-    return CW_OK;
-}
-
-int cw_dev_store_compact(const void *d_store, size_t store_bytes, const cw_chunk_loc *d_dir, size_t dir_entries, const uint32_t *d_live,
-                         void *d_new_store, size_t new_store_bytes, uint64_t *d_new_used, cw_chunk_loc *d_new_dir, uint64_t *d_result,
-                         void *stream)
-{
-    if (!d_dir || !d_live || !d_new_used || !d_new_dir || !d_result || (store_bytes && !d_store) || (new_store_bytes && !d_new_store))
-        return fail(CW_ERR_BAD_ARG, "NULL pointer");
-    if (dir_entries == 0) return fail(CW_ERR_BAD_ARG, "dir_entries is 0");
-    if (((uintptr_t)d_dir | (uintptr_t)d_new_dir) & 15) return fail(CW_ERR_BAD_ARG, "d_dir / d_new_dir is not 16-byte aligned");
-    if (((uintptr_t)d_new_used | (uintptr_t)d_result) & 7) return fail(CW_ERR_BAD_ARG, "d_new_used / d_result not 8-byte aligned");
-    if (ranges_overlap(d_store, store_bytes, d_new_store, new_store_bytes)) return fail(CW_ERR_BAD_ARG, "d_new_store overlaps d_store");
-    if (d_new_dir != d_dir && ranges_overlap(d_dir, dir_entries * sizeof(cw_chunk_loc), d_new_dir, dir_entries * sizeof(cw_chunk_loc)))
-        return fail(CW_ERR_BAD_ARG, "d_new_dir overlaps d_dir without being d_dir");
-    int rc = ensure_init();
-    if (rc != CW_OK) return rc;
-    const hipError_t e = cw::store_compact_launch((const uint8_t *)d_store, store_bytes, d_dir, dir_entries, d_live, (uint8_t *)d_new_store,
-                                                  new_store_bytes, d_new_used, d_new_dir, d_result, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? CW_ERR_NOMEM : CW_ERR_HIP, "store compact launch: %s", hipGetErrorString(e));
-    return CW_OK;
-}
-
 // Pieces of at most kMaxChunkBytes: each piece is chunked with final = 0 (the last with final = 1); the bytes after the last
 // cut of a piece -- fewer than max_size -- are copied to the front of the next piece's buffer.
 int cw_cdc_hash(const cw_cdc_params *p, int hash_alg, const void *src, size_t nbytes, uint64_t *offsets, size_t max_offsets,
@@ -1573,724 +1280,6 @@ int cw_cdc_hash(const cw_cdc_params *p, int hash_alg, const void *src, size_t nb
     }
     *nchunks = k_total;
     return CW_OK;
-}
-
-} // extern "C"
-
-// ---- dedupe index (kernels and protocol: dedupe_kernels.hip) -------------------------------------------------------
-struct cw_dedupe {
-    int device = -1, hash_alg = 0;
-    unsigned words = 0;              // u64 words per digest
-    size_t max_entries = 0;
-    uint64_t cap = 0;                // slots: a power of two >= 2 x max_entries
-    void *table = nullptr;           // one allocation: state | value | key | min_idx | ctrl
-    uint64_t *state = nullptr, *value = nullptr, *key = nullptr;
-    uint32_t *min_idx = nullptr;
-    uint64_t *ctrl = nullptr;        // [0] count, [1] a probe / lookup / rehash walk reached its bound, [2] n_new of the fused call
-    uint64_t *h_ctrl = nullptr;      // pinned: the fused call's copy of ctrl[1..2]
-    DevBuf rec, flags, offs, gather; // per-call scratch, shared by the calls because they are serialised
-    DevBuf stage_dig, stage_val, stage_out; // the host forms' pieces: digests | values | ref, new_idx, n_new of an import piece
-    size_t stage_entries = (size_t)1 << 20; // pairs per piece (cw_dedupe_set_stage_entries)
-    hipEvent_t last = nullptr;       // the last call's work: the next call's stream waits for it
-    uint64_t count_bound = 0;        // upper bound on ctrl[0] (every block of every call counted)
-    std::mutex lock;                 // guards `last`, the scratch and count_bound
-};
-
-namespace {
-// block indices are u32 on the device, and a launch of one lane per block must stay below 2^32 work-items
-constexpr size_t kMaxDedupeBlocks = ((size_t)1 << 32) - 256;
-
-// checks shared by the dedupe calls
-int dedupe_args(cw_dedupe *x, size_t nblocks, uint64_t base)
-{
-    int rc = ensure_init();
-    if (rc != CW_OK) return rc;
-    if (!x) return fail(CW_ERR_BAD_ARG, "NULL dedupe index");
-    if (current_device() != x->device) return fail(CW_ERR_BAD_ARG, "dedupe index of device %d used on device %d", x->device, current_device());
-    if (nblocks > kMaxDedupeBlocks) return fail(CW_ERR_BAD_ARG, "nblocks %zu > 2^32 - 256", nblocks);
-    if (base > UINT64_MAX - nblocks) return fail(CW_ERR_BAD_ARG, "base + nblocks wraps");
-    return CW_OK;
-}
-
-// x->lock held: refuse a call that could overflow the table.  The host bound only grows, so only when it would refuse is the
-// exact count read (after the last call has finished).
-int dedupe_admit(cw_dedupe *x, size_t n)
-{
-    if (x->count_bound + n <= x->max_entries) return CW_OK;
-    HIP_TRY(hipEventSynchronize(x->last));
-    uint64_t c[2];
-    HIP_TRY(hipMemcpy(c, x->ctrl, sizeof c, hipMemcpyDeviceToHost));
-    if (c[1]) return fail(CW_ERR_HIP, "dedupe index: a probe reached its bound (the table is inconsistent)");
-    x->count_bound = c[0];
-    if (c[0] + n > x->max_entries)
-        return fail(CW_ERR_NOMEM, "dedupe index full: %llu entries + %zu blocks > max_entries %zu", (unsigned long long)c[0], n, x->max_entries);
-    return CW_OK;
-}
-
-// x->lock held: the shared "index is inconsistent" check of a copy of ctrl[0..1]
-int dedupe_read_count(cw_dedupe *x, uint64_t *count)
-{
-    HIP_TRY(hipEventSynchronize(x->last));
-    uint64_t c[2];
-    HIP_TRY(hipMemcpy(c, x->ctrl, sizeof c, hipMemcpyDeviceToHost));
-    if (c[1]) return fail(CW_ERR_HIP, "dedupe index: a probe reached its bound (the table is inconsistent)");
-    x->count_bound = *count = c[0];
-    return CW_OK;
-}
-
-// x->lock held: index-owned scratch of at least `bytes`; growing frees a buffer the last call may still use
-int dedupe_scratch(cw_dedupe *x, DevBuf &b, size_t bytes)
-{
-    if (b.buf.bytes() < bytes) HIP_TRY(hipEventSynchronize(x->last));
-    return b.reserve(bytes);
-}
-
-// x->lock held, admitted: probe, resolve, index-only pack scan of the new flags, scatter -- queued on s.  values != NULL: block i
-// carries values[i] instead of base + i.
-int dedupe_enqueue(cw_dedupe *x, const uint64_t *dig, uint32_t n, uint64_t base, const uint64_t *values, uint64_t *ref, uint32_t *new_idx,
-                   uint64_t *d_n_new, hipStream_t s)
-{
-    int rc;
-    if ((rc = dedupe_scratch(x, x->rec, (size_t)n * 8)) != CW_OK || (rc = dedupe_scratch(x, x->flags, (size_t)n * 4)) != CW_OK ||
-        (rc = dedupe_scratch(x, x->offs, ((size_t)n + 1) * 8)) != CW_OK)
-        return rc;
-    uint64_t *rec = (uint64_t *)x->rec.p, *off = (uint64_t *)x->offs.p;
-    uint32_t *flags = (uint32_t *)x->flags.p;
-    x->count_bound += n; // from the first launch on, the table may change
-    hipError_t e = cw::dedupe_probe_launch(x->words, dig, n, x->state, x->min_idx, x->value, x->key, x->cap - 1, rec, ref,
-                                           reinterpret_cast<unsigned long long *>(x->ctrl + 1), s);
-    if (e == hipSuccess)
-        e = cw::dedupe_resolve_launch(x->words, dig, n, base, values, x->min_idx, x->state, x->value, x->key, rec, ref, flags, s);
-    if (e == hipSuccess) e = cw::pack_launch(nullptr, 0, flags, n, nullptr, off, s);
-    if (e == hipSuccess) e = cw::dedupe_scatter_launch(flags, off, n, rec, x->min_idx, new_idx, d_n_new, x->ctrl, s);
-    if (e != hipSuccess) return fail(CW_ERR_HIP, "dedupe launch: %s", hipGetErrorString(e));
-    return CW_OK;
-}
-} // namespace
-
-namespace {
-// the table of an index: one allocation, state | value | key | min_idx | ctrl
-struct DedupeTable {
-    void *mem = nullptr;
-    uint64_t *state = nullptr, *value = nullptr, *key = nullptr, *ctrl = nullptr;
-    uint32_t *min_idx = nullptr;
-};
-uint64_t dedupe_cap(size_t max_entries)
-{
-    uint64_t cap = 2;
-    while (cap < 2 * (uint64_t)max_entries) cap <<= 1;
-    return cap;
-}
-size_t dedupe_table_bytes(uint64_t cap, size_t db) { return cap * (20 + db) + 4 * sizeof(uint64_t); }
-// allocated and emptied (state EMPTY, min_idx UINT32_MAX, ctrl 0) on stream s, not synchronised; on failure nothing is held
-hipError_t dedupe_table_alloc(uint64_t cap, size_t db, hipStream_t s, DedupeTable *t)
-{
-    hipError_t e = hipMalloc(&t->mem, dedupe_table_bytes(cap, db));
-    if (e != hipSuccess) { t->mem = nullptr; return e; }
-    uint8_t *p = (uint8_t *)t->mem;
-    t->state = (uint64_t *)p;
-    t->value = (uint64_t *)(p + cap * 8);
-    t->key = (uint64_t *)(p + cap * 16);
-    t->min_idx = (uint32_t *)(p + cap * (16 + db));
-    t->ctrl = (uint64_t *)(p + cap * (20 + db)); // cap is even: 8-byte aligned
-    e = hipMemsetAsync(t->state, 0, cap * 8, s);
-    if (e == hipSuccess) e = hipMemsetAsync(t->min_idx, 0xFF, cap * 4, s);
-    if (e == hipSuccess) e = hipMemsetAsync(t->ctrl, 0, 4 * sizeof(uint64_t), s);
-    if (e != hipSuccess) { (void)hipFree(t->mem); t->mem = nullptr; }
-    return e;
-}
-void dedupe_table_adopt(cw_dedupe *x, const DedupeTable &t, uint64_t cap, size_t max_entries)
-{
-    x->table = t.mem; x->state = t.state; x->value = t.value; x->key = t.key; x->min_idx = t.min_idx; x->ctrl = t.ctrl;
-    x->cap = cap;
-    x->max_entries = max_entries;
-}
-} // namespace
-
-cw_dedupe_t *cw_dedupe_create(int hash_alg, size_t max_entries)
-{
-    if (ensure_init() != CW_OK) return nullptr;
-    const size_t db = cw_digest_bytes(hash_alg);
-    if (db == 0 || max_entries == 0 || max_entries > ((size_t)1 << 40)) {
-        fail(CW_ERR_BAD_ARG, "cw_dedupe_create: hash algorithm %d / max_entries %zu not usable", hash_alg, max_entries);
-        return nullptr;
-    }
-    cw_dedupe *x = new cw_dedupe;
-    x->device = current_device();
-    x->hash_alg = hash_alg;
-    x->words = (unsigned)(db / 8);
-    const uint64_t cap = dedupe_cap(max_entries);
-    const size_t bytes = dedupe_table_bytes(cap, db);
-    DedupeTable t;
-    hipError_t e = dedupe_table_alloc(cap, db, nullptr, &t);
-    if (e == hipSuccess) {
-        dedupe_table_adopt(x, t, cap, max_entries);
-        e = hipDeviceSynchronize(); // the calls come on other streams
-    }
-    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&x->h_ctrl), 2 * sizeof(uint64_t), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&x->last, hipEventDisableTiming);
-    if (e != hipSuccess) {
-        fail(e == hipErrorOutOfMemory ? CW_ERR_NOMEM : CW_ERR_HIP, "cw_dedupe_create(%zu entries, %zu bytes): %s", max_entries, bytes,
-             hipGetErrorString(e));
-        cw_dedupe_destroy(x);
-        return nullptr;
-    }
-    return x;
-}
-
-void cw_dedupe_destroy(cw_dedupe_t *x)
-{
-    if (!x) return;
-    (void)hipSetDevice(x->device);
-    if (x->last) { (void)hipEventSynchronize(x->last); (void)hipEventDestroy(x->last); }
-    x->rec.release(); x->flags.release(); x->offs.release(); x->gather.release();
-    x->stage_dig.release(); x->stage_val.release(); x->stage_out.release();
-    if (x->table) (void)hipFree(x->table);
-    if (x->h_ctrl) (void)hipHostFree(x->h_ctrl);
-    delete x;
-}
-
-int cw_dedupe_count(cw_dedupe_t *x, uint64_t *count)
-{
-    int rc = dedupe_args(x, 0, 0);
-    if (rc != CW_OK) return rc;
-    if (!count) return fail(CW_ERR_BAD_ARG, "NULL count");
-    std::lock_guard<std::mutex> g(x->lock);
-    return dedupe_read_count(x, count);
-}
-
-int cw_dedupe_max_entries(cw_dedupe_t *x, size_t *max_entries)
-{
-    if (!x || !max_entries) return fail(CW_ERR_BAD_ARG, "NULL %s", x ? "max_entries" : "dedupe index");
-    std::lock_guard<std::mutex> g(x->lock);
-    *max_entries = x->max_entries;
-    return CW_OK;
-}
-
-int cw_dedupe_set_stage_entries(cw_dedupe_t *x, size_t entries)
-{
-    if (!x) return fail(CW_ERR_BAD_ARG, "NULL dedupe index");
-    if (entries > kMaxDedupeBlocks) return fail(CW_ERR_BAD_ARG, "stage entries %zu > 2^32 - 256", entries);
-    std::lock_guard<std::mutex> g(x->lock);
-    x->stage_entries = entries ? entries : (size_t)1 << 20;
-    return CW_OK;
-}
-
-int cw_dev_dedupe(cw_dedupe_t *x, const void *d_digests, size_t nblocks, uint64_t base, uint64_t *d_ref, uint32_t *d_new_idx,
-                  uint64_t *d_n_new, void *stream)
-{
-    int rc = dedupe_args(x, nblocks, base);
-    if (rc != CW_OK || nblocks == 0) return rc;
-    if (!d_digests || !d_ref || !d_new_idx || !d_n_new) return fail(CW_ERR_BAD_ARG, "NULL device pointer");
-    if ((uintptr_t)d_digests % 8) return fail(CW_ERR_BAD_ARG, "d_digests must be 8-byte aligned");
-    const hipStream_t s = (hipStream_t)stream;
-    std::lock_guard<std::mutex> g(x->lock);
-    if ((rc = dedupe_admit(x, nblocks)) != CW_OK) return rc;
-    HIP_TRY(hipStreamWaitEvent(s, x->last, 0));
-    rc = dedupe_enqueue(x, (const uint64_t *)d_digests, (uint32_t)nblocks, base, nullptr, d_ref, d_new_idx, d_n_new, s);
-    HIP_TRY(hipEventRecord(x->last, s));
-    return rc;
-}
-
-int cw_dev_dedupe_insert(cw_dedupe_t *x, const void *d_digests, const uint64_t *d_values, size_t n, uint64_t *d_ref, uint32_t *d_new_idx,
-                         uint64_t *d_n_new, void *stream)
-{
-    int rc = dedupe_args(x, n, 0);
-    if (rc != CW_OK || n == 0) return rc;
-    if (!d_digests || !d_values || !d_ref || !d_new_idx || !d_n_new) return fail(CW_ERR_BAD_ARG, "NULL device pointer");
-    if ((uintptr_t)d_digests % 8) return fail(CW_ERR_BAD_ARG, "d_digests must be 8-byte aligned");
-    const hipStream_t s = (hipStream_t)stream;
-    std::lock_guard<std::mutex> g(x->lock);
-    if ((rc = dedupe_admit(x, n)) != CW_OK) return rc;
-    HIP_TRY(hipStreamWaitEvent(s, x->last, 0));
-    rc = dedupe_enqueue(x, (const uint64_t *)d_digests, (uint32_t)n, 0, d_values, d_ref, d_new_idx, d_n_new, s);
-    HIP_TRY(hipEventRecord(x->last, s));
-    return rc;
-}
-
-int cw_dev_dedupe_lookup(cw_dedupe_t *x, const void *d_digests, size_t n, uint64_t *d_ref, uint64_t *d_n_found, void *stream)
-{
-    int rc = dedupe_args(x, n, 0);
-    if (rc != CW_OK || n == 0) return rc;
-    if (!d_digests || !d_ref || !d_n_found) return fail(CW_ERR_BAD_ARG, "NULL device pointer");
-    if ((uintptr_t)d_digests % 8) return fail(CW_ERR_BAD_ARG, "d_digests must be 8-byte aligned");
-    const hipStream_t s = (hipStream_t)stream;
-    std::lock_guard<std::mutex> g(x->lock);
-    HIP_TRY(hipStreamWaitEvent(s, x->last, 0));
-    const hipError_t e = cw::dedupe_lookup_launch(x->words, (const uint64_t *)d_digests, (uint32_t)n, x->state, x->value, x->key, x->cap - 1, d_ref,
-                                                  d_n_found, reinterpret_cast<unsigned long long *>(x->ctrl + 1), s);
-    HIP_TRY(hipEventRecord(x->last, s));
-    return e == hipSuccess ? CW_OK : fail(CW_ERR_HIP, "dedupe lookup launch: %s", hipGetErrorString(e));
-}
-
-namespace {
-// x->lock held, s waits for x->last: tile counts and their scan into the index's scratch (flags = counts, offs)
-int dedupe_export_scan(cw_dedupe *x, hipStream_t s)
-{
-    const uint64_t ntiles = cw::dedupe_export_tiles(x->cap);
-    int rc;
-    if ((rc = dedupe_scratch(x, x->flags, ntiles * 4)) != CW_OK || (rc = dedupe_scratch(x, x->offs, (ntiles + 1) * 8)) != CW_OK) return rc;
-    const hipError_t e = cw::dedupe_export_scan_launch(x->state, x->cap, (uint32_t *)x->flags.p, (uint64_t *)x->offs.p, s);
-    return e == hipSuccess ? CW_OK : fail(CW_ERR_HIP, "dedupe export scan launch: %s", hipGetErrorString(e));
-}
-int dedupe_export_scatter(cw_dedupe *x, uint64_t first, uint64_t max_out, void *d_digests, uint64_t *d_values, uint64_t *d_n, hipStream_t s)
-{
-    const hipError_t e = cw::dedupe_export_scatter_launch(x->words, x->state, x->value, x->key, x->cap, (const uint64_t *)x->offs.p, first, max_out,
-                                                          (uint64_t *)d_digests, d_values, d_n, s);
-    return e == hipSuccess ? CW_OK : fail(CW_ERR_HIP, "dedupe export launch: %s", hipGetErrorString(e));
-}
-} // namespace
-
-int cw_dev_dedupe_export(cw_dedupe_t *x, void *d_digests, uint64_t *d_values, size_t max_out, uint64_t *d_n, void *stream)
-{
-    int rc = dedupe_args(x, 0, 0);
-    if (rc != CW_OK) return rc;
-    if (!d_n || (max_out && (!d_digests || !d_values))) return fail(CW_ERR_BAD_ARG, "NULL device pointer");
-    if ((uintptr_t)d_digests % 8) return fail(CW_ERR_BAD_ARG, "d_digests must be 8-byte aligned");
-    const hipStream_t s = (hipStream_t)stream;
-    std::lock_guard<std::mutex> g(x->lock);
-    HIP_TRY(hipStreamWaitEvent(s, x->last, 0));
-    if ((rc = dedupe_export_scan(x, s)) == CW_OK) rc = dedupe_export_scatter(x, 0, max_out, d_digests, d_values, d_n, s);
-    HIP_TRY(hipEventRecord(x->last, s));
-    return rc;
-}
-
-int cw_dedupe_export(cw_dedupe_t *x, void *digests, uint64_t *values, size_t max_out, size_t *n)
-{
-    int rc = dedupe_args(x, 0, 0);
-    if (rc != CW_OK) return rc;
-    if (!n || (max_out && (!digests || !values))) return fail(CW_ERR_BAD_ARG, "NULL pointer");
-    ThreadCtx *c;
-    if ((rc = thread_ctx(&c)) != CW_OK) return rc;
-    const hipStream_t s = c->stream;
-    const size_t db = (size_t)x->words * 8;
-    std::lock_guard<std::mutex> g(x->lock);
-    HIP_TRY(hipStreamWaitEvent(s, x->last, 0));
-    if ((rc = dedupe_export_scan(x, s)) != CW_OK) return rc;
-    uint64_t total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, (const uint64_t *)x->offs.p + cw::dedupe_export_tiles(x->cap), sizeof total, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    const size_t want = total < max_out ? (size_t)total : max_out, piece = x->stage_entries < want ? x->stage_entries : want;
-    if (piece && ((rc = dedupe_scratch(x, x->stage_dig, piece * db)) != CW_OK || (rc = dedupe_scratch(x, x->stage_val, piece * 8)) != CW_OK)) return rc;
-    for (size_t first = 0; first < want && rc == CW_OK; first += piece) {
-        const size_t k = want - first < piece ? want - first : piece;
-        if ((rc = dedupe_export_scatter(x, first, k, x->stage_dig.p, (uint64_t *)x->stage_val.p, nullptr, s)) != CW_OK) break;
-        HIP_TRY(hipMemcpyAsync((uint8_t *)digests + first * db, x->stage_dig.p, k * db, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(values + first, x->stage_val.p, k * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s)); // the next piece overwrites the staging buffers
-    }
-    HIP_TRY(hipEventRecord(x->last, s));
-    if (rc == CW_OK) *n = (size_t)total;
-    return rc;
-}
-
-int cw_dedupe_import(cw_dedupe_t *x, const void *digests, const uint64_t *values, size_t n, size_t *n_inserted)
-{
-    if (n_inserted) *n_inserted = 0;
-    int rc = dedupe_args(x, 0, 0);
-    if (rc != CW_OK) return rc;
-    if (!n_inserted || (n && (!digests || !values))) return fail(CW_ERR_BAD_ARG, "NULL pointer");
-    if (n == 0) return CW_OK;
-    ThreadCtx *c;
-    if ((rc = thread_ctx(&c)) != CW_OK) return rc;
-    const hipStream_t s = c->stream;
-    const size_t db = (size_t)x->words * 8;
-    std::lock_guard<std::mutex> g(x->lock);
-    if ((rc = dedupe_admit(x, n)) != CW_OK) return rc; // the whole import: count only grows by what the pieces insert, so no piece can overflow
-    const size_t piece = x->stage_entries < n ? x->stage_entries : n;
-    if ((rc = dedupe_scratch(x, x->stage_dig, piece * db)) != CW_OK || (rc = dedupe_scratch(x, x->stage_val, piece * 8)) != CW_OK ||
-        (rc = dedupe_scratch(x, x->stage_out, piece * 12 + 16)) != CW_OK)
-        return rc;
-    uint64_t *d_ref = (uint64_t *)x->stage_out.p, *d_k = d_ref + piece;
-    uint32_t *d_new = (uint32_t *)(d_k + 1);
-    HIP_TRY(hipStreamWaitEvent(s, x->last, 0));
-    size_t inserted = 0;
-    for (size_t first = 0; first < n && rc == CW_OK; first += piece) {
-        const size_t k = n - first < piece ? n - first : piece;
-        uint64_t k_new = 0;
-        HIP_TRY(hipMemcpyAsync(x->stage_dig.p, (const uint8_t *)digests + first * db, k * db, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(x->stage_val.p, values + first, k * 8, hipMemcpyHostToDevice, s));
-        rc = dedupe_enqueue(x, (const uint64_t *)x->stage_dig.p, (uint32_t)k, 0, (const uint64_t *)x->stage_val.p, d_ref, d_new, d_k, s);
-        HIP_TRY(hipEventRecord(x->last, s));
-        if (rc != CW_OK) break;
-        HIP_TRY(hipMemcpyAsync(&k_new, d_k, sizeof k_new, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s)); // the next piece overwrites the staging buffers
-        inserted += (size_t)k_new;
-    }
-    if (rc == CW_OK) *n_inserted = inserted;
-    return rc;
-}
-
-int cw_dedupe_resize(cw_dedupe_t *x, size_t new_max_entries)
-{
-    int rc = dedupe_args(x, 0, 0);
-    if (rc != CW_OK) return rc;
-    std::lock_guard<std::mutex> g(x->lock);
-    uint64_t count = 0;
-    if ((rc = dedupe_read_count(x, &count)) != CW_OK) return rc;
-    if (new_max_entries == 0 || new_max_entries > ((size_t)1 << 40) || new_max_entries < count)
-        return fail(CW_ERR_BAD_ARG, "cw_dedupe_resize: max_entries %zu not in [max(1, count = %llu), 2^40]", new_max_entries, (unsigned long long)count);
-    const uint64_t cap = dedupe_cap(new_max_entries);
-    if (cap == x->cap) { // the same table serves
-        x->max_entries = new_max_entries;
-        return CW_OK;
-    }
-    const size_t db = (size_t)x->words * 8;
-    DedupeTable t;
-    hipError_t e = dedupe_table_alloc(cap, db, nullptr, &t);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(e == hipErrorOutOfMemory ? CW_ERR_NOMEM : CW_ERR_HIP, "cw_dedupe_resize(%zu entries, %zu bytes beside the old table): %s", new_max_entries,
-                    dedupe_table_bytes(cap, db), hipGetErrorString(e));
-    }
-    // the old table is idle (the last call has finished, the lock keeps new ones out): rehash and carry ctrl over on the NULL stream
-    uint64_t err = 0;
-    e = cw::dedupe_rehash_launch(x->words, x->state, x->value, x->key, x->cap, t.state, t.value, t.key, cap - 1,
-                                 reinterpret_cast<unsigned long long *>(t.ctrl + 1), nullptr);
-    if (e == hipSuccess) e = hipMemcpyAsync(&err, t.ctrl + 1, sizeof err, hipMemcpyDeviceToHost, nullptr);
-    if (e == hipSuccess) e = hipMemcpyAsync(t.ctrl, x->ctrl, 4 * sizeof(uint64_t), hipMemcpyDeviceToDevice, nullptr);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess || err) {
-        (void)hipFree(t.mem);
-        return e != hipSuccess ? fail(CW_ERR_HIP, "cw_dedupe_resize: %s", hipGetErrorString(e))
-                               : fail(CW_ERR_HIP, "cw_dedupe_resize: an entry found no slot in the new table (the index is unchanged)");
-    }
-    void *old = x->table;
-    dedupe_table_adopt(x, t, cap, new_max_entries);
-    x->count_bound = count;
-    HIP_TRY(hipEventRecord(x->last, nullptr));
-    HIP_TRY(hipFree(old));
-    return CW_OK;
-}
-
-// cw_dedupe_resize with a filter (the keep rule: dedupe_retain_kernel).  When the new table could not hold every entry of the old one
-// (new_max_entries below the old count) the kept entries are counted first, by the same kernel without a table: rehashing more
-// entries than the table has slots would walk the whole table once per entry that finds none.
-int cw_dedupe_retain(cw_dedupe_t *x, const uint32_t *d_live, uint64_t dir_base, size_t dir_entries, size_t new_max_entries, uint64_t *n_removed)
-{
-    if (!x || !d_live) return fail(CW_ERR_BAD_ARG, "cw_dedupe_retain: NULL %s", x ? "d_live" : "dedupe index");
-    if (dir_entries == 0) return fail(CW_ERR_BAD_ARG, "cw_dedupe_retain: dir_entries is 0");
-    if (new_max_entries > ((size_t)1 << 40)) return fail(CW_ERR_BAD_ARG, "cw_dedupe_retain: max_entries %zu > 2^40", new_max_entries);
-    int rc = dedupe_args(x, 0, 0);
-    if (rc != CW_OK) return rc;
-    std::lock_guard<std::mutex> g(x->lock);
-    uint64_t count = 0;
-    if ((rc = dedupe_read_count(x, &count)) != CW_OK) return rc;
-    const size_t want = new_max_entries ? new_max_entries : x->max_entries;
-    const uint64_t cap = dedupe_cap(want);
-    const size_t db = (size_t)x->words * 8;
-    DedupeTable t;
-    hipError_t e = dedupe_table_alloc(cap, db, nullptr, &t);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(e == hipErrorOutOfMemory ? CW_ERR_NOMEM : CW_ERR_HIP, "cw_dedupe_retain(%zu entries, %zu bytes beside the old table): %s", want,
-                    dedupe_table_bytes(cap, db), hipGetErrorString(e));
-    }
-    // the old table is idle (the last call has finished, the lock keeps new ones out): everything below is on the NULL stream.
-    // t.ctrl[0] counts the kept entries, t.ctrl[1] takes the walks' error word
-    unsigned long long *kept_d = reinterpret_cast<unsigned long long *>(t.ctrl), *err_d = kept_d + 1;
-    uint64_t c[2] = {0, 0}; // kept, err
-    if (want < count) {
-        e = cw::dedupe_retain_launch(x->words, x->state, x->value, x->key, x->cap, d_live, dir_base, dir_entries, nullptr, nullptr, nullptr, 0, kept_d,
-                                     err_d, nullptr);
-        if (e == hipSuccess) e = hipMemcpyAsync(c, t.ctrl, sizeof c, hipMemcpyDeviceToHost, nullptr);
-        if (e == hipSuccess) e = hipMemsetAsync(t.ctrl, 0, sizeof c, nullptr);
-        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    }
-    if (e == hipSuccess && c[0] <= want) {
-        e = cw::dedupe_retain_launch(x->words, x->state, x->value, x->key, x->cap, d_live, dir_base, dir_entries, t.state, t.value, t.key, cap - 1,
-                                     kept_d, err_d, nullptr);
-        if (e == hipSuccess) e = hipMemcpyAsync(c, t.ctrl, sizeof c, hipMemcpyDeviceToHost, nullptr);
-        if (e == hipSuccess) e = hipMemcpyAsync(t.ctrl + 2, x->ctrl + 2, 2 * sizeof(uint64_t), hipMemcpyDeviceToDevice, nullptr);
-        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    }
-    if (e != hipSuccess || c[1] || c[0] > want) {
-        (void)hipFree(t.mem);
-        if (e != hipSuccess) return fail(CW_ERR_HIP, "cw_dedupe_retain: %s", hipGetErrorString(e));
-        if (c[0] > want)
-            return fail(CW_ERR_BAD_ARG, "cw_dedupe_retain: max_entries %zu below the %llu kept entries (the index is unchanged)", want,
-                        (unsigned long long)c[0]);
-        return fail(CW_ERR_HIP, "cw_dedupe_retain: an entry found no slot in the new table (the index is unchanged)");
-    }
-    void *old = x->table;
-    dedupe_table_adopt(x, t, cap, want);
-    x->count_bound = c[0];
-    if (n_removed) *n_removed = count - c[0];
-    HIP_TRY(hipEventRecord(x->last, nullptr));
-    HIP_TRY(hipFree(old));
-    return CW_OK;
-}
-
-// hash -> dedupe -> one 16-byte copy back + a synchronise -> the codec over the new blocks only.  The codec cannot start before
-// the dedupe result, so hash and codec do not overlap as in dev_fused.
-int cw_dev_hash_dedupe_compress(cw_dedupe_t *x, int comp_alg, const void *d_src, size_t block_bytes, size_t src_stride, size_t nblocks,
-                                uint64_t base, void *d_digests, uint64_t *d_ref, uint32_t *d_new_idx, void *d_dst, size_t dst_stride,
-                                uint32_t *d_sizes, size_t *n_new, void *stream)
-{
-    if (n_new) *n_new = 0;
-    int rc = dedupe_args(x, nblocks, base);
-    if (rc != CW_OK) return rc;
-    if (!n_new) return fail(CW_ERR_BAD_ARG, "NULL n_new");
-    if (comp_alg != CW_COMP_LZ4 && comp_alg != CW_COMP_LZF) return fail(CW_ERR_BAD_ARG, "unknown compression algorithm %d", comp_alg);
-    if (nblocks == 0) return CW_OK;
-    if (!d_src || !d_digests || !d_ref || !d_new_idx || !d_dst || !d_sizes) return fail(CW_ERR_BAD_ARG, "NULL device pointer");
-    if ((uintptr_t)d_digests % 8) return fail(CW_ERR_BAD_ARG, "d_digests must be 8-byte aligned");
-    if (block_bytes == 0 || (rc = check_block(block_bytes)) != CW_OK) return rc ? rc : fail(CW_ERR_BAD_ARG, "block_bytes == 0");
-    if (src_stride < block_bytes) return fail(CW_ERR_BAD_ARG, "src_stride < block_bytes");
-    if (dst_stride < cw_compress_bound(comp_alg, block_bytes))
-        return fail(CW_ERR_BAD_ARG, "dst_stride %zu < bound %zu", dst_stride, cw_compress_bound(comp_alg, block_bytes));
-    const hipStream_t s = (hipStream_t)stream;
-    const uint8_t *src = (const uint8_t *)d_src;
-    std::lock_guard<std::mutex> g(x->lock); // held to the end: the gather buffer is the index's
-    if ((rc = dedupe_admit(x, nblocks)) != CW_OK) return rc;
-    HIP_TRY(hipStreamWaitEvent(s, x->last, 0));
-    rc = dev_hash(x->hash_alg, src, block_bytes, src_stride, nblocks, (uint8_t *)d_digests, s, false, true);
-    if (rc == CW_OK) rc = dedupe_enqueue(x, (const uint64_t *)d_digests, (uint32_t)nblocks, base, nullptr, d_ref, d_new_idx, x->ctrl + 2, s);
-    if (rc == CW_OK) {
-        HIP_TRY(hipMemcpyAsync(x->h_ctrl, x->ctrl + 1, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (x->h_ctrl[0]) rc = fail(CW_ERR_HIP, "dedupe index: a probe reached its bound (the table is inconsistent)");
-    }
-    const size_t k = rc == CW_OK ? (size_t)x->h_ctrl[1] : 0;
-    if (rc == CW_OK && k == nblocks) { // all new: the codec on the caller's blocks, slots as cw_dev_hash_and_compress
-        rc = dev_compress(comp_alg, src, block_bytes, src_stride, nblocks, (uint8_t *)d_dst, dst_stride, d_sizes, s);
-    } else if (rc == CW_OK && k) { // (the stream is idle here, and it waited for the last call: nothing uses the old buffer)
-        rc = x->gather.reserve(k * block_bytes);
-        hipError_t e = rc == CW_OK ? cw::dedupe_gather_launch(src, block_bytes, src_stride, d_new_idx, k, (uint8_t *)x->gather.p, s) : hipSuccess;
-        if (e != hipSuccess) rc = fail(CW_ERR_HIP, "gather launch: %s", hipGetErrorString(e));
-        if (rc == CW_OK)
-            rc = dev_compress(comp_alg, (const uint8_t *)x->gather.p, block_bytes, block_bytes, k, (uint8_t *)d_dst, dst_stride, d_sizes, s);
-    }
-    HIP_TRY(hipEventRecord(x->last, s));
-    if (rc == CW_OK) *n_new = k;
-    return rc;
-}
-
-// cdc -> hash of every chunk -> one 8-byte copy back + a synchronise (the dedupe's admit check and launch need the count on the
-// host) -> dedupe -> the chunk codec over the new chunks, selected on the device: n_new never comes back to the host.
-int cw_dev_cdc_dedupe_compress(cw_dedupe_t *x, const cw_cdc_params *p, int comp_alg, const void *d_src, size_t nbytes, int final,
-                               uint64_t base, uint64_t *d_offsets, size_t max_offsets, uint64_t *d_nchunks, void *d_digests, uint64_t *d_ref,
-                               uint32_t *d_new_idx, uint64_t *d_n_new, void *d_dst, size_t dst_bytes, uint32_t *d_sizes, size_t *nchunks,
-                               void *stream)
-{
-    if (nchunks) *nchunks = 0;
-    cw::CdcParams cp;
-    int rc = cdc_params(p, &cp);
-    if (rc != CW_OK) return rc;
-    if (!nchunks) return fail(CW_ERR_BAD_ARG, "NULL nchunks");
-    if (!d_offsets || !d_nchunks || !d_digests || !d_ref || !d_new_idx || !d_n_new || (nbytes && !d_src)) return fail(CW_ERR_BAD_ARG, "NULL pointer");
-    if (max_offsets < nbytes / cp.min_size + 2)
-        return fail(CW_ERR_BAD_ARG, "max_offsets %zu < nbytes / min_size + 2 = %zu", max_offsets, nbytes / cp.min_size + 2);
-    if ((uintptr_t)d_digests % 8) return fail(CW_ERR_BAD_ARG, "d_digests must be 8-byte aligned");
-    const size_t max_chunks = max_offsets - 1;
-    if ((rc = compress_chunks_args(comp_alg, d_src, nbytes, d_offsets, d_nchunks, max_chunks, d_new_idx, d_n_new, d_dst, dst_bytes, d_sizes)) != CW_OK)
-        return rc;
-    if ((rc = dedupe_args(x, 0, base)) != CW_OK) return rc; // (base + the chunk count: checked when the count is known, as cw_dev_dedupe would)
-    const hipStream_t s = (hipStream_t)stream;
-    const uint8_t *src = (const uint8_t *)d_src;
-    std::lock_guard<std::mutex> g(x->lock);
-    HIP_TRY(hipStreamWaitEvent(s, x->last, 0));
-    rc = dev_cdc(cp, src, nbytes, final ? 1 : 0, d_offsets, max_offsets, d_nchunks, s);
-    if (rc == CW_OK) rc = dev_hash_chunks(x->hash_alg, src, nbytes, d_offsets, d_nchunks, max_chunks, (uint8_t *)d_digests, s);
-    if (rc != CW_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(x->h_ctrl, d_nchunks, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    const size_t k = (size_t)x->h_ctrl[0];
-    *nchunks = k;
-    if (k == 0) { // (an empty input: cw_dev_dedupe would launch nothing)
-        HIP_TRY(hipMemsetAsync(d_n_new, 0, sizeof(uint64_t), s));
-        return CW_OK;
-    }
-    if (base > UINT64_MAX - k) return fail(CW_ERR_BAD_ARG, "base + nchunks wraps");
-    if ((rc = dedupe_admit(x, k)) != CW_OK) return rc; // offsets and digests are written; nothing inserted, nothing compressed
-    rc = dedupe_enqueue(x, (const uint64_t *)d_digests, (uint32_t)k, base, nullptr, d_ref, d_new_idx, d_n_new, s);
-    if (rc == CW_OK)
-        rc = dev_compress_chunks(comp_alg, src, nbytes, d_offsets, d_nchunks, max_chunks, d_new_idx, d_n_new, (uint8_t *)d_dst, d_sizes, s);
-    HIP_TRY(hipEventRecord(x->last, s));
-    return rc;
-}
-
-// ---- HashOffload -------------------------------------------------------------------------------------------------
-struct cw_offload {
-    int hash_alg;
-    int n_blocks;           // offloadCount
-    size_t block_bytes;
-    char *data = nullptr;   // host
-    char *results = nullptr;
-    void (*on_complete)(void *) = nullptr;
-    void *arg = nullptr;
-    std::atomic<int> state{CW_OFFLOAD_INIT};
-    int error = CW_OK;      // why the object is in CW_OFFLOAD_FAILED
-    char error_msg[256] = "";
-    int device = -1;        // the device the object was created on
-    hipStream_t stream = nullptr;
-    DevBuf d_src, d_dig;
-};
-
-namespace {
-int offload_fail(cw_offload *h, int rc) // record the failure on the object, so that waiters and Complete() see it
-{
-    h->error = rc;
-    strncpy(h->error_msg, t_err, sizeof h->error_msg - 1);
-    h->state.store(CW_OFFLOAD_FAILED);
-    return rc;
-}
-} // namespace
-
-cw_offload_t *cw_offload_create(int hash_alg, int n_blocks, size_t block_bytes)
-{
-    if (ensure_init() != CW_OK) return nullptr;
-    if (n_blocks <= 0 || cw_digest_bytes(hash_alg) == 0 || check_block(block_bytes) != CW_OK) {
-        fail(CW_ERR_BAD_ARG, "cw_offload_create: bad arguments");
-        return nullptr;
-    }
-    cw_offload *h = new cw_offload;
-    h->hash_alg = hash_alg; h->n_blocks = n_blocks; h->block_bytes = block_bytes;
-    h->device = current_device();
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
-        h->d_src.reserve((size_t)n_blocks * block_bytes + 16) != CW_OK || h->d_dig.reserve((size_t)n_blocks * cw_digest_bytes(hash_alg)) != CW_OK) {
-        cw_offload_destroy(h);
-        fail(CW_ERR_HIP, "cw_offload_create: device resources");
-        return nullptr;
-    }
-    return h;
-}
-
-void cw_offload_destroy(cw_offload_t *h)
-{
-    if (!h) return;
-    h->d_src.release(); h->d_dig.release();
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
-
-int cw_offload_reset(cw_offload_t *h, char *data, char *results, void (*on_complete)(void *), void *arg)
-{
-    if (!h) return fail(CW_ERR_BAD_ARG, "NULL offload");
-    h->data = data; h->results = results; h->on_complete = on_complete; h->arg = arg;
-    h->error = CW_OK; h->error_msg[0] = 0;
-    h->state.store(CW_OFFLOAD_INIT);
-    return CW_OK;
-}
-
-int cw_offload_enqueue(cw_offload_t *h)
-{
-    if (!h) return fail(CW_ERR_BAD_ARG, "NULL offload");
-    int want = CW_OFFLOAD_INIT;
-    if (!h->state.compare_exchange_strong(want, CW_OFFLOAD_QUEUED)) return fail(CW_ERR_STATE, "Enqueue: state %d != hInit", want);
-    return CW_OK;
-}
-
-int cw_offload_start(cw_offload_t *h)
-{
-    if (!h) return fail(CW_ERR_BAD_ARG, "NULL offload");
-    if (h->state.load() != CW_OFFLOAD_QUEUED) return fail(CW_ERR_STATE, "Start: state %d != hQueued", h->state.load());
-    // everything that can fail is checked or attempted BEFORE the object counts as offloaded; a failure leaves it in
-    // CW_OFFLOAD_FAILED with the reason on the object (cw_offload_error), never in hOffloaded with nothing in flight
-    if (!h->data || !h->results) return offload_fail(h, fail(CW_ERR_BAD_ARG, "Start: Reset() gave no data/results"));
-    const size_t bytes = (size_t)h->n_blocks * h->block_bytes, db = cw_digest_bytes(h->hash_alg);
-    hipError_t e = hipSetDevice(h->device);
-    if (e == hipSuccess && bytes) e = hipMemcpyAsync(h->d_src.p, h->data, bytes, hipMemcpyHostToDevice, h->stream);
-    if (e != hipSuccess) return offload_fail(h, fail(CW_ERR_HIP, "Start: %s", hipGetErrorString(e)));
-    int rc = dev_hash(h->hash_alg, (const uint8_t *)h->d_src.p, h->block_bytes, h->block_bytes, (size_t)h->n_blocks, (uint8_t *)h->d_dig.p, h->stream);
-    if (rc != CW_OK) { (void)hipStreamSynchronize(h->stream); return offload_fail(h, rc); }
-    e = hipMemcpyAsync(h->results, h->d_dig.p, (size_t)h->n_blocks * db, hipMemcpyDeviceToHost, h->stream);
-    if (e != hipSuccess) { (void)hipStreamSynchronize(h->stream); return offload_fail(h, fail(CW_ERR_HIP, "Start: %s", hipGetErrorString(e))); }
-    h->state.store(CW_OFFLOAD_OFFLOADED);
-    return CW_OK;
-}
-
-int cw_offload_complete(cw_offload_t *h)
-{
-    if (!h) return fail(CW_ERR_BAD_ARG, "NULL offload");
-    if (h->state.load() == CW_OFFLOAD_FAILED) return fail(h->error, "Complete: the offload failed: %s", h->error_msg);
-    if (h->state.load() != CW_OFFLOAD_OFFLOADED) return fail(CW_ERR_STATE, "Complete: state %d != hOffloaded", h->state.load());
-    hipError_t e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) return offload_fail(h, fail(CW_ERR_HIP, "Complete: %s", hipGetErrorString(e)));
-    h->state.store(CW_OFFLOAD_COMPLETE);
-    if (h->on_complete) h->on_complete(h->arg);
-    return CW_OK;
-}
-
-int cw_offload_completed(const cw_offload_t *h) { return h && h->state.load() == CW_OFFLOAD_COMPLETE; }
-int cw_offload_state(const cw_offload_t *h) { return h ? h->state.load() : CW_ERR_BAD_ARG; }
-int cw_offload_error(const cw_offload_t *h) { return h ? h->error : CW_ERR_BAD_ARG; }
-
-int cw_offload_do(cw_offload_t *h)
-{
-    int rc = cw_offload_start(h);
-    return rc == CW_OK ? cw_offload_complete(h) : rc;
-}
-
-// ---- the offload thread (:160-183) ---------------------------------------------------------------------------
-namespace {
-std::mutex q_lock;               // hashLock
-std::condition_variable q_cv;    // hashCV
-std::deque<cw_offload *> q_work; // hashQueue
-bool q_finished = false;         // allWorkFinished
-std::thread q_thread;
-bool q_running = false;
-
-void offload_entry_point()
-{
-    std::unique_lock<std::mutex> lk(q_lock);
-    for (;;) {
-        if (q_work.empty()) {
-            if (q_finished) break; // drain before exiting
-            q_cv.wait(lk);
-            continue;
-        }
-        cw_offload *h = q_work.front();
-        q_work.pop_front();
-        lk.unlock();
-        if (cw_offload_do(h) != CW_OK) {
-            // the reason is on the object (CW_OFFLOAD_FAILED, cw_offload_error); whoever waits for the callback is
-            // still woken, and finds Completed() false
-            fprintf(stderr, "libcwhc: offload failed: %s\n", t_err);
-            if (h->state.load() != CW_OFFLOAD_FAILED) offload_fail(h, CW_ERR_STATE);
-            if (h->on_complete) h->on_complete(h->arg);
-        }
-        lk.lock();
-    }
-}
-} // namespace
-
-int cw_offload_thread_start(void)
-{
-    int rc = ensure_init();
-    if (rc != CW_OK) return rc;
-    std::lock_guard<std::mutex> g(q_lock);
-    if (q_running) return CW_OK;
-    q_finished = false;
-    q_thread = std::thread(offload_entry_point);
-    q_running = true;
-    return CW_OK;
-}
-
-int cw_offload_submit(cw_offload_t *h)
-{
-    int rc = cw_offload_enqueue(h);
-    if (rc != CW_OK) return rc;
-    {
-        std::lock_guard<std::mutex> g(q_lock);
-        if (!q_running) return fail(CW_ERR_STATE, "offload thread not started");
-        q_work.push_back(h);
-    }
-    q_cv.notify_one();
-    return CW_OK;
-}
-
-void cw_offload_thread_stop(void)
-{
-    {
-        std::lock_guard<std::mutex> g(q_lock);
-        if (!q_running) return;
-        q_finished = true;
-    }
-    q_cv.notify_all();
-    q_thread.join();
-    std::lock_guard<std::mutex> g(q_lock);
-    q_running = false;
 }
 
 } // extern "C"

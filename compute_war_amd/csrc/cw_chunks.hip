@@ -1,0 +1,266 @@
+// cw_chunks.hip -- host side of the device-resident calls over content-defined chunks: the cut (kernels: cdc_kernels.hip), the per-chunk
+// hash, the chunk codecs and their pack (chunk_codec_kernels.hip, pack_kernels.hip), the chunk store (restore_kernels.hip) and its mark and
+// compact (store_gc_kernels.hip).  Semantics: the public header.  Every refusal here comes before the device is touched.
+
+#include "cw_host.h"
+
+using namespace cw::host;
+
+namespace {
+
+uint64_t splitmix64_host(uint64_t x)
+{
+    uint64_t z = x + 0x9E3779B97F4A7C15ULL;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    return z ^ (z >> 31);
+}
+
+struct DefaultGear {
+    uint64_t g[256];
+    DefaultGear() { for (int v = 0; v < 256; v++) g[v] = splitmix64_host((uint64_t)v); }
+};
+const DefaultGear kDefaultGear;
+
+// `bits`: the pointers of `names` or-ed together
+int check_dir_aligned(uintptr_t bits, const char *names) { return bits & 15 ? fail(CW_ERR_BAD_ARG, "%s is not 16-byte aligned", names) : CW_OK; }
+int check_word_aligned(uintptr_t bits, const char *names) { return bits & 7 ? fail(CW_ERR_BAD_ARG, "%s not 8-byte aligned", names) : CW_OK; }
+
+// [a, a + an) and [b, b + bn) share a byte
+bool ranges_overlap(const void *a, size_t an, const void *b, size_t bn)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return an && bn && x < y + bn && y < x + an;
+}
+
+} // namespace
+
+int cw::host::cdc_params(const cw_cdc_params *p, cw::CdcParams *out)
+{
+    if (!p) return fail(CW_ERR_BAD_ARG, "NULL cdc params");
+    if (p->reserved != 0) return fail(CW_ERR_BAD_ARG, "cdc params: reserved must be 0");
+    if (!(64 <= p->min_size && p->min_size <= p->normal_size && p->normal_size <= p->max_size && p->max_size <= (1u << 24)))
+        return fail(CW_ERR_BAD_ARG, "cdc params: need 64 <= min %u <= normal %u <= max %u <= 2^24", p->min_size, p->normal_size, p->max_size);
+    *out = cw::CdcParams{p->min_size, p->normal_size, p->max_size, p->mask_s, p->mask_l, p->gear ? p->gear : kDefaultGear.g};
+    return CW_OK;
+}
+
+int cw::host::dev_cdc(const cw::CdcParams &p, const uint8_t *d_src, size_t nbytes, int final_, uint64_t *d_offsets, size_t max_offsets,
+                      uint64_t *d_nchunks, hipStream_t s)
+{
+    const uint64_t seg = cw::cdc_segment_bytes(p.max_size, cw::knobs().cdc_segment);
+    ProfScope prof(PROF_HASH, s);
+    hipError_t e = cw::cdc_launch(p, d_src, nbytes, final_, d_offsets, max_offsets, d_nchunks, seg, s);
+    if (e == hipErrorOutOfMemory) return fail(CW_ERR_NOMEM, "cdc workspace (%zu bytes): %s", cw::cdc_workspace_bytes(nbytes, p.min_size, seg),
+                                              hipGetErrorString(e));
+    return launched(e, "cdc launch");
+}
+
+int cw::host::dev_hash_chunks(int alg, const uint8_t *d_src, size_t src_bytes, const uint64_t *d_offsets, const uint64_t *d_nchunks,
+                              size_t max_chunks, uint8_t *d_dig, hipStream_t s)
+{
+    if (alg == CW_HASH_NONE) return CW_OK;
+    if (alg != CW_HASH_SKEIN512 && alg != CW_HASH_SKEIN256_128 && alg != CW_HASH_SHA256) return fail(CW_ERR_BAD_ARG, "unknown hash algorithm %d", alg);
+    if (int rc = check_count("max_chunks", max_chunks)) return rc;
+    if (max_chunks == 0) return CW_OK;
+    ProfScope prof(PROF_HASH, s);
+    struct Call { int alg; const uint8_t *src; size_t src_bytes; const uint64_t *off, *n; size_t max; uint8_t *dig; hipStream_t s; };
+    Call call{alg, d_src, src_bytes, d_offsets, d_nchunks, max_chunks, d_dig, s};
+    const cw::ChunkHash hash{[](void *ctx, const uint32_t *perm) {
+                                 const Call &k = *static_cast<const Call *>(ctx);
+                                 if (k.alg == CW_HASH_SHA256) return cw::sha256_chunks_launch(k.src, k.src_bytes, k.off, perm, k.n, k.max, k.dig, k.s);
+                                 const int nw = k.alg == CW_HASH_SKEIN512 ? 8 : 4;
+                                 return cw::skein_chunks_launch(nw, k.src, k.src_bytes, k.off, perm, k.n, k.max, skein_iv(nw), k.dig, nw == 8 ? 64 : 16, k.s);
+                             },
+                             &call};
+    // the step counts the sort orders by: 64-byte steps (Skein-512, SHA-256) or 32-byte steps (Skein-256)
+    return launched_nomem(cw::chunk_hash_launch(d_offsets, d_nchunks, max_chunks, src_bytes, alg == CW_HASH_SKEIN256_128 ? 5 : 6, hash, s),
+                          "hash chunks launch");
+}
+
+int cw::host::compress_chunks_args(int comp_alg, const void *d_src, size_t src_bytes, const uint64_t *d_offsets, const uint64_t *d_nchunks,
+                                   size_t max_chunks, const uint32_t *d_sel, const uint64_t *d_nsel, const void *d_dst, size_t dst_bytes,
+                                   const uint32_t *d_sizes)
+{
+    int rc;
+    if ((rc = check_codec(comp_alg)) != CW_OK || (rc = check_count("max_chunks", max_chunks)) != CW_OK) return rc;
+    if (src_bytes > ((size_t)1 << 62)) return fail(CW_ERR_BAD_ARG, "src_bytes %zu not usable", src_bytes);
+    if (!d_offsets || !d_nchunks || !d_dst || !d_sizes || (src_bytes && !d_src) || (d_sel && !d_nsel)) return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    const size_t need = (size_t)cw::chunk_slot_offset(comp_alg == CW_COMP_LZ4, src_bytes, max_chunks) + 16;
+    if (dst_bytes < need) return fail(CW_ERR_BAD_ARG, "dst_bytes %zu < cw_chunk_slots_bytes = %zu", dst_bytes, need);
+    return CW_OK;
+}
+
+int cw::host::dev_compress_chunks(int comp_alg, const uint8_t *d_src, size_t src_bytes, const uint64_t *d_offsets, const uint64_t *d_nchunks,
+                                  size_t max_chunks, const uint32_t *d_sel, const uint64_t *d_nsel, uint8_t *d_dst, uint32_t *d_sizes, hipStream_t s)
+{
+    ProfScope prof(PROF_CODEC, s);
+    const hipError_t e = cw::chunk_compress_launch(comp_alg == CW_COMP_LZF, d_src, src_bytes, d_offsets, d_nchunks, max_chunks, d_sel, d_nsel,
+                                                   d_dst, d_sizes, s);
+    if (e == hipErrorOutOfMemory)
+        return fail(CW_ERR_NOMEM, "chunk parser workspace (order %zu bytes, lane tables of %zu bytes each): %s", (2048 + max_chunks) * 4,
+                    cw::chunk_lane_table_bytes(comp_alg == CW_COMP_LZF), hipGetErrorString(e));
+    return launched(e, "compress chunks launch");
+}
+
+extern "C" {
+
+void cw_cdc_default_params(cw_cdc_params *p, uint32_t normal_size)
+{
+    if (!p) return;
+    // normal_size is clamped to [256, 2^21] and rounded down to a power of two, so every field is defined and valid
+    unsigned lg = 8;
+    while (lg < 21 && (1u << (lg + 1)) <= normal_size) lg++;
+    const uint32_t normal = 1u << lg;
+    p->min_size = normal / 4;
+    p->normal_size = normal;
+    p->max_size = normal * 8;
+    p->reserved = 0;
+    p->mask_s = ~0ull << (64 - (lg + 2));
+    p->mask_l = ~0ull << (64 - (lg - 2));
+    p->gear = NULL;
+}
+
+int cw_dev_cdc(const cw_cdc_params *p, const void *d_src, size_t nbytes, int final, uint64_t *d_offsets, size_t max_offsets,
+               uint64_t *d_nchunks, void *stream)
+{
+    cw::CdcParams cp;
+    int rc = cdc_params(p, &cp);
+    if (rc != CW_OK) return rc;
+    if (!d_offsets || !d_nchunks || (nbytes && !d_src)) return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    if (max_offsets < nbytes / cp.min_size + 2)
+        return fail(CW_ERR_BAD_ARG, "max_offsets %zu < nbytes / min_size + 2 = %zu", max_offsets, nbytes / cp.min_size + 2);
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    return dev_cdc(cp, (const uint8_t *)d_src, nbytes, final ? 1 : 0, d_offsets, max_offsets, d_nchunks, (hipStream_t)stream);
+}
+
+int cw_dev_hash_chunks(int hash_alg, const void *d_src, size_t src_bytes, const uint64_t *d_offsets, const uint64_t *d_nchunks,
+                       size_t max_chunks, void *d_digests, void *stream)
+{
+    if (hash_alg < 0 || hash_alg > CW_HASH_NONE) return fail(CW_ERR_BAD_ARG, "unknown hash algorithm %d", hash_alg);
+    if (hash_alg != CW_HASH_NONE && max_chunks && (!d_offsets || !d_nchunks || !d_digests || (src_bytes && !d_src)))
+        return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    int rc = ensure_init();
+    if (rc != CW_OK) return rc;
+    return dev_hash_chunks(hash_alg, (const uint8_t *)d_src, src_bytes, d_offsets, d_nchunks, max_chunks, (uint8_t *)d_digests,
+                           (hipStream_t)stream);
+}
+
+uint64_t cw_chunk_slot_offset(int comp_alg, uint64_t o, uint64_t i) { return cw::chunk_slot_offset(comp_alg != CW_COMP_LZF, o, i); }
+size_t cw_chunk_slots_bytes(int comp_alg, size_t src_bytes, size_t max_chunks)
+{
+    return (size_t)cw_chunk_slot_offset(comp_alg, src_bytes, max_chunks) + 16;
+}
+
+int cw_dev_compress_chunks(int comp_alg, const void *d_src, size_t src_bytes, const uint64_t *d_offsets, const uint64_t *d_nchunks,
+                           size_t max_chunks, const uint32_t *d_sel, const uint64_t *d_nsel, void *d_dst, size_t dst_bytes,
+                           uint32_t *d_sizes, void *stream)
+{
+    int rc = compress_chunks_args(comp_alg, d_src, src_bytes, d_offsets, d_nchunks, max_chunks, d_sel, d_nsel, d_dst, dst_bytes, d_sizes);
+    if (rc != CW_OK) return rc;
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    return dev_compress_chunks(comp_alg, (const uint8_t *)d_src, src_bytes, d_offsets, d_nchunks, max_chunks, d_sel, d_nsel, (uint8_t *)d_dst,
+                               d_sizes, (hipStream_t)stream);
+}
+
+int cw_dev_pack_chunks(int comp_alg, const void *d_slots, const uint64_t *d_offsets, const uint32_t *d_sel, const uint64_t *d_count,
+                       size_t max_count, const uint32_t *d_sizes, void *d_packed, uint64_t *d_packed_offsets, void *stream)
+{
+    int rc;
+    if ((rc = check_codec(comp_alg)) != CW_OK || (rc = check_count("max_count", max_count)) != CW_OK) return rc;
+    if (!d_packed_offsets || (max_count && (!d_count || !d_sizes || (d_packed && (!d_slots || !d_offsets)))))
+        return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    return launched_nomem(cw::chunk_pack_launch(comp_alg == CW_COMP_LZF, (const uint8_t *)d_slots, d_offsets, d_sel, d_count, max_count, d_sizes,
+                                                (uint8_t *)d_packed, d_packed_offsets, (hipStream_t)stream),
+                          "pack chunks launch");
+}
+
+int cw_dev_decompress_chunks(int comp_alg, const void *d_comp, const uint64_t *d_comp_offsets, const uint64_t *d_raw_offsets,
+                             const uint64_t *d_count, size_t max_count, void *d_dst, size_t dst_bytes, uint32_t *d_status, void *stream)
+{
+    int rc;
+    if ((rc = check_codec(comp_alg)) != CW_OK || (rc = check_count("max_count", max_count)) != CW_OK) return rc;
+    if (max_count && (!d_comp || !d_comp_offsets || !d_raw_offsets || !d_count || !d_status || (dst_bytes && !d_dst)))
+        return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    ProfScope prof(PROF_CODEC, (hipStream_t)stream);
+    return launched(cw::chunk_decompress_launch(comp_alg == CW_COMP_LZF, (const uint8_t *)d_comp, d_comp_offsets, d_raw_offsets, d_count, max_count,
+                                                (uint8_t *)d_dst, dst_bytes, d_status, (hipStream_t)stream),
+                    "decompress chunks launch");
+}
+
+// ---- the chunk store (kernels: restore_kernels.hip) -------------------------------------------------------------------------
+static_assert(sizeof(cw_chunk_loc) == 16, "cw_chunk_loc is one 16-byte store");
+
+int cw_dev_store_chunks(int comp_alg, const void *d_src, size_t src_bytes, const uint64_t *d_offsets, const uint64_t *d_nchunks,
+                        size_t max_chunks, const uint32_t *d_sel, const uint64_t *d_nsel, const void *d_slots, const uint32_t *d_sizes,
+                        uint64_t base, void *d_store, size_t store_bytes, uint64_t *d_used, cw_chunk_loc *d_dir, uint64_t dir_base,
+                        size_t dir_entries, uint64_t *d_result, void *stream)
+{
+    int rc;
+    if ((rc = check_codec(comp_alg)) != CW_OK || (rc = check_count("max_chunks", max_chunks)) != CW_OK) return rc;
+    if (!d_offsets || !d_nchunks || !d_slots || !d_sizes || !d_used || !d_dir || !d_result || (src_bytes && !d_src) || (store_bytes && !d_store) ||
+        !d_sel != !d_nsel)
+        return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    if (dir_entries == 0) return fail(CW_ERR_BAD_ARG, "dir_entries is 0");
+    if ((rc = check_dir_aligned((uintptr_t)d_dir, "d_dir")) != CW_OK) return rc;
+    if ((rc = check_word_aligned((uintptr_t)d_used | (uintptr_t)d_result, "d_used / d_result")) != CW_OK) return rc;
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    return launched_nomem(cw::chunk_store_launch(comp_alg == CW_COMP_LZF, (const uint8_t *)d_src, src_bytes, d_offsets, d_nchunks, max_chunks, d_sel,
+                                                 d_nsel, (const uint8_t *)d_slots, d_sizes, base, (uint8_t *)d_store, store_bytes, d_used, d_dir,
+                                                 dir_base, dir_entries, d_result, (hipStream_t)stream),
+                          "store chunks launch");
+}
+
+int cw_dev_restore_chunks(int comp_alg, const void *d_store, size_t store_bytes, const cw_chunk_loc *d_dir, uint64_t dir_base,
+                          size_t dir_entries, const uint64_t *d_ref, const uint64_t *d_raw_offsets, const uint64_t *d_count, size_t max_count,
+                          void *d_dst, size_t dst_bytes, uint32_t *d_status, void *stream)
+{
+    int rc;
+    if ((rc = check_codec(comp_alg)) != CW_OK || (rc = check_count("max_count", max_count)) != CW_OK) return rc;
+    if (!d_dir || !d_ref || !d_raw_offsets || !d_count || !d_status || (store_bytes && !d_store) || (dst_bytes && !d_dst))
+        return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    if (dir_entries == 0) return fail(CW_ERR_BAD_ARG, "dir_entries is 0");
+    if ((rc = check_dir_aligned((uintptr_t)d_dir, "d_dir")) != CW_OK) return rc;
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    ProfScope prof(PROF_CODEC, (hipStream_t)stream);
+    return launched(cw::chunk_restore_launch(comp_alg == CW_COMP_LZF, (const uint8_t *)d_store, store_bytes, d_dir, dir_base, dir_entries, d_ref,
+                                             d_raw_offsets, d_count, max_count, (uint8_t *)d_dst, dst_bytes, d_status, (hipStream_t)stream),
+                    "restore chunks launch");
+}
+
+// ---- the chunk store forgets: mark and compact (kernels: store_gc_kernels.hip) -------------------------------------------------
+int cw_dev_store_mark(const uint64_t *d_ref, const uint64_t *d_count, size_t max_count, uint64_t dir_base, size_t dir_entries, uint32_t *d_live,
+                      uint64_t *d_n_outside, void *stream)
+{
+    int rc = check_count("max_count", max_count);
+    if (rc != CW_OK) return rc;
+    if (!d_ref || !d_count || !d_live || !d_n_outside) return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    if (dir_entries == 0) return fail(CW_ERR_BAD_ARG, "dir_entries is 0");
+    if ((rc = check_word_aligned((uintptr_t)d_n_outside, "d_n_outside")) != CW_OK) return rc;
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    return launched(cw::store_mark_launch(d_ref, d_count, max_count, dir_base, dir_entries, d_live, d_n_outside, (hipStream_t)stream),
+                    "store mark launch");
+}
+
+int cw_dev_store_compact(const void *d_store, size_t store_bytes, const cw_chunk_loc *d_dir, size_t dir_entries, const uint32_t *d_live,
+                         void *d_new_store, size_t new_store_bytes, uint64_t *d_new_used, cw_chunk_loc *d_new_dir, uint64_t *d_result,
+                         void *stream)
+{
+    int rc;
+    if (!d_dir || !d_live || !d_new_used || !d_new_dir || !d_result || (store_bytes && !d_store) || (new_store_bytes && !d_new_store))
+        return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    if (dir_entries == 0) return fail(CW_ERR_BAD_ARG, "dir_entries is 0");
+    if ((rc = check_dir_aligned((uintptr_t)d_dir | (uintptr_t)d_new_dir, "d_dir / d_new_dir")) != CW_OK) return rc;
+    if ((rc = check_word_aligned((uintptr_t)d_new_used | (uintptr_t)d_result, "d_new_used / d_result")) != CW_OK) return rc;
+    if (ranges_overlap(d_store, store_bytes, d_new_store, new_store_bytes)) return fail(CW_ERR_BAD_ARG, "d_new_store overlaps d_store");
+    if (d_new_dir != d_dir && ranges_overlap(d_dir, dir_entries * sizeof(cw_chunk_loc), d_new_dir, dir_entries * sizeof(cw_chunk_loc)))
+        return fail(CW_ERR_BAD_ARG, "d_new_dir overlaps d_dir without being d_dir");
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    return launched_nomem(cw::store_compact_launch((const uint8_t *)d_store, store_bytes, d_dir, dir_entries, d_live, (uint8_t *)d_new_store,
+                                                   new_store_bytes, d_new_used, d_new_dir, d_result, (hipStream_t)stream),
+                          "store compact launch");
+}
+
+} // extern "C"

@@ -542,3 +542,54 @@ def test_bad_arguments_launch_nothing(cw):
         torch.cuda.synchronize()
         assert (u.cpu() == 77).all() and idx.count() == 4 and idx.max_entries == 64
         check_lookup(idx, model, d)
+
+
+@pytest.mark.parametrize("refusal", ["cdc_full", "cdc_wraps", "dedupe_full", "dedupe_wraps"])
+def test_a_refused_call_on_one_stream_orders_the_next_call_on_another(cw, refusal):
+    """A call that is refused after it queued work -- the fused chunk call once its cut and hash are queued: the index is full, or
+    base + the chunk count wraps -- or before it queued any (cw_dev_dedupe: too many blocks, a base that wraps) leaves the index
+    usable from another stream with no synchronisation by the caller: an insert of 32 digests and a lookup of them answer as the
+    model does."""
+    import torch
+    db = 64
+    rng = np.random.default_rng(77)
+    with cw.DedupeIndex("skein512", 64) as idx:
+        model = Model()
+        known = rng.integers(0, 256, (32, db), dtype=np.uint8)
+        values = 1000 + 3 * np.arange(32, dtype=np.uint64)
+        d_known, d_values = _dev(known), _dev(values)
+        z = lambda n, dt, v: torch.full((n,), v, dtype=dt, device="cuda")  # noqa: E731
+        ref, new_idx, n_new = z(32, torch.int64, -1), z(32, torch.int32, -1), z(1, torch.int64, -1)
+        found, n_found = z(32, torch.int64, 12345), z(1, torch.int64, -7)
+        a, b = torch.cuda.Stream(), torch.cuda.Stream()
+        p = cw.CdcParams.default(256)
+        src = torch.from_numpy(rng.integers(0, 256, 64 << 10, dtype=np.uint8)).cuda()
+        cap = p.max_offsets(src.numel())
+        off, k, dig = z(cap, torch.int64, 0), z(1, torch.int64, 0), z(cap * db, torch.uint8, 0)
+        c_ref, c_new, c_n_new = z(cap, torch.int64, -1), z(cap, torch.int32, -1), z(1, torch.int64, -1)
+        total = cw.chunk_slots_bytes("lz4", src.numel(), cap - 1)
+        dst, sizes = z(total, torch.uint8, 0), z(cap, torch.int32, -1)
+        many = _dev(rng.integers(0, 256, (256, db), dtype=np.uint8))
+        torch.cuda.synchronize()  # (torch filled the buffers on its own stream)
+        with pytest.raises(cw.CwError) as e:
+            if refusal.startswith("cdc"):
+                idx.dev_cdc_dedupe_compress(p, "lz4", src.data_ptr(), src.numel(), True, 0 if refusal == "cdc_full" else 2 ** 64 - 1, off.data_ptr(),
+                                            cap, k.data_ptr(), dig.data_ptr(), c_ref.data_ptr(), c_new.data_ptr(), c_n_new.data_ptr(),
+                                            dst.data_ptr(), total, sizes.data_ptr(), a.cuda_stream)
+            else:
+                idx.dev_dedupe(many.data_ptr(), 256, 0 if refusal == "dedupe_full" else 2 ** 64 - 1, c_ref.data_ptr(), c_new.data_ptr(),
+                               c_n_new.data_ptr(), a.cuda_stream)
+        assert e.value.code == (CW_ERR_NOMEM if refusal.endswith("full") else CW_ERR_BAD_ARG)
+        if refusal.startswith("cdc"):
+            assert e.value.nchunks > 64, e.value.nchunks
+        idx.dev_insert(d_known.data_ptr(), d_values.data_ptr(), 32, ref.data_ptr(), new_idx.data_ptr(), n_new.data_ptr(), b.cuda_stream)
+        idx.dev_lookup(d_known.data_ptr(), 32, found.data_ptr(), n_found.data_ptr(), b.cuda_stream)
+        torch.cuda.synchronize()
+        mref, mnew = model.insert(known, values)
+        assert np.array_equal(ref.cpu().numpy().view(np.uint64), mref)
+        assert int(n_new.item()) == len(mnew) == 32 and np.array_equal(new_idx.cpu().numpy().view(np.uint32), mnew)
+        lref, lfound = model.lookup(known)
+        assert np.array_equal(found.cpu().numpy().view(np.uint64), lref) and int(n_found.item()) == lfound == 32
+        assert idx.count() == 32
+        if refusal.startswith("cdc"):  # the refused call wrote its cuts, and nothing of the dedupe or the codec
+            assert int(k.item()) == e.value.nchunks and (c_ref.cpu() == -1).all() and (sizes.cpu() == -1).all()
