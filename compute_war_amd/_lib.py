@@ -30,7 +30,7 @@ ABI_SYMBOLS = [
     "cw_dedupe_set_stage_entries", "cw_dedupe_resize", "cw_dedupe_max_entries",
     "cw_cdc_default_params", "cw_dev_cdc", "cw_dev_hash_chunks", "cw_cdc_hash",
     "cw_chunk_slot_offset", "cw_chunk_slots_bytes", "cw_dev_compress_chunks", "cw_dev_pack_chunks", "cw_dev_decompress_chunks",
-    "cw_dev_cdc_dedupe_compress", "cw_dev_store_chunks", "cw_dev_restore_chunks",
+    "cw_dev_cdc_dedupe_compress", "cw_dev_store_chunks", "cw_dev_restore_chunks", "cw_dev_read_ranges",
     "cw_dev_store_mark", "cw_dev_store_compact", "cw_dedupe_retain",
     "cw_shard_range", "cw_mgpu_create", "cw_mgpu_destroy", "cw_mgpu_ndev", "cw_mgpu_device", "cw_mgpu_last_error", "cw_mgpu_gather",
 ]
@@ -150,6 +150,7 @@ def lib() -> C.CDLL:
                                        C.c_int),
         "cw_dev_store_chunks": ([C.c_int, vp, sz, vp, vp, sz, vp, vp, vp, u32p, C.c_uint64, vp, sz, vp, vp, C.c_uint64, sz, vp, vp], C.c_int),
         "cw_dev_restore_chunks": ([C.c_int, vp, sz, vp, C.c_uint64, sz, vp, vp, vp, sz, vp, sz, u32p, vp], C.c_int),
+        "cw_dev_read_ranges": ([C.c_int, vp, sz, vp, C.c_uint64, sz, vp, vp, vp, sz, vp, vp, vp, vp, sz, vp, sz, u32p, vp], C.c_int),
         "cw_dev_store_mark": ([vp, vp, sz, C.c_uint64, sz, u32p, vp, vp], C.c_int),
         "cw_dev_store_compact": ([vp, sz, vp, sz, u32p, vp, sz, vp, vp, vp, vp], C.c_int),
         "cw_dedupe_retain": ([vp, u32p, C.c_uint64, sz, sz, vp], C.c_int),

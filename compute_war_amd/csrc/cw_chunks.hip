@@ -1,6 +1,6 @@
 // cw_chunks.hip -- host side of the device-resident calls over content-defined chunks: the cut (kernels: cdc_kernels.hip), the per-chunk
-// hash, the chunk codecs and their pack (chunk_codec_kernels.hip, pack_kernels.hip), the chunk store (restore_kernels.hip) and its mark and
-// compact (store_gc_kernels.hip).  Semantics: the public header.  Every refusal here comes before the device is touched.
+// hash, the chunk codecs and their pack (chunk_codec_kernels.hip, pack_kernels.hip), the chunk store (restore_kernels.hip), its ranged reads (read_kernels.hip)
+// and its mark and compact (store_gc_kernels.hip).  Semantics: the public header.  Every refusal here comes before the device is touched.
 
 #include "cw_host.h"
 
@@ -228,6 +228,30 @@ int cw_dev_restore_chunks(int comp_alg, const void *d_store, size_t store_bytes,
     return launched(cw::chunk_restore_launch(comp_alg == CW_COMP_LZF, (const uint8_t *)d_store, store_bytes, d_dir, dir_base, dir_entries, d_ref,
                                              d_raw_offsets, d_count, max_count, (uint8_t *)d_dst, dst_bytes, d_status, (hipStream_t)stream),
                     "restore chunks launch");
+}
+
+int cw_dev_read_ranges(int comp_alg, const void *d_store, size_t store_bytes, const cw_chunk_loc *d_dir, uint64_t dir_base, size_t dir_entries,
+                       const uint64_t *d_ref, const uint64_t *d_raw_offsets, const uint64_t *d_count, size_t max_count,
+                       const uint64_t *d_range_off, const uint64_t *d_range_len, const uint64_t *d_range_dst, const uint64_t *d_nranges,
+                       size_t max_ranges, void *d_dst, size_t dst_bytes, uint32_t *d_status, void *stream)
+{
+    int rc;
+    if ((rc = check_codec(comp_alg)) != CW_OK || (rc = check_count("max_count", max_count)) != CW_OK ||
+        (rc = check_count("max_ranges", max_ranges)) != CW_OK)
+        return rc;
+    if (!d_dir || !d_ref || !d_raw_offsets || !d_count || !d_range_off || !d_range_len || !d_range_dst || !d_nranges || !d_status ||
+        (store_bytes && !d_store) || (dst_bytes && !d_dst))
+        return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    if (dir_entries == 0) return fail(CW_ERR_BAD_ARG, "dir_entries is 0");
+    if ((rc = check_dir_aligned((uintptr_t)d_dir, "d_dir")) != CW_OK) return rc;
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    ProfScope prof(PROF_CODEC, (hipStream_t)stream);
+    const hipError_t e = cw::read_ranges_launch(comp_alg == CW_COMP_LZF, (const uint8_t *)d_store, store_bytes, d_dir, dir_base, dir_entries, d_ref,
+                                                d_raw_offsets, d_count, max_count, d_range_off, d_range_len, d_range_dst, d_nranges, max_ranges,
+                                                (uint8_t *)d_dst, dst_bytes, d_status, (hipStream_t)stream);
+    if (e == hipErrorOutOfMemory)
+        return fail(CW_ERR_NOMEM, "read ranges scratch (up to %zu bytes): %s", cw::read_ranges_scratch_bytes(max_ranges), hipGetErrorString(e));
+    return launched(e, "read ranges launch");
 }
 
 // ---- the chunk store forgets: mark and compact (kernels: store_gc_kernels.hip) -------------------------------------------------

@@ -230,6 +230,12 @@ hipError_t chunk_store_launch(int lzf, const uint8_t *src, size_t src_bytes, con
 hipError_t chunk_restore_launch(int lzf, const uint8_t *store, size_t store_bytes, const void *dir, uint64_t dir_base, size_t dir_entries,
                                 const uint64_t *ref, const uint64_t *raw_offsets, const uint64_t *d_count, size_t max_count, uint8_t *dst,
                                 size_t dst_bytes, uint32_t *status, hipStream_t stream);
+// byte ranges of a restored stream (read_kernels.hip; semantics: the public header).  The recipe as chunk_restore_launch takes it
+hipError_t read_ranges_launch(int lzf, const uint8_t *store, size_t store_bytes, const void *dir, uint64_t dir_base, size_t dir_entries,
+                              const uint64_t *ref, const uint64_t *raw_offsets, const uint64_t *d_count, size_t max_count,
+                              const uint64_t *range_off, const uint64_t *range_len, const uint64_t *range_dst, const uint64_t *d_nranges,
+                              size_t max_ranges, uint8_t *dst, size_t dst_bytes, uint32_t *status, hipStream_t stream);
+size_t read_ranges_scratch_bytes(size_t max_ranges); // what a call reserves at most
 
 // mark and compact (store_gc_kernels.hip; semantics: the public header).  new_dir may be dir itself
 hipError_t store_mark_launch(const uint64_t *ref, const uint64_t *d_count, size_t max_count, uint64_t dir_base, size_t dir_entries,

@@ -636,6 +636,17 @@ def dev_restore_chunks(comp_alg, d_store: int, store_bytes: int, d_dir: int, dir
                                       d_raw_offsets, d_count, max_count, d_dst or None, dst_bytes, d_status, stream))
 
 
+def dev_read_ranges(comp_alg, d_store: int, store_bytes: int, d_dir: int, dir_base: int, dir_entries: int, d_ref: int, d_raw_offsets: int,
+                    d_count: int, max_count: int, d_range_off: int, d_range_len: int, d_range_dst: int, d_nranges: int, max_ranges: int,
+                    d_dst: int, dst_bytes: int, d_status: int, stream: int = 0) -> None:
+    """Range k < min(*d_nranges, max_ranges): stream bytes [range_off[k], + range_len[k]) of the recipe (dev_restore_chunks' arguments,
+    in raw_offsets' coordinates) into d_dst[range_dst[k] ..); d_status[k] = 0 read, 1 a touched chunk's stored bytes are malformed,
+    2 a touched position is refused as dev_restore_chunks refuses it, 3 the range leaves the stream or the destination."""
+    check(lib().cw_dev_read_ranges(_comp_id(comp_alg), d_store or None, store_bytes, d_dir, dir_base, dir_entries, d_ref, d_raw_offsets,
+                                   d_count, max_count, d_range_off, d_range_len, d_range_dst, d_nranges, max_ranges, d_dst or None,
+                                   dst_bytes, d_status, stream))
+
+
 def dev_store_mark(d_ref: int, d_count: int, max_count: int, dir_base: int, dir_entries: int, d_live: int, d_n_outside: int,
                    stream: int = 0) -> None:
     """d_live[d_ref[j] - dir_base] = 1 (u32) for every position j < min(*d_count, max_count) that names a directory entry;
@@ -668,7 +679,7 @@ class Recipe:
 
 class ChunkStore:
     """A dedupe index with the bytes behind it: ``ingest`` chunks, dedupes and compresses a buffer and appends its new chunks to a
-    device-resident store, ``restore`` turns a recipe back into bytes, ``compact`` forgets every stream but the ones named.
+    device-resident store, ``restore`` turns a recipe back into bytes, ``read`` / ``read_ranges`` give byte ranges of it, ``compact`` forgets every stream but the ones named.
     The store is three torch buffers this object owns (bytes, cursor, directory: the caller-owned triple of cw_dev_store_chunks);
     chunk values count up from ``dir_base`` over the ingests.
     One device call per ingest: the whole buffer has to fit on the device next to its slots."""
@@ -755,6 +766,44 @@ class ChunkStore:
                 raise _lib.CwError(-2, f"chunk store: verify failed at position {int(bad[0])}: the index answers {int(got[bad[0]])}, "
                                        f"the recipe says {int(recipe.refs[bad[0]])} ({len(bad)} positions differ)")
         return out.cpu().numpy()[:n].tobytes()
+
+    def read_ranges(self, recipe: Recipe, ranges) -> list:
+        """The bytes of the ranges ``(offset, length)`` of an ingested stream, in the recipe's own zero-based coordinates, without
+        restoring the stream: one device call, the destinations packed back to back.  Raises CwError (-2) naming the first range
+        with a status other than 0."""
+        if device_count() <= 0:
+            init()  # (raises: no device)
+        import torch
+        ranges = [(int(o), int(l)) for o, l in ranges]
+        k, m, s = len(recipe.refs), len(ranges), self._stream()
+        if m == 0:
+            return []
+        if any(o < 0 or l < 0 or o + l >= 1 << 64 for o, l in ranges):
+            raise ValueError("ranges are (offset, length) with 0 <= offset, 0 <= length and offset + length < 2^64")
+        lens = np.array([l for _, l in ranges], np.uint64)
+        dsts = np.concatenate([[0], np.cumsum(lens, dtype=np.uint64)]).astype(np.uint64)
+        total = int(dsts[-1])
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64).copy()).cuda()  # noqa: E731
+        d_ref, d_raw, d_count = up(recipe.refs if k else [0]), up(recipe.offsets - recipe.offsets[0]), up([k])
+        d_off, d_len, d_to, d_m = up([o for o, _ in ranges]), up(lens), up(dsts[:-1]), up([m])
+        out = torch.zeros(max(total, 1), dtype=torch.uint8, device="cuda")
+        status = torch.zeros(m, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        dev_read_ranges(self.comp_alg, self.d_store.data_ptr(), self.store_bytes, self.d_dir.data_ptr(), self.dir_base, self.dir_entries,
+                        d_ref.data_ptr(), d_raw.data_ptr(), d_count.data_ptr(), k, d_off.data_ptr(), d_len.data_ptr(), d_to.data_ptr(),
+                        d_m.data_ptr(), m, out.data_ptr(), total, status.data_ptr(), s)
+        torch.cuda.synchronize()
+        st = status.cpu().numpy()
+        if st.any():
+            j = int(np.nonzero(st)[0][0])
+            raise _lib.CwError(-2, f"chunk store: {int((st != 0).sum())} of {m} ranges not read; range {j} (offset {ranges[j][0]}, length "
+                                   f"{ranges[j][1]}) has status {int(st[j])}")
+        host = out.cpu().numpy()
+        return [host[int(dsts[i]):int(dsts[i + 1])].tobytes() for i in range(m)]
+
+    def read(self, recipe: Recipe, offset: int, length: int) -> bytes:
+        """Bytes [offset, offset + length) of an ingested stream: ``read_ranges`` with one range."""
+        return self.read_ranges(recipe, [(offset, length)])[0]
 
     def compact(self, keep, store_bytes: int | None = None) -> dict:
         """Forget every stream but the recipes in ``keep``: mark their chunks, move the marked chunks' stored bytes into a new store

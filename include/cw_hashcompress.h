@@ -431,6 +431,46 @@ int cw_dev_restore_chunks(int comp_alg, const void *d_store, size_t store_bytes,
                           uint64_t dir_base, size_t dir_entries, const uint64_t *d_ref, const uint64_t *d_raw_offsets,
                           const uint64_t *d_count, size_t max_count, void *d_dst, size_t dst_bytes,
                           uint32_t *d_status, void *stream);
+/* Byte ranges of a stream without rebuilding it.  The store, the directory and the recipe are
+ * cw_dev_restore_chunks' arguments; n = min(*d_count, max_count) and R = min(*d_nranges, max_ranges) are read on the device, and
+ * nothing behind position n of the recipe or entry R of the range arrays is read.  Stream coordinates are d_raw_offsets' own: the
+ * stream is [d_raw_offsets[0], d_raw_offsets[n]), and d_raw_offsets[0] need not be 0.  Range k < R is the stream bytes
+ * [a, a + len), a = d_range_off[k], len = d_range_len[k]; stream byte x of it goes to d_dst[d_range_dst[k] + (x - a)].  Position j
+ * is touched by a range iff its raw extent [d_raw_offsets[j], d_raw_offsets[j+1]) is non-empty and intersects the range.
+ * d_status[k] (one u32 per range; no d_status[k] with k >= R is written) =
+ *   3  the range is refused, nothing is read from the store and nothing written: len > 0 and a < d_raw_offsets[0], a + len wraps
+ *      or exceeds d_raw_offsets[n], n == 0, d_range_dst[k] + len wraps or exceeds dst_bytes.  len == 0 is never refused: it gives
+ *      0 and reads and writes nothing, whatever a and d_range_dst[k] are;
+ *   otherwise the largest status among the touched positions, each judged exactly as cw_dev_restore_chunks judges it, except
+ *      that the destination check is the range's and not the chunk's:
+ *   2  d_ref[j] outside [dir_base, dir_base + dir_entries); an entry with length 0, a length above 65536 or bits 17..30 set; a
+ *      length that is not the raw extent's; stored == 0; a raw entry with stored != length; pos + stored > store_bytes; a raw
+ *      extent that is decreasing or longer than 65536;
+ *   1  the stored bytes are malformed: the decoder's verdict on the WHOLE chunk, so a range that ends before the damaged spot of
+ *      a chunk still gets 1 -- the verdict is a property of the stored chunk, as everywhere else in this library;
+ *   0  every byte of the range's destination extent holds the stream's byte.
+ * A range with a status other than 0 leaves the bytes inside its own destination extent unspecified.  Whatever the store, the
+ * directory, the recipe and the range arrays hold, no load leaves d_store[0..store_bytes), d_dir[0..dir_entries), the recipe or the
+ * range arrays, and no store leaves d_dst[d_range_dst[k] .. + len) of a range k with a status other than 3, or d_status[0..R).
+ * Ranges may overlap in the stream and name the same chunks: each is served on its own, a chunk named twice is decoded twice.
+ * Ranges whose destination extents overlap are the caller's business.  d_raw_offsets[0..n] is expected to be non-decreasing (what
+ * cw_dev_cdc writes); for any other list, which positions a range is taken to touch is unspecified -- every position taken is
+ * still checked as above, and the sentence on loads and stores holds unchanged.
+ * A compressed chunk that lies wholly inside its range is decoded straight into d_dst, raw entries are copied clipped to the
+ * range; the at most two compressed chunks a range covers only in part (its first and its last) are decoded whole into scratch
+ * and their covered bytes copied out.  Scratch, per stream and freed like cw_dev_cdc's: 72 + 16 * max_ranges bytes (the first
+ * touched position, the piece count and the scanned piece offset of every range) and one 64 KiB decode buffer per edge lane,
+ * min(2 * max_ranges, 16384) of them (1 GiB at most; 384 KiB for three ranges); if the device cannot give the buffers the call
+ * runs with half the lanes, and so on down to 64, before it fails with CW_ERR_NOMEM.
+ * CW_ERR_BAD_ARG before anything is launched: a NULL pointer (d_store when store_bytes is 0 and d_dst when dst_bytes is 0 may be),
+ * an unknown codec, max_count or max_ranges > 2^32 - 256, dir_entries == 0, a d_dir that is not 16-byte aligned.
+ * max_ranges == 0 is a no-op.  Not synchronised.                                                                              */
+int cw_dev_read_ranges(int comp_alg, const void *d_store, size_t store_bytes, const cw_chunk_loc *d_dir,
+                       uint64_t dir_base, size_t dir_entries, const uint64_t *d_ref, const uint64_t *d_raw_offsets,
+                       const uint64_t *d_count, size_t max_count,
+                       const uint64_t *d_range_off, const uint64_t *d_range_len, const uint64_t *d_range_dst,
+                       const uint64_t *d_nranges, size_t max_ranges,
+                       void *d_dst, size_t dst_bytes, uint32_t *d_status, void *stream);
 
 /* ---- the store forgets: mark, compact, and the index's retain ----------------------------------------
  * Mark and sweep over the same caller-owned buffers, plus one more the caller owns: d_live[dir_entries] (u32), a flag per
