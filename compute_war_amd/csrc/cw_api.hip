@@ -231,24 +231,23 @@ int cw::host::check_count(const char *name, size_t n)
     return n <= ((size_t)1 << 32) - 256 ? CW_OK : fail(CW_ERR_BAD_ARG, "%s %zu > 2^32 - 256", name, n);
 }
 
-int cw::host::dev_hash(int alg, const uint8_t *d_src, size_t bb, size_t stride, size_t n, uint8_t *d_dig, hipStream_t s, bool lean, bool sliced)
+// the state words of the plan's call (launch_plan.h): 8 / 4 for the two Skeins, 0 for SHA-256, -1 for no hash kernel at all
+static int hash_state_words(int alg)
 {
-    hipError_t e;
+    return alg == CW_HASH_SKEIN512 ? 8 : alg == CW_HASH_SKEIN256_128 ? 4 : alg == CW_HASH_SHA256 ? 0 : -1;
+}
+
+// plan (launch_plan.cpp: every decision), enqueue
+int cw::host::dev_hash(int alg, const uint8_t *d_src, size_t bb, size_t stride, size_t n, uint8_t *d_dig, hipStream_t s, bool sliced)
+{
     ProfScope prof(PROF_HASH, s);
-    // CW_SKEIN_SLICED=0: always the one-launch hash kernel (profiling knob)
-    if (sliced && cw::knobs().skein_sliced && (alg == CW_HASH_SKEIN512 || alg == CW_HASH_SKEIN256_128)) {
-        const int nw = alg == CW_HASH_SKEIN512 ? 8 : 4;
-        if (cw::skein_sliced_applies(nw, d_src, bb, stride, n, d_dig))
-            return launched(cw::skein_sliced_launch(nw, d_src, bb, stride, n, skein_iv(nw), d_dig, nw == 8 ? 64 : 16, s), "hash launch");
-    }
-    switch (alg) {
-    case CW_HASH_SKEIN512: e = cw::skein512_launch(d_src, bb, stride, n, g_iv512_512, d_dig, 64, s, lean); break;
-    case CW_HASH_SKEIN256_128: e = cw::skein256_launch(d_src, bb, stride, n, g_iv256_128, d_dig, 16, s, lean); break;
-    case CW_HASH_SHA256: e = cw::sha256_launch(d_src, bb, stride, n, d_dig, s); break;
-    case CW_HASH_NONE: return CW_OK;
-    default: return fail(CW_ERR_BAD_ARG, "unknown hash algorithm %d", alg);
-    }
-    return launched(e, "hash launch");
+    if (alg == CW_HASH_NONE) return CW_OK;
+    const int nw = hash_state_words(alg);
+    if (nw < 0) return fail(CW_ERR_BAD_ARG, "unknown hash algorithm %d", alg);
+    const cw::HashPlan p = cw::hash_plan(cw::hash_call(nw, d_src, bb, stride, n, d_dig, sliced), cw::knobs());
+    return launched(nw ? cw::skein_launch(p, d_src, bb, stride, n, skein_iv(nw), d_dig, nw == 8 ? 64 : 16, s)
+                       : cw::sha256_launch(p, d_src, bb, stride, n, d_dig, s),
+                    "hash launch");
 }
 
 int cw::host::dev_compress(int alg, const uint8_t *d_src, size_t bb, size_t stride, size_t n, uint8_t *d_dst, size_t dst_stride,
@@ -408,6 +407,22 @@ int cw_plan_describe(int comp_alg, size_t block_bytes, size_t nblocks, unsigned 
     return CW_OK;
 }
 
+int cw_hash_plan_describe(int hash_alg, size_t block_bytes, size_t nblocks, unsigned src_misalign, unsigned digest_misalign, int may_slice,
+                          char *buf, size_t cap)
+{
+    const int nw = hash_state_words(hash_alg);
+    if (nw < 0 && hash_alg != CW_HASH_NONE) return fail(CW_ERR_BAD_ARG, "unknown hash algorithm %d", hash_alg);
+    if (int bad = check_block(block_bytes)) return bad;
+    std::string text = "\n"; // (no blocks, no hash: such a call launches nothing)
+    if (nblocks && nw >= 0) {
+        const cw::HashPlan p = cw::hash_plan({nw, block_bytes, nblocks, src_misalign & 15, digest_misalign & 15, may_slice != 0}, cw::knobs());
+        text = std::string(cw::describe(p).text) + "\n" + cw::dump(p);
+    }
+    if (!buf || cap <= text.size()) return fail(CW_ERR_BAD_ARG, "cw_hash_plan_describe: the text needs a buffer of %zu bytes", text.size() + 1);
+    memcpy(buf, text.c_str(), text.size() + 1);
+    return CW_OK;
+}
+
 // ---- lifecycle ------------------------------------------------------------------------------------
 int cw_device_count(void)
 {
@@ -495,7 +510,7 @@ int cw_dev_hash(int hash_alg, const void *d_src, size_t block_bytes, size_t src_
     if (src_stride < block_bytes) return fail(CW_ERR_BAD_ARG, "src_stride < block_bytes");
     // long Skein messages in sliced launches here too: alone they are as fast as the one-launch kernel (46.6 ms per Mi blocks
     // either way, slightly ahead on small batches), and the hot kernel is then the same with and without a codec beside it
-    return dev_hash(hash_alg, (const uint8_t *)d_src, block_bytes, src_stride, nblocks, (uint8_t *)d_digests, (hipStream_t)stream, false, true);
+    return dev_hash(hash_alg, (const uint8_t *)d_src, block_bytes, src_stride, nblocks, (uint8_t *)d_digests, (hipStream_t)stream, true);
 }
 
 int cw_dev_compress(int comp_alg, const void *d_src, size_t block_bytes, size_t src_stride, size_t nblocks, void *d_dst,
@@ -522,7 +537,7 @@ static int dev_fused(cw::SideStream &side_s, int hash_alg, int comp_alg, const u
     const cw::Knobs kn = cw::knobs();
     if (kn.serial) { // CW_SERIAL=1: both kernels on the caller's stream (profiling knob)
         rc = dev_compress(comp_alg, d_src, block_bytes, src_stride, nblocks, d_dst, dst_stride, d_sizes, main_s);
-        return rc == CW_OK ? dev_hash(hash_alg, d_src, block_bytes, src_stride, nblocks, d_digests, main_s, false, true) : rc;
+        return rc == CW_OK ? dev_hash(hash_alg, d_src, block_bytes, src_stride, nblocks, d_digests, main_s, true) : rc;
     }
     cw::SideStream::Fork fork(side_s, main_s); // (a return before the join below still joins)
     HIP_TRY(fork.err);
@@ -542,7 +557,7 @@ static int dev_fused(cw::SideStream &side_s, int hash_alg, int comp_alg, const u
     const cw::AfterScan hook = {[](void *p) -> hipError_t {
                                     Gate *g = static_cast<Gate *>(p);
                                     g->called = true;
-                                    g->rc = dev_hash(g->hash_alg, g->src, g->bb, g->stride, g->n, g->dig, g->side, false, true);
+                                    g->rc = dev_hash(g->hash_alg, g->src, g->bb, g->stride, g->n, g->dig, g->side, true);
                                     return g->rc != CW_OK ? hipErrorUnknown : g->fork->join();
                                 }, &gate};
     ThreadCtx *tc = nullptr;
@@ -560,7 +575,7 @@ static int dev_fused(cw::SideStream &side_s, int hash_alg, int comp_alg, const u
     const bool gated = hint && (kn.fused_gate ? *kn.fused_gate : block_bytes <= 4096 && nblocks >= 16384 && hint->queued_share >= 0.25f);
     rc = dev_compress(comp_alg, d_src, block_bytes, src_stride, nblocks, d_dst, dst_stride, d_sizes, main_s, gated ? &hook : nullptr);
     if (gate.called && gate.rc != CW_OK) return gate.rc;
-    if (rc == CW_OK && !gate.called) rc = dev_hash(hash_alg, d_src, block_bytes, src_stride, nblocks, d_digests, side, false, true);
+    if (rc == CW_OK && !gate.called) rc = dev_hash(hash_alg, d_src, block_bytes, src_stride, nblocks, d_digests, side, true);
     HIP_TRY(fork.join());
     if (rc == CW_OK && hint && !hint->pending) { // this call's queued share, for the next call
         const uint32_t *word = cw::lz4_queued_blocks_word(main_s);
@@ -790,7 +805,7 @@ int slot_kernels(const HostJob &j, Slot &s, size_t n)
     else if (j.do_comp)
         rc = dev_compress(j.comp_alg, (const uint8_t *)s.src.p, j.bb, j.bb, n, (uint8_t *)s.dst.p, j.d_stride, (uint32_t *)s.sizes.p, s.stream);
     else
-        rc = dev_hash(j.hash_alg, (const uint8_t *)s.src.p, j.bb, j.bb, n, (uint8_t *)s.dig.p, s.stream, false, true);
+        rc = dev_hash(j.hash_alg, (const uint8_t *)s.src.p, j.bb, j.bb, n, (uint8_t *)s.dig.p, s.stream, true);
     if (rc != CW_OK || !j.do_comp) return rc;
     return launched(cw::pack_launch((const uint8_t *)s.dst.p, j.d_stride, (const uint32_t *)s.sizes.p, n, (uint8_t *)s.pack.p, (uint64_t *)s.offs.p, s.stream),
                     "pack launch");

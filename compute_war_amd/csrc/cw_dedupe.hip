@@ -458,7 +458,7 @@ int cw_dev_hash_dedupe_compress(cw_dedupe_t *x, int comp_alg, const void *d_src,
     const uint8_t *src = (const uint8_t *)d_src;
     return dedupe_on_stream(x, s, [&]() -> int { // (the lock is held to the end: the gather buffer is the index's)
         int rc = dedupe_admit(x, nblocks);
-        if (rc == CW_OK) rc = dev_hash(x->hash_alg, src, block_bytes, src_stride, nblocks, (uint8_t *)d_digests, s, false, true);
+        if (rc == CW_OK) rc = dev_hash(x->hash_alg, src, block_bytes, src_stride, nblocks, (uint8_t *)d_digests, s, true);
         if (rc == CW_OK) rc = dedupe_enqueue(x, (const uint64_t *)d_digests, (uint32_t)nblocks, base, nullptr, d_ref, d_new_idx, x->t.ctrl + 2, s);
         if (rc != CW_OK) return rc;
         HIP_TRY(hipMemcpyAsync(x->h_ctrl, x->t.ctrl + 1, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));

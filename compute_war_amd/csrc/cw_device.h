@@ -55,22 +55,16 @@ struct SkeinIV { uint64_t w[8]; };
 void note_kernels(int kind, const char *names);
 // host: chaining value after the configuration block (Skein_*_Init)
 void skein_compute_iv(int state_words, unsigned hash_bits, SkeinIV *iv, uint64_t tree_info = 0);
-// sliced Skein for the fused call: the steps of every block in 8 launches (see skein_kernels.hip)
-bool skein_sliced_applies(int state_words, const uint8_t *src, size_t block_bytes, size_t src_stride, size_t nblocks,
-                          const uint8_t *digests);
-hipError_t skein_sliced_launch(int state_words, const uint8_t *src, size_t block_bytes, size_t src_stride, size_t nblocks, const SkeinIV &iv,
-                               uint8_t *digests, unsigned digest_bytes, hipStream_t stream);
 // tree hashing of every block (one wavefront per block, lane = leaf/node); digest = hash_bits / 8 bytes per block
 hipError_t skein_tree_launch(int state_words, const uint8_t *src, size_t block_bytes, size_t src_stride, size_t nblocks,
                              unsigned hash_bits, unsigned leaf, unsigned node, unsigned max_level, uint8_t *digests, hipStream_t stream);
 
-// device launches (async on `stream`); src_stride = distance between consecutive blocks in bytes
-// lean: the caller runs codec wavefronts beside the hash kernel and wants its low-register variant
-hipError_t skein512_launch(const uint8_t *src, size_t block_bytes, size_t src_stride, size_t nblocks, const SkeinIV &iv,
-                           uint8_t *digests, unsigned digest_bytes, hipStream_t stream, bool lean = false);
-hipError_t skein256_launch(const uint8_t *src, size_t block_bytes, size_t src_stride, size_t nblocks, const SkeinIV &iv,
-                           uint8_t *digests, unsigned digest_bytes, hipStream_t stream, bool lean = false);
-hipError_t sha256_launch(const uint8_t *src, size_t block_bytes, size_t src_stride, size_t nblocks, uint8_t *digests,
+// device launches (async on `stream`) of what the plan says (launch_plan.h: hash_plan); src_stride = distance between consecutive
+// blocks in bytes.  skein_launch: one kernel, or the sliced launches of a long message (see skein_kernels.hip)
+struct HashPlan;
+hipError_t skein_launch(const HashPlan &p, const uint8_t *src, size_t block_bytes, size_t src_stride, size_t nblocks, const SkeinIV &iv,
+                        uint8_t *digests, unsigned digest_bytes, hipStream_t stream);
+hipError_t sha256_launch(const HashPlan &p, const uint8_t *src, size_t block_bytes, size_t src_stride, size_t nblocks, uint8_t *digests,
                          hipStream_t stream);
 // after_scan (optional): called ONCE, right behind the launch of the scan and in front of everything else, if the call gets that far (the caller
 // checks): what it enqueues on other streams runs beside the scan; what it makes `stream` wait for, the parsers wait for

@@ -57,7 +57,7 @@ int check_count(const char *name, size_t n);      // <= 2^32 - 256: block and ch
 
 // ---- fixed-block launches ----
 // sliced: long Skein messages (>= 256 steps, >= 4096 blocks) are hashed in several launches of short-lived wavefronts
-int dev_hash(int alg, const uint8_t *d_src, size_t bb, size_t stride, size_t n, uint8_t *d_dig, hipStream_t s, bool lean = false, bool sliced = false);
+int dev_hash(int alg, const uint8_t *d_src, size_t bb, size_t stride, size_t n, uint8_t *d_dig, hipStream_t s, bool sliced = false);
 int dev_compress(int alg, const uint8_t *d_src, size_t bb, size_t stride, size_t n, uint8_t *d_dst, size_t dst_stride, uint32_t *d_sizes,
                  hipStream_t s, const cw::AfterScan *after_scan = nullptr);
 

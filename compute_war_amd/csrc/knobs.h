@@ -14,7 +14,7 @@ namespace cw {
 // the call stay where the call decides.
 enum class Lz4Mode : uint8_t { normal, scan, generic, stream, cut }; // CW_LZ4_MODE (other values: normal)
 enum class LzfMode : uint8_t { normal, cut, table };                // CW_LZF_MODE (other values: normal)
-enum class SkeinMode : uint8_t { by_lean, steps, lines };           // CW_SKEIN_MODE: unset / "steps" / any other value
+enum class SkeinMode : uint8_t { unset, steps, lines };             // CW_SKEIN_MODE: unset / "steps" / any other value
 enum class SidePrio : uint8_t { both, lanes, none };                // CW_SIDE_PRIO: unset or 2... / other / 0...: streams on the high-priority pool
 struct Knobs {
     // first character
@@ -26,7 +26,7 @@ struct Knobs {
     // strings, presence
     Lz4Mode lz4_mode = Lz4Mode::normal;
     LzfMode lzf_mode = LzfMode::normal;
-    SkeinMode skein_mode = SkeinMode::by_lean;
+    SkeinMode skein_mode = SkeinMode::unset;
     bool lz4_parse_fp = false; // CW_LZ4_PARSE == "fp"
     bool debug_lzf = false;    // set, to any value
     // > 0

@@ -1,5 +1,5 @@
-// launch_plan.cpp -- the launch policy of the LZ4 and LZF compressors (launch_plan.h): thresholds, their measurements, and the
-// description and dump of a plan.  Host code only.
+// launch_plan.cpp -- the launch policy of the LZ4 and LZF compressors and of the hashes (launch_plan.h): thresholds, their
+// measurements, and the description and dump of a plan.  Host code only.
 #include "launch_plan.h"
 
 #include <stdarg.h>
@@ -327,6 +327,44 @@ LzfPlan lzf_plan(const CodecCall &call, const Knobs &kn, bool lanes_allowed)
     return p;
 }
 
+// ---- hashes ---------------------------------------------------------------------------------------------------------------------------
+HashPlan hash_plan(const HashCall &call, const Knobs &kn)
+{
+    HashPlan p;
+    const int nw = p.state_words = call.state_words;
+    const size_t bb = nw ? (size_t)nw * 8 : 64;
+    p.grid = (uint32_t)((call.nblocks + kHashThreads - 1) / kHashThreads);
+    p.aligned = call.src_mis16 == 0;
+    // (an empty message is "ragged" too: its only step is padding, and the hot kernels' first load would read bytes that are not there)
+    p.ragged = call.block_bytes == 0 || call.block_bytes % bb != 0;
+    if (!nw) return p; // SHA-256: one kernel family, the member by (aligned, ragged)
+    // Long Skein messages go out in sliced launches (skein_kernels.hip has the measurements); CW_SKEIN_SLICED=0: never (profiling knob)
+    if (call.may_slice && kn.skein_sliced && call.nblocks >= kSlicedMinBlocks && !p.ragged && call.block_bytes / bb + 1 >= kSlicedMinSteps &&
+        p.aligned && call.digest_mis16 == 0) {
+        p.sliced = true;
+        const size_t total = p.total = call.block_bytes / bb + 1, spl = 128 / bb;
+        const size_t nsl = kn.skein_nslices ? (size_t)kn.skein_nslices : kSkeinSlices; // CW_SKEIN_NSLICES: profiling knob
+        size_t slice_steps = (total + nsl - 1) / nsl;
+        p.slice_steps = slice_steps = (slice_steps + spl - 1) / spl * spl; // whole 128-byte lines
+        p.state_bytes = call.nblocks * (size_t)nw * sizeof(uint64_t);
+        for (size_t b = 0; b < total; b += slice_steps) {
+            const size_t e = b + slice_steps < total ? b + slice_steps : total;
+            // 8 words only: for 4 words hipcc moves a quarter of the mask-free line request to the loop top
+            const bool interior = nw == 8 && (e - b) % spl == 0 && e + spl <= total - 1; // the slice and its prefetches stay inside the message
+            p.slices.push_back({b, e, interior});
+        }
+        return p;
+    }
+    // Two hot kernels for aligned, whole-step blocks: the line kernel (105 VGPRs, every cache line fetched once) and
+    // the step kernel (92 VGPRs, 64 bytes per step, ~40 % of the lines fetched twice).  Alone they are equally fast;
+    // beside codec wavefronts the step kernel keeps 4 instead of 3 hash wavefronts per SIMD, which helped at 512 Ki
+    // blocks (32.7 vs 36-42 ms) and made no difference at 1 Mi blocks (68 vs 69 ms), so no caller asks for it;
+    // CW_SKEIN_MODE=steps|lines overrides (profiling knob).
+    const bool steps = kn.skein_mode == SkeinMode::steps;
+    p.form = p.ragged ? SkeinForm::ragged : p.aligned && steps ? SkeinForm::steps : SkeinForm::lines;
+    return p;
+}
+
 // ---- description ----------------------------------------------------------------------------------------------------------------------
 namespace {
 // parts joined by " + "; a part that does not fit is cut at the buffer's end
@@ -389,6 +427,22 @@ Description describe(const LzfPlan &p)
     return d;
 }
 
+Description describe(const HashPlan &p)
+{
+    Description d = {""};
+    if (!p.state_words) {
+        add(d, "%s", sha256_kernel_name(p.aligned, p.ragged));
+    } else if (p.sliced) {
+        bool interior = false;
+        for (const SkeinSlice &s : p.slices) interior |= s.interior;
+        if (interior) add(d, "%s", skein_slice_kernel_name(p.state_words, true));
+        add(d, "%s", skein_slice_kernel_name(p.state_words, false)); // (a hash's last launch is never interior)
+    } else {
+        add(d, "%s", skein_kernel_name(p.state_words, p.form, p.aligned));
+    }
+    return d;
+}
+
 // ---- dump -----------------------------------------------------------------------------------------------------------------------------
 namespace {
 struct Dump {
@@ -435,6 +489,14 @@ std::string dump(const Lz4Plan &p)
     d.kv("cut_only", p.cut_only);
     d.kv("queue_bytes", p.queue_bytes); d.kv("queue_min_bytes", p.queue_min_bytes);
     return d.out;
+}
+
+std::string dump(const HashPlan &p)
+{
+    std::string out;
+    for (const SkeinSlice &s : p.slices)
+        out += "slice=" + std::to_string(s.begin) + ".." + std::to_string(s.end) + " interior=" + (s.interior ? "1" : "0") + "\n";
+    return out;
 }
 
 std::string dump(const LzfPlan &p)

@@ -1,4 +1,4 @@
-// launch_plan.h -- what an LZ4 / LZF compression call launches, decided apart from the code that enqueues it.
+// launch_plan.h -- what an LZ4 / LZF compression call and a hash call launch, decided apart from the code that enqueues it.
 //
 // lz4_plan / lzf_plan are pure: no HIP call, no allocation, no global, no environment -- the call's sizes and alignment facts and one
 // knobs snapshot in, every decision of the launch out: the kernel of every stage (a member of its family), grids, LDS bytes, streams,
@@ -13,6 +13,7 @@
 #include <stdlib.h>
 
 #include <string>
+#include <vector>
 
 #include "knobs.h"
 
@@ -148,12 +149,58 @@ struct LzfPlan {
 Lz4Plan lz4_plan(const CodecCall &call, const Knobs &kn, bool lanes_allowed = true);
 LzfPlan lzf_plan(const CodecCall &call, const Knobs &kn, bool lanes_allowed = true);
 
+// ---- hashes -------------------------------------------------------------------------------------------------------------------------
+// hash_plan is pure like the two above: which instantiation a cw_dev_hash-like call runs, whether a Skein call is cut into sliced
+// launches, and then every launch's steps.  skein_launch / sha256_launch (skein_kernels.hip, sha256_kernel.hip) enqueue what it says;
+// cw_hash_plan_describe prints it without a device.
+enum class SkeinForm : uint8_t { steps, ragged, lines }; // skein_blocks_kernel<NW, A, false> / <NW, A, true> / skein_lines_kernel<NW, A>
+// (defined beside the kernels' tables: skein_kernels.hip, sha256_kernel.hip)
+const char *skein_kernel_name(int state_words, SkeinForm form, bool aligned);
+const char *skein_slice_kernel_name(int state_words, bool interior);
+const char *sha256_kernel_name(bool aligned, bool ragged);
+
+constexpr size_t kHashThreads = 64;        // lanes (= blocks) per workgroup of every hash kernel (CW_SKEIN_THREADS)
+constexpr uint32_t kSkeinSlices = 8;       // launches of a sliced hash unless CW_SKEIN_NSLICES says otherwise
+constexpr size_t kSlicedMinBlocks = 4096;  // sliced launches: from this many blocks on ...
+constexpr size_t kSlicedMinSteps = 256;    // ... and this many steps (message steps + the output transform) per block
+
+struct HashCall {
+    int state_words;       // 8 = Skein-512, 4 = Skein-256, 0 = SHA-256
+    size_t block_bytes, nblocks;
+    unsigned src_mis16;    // (src | src_stride) & 15
+    unsigned digest_mis16; // digests & 15
+    bool may_slice;        // the caller lets long Skein messages go out in sliced launches (all but HashOffload)
+};
+inline HashCall hash_call(int state_words, const void *src, size_t block_bytes, size_t src_stride, size_t nblocks, const void *digests,
+                          bool may_slice)
+{
+    return {state_words, block_bytes, nblocks, (unsigned)((reinterpret_cast<uintptr_t>(src) | src_stride) & 15),
+            (unsigned)(reinterpret_cast<uintptr_t>(digests) & 15), may_slice};
+}
+// one launch of a sliced hash: steps [begin, end) of every block.  interior: the steps and the line prefetched behind them all lie
+// inside the message (skein_slice_kernel<8, true, true>)
+struct SkeinSlice { size_t begin, end; bool interior; };
+struct HashPlan {
+    int state_words = 0;
+    uint32_t grid = 0;                   // workgroups of kHashThreads lanes, the same for every launch of the call
+    bool aligned = false, ragged = false; // 16-byte aligned source; block_bytes is 0 or no multiple of the step
+    SkeinForm form = SkeinForm::lines;   // Skein, one launch
+    bool sliced = false;
+    size_t total = 0, slice_steps = 0;   // sliced: steps per block (message steps + output transform); steps per launch
+    size_t state_bytes = 0;              // sliced: the chaining values between the launches
+    std::vector<SkeinSlice> slices;      // sliced: the launches, in order
+};
+HashPlan hash_plan(const HashCall &call, const Knobs &kn);
+
 // the kernels of a plan as cw_profile_kernels reports them (at most 319 characters)
 struct Description { char text[320]; };
 Description describe(const Lz4Plan &p);
 Description describe(const LzfPlan &p);
+Description describe(const HashPlan &p);
 // one `key=value` line per field, in the order of the structs
 std::string dump(const Lz4Plan &p);
 std::string dump(const LzfPlan &p);
+// one `slice=begin..end interior=0|1` line per launch of a sliced hash, nothing otherwise
+std::string dump(const HashPlan &p);
 
 } // namespace cw

@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "cw_device.h"
+#include "launch_plan.h"
 
 namespace cw {
 
@@ -234,22 +235,23 @@ hipError_t sha256_chunks_launch(const uint8_t *src, size_t src_bytes, const uint
     return hipGetLastError();
 }
 
-hipError_t sha256_launch(const uint8_t *src, size_t block_bytes, size_t src_stride, size_t nblocks, uint8_t *digests,
+// ---- the kernel family of the launch (launch_plan.h): member, name as rocprofv3 prints it, kernel ----
+namespace {
+struct Sha256Row { bool aligned, ragged; const char *name; decltype(sha256_blocks_kernel<true, true>) *fn; };
+#define CW_ROW(A, R) {A, R, "cw::sha256_blocks_kernel<" #A ", " #R ">", sha256_blocks_kernel<A, R>}
+const Sha256Row kSha256Kernels[] = {CW_ROW(true, false), CW_ROW(true, true), CW_ROW(false, false), CW_ROW(false, true)};
+#undef CW_ROW
+const Sha256Row &sha256_row(bool aligned, bool ragged) { return kSha256Kernels[(aligned ? 0 : 2) + (ragged ? 1 : 0)]; }
+} // namespace
+const char *sha256_kernel_name(bool aligned, bool ragged) { return sha256_row(aligned, ragged).name; }
+
+hipError_t sha256_launch(const HashPlan &p, const uint8_t *src, size_t block_bytes, size_t src_stride, size_t nblocks, uint8_t *digests,
                          hipStream_t stream)
 {
     if (nblocks == 0) return hipSuccess;
-    const dim3 grid((unsigned)((nblocks + CW_SKEIN_THREADS - 1) / CW_SKEIN_THREADS)), block(CW_SKEIN_THREADS);
-    const bool aligned = ((reinterpret_cast<uintptr_t>(src) | src_stride) & 15) == 0;
-    // (an empty message is "ragged" too: its only chunk is the padding, and the hot path's first load would read 64 bytes that are not there)
-    const bool ragged = block_bytes == 0 || (block_bytes % 64) != 0;
-#define CW_LAUNCH(A, R) hipLaunchKernelGGL((sha256_blocks_kernel<A, R>), grid, block, 0, stream, src, block_bytes, src_stride, nblocks, digests)
-    if (aligned && !ragged) CW_LAUNCH(true, false);
-    else if (aligned) CW_LAUNCH(true, true);
-    else if (!ragged) CW_LAUNCH(false, false);
-    else CW_LAUNCH(false, true);
-    note_kernels(1, aligned ? (ragged ? "cw::sha256_blocks_kernel<true, true>" : "cw::sha256_blocks_kernel<true, false>")
-                            : (ragged ? "cw::sha256_blocks_kernel<false, true>" : "cw::sha256_blocks_kernel<false, false>"));
-#undef CW_LAUNCH
+    const Sha256Row &row = sha256_row(p.aligned, p.ragged);
+    hipLaunchKernelGGL(row.fn, dim3(p.grid), dim3(CW_SKEIN_THREADS), 0, stream, src, block_bytes, src_stride, nblocks, digests);
+    note_kernels(1, row.name);
     return hipGetLastError();
 }
 

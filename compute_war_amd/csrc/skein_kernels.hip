@@ -22,6 +22,7 @@
 #include <string.h>
 
 #include "cw_device.h"
+#include "launch_plan.h"
 #include "stream_scratch.h"
 
 namespace cw {
@@ -367,7 +368,7 @@ skein_lines_kernel(const uint8_t *__restrict__ src, size_t block_bytes, size_t s
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Sliced launches: the steps of a block are cut into kSkeinSlices launches of short-lived wavefronts
+// Sliced launches: the steps of a block are cut into kSkeinSlices (launch_plan.h) launches of short-lived wavefronts
 // that hand the chaining values on through a state array (kernel boundaries order and publish it: no flags, no
 // spinning -- a persistent-grid version with in-kernel dependencies lost to the oldest-first issue order).
 // Beside the codec this is 61.6 instead of 64.5 ms per Mi blocks of 64 KiB: the scan then finishes after 33 instead of
@@ -380,7 +381,6 @@ skein_lines_kernel(const uint8_t *__restrict__ src, size_t block_bytes, size_t s
 // per line and s_end + one line <= the message steps): every step is a plain message step and no prefetched line needs the "past the
 // message" mask or the clamped address, i.e. 32 v_cndmask_b32 + the compares per loop iteration less.  All but a hash's last slice are
 // launched so; the two instantiations never run in the same launch, so the instruction cache holds one loop body at a time as before.
-constexpr uint32_t kSkeinSlices = 8;
 
 #ifdef CW_CLOCK_STAMP
 __device__ unsigned long long g_clock_skein[4 * kClockSlots];
@@ -485,50 +485,40 @@ skein_slice_kernel(const uint8_t *__restrict__ src, size_t block_bytes, size_t s
 
 namespace {
 StreamScratch<DeviceBuf> slices; // per stream: the chaining values between the slices of one hash
-}
 
-bool skein_sliced_applies(int nw, const uint8_t *src, size_t block_bytes, size_t src_stride, size_t nblocks, const uint8_t *digests)
-{
-    const size_t bb = (size_t)nw * 8;
-    return nblocks >= 4096 && block_bytes % bb == 0 && block_bytes / bb + 1 >= 256 &&
-           ((reinterpret_cast<uintptr_t>(src) | src_stride | reinterpret_cast<uintptr_t>(digests)) & 15) == 0;
-}
+// ---- the kernel families of the launch (launch_plan.h): member, name as rocprofv3 prints it, kernel ------------------------------
+struct SkeinRow { int nw; SkeinForm form; bool aligned; const char *name; decltype(skein_lines_kernel<8, true>) *fn; };
+#define CW_ROW_BLOCKS(NW, A, R) {NW, R ? SkeinForm::ragged : SkeinForm::steps, A, "cw::skein_blocks_kernel<" #NW ", " #A ", " #R ">", skein_blocks_kernel<NW, A, R>}
+#define CW_ROW_LINES(NW, A) {NW, SkeinForm::lines, A, "cw::skein_lines_kernel<" #NW ", " #A ">", skein_lines_kernel<NW, A>}
+const SkeinRow kSkeinKernels[] = {
+    CW_ROW_BLOCKS(8, true, false), CW_ROW_BLOCKS(8, true, true), CW_ROW_BLOCKS(8, false, true), CW_ROW_LINES(8, true), CW_ROW_LINES(8, false),
+    CW_ROW_BLOCKS(4, true, false), CW_ROW_BLOCKS(4, true, true), CW_ROW_BLOCKS(4, false, true), CW_ROW_LINES(4, true), CW_ROW_LINES(4, false),
+};
+#undef CW_ROW_BLOCKS
+#undef CW_ROW_LINES
+struct SkeinSliceRow { int nw; bool interior; const char *name; decltype(skein_slice_kernel<8, true, true>) *fn; };
+const SkeinSliceRow kSkeinSliceKernels[] = {
+    {8, true, "cw::skein_slice_kernel<8, true, true>", skein_slice_kernel<8, true, true>},
+    {8, false, "cw::skein_slice_kernel<8, true, false>", skein_slice_kernel<8, true, false>},
+    {4, false, "cw::skein_slice_kernel<4, true, false>", skein_slice_kernel<4, true, false>},
+};
+static_assert(kHashThreads == CW_SKEIN_THREADS, "the plan's grid counts workgroups of CW_SKEIN_THREADS lanes");
 
-hipError_t skein_sliced_launch(int nw, const uint8_t *src, size_t block_bytes, size_t src_stride, size_t nblocks, const SkeinIV &iv,
-                               uint8_t *digests, unsigned digest_bytes, hipStream_t stream)
+const SkeinRow &skein_row(int nw, SkeinForm form, bool aligned)
 {
-    const size_t bb = (size_t)nw * 8, total = block_bytes / bb + 1, spl = 128 / bb;
-    const Knobs kn = knobs();
-    const size_t nsl = kn.skein_nslices ? (size_t)kn.skein_nslices : kSkeinSlices; // CW_SKEIN_NSLICES: profiling knob
-    size_t slice_steps = (total + nsl - 1) / nsl;
-    slice_steps = (slice_steps + spl - 1) / spl * spl;
-    auto &w = slices.at(stream);
-    LaunchLock sequence(w.launch); // the slices hand their chaining values on through the entry's buffer
-    const hipError_t err = w.reserve(nblocks * (size_t)nw * sizeof(uint64_t));
-    if (err != hipSuccess) return err;
-    uint64_t *state = w.as<uint64_t>();
-    const dim3 grid((unsigned)((nblocks + CW_SKEIN_THREADS - 1) / CW_SKEIN_THREADS)), block(CW_SKEIN_THREADS);
-    bool interior_used = false;
-    for (size_t b = 0; b < total; b += slice_steps) {
-        const size_t e = b + slice_steps < total ? b + slice_steps : total;
-        // 8 words only: for 4 words hipcc moves a quarter of the mask-free line request to the loop top
-        const bool interior = nw == 8 && (e - b) % spl == 0 && e + spl <= total - 1; // the slice and its prefetches stay inside the message
-        interior_used |= interior;
-        if (interior)
-            hipLaunchKernelGGL((skein_slice_kernel<8, true, true>), grid, block, 0, stream, src, block_bytes, src_stride, nblocks, iv, digests,
-                               digest_bytes, state, b, e);
-        else if (nw == 8)
-            hipLaunchKernelGGL((skein_slice_kernel<8, true, false>), grid, block, 0, stream, src, block_bytes, src_stride, nblocks, iv, digests,
-                               digest_bytes, state, b, e);
-        else
-            hipLaunchKernelGGL((skein_slice_kernel<4, true, false>), grid, block, 0, stream, src, block_bytes, src_stride, nblocks, iv, digests,
-                               digest_bytes, state, b, e);
-    }
-    note_kernels(1, interior_used ? "cw::skein_slice_kernel<8, true, true> + cw::skein_slice_kernel<8, true, false>"
-                    : nw == 8     ? "cw::skein_slice_kernel<8, true, false>"
-                                  : "cw::skein_slice_kernel<4, true, false>");
-    return hipGetLastError();
+    for (const SkeinRow &r : kSkeinKernels)
+        if (r.nw == nw && r.form == form && r.aligned == aligned) return r;
+    abort(); // a plan names members of the table only
 }
+const SkeinSliceRow &skein_slice_row(int nw, bool interior)
+{
+    for (const SkeinSliceRow &r : kSkeinSliceKernels)
+        if (r.nw == nw && r.interior == interior) return r;
+    abort();
+}
+} // namespace
+const char *skein_kernel_name(int nw, SkeinForm form, bool aligned) { return skein_row(nw, form, aligned).name; }
+const char *skein_slice_kernel_name(int nw, bool interior) { return skein_slice_row(nw, interior).name; }
 
 // ---------------------------------------------------------------------------------------------------
 // Tree hashing (semantics of the reference's Skein_TreeHash, skein_test.c:616-680, restated on the
@@ -644,48 +634,28 @@ hipError_t skein_tree_launch(int nw, const uint8_t *src, size_t block_bytes, siz
     return hipGetLastError();
 }
 
-template <int NW>
-static hipError_t launch_skein(const uint8_t *src, size_t block_bytes, size_t src_stride, size_t nblocks, const SkeinIV &iv,
-                               uint8_t *digests, unsigned digest_bytes, hipStream_t stream, bool lean)
+// enqueue what the plan says (launch_plan.cpp: every decision): one launch, or the sliced launches in order
+hipError_t skein_launch(const HashPlan &p, const uint8_t *src, size_t block_bytes, size_t src_stride, size_t nblocks, const SkeinIV &iv,
+                        uint8_t *digests, unsigned digest_bytes, hipStream_t stream)
 {
     if (nblocks == 0) return hipSuccess;
-    const dim3 grid((unsigned)((nblocks + CW_SKEIN_THREADS - 1) / CW_SKEIN_THREADS)), block(CW_SKEIN_THREADS);
-    const bool aligned = ((reinterpret_cast<uintptr_t>(src) | src_stride) & 15) == 0;
-    const bool ragged = block_bytes == 0 || (block_bytes % (NW * 8)) != 0;
-    // the name is noted by the macro that launches (cw_profile_kernels), spelled as rocprofv3 prints the instantiation
-#define CW_LAUNCH(A, R) do { hipLaunchKernelGGL((skein_blocks_kernel<NW, A, R>), grid, block, 0, stream, \
-                                                src, block_bytes, src_stride, nblocks, iv, digests, digest_bytes); \
-                             note_kernels(1, NW == 8 ? "cw::skein_blocks_kernel<8, " #A ", " #R ">" : "cw::skein_blocks_kernel<4, " #A ", " #R ">"); } while (0)
-#define CW_LAUNCH_LINES(A) do { hipLaunchKernelGGL((skein_lines_kernel<NW, A>), grid, block, 0, stream, \
-                                                   src, block_bytes, src_stride, nblocks, iv, digests, digest_bytes); \
-                                note_kernels(1, NW == 8 ? "cw::skein_lines_kernel<8, " #A ">" : "cw::skein_lines_kernel<4, " #A ">"); } while (0)
-    // Two hot kernels for aligned, whole-step blocks: the line kernel (105 VGPRs, every cache line fetched once) and
-    // the step kernel (92 VGPRs, 64 bytes per step, ~40 % of the lines fetched twice).  Alone they are equally fast;
-    // beside codec wavefronts the step kernel keeps 4 instead of 3 hash wavefronts per SIMD, which helped at 512 Ki
-    // blocks (32.7 vs 36-42 ms) and made no difference at 1 Mi blocks (68 vs 69 ms), so callers do not ask for it
-    // (`lean` stays false); CW_SKEIN_MODE=steps|lines overrides (profiling knob).
-    const SkeinMode mode = knobs().skein_mode;
-    const bool steps = mode == SkeinMode::by_lean ? lean : mode == SkeinMode::steps;
-    if (aligned && !ragged && steps) CW_LAUNCH(true, false);
-    else if (aligned && !ragged) CW_LAUNCH_LINES(true);
-    else if (aligned) CW_LAUNCH(true, true);
-    else if (!ragged) CW_LAUNCH_LINES(false);
-    else CW_LAUNCH(false, true);
-#undef CW_LAUNCH
-#undef CW_LAUNCH_LINES
+    const dim3 grid(p.grid), block(CW_SKEIN_THREADS);
+    if (!p.sliced) {
+        hipLaunchKernelGGL(skein_row(p.state_words, p.form, p.aligned).fn, grid, block, 0, stream, src, block_bytes, src_stride, nblocks, iv,
+                           digests, digest_bytes);
+        note_kernels(1, describe(p).text);
+        return hipGetLastError();
+    }
+    auto &w = slices.at(stream);
+    LaunchLock sequence(w.launch); // the slices hand their chaining values on through the entry's buffer
+    const hipError_t err = w.reserve(p.state_bytes);
+    if (err != hipSuccess) return err;
+    uint64_t *state = w.as<uint64_t>();
+    for (const SkeinSlice &sl : p.slices)
+        hipLaunchKernelGGL(skein_slice_row(p.state_words, sl.interior).fn, grid, block, 0, stream, src, block_bytes, src_stride, nblocks, iv,
+                           digests, digest_bytes, state, sl.begin, sl.end);
+    note_kernels(1, describe(p).text);
     return hipGetLastError();
-}
-
-hipError_t skein512_launch(const uint8_t *src, size_t block_bytes, size_t src_stride, size_t nblocks, const SkeinIV &iv,
-                           uint8_t *digests, unsigned digest_bytes, hipStream_t stream, bool lean)
-{
-    return launch_skein<8>(src, block_bytes, src_stride, nblocks, iv, digests, digest_bytes, stream, lean);
-}
-
-hipError_t skein256_launch(const uint8_t *src, size_t block_bytes, size_t src_stride, size_t nblocks, const SkeinIV &iv,
-                           uint8_t *digests, unsigned digest_bytes, hipStream_t stream, bool lean)
-{
-    return launch_skein<4>(src, block_bytes, src_stride, nblocks, iv, digests, digest_bytes, stream, lean);
 }
 
 // ---- variable-length chunks (cw_dev_hash_chunks): lane j hashes chunk perm[j] of any length at any byte -----------------

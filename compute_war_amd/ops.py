@@ -285,6 +285,16 @@ def plan_describe(alg, block_bytes: int, nblocks: int, src_misalign: int = 0, ds
     return buf.value.decode()
 
 
+def hash_plan_describe(alg, block_bytes: int, nblocks: int, src_misalign: int = 0, digest_misalign: int = 0, may_slice: bool = True) -> str:
+    """cw_hash_plan_describe: what dev_hash would launch under the knobs as they are now -- line 1 as profile_kernels()["hash"]
+    reports it afterwards, then one `slice=b..e interior=0|1` line per launch of a sliced Skein hash.  may_slice=False describes
+    HashOffload, which never slices.  Needs no device."""
+    cap = 1 << 16
+    buf = C.create_string_buffer(cap)
+    check(lib().cw_hash_plan_describe(_hash_id(alg), block_bytes, nblocks, src_misalign, digest_misalign, 1 if may_slice else 0, buf, cap))
+    return buf.value.decode()
+
+
 def profile_kernels() -> dict:
     """Names of the kernels the calling thread's latest codec / hash launch used (as rocprofv3 prints them)."""
     out = {}

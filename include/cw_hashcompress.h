@@ -550,6 +550,14 @@ void cw_tune_reset(void);
  * that is too small.                                                                                                     */
 int  cw_plan_describe(int comp_alg, size_t block_bytes, size_t nblocks, unsigned src_misalign, unsigned dst_misalign, char *buf,
                       size_t cap);
+/* The same for cw_dev_hash: line 1 = the hash kernels as cw_profile_kernels(1, ...) reports them after such a call; for a Skein call
+ * that goes out in sliced launches, one `slice=b..e interior=0|1` line per launch follows (steps [b, e) of every block, the output
+ * transform being a block's last step; interior = the all-message-steps kernel).  src_misalign stands for (src | src_stride) & 15,
+ * digest_misalign for d_digests & 15.  may_slice = 0 describes the one caller that never slices, HashOffload; every other call
+ * that hashes fixed-size blocks is described by may_slice = 1.  CW_ERR_BAD_ARG: what cw_dev_hash refuses (an unknown hash_alg,
+ * block_bytes > CW_MAX_BLOCK_BYTES), or a buffer that is too small.                                                        */
+int  cw_hash_plan_describe(int hash_alg, size_t block_bytes, size_t nblocks, unsigned src_misalign, unsigned digest_misalign,
+                           int may_slice, char *buf, size_t cap);
 
 /* ---- HashOffload (HashOffload.h:13-64): batch object + the offload thread that drains it -------
  * Lifecycle  hInit --Enqueue--> hQueued --Start--> hOffloaded --Complete--> hComplete.

@@ -2,7 +2,8 @@
 """Time-boxed randomized soak of the hash kernels against the oracle (test infrastructure; run by hand on a GPU box):
     python tests/soak_hash.py 120 [seed]
 Random block sizes (0 .. 65536, biased to the sizes with their own kernel variants), block counts on both sides of the kernel
-selection thresholds, all three algorithms, host-batch and device entry points (contiguous and strided), the fused call."""
+selection thresholds, all three algorithms, host-batch and device entry points (contiguous and strided), the fused call; every round
+draws CW_SKEIN_MODE and CW_SKEIN_NSLICES, and one round in sixteen a batch long and large enough for the sliced launches."""
 import os
 import sys
 import time
@@ -27,12 +28,22 @@ while time.time() - t0 < budget:
     n = int(rng.choice(SIZES)) if rng.random() < 0.7 else int(rng.integers(0, 65537))
     count = int(rng.choice([1, 2, 63, 64, 65, 200, 4096, 4100])) if n <= 4096 and rng.random() < 0.5 else int(rng.integers(1, max(2, min(300, (4 << 20) // max(n, 1)))))
     alg = ["skein512", "skein", "sha256mb"][rounds % 3]
+    if rng.random() < 1 / 16 and alg != "sha256mb":   # the sliced launches: >= 4096 blocks of >= 255 whole steps
+        n = (64 if alg == "skein512" else 32) * int(rng.choice([255, 256, 257, 258, 300]))
+        count = int(rng.integers(4096, 4111))
+    knobs = {}
+    if rng.random() < 0.5:
+        knobs["CW_SKEIN_MODE"] = str(rng.choice(["steps", "lines"]))
+    if rng.random() < 0.5:
+        knobs["CW_SKEIN_NSLICES"] = int(rng.choice([1, 2, 3, 7, 64, 127, 255, 100000]))
     data = rng.integers(0, 256, max(n * count, 1), dtype=np.uint8)
     check = sorted(set([0, count - 1] + [int(x) for x in rng.integers(0, count, min(count, 24))]))
     want = {i: REF[alg](data[i * n:(i + 1) * n].tobytes()) for i in check}
     mode = rounds % 4
     if os.environ.get("CW_SOAK_VERBOSE"):
-        print("round", rounds, alg, "n", n, "count", count, "mode", mode, flush=True)
+        print("round", rounds, alg, "n", n, "count", count, "mode", mode, knobs, flush=True)
+    for k, v in knobs.items():
+        cw.tune_set(k, v)
     if mode == 0 and n > 0:      # host batch entry point
         got = cw.hash_blocks(alg, data[:n * count], n)
     else:                        # device entry point, strided and misaligned by `shift`
@@ -53,10 +64,11 @@ while time.time() - t0 < budget:
             cw.dev_hash(alg, d.data_ptr() + shift, n, count, dig.data_ptr(), s, src_stride=stride)
         torch.cuda.synchronize()
         got = dig[:count * db].cpu().numpy().reshape(count, db)
+    cw.tune_reset()
     for i in check:
         if got[i].tobytes() != want[i]:
             bad += 1
-            print("MISMATCH", alg, "n", n, "block", i, "of", count, "mode", mode, "seed", seed0 + rounds, flush=True)
+            print("MISMATCH", alg, "n", n, "block", i, "of", count, "mode", mode, knobs, "seed", seed0 + rounds, flush=True)
     rounds += 1
     digests += len(check)
 print(f"soak: {rounds} rounds, {digests} digests checked against the oracle in {time.time() - t0:.0f} s, seed0 {seed0}: {bad} mismatches", flush=True)
