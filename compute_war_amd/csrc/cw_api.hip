@@ -96,23 +96,6 @@ const cw::SkeinIV &cw::host::skein_iv(int nw) { return nw == 8 ? g_iv512_512 : g
 
 // ---- per-(thread, device) context ---------------------------------------------------------------------
 namespace {
-struct PinnedBuf { // page-locked host staging: the only kind of host memory a copy engine reads or writes at bus speed
-    void *p = nullptr;
-    size_t cap = 0;
-    int reserve(size_t n)
-    {
-        if (n <= cap) return CW_OK;
-        if (p) (void)hipHostFree(p);
-        p = nullptr; cap = 0;
-        size_t want = n < (1u << 20) ? (1u << 20) : n;
-        hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-        if (e != hipSuccess) return fail(CW_ERR_NOMEM, "hipHostMalloc(%zu): %s", want, hipGetErrorString(e));
-        cap = want;
-        return CW_OK;
-    }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
-};
-
 // one chunk of the host batch path in flight: device buffers, pinned staging, the events of its three stages
 constexpr int kSlots = 3;
 struct Slot {
@@ -166,6 +149,7 @@ struct ThreadCtx {
     cw::SideStream side;
     DevBuf src, dst, dig, sizes;             // unpipelined helpers (decompress, tree hash)
     Slot slot[kSlots];
+    StoreCtx store;                          // cw_store_ingest / cw_store_restore
     int open(int dev)
     {
         if (stream) return CW_OK;
@@ -183,6 +167,7 @@ struct ThreadCtx {
         (void)hipSetDevice(device);
         src.release(); dst.release(); dig.release(); sizes.release();
         for (Slot &s : slot) s.release();
+        store.release();
         if (hint.ev) (void)hipEventDestroy(hint.ev);
         if (hint.h_queued) (void)hipHostFree(hint.h_queued);
         cw::release_stream_workspaces(side.stream); cw::release_stream_workspaces(stream);
@@ -215,6 +200,22 @@ int cw::host::ctx_stream(hipStream_t *s)
     const int rc = thread_ctx(&c);
     if (rc == CW_OK) *s = c->stream;
     return rc;
+}
+
+int cw::host::ctx_store(StoreCtx **c, hipStream_t *stream, hipStream_t *s_h2d, hipStream_t *s_d2h)
+{
+    ThreadCtx *t;
+    int rc = thread_ctx(&t);
+    if (rc != CW_OK || (rc = t->store.open()) != CW_OK) return rc;
+    *c = &t->store; *stream = t->stream; *s_h2d = t->s_h2d; *s_d2h = t->s_d2h;
+    return CW_OK;
+}
+
+bool cw::host::is_pinned(const void *p)
+{
+    hipPointerAttribute_t a;
+    if (!p || hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return a.type == hipMemoryTypeHost;
 }
 
 int cw::host::check_block(size_t block_bytes)
@@ -314,6 +315,7 @@ const KnobDef kKnobTable[] = {
     {"CW_HOST_CHUNK_MB", [](Knobs &k, const char *v) { positive(k.host_chunk_mb, v); }},
     {"CW_HOST_BIG_CHUNK_MB", [](Knobs &k, const char *v) { positive(k.host_big_chunk_mb, v); }},
     {"CW_CDC_SEGMENT", [](Knobs &k, const char *v) { positive(k.cdc_segment, v); }},
+    {"CW_STORE_PIECE", [](Knobs &k, const char *v) { positive(k.store_piece, v); }},
     {"CW_LZ_FORCE_REDO", [](Knobs &k, const char *v) { k.force_redo = atoi(v) > 0; }},
     {"CW_LZF_SHARE_GIVE_UP", [](Knobs &k, const char *v) { k.lzf_share_give_up = atoi(v) > 0; }},
     {"CW_LZ4_LANES", [](Knobs &k, const char *v) { k.lz4_lanes = atoi(v); }},
@@ -766,13 +768,6 @@ struct HostJob {
     size_t db, d_stride;
     uint64_t packed_off;
 };
-
-bool is_pinned(const void *p)
-{
-    hipPointerAttribute_t a;
-    if (!p || hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeHost;
-}
 
 size_t meta_off_total(size_t n) { return (n * 4 + 7) & ~(size_t)7; }
 size_t meta_off_dig(size_t n) { return meta_off_total(n) + 8; }

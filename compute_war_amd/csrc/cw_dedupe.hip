@@ -478,12 +478,16 @@ int cw_dev_hash_dedupe_compress(cw_dedupe_t *x, int comp_alg, const void *d_src,
     });
 }
 
-// cdc -> hash of every chunk -> one 8-byte copy back + a synchronise (the dedupe's admit check and launch need the count on the
-// host) -> dedupe -> the chunk codec over the new chunks, selected on the device: n_new never comes back to the host.
-int cw_dev_cdc_dedupe_compress(cw_dedupe_t *x, const cw_cdc_params *p, int comp_alg, const void *d_src, size_t nbytes, int final,
-                               uint64_t base, uint64_t *d_offsets, size_t max_offsets, uint64_t *d_nchunks, void *d_digests, uint64_t *d_ref,
-                               uint32_t *d_new_idx, uint64_t *d_n_new, void *d_dst, size_t dst_bytes, uint32_t *d_sizes, size_t *nchunks,
-                               void *stream)
+} // extern "C"
+
+// cdc -> hash of every chunk -> one small copy back + a synchronise (the dedupe's admit check and launch need the count on the
+// host) -> dedupe -> the chunk codec over the new chunks, selected on the device: n_new never comes back to the host.  With a hook
+// (cw_store_ingest's pieces) the copy also carries the bytes consumed, the store's cursor and the last commit's verdict, and the
+// hook's admission runs beside the index's, before anything is inserted.
+int cw::host::dev_cdc_dedupe_compress(cw_dedupe_t *x, const cw_cdc_params *p, int comp_alg, const void *d_src, size_t nbytes, int final_, uint64_t base,
+                                      uint64_t *d_offsets, size_t max_offsets, uint64_t *d_nchunks, void *d_digests, uint64_t *d_ref,
+                                      uint32_t *d_new_idx, uint64_t *d_n_new, void *d_dst, size_t dst_bytes, uint32_t *d_sizes, size_t *nchunks,
+                                      hipStream_t s, const PieceAdmit *hook)
 {
     if (nchunks) *nchunks = 0;
     cw::CdcParams cp;
@@ -498,16 +502,23 @@ int cw_dev_cdc_dedupe_compress(cw_dedupe_t *x, const cw_cdc_params *p, int comp_
     if ((rc = compress_chunks_args(comp_alg, d_src, nbytes, d_offsets, d_nchunks, max_chunks, d_new_idx, d_n_new, d_dst, dst_bytes, d_sizes)) != CW_OK)
         return rc;
     if ((rc = dedupe_args(x, 0, base)) != CW_OK) return rc; // (base + the chunk count: checked when the count is known, as cw_dev_dedupe would)
-    const hipStream_t s = (hipStream_t)stream;
     const uint8_t *src = (const uint8_t *)d_src;
     return dedupe_on_stream(x, s, [&]() -> int {
-        int rc = dev_cdc(cp, src, nbytes, final ? 1 : 0, d_offsets, max_offsets, d_nchunks, s);
+        int rc = dev_cdc(cp, src, nbytes, final_ ? 1 : 0, d_offsets, max_offsets, d_nchunks, s);
         if (rc == CW_OK) rc = dev_hash_chunks(x->hash_alg, src, nbytes, d_offsets, d_nchunks, max_chunks, (uint8_t *)d_digests, s);
         if (rc != CW_OK) return rc;
-        HIP_TRY(hipMemcpyAsync(x->h_ctrl, d_nchunks, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        uint64_t *h_counts = hook ? hook->h_counts : x->h_ctrl;
+        if (hook) {
+            rc = launched(cw::piece_counts_launch(d_offsets, d_nchunks, max_chunks, hook->d_used, hook->d_verdict, hook->d_counts, s), "piece counts launch");
+            if (rc != CW_OK) return rc;
+            HIP_TRY(hipMemcpyAsync(h_counts, hook->d_counts, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        } else {
+            HIP_TRY(hipMemcpyAsync(h_counts, d_nchunks, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        }
         HIP_TRY(hipStreamSynchronize(s));
-        const size_t k = (size_t)x->h_ctrl[0];
+        const size_t k = (size_t)h_counts[0];
         *nchunks = k;
+        if (hook && (rc = hook->admit(hook->self, k, h_counts)) != CW_OK) return rc;
         if (k == 0) { // (an empty input: cw_dev_dedupe would launch nothing)
             HIP_TRY(hipMemsetAsync(d_n_new, 0, sizeof(uint64_t), s));
             return CW_OK;
@@ -515,8 +526,17 @@ int cw_dev_cdc_dedupe_compress(cw_dedupe_t *x, const cw_cdc_params *p, int comp_
         if (base > UINT64_MAX - k) return fail(CW_ERR_BAD_ARG, "base + nchunks wraps");
         if ((rc = dedupe_admit(x, k)) != CW_OK) return rc; // offsets and digests are written; nothing inserted, nothing compressed
         rc = dedupe_enqueue(x, (const uint64_t *)d_digests, (uint32_t)k, base, nullptr, d_ref, d_new_idx, d_n_new, s);
-        return rc != CW_OK ? rc : dev_compress_chunks(comp_alg, src, nbytes, d_offsets, d_nchunks, max_chunks, d_new_idx, d_n_new, (uint8_t *)d_dst, d_sizes, s);
+        if (rc != CW_OK) return rc;
+        if (hook) *hook->inserted = true;
+        return dev_compress_chunks(comp_alg, src, nbytes, d_offsets, d_nchunks, max_chunks, d_new_idx, d_n_new, (uint8_t *)d_dst, d_sizes, s);
     });
 }
 
-} // extern "C"
+extern "C" int cw_dev_cdc_dedupe_compress(cw_dedupe_t *x, const cw_cdc_params *p, int comp_alg, const void *d_src, size_t nbytes, int final,
+                                          uint64_t base, uint64_t *d_offsets, size_t max_offsets, uint64_t *d_nchunks, void *d_digests,
+                                          uint64_t *d_ref, uint32_t *d_new_idx, uint64_t *d_n_new, void *d_dst, size_t dst_bytes, uint32_t *d_sizes,
+                                          size_t *nchunks, void *stream)
+{
+    return dev_cdc_dedupe_compress(x, p, comp_alg, d_src, nbytes, final, base, d_offsets, max_offsets, d_nchunks, d_digests, d_ref, d_new_idx, d_n_new,
+                                   d_dst, dst_bytes, d_sizes, nchunks, (hipStream_t)stream, nullptr);
+}

@@ -1,5 +1,6 @@
 // cw_host.h -- what the host files of libcwhc.so share (internal).  cw_api.hip defines errors, devices, contexts and the fixed-block
-// launches declared here; cw_chunks.hip defines the chunk helpers at the end.  cw_dedupe.hip and cw_offload.hip only use them.
+// launches declared here; cw_chunks.hip defines the chunk helpers, cw_dedupe.hip the fused call's internal form at the end.
+// cw_offload.hip and cw_ingest.hip only use them.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -50,6 +51,40 @@ struct DevBuf { // cw::DeviceBuf with a floor of 1 MiB and the library's error c
     void release() { (void)buf.release(); p = nullptr; }
 };
 
+struct PinnedBuf { // page-locked host staging: the only kind of host memory a copy engine reads or writes at bus speed
+    void *p = nullptr;
+    size_t cap = 0;
+    int reserve(size_t n)
+    {
+        if (n <= cap) return CW_OK;
+        if (p) (void)hipHostFree(p);
+        p = nullptr; cap = 0;
+        size_t want = n < (1u << 20) ? (1u << 20) : n;
+        hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
+        if (e != hipSuccess) return fail(CW_ERR_NOMEM, "hipHostMalloc(%zu): %s", want, hipGetErrorString(e));
+        cap = want;
+        return CW_OK;
+    }
+    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
+};
+bool is_pinned(const void *p); // page-locked host memory (cw_host_alloc / cw_host_register): the copy engines use it in place
+
+// What cw_store_ingest / cw_store_restore keep per calling thread and device (cw_ingest.hip); grows only, freed with the context.
+// Index 0 / 1: the two buffers the pieces (windows) alternate between.
+struct StoreCtx {
+    DevBuf src[2];                                   // ingest: a piece's carry + fresh bytes; restore: a window's bytes
+    DevBuf off, dig, ref, new_idx, sizes, slots;     // ingest: one piece's lists and codec slots
+    DevBuf rec_ref, rec_off, words;                  // ingest: the recipe as it grows; the counts, results and statistics
+    DevBuf meta[2], status[2];                       // restore: a window's count | refs | offsets, and its statuses
+    PinnedBuf stage[2], h_meta[2], h_status[2], h_words;
+    hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr}; // upload into buffer b done; buffer b free again
+    hipEvent_t ev_kernel[2] = {nullptr, nullptr};                              // restore: the window's kernel done
+    int open();
+    void release();
+};
+// the calling thread's context: its kernel stream, its two copy streams and its StoreCtx (opened)
+int ctx_store(StoreCtx **c, hipStream_t *stream, hipStream_t *s_h2d, hipStream_t *s_d2h);
+
 // ---- argument checks written once ----
 int check_block(size_t block_bytes);              // <= CW_MAX_BLOCK_BYTES
 int check_codec(int comp_alg);                    // LZ4 or LZF
@@ -72,6 +107,24 @@ int compress_chunks_args(int comp_alg, const void *d_src, size_t src_bytes, cons
                          const uint32_t *d_sel, const uint64_t *d_nsel, const void *d_dst, size_t dst_bytes, const uint32_t *d_sizes);
 int dev_compress_chunks(int comp_alg, const uint8_t *d_src, size_t src_bytes, const uint64_t *d_offsets, const uint64_t *d_nchunks, size_t max_chunks,
                         const uint32_t *d_sel, const uint64_t *d_nsel, uint8_t *d_dst, uint32_t *d_sizes, hipStream_t s);
+
+
+// ---- the fused chunk call's internal form (cw_dedupe.hip) ----
+// cw_store_ingest's part in a piece's one synchronise: the chunk count, the bytes consumed, *d_used and *d_verdict (the previous
+// piece's commit) come back together through d_counts -> h_counts (pinned), and admit(self, k, h_counts) runs beside the index's own
+// admission, before anything is inserted.  Whatever it returns other than CW_OK ends the call there.
+struct PieceAdmit {
+    const uint64_t *d_used, *d_verdict;
+    uint64_t *d_counts, *h_counts; // [4]
+    int (*admit)(void *self, size_t k, const uint64_t *h_counts);
+    void *self;
+    bool *inserted; // set once the piece's chunks are queued for the index: a failure behind that point is no refusal
+};
+// cw_dev_cdc_dedupe_compress is this with hook == nullptr
+int dev_cdc_dedupe_compress(cw_dedupe_t *x, const cw_cdc_params *p, int comp_alg, const void *d_src, size_t nbytes, int final_, uint64_t base,
+                            uint64_t *d_offsets, size_t max_offsets, uint64_t *d_nchunks, void *d_digests, uint64_t *d_ref, uint32_t *d_new_idx,
+                            uint64_t *d_n_new, void *d_dst, size_t dst_bytes, uint32_t *d_sizes, size_t *nchunks, hipStream_t s,
+                            const PieceAdmit *hook);
 
 } // namespace host
 } // namespace cw

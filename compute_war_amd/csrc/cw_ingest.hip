@@ -1,0 +1,341 @@
+// cw_ingest.hip -- the chunk store's host-buffer calls (semantics: the public header): cw_store_ingest streams a
+// host buffer of any size through the device in pieces, cw_store_restore streams a recipe back in windows, and cw_dev_ingest_commit is
+// the device step that assembles a recipe piece by piece (kernels: ingest_kernels.hip).
+//
+// Ingest, piece i in buffer b = i & 1 (F = max_size rounded up to 256, P = the fresh bytes per piece):
+//     s_h2d    wait ev_done[b] (piece i-2 has left the buffer) | fresh bytes -> buf[b] + F | record ev_up[b]
+//     stream   wait ev_up[b] | cdc, hash, counts | SYNCHRONISE, admit | dedupe, codec, append, commit
+//              | carry -> buf[b^1] + F - carry | record ev_done[b]
+// The upload of piece i+1 is queued before piece i's kernels, so it runs beside them; its address does not depend on any count.
+// Restore, window w in buffer b = w & 1:
+//     s_h2d    count | refs | rebased offsets -> meta[b] | record ev_up[b]
+//     stream   wait ev_up[b] | restore into src[b] | record ev_kernel[b]
+//     s_d2h    wait ev_kernel[b] | bytes and statuses -> host | record ev_done[b]
+// and the host takes window w-2 out of its buffer (waiting for ev_done[b]) before it queues window w into it.
+
+#include <string.h>
+
+#include <vector>
+
+#include "cw_host.h"
+
+using namespace cw::host;
+
+int cw::host::StoreCtx::open()
+{
+    if (ev_up[0]) return CW_OK;
+    for (int b = 0; b < 2; b++) {
+        HIP_TRY(hipEventCreateWithFlags(&ev_up[b], hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&ev_done[b], hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&ev_kernel[b], hipEventDisableTiming));
+    }
+    return CW_OK;
+}
+
+void cw::host::StoreCtx::release()
+{
+    for (int b = 0; b < 2; b++) {
+        src[b].release(); meta[b].release(); status[b].release();
+        stage[b].release(); h_meta[b].release(); h_status[b].release();
+        if (ev_up[b]) (void)hipEventDestroy(ev_up[b]);
+        if (ev_done[b]) (void)hipEventDestroy(ev_done[b]);
+        if (ev_kernel[b]) (void)hipEventDestroy(ev_kernel[b]);
+        ev_up[b] = ev_done[b] = ev_kernel[b] = nullptr;
+    }
+    off.release(); dig.release(); ref.release(); new_idx.release(); sizes.release(); slots.release();
+    rec_ref.release(); rec_off.release(); words.release(); h_words.release();
+}
+
+namespace {
+
+const size_t kDefaultPiece = (size_t)256 << 20; // the fresh bytes per piece (CW_STORE_PIECE): the piece of cw_cdc_hash
+const size_t kWindowPositions = (size_t)1 << 24; // positions per restore window at most (empty positions take no bytes)
+
+// u64 words of StoreCtx::words (device) and h_words (pinned)
+enum { W_NCHUNKS = 0, W_NNEW = 1, W_RESULT = 2, W_COUNTS = 4, W_VERDICT = 8, W_REC_COUNT = 9, W_STATS = 16, W_WORDS = 24 };
+
+int check_store(const cw_store *st)
+{
+    if (!st) return fail(CW_ERR_BAD_ARG, "NULL store");
+    if (!st->d_used || !st->d_dir || (st->store_bytes && !st->d_store)) return fail(CW_ERR_BAD_ARG, "NULL pointer in the store");
+    if (st->dir_entries == 0) return fail(CW_ERR_BAD_ARG, "dir_entries is 0");
+    if ((uintptr_t)st->d_dir & 15) return fail(CW_ERR_BAD_ARG, "d_dir is not 16-byte aligned");
+    if ((uintptr_t)st->d_used & 7) return fail(CW_ERR_BAD_ARG, "d_used not 8-byte aligned");
+    return CW_OK;
+}
+
+// whatever happens, nothing of the call is in flight when it returns: the caller's buffers and the staging are free again
+void drain(hipStream_t s, hipStream_t s_copy)
+{
+    (void)hipStreamSynchronize(s_copy);
+    (void)hipStreamSynchronize(s);
+}
+
+// the admission of one piece (PieceAdmit::admit): the last commit went through, the directory holds [base_k, base_k + k), and the
+// store holds the piece even if every chunk of it were new and kept raw
+struct Admission {
+    const cw_store *st;
+    uint64_t base_k;
+};
+int admit_piece(void *self, size_t k, const uint64_t *h)
+{
+    const Admission &a = *static_cast<const Admission *>(self);
+    const cw_store &st = *a.st;
+    const uint64_t consumed = h[1], used = h[2];
+    if (h[3]) return fail(CW_ERR_STATE, "cw_store_ingest: an admitted piece was not committed (verdict %llu)", (unsigned long long)h[3]);
+    if (k && (a.base_k < st.dir_base || a.base_k - st.dir_base > st.dir_entries || k > st.dir_entries - (a.base_k - st.dir_base)))
+        return fail(CW_ERR_NOMEM, "chunk store: values %llu .. +%zu leave the directory [%llu, +%zu)", (unsigned long long)a.base_k, k,
+                    (unsigned long long)st.dir_base, st.dir_entries);
+    if (used > st.store_bytes || consumed > st.store_bytes - used)
+        return fail(CW_ERR_NOMEM, "chunk store: a piece of %llu bytes may not fit behind %llu of %zu", (unsigned long long)consumed,
+                    (unsigned long long)used, st.store_bytes);
+    return CW_OK;
+}
+
+struct Ingest {
+    cw_dedupe_t *x; const cw_cdc_params *p; int comp_alg; const cw_store *st;
+    const uint8_t *src; size_t nbytes; uint64_t base;
+    StoreCtx *c; hipStream_t s, s_h2d;
+    size_t piece, front, cap, slots_bytes, rec_cap; // P, F, a piece's max_offsets, its slot bytes, the recipe's entries
+    bool pinned;
+    size_t k_total = 0, done = 0;                    // chunks and stream bytes of the pieces that went in
+
+    size_t pieces() const { return (nbytes + piece - 1) / piece; }
+
+    int upload(size_t i)
+    {
+        const int b = (int)(i & 1);
+        const size_t first = i * piece, take = nbytes - first < piece ? nbytes - first : piece;
+        const void *from = src + first;
+        if (!pinned) {
+            if (i >= 2) HIP_TRY(hipEventSynchronize(c->ev_up[b])); // the staging buffer's last copy has left it
+            memcpy(c->stage[b].p, from, take);
+            from = c->stage[b].p;
+        }
+        if (i >= 2) HIP_TRY(hipStreamWaitEvent(s_h2d, c->ev_done[b], 0));
+        HIP_TRY(hipMemcpyAsync((uint8_t *)c->src[b].p + front, from, take, hipMemcpyHostToDevice, s_h2d));
+        HIP_TRY(hipEventRecord(c->ev_up[b], s_h2d));
+        return CW_OK;
+    }
+
+    // CW_OK with *refused set: the piece did not go in and nothing changed
+    int run(bool *refused)
+    {
+        uint64_t *w = (uint64_t *)c->words.p, *h = (uint64_t *)c->h_words.p;
+        const size_t n = pieces();
+        size_t carry = 0;
+        int rc = upload(0);
+        for (size_t i = 0; rc == CW_OK && i < n; i++) {
+            const int b = (int)(i & 1);
+            if (i + 1 < n && (rc = upload(i + 1)) != CW_OK) return rc;
+            const size_t take = nbytes - i * piece < piece ? nbytes - i * piece : piece, len = carry + take;
+            uint8_t *d_piece = (uint8_t *)c->src[b].p + front - carry;
+            HIP_TRY(hipStreamWaitEvent(s, c->ev_up[b], 0));
+            Admission a{st, base + k_total};
+            bool inserted = false;
+            PieceAdmit hook{st->d_used, w + W_VERDICT, w + W_COUNTS, h + W_COUNTS, admit_piece, &a, &inserted};
+            size_t k = 0;
+            rc = dev_cdc_dedupe_compress(x, p, comp_alg, d_piece, len, i + 1 == n, a.base_k, (uint64_t *)c->off.p, cap, w + W_NCHUNKS, c->dig.p,
+                                         (uint64_t *)c->ref.p, (uint32_t *)c->new_idx.p, w + W_NNEW, c->slots.p, slots_bytes, (uint32_t *)c->sizes.p, &k,
+                                         s, &hook);
+            if (rc == CW_ERR_NOMEM && !inserted) { *refused = true; return CW_OK; }
+            if (rc == CW_ERR_NOMEM) return fail(CW_ERR_STATE, "cw_store_ingest: device memory ran out behind an admitted piece");
+            if (rc != CW_OK) return rc;
+            rc = cw_dev_store_chunks(comp_alg, d_piece, len, (uint64_t *)c->off.p, w + W_NCHUNKS, cap - 1, (uint32_t *)c->new_idx.p, w + W_NNEW,
+                                     c->slots.p, (uint32_t *)c->sizes.p, a.base_k, st->d_store, st->store_bytes, st->d_used, st->d_dir, st->dir_base,
+                                     st->dir_entries, w + W_RESULT, s);
+            if (rc == CW_OK)
+                rc = cw_dev_ingest_commit((uint64_t *)c->ref.p, (uint64_t *)c->off.p, w + W_NCHUNKS, cap - 1, w + W_NNEW, w + W_RESULT, done,
+                                          (uint64_t *)c->rec_ref.p, (uint64_t *)c->rec_off.p, w + W_REC_COUNT, rec_cap, w + W_STATS, w + W_VERDICT, s);
+            if (rc != CW_OK) return rc == CW_ERR_NOMEM ? fail(CW_ERR_STATE, "cw_store_ingest: no scratch behind an admitted piece") : rc;
+            const size_t consumed = (size_t)h[W_COUNTS + 1];
+            if (i + 1 < n) { // the bytes behind the last cut (< max_size) go in front of the next piece's fresh bytes
+                carry = len - consumed;
+                if (carry > front) return fail(CW_ERR_STATE, "cw_store_ingest: a carry of %zu bytes", carry);
+                if (carry) HIP_TRY(hipMemcpyAsync((uint8_t *)c->src[b ^ 1].p + front - carry, d_piece + consumed, carry, hipMemcpyDeviceToDevice, s));
+            }
+            HIP_TRY(hipEventRecord(c->ev_done[b], s));
+            k_total += k;
+            done += consumed;
+        }
+        return rc;
+    }
+};
+
+} // namespace
+
+extern "C" {
+
+int cw_dev_ingest_commit(const uint64_t *d_ref, const uint64_t *d_offsets, const uint64_t *d_nchunks, size_t max_chunks, const uint64_t *d_n_new,
+                         const uint64_t *d_store_result, uint64_t stream_off, uint64_t *d_rec_ref, uint64_t *d_rec_off, uint64_t *d_rec_count,
+                         size_t rec_cap, uint64_t *d_stats, uint64_t *d_verdict, void *stream)
+{
+    int rc = check_count("max_chunks", max_chunks);
+    if (rc != CW_OK) return rc;
+    if (!d_ref || !d_offsets || !d_nchunks || !d_n_new || !d_rec_ref || !d_rec_off || !d_rec_count || !d_verdict)
+        return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    if (((uintptr_t)d_ref | (uintptr_t)d_offsets | (uintptr_t)d_nchunks | (uintptr_t)d_n_new | (uintptr_t)d_store_result | (uintptr_t)d_rec_ref |
+         (uintptr_t)d_rec_off | (uintptr_t)d_rec_count | (uintptr_t)d_stats | (uintptr_t)d_verdict) & 7)
+        return fail(CW_ERR_BAD_ARG, "a pointer is not 8-byte aligned");
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    return launched(cw::ingest_commit_launch(d_ref, d_offsets, d_nchunks, max_chunks, d_n_new, d_store_result, stream_off, d_rec_ref, d_rec_off,
+                                             d_rec_count, rec_cap, d_stats, d_verdict, (hipStream_t)stream),
+                    "ingest commit launch");
+}
+
+int cw_store_ingest(cw_dedupe_t *x, const cw_cdc_params *p, int comp_alg, const cw_store *st, const void *src, size_t nbytes, uint64_t base,
+                    uint64_t *refs, uint64_t *offsets, size_t max_offsets, size_t *nchunks, size_t *consumed, cw_ingest_stats *stats)
+{
+    if (nchunks) *nchunks = 0;
+    if (consumed) *consumed = 0;
+    if (stats) memset(stats, 0, sizeof *stats);
+    cw::CdcParams cp;
+    int rc = cdc_params(p, &cp);
+    if (rc != CW_OK || (rc = check_codec(comp_alg)) != CW_OK) return rc;
+    if (!x || !refs || !offsets || !nchunks || !consumed || (nbytes && !src)) return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    if (cp.max_size > CW_MAX_BLOCK_BYTES) return fail(CW_ERR_BAD_ARG, "max_size %u > %u: such a chunk cannot be stored", cp.max_size, CW_MAX_BLOCK_BYTES);
+    if (max_offsets < nbytes / cp.min_size + 2)
+        return fail(CW_ERR_BAD_ARG, "max_offsets %zu < nbytes / min_size + 2 = %zu", max_offsets, nbytes / cp.min_size + 2);
+    if ((rc = check_store(st)) != CW_OK) return rc;
+    if (base > UINT64_MAX - (nbytes / cp.min_size + 1)) return fail(CW_ERR_BAD_ARG, "base + nbytes / min_size + 1 wraps");
+    Ingest g{x, p, comp_alg, st, (const uint8_t *)src, nbytes, base};
+    hipStream_t s_d2h;
+    if ((rc = ctx_store(&g.c, &g.s, &g.s_h2d, &s_d2h)) != CW_OK) return rc;
+    offsets[0] = 0;
+    if (nbytes == 0) return CW_OK;
+
+    const long knob = cw::knobs().store_piece;
+    size_t piece = knob ? (size_t)knob : kDefaultPiece;
+    if (piece < cp.max_size) piece = cp.max_size;
+    if (piece > nbytes) piece = nbytes > cp.max_size ? nbytes : cp.max_size; // one piece: no more than it needs
+    g.piece = piece;
+    g.front = ((size_t)cp.max_size + 255) & ~(size_t)255;
+    g.cap = (cp.max_size + piece) / cp.min_size + 2;
+    g.slots_bytes = cw_chunk_slots_bytes(comp_alg, cp.max_size + piece, g.cap - 1);
+    g.rec_cap = nbytes / cp.min_size + 2;
+    g.pinned = is_pinned(src);
+    StoreCtx &c = *g.c;
+    const size_t two = g.pieces() > 1 ? 2 : 1;
+    for (size_t b = 0; b < two; b++) {
+        if ((rc = c.src[b].reserve(g.front + piece + 16)) != CW_OK) return rc; // (+16: the scan loads whole granules)
+        if (!g.pinned && (rc = c.stage[b].reserve(piece)) != CW_OK) return rc;
+    }
+    if ((rc = c.off.reserve(g.cap * 8)) != CW_OK || (rc = c.dig.reserve(g.cap * 64)) != CW_OK || (rc = c.ref.reserve(g.cap * 8)) != CW_OK ||
+        (rc = c.new_idx.reserve(g.cap * 4)) != CW_OK || (rc = c.sizes.reserve(g.cap * 4)) != CW_OK || (rc = c.slots.reserve(g.slots_bytes)) != CW_OK ||
+        (rc = c.rec_ref.reserve(g.rec_cap * 8)) != CW_OK || (rc = c.rec_off.reserve(g.rec_cap * 8)) != CW_OK ||
+        (rc = c.words.reserve(W_WORDS * 8)) != CW_OK || (rc = c.h_words.reserve(W_WORDS * 8)) != CW_OK)
+        return rc;
+    HIP_TRY(hipMemsetAsync(c.words.p, 0, W_WORDS * 8, g.s));
+    HIP_TRY(hipMemsetAsync(c.rec_off.p, 0, 8, g.s));
+
+    bool refused = false;
+    rc = g.run(&refused);
+    uint64_t *h = (uint64_t *)c.h_words.p;
+    if (rc == CW_OK) {
+        const hipError_t e = hipMemcpyAsync(h + W_VERDICT, (uint64_t *)c.words.p + W_VERDICT, (W_WORDS - W_VERDICT) * 8, hipMemcpyDeviceToHost, g.s);
+        rc = launched(e, "cw_store_ingest: the counts");
+    }
+    drain(g.s, g.s_h2d);
+    if (rc != CW_OK) return rc;
+    const size_t k = (size_t)h[W_REC_COUNT];
+    if (h[W_VERDICT] || k != g.k_total || k + 1 > max_offsets)
+        return fail(CW_ERR_STATE, "cw_store_ingest: an admitted piece was not committed (verdict %llu, %zu of %zu chunks)", (unsigned long long)h[W_VERDICT],
+                    k, g.k_total);
+    if (k) HIP_TRY(hipMemcpy(refs, c.rec_ref.p, k * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(offsets, c.rec_off.p, (k + 1) * 8, hipMemcpyDeviceToHost));
+    *nchunks = k;
+    *consumed = (size_t)offsets[k];
+    if (stats) memcpy(stats, h + W_STATS, 5 * sizeof(uint64_t));
+    if (refused) return CW_ERR_NOMEM; // (the message is the admission's)
+    return *consumed == nbytes ? CW_OK : fail(CW_ERR_STATE, "cw_store_ingest: %zu of %zu bytes went in", *consumed, nbytes);
+}
+
+int cw_store_restore(int comp_alg, const cw_store *st, const uint64_t *refs, const uint64_t *offsets, size_t nchunks, void *dst, size_t dst_bytes,
+                     uint32_t *status, size_t *n_bad)
+{
+    if (n_bad) *n_bad = 0;
+    int rc = check_codec(comp_alg);
+    if (rc != CW_OK || (rc = check_store(st)) != CW_OK) return rc;
+    if (!offsets || !n_bad || (nchunks && !refs)) return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    // the windows: whole positions whose raw bytes fit a piece
+    const long knob = cw::knobs().store_piece;
+    size_t piece = knob ? (size_t)knob : kDefaultPiece;
+    if (piece < CW_MAX_BLOCK_BYTES) piece = CW_MAX_BLOCK_BYTES;
+    std::vector<size_t> first; // first position of every window, and the end
+    size_t in_window = 0, most = 0, widest = 0;
+    for (size_t j = 0; j < nchunks; j++) {
+        if (offsets[j + 1] < offsets[j]) return fail(CW_ERR_BAD_ARG, "offsets decrease at position %zu", j);
+        const uint64_t l = offsets[j + 1] - offsets[j];
+        if (l > CW_MAX_BLOCK_BYTES) return fail(CW_ERR_BAD_ARG, "position %zu is %llu bytes long (> %u)", j, (unsigned long long)l, CW_MAX_BLOCK_BYTES);
+        if (first.empty() || in_window + l > piece || j - first.back() == kWindowPositions) {
+            first.push_back(j);
+            in_window = 0;
+        }
+        in_window += (size_t)l;
+        if (in_window > widest) widest = in_window;
+        if (j + 1 - first.back() > most) most = j + 1 - first.back();
+    }
+    first.push_back(nchunks);
+    const uint64_t total = nchunks ? offsets[nchunks] - offsets[0] : 0;
+    if (dst_bytes < total) return fail(CW_ERR_BAD_ARG, "dst_bytes %zu < the stream's %llu bytes", dst_bytes, (unsigned long long)total);
+    if (total && !dst) return fail(CW_ERR_BAD_ARG, "NULL dst");
+    StoreCtx *cp;
+    hipStream_t s, s_h2d, s_d2h;
+    if ((rc = ctx_store(&cp, &s, &s_h2d, &s_d2h)) != CW_OK) return rc;
+    if (nchunks == 0) return CW_OK;
+    StoreCtx &c = *cp;
+    const size_t windows = first.size() - 1, meta_bytes = 8 + most * 8 + (most + 1) * 8;
+    const bool pinned = total == 0 || is_pinned(dst);
+    for (size_t b = 0; b < (windows > 1 ? 2u : 1u); b++) {
+        if ((rc = c.src[b].reserve(widest + 16)) != CW_OK || (rc = c.meta[b].reserve(meta_bytes)) != CW_OK || (rc = c.status[b].reserve(most * 4)) != CW_OK ||
+            (rc = c.h_meta[b].reserve(meta_bytes)) != CW_OK || (rc = c.h_status[b].reserve(most * 4)) != CW_OK)
+            return rc;
+        if (!pinned && (rc = c.stage[b].reserve(widest)) != CW_OK) return rc;
+    }
+    size_t bad = 0;
+    // window w has arrived: out of the staging, statuses to the caller
+    auto finish = [&](size_t w) -> int {
+        const int b = (int)(w & 1);
+        const size_t j0 = first[w], n = first[w + 1] - j0, bytes = (size_t)(offsets[first[w + 1]] - offsets[j0]);
+        HIP_TRY(hipEventSynchronize(c.ev_done[b]));
+        if (!pinned && bytes) memcpy((uint8_t *)dst + (offsets[j0] - offsets[0]), c.stage[b].p, bytes);
+        const uint32_t *got = (const uint32_t *)c.h_status[b].p;
+        for (size_t j = 0; j < n; j++) bad += got[j] != 0;
+        if (status) memcpy(status + j0, got, n * 4);
+        return CW_OK;
+    };
+    auto run = [&]() -> int {
+        for (size_t w = 0; w < windows; w++) {
+            const int b = (int)(w & 1);
+            int rc;
+            if (w >= 2 && (rc = finish(w - 2)) != CW_OK) return rc;
+            const size_t j0 = first[w], n = first[w + 1] - j0, bytes = (size_t)(offsets[first[w + 1]] - offsets[j0]);
+            uint64_t *m = (uint64_t *)c.h_meta[b].p, *d_m = (uint64_t *)c.meta[b].p;
+            m[0] = n;
+            memcpy(m + 1, refs + j0, n * 8);
+            for (size_t j = 0; j <= n; j++) m[1 + n + j] = offsets[j0 + j] - offsets[j0];
+            HIP_TRY(hipMemcpyAsync(d_m, m, 8 + n * 8 + (n + 1) * 8, hipMemcpyHostToDevice, s_h2d));
+            HIP_TRY(hipEventRecord(c.ev_up[b], s_h2d));
+            HIP_TRY(hipStreamWaitEvent(s, c.ev_up[b], 0));
+            rc = cw_dev_restore_chunks(comp_alg, st->d_store, st->store_bytes, st->d_dir, st->dir_base, st->dir_entries, d_m + 1, d_m + 1 + n, d_m, n,
+                                       c.src[b].p, bytes, (uint32_t *)c.status[b].p, s);
+            if (rc != CW_OK) return rc;
+            HIP_TRY(hipEventRecord(c.ev_kernel[b], s));
+            HIP_TRY(hipStreamWaitEvent(s_d2h, c.ev_kernel[b], 0));
+            void *to = pinned ? (void *)((uint8_t *)dst + (offsets[j0] - offsets[0])) : c.stage[b].p;
+            if (bytes) HIP_TRY(hipMemcpyAsync(to, c.src[b].p, bytes, hipMemcpyDeviceToHost, s_d2h));
+            HIP_TRY(hipMemcpyAsync(c.h_status[b].p, c.status[b].p, n * 4, hipMemcpyDeviceToHost, s_d2h));
+            HIP_TRY(hipEventRecord(c.ev_done[b], s_d2h));
+        }
+        for (size_t w = windows >= 2 ? windows - 2 : 0; w < windows; w++)
+            if (int rc = finish(w)) return rc;
+        return CW_OK;
+    };
+    rc = run();
+    drain(s, s_h2d);
+    (void)hipStreamSynchronize(s_d2h);
+    if (rc == CW_OK) *n_bad = bad;
+    return rc;
+}
+
+} // extern "C"

@@ -673,6 +673,54 @@ def dev_store_compact(d_store: int, store_bytes: int, d_dir: int, dir_entries: i
                                      d_new_used, d_new_dir, d_result, stream))
 
 
+class Store(C.Structure):
+    """cw_store: the caller-owned triple of the chunk store (bytes, cursor, directory) as one argument."""
+    _fields_ = [("d_store", C.c_void_p), ("store_bytes", C.c_size_t), ("d_used", C.c_void_p), ("d_dir", C.c_void_p),
+                ("dir_base", C.c_uint64), ("dir_entries", C.c_size_t)]
+
+
+class IngestStats(C.Structure):
+    """cw_ingest_stats: one store_ingest call's bytes, chunks, new chunks, stored bytes and pieces, over the pieces that went in."""
+    _fields_ = [("bytes", C.c_uint64), ("chunks", C.c_uint64), ("new_chunks", C.c_uint64), ("stored_bytes", C.c_uint64),
+                ("pieces", C.c_uint64), ("reserved", C.c_uint64 * 3)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k in ("bytes", "chunks", "new_chunks", "stored_bytes", "pieces")}
+
+
+def store_ingest(index: "DedupeIndex", params: "CdcParams", comp_alg, store: Store, src: int, nbytes: int, base: int):
+    """cw_store_ingest of the host bytes at address ``src``: (rc, refs, offsets, consumed, stats as a dict).  rc is 0, or -5 when a
+    piece was refused: refs / offsets / consumed then cover the pieces before it.  Any other failure raises."""
+    cap = params.max_offsets(nbytes)
+    refs, offs = np.zeros(cap, np.uint64), np.zeros(cap, np.uint64)
+    k, consumed, stats = C.c_size_t(0), C.c_size_t(0), IngestStats()
+    rc = lib().cw_store_ingest(index._x(), C.byref(params), _comp_id(comp_alg), C.byref(store), src or None, nbytes, base, refs.ctypes.data,
+                               offs.ctypes.data, cap, C.byref(k), C.byref(consumed), C.byref(stats))
+    if rc not in (0, -5):
+        check(rc)
+    k = int(k.value)
+    return rc, refs[:k].copy(), offs[:k + 1].copy(), int(consumed.value), stats.as_dict()
+
+
+def store_restore(comp_alg, store: Store, refs, offsets, dst: int, dst_bytes: int):
+    """cw_store_restore into the host memory at address ``dst``: the status of every position (u32 array)."""
+    refs, offsets = np.ascontiguousarray(refs, np.uint64), np.ascontiguousarray(offsets, np.uint64)
+    status, n_bad = np.zeros(max(len(refs), 1), np.uint32), C.c_size_t(0)
+    check(lib().cw_store_restore(_comp_id(comp_alg), C.byref(store), refs.ctypes.data if len(refs) else None, offsets.ctypes.data, len(refs),
+                                 dst or None, dst_bytes, status.ctypes.data, C.byref(n_bad)))
+    status = status[:len(refs)]
+    assert int(n_bad.value) == int((status != 0).sum())
+    return status
+
+
+def dev_ingest_commit(d_ref: int, d_offsets: int, d_nchunks: int, max_chunks: int, d_n_new: int, d_store_result: int, stream_off: int,
+                      d_rec_ref: int, d_rec_off: int, d_rec_count: int, rec_cap: int, d_stats: int, d_verdict: int, stream: int = 0) -> None:
+    """Append one piece's refs and cuts (shifted by stream_off) to a recipe that grows on the device, behind the piece's
+    dev_store_chunks; *d_verdict = 0, or 1 (the append was refused) / 2 (the recipe is full) with nothing changed.  Not synchronised."""
+    check(lib().cw_dev_ingest_commit(d_ref, d_offsets, d_nchunks, max_chunks, d_n_new, d_store_result or None, stream_off, d_rec_ref, d_rec_off,
+                                     d_rec_count, rec_cap, d_stats or None, d_verdict, stream))
+
+
 class Recipe:
     """What restores one ingested stream: refs[j] = the value of chunk j's first occurrence, offsets[0..k] = its cuts."""
 
@@ -692,7 +740,10 @@ class ChunkStore:
     device-resident store, ``restore`` turns a recipe back into bytes, ``read`` / ``read_ranges`` give byte ranges of it, ``compact`` forgets every stream but the ones named.
     The store is three torch buffers this object owns (bytes, cursor, directory: the caller-owned triple of cw_dev_store_chunks);
     chunk values count up from ``dir_base`` over the ingests.
-    One device call per ingest: the whole buffer has to fit on the device next to its slots."""
+    ``ingest`` is one device call: the whole buffer has to fit on the device next to its slots.  ``ingest_stream`` and
+    ``restore_stream`` take and give host buffers of any size, streamed through the device in pieces (cw_store_ingest /
+    cw_store_restore); ``last_stats`` holds the last streamed ingest's statistics."""
+    last_stats = None
 
     def __init__(self, index: DedupeIndex, comp_alg, params: CdcParams, store_bytes: int, dir_entries: int, dir_base: int = 0):
         import torch
@@ -743,6 +794,40 @@ class ChunkStore:
             raise err
         self.base += k
         return Recipe(ref.cpu().numpy().view(np.uint64)[:k], off.cpu().numpy().view(np.uint64)[:k + 1])
+
+    def _triple(self) -> Store:
+        return Store(self.d_store.data_ptr(), self.store_bytes, self.d_used.data_ptr(), self.d_dir.data_ptr(), self.dir_base, self.dir_entries)
+
+    def ingest_stream(self, data) -> Recipe:
+        """``ingest`` for host data of any size, piece by piece with uploads beside the kernels.  When the index, the directory or
+        the store cannot take a piece, raises CwError (-5) with ``e.consumed`` and ``e.nchunks`` (the bytes and chunks of the pieces that
+        went in; ``base`` has advanced by them) and ``e.recipe``, which restores ``data[:e.consumed]``: make room, then ingest
+        ``data[e.consumed:]``."""
+        import torch
+        a = _np_u8(data)
+        torch.cuda.synchronize()  # (the buffers were filled on torch's stream)
+        rc, refs, offs, consumed, stats = store_ingest(self.index, self.params, self.comp_alg, self._triple(), a.ctypes.data if a.size else 0,
+                                                       a.size, self.base)
+        self.base += len(refs)
+        self.last_stats = stats
+        recipe = Recipe(refs, offs)
+        if rc:
+            err = _lib.CwError(rc, lib().cw_last_error().decode(errors="replace"))
+            err.consumed, err.nchunks, err.recipe = consumed, len(refs), recipe
+            raise err
+        return recipe
+
+    def restore_stream(self, recipe: Recipe) -> bytes:
+        """``restore`` into host memory, window by window with downloads beside the kernels.  Raises as ``restore`` does."""
+        import torch
+        out = np.zeros(max(recipe.nbytes, 1), np.uint8)
+        torch.cuda.synchronize()
+        st = store_restore(self.comp_alg, self._triple(), recipe.refs, recipe.offsets, out.ctypes.data, recipe.nbytes)
+        if st.any():
+            j = int(np.nonzero(st)[0][0])
+            raise _lib.CwError(-2, f"chunk store: {int((st != 0).sum())} of {len(st)} positions not restored; position {j} (ref "
+                                   f"{int(recipe.refs[j])}) has status {int(st[j])}")
+        return out[:recipe.nbytes].tobytes()
 
     def restore(self, recipe: Recipe, verify: bool = False) -> bytes:
         """The bytes of an ingested stream.  Raises CwError (-2) unless every position restores.  verify: the restored chunks are

@@ -472,6 +472,75 @@ int cw_dev_read_ranges(int comp_alg, const void *d_store, size_t store_bytes, co
                        const uint64_t *d_nranges, size_t max_ranges,
                        void *d_dst, size_t dst_bytes, uint32_t *d_status, void *stream);
 
+/* ---- the chunk store from host buffers: pipelined ingest and restore of any size ------------------------
+ * The calls above take a buffer that already lies in device memory, next to its slots, in one call.  These take host memory of any
+ * size and stream it through the device.  The caller-owned triple of cw_dev_store_chunks as one argument:                         */
+typedef struct cw_store {
+    void *d_store; size_t store_bytes; uint64_t *d_used;
+    cw_chunk_loc *d_dir; uint64_t dir_base; size_t dir_entries;
+} cw_store;
+typedef struct cw_ingest_stats {   /* of one cw_store_ingest call, over the pieces that went in */
+    uint64_t bytes, chunks, new_chunks, stored_bytes, pieces, reserved[3];
+} cw_ingest_stats;
+/* Chunks, hashes, dedupes and compresses src[0..nbytes) and appends its new chunks to the store.  Synchronous; host pointers except
+ * inside *st.  The stream crosses the device in pieces: CW_STORE_PIECE fresh bytes each (default 256 MiB, raised to max_size; taken as
+ * given otherwise) in front of which lie the bytes behind the previous piece's last cut, fewer than max_size.  Every piece but the
+ * last is chunked with final = 0, the last with final = 1: cw_cdc_hash's contract.  Chunk i of the whole stream has value base + i.
+ *   result        Cuts, refs, the store bytes [0, *d_used), the directory and the index are byte for byte what ONE
+ *                 cw_dev_cdc_dedupe_compress + cw_dev_store_chunks over the whole stream leaves: the cuts by the final = 0 contract, the
+ *                 store because the append places positions in selection order without padding.  refs[*nchunks] and
+ *                 offsets[*nchunks + 1] are in stream coordinates; *consumed = offsets[*nchunks].
+ *   admission     No piece leaves the index ahead of the store.  A piece's one synchronise brings its chunk count k, the bytes it
+ *                 consumes and *d_used to the host, and before anything is inserted the piece is admitted: count + k <= max_entries
+ *                 (the index's own check); [base_k, base_k + k) inside [dir_base, dir_base + dir_entries), exactly; and, conservatively,
+ *                 *d_used + the bytes consumed <= store_bytes.  A chunk's stored form is never longer than the chunk, so an admitted
+ *                 append cannot be refused (if it is: CW_ERR_STATE, a bug).  The price of the conservatism: a nearly full store refuses
+ *                 a piece of duplicates that a one-call ingest would have taken.
+ *   refusal       CW_ERR_NOMEM: *nchunks and *consumed cover the pieces before the refused one; index, store and directory are exactly
+ *                 what ingesting src[0, *consumed) as a whole stream gives, and the recipe so far restores those bytes.  Make room
+ *                 (cw_dedupe_resize, or compaction into a larger store) and call again with src + *consumed, nbytes - *consumed,
+ *                 base + *nchunks: *consumed is a cut, so the resumed run's cuts are the uninterrupted run's.  Not all or nothing:
+ *                 consistent at every piece boundary, and resumable.
+ *   CW_ERR_BAD_ARG, before the device is touched: a NULL pointer (src may be NULL when nbytes is 0; stats may be NULL), what
+ *                 cw_dev_cdc and the codecs refuse, max_size > CW_MAX_BLOCK_BYTES (a longer chunk stores nothing and could never be
+ *                 restored), max_offsets < nbytes / min_size + 2, a d_dir that is not 16-byte or a d_used that is not 8-byte aligned,
+ *                 dir_entries == 0, base + nbytes / min_size + 1 wrapping.  nbytes == 0: CW_OK, 0 chunks, offsets[0] = 0.
+ * The upload of piece k + 1 runs beside the kernels of piece k.  All kernels go on the calling thread's one stream (the codecs' lane
+ * tables are per stream), uploads on its copy stream, into two buffers used alternately; fresh bytes always land at the same offset of
+ * a buffer (max_size rounded up to 256) and the carry is copied in front of them, so no upload waits for a count.  Page-locked src
+ * (cw_host_alloc / cw_host_register) is read in place, other memory goes through two pinned staging buffers with one memcpy.
+ * Scratch of the calling thread's context (grows only, freed with the context), for a piece of P bytes, max_size M, min_size m and
+ * c = (M + P) / m + 2: two source buffers of P + M (rounded) bytes, cw_chunk_slots_bytes(P + M, c - 1) of slots, c * (64 + 8 + 8 + 4 + 4)
+ * bytes of digests, offsets, refs, new-chunk list and sizes, and 16 bytes per nbytes / m + 2 for the recipe.  At the default piece
+ * and cw_cdc_default_params(8192) (m = 2048, M = 65536): 512.1 MiB + 261.1 MiB + 11.0 MiB = 784.2 MiB per calling thread, plus the
+ * recipe (8 MiB per GiB of input) and, for pageable src, 512 MiB of pinned staging.  An input shorter than a piece takes buffers of its own size. */
+int cw_store_ingest(cw_dedupe_t *x, const cw_cdc_params *p, int comp_alg, const cw_store *st,
+                    const void *src, size_t nbytes, uint64_t base,
+                    uint64_t *refs, uint64_t *offsets, size_t max_offsets,
+                    size_t *nchunks, size_t *consumed, cw_ingest_stats *stats /* may be NULL */);
+/* The device step behind a piece's cw_dev_store_chunks that assembles the recipe on the device, for callers that stream
+ * device-resident pieces themselves (cw_store_ingest uses it).  Every count is read on the device, nothing synchronises.  With
+ * n = min(*d_nchunks, max_chunks) and c = *d_rec_count: d_rec_ref[c + j] = d_ref[j] for j < n, d_rec_off[c + j] = stream_off +
+ * d_offsets[j] for j <= n, then *d_rec_count = c + n; d_stats (cw_ingest_stats' layout) accumulates bytes += d_offsets[n] -
+ * d_offsets[0], chunks += n, new_chunks += *d_n_new, stored_bytes += d_store_result[1], pieces += 1.  All or nothing, decided on the
+ * device: *d_verdict = 1 when d_store_result[0] != 0 (the append was refused), else 2 when c + n + 1 > rec_cap, else 0; when it is
+ * not 0, no recipe entry, no count and no statistic changes.  No load leaves d_ref[0..max_chunks) or d_offsets[0..max_chunks], no
+ * store d_rec_ref / d_rec_off [0..rec_cap).  CW_ERR_BAD_ARG before anything is launched: a NULL pointer (d_store_result and d_stats
+ * may be), a pointer that is not 8-byte aligned, max_chunks > 2^32 - 256.  No scratch.                                              */
+int cw_dev_ingest_commit(const uint64_t *d_ref, const uint64_t *d_offsets, const uint64_t *d_nchunks, size_t max_chunks,
+                         const uint64_t *d_n_new, const uint64_t *d_store_result /* may be NULL */, uint64_t stream_off,
+                         uint64_t *d_rec_ref, uint64_t *d_rec_off, uint64_t *d_rec_count, size_t rec_cap,
+                         uint64_t *d_stats /* [8], may be NULL */, uint64_t *d_verdict, void *stream);
+/* Rebuilds the stream of a recipe into host memory: stream byte x goes to dst[x - offsets[0]].  Synchronous.  The recipe is cut into
+ * windows of whole positions whose raw bytes fit a piece (CW_STORE_PIECE, raised to 65536); each window's offsets are rebased and
+ * uploaded, cw_dev_restore_chunks writes into one of two device buffers, and a window's download runs beside the next window's
+ * kernel.  status[j] (may be NULL) = cw_dev_restore_chunks' status of position j, *n_bad = how many are not 0; the call is CW_OK
+ * whatever they are, like cw_decompress_blocks, and the bytes of a position with a status other than 0 are unspecified inside its own
+ * extent.  A page-locked dst is written in place.  CW_ERR_BAD_ARG: a NULL pointer, what cw_dev_restore_chunks refuses,
+ * dst_bytes < offsets[nchunks] - offsets[0], a decreasing offsets array, a position longer than 65536.                              */
+int cw_store_restore(int comp_alg, const cw_store *st, const uint64_t *refs, const uint64_t *offsets, size_t nchunks,
+                     void *dst, size_t dst_bytes, uint32_t *status /* [nchunks], may be NULL */, size_t *n_bad);
+
 /* ---- the store forgets: mark, compact, and the index's retain ----------------------------------------
  * Mark and sweep over the same caller-owned buffers, plus one more the caller owns: d_live[dir_entries] (u32), a flag per
  * directory entry.  To drop streams: zero d_live and *d_n_outside, mark every recipe that stays, compact, retain.  Marking is
@@ -536,7 +605,7 @@ int  cw_profile_kernels(int kind, char *buf, size_t cap);
 
 /* ---- CW_TESTING: tuning and test knobs -----------------------------------------------------------------------------
  * Every knob the launch policy reads (thresholds such as CW_LZ4_LANES / CW_LZF_LANES / CW_LZ4_VTAB, CW_LANES_*, CW_LZF_ROUND,
- * CW_LZ_FORCE_REDO, CW_DECODE_LANES, CW_HOST_*CHUNK_MB, ...; README.md lists them) is read PER CALL: the value given
+ * CW_LZ_FORCE_REDO, CW_DECODE_LANES, CW_HOST_*CHUNK_MB, CW_STORE_PIECE, ...; README.md lists them) is read PER CALL: the value given
  * here wins, the environment variable of the same name is the default.  value = NULL removes an override; a name the
  * library does not read is refused with CW_ERR_BAD_ARG.  A launch sees the knobs as they were when it started, so setting
  * them while other threads compute is safe.  Not part of the reference's interface (it has no tunables beyond its CLI);
