@@ -15,12 +15,15 @@
 //    wavefront) follows the true chain only where a merge failed, which happens in runs where chains keep their phase.
 //    Every walk steps over runs without candidates by c += k*M and over runs where every position is a candidate by
 //    c += k*m, using the summaries.  count + pack_launch (index only) + write produce d_offsets and the chunk count.
+//    The resolve's code is cdc_resolve.h; its other instantiation, over many streams in one buffer (cw_dev_cdc_streams), and that
+//    form's own kernels are cdc_streams_kernels.hip.  The launch below serves both: the workspace and the scan are the same.
 // 4. chunk sort for cw_dev_hash_chunks: a counting sort of the chunks by Threefish / SHA-256 step count (longest first), so
 //    that the lanes of a wavefront hash chunks of about the same length.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cdc_resolve.h"
 #include "cw_device.h"
 #include "stream_scratch.h"
 
@@ -29,10 +32,6 @@ namespace cw {
 namespace {
 
 constexpr unsigned kScanThreads = 512;
-constexpr uint64_t kEnd = ~0ull;
-
-__device__ __forceinline__ uint64_t ctz64(uint64_t v) { return (uint64_t)__builtin_ctzll(v); }
-__host__ __device__ __forceinline__ uint64_t umin(uint64_t a, uint64_t b) { return a < b ? a : b; }
 
 // ---- 1. candidate scan ------------------------------------------------------------------------------------------------
 // HI: both masks have a zero low word, so only the high word of H is tested.  EDGE: the wavefront's 4 KiB touch the first
@@ -133,312 +132,7 @@ cdc_summary_kernel(const uint64_t *__restrict__ in, uint64_t nin, uint64_t *__re
     }
 }
 
-// ---- 3. resolve ---------------------------------------------------------------------------------------------------------
-struct Cdc { // few pointers: the resolve kernels keep the walk's state in scalar registers
-    const uint64_t *l0; // mask_s words, then mask_l words
-    const uint64_t *lv; // summaries: level 1 (n1 entries), 2 (n2), 3, four u64 per entry
-    uint64_t nwords, n1, n2, off, n, seg, nseg;
-    uint32_t m, a, M, cap; // cap = cuts one segment can hold
-    int final_;
-    uint64_t *segs; // per segment: list[cap], pre[cap], exit_spec, exit_walk, the notmerged bits, then cnt, start, precnt (u32)
-    __device__ uint64_t *list(uint64_t g) const { return segs + g * cap; }
-    __device__ uint64_t *pre(uint64_t g) const { return segs + (nseg + g) * cap; }
-    __device__ uint64_t *exit_spec() const { return segs + 2 * nseg * cap; }
-    __device__ uint64_t *exit_walk() const { return exit_spec() + nseg; }
-    __device__ uint64_t *notmerged() const { return exit_spec() + 2 * nseg; }
-    __device__ uint32_t *cnt() const { return reinterpret_cast<uint32_t *>(notmerged() + (nseg + 63) / 64); }
-    __device__ uint32_t *start() const { return cnt() + nseg; }
-    __device__ uint32_t *precnt() const { return cnt() + 2 * nseg; }
-};
-
-// map: 0 = mask_s candidates, 1 = mask_l candidates, 2 / 3 = the positions that are NOT a candidate of 0 / 1
-__device__ __forceinline__ uint64_t word0(const Cdc &c, int map, uint64_t w)
-{
-    const uint64_t v = c.l0[(map & 1) * c.nwords + w];
-    return map >= 2 ? ~v : v;
-}
-
-// first word index in [w, wlast] whose level-1 summary bit is set, else kEnd
-__device__ uint64_t next_word(const Cdc &c, int map, uint64_t w, uint64_t wlast)
-{
-    for (;;) {
-        if (w > wlast) return kEnd;
-        const uint64_t i1 = w >> 6;
-        const uint64_t b1 = c.lv[i1 * 4 + map] & (~0ull << (w & 63));
-        if (b1) { const uint64_t r = (i1 << 6) + ctz64(b1); return r <= wlast ? r : kEnd; }
-        const uint64_t j = i1 + 1; // level-1 entry
-        if ((j << 6) > wlast) return kEnd;
-        const uint64_t b2 = c.lv[(c.n1 + (j >> 6)) * 4 + map] & (~0ull << (j & 63));
-        if (b2) { w = (((j >> 6) << 6) + ctz64(b2)) << 6; continue; }
-        uint64_t k = (j >> 6) + 1; // level-2 entry
-        for (;;) {
-            if ((k << 12) > wlast) return kEnd;
-            const uint64_t b3 = c.lv[(c.n1 + c.n2 + (k >> 6)) * 4 + map] & (~0ull << (k & 63));
-            if (b3) { w = (((k >> 6) << 6) + ctz64(b3)) << 12; break; }
-            k = ((k >> 6) + 1) << 6;
-        }
-    }
-}
-
-// first real position p in [lo, hi) whose bit is set in `map`, else hi
-__device__ uint64_t first_bit(const Cdc &c, int map, uint64_t lo, uint64_t hi)
-{
-    if (lo >= hi) return hi;
-    const uint64_t q = lo + c.off, qhi = hi + c.off;
-    uint64_t w = q >> 6;
-    uint64_t b = word0(c, map, w) & (~0ull << (q & 63));
-    if (!b) {
-        w = next_word(c, map, w + 1, (qhi - 1) >> 6);
-        if (w == kEnd) return hi;
-        b = word0(c, map, w);
-    }
-    const uint64_t p = (w << 6) + ctz64(b);
-    return p < qhi ? p - c.off : hi;
-}
-
-__device__ __forceinline__ bool terminal(const Cdc &c, uint64_t cut) { return c.final_ ? cut == c.n : cut + c.M > c.n; }
-
-// From a non-terminal cut: the next cuts are cut + stride * i, i = 1..k.  k > 1 only across a run without candidates
-// (stride M) or a run where every position is a candidate (stride m), and then only while every start leaves M bytes;
-// k stops at the first cut >= bound.
-struct Step { uint64_t stride, k; };
-__device__ Step cdc_step(const Cdc &c, uint64_t cut, uint64_t bound)
-{
-    const uint64_t n = c.n, r = n - cut, m = c.m, M = c.M;
-    if (r <= m) return {r, 1};
-    const uint64_t kb = bound > cut ? (bound - cut + m - 1) / m : 1; // m-steps to reach the bound (an upper bound for M-steps too)
-    const bool room = cut + M <= n;
-    if (room && m == M) { // every chunk has size M
-        const uint64_t k = umin((n - cut) / M, umin((bound > cut ? (bound - cut + M - 1) / M : 1), kb));
-        return {M, k ? k : 1};
-    }
-    const uint64_t e = cut + umin(M, r), z = cut + umin(c.a, r);
-    const uint64_t lim = umin(n, (bound > cut ? bound : cut) + M);
-    // the searches run one after the other through ONE inlined first_bit (it is large): 0 = mask_s range, 1 = mask_l range,
-    // 2 / 3 = the next candidates of either kind past cut + M - 1, 4 = the next non-candidate
-    uint64_t x = e, q = lim;
-    int phase = 0, map = 0;
-    uint64_t lo = cut + m - 1, hi = z - 1;
-    for (;;) {
-        const uint64_t p = first_bit(c, map, lo, hi);
-        if (phase == 0) {
-            if (p < hi) x = p + 1;
-            else { phase = 1; map = 1; lo = z - 1; hi = e - 1; continue; }
-        } else if (phase == 1) {
-            x = p < hi ? p + 1 : e;
-        } else if (phase == 2) {
-            q = p; phase = 3; map = 1; continue;
-        } else if (phase == 3) {
-            q = umin(q, p); // no candidate in [cut + m - 1, q): how many M-steps see none
-            uint64_t k = (q + 1 - cut) / M;
-            k = umin(k, (n - cut) / M);
-            k = umin(k, bound > cut ? (bound - cut + M - 1) / M : 1);
-            return {M, k ? k : 1};
-        } else { // phase 4: every position in [cut + m - 1, p) is a candidate: how many m-steps in a row find one
-            uint64_t k = (p - cut) / m;
-            k = umin(k, (n - M - cut) / m + 1);
-            k = umin(k, kb);
-            return {m, k ? k : 1};
-        }
-        // x is the next cut
-        if (!room) return {x - cut, 1};
-        if (x == cut + M) { phase = 2; map = 0; lo = cut + M - 1; hi = lim; continue; }
-        if (x == cut + m) { phase = 4; map = m < c.a ? 2 : 3; lo = cut + m - 1; hi = lim; continue; }
-        return {x - cut, 1};
-    }
-}
-
-// spec: the chain of segment g from g * S (cuts in [gS, (g+1)S) into list, the first cut >= (g+1)S into exit_spec, kEnd if the
-// chain ends first)
-__global__ void __launch_bounds__(64)
-cdc_spec_kernel(Cdc c, uint64_t nseg)
-{
-    const uint64_t g = (uint64_t)blockIdx.x * 64 + threadIdx.x;
-    if (g >= nseg) return;
-    uint64_t *list = c.list(g);
-    const uint64_t bound = (g + 1) * c.seg;
-    uint64_t cut = g * c.seg;
-    uint32_t k = 0;
-    list[k++] = cut;
-    uint64_t ex = kEnd;
-    while (!terminal(c, cut)) {
-        const Step s = cdc_step(c, cut, bound);
-        uint64_t i = 1;
-        for (; i <= s.k; i++) {
-            const uint64_t nc = cut + s.stride * i;
-            if (nc >= bound) break;
-            list[k++] = nc;
-        }
-        if (i <= s.k) { ex = cut + s.stride * i; break; }
-        cut += s.stride * s.k;
-    }
-    c.cnt()[g] = k;
-    c.exit_spec()[g] = ex;
-}
-
-// Walks from `cut` (a true cut in segment g) until it lands on a cut of segment g's own chain (merged: start = its index) or
-// leaves the segment.  The cuts before the landing go to pre.  Returns true when merged; *ex = the exit of the walked chain.
-__device__ bool walk_segment(const Cdc &c, uint64_t g, uint64_t cut, uint32_t *pcount, uint64_t *ex)
-{
-    const uint64_t *list = c.list(g);
-    uint64_t *pre = c.pre(g);
-    const uint32_t cnt = c.cnt()[g];
-    const uint64_t bound = (g + 1) * c.seg;
-    uint32_t j = 0, P = 0;
-    for (;;) {
-        // cut is a true cut inside segment g
-        while (j < cnt && list[j] < cut) j++;
-        if (j < cnt && list[j] == cut) {
-            c.start()[g] = j; c.precnt()[g] = P; *pcount = P; *ex = c.exit_spec()[g];
-            return true;
-        }
-        pre[P++] = cut;
-        if (terminal(c, cut)) break;
-        const Step s = cdc_step(c, cut, bound);
-        uint64_t i = 1;
-        for (; i < s.k; i++) { // the progression's inner cuts: each may land on the chain too
-            const uint64_t nc = cut + s.stride * i;
-            while (j < cnt && list[j] < nc) j++;
-            if (j < cnt && list[j] == nc) break;
-            pre[P++] = nc;
-        }
-        cut += s.stride * i;
-        if (cut >= bound) { c.start()[g] = cnt; c.precnt()[g] = P; *pcount = P; *ex = cut; return false; }
-    }
-    c.start()[g] = cnt; c.precnt()[g] = P; *pcount = P; *ex = kEnd;
-    return false;
-}
-
-// merge: segment g walked from the spec exit of segment g - 1
-__global__ void __launch_bounds__(64)
-cdc_merge_kernel(Cdc c, uint64_t nseg)
-{
-    const uint64_t g = (uint64_t)blockIdx.x * 64 + threadIdx.x;
-    if (g >= nseg) return;
-    if (g == 0) { c.start()[0] = 0; c.precnt()[0] = 0; c.exit_walk()[0] = c.exit_spec()[0]; return; }
-    const uint64_t entry = c.exit_spec()[g - 1];
-    if (entry == kEnd) { c.start()[g] = c.cnt()[g]; c.precnt()[g] = 0; c.exit_walk()[g] = kEnd; return; }
-    uint32_t P;
-    uint64_t ex;
-    if (!walk_segment(c, g, entry, &P, &ex)) atomicOr(reinterpret_cast<unsigned long long *>(c.notmerged() + (g >> 6)), 1ull << (g & 63));
-    c.exit_walk()[g] = ex;
-}
-
-// the progression t + stride * i, 1 <= i < k: the index of its first cut in segment h (every later segment starts past t), and its
-// number of cuts in h
-__device__ __forceinline__ uint64_t prog_lo(const Cdc &c, uint64_t t, uint64_t stride, uint64_t h)
-{
-    const uint64_t s = h * c.seg;
-    return s <= t ? 1 : (s - t + stride - 1) / stride; // >= 1
-}
-__device__ __forceinline__ uint64_t prog_count(const Cdc &c, uint64_t t, uint64_t stride, uint64_t k, uint64_t h)
-{
-    const uint64_t lo = prog_lo(c, t, stride, h), hi = umin(k, prog_lo(c, t, stride, h + 1));
-    return hi > lo ? hi - lo : 0;
-}
-
-// fixup (one wavefront): follows the true chain wherever a segment's merge walk did not land on its own chain.  The walk is
-// not bounded by segments: across a run without candidates (or of all candidates) cdc_step returns the whole run as one
-// progression, whose cuts the lanes write into the lists of the segments it covers, so a run of any length costs one step
-// and a lane-parallel fill.  The segments past the end of the chain are emptied lane-parallel.
-__global__ void __launch_bounds__(64)
-cdc_fixup_kernel(Cdc params, uint64_t nseg)
-{
-    // The walk's parameters are read from LDS: there is no scalar LDS read, so they live in vector registers and the scalar
-    // file keeps the walk's control state (with the parameters in scalar registers the kernel needs more than it has).
-    __shared__ Cdc shared_params;
-    const unsigned lane = threadIdx.x;
-    if (lane == 0) shared_params = params;
-    __syncthreads();
-    const Cdc &c = shared_params;
-    const uint64_t nbits = (nseg + 63) / 64;
-    uint64_t g = 1;
-    for (;;) {
-        // the next segment >= g whose merge walk failed
-        uint64_t g0 = kEnd;
-        for (uint64_t w = g >> 6; w < nbits && g0 == kEnd; w += 64) {
-            const uint64_t i = w + lane;
-            uint64_t v = i < nbits ? c.notmerged()[i] : 0;
-            if (i == (g >> 6)) v &= ~0ull << (g & 63);
-            const uint64_t b = __ballot(v != 0);
-            if (b) {
-                const unsigned src = (unsigned)ctz64(b);
-                g0 = ((w + src) << 6) + ctz64(__shfl(v, src, 64));
-            }
-        }
-        if (g0 == kEnd || g0 + 1 >= nseg) return;
-        uint64_t t = c.exit_walk()[g0];
-        if (t == c.exit_spec()[g0]) { g = g0 + 1; continue; } // the next segment's merge walk started where the true chain enters
-        // walk the true chain from t until it lands on a segment's own chain; h = the segment of t, P = cuts already in its pre
-        uint64_t h = t == kEnd ? g0 : t / c.seg;
-        uint32_t P = 0, j = 0;
-        for (;;) {
-            if (t == kEnd) {
-                for (uint64_t e = h + 1 + lane; e < nseg; e += 64) { c.precnt()[e] = 0; c.start()[e] = c.cnt()[e]; }
-                return;
-            }
-            const uint64_t *list = c.list(h);
-            const uint32_t cnt = c.cnt()[h];
-            while (j < cnt && list[j] < t) j++;
-            if (j < cnt && list[j] == t) { // landed: from here segment h's own chain is the true one
-                if (lane == 0) { c.start()[h] = j; c.precnt()[h] = P; }
-                g = h + 1;
-                break;
-            }
-            if (lane == 0) c.pre(h)[P] = t;
-            P++;
-            if (terminal(c, t)) {
-                if (lane == 0) { c.start()[h] = cnt; c.precnt()[h] = P; }
-                t = kEnd;
-                continue;
-            }
-            const Step st = cdc_step(c, t, c.n);
-            const uint64_t nt = t + st.stride * st.k, hn = nt / c.seg;
-            if (st.k > 1) {
-                for (uint64_t i = 1 + lane; i < st.k; i += 64) {
-                    const uint64_t q = t + st.stride * i, hq = q / c.seg;
-                    c.pre(hq)[(hq == h ? P : 0) + (i - prog_lo(c, t, st.stride, hq))] = q;
-                }
-            }
-            if (hn == h) {
-                P += (uint32_t)(st.k - 1);
-            } else {
-                if (lane == 0) { c.start()[h] = cnt; c.precnt()[h] = P + (uint32_t)prog_count(c, t, st.stride, st.k, h); }
-                for (uint64_t e = h + 1 + lane; e < hn; e += 64) {
-                    c.start()[e] = c.cnt()[e];
-                    c.precnt()[e] = (uint32_t)prog_count(c, t, st.stride, st.k, e);
-                }
-                P = (uint32_t)prog_count(c, t, st.stride, st.k, hn);
-                j = 0;
-                h = hn;
-            }
-            t = nt;
-        }
-        if (g >= nseg) return;
-    }
-}
-
-__global__ void __launch_bounds__(256)
-cdc_count_kernel(Cdc c, uint64_t nseg, uint32_t *__restrict__ counts)
-{
-    const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (g < nseg) counts[g] = c.precnt()[g] + (c.cnt()[g] - c.start()[g]);
-}
-
-__global__ void __launch_bounds__(64)
-cdc_write_kernel(Cdc c, uint64_t nseg, const uint64_t *__restrict__ segoff, uint64_t *__restrict__ out, uint64_t max_out,
-                 uint64_t *__restrict__ nchunks)
-{
-    const uint64_t g = blockIdx.x;
-    const unsigned lane = threadIdx.x;
-    const uint64_t base = segoff[g];
-    const uint32_t P = c.precnt()[g], s = c.start()[g], k = c.cnt()[g];
-    const uint64_t *pre = c.pre(g), *list = c.list(g);
-    // the chain has at most nbytes / min_size + 2 cuts, which the host checked max_out against; the bound is kept anyway
-    for (uint32_t i = lane; i < P; i += 64) if (base + i < max_out) out[base + i] = pre[i];
-    for (uint32_t i = s + lane; i < k; i += 64) if (base + P + (i - s) < max_out) out[base + P + (i - s)] = list[i];
-    if (g == 0 && lane == 0) *nchunks = segoff[nseg] - 1;
-}
+// ---- 3. resolve: cdc_resolve.h (instantiated over Cdc by the launch below) ----------------------------------------------------
 
 // ---- 4. chunk sort by step count (longest first) ----------------------------------------------------------------------
 constexpr unsigned kBuckets = 4096;
@@ -517,34 +211,45 @@ size_t cdc_workspace_bytes(size_t nbytes, uint32_t min_size, uint64_t seg)
            up256(2 * nseg * cap * 8 + 2 * nseg * 8 + (nseg + 63) / 64 * 8 + 3 * nseg * 4) + up256(nseg * 4) + up256((nseg + 1) * 8);
 }
 
-hipError_t cdc_launch(const CdcParams &p, const uint8_t *src, size_t nbytes, int final_, uint64_t *offsets, size_t max_offsets,
-                      uint64_t *nchunks, uint64_t seg, hipStream_t stream)
+// the stream form's lists hold nstreams more cuts in all (each end lies in one segment), twice; eidx is u32[nseg + 1]
+size_t cdc_streams_workspace_bytes(size_t nbytes, size_t nstreams, uint32_t min_size, uint64_t seg)
 {
-    if (nbytes == 0) {
-        hipError_t e = hipMemsetAsync(offsets, 0, sizeof(uint64_t), stream);
-        return e != hipSuccess ? e : hipMemsetAsync(nchunks, 0, sizeof(uint64_t), stream);
-    }
+    const uint64_t nseg = nbytes / seg + 1;
+    return cdc_workspace_bytes(nbytes, min_size, seg) + up256(2 * nstreams * 8) + up256((nseg + 1) * 4);
+}
+
+namespace {
+// the launches of both forms: st == nullptr is cw_dev_cdc, else final_ is 1 and nbytes > 0
+hipError_t cdc_launch_any(const CdcParams &p, const uint8_t *src, size_t nbytes, int final_, uint64_t *offsets, size_t max_offsets,
+                          uint64_t *nchunks, uint64_t seg, const CdcStreams *st, hipStream_t stream)
+{
     const uint64_t off = reinterpret_cast<uintptr_t>(src) & 15;
     const uint8_t *base = src - off;
     const uint64_t nv = nbytes + off, nwords = (nv + 63) / 64, n1 = (nwords + 63) / 64, n2 = (n1 + 63) / 64, n3 = (n2 + 63) / 64;
     const uint64_t nseg = nbytes / seg + 1, cap = seg / p.min_size + 2;
     auto &space = scan_space.at(stream);
     LaunchLock sequence(space.launch); // the scratch is shared by the launches below
-    hipError_t e = space.reserve(cdc_workspace_bytes(nbytes, p.min_size, seg), kFloor);
+    const size_t nstreams = st ? st->nstreams : 0;
+    hipError_t e = space.reserve(st ? cdc_streams_workspace_bytes(nbytes, nstreams, p.min_size, seg) : cdc_workspace_bytes(nbytes, p.min_size, seg), kFloor);
     if (e != hipSuccess) return e;
     uint8_t *w = space.as<uint8_t>();
     auto take = [&](size_t bytes) { uint8_t *r = w; w += up256(bytes); return r; };
     uint64_t *gear = reinterpret_cast<uint64_t *>(take(2048));
     uint64_t *l0 = reinterpret_cast<uint64_t *>(take(2 * nwords * 8));
     uint64_t *lv = reinterpret_cast<uint64_t *>(take(4 * 8 * (n1 + n2 + n3)));
-    uint64_t *segs = reinterpret_cast<uint64_t *>(take(2 * nseg * cap * 8 + 2 * nseg * 8 + (nseg + 63) / 64 * 8 + 3 * nseg * 4));
-    uint64_t *notmerged = segs + 2 * nseg * cap + 2 * nseg;
+    const uint64_t cuts = nseg * cap + nstreams; // the entries of all lists (and of all pres)
+    uint64_t *segs = reinterpret_cast<uint64_t *>(take(2 * cuts * 8 + 2 * nseg * 8 + (nseg + 63) / 64 * 8 + 3 * nseg * 4));
+    uint64_t *notmerged = segs + 2 * cuts + 2 * nseg;
     uint32_t *counts = reinterpret_cast<uint32_t *>(take(nseg * 4));
     uint64_t *segoff = reinterpret_cast<uint64_t *>(take((nseg + 1) * 8));
+    uint32_t *eidx = st ? reinterpret_cast<uint32_t *>(take((nseg + 1) * 4)) : nullptr;
 
     e = hipMemcpyAsync(gear, p.gear, 2048, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) e = hipMemsetAsync(notmerged, 0, (nseg + 63) / 64 * 8, stream);
     if (e != hipSuccess) return e;
+    if (st) { // the verdict comes first; behind it either the empty result or eidx
+        if ((e = cdc_streams_verdict_launch(*st, nbytes, seg, nseg, eidx, offsets, nchunks, stream)) != hipSuccess) return e;
+    }
     const bool hi = (uint32_t)p.mask_s == 0 && (uint32_t)p.mask_l == 0;
     // 8 wavefronts per workgroup, one span each; 2 workgroups per CU (64 KiB of LDS tables each), grid-stride beyond 512
     const unsigned scan_grid = (unsigned)(n1 < 4096 ? (n1 + 7) / 8 : 512);
@@ -556,23 +261,53 @@ hipError_t cdc_launch(const CdcParams &p, const uint8_t *src, size_t nbytes, int
     hipLaunchKernelGGL(cdc_summary_kernel, dim3((unsigned)umin((n2 + 3) / 4, 1024)), dim3(256), 0, stream, l1, n1, l2, n2);
     hipLaunchKernelGGL(cdc_summary_kernel, dim3((unsigned)umin((n3 + 3) / 4, 1024)), dim3(256), 0, stream, l2, n2, l3, n3);
 
-    Cdc c;
+    CdcS c; // (the single-stream kernels take its Cdc part)
     c.l0 = l0; c.lv = lv;
     c.nwords = nwords; c.n1 = n1; c.n2 = n2; c.off = off; c.n = nbytes; c.seg = seg; c.nseg = nseg;
     c.m = p.min_size; c.a = p.normal_size; c.M = p.max_size; c.cap = (uint32_t)cap; c.final_ = final_;
     c.segs = segs;
-    const unsigned sg = (unsigned)((nseg + 63) / 64);
-    hipLaunchKernelGGL(cdc_spec_kernel, dim3(sg), dim3(64), 0, stream, c, nseg);
-    hipLaunchKernelGGL(cdc_merge_kernel, dim3(sg), dim3(64), 0, stream, c, nseg);
-    hipLaunchKernelGGL(cdc_fixup_kernel, dim3(1), dim3(64), 0, stream, c, nseg);
-    hipLaunchKernelGGL(cdc_count_kernel, dim3((unsigned)((nseg + 255) / 256)), dim3(256), 0, stream, c, nseg, counts);
+    const unsigned sg = (unsigned)((nseg + 63) / 64), cg = (unsigned)((nseg + 255) / 256);
+    if (st) {
+        c.ends = st->ends; c.eidx = eidx; c.verdict = st->result; c.nstreams = nstreams;
+        if ((e = cdc_streams_resolve_launch(c, counts, stream)) != hipSuccess) return e;
+    } else {
+        const Cdc &c1 = c;
+        hipLaunchKernelGGL(cdc_spec_kernel<Cdc>, dim3(sg), dim3(64), 0, stream, c1, nseg);
+        hipLaunchKernelGGL(cdc_merge_kernel<Cdc>, dim3(sg), dim3(64), 0, stream, c1, nseg);
+        hipLaunchKernelGGL(cdc_fixup_kernel<Cdc>, dim3(1), dim3(64), 0, stream, c1, nseg);
+        hipLaunchKernelGGL(cdc_count_kernel<Cdc>, dim3(cg), dim3(256), 0, stream, c1, nseg, counts);
+    }
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     e = pack_launch(nullptr, 0, counts, nseg, nullptr, segoff, stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(cdc_write_kernel, dim3((unsigned)nseg), dim3(64), 0, stream, c, nseg, segoff, offsets, (uint64_t)max_offsets, nchunks);
-    note_kernels(1, "cw::cdc_scan_kernel, cw::cdc_spec_kernel, cw::cdc_merge_kernel, cw::cdc_fixup_kernel");
+    if (st) {
+        return cdc_streams_write_launch(c, *st, segoff, offsets, max_offsets, nchunks, stream);
+    } else {
+        hipLaunchKernelGGL(cdc_write_kernel<Cdc>, dim3((unsigned)nseg), dim3(64), 0, stream, static_cast<const Cdc &>(c), nseg, segoff, offsets,
+                           (uint64_t)max_offsets, nchunks);
+        note_kernels(1, "cw::cdc_scan_kernel, cw::cdc_spec_kernel, cw::cdc_merge_kernel, cw::cdc_fixup_kernel");
+    }
     return hipGetLastError();
+}
+} // namespace
+
+hipError_t cdc_launch(const CdcParams &p, const uint8_t *src, size_t nbytes, int final_, uint64_t *offsets, size_t max_offsets,
+                      uint64_t *nchunks, uint64_t seg, hipStream_t stream)
+{
+    if (nbytes == 0) {
+        hipError_t e = hipMemsetAsync(offsets, 0, sizeof(uint64_t), stream);
+        return e != hipSuccess ? e : hipMemsetAsync(nchunks, 0, sizeof(uint64_t), stream);
+    }
+    return cdc_launch_any(p, src, nbytes, final_, offsets, max_offsets, nchunks, seg, nullptr, stream);
+}
+
+hipError_t cdc_streams_launch(const CdcParams &p, const uint8_t *src, size_t nbytes, const CdcStreams &st, uint64_t *offsets, size_t max_offsets,
+                              uint64_t *nchunks, uint64_t seg, hipStream_t stream)
+{
+    if (nbytes) return cdc_launch_any(p, src, nbytes, 1, offsets, max_offsets, nchunks, seg, &st, stream);
+    // no byte, no chunk: the verdict (streams that are all empty) and the empty result
+    return cdc_streams_verdict_launch(st, 0, seg, 1, nullptr, offsets, nchunks, stream);
 }
 
 hipError_t chunk_hash_launch(const uint64_t *offsets, const uint64_t *d_n, size_t max_chunks, size_t src_bytes, unsigned step_shift,

@@ -56,6 +56,32 @@ int cw::host::dev_cdc(const cw::CdcParams &p, const uint8_t *d_src, size_t nbyte
     return launched(e, "cdc launch");
 }
 
+int cw::host::cdc_streams_args(const cw::CdcParams &cp, const void *d_src, size_t nbytes, const StreamList &sl, const uint64_t *d_offsets,
+                                size_t max_offsets, const uint64_t *d_nchunks)
+{
+    if (!d_offsets || !d_nchunks || !sl.d_first || !sl.d_result || (nbytes && !d_src) || (sl.nstreams && !sl.d_ends))
+        return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    if (int rc = check_word_aligned((uintptr_t)sl.d_result, "d_result")) return rc;
+    if (int rc = check_count("nstreams", sl.nstreams)) return rc;
+    if (sl.nstreams == 0 && nbytes) return fail(CW_ERR_BAD_ARG, "nstreams is 0 and nbytes is %zu", nbytes);
+    const size_t need = nbytes / cp.min_size + sl.nstreams + 1;
+    if (max_offsets < need) return fail(CW_ERR_BAD_ARG, "max_offsets %zu < nbytes / min_size + nstreams + 1 = %zu", max_offsets, need);
+    return CW_OK;
+}
+
+int cw::host::dev_cdc_streams(const cw::CdcParams &p, const uint8_t *d_src, size_t nbytes, const StreamList &sl, uint64_t *d_offsets,
+                              size_t max_offsets, uint64_t *d_nchunks, hipStream_t s)
+{
+    const uint64_t seg = cw::cdc_segment_bytes(p.max_size, cw::knobs().cdc_segment);
+    ProfScope prof(PROF_HASH, s);
+    const cw::CdcStreams st{sl.d_ends, sl.nstreams, sl.d_first, sl.d_result};
+    hipError_t e = cw::cdc_streams_launch(p, d_src, nbytes, st, d_offsets, max_offsets, d_nchunks, seg, s);
+    if (e == hipErrorOutOfMemory)
+        return fail(CW_ERR_NOMEM, "cdc workspace (%zu bytes): %s", cw::cdc_streams_workspace_bytes(nbytes, sl.nstreams, p.min_size, seg),
+                    hipGetErrorString(e));
+    return launched(e, "cdc streams launch");
+}
+
 int cw::host::dev_hash_chunks(int alg, const uint8_t *d_src, size_t src_bytes, const uint64_t *d_offsets, const uint64_t *d_nchunks,
                               size_t max_chunks, uint8_t *d_dig, hipStream_t s)
 {
@@ -132,6 +158,18 @@ int cw_dev_cdc(const cw_cdc_params *p, const void *d_src, size_t nbytes, int fin
         return fail(CW_ERR_BAD_ARG, "max_offsets %zu < nbytes / min_size + 2 = %zu", max_offsets, nbytes / cp.min_size + 2);
     if ((rc = ensure_init()) != CW_OK) return rc;
     return dev_cdc(cp, (const uint8_t *)d_src, nbytes, final ? 1 : 0, d_offsets, max_offsets, d_nchunks, (hipStream_t)stream);
+}
+
+int cw_dev_cdc_streams(const cw_cdc_params *p, const void *d_src, size_t nbytes, const uint64_t *d_ends, size_t nstreams, uint64_t *d_offsets,
+                       size_t max_offsets, uint64_t *d_nchunks, uint64_t *d_stream_first, uint64_t *d_result, void *stream)
+{
+    cw::CdcParams cp;
+    int rc = cdc_params(p, &cp);
+    if (rc != CW_OK) return rc;
+    const StreamList sl{d_ends, nstreams, d_stream_first, d_result};
+    if ((rc = cdc_streams_args(cp, d_src, nbytes, sl, d_offsets, max_offsets, d_nchunks)) != CW_OK) return rc;
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    return dev_cdc_streams(cp, (const uint8_t *)d_src, nbytes, sl, d_offsets, max_offsets, d_nchunks, (hipStream_t)stream);
 }
 
 int cw_dev_hash_chunks(int hash_alg, const void *d_src, size_t src_bytes, const uint64_t *d_offsets, const uint64_t *d_nchunks,

@@ -487,7 +487,7 @@ int cw_dev_hash_dedupe_compress(cw_dedupe_t *x, int comp_alg, const void *d_src,
 int cw::host::dev_cdc_dedupe_compress(cw_dedupe_t *x, const cw_cdc_params *p, int comp_alg, const void *d_src, size_t nbytes, int final_, uint64_t base,
                                       uint64_t *d_offsets, size_t max_offsets, uint64_t *d_nchunks, void *d_digests, uint64_t *d_ref,
                                       uint32_t *d_new_idx, uint64_t *d_n_new, void *d_dst, size_t dst_bytes, uint32_t *d_sizes, size_t *nchunks,
-                                      hipStream_t s, const PieceAdmit *hook)
+                                      hipStream_t s, const PieceAdmit *hook, const StreamList *streams)
 {
     if (nchunks) *nchunks = 0;
     cw::CdcParams cp;
@@ -495,8 +495,11 @@ int cw::host::dev_cdc_dedupe_compress(cw_dedupe_t *x, const cw_cdc_params *p, in
     if (rc != CW_OK) return rc;
     if (!nchunks) return fail(CW_ERR_BAD_ARG, "NULL nchunks");
     if (!d_offsets || !d_nchunks || !d_digests || !d_ref || !d_new_idx || !d_n_new || (nbytes && !d_src)) return fail(CW_ERR_BAD_ARG, "NULL pointer");
-    if (max_offsets < nbytes / cp.min_size + 2)
+    if (streams) {
+        if ((rc = cdc_streams_args(cp, d_src, nbytes, *streams, d_offsets, max_offsets, d_nchunks)) != CW_OK) return rc;
+    } else if (max_offsets < nbytes / cp.min_size + 2) {
         return fail(CW_ERR_BAD_ARG, "max_offsets %zu < nbytes / min_size + 2 = %zu", max_offsets, nbytes / cp.min_size + 2);
+    }
     if ((rc = dedupe_dev_ptrs(true, d_digests)) != CW_OK) return rc;
     const size_t max_chunks = max_offsets - 1;
     if ((rc = compress_chunks_args(comp_alg, d_src, nbytes, d_offsets, d_nchunks, max_chunks, d_new_idx, d_n_new, d_dst, dst_bytes, d_sizes)) != CW_OK)
@@ -504,7 +507,8 @@ int cw::host::dev_cdc_dedupe_compress(cw_dedupe_t *x, const cw_cdc_params *p, in
     if ((rc = dedupe_args(x, 0, base)) != CW_OK) return rc; // (base + the chunk count: checked when the count is known, as cw_dev_dedupe would)
     const uint8_t *src = (const uint8_t *)d_src;
     return dedupe_on_stream(x, s, [&]() -> int {
-        int rc = dev_cdc(cp, src, nbytes, final_ ? 1 : 0, d_offsets, max_offsets, d_nchunks, s);
+        int rc = streams ? dev_cdc_streams(cp, src, nbytes, *streams, d_offsets, max_offsets, d_nchunks, s)
+                         : dev_cdc(cp, src, nbytes, final_ ? 1 : 0, d_offsets, max_offsets, d_nchunks, s);
         if (rc == CW_OK) rc = dev_hash_chunks(x->hash_alg, src, nbytes, d_offsets, d_nchunks, max_chunks, (uint8_t *)d_digests, s);
         if (rc != CW_OK) return rc;
         uint64_t *h_counts = hook ? hook->h_counts : x->h_ctrl;
@@ -514,8 +518,10 @@ int cw::host::dev_cdc_dedupe_compress(cw_dedupe_t *x, const cw_cdc_params *p, in
             HIP_TRY(hipMemcpyAsync(h_counts, hook->d_counts, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         } else {
             HIP_TRY(hipMemcpyAsync(h_counts, d_nchunks, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+            if (streams) HIP_TRY(hipMemcpyAsync(h_counts + 1, streams->d_result, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         }
         HIP_TRY(hipStreamSynchronize(s));
+        if (streams && h_counts[1]) return fail(CW_ERR_BAD_ARG, "d_ends decreases or does not end at nbytes = %zu", nbytes);
         const size_t k = (size_t)h_counts[0];
         *nchunks = k;
         if (hook && (rc = hook->admit(hook->self, k, h_counts)) != CW_OK) return rc;
@@ -539,4 +545,15 @@ extern "C" int cw_dev_cdc_dedupe_compress(cw_dedupe_t *x, const cw_cdc_params *p
 {
     return dev_cdc_dedupe_compress(x, p, comp_alg, d_src, nbytes, final, base, d_offsets, max_offsets, d_nchunks, d_digests, d_ref, d_new_idx, d_n_new,
                                    d_dst, dst_bytes, d_sizes, nchunks, (hipStream_t)stream, nullptr);
+}
+
+extern "C" int cw_dev_cdc_streams_dedupe_compress(cw_dedupe_t *x, const cw_cdc_params *p, int comp_alg, const void *d_src, size_t nbytes,
+                                                  const uint64_t *d_ends, size_t nstreams, uint64_t base, uint64_t *d_offsets, size_t max_offsets,
+                                                  uint64_t *d_nchunks, uint64_t *d_stream_first, uint64_t *d_result, void *d_digests,
+                                                  uint64_t *d_ref, uint32_t *d_new_idx, uint64_t *d_n_new, void *d_dst, size_t dst_bytes,
+                                                  uint32_t *d_sizes, size_t *nchunks, void *stream)
+{
+    const StreamList sl{d_ends, nstreams, d_stream_first, d_result};
+    return dev_cdc_dedupe_compress(x, p, comp_alg, d_src, nbytes, 1, base, d_offsets, max_offsets, d_nchunks, d_digests, d_ref, d_new_idx, d_n_new,
+                                   d_dst, dst_bytes, d_sizes, nchunks, (hipStream_t)stream, nullptr, &sl);
 }

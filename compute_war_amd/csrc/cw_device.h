@@ -130,6 +130,12 @@ size_t cdc_workspace_bytes(size_t nbytes, uint32_t min_size, uint64_t seg);
 // offsets[0..K] and *nchunks = K on the device; at most nbytes / min_size + 2 offsets are written
 hipError_t cdc_launch(const CdcParams &p, const uint8_t *src, size_t nbytes, int final_, uint64_t *offsets, size_t max_offsets,
                       uint64_t *nchunks, uint64_t seg, hipStream_t stream);
+// many streams in one buffer (cw_dev_cdc_streams): ends[nstreams], first[nstreams + 1] and *result on the device; at most
+// nbytes / min_size + nstreams + 1 offsets are written
+struct CdcStreams { const uint64_t *ends; size_t nstreams; uint64_t *first, *result; };
+size_t cdc_streams_workspace_bytes(size_t nbytes, size_t nstreams, uint32_t min_size, uint64_t seg);
+hipError_t cdc_streams_launch(const CdcParams &p, const uint8_t *src, size_t nbytes, const CdcStreams &st, uint64_t *offsets, size_t max_offsets,
+                              uint64_t *nchunks, uint64_t seg, hipStream_t stream);
 // orders the chunks i < min(*d_n, max_chunks) by (length >> step_shift), longest first, into a permutation in the stream's
 // workspace, and calls hash.fn(hash.ctx, perm) to queue the hash that reads it -- both under the workspace's launch lock
 struct ChunkHash { hipError_t (*fn)(void *ctx, const uint32_t *perm); void *ctx; };

@@ -100,6 +100,13 @@ int dev_compress(int alg, const uint8_t *d_src, size_t bb, size_t stride, size_t
 int cdc_params(const cw_cdc_params *p, cw::CdcParams *out); // checked and with the default gear filled in
 int dev_cdc(const cw::CdcParams &p, const uint8_t *d_src, size_t nbytes, int final_, uint64_t *d_offsets, size_t max_offsets, uint64_t *d_nchunks,
             hipStream_t s);
+// the streams of cw_dev_cdc_streams: d_ends[nstreams], d_first[nstreams + 1] and *d_result on the device
+struct StreamList { const uint64_t *d_ends; size_t nstreams; uint64_t *d_first, *d_result; };
+// everything cw_dev_cdc_streams refuses behind its parameters, none of it needing a device
+int cdc_streams_args(const cw::CdcParams &cp, const void *d_src, size_t nbytes, const StreamList &sl, const uint64_t *d_offsets, size_t max_offsets,
+                     const uint64_t *d_nchunks);
+int dev_cdc_streams(const cw::CdcParams &p, const uint8_t *d_src, size_t nbytes, const StreamList &sl, uint64_t *d_offsets, size_t max_offsets,
+                    uint64_t *d_nchunks, hipStream_t s);
 int dev_hash_chunks(int alg, const uint8_t *d_src, size_t src_bytes, const uint64_t *d_offsets, const uint64_t *d_nchunks, size_t max_chunks,
                     uint8_t *d_dig, hipStream_t s);
 // everything cw_dev_compress_chunks refuses, none of it needing a device
@@ -120,11 +127,12 @@ struct PieceAdmit {
     void *self;
     bool *inserted; // set once the piece's chunks are queued for the index: a failure behind that point is no refusal
 };
-// cw_dev_cdc_dedupe_compress is this with hook == nullptr
+// cw_dev_cdc_dedupe_compress is this with hook == nullptr and streams == nullptr; cw_dev_cdc_streams_dedupe_compress gives `streams`
+// (the chunker is then cw_dev_cdc_streams, final_ is not read, and the verdict on d_ends comes back with the chunk count)
 int dev_cdc_dedupe_compress(cw_dedupe_t *x, const cw_cdc_params *p, int comp_alg, const void *d_src, size_t nbytes, int final_, uint64_t base,
                             uint64_t *d_offsets, size_t max_offsets, uint64_t *d_nchunks, void *d_digests, uint64_t *d_ref, uint32_t *d_new_idx,
                             uint64_t *d_n_new, void *d_dst, size_t dst_bytes, uint32_t *d_sizes, size_t *nchunks, hipStream_t s,
-                            const PieceAdmit *hook);
+                            const PieceAdmit *hook, const StreamList *streams = nullptr);
 
 } // namespace host
 } // namespace cw

@@ -361,6 +361,24 @@ class DedupeIndex:
             raise err
         return int(k.value)
 
+    def dev_cdc_streams_dedupe_compress(self, params: "CdcParams", comp_alg, d_src: int, nbytes: int, d_ends: int, nstreams: int, base: int,
+                                        d_offsets: int, max_offsets: int, d_nchunks: int, d_stream_first: int, d_result: int, d_digests: int,
+                                        d_ref: int, d_new_idx: int, d_n_new: int, d_dst: int, dst_bytes: int, d_sizes: int,
+                                        stream: int = 0) -> int:
+        """``dev_cdc_dedupe_compress`` over many streams in one buffer (``dev_cdc_streams``): every stream gets its own cuts, chunk i of
+        the buffer carries value base + i, and stream f's chunks are positions [first[f], first[f + 1]).  max_offsets >=
+        ``params.max_offsets_streams(nbytes, nstreams)``.  Synchronises the stream once; returns the chunk count.  Refused ends raise
+        CwError -2 with nothing inserted; a full index raises CwError -5 with ``e.nchunks`` set."""
+        k = C.c_size_t(0)
+        rc = lib().cw_dev_cdc_streams_dedupe_compress(self._x(), C.byref(params), _comp_id(comp_alg), d_src or None, nbytes, d_ends or None,
+                                                      nstreams, base, d_offsets, max_offsets, d_nchunks, d_stream_first, d_result, d_digests,
+                                                      d_ref, d_new_idx, d_n_new, d_dst, dst_bytes, d_sizes, C.byref(k), stream)
+        if rc != 0:
+            err = _lib.CwError(rc, lib().cw_last_error().decode(errors="replace"))
+            err.nchunks = int(k.value)
+            raise err
+        return int(k.value)
+
     def dev_lookup(self, d_digests: int, n: int, d_ref: int, d_n_found: int, stream: int = 0) -> None:
         """Read-only: ref[i] = the stored value of digest i or ``MISS``; *d_n_found = hits (u64).  The index is unchanged."""
         check(lib().cw_dev_dedupe_lookup(self._x(), d_digests, n, d_ref, d_n_found, stream))
@@ -559,11 +577,23 @@ class CdcParams(C.Structure):
     def max_offsets(self, nbytes: int) -> int:
         return nbytes // self.min_size + 2
 
+    def max_offsets_streams(self, nbytes: int, nstreams: int) -> int:
+        return nbytes // self.min_size + nstreams + 1
+
 
 def dev_cdc(params: CdcParams, d_src: int, nbytes: int, final: bool, d_offsets: int, max_offsets: int, d_nchunks: int,
             stream: int = 0) -> None:
     """Cuts of d_src[0..nbytes): d_offsets[0..K] (u64) and *d_nchunks = K, on the device, queued on `stream`."""
     check(lib().cw_dev_cdc(C.byref(params), d_src, nbytes, 1 if final else 0, d_offsets, max_offsets, d_nchunks, stream))
+
+
+def dev_cdc_streams(params: CdcParams, d_src: int, nbytes: int, d_ends: int, nstreams: int, d_offsets: int, max_offsets: int, d_nchunks: int,
+                    d_stream_first: int, d_result: int, stream: int = 0) -> None:
+    """Cuts of the streams d_src[ends[f-1] .. ends[f]) (u64 ends on the device, the last = nbytes), each as ``dev_cdc`` cuts it alone:
+    d_offsets[0..K], *d_nchunks = K, d_stream_first[0..nstreams] (stream f = chunks [first[f], first[f + 1])) and *d_result = 1 when
+    the ends were refused (then K = 0).  Queued on `stream`, not synchronised."""
+    check(lib().cw_dev_cdc_streams(C.byref(params), d_src or None, nbytes, d_ends or None, nstreams, d_offsets, max_offsets, d_nchunks,
+                                   d_stream_first, d_result, stream))
 
 
 def dev_hash_chunks(hash_alg, d_src: int, src_bytes: int, d_offsets: int, d_nchunks: int, max_chunks: int, d_digests: int,
@@ -794,6 +824,48 @@ class ChunkStore:
             raise err
         self.base += k
         return Recipe(ref.cpu().numpy().view(np.uint64)[:k], off.cpu().numpy().view(np.uint64)[:k + 1])
+
+    def ingest_many(self, datas) -> list:
+        """``ingest`` of many buffers at once: one upload of their concatenation, one fused call (``dev_cdc_streams_dedupe_compress``)
+        and one ``dev_store_chunks``.  Every buffer is chunked as if alone, so the recipes, the store and the index are what a loop of
+        ``ingest`` over ``datas`` leaves.  Returns one Recipe per buffer, its offsets starting at 0.  Raises as ``ingest`` does."""
+        import torch
+        parts = [_np_u8(d) for d in datas]
+        if not parts:
+            return []
+        ends = np.cumsum([a.size for a in parts], dtype=np.uint64)
+        n, nf, s = int(ends[-1]), len(parts), self._stream()
+        src = torch.from_numpy(np.concatenate(parts) if n else np.zeros(1, np.uint8)).cuda()
+        d_ends = torch.from_numpy(ends.view(np.int64)).cuda()
+        cap = self.params.max_offsets_streams(n, nf)
+        total = chunk_slots_bytes(self.comp_alg, n, cap - 1)
+        z = lambda k, dt: torch.zeros(k, dtype=dt, device="cuda")  # noqa: E731
+        off, k_dev, dig = z(cap, torch.int64), z(1, torch.int64), z(cap * digest_bytes(self.index.hash_alg), torch.uint8)
+        ref, new_idx, n_new = z(cap, torch.int64), z(cap, torch.int32), z(1, torch.int64)
+        slots, sizes, result = torch.empty(total, dtype=torch.uint8, device="cuda"), z(cap, torch.int32), z(2, torch.int64)
+        first, ends_ok = z(nf + 1, torch.int64), z(1, torch.int64)
+        torch.cuda.synchronize()
+        k = self.index.dev_cdc_streams_dedupe_compress(self.params, self.comp_alg, src.data_ptr(), n, d_ends.data_ptr(), nf, self.base,
+                                                       off.data_ptr(), cap, k_dev.data_ptr(), first.data_ptr(), ends_ok.data_ptr(),
+                                                       dig.data_ptr(), ref.data_ptr(), new_idx.data_ptr(), n_new.data_ptr(), slots.data_ptr(),
+                                                       total, sizes.data_ptr(), s)
+        dev_store_chunks(self.comp_alg, src.data_ptr(), n, off.data_ptr(), k_dev.data_ptr(), cap - 1, slots.data_ptr(), sizes.data_ptr(),
+                         self.base, self.d_store.data_ptr(), self.store_bytes, self.d_used.data_ptr(), self.d_dir.data_ptr(), self.dir_base,
+                         self.dir_entries, result.data_ptr(), s, new_idx.data_ptr(), n_new.data_ptr())
+        torch.cuda.synchronize()
+        verdict, needed = (int(v) for v in result.cpu().numpy().view(np.uint64))
+        if verdict:
+            err = _lib.CwError(-5, f"chunk store: {needed} bytes do not fit behind {self.used()} of {self.store_bytes}" if verdict == 1 else
+                               f"chunk store: values {self.base} .. {self.base + k} leave the directory [{self.dir_base}, "
+                               f"{self.dir_base + self.dir_entries})")
+            err.needed = needed
+            raise err
+        self.base += k
+        refs, offs = ref.cpu().numpy().view(np.uint64)[:k], off.cpu().numpy().view(np.uint64)[:k + 1]
+        lo = first.cpu().numpy().view(np.uint64)
+        starts = np.concatenate([np.zeros(1, np.uint64), ends[:-1]])
+        return [Recipe(refs[a:b], offs[a:b + 1] - starts[f]) if b > a else Recipe([], [0])
+                for f, (a, b) in enumerate(zip(lo[:-1].tolist(), lo[1:].tolist()))]
 
     def _triple(self) -> Store:
         return Store(self.d_store.data_ptr(), self.store_bytes, self.d_used.data_ptr(), self.d_dir.data_ptr(), self.dir_base, self.dir_entries)

@@ -306,6 +306,30 @@ int cw_dev_hash_chunks(int hash_alg, const void *d_src, size_t src_bytes, const 
  * min_size + 2), digests[*nchunks].  Uses the calling thread's staging buffers and the workspaces of its stream.      */
 int cw_cdc_hash(const cw_cdc_params *p, int hash_alg, const void *src, size_t nbytes,
                 uint64_t *offsets, size_t max_offsets, size_t *nchunks, void *digests);
+/* Many streams in one device buffer, each cut as if alone.  Stream f is d_src[d_ends[f-1] .. d_ends[f]) with
+ * d_ends[-1] = 0: d_ends[nstreams] (u64, device memory) is non-decreasing and its last entry is nbytes; equal neighbours are empty
+ * streams; nstreams is a host count.  Every stream is complete: there is no final = 0 form.
+ *   d_offsets[0..K]   the cuts of every non-empty stream as cw_dev_cdc(final = 1) over that stream alone gives them, shifted by the
+ *                     stream's start, in order: strictly ascending, d_offsets[0] = 0, d_offsets[K] = nbytes.  An empty stream gives no
+ *                     chunk.  *d_nchunks = K <= nbytes / min_size + nstreams (a stream of L bytes has at most L / min_size + 1 chunks).
+ *   d_stream_first[0..nstreams]   [f] = the index of stream f's first chunk, for an empty stream that of the next stream's first chunk,
+ *                     [nstreams] = K: stream f's chunks are positions [first[f], first[f+1]) and its cuts d_offsets[first[f] ..
+ *                     first[f+1]] - d_offsets[first[f]].
+ *   *d_result (u64, 8-byte aligned)   the verdict on d_ends, decided on the device before anything else is written: 1 when d_ends
+ *                     decreases anywhere or its last entry is not nbytes -- then *d_nchunks = 0, d_offsets[0] = 0, every
+ *                     d_stream_first[f] = 0 and nothing else is written -- else 0.
+ * Whatever d_ends holds, no load leaves d_ends[0..nstreams) or the 16-byte-aligned granules that overlap d_src[0..nbytes), and no store
+ * leaves d_offsets[0..max_offsets), d_stream_first[0..nstreams], the two scalars or the workspace.
+ * CW_ERR_BAD_ARG, before anything is launched: what cw_dev_cdc refuses, a NULL pointer (d_src may be NULL when nbytes is 0, d_ends
+ * when nstreams is 0), a d_result that is not 8-byte aligned, nstreams > 2^32 - 256, nstreams == 0 with nbytes != 0, and max_offsets <
+ * nbytes / min_size + nstreams + 1.  nstreams == 0 (nbytes == 0) gives zero chunks and verdict 0.  With nstreams == 1 the cuts are
+ * cw_dev_cdc(final = 1)'s.  Queued on `stream`, not synchronised.
+ * Scratch: cw_dev_cdc's workspace, with cut lists that also hold every stream end (a segment's two lists hold nstreams_inside_it more
+ * cuts each: 16 * nstreams bytes in all, so a segment full of one-byte streams fits) and 4 bytes per segment: a host function of nbytes,
+ * nstreams and CW_CDC_SEGMENT.  A step of the resolve finds its stream's end by a binary search among the ends inside its segment.  */
+int cw_dev_cdc_streams(const cw_cdc_params *p, const void *d_src, size_t nbytes, const uint64_t *d_ends, size_t nstreams,
+                       uint64_t *d_offsets, size_t max_offsets, uint64_t *d_nchunks,
+                       uint64_t *d_stream_first /* [nstreams + 1] */, uint64_t *d_result, void *stream);
 
 /* ---- codecs over chunks ----------------------------------------------------------------------
  * The codec calls above take one block size per call; these take an offset list as cw_dev_cdc writes it, every chunk
@@ -375,6 +399,19 @@ int cw_dev_cdc_dedupe_compress(cw_dedupe_t *x, const cw_cdc_params *p, int comp_
                                void *d_digests, uint64_t *d_ref, uint32_t *d_new_idx, uint64_t *d_n_new,
                                void *d_dst, size_t dst_bytes, uint32_t *d_sizes,
                                size_t *nchunks, void *stream);
+/* cw_dev_cdc_dedupe_compress with cw_dev_cdc_streams as its chunker: the arguments of both (no `final`), chunk i of the whole buffer
+ * carries value base + i.  max_offsets >= nbytes / min_size + nstreams + 1 and dst_bytes >= cw_chunk_slots_bytes(comp_alg, nbytes,
+ * max_offsets - 1).  Its one synchronise brings the chunk count AND the verdict to the host: verdict 1 gives CW_ERR_BAD_ARG with
+ * *nchunks = 0, nothing inserted and nothing compressed (*d_result stays 1).  The CW_ERR_NOMEM and wrap rules are those of
+ * cw_dev_cdc_dedupe_compress.  cw_dev_store_chunks, cw_dev_pack_chunks, cw_dev_restore_chunks and cw_dev_read_ranges work behind it
+ * unchanged (they see only offsets); a recipe per stream is positions [first[f], first[f+1]) of d_ref with the cuts rebased.      */
+int cw_dev_cdc_streams_dedupe_compress(cw_dedupe_t *x, const cw_cdc_params *p, int comp_alg,
+                                       const void *d_src, size_t nbytes, const uint64_t *d_ends, size_t nstreams, uint64_t base,
+                                       uint64_t *d_offsets, size_t max_offsets, uint64_t *d_nchunks,
+                                       uint64_t *d_stream_first, uint64_t *d_result,
+                                       void *d_digests, uint64_t *d_ref, uint32_t *d_new_idx, uint64_t *d_n_new,
+                                       void *d_dst, size_t dst_bytes, uint32_t *d_sizes,
+                                       size_t *nchunks, void *stream);
 
 /* ---- chunk store: keep the new chunks, restore deduplicated streams ---------------------------------
  * The read side of the dedupe path.  The library keeps no state: the CALLER owns three plain device buffers, and all three
