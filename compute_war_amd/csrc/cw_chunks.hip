@@ -1,6 +1,6 @@
 // cw_chunks.hip -- host side of the device-resident calls over content-defined chunks: the cut (kernels: cdc_kernels.hip), the per-chunk
-// hash, the chunk codecs and their pack (chunk_codec_kernels.hip, pack_kernels.hip), the chunk store (restore_kernels.hip), its ranged reads (read_kernels.hip)
-// and its mark and compact (store_gc_kernels.hip).  Semantics: the public header.  Every refusal here comes before the device is touched.
+// hash, the chunk codecs and their pack (chunk_codec_kernels.hip, pack_kernels.hip), the chunk store (restore_kernels.hip), its ranged reads (read_kernels.hip),
+// its mark and compact (store_gc_kernels.hip) and its chunk bundles (replicate_kernels.hip).  Semantics: the public header.  Every refusal here comes before the device is touched.
 
 #include "cw_host.h"
 
@@ -323,6 +323,60 @@ int cw_dev_store_compact(const void *d_store, size_t store_bytes, const cw_chunk
     return launched_nomem(cw::store_compact_launch((const uint8_t *)d_store, store_bytes, d_dir, dir_entries, d_live, (uint8_t *)d_new_store,
                                                    new_store_bytes, d_new_used, d_new_dir, d_result, (hipStream_t)stream),
                           "store compact launch");
+}
+
+// ---- chunk bundles between stores: export, import, translate (kernels: replicate_kernels.hip) ----------------------------------
+int cw_dev_store_export_chunks(const void *d_store, size_t store_bytes, const cw_chunk_loc *d_dir, uint64_t dir_base, size_t dir_entries,
+                               const uint64_t *d_values, const uint64_t *d_count, size_t max_count, void *d_out, size_t out_bytes,
+                               cw_chunk_loc *d_out_loc, uint64_t *d_result, void *stream)
+{
+    int rc = check_count("max_count", max_count);
+    if (rc != CW_OK) return rc;
+    if (!d_dir || !d_values || !d_count || !d_out_loc || !d_result || (store_bytes && !d_store) || (out_bytes && !d_out))
+        return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    if (dir_entries == 0) return fail(CW_ERR_BAD_ARG, "dir_entries is 0");
+    if ((rc = check_dir_aligned((uintptr_t)d_dir | (uintptr_t)d_out_loc, "d_dir / d_out_loc")) != CW_OK) return rc;
+    if ((rc = check_word_aligned((uintptr_t)d_values | (uintptr_t)d_count | (uintptr_t)d_result, "d_values / d_count / d_result")) != CW_OK) return rc;
+    if (ranges_overlap(d_store, store_bytes, d_out, out_bytes)) return fail(CW_ERR_BAD_ARG, "d_out overlaps d_store");
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    return launched_nomem(cw::store_export_launch((const uint8_t *)d_store, store_bytes, d_dir, dir_base, dir_entries, d_values, d_count, max_count,
+                                                  (uint8_t *)d_out, out_bytes, d_out_loc, d_result, (hipStream_t)stream),
+                          "store export launch");
+}
+
+int cw_dev_store_import_chunks(const void *d_in, size_t in_bytes, const cw_chunk_loc *d_in_loc, const uint64_t *d_count, size_t max_count,
+                               const uint32_t *d_sel, const uint64_t *d_nsel, uint64_t base, void *d_store, size_t store_bytes, uint64_t *d_used,
+                               cw_chunk_loc *d_dir, uint64_t dir_base, size_t dir_entries, uint64_t *d_result, void *stream)
+{
+    int rc = check_count("max_count", max_count);
+    if (rc != CW_OK) return rc;
+    if (!d_in_loc || !d_count || !d_used || !d_dir || !d_result || (in_bytes && !d_in) || (store_bytes && !d_store) || !d_sel != !d_nsel)
+        return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    if (dir_entries == 0) return fail(CW_ERR_BAD_ARG, "dir_entries is 0");
+    if ((rc = check_dir_aligned((uintptr_t)d_in_loc | (uintptr_t)d_dir, "d_in_loc / d_dir")) != CW_OK) return rc;
+    if ((rc = check_word_aligned((uintptr_t)d_count | (uintptr_t)d_nsel | (uintptr_t)d_used | (uintptr_t)d_result,
+                                 "d_count / d_nsel / d_used / d_result")) != CW_OK)
+        return rc;
+    if (ranges_overlap(d_in, in_bytes, d_store, store_bytes)) return fail(CW_ERR_BAD_ARG, "d_in overlaps d_store");
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    return launched_nomem(cw::store_import_launch((const uint8_t *)d_in, in_bytes, d_in_loc, d_count, max_count, d_sel, d_nsel, base,
+                                                  (uint8_t *)d_store, store_bytes, d_used, d_dir, dir_base, dir_entries, d_result, (hipStream_t)stream),
+                          "store import launch");
+}
+
+int cw_dev_translate_refs(const uint64_t *d_ref, const uint64_t *d_count, size_t max_count, const uint64_t *d_from, const uint64_t *d_to,
+                          const uint64_t *d_npairs, size_t max_pairs, uint64_t *d_out, uint64_t *d_n_missing, void *stream)
+{
+    int rc;
+    if ((rc = check_count("max_count", max_count)) != CW_OK || (rc = check_count("max_pairs", max_pairs)) != CW_OK) return rc;
+    if (!d_ref || !d_count || !d_from || !d_to || !d_npairs || !d_out || !d_n_missing) return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    if ((rc = check_word_aligned((uintptr_t)d_ref | (uintptr_t)d_count | (uintptr_t)d_from | (uintptr_t)d_to | (uintptr_t)d_npairs | (uintptr_t)d_out |
+                                     (uintptr_t)d_n_missing,
+                                 "a u64 pointer is")) != CW_OK)
+        return rc;
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    return launched(cw::translate_refs_launch(d_ref, d_count, max_count, d_from, d_to, d_npairs, max_pairs, d_out, d_n_missing, (hipStream_t)stream),
+                    "translate refs launch");
 }
 
 } // extern "C"

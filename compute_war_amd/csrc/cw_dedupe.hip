@@ -1,5 +1,5 @@
 // cw_dedupe.hip -- host side of the dedupe index (kernels and protocol: dedupe_kernels.hip; semantics: the public header): the index
-// object and its table, insert / lookup / export / import, the rebuild behind resize and retain, and the two fused calls that end in
+// object and its table, insert / lookup / export / export of the live entries / import, the rebuild behind resize and retain, and the two fused calls that end in
 // the codec over the new blocks or chunks only.
 //
 // The calls of one index are serialised: each takes the index's lock and goes through dedupe_on_stream, which orders its work behind
@@ -303,6 +303,26 @@ int cw_dev_dedupe_export(cw_dedupe_t *x, void *d_digests, uint64_t *d_values, si
     return dedupe_on_stream(x, s, [&]() -> int {
         const int ok = dedupe_export_scan(x, s);
         return ok != CW_OK ? ok : dedupe_export_scatter(x, 0, max_out, d_digests, d_values, d_n, s);
+    });
+}
+
+int cw_dev_dedupe_export_live(cw_dedupe_t *x, const uint32_t *d_live, uint64_t dir_base, size_t dir_entries, void *d_digests, uint64_t *d_values,
+                              size_t max_out, uint64_t *d_result, void *stream)
+{
+    int rc;
+    if (!x || !d_live || !d_result || (max_out && (!d_digests || !d_values))) return fail(CW_ERR_BAD_ARG, "NULL %s", x ? "pointer" : "dedupe index");
+    if (((uintptr_t)d_digests | (uintptr_t)d_values | (uintptr_t)d_result) % 8)
+        return fail(CW_ERR_BAD_ARG, "d_digests / d_values / d_result not 8-byte aligned");
+    if (dir_entries == 0) return fail(CW_ERR_BAD_ARG, "dir_entries is 0");
+    if ((rc = check_count("dir_entries", dir_entries)) != CW_OK || (rc = check_count("max_out", max_out)) != CW_OK) return rc;
+    if ((rc = dedupe_args(x, 0, 0)) != CW_OK) return rc;
+    const hipStream_t s = (hipStream_t)stream;
+    return dedupe_on_stream(x, s, [&]() -> int { // the flags and their ranks go into the index's scratch (flags, offs)
+        int ok;
+        if ((ok = dedupe_scratch(x, x->flags, dir_entries * 4)) != CW_OK || (ok = dedupe_scratch(x, x->offs, (dir_entries + 1) * 8)) != CW_OK) return ok;
+        return launched(cw::dedupe_export_live_launch(x->words, x->t.state, x->t.value, x->t.key, x->cap, d_live, dir_base, dir_entries,
+                                                      (uint32_t *)x->flags.p, (uint64_t *)x->offs.p, max_out, (uint64_t *)d_digests, d_values, d_result, s),
+                        "dedupe export live launch");
     });
 }
 

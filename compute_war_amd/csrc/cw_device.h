@@ -111,6 +111,11 @@ hipError_t dedupe_export_scan_launch(const uint64_t *state, uint64_t cap, uint32
 hipError_t dedupe_export_scatter_launch(unsigned words, const uint64_t *state, const uint64_t *value, const uint64_t *key, uint64_t cap,
                                         const uint64_t *offs, uint64_t first, uint64_t max_out, uint64_t *out_dig, uint64_t *out_val, uint64_t *d_n,
                                         hipStream_t s);
+// the digests of the flagged directory entries' values in ascending value (cw_dev_dedupe_export_live): flags[dir_entries] (u32) and
+// rank[dir_entries + 1] are the caller's scratch; result[2] = {flagged entries, table entries with a flagged value}
+hipError_t dedupe_export_live_launch(unsigned words, const uint64_t *state, const uint64_t *value, const uint64_t *key, uint64_t cap,
+                                     const uint32_t *live, uint64_t dir_base, uint64_t dir_entries, uint32_t *flags, uint64_t *rank, uint64_t max_out,
+                                     uint64_t *out_dig, uint64_t *out_val, uint64_t *result, hipStream_t s);
 // every committed entry of the old table into the (empty) new one; err = 1 if an entry found no slot
 hipError_t dedupe_rehash_launch(unsigned words, const uint64_t *old_state, const uint64_t *old_value, const uint64_t *old_key, uint64_t old_cap,
                                 uint64_t *state, uint64_t *value, uint64_t *key, uint64_t mask, unsigned long long *err, hipStream_t s);
@@ -250,6 +255,16 @@ hipError_t store_mark_launch(const uint64_t *ref, const uint64_t *d_count, size_
 hipError_t store_compact_launch(const uint8_t *store, size_t store_bytes, const void *dir, size_t dir_entries, const uint32_t *live,
                                 uint8_t *new_store, size_t new_store_bytes, uint64_t *new_used, void *new_dir, uint64_t *result,
                                 hipStream_t stream);
+
+// chunk bundles between stores (replicate_kernels.hip; semantics: the public header).  loc / dir: cw_chunk_loc entries, 16-byte aligned
+hipError_t store_export_launch(const uint8_t *store, size_t store_bytes, const void *dir, uint64_t dir_base, size_t dir_entries,
+                               const uint64_t *values, const uint64_t *d_count, size_t max_count, uint8_t *out, size_t out_bytes, void *out_loc,
+                               uint64_t *result, hipStream_t stream);
+hipError_t store_import_launch(const uint8_t *in, size_t in_bytes, const void *in_loc, const uint64_t *d_count, size_t max_count,
+                               const uint32_t *sel, const uint64_t *d_nsel, uint64_t base, uint8_t *store, size_t store_bytes, uint64_t *d_used,
+                               void *dir, uint64_t dir_base, size_t dir_entries, uint64_t *result, hipStream_t stream);
+hipError_t translate_refs_launch(const uint64_t *ref, const uint64_t *d_count, size_t max_count, const uint64_t *from, const uint64_t *to,
+                                 const uint64_t *d_npairs, size_t max_pairs, uint64_t *out, uint64_t *n_missing, hipStream_t stream);
 
 hipError_t sum_sizes_launch(const uint32_t *sizes, size_t n, uint32_t raw_bytes, uint64_t *totals, hipStream_t stream);
 hipError_t gen_random_launch(uint64_t seed, uint64_t first_block, size_t nblocks, size_t block_bytes, uint8_t *dst,

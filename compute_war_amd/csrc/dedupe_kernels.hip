@@ -1,6 +1,6 @@
 // dedupe_kernels.hip -- device-resident fingerprint index (cw_dedupe_*, cw_dev_dedupe*): batched lookup-or-insert of full
-// digests in an open-addressed table with linear probing, on gfx950, and the index's lifecycle: read-only lookup, export, the
-// rehash of cw_dedupe_resize and the filtered rehash of cw_dedupe_retain.  The reference has no counterpart: HashAndCompress.cpp computes the digests and drops them (:257,
+// digests in an open-addressed table with linear probing, on gfx950, and the index's lifecycle: read-only lookup, export, the export of
+// a directory's flagged entries in value order (cw_dev_dedupe_export_live), the rehash of cw_dedupe_resize and the filtered rehash of cw_dedupe_retain.  The reference has no counterpart: HashAndCompress.cpp computes the digests and drops them (:257,
 // SURVEY.md D3).
 //
 // Table (allocated by cw_dedupe_create and again by cw_dedupe_resize; capacity a power of two >= 2 x max_entries, so the load stays <= 0.5):
@@ -347,6 +347,69 @@ dedupe_retain_kernel(const uint64_t *__restrict__ old_state, const uint64_t *__r
     }
 }
 
+// ---- the digests behind a directory's flagged entries (cw_dev_dedupe_export_live) -----------------------
+// The export with a filter and an order: the table maps digest -> value, this answers "the digests of the values live[] flags", in
+// ascending value.  Three kernels, each behind a kernel boundary: flags[idx] = live[idx] != 0, whose index-only pack scan gives every
+// flagged idx its rank; a fill that writes (CW_DEDUPE_MISS, zero digest) to every rank below max_out, so a flagged value the table
+// lacks is answered without a second pass; one sweep of the table that places each committed entry with a flagged value at its rank.
+__global__ void __launch_bounds__(kThreads)
+dedupe_live_flags_kernel(const uint32_t *__restrict__ live, uint64_t dir_entries, uint32_t *__restrict__ flags)
+{
+    for (uint64_t idx = (uint64_t)blockIdx.x * kThreads + threadIdx.x; idx < dir_entries; idx += (uint64_t)gridDim.x * kThreads)
+        flags[idx] = live[idx] != 0;
+}
+
+// result = {L, 0}: the sweep counts its hits into result[1]
+template <int W>
+__global__ void __launch_bounds__(kThreads)
+dedupe_live_fill_kernel(const uint32_t *__restrict__ live, uint64_t dir_entries, const unsigned long long *__restrict__ rank, uint64_t max_out,
+                        uint64_t *__restrict__ out_dig, uint64_t *__restrict__ out_val, uint64_t *__restrict__ result)
+{
+    for (uint64_t idx = (uint64_t)blockIdx.x * kThreads + threadIdx.x; idx < dir_entries; idx += (uint64_t)gridDim.x * kThreads) {
+        const uint64_t k = rank[idx];
+        if (live[idx] == 0 || k >= max_out) continue;
+        out_val[k] = UINT64_MAX;
+        for (int w = 0; w < W; w++) out_dig[k * W + w] = 0;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        result[0] = rank[dir_entries];
+        result[1] = 0;
+    }
+}
+
+// One lane per slot, plain loads of the table as in the lookup.  A hit claims its rank with one 64-bit CAS CW_DEDUPE_MISS -> value
+// on out_val and only the claimant writes the digest: of two entries that carry the same flagged value, one digest is written whole.
+// The hits are counted whether they claim or not, per workgroup as the retain counts.
+template <int W>
+__global__ void __launch_bounds__(kThreads)
+dedupe_live_sweep_kernel(const uint64_t *__restrict__ state, const uint64_t *__restrict__ value, const uint64_t *__restrict__ key, uint64_t cap,
+                         const uint32_t *__restrict__ live, uint64_t dir_base, uint64_t dir_entries, const unsigned long long *__restrict__ rank,
+                         uint64_t max_out, uint64_t *__restrict__ out_dig, uint64_t *out_val, unsigned long long *__restrict__ n_hits)
+{
+    uint32_t mine = 0; // (a lane sees at most cap / (gridDim.x * kThreads) + 1 < 2^32 slots)
+    for (uint64_t o = (uint64_t)blockIdx.x * kThreads + threadIdx.x; o < cap; o += (uint64_t)gridDim.x * kThreads) {
+        if (state[o] != kCommitted) continue;
+        const uint64_t v = value[o], idx = v - dir_base;
+        if (idx >= dir_entries || live[idx] == 0) continue;
+        mine++;
+        const uint64_t k = rank[idx];
+        if (k >= max_out) continue;
+        uint64_t old = UINT64_MAX;
+        __hip_atomic_compare_exchange_strong(out_val + k, &old, v, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (old != UINT64_MAX) continue; // another entry with this value came first
+        for (int w = 0; w < W; w++) out_dig[k * W + w] = key[o * W + w];
+    }
+    __shared__ uint32_t whits[kThreads / 64];
+    for (int off = 32; off > 0; off >>= 1) mine += __shfl_down(mine, off, 64);
+    if ((threadIdx.x & 63u) == 0) whits[threadIdx.x >> 6] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t all = 0;
+        for (uint32_t w = 0; w < kThreads / 64; w++) all += whits[w];
+        if (all) __hip_atomic_fetch_add(n_hits, (unsigned long long)all, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 unsigned grid_of(uint32_t n) { return (n + kThreads - 1) / kThreads; }
 // grid-stride kernels over `tiles` tiles of kThreads slots
 unsigned grid_stride_of(uint64_t tiles) { return (unsigned)(tiles < (1u << 20) ? tiles : (1u << 20)); }
@@ -440,6 +503,30 @@ hipError_t dedupe_export_scatter_launch(unsigned words, const uint64_t *state, c
     case 8: hipLaunchKernelGGL(dedupe_export_scatter_kernel<8>, g, b, 0, s, state, value, key, cap, ntiles, off, first, max_out, out_dig, out_val, d_n, vec); break;
     default: return hipErrorInvalidValue;
     }
+    return hipGetLastError();
+}
+
+// flags[dir_entries] (u32) and rank[dir_entries + 1] are the caller's scratch; result[2] = {flagged entries, table entries with a flagged value}
+hipError_t dedupe_export_live_launch(unsigned words, const uint64_t *state, const uint64_t *value, const uint64_t *key, uint64_t cap,
+                                     const uint32_t *live, uint64_t dir_base, uint64_t dir_entries, uint32_t *flags, uint64_t *rank, uint64_t max_out,
+                                     uint64_t *out_dig, uint64_t *out_val, uint64_t *result, hipStream_t s)
+{
+    const dim3 g(grid_stride_of(dedupe_export_tiles(dir_entries))), gt(grid_stride_of(dedupe_export_tiles(cap))), b(kThreads);
+    hipLaunchKernelGGL(dedupe_live_flags_kernel, g, b, 0, s, live, dir_entries, flags);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || (e = pack_launch(nullptr, 0, flags, dir_entries, nullptr, rank, s)) != hipSuccess) return e;
+    const unsigned long long *r = reinterpret_cast<const unsigned long long *>(rank);
+    unsigned long long *hits = reinterpret_cast<unsigned long long *>(result + 1);
+#define CW_LIVE(W)                                                                                                                                \
+    hipLaunchKernelGGL(dedupe_live_fill_kernel<W>, g, b, 0, s, live, dir_entries, r, max_out, out_dig, out_val, result);                         \
+    hipLaunchKernelGGL(dedupe_live_sweep_kernel<W>, gt, b, 0, s, state, value, key, cap, live, dir_base, dir_entries, r, max_out, out_dig, out_val, hits)
+    switch (words) {
+    case 2: CW_LIVE(2); break;
+    case 4: CW_LIVE(4); break;
+    case 8: CW_LIVE(8); break;
+    default: return hipErrorInvalidValue;
+    }
+#undef CW_LIVE
     return hipGetLastError();
 }
 

@@ -392,6 +392,14 @@ class DedupeIndex:
         """The entries as parallel device arrays: *d_n = the entry count (u64), min(*d_n, max_out) pairs written."""
         check(lib().cw_dev_dedupe_export(self._x(), d_digests, d_values, max_out, d_n, stream))
 
+    def dev_export_live(self, d_live: int, dir_base: int, dir_entries: int, d_digests: int, d_values: int, max_out: int, d_result: int,
+                        stream: int = 0) -> None:
+        """The digests behind the directory entries d_live (u32[dir_entries]) flags, in ascending value: d_values[k] = dir_base + idx
+        of the k-th flagged idx with its digest, or ``MISS`` and a zero digest when the index has no entry with that value;
+        d_result = {flagged entries, index entries with a flagged value}; min(flagged, max_out) slots written.  The index is unchanged."""
+        check(lib().cw_dev_dedupe_export_live(self._x(), d_live, dir_base, dir_entries, d_digests or None, d_values or None, max_out, d_result,
+                                              stream))
+
     def resize(self, max_entries: int) -> None:
         """Rebuild the table for ``max_entries`` (synchronous; at least ``count()``).  Every lookup answers as before."""
         check(lib().cw_dedupe_resize(self._x(), max_entries))
@@ -703,6 +711,32 @@ def dev_store_compact(d_store: int, store_bytes: int, d_dir: int, dir_entries: i
                                      d_new_used, d_new_dir, d_result, stream))
 
 
+def dev_store_export_chunks(d_store: int, store_bytes: int, d_dir: int, dir_base: int, dir_entries: int, d_values: int, d_count: int,
+                            max_count: int, d_out: int, out_bytes: int, d_out_loc: int, d_result: int, stream: int = 0) -> None:
+    """The stored bytes of the entries d_values[k], k < min(*d_count, max_count), back to back into d_out with d_out_loc[k] = where.
+    d_result[0..3) = verdict (1: does not fit, 2: a position names no sound entry; nothing written then), total bytes, positions.
+    d_out = 0 with out_bytes = 0 is a dry run.  Not synchronised."""
+    check(lib().cw_dev_store_export_chunks(d_store or None, store_bytes, d_dir, dir_base, dir_entries, d_values, d_count, max_count,
+                                           d_out or None, out_bytes, d_out_loc, d_result, stream))
+
+
+def dev_store_import_chunks(d_in: int, in_bytes: int, d_in_loc: int, d_count: int, max_count: int, base: int, d_store: int, store_bytes: int,
+                            d_used: int, d_dir: int, dir_base: int, dir_entries: int, d_result: int, stream: int = 0, d_sel: int = 0,
+                            d_nsel: int = 0) -> None:
+    """``dev_store_chunks`` for chunks in stored form: the selected chunks k of a bundle (d_in, d_in_loc) go behind *d_used, chunk k
+    gets the entry d_dir[base + k - dir_base].  d_result[0] = 0, or 3 (a selected chunk is not in the bundle or its entry is
+    unsound) / 1 (does not fit) / 2 (an entry outside the directory) with nothing changed; d_result[1] = the bytes.  Not synchronised."""
+    check(lib().cw_dev_store_import_chunks(d_in or None, in_bytes, d_in_loc, d_count, max_count, d_sel or None, d_nsel or None, base,
+                                           d_store or None, store_bytes, d_used, d_dir, dir_base, dir_entries, d_result, stream))
+
+
+def dev_translate_refs(d_ref: int, d_count: int, max_count: int, d_from: int, d_to: int, d_npairs: int, max_pairs: int, d_out: int,
+                       d_n_missing: int, stream: int = 0) -> None:
+    """d_out[j] = d_to[k] where d_from[k] == d_ref[j] (d_from ascending), else ``MISS``; *d_n_missing (u64) += the misses.
+    d_out may be d_ref.  Not synchronised."""
+    check(lib().cw_dev_translate_refs(d_ref, d_count, max_count, d_from, d_to, d_npairs, max_pairs, d_out, d_n_missing, stream))
+
+
 class Store(C.Structure):
     """cw_store: the caller-owned triple of the chunk store (bytes, cursor, directory) as one argument."""
     _fields_ = [("d_store", C.c_void_p), ("store_bytes", C.c_size_t), ("d_used", C.c_void_p), ("d_dir", C.c_void_p),
@@ -763,6 +797,51 @@ class Recipe:
     @property
     def nbytes(self) -> int:
         return int(self.offsets[-1] - self.offsets[0])
+
+
+LOC_DTYPE = np.dtype([("pos", "<u8"), ("stored", "<u4"), ("raw", "<u4")])  # cw_chunk_loc as a numpy record
+_MISS = np.uint64(DedupeIndex.MISS)
+
+
+class Bundle:
+    """Chunks on their way from one ChunkStore to another, as plain host data.  The manifest lists the n
+    distinct chunks ``recipes`` name in ascending sender value: ``digests`` uint8[n, digest bytes], ``values`` uint64[n] (the
+    sender's), ``locs`` LOC_DTYPE[n] (where the chunk lies in ``payload``; all zero = listed, not carried).  ``payload`` uint8 holds
+    the carried chunks' stored bytes back to back, in the sender's stored form: sender and receiver share ``hash_alg`` and
+    ``comp_alg``."""
+
+    def __init__(self, digests, values, locs, payload, hash_alg, comp_alg, recipes):
+        self.hash_alg, self.comp_alg = _hash_id(hash_alg), _comp_id(comp_alg)
+        self.values = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1)
+        self.digests = np.ascontiguousarray(digests, dtype=np.uint8).reshape(len(self.values), digest_bytes(self.hash_alg))
+        self.locs = np.ascontiguousarray(locs, dtype=LOC_DTYPE).reshape(-1)
+        self.payload = np.ascontiguousarray(payload, dtype=np.uint8).reshape(-1)
+        self.recipes = list(recipes)
+        if len(self.locs) != len(self.values):
+            raise ValueError(f"{len(self.values)} values, {len(self.locs)} locs")
+
+    @property
+    def carried(self) -> np.ndarray:
+        """bool[n]: the chunks whose stored bytes the payload holds."""
+        return (self.locs["pos"] != 0) | (self.locs["stored"] != 0) | (self.locs["raw"] != 0)
+
+    def save(self, path) -> None:
+        """One ``.npz``: manifest, payload, the algorithm ids and the recipes (refs and offsets concatenated, with their lengths)."""
+        cat = lambda arrays: np.concatenate(arrays) if arrays else np.zeros(0, np.uint64)  # noqa: E731
+        with open(path, "wb") as f:
+            np.savez(f, hash_alg=np.int64(self.hash_alg), comp_alg=np.int64(self.comp_alg), digests=self.digests, values=self.values,
+                     locs=self.locs, payload=self.payload, recipe_lens=np.array([len(r.refs) for r in self.recipes], np.uint64),
+                     recipe_refs=cat([r.refs for r in self.recipes]), recipe_offsets=cat([r.offsets for r in self.recipes]))
+
+    @classmethod
+    def load(cls, path) -> "Bundle":
+        with np.load(path) as z:
+            lens, refs, offs = z["recipe_lens"].tolist(), z["recipe_refs"], z["recipe_offsets"]
+            recipes, a = [], 0
+            for i, k in enumerate(lens):
+                recipes.append(Recipe(refs[a:a + k], offs[a + i:a + i + k + 1]))
+                a += k
+            return cls(z["digests"], z["values"], z["locs"], z["payload"], int(z["hash_alg"]), int(z["comp_alg"]), recipes)
 
 
 class ChunkStore:
@@ -1020,6 +1099,169 @@ class ChunkStore:
         removed = self.index.retain(live.data_ptr(), self.dir_base, n)
         self.d_store, self.d_used, self.d_dir, self.store_bytes = new_store, new_used, new_dir, store_bytes
         return dict(kept=kept, dropped=dropped, bytes_before=bytes_before, bytes_after=needed, removed=removed)
+
+    def export_bundle(self, recipes, known=None) -> Bundle:
+        """The chunks ``recipes`` name as a Bundle: their digests and values in ascending value (``dev_store_mark`` of every recipe,
+        then ``dev_export_live``) and their stored bytes (``dev_store_export_chunks``, sized by a dry run).  ``known`` is a DedupeIndex
+        on this device, or a ChunkStore standing for its index, typically the receiver's: chunks it holds are listed in the manifest
+        but not carried.  Raises CwError (-2), the store untouched, when a recipe names a value outside the directory, when the
+        index and the store disagree about a named value, or when a named chunk's entry is damaged."""
+        import torch
+        recipes = list(recipes)
+        known = known.index if isinstance(known, ChunkStore) else known
+        if known is not None and known.hash_alg != self.index.hash_alg:
+            raise ValueError(f"known index hashes with algorithm {known.hash_alg}, this store with {self.index.hash_alg}")
+        s, n, db = self._stream(), self.dir_entries, digest_bytes(self.index.hash_alg)
+        z = lambda k, dt: torch.zeros(max(k, 1), dtype=dt, device="cuda")  # noqa: E731
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64).copy()).cuda()  # noqa: E731
+        live, n_out, res = z(n, torch.int32), z(1, torch.int64), z(3, torch.int64)
+        marks = [(up(r.refs), up([len(r.refs)]), len(r.refs)) for r in recipes if len(r.refs)]
+        torch.cuda.synchronize()  # (torch zeroed and copied on its own stream)
+        for d_ref, d_count, k in marks:
+            dev_store_mark(d_ref.data_ptr(), d_count.data_ptr(), k, self.dir_base, n, live.data_ptr(), n_out.data_ptr(), s)
+        torch.cuda.synchronize()
+        outside, flagged = int(n_out.item()), int(torch.count_nonzero(live).item())
+        if outside:
+            raise _lib.CwError(-2, f"chunk store: {outside} positions of the recipes name no entry of the directory [{self.dir_base}, "
+                                   f"{self.dir_base + n})")
+        dig, val = z(flagged * db, torch.uint8), z(flagged, torch.int64)
+        torch.cuda.synchronize()
+        self.index.dev_export_live(live.data_ptr(), self.dir_base, n, dig.data_ptr(), val.data_ptr(), flagged, res.data_ptr(), s)
+        torch.cuda.synchronize()
+        count, hits = (int(v) for v in res.cpu().numpy().view(np.uint64)[:2])
+        values = val.cpu().numpy().view(np.uint64)[:flagged]
+        if count != flagged or hits != flagged or (values == _MISS).any():
+            raise _lib.CwError(-2, f"chunk store: the recipes name {flagged} chunks, the index holds {hits} entries with their values "
+                                   f"({int((values == _MISS).sum())} values have none): store and index disagree")
+        carry = np.ones(flagged, bool)
+        if known is not None and flagged:
+            found, n_found = z(flagged, torch.int64), z(1, torch.int64)
+            torch.cuda.synchronize()
+            known.dev_lookup(dig.data_ptr(), flagged, found.data_ptr(), n_found.data_ptr(), s)
+            torch.cuda.synchronize()
+            carry = found.cpu().numpy().view(np.uint64)[:flagged] == _MISS
+        locs, payload, nc = np.zeros(flagged, LOC_DTYPE), np.zeros(0, np.uint8), int(carry.sum())
+        if nc:
+            d_val, d_count, d_loc = up(values[carry]), up([nc]), z(nc * 2, torch.int64)
+            torch.cuda.synchronize()
+
+            def run(d_out: int, out_bytes: int):
+                dev_store_export_chunks(self.d_store.data_ptr(), self.store_bytes, self.d_dir.data_ptr(), self.dir_base, n, d_val.data_ptr(),
+                                        d_count.data_ptr(), nc, d_out, out_bytes, d_loc.data_ptr(), res.data_ptr(), s)
+                torch.cuda.synchronize()
+                verdict, total = (int(v) for v in res.cpu().numpy().view(np.uint64)[:2])
+                if verdict == 2:
+                    raise _lib.CwError(-2, "chunk store: a named chunk's directory entry is damaged")
+                return verdict, total
+
+            _, total = run(0, 0)  # the dry run: verdict 1 with the bytes needed
+            out = z(total, torch.uint8)
+            torch.cuda.synchronize()
+            verdict, _ = run(out.data_ptr(), total)
+            if verdict:
+                raise _lib.CwError(-4, f"chunk store: the export of {total} bytes was refused with verdict {verdict} after its dry run")
+            locs[carry] = d_loc.cpu().numpy().view(LOC_DTYPE)[:nc]
+            payload = out.cpu().numpy()[:total]
+        return Bundle(dig.cpu().numpy()[:flagged * db], values, locs, payload, self.index.hash_alg, self.comp_alg, recipes)
+
+    def import_bundle(self, bundle: Bundle, verify: bool = True) -> list:
+        """Take a Bundle's chunks into this store and return its recipes in this store's values (offsets unchanged).  Chunks this
+        store's index already holds keep their value here; the others are appended in manifest order under the values ``base`` + k,
+        and ``base`` grows by the manifest's length.  Everything that can refuse comes before the index is touched, so a refusal
+        leaves index, store, directory and ``base`` as they were: ValueError when codec or hash algorithm differ; CwError (-2) when
+        the bundle lacks a chunk this store needs, when a needed chunk's place in the payload is unsound, when a recipe names a
+        value the manifest lacks or -- with ``verify`` -- when a carried chunk does not restore from the bundle or does not hash to
+        its manifest digest; CwError (-5) when the index, the directory or the store cannot take the new chunks."""
+        import torch
+        if bundle.comp_alg != self.comp_alg or bundle.hash_alg != self.index.hash_alg:
+            raise ValueError(f"bundle of codec {bundle.comp_alg} / hash {bundle.hash_alg}, store of codec {self.comp_alg} / hash "
+                             f"{self.index.hash_alg}")
+        n, s, db = len(bundle.values), self._stream(), digest_bytes(self.index.hash_alg)
+        if bundle.digests.shape != (n, db):
+            raise ValueError(f"{n} values need digests of shape ({n}, {db}), not {bundle.digests.shape}")
+        for r in bundle.recipes:
+            if not np.isin(r.refs, bundle.values).all():
+                raise _lib.CwError(-2, "chunk bundle: a recipe names a value the manifest lacks")
+        if n == 0:
+            return [Recipe(r.refs, r.offsets) for r in bundle.recipes]
+        z = lambda k, dt: torch.zeros(max(k, 1), dtype=dt, device="cuda")  # noqa: E731
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64).copy()).cuda()  # noqa: E731
+        raw = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()  # noqa: E731
+        in_bytes = len(bundle.payload)
+        d_dig, d_loc, d_in = raw(bundle.digests), raw(bundle.locs), raw(bundle.payload if in_bytes else np.zeros(1, np.uint8))
+        found, n_found = z(n, torch.int64), z(1, torch.int64)
+        torch.cuda.synchronize()
+        # 2. what this store lacks, read-only; every such chunk is carried, soundly, and there is room for all of them
+        self.index.dev_lookup(d_dig.data_ptr(), n, found.data_ptr(), n_found.data_ptr(), s)
+        torch.cuda.synchronize()
+        lacks, carried, locs = found.cpu().numpy().view(np.uint64) == _MISS, bundle.carried, bundle.locs
+        if (lacks & ~carried).any():
+            raise _lib.CwError(-2, f"chunk bundle: {int((lacks & ~carried).sum())} chunks this store lacks are listed but not carried")
+        pos, stored, word = locs["pos"], locs["stored"].astype(np.int64), locs["raw"].astype(np.int64)
+        length, is_raw = word & 0x1FFFF, (word & ChunkLoc.RAW) != 0
+        sound = ((word & ~(ChunkLoc.RAW | 0x1FFFF)) == 0) & (length >= 1) & (length <= 65536) & (stored != 0) & (~is_raw | (stored == length)) & \
+            (pos <= in_bytes) & (stored <= in_bytes - np.minimum(pos, np.uint64(in_bytes)).astype(np.int64))
+        if (lacks & ~sound).any():
+            raise _lib.CwError(-2, f"chunk bundle: chunk {int(np.nonzero(lacks & ~sound)[0][0])}'s place in the payload is unsound")
+        n_lacks, need, count, used = int(lacks.sum()), int(stored[lacks].sum()), self.index.count(), self.used()
+        if count + n_lacks > self.index.max_entries:
+            raise _lib.CwError(-5, f"chunk bundle: {count} entries + {n_lacks} new chunks > max_entries {self.index.max_entries}")
+        if self.base + n > self.dir_base + self.dir_entries:
+            raise _lib.CwError(-5, f"chunk bundle: values {self.base} .. {self.base + n} leave the directory [{self.dir_base}, "
+                                   f"{self.dir_base + self.dir_entries})")
+        if used + need > self.store_bytes:
+            err = _lib.CwError(-5, f"chunk bundle: {need} bytes do not fit behind {used} of {self.store_bytes}")
+            err.needed = need
+            raise err
+        # 3. the carried chunks restore from the bundle itself (the payload as the store, the locs as its directory) and hash to
+        # the manifest's digests
+        which = np.nonzero(carried)[0]
+        if verify and len(which):
+            if not sound[which].all():
+                raise _lib.CwError(-2, f"chunk bundle: chunk {int(which[~sound[which]][0])}'s place in the payload is unsound")
+            cuts = np.concatenate([[0], np.cumsum(length[which])]).astype(np.uint64)
+            k, total = len(which), int(cuts[-1])
+            d_ref, d_raw, d_count = up(which), up(cuts), up([k])
+            out, status, dig2 = z(total, torch.uint8), z(k, torch.int32), z(k * db, torch.uint8)
+            torch.cuda.synchronize()
+            dev_restore_chunks(self.comp_alg, d_in.data_ptr(), in_bytes, d_loc.data_ptr(), 0, n, d_ref.data_ptr(), d_raw.data_ptr(),
+                               d_count.data_ptr(), k, out.data_ptr(), total, status.data_ptr(), s)
+            dev_hash_chunks(self.index.hash_alg, out.data_ptr(), total, d_raw.data_ptr(), d_count.data_ptr(), k, dig2.data_ptr(), s)
+            torch.cuda.synchronize()
+            st = status.cpu().numpy()[:k]
+            if st.any():
+                j = int(np.nonzero(st)[0][0])
+                raise _lib.CwError(-2, f"chunk bundle: {int((st != 0).sum())} of {k} carried chunks do not restore; chunk {int(which[j])} has "
+                                       f"status {int(st[j])}")
+            bad = np.nonzero((dig2.cpu().numpy()[:k * db].reshape(k, db) != bundle.digests[which]).any(axis=1))[0]
+            if len(bad):
+                raise _lib.CwError(-2, f"chunk bundle: {len(bad)} carried chunks do not hash to their manifest digest; the first is chunk "
+                                       f"{int(which[bad[0]])}")
+        # 4. the index, the store, the recipes
+        ref, new_idx, n_new = z(n, torch.int64), z(n, torch.int32), z(1, torch.int64)
+        d_n, d_from, result, n_missing = up([n]), up(bundle.values), z(2, torch.int64), z(1, torch.int64)
+        outs = [(up(r.refs), up([len(r.refs)]), len(r.refs)) for r in bundle.recipes]
+        torch.cuda.synchronize()
+        self.index.dev_dedupe(d_dig.data_ptr(), n, self.base, ref.data_ptr(), new_idx.data_ptr(), n_new.data_ptr(), s)
+        dev_store_import_chunks(d_in.data_ptr(), in_bytes, d_loc.data_ptr(), d_n.data_ptr(), n, self.base, self.d_store.data_ptr(), self.store_bytes,
+                                self.d_used.data_ptr(), self.d_dir.data_ptr(), self.dir_base, self.dir_entries, result.data_ptr(), s,
+                                new_idx.data_ptr(), n_new.data_ptr())
+        for d_r, d_k, k in outs:
+            if k:
+                dev_translate_refs(d_r.data_ptr(), d_k.data_ptr(), k, d_from.data_ptr(), ref.data_ptr(), d_n.data_ptr(), n, d_r.data_ptr(),
+                                   n_missing.data_ptr(), s)
+        torch.cuda.synchronize()
+        verdict, total = (int(v) for v in result.cpu().numpy().view(np.uint64))
+        if verdict or int(n_missing.item()):
+            raise _lib.CwError(-4, f"chunk bundle: admitted, yet the append was refused with verdict {verdict} ({total} bytes) or "
+                                   f"{int(n_missing.item())} recipe positions found no value")
+        self.base += n
+        return [Recipe(d_r.cpu().numpy().view(np.uint64)[:k], r.offsets) for (d_r, _, k), r in zip(outs, bundle.recipes)]
+
+    def replicate_to(self, other: "ChunkStore", recipes, verify: bool = True) -> list:
+        """``other.import_bundle(self.export_bundle(recipes, known=other.index), verify)``: only the chunks ``other`` lacks travel, in
+        their stored form, and ``other`` gets recipes of its own for the same streams."""
+        return other.import_bundle(self.export_bundle(recipes, known=other.index), verify)
 
     def save(self, path) -> None:
         """One ``.npz``: the index's export, the store bytes [0, used), the directory, base and the parameters."""

@@ -242,6 +242,21 @@ int cw_dev_dedupe_insert(cw_dedupe_t *x, const void *d_digests, const uint64_t *
  * slots.                                                                                                              */
 int cw_dev_dedupe_export(cw_dedupe_t *x, void *d_digests, uint64_t *d_values, size_t max_out, uint64_t *d_n,
                          void *stream);
+/* From values to digests, for the entries of a chunk store's directory that d_live[dir_entries] (u32, cw_dev_store_mark's flags)
+ * marks: the export with a filter and an order.  With L = the number of idx < dir_entries with
+ * d_live[idx] != 0: the k-th such idx in ascending order gets d_values[k] = dir_base + idx and d_digests[k] = the digest the index
+ * stores with that value; when the index holds no entry with that value, d_values[k] = CW_DEDUPE_MISS and d_digests[k] is all zero.
+ * d_result[2] (u64) = {L, the number of index entries whose value is flagged}.  Exactly min(L, max_out) slots are written and
+ * nothing behind them (max_out == 0 just counts; the arrays may be NULL then).  Index entries whose value lies outside
+ * [dir_base, dir_base + dir_entries) are ignored.  Two entries may carry the same flagged value (cw_dev_dedupe_insert allows it):
+ * then one of their digests is written, whole, and d_result[1] > L; d_result[1] == L with no CW_DEDUPE_MISS among the values
+ * means the index and the flags agree one to one.  The index is unchanged, nothing is counted against max_entries (it works on
+ * a full index), and two calls on an unchanged index and d_live give the same bytes unless values repeat.  No load leaves
+ * d_live[0..dir_entries).  CW_ERR_BAD_ARG with nothing launched: a NULL pointer, a d_digests, d_values or d_result that is not
+ * 8-byte aligned, dir_entries == 0, dir_entries or max_out > 2^32 - 256, a wrong device.  A rank scan over the flags, a fill, one
+ * sweep of the table.  Scratch of the index: 12 B per directory entry.                                                          */
+int cw_dev_dedupe_export_live(cw_dedupe_t *x, const uint32_t *d_live, uint64_t dir_base, size_t dir_entries,
+                              void *d_digests, uint64_t *d_values, size_t max_out, uint64_t *d_result /* [2] */, void *stream);
 /* Host forms, synchronous, host buffers: staged through device buffers of the index in pieces of 2^20 pairs.
  * export: *n = the entry count, min(*n, max_out) pairs written.  import: cw_dev_dedupe_insert of the n pairs in order,
  * *n_inserted = how many were new; the whole n is admitted up front, CW_ERR_NOMEM (index unchanged) when
@@ -624,6 +639,57 @@ int cw_dev_store_compact(const void *d_store, size_t store_bytes, const cw_chunk
  * CW_ERR_NOMEM (index unchanged) when the new table cannot be allocated.  Old and new table are live at once during the call. */
 int cw_dedupe_retain(cw_dedupe_t *x, const uint32_t *d_live, uint64_t dir_base, size_t dir_entries,
                      size_t new_max_entries /* 0 = as it is */, uint64_t *n_removed);
+
+/* ---- chunk bundles: stored chunks from one store to another -------------------------------------------
+ * A bundle is a manifest and a payload.  The manifest lists the n distinct chunks a set of recipes names, in ascending value of
+ * the sending store: digest[k], value[k] and loc[k] (a cw_chunk_loc whose pos is relative to the payload; all zero = listed but
+ * not carried).  The payload holds the carried chunks' stored bytes back to back.  Stored form is the store's own (compressed, or
+ * raw with CW_CHUNK_RAW): nothing on the path decodes or encodes, so sender and receiver agree on codec and hash algorithm.
+ * The manifest comes from cw_dev_store_mark + cw_dev_dedupe_export_live, the payload from cw_dev_store_export_chunks; the receiver
+ * runs cw_dev_dedupe over the manifest's digests, cw_dev_store_import_chunks with that call's selection, and
+ * cw_dev_translate_refs over every recipe.  The calls follow the store's conventions: device pointers, counts read on the device,
+ * queued on `stream`, nothing synchronises, every decision made on the device and all or nothing.                               */
+/* Takes stored chunks out by value.  n = min(*d_count, max_count); position k < n names the directory entry of value d_values[k],
+ * which must exist and be sound by cw_dev_store_compact's entry checks.  The entries' stored bytes go to d_out back to back in
+ * position order, d_out_loc[k] = {pos in d_out, stored, raw word}.  d_result[3] = {verdict, the total bytes, n}: verdict 2 when a
+ * position names no entry of the directory (CW_DEDUPE_MISS does), an all-zero entry or an unsound one -- the total then counts
+ * the other positions; else 1 when the total > out_bytes; else 0.  With a verdict other than 0 no byte of d_out and no
+ * d_out_loc changes: out_bytes == 0 with d_out == NULL is a dry run that reports the room needed.  A value named twice is
+ * exported twice.  No load leaves d_store[0..store_bytes), d_dir[0..dir_entries) or d_values[0..n), whatever they hold.
+ * CW_ERR_BAD_ARG before anything is launched: a NULL pointer (d_store when store_bytes is 0 and d_out when out_bytes is 0 may
+ * be), max_count > 2^32 - 256, dir_entries == 0, a d_dir or d_out_loc that is not 16-byte aligned, a d_values, d_count or
+ * d_result that is not 8-byte aligned, [d_out, +out_bytes) overlapping [d_store, +store_bytes).  Scratch, per stream:
+ * 72 + 12 * max_count bytes.                                                                                                   */
+int cw_dev_store_export_chunks(const void *d_store, size_t store_bytes, const cw_chunk_loc *d_dir, uint64_t dir_base,
+                               size_t dir_entries, const uint64_t *d_values, const uint64_t *d_count, size_t max_count,
+                               void *d_out, size_t out_bytes, cw_chunk_loc *d_out_loc, uint64_t *d_result /* [3] */, void *stream);
+/* cw_dev_store_chunks for chunks that arrive in stored form: a bundle of n = min(*d_count, max_count) chunks, d_in_loc[k]
+ * pointing into d_in[0..in_bytes).  d_sel / d_nsel select as cw_dev_store_chunks' do (cw_dev_dedupe's d_new_idx / d_n_new over
+ * the manifest's digests; NULL / NULL = every chunk; at most max_count positions).  Selected position j names chunk k = d_sel[j]:
+ * its bytes d_in[loc.pos .. + loc.stored) are appended at *d_used + the stored bytes of the selected positions before it,
+ * d_dir[base + k - dir_base] = {new pos, stored, raw word}, then *d_used grows by the total.  d_result[2] = {verdict, the total}:
+ * verdict 3 when a selected k >= n or a selected entry is all zero, unsound by cw_dev_store_compact's checks or leaves in_bytes
+ * (the total then counts the other positions); else 1 when *d_used + total > store_bytes; else 2 when a selected base + k leaves
+ * [dir_base, dir_base + dir_entries) or wraps; else 0.  With a verdict other than 0, no store byte, no directory entry and not
+ * *d_used change.  Two positions naming one chunk store it twice; either entry stays.  No load leaves d_in[0..in_bytes),
+ * d_in_loc[0..n) or the selection.  CW_ERR_BAD_ARG before anything is launched: a NULL pointer (d_sel and d_nsel may be NULL
+ * together; d_in when in_bytes is 0; d_store when store_bytes is 0), max_count > 2^32 - 256, dir_entries == 0, a d_in_loc or d_dir
+ * that is not 16-byte aligned, a d_count, d_nsel, d_used or d_result that is not 8-byte aligned, [d_in, +in_bytes) overlapping
+ * [d_store, +store_bytes).  Scratch, per stream: 72 + 12 * max_count bytes.                                                    */
+int cw_dev_store_import_chunks(const void *d_in, size_t in_bytes, const cw_chunk_loc *d_in_loc, const uint64_t *d_count,
+                               size_t max_count, const uint32_t *d_sel, const uint64_t *d_nsel, uint64_t base,
+                               void *d_store, size_t store_bytes, uint64_t *d_used,
+                               cw_chunk_loc *d_dir, uint64_t dir_base, size_t dir_entries, uint64_t *d_result /* [2] */, void *stream);
+/* Rewrites a recipe from one store's values to another's.  d_from[0..p), p = min(*d_npairs, max_pairs), is ascending (what
+ * cw_dev_dedupe_export_live writes when the index holds every flagged value); for each position j < min(*d_count, max_count) a binary search of
+ * d_ref[j] in d_from: a hit at k gives d_out[j] = d_to[k], any other position gives CW_DEDUPE_MISS and is counted:
+ * *d_n_missing (u64) += their number, so several calls accumulate as cw_dev_store_mark's counter does.  d_out may be d_ref.  With
+ * d_to = the d_ref cw_dev_dedupe wrote for the manifest's digests, the sender's recipe becomes the receiver's.  CW_ERR_BAD_ARG
+ * before anything is launched: a NULL pointer, a pointer that is not 8-byte aligned, max_count or max_pairs > 2^32 - 256.
+ * No scratch.                                                                                                                  */
+int cw_dev_translate_refs(const uint64_t *d_ref, const uint64_t *d_count, size_t max_count,
+                          const uint64_t *d_from, const uint64_t *d_to, const uint64_t *d_npairs, size_t max_pairs,
+                          uint64_t *d_out, uint64_t *d_n_missing, void *stream);
 
 /* plain device memory on the calling thread's device, for C callers of cw_dev_* (the host programs link no HIP runtime) */
 void *cw_dev_alloc(size_t bytes);                                   /* NULL on failure */
