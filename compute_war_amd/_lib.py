@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "cw_dev_store_mark", "cw_dev_store_compact", "cw_dedupe_retain",
     "cw_store_ingest", "cw_dev_ingest_commit", "cw_store_restore",
     "cw_dev_cdc_streams", "cw_dev_cdc_streams_dedupe_compress",
+    "cw_dev_cdc_streams_part", "cw_dev_cdc_streams_part_dedupe_compress", "cw_dev_ingest_commit_streams", "cw_store_ingest_streams",
     "cw_dev_dedupe_export_live", "cw_dev_store_export_chunks", "cw_dev_store_import_chunks", "cw_dev_translate_refs",
     "cw_shard_range", "cw_mgpu_create", "cw_mgpu_destroy", "cw_mgpu_ndev", "cw_mgpu_device", "cw_mgpu_last_error", "cw_mgpu_gather",
 ]
@@ -164,6 +165,12 @@ def lib() -> C.CDLL:
         "cw_dev_cdc_streams": ([vp, vp, sz, vp, sz, vp, sz, vp, vp, vp, vp], C.c_int),
         "cw_dev_cdc_streams_dedupe_compress": ([vp, vp, C.c_int, vp, sz, vp, sz, C.c_uint64, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, sz, u32p, vp,
                                                vp], C.c_int),
+        "cw_dev_cdc_streams_part": ([vp, vp, sz, vp, sz, C.c_int, vp, sz, vp, vp, vp, vp], C.c_int),
+        "cw_dev_cdc_streams_part_dedupe_compress": ([vp, vp, C.c_int, vp, sz, vp, sz, C.c_int, C.c_uint64, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, sz,
+                                                    u32p, vp, vp], C.c_int),
+        "cw_dev_ingest_commit_streams": ([vp, vp, vp, sz, vp, vp, C.c_uint64, vp, vp, vp, sz, vp, vp, vp, sz, C.c_uint64, C.c_int, vp, sz, vp],
+                                         C.c_int),
+        "cw_store_ingest_streams": ([vp, vp, C.c_int, vp, vp, vp, sz, C.c_uint64, vp, vp, sz, vp, vp, vp, vp, vp], C.c_int),
         "cw_dev_dedupe_export_live": ([vp, u32p, C.c_uint64, sz, vp, vp, sz, vp, vp], C.c_int),
         "cw_dev_store_export_chunks": ([vp, sz, vp, C.c_uint64, sz, vp, vp, sz, vp, sz, vp, vp, vp], C.c_int),
         "cw_dev_store_import_chunks": ([vp, sz, vp, vp, sz, u32p, vp, C.c_uint64, vp, sz, vp, vp, C.c_uint64, sz, vp, vp], C.c_int),

@@ -219,7 +219,7 @@ size_t cdc_streams_workspace_bytes(size_t nbytes, size_t nstreams, uint32_t min_
 }
 
 namespace {
-// the launches of both forms: st == nullptr is cw_dev_cdc, else final_ is 1 and nbytes > 0
+// the launches of both forms: st == nullptr is cw_dev_cdc, else final_ is st's and nbytes > 0
 hipError_t cdc_launch_any(const CdcParams &p, const uint8_t *src, size_t nbytes, int final_, uint64_t *offsets, size_t max_offsets,
                           uint64_t *nchunks, uint64_t seg, const CdcStreams *st, hipStream_t stream)
 {
@@ -305,7 +305,7 @@ hipError_t cdc_launch(const CdcParams &p, const uint8_t *src, size_t nbytes, int
 hipError_t cdc_streams_launch(const CdcParams &p, const uint8_t *src, size_t nbytes, const CdcStreams &st, uint64_t *offsets, size_t max_offsets,
                               uint64_t *nchunks, uint64_t seg, hipStream_t stream)
 {
-    if (nbytes) return cdc_launch_any(p, src, nbytes, 1, offsets, max_offsets, nchunks, seg, &st, stream);
+    if (nbytes) return cdc_launch_any(p, src, nbytes, st.final_ ? 1 : 0, offsets, max_offsets, nchunks, seg, &st, stream);
     // no byte, no chunk: the verdict (streams that are all empty) and the empty result
     return cdc_streams_verdict_launch(st, 0, seg, 1, nullptr, offsets, nchunks, stream);
 }

@@ -111,7 +111,18 @@ __device__ uint64_t first_bit(const Cdc &c, int map, uint64_t lo, uint64_t hi)
     return p < qhi ? p - c.off : hi;
 }
 
-__device__ __forceinline__ bool terminal(const Cdc &c, uint64_t cut) { return c.final_ ? cut == c.n : cut + c.M > c.n; }
+// Where a chain stops.  One stream: at n (final), else at the first cut that leaves less than max_size.  Streams: the complete ones are
+// chunked to their ends whatever is left behind them, so only a cut at or behind the start of the last stream can stop short of n, and
+// only when that stream is open (final_ == 0: cw_dev_cdc_streams_part).  The start is read where a cut first leaves less than max_size.
+template <class C> __device__ __forceinline__ bool terminal(const C &c, uint64_t cut)
+{
+    if constexpr (!C::kStreams) {
+        return c.final_ ? cut == c.n : cut + c.M > c.n;
+    } else {
+        if (cut + c.M <= c.n) return false;
+        return c.final_ ? cut == c.n : cut >= (c.nstreams > 1 ? c.ends[c.nstreams - 2] : 0);
+    }
+}
 
 // the end a step from the non-terminal `cut` sees: the stream's, or (streams) the smallest end above cut, which lies among the ends of
 // cut's segment or is the first one behind them; the last end is n > cut

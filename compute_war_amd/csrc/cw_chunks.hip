@@ -74,7 +74,7 @@ int cw::host::dev_cdc_streams(const cw::CdcParams &p, const uint8_t *d_src, size
 {
     const uint64_t seg = cw::cdc_segment_bytes(p.max_size, cw::knobs().cdc_segment);
     ProfScope prof(PROF_HASH, s);
-    const cw::CdcStreams st{sl.d_ends, sl.nstreams, sl.d_first, sl.d_result};
+    const cw::CdcStreams st{sl.d_ends, sl.nstreams, sl.d_first, sl.d_result, sl.final_};
     hipError_t e = cw::cdc_streams_launch(p, d_src, nbytes, st, d_offsets, max_offsets, d_nchunks, seg, s);
     if (e == hipErrorOutOfMemory)
         return fail(CW_ERR_NOMEM, "cdc workspace (%zu bytes): %s", cw::cdc_streams_workspace_bytes(nbytes, sl.nstreams, p.min_size, seg),
@@ -163,10 +163,16 @@ int cw_dev_cdc(const cw_cdc_params *p, const void *d_src, size_t nbytes, int fin
 int cw_dev_cdc_streams(const cw_cdc_params *p, const void *d_src, size_t nbytes, const uint64_t *d_ends, size_t nstreams, uint64_t *d_offsets,
                        size_t max_offsets, uint64_t *d_nchunks, uint64_t *d_stream_first, uint64_t *d_result, void *stream)
 {
+    return cw_dev_cdc_streams_part(p, d_src, nbytes, d_ends, nstreams, 1, d_offsets, max_offsets, d_nchunks, d_stream_first, d_result, stream);
+}
+
+int cw_dev_cdc_streams_part(const cw_cdc_params *p, const void *d_src, size_t nbytes, const uint64_t *d_ends, size_t nstreams, int final,
+                            uint64_t *d_offsets, size_t max_offsets, uint64_t *d_nchunks, uint64_t *d_stream_first, uint64_t *d_result, void *stream)
+{
     cw::CdcParams cp;
     int rc = cdc_params(p, &cp);
     if (rc != CW_OK) return rc;
-    const StreamList sl{d_ends, nstreams, d_stream_first, d_result};
+    const StreamList sl{d_ends, nstreams, d_stream_first, d_result, final ? 1 : 0};
     if ((rc = cdc_streams_args(cp, d_src, nbytes, sl, d_offsets, max_offsets, d_nchunks)) != CW_OK) return rc;
     if ((rc = ensure_init()) != CW_OK) return rc;
     return dev_cdc_streams(cp, (const uint8_t *)d_src, nbytes, sl, d_offsets, max_offsets, d_nchunks, (hipStream_t)stream);

@@ -538,10 +538,12 @@ int cw::host::dev_cdc_dedupe_compress(cw_dedupe_t *x, const cw_cdc_params *p, in
             HIP_TRY(hipMemcpyAsync(h_counts, hook->d_counts, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         } else {
             HIP_TRY(hipMemcpyAsync(h_counts, d_nchunks, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-            if (streams) HIP_TRY(hipMemcpyAsync(h_counts + 1, streams->d_result, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         }
+        // the verdict on d_ends has a word of its own: with a hook, h_counts[1] is the bytes consumed
+        uint64_t *h_ends_verdict = h_counts + (hook ? 4 : 1);
+        if (streams) HIP_TRY(hipMemcpyAsync(h_ends_verdict, streams->d_result, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        if (streams && h_counts[1]) return fail(CW_ERR_BAD_ARG, "d_ends decreases or does not end at nbytes = %zu", nbytes);
+        if (streams && *h_ends_verdict) return fail(CW_ERR_BAD_ARG, "d_ends decreases or does not end at nbytes = %zu", nbytes);
         const size_t k = (size_t)h_counts[0];
         *nchunks = k;
         if (hook && (rc = hook->admit(hook->self, k, h_counts)) != CW_OK) return rc;
@@ -574,6 +576,17 @@ extern "C" int cw_dev_cdc_streams_dedupe_compress(cw_dedupe_t *x, const cw_cdc_p
                                                   uint32_t *d_sizes, size_t *nchunks, void *stream)
 {
     const StreamList sl{d_ends, nstreams, d_stream_first, d_result};
+    return dev_cdc_dedupe_compress(x, p, comp_alg, d_src, nbytes, 1, base, d_offsets, max_offsets, d_nchunks, d_digests, d_ref, d_new_idx, d_n_new,
+                                   d_dst, dst_bytes, d_sizes, nchunks, (hipStream_t)stream, nullptr, &sl);
+}
+
+extern "C" int cw_dev_cdc_streams_part_dedupe_compress(cw_dedupe_t *x, const cw_cdc_params *p, int comp_alg, const void *d_src, size_t nbytes,
+                                                       const uint64_t *d_ends, size_t nstreams, int final, uint64_t base, uint64_t *d_offsets,
+                                                       size_t max_offsets, uint64_t *d_nchunks, uint64_t *d_stream_first, uint64_t *d_result,
+                                                       void *d_digests, uint64_t *d_ref, uint32_t *d_new_idx, uint64_t *d_n_new, void *d_dst,
+                                                       size_t dst_bytes, uint32_t *d_sizes, size_t *nchunks, void *stream)
+{
+    const StreamList sl{d_ends, nstreams, d_stream_first, d_result, final ? 1 : 0};
     return dev_cdc_dedupe_compress(x, p, comp_alg, d_src, nbytes, 1, base, d_offsets, max_offsets, d_nchunks, d_digests, d_ref, d_new_idx, d_n_new,
                                    d_dst, dst_bytes, d_sizes, nchunks, (hipStream_t)stream, nullptr, &sl);
 }

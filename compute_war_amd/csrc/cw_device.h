@@ -137,7 +137,8 @@ hipError_t cdc_launch(const CdcParams &p, const uint8_t *src, size_t nbytes, int
                       uint64_t *nchunks, uint64_t seg, hipStream_t stream);
 // many streams in one buffer (cw_dev_cdc_streams): ends[nstreams], first[nstreams + 1] and *result on the device; at most
 // nbytes / min_size + nstreams + 1 offsets are written
-struct CdcStreams { const uint64_t *ends; size_t nstreams; uint64_t *first, *result; };
+// final_ = 0 (cw_dev_cdc_streams_part): the last stream is open and its chain stops where less than max_size is left
+struct CdcStreams { const uint64_t *ends; size_t nstreams; uint64_t *first, *result; int final_ = 1; };
 size_t cdc_streams_workspace_bytes(size_t nbytes, size_t nstreams, uint32_t min_size, uint64_t seg);
 hipError_t cdc_streams_launch(const CdcParams &p, const uint8_t *src, size_t nbytes, const CdcStreams &st, uint64_t *offsets, size_t max_offsets,
                               uint64_t *nchunks, uint64_t seg, hipStream_t stream);
@@ -242,6 +243,12 @@ hipError_t ingest_commit_launch(const uint64_t *ref, const uint64_t *offsets, co
                                 size_t rec_cap, uint64_t *stats, uint64_t *d_verdict, hipStream_t stream);
 hipError_t piece_counts_launch(const uint64_t *offsets, const uint64_t *d_nchunks, size_t max_chunks, const uint64_t *d_used,
                                const uint64_t *d_verdict, uint64_t *counts, hipStream_t stream);
+// the commit of a piece of many streams (commit_streams_kernels.hip; semantics: the public header's cw_dev_ingest_commit_streams)
+struct CommitStreams { const uint64_t *first; uint64_t nstreams, first_stream, skip_first; uint64_t *rec_first; uint64_t first_cap; };
+hipError_t ingest_commit_streams_launch(const uint64_t *ref, const uint64_t *offsets, const uint64_t *d_nchunks, size_t max_chunks,
+                                        const uint64_t *d_n_new, const uint64_t *store_result, uint64_t stream_off, uint64_t *rec_ref,
+                                        uint64_t *rec_off, uint64_t *d_rec_count, size_t rec_cap, uint64_t *stats, uint64_t *d_verdict,
+                                        const CommitStreams &cs, hipStream_t stream);
 // byte ranges of a restored stream (read_kernels.hip; semantics: the public header).  The recipe as chunk_restore_launch takes it
 hipError_t read_ranges_launch(int lzf, const uint8_t *store, size_t store_bytes, const void *dir, uint64_t dir_base, size_t dir_entries,
                               const uint64_t *ref, const uint64_t *raw_offsets, const uint64_t *d_count, size_t max_count,

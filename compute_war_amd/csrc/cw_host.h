@@ -75,6 +75,8 @@ struct StoreCtx {
     DevBuf src[2];                                   // ingest: a piece's carry + fresh bytes; restore: a window's bytes
     DevBuf off, dig, ref, new_idx, sizes, slots;     // ingest: one piece's lists and codec slots
     DevBuf rec_ref, rec_off, words;                  // ingest: the recipe as it grows; the counts, results and statistics
+    DevBuf ends, first, rec_first;                   // ingest of many streams: a piece's ends and stream index, the recipe's stream index
+    PinnedBuf h_ends;                                // the piece's ends on their way up
     DevBuf meta[2], status[2];                       // restore: a window's count | refs | offsets, and its statuses
     PinnedBuf stage[2], h_meta[2], h_status[2], h_words;
     hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr}; // upload into buffer b done; buffer b free again
@@ -101,7 +103,8 @@ int cdc_params(const cw_cdc_params *p, cw::CdcParams *out); // checked and with 
 int dev_cdc(const cw::CdcParams &p, const uint8_t *d_src, size_t nbytes, int final_, uint64_t *d_offsets, size_t max_offsets, uint64_t *d_nchunks,
             hipStream_t s);
 // the streams of cw_dev_cdc_streams: d_ends[nstreams], d_first[nstreams + 1] and *d_result on the device
-struct StreamList { const uint64_t *d_ends; size_t nstreams; uint64_t *d_first, *d_result; };
+// (final_ = 0: the last stream is open, cw_dev_cdc_streams_part)
+struct StreamList { const uint64_t *d_ends; size_t nstreams; uint64_t *d_first, *d_result; int final_ = 1; };
 // everything cw_dev_cdc_streams refuses behind its parameters, none of it needing a device
 int cdc_streams_args(const cw::CdcParams &cp, const void *d_src, size_t nbytes, const StreamList &sl, const uint64_t *d_offsets, size_t max_offsets,
                      const uint64_t *d_nchunks);
@@ -122,13 +125,14 @@ int dev_compress_chunks(int comp_alg, const uint8_t *d_src, size_t src_bytes, co
 // admission, before anything is inserted.  Whatever it returns other than CW_OK ends the call there.
 struct PieceAdmit {
     const uint64_t *d_used, *d_verdict;
-    uint64_t *d_counts, *h_counts; // [4]
+    uint64_t *d_counts, *h_counts; // d_counts[4]; h_counts[5]: with streams, [4] takes the verdict on d_ends
     int (*admit)(void *self, size_t k, const uint64_t *h_counts);
     void *self;
     bool *inserted; // set once the piece's chunks are queued for the index: a failure behind that point is no refusal
 };
 // cw_dev_cdc_dedupe_compress is this with hook == nullptr and streams == nullptr; cw_dev_cdc_streams_dedupe_compress gives `streams`
-// (the chunker is then cw_dev_cdc_streams, final_ is not read, and the verdict on d_ends comes back with the chunk count)
+// (the chunker is then cw_dev_cdc_streams_part with streams->final_, final_ is not read, and the verdict on d_ends comes back with the
+// chunk count, in a word of its own)
 int dev_cdc_dedupe_compress(cw_dedupe_t *x, const cw_cdc_params *p, int comp_alg, const void *d_src, size_t nbytes, int final_, uint64_t base,
                             uint64_t *d_offsets, size_t max_offsets, uint64_t *d_nchunks, void *d_digests, uint64_t *d_ref, uint32_t *d_new_idx,
                             uint64_t *d_n_new, void *d_dst, size_t dst_bytes, uint32_t *d_sizes, size_t *nchunks, hipStream_t s,

@@ -1,6 +1,9 @@
 // cw_ingest.hip -- the chunk store's host-buffer calls (semantics: the public header): cw_store_ingest streams a
 // host buffer of any size through the device in pieces, cw_store_restore streams a recipe back in windows, and cw_dev_ingest_commit is
-// the device step that assembles a recipe piece by piece (kernels: ingest_kernels.hip).
+// the device step that assembles a recipe piece by piece (kernels: ingest_kernels.hip).  cw_store_ingest_streams (section 21) is the
+// ingest over many host streams: the same pieces, buffers and events, each piece chunked by cw_dev_cdc_streams_part with the stream
+// ends that fall into it and committed by cw_dev_ingest_commit_streams (commit_streams_kernels.hip); a piece's ends are copied on the
+// kernel stream in front of its kernels, since their rebasing needs the carry.
 //
 // Ingest, piece i in buffer b = i & 1 (F = max_size rounded up to 256, P = the fresh bytes per piece):
 //     s_h2d    wait ev_done[b] (piece i-2 has left the buffer) | fresh bytes -> buf[b] + F | record ev_up[b]
@@ -44,6 +47,7 @@ void cw::host::StoreCtx::release()
     }
     off.release(); dig.release(); ref.release(); new_idx.release(); sizes.release(); slots.release();
     rec_ref.release(); rec_off.release(); words.release(); h_words.release();
+    ends.release(); first.release(); rec_first.release(); h_ends.release();
 }
 
 namespace {
@@ -52,7 +56,8 @@ const size_t kDefaultPiece = (size_t)256 << 20; // the fresh bytes per piece (CW
 const size_t kWindowPositions = (size_t)1 << 24; // positions per restore window at most (empty positions take no bytes)
 
 // u64 words of StoreCtx::words (device) and h_words (pinned)
-enum { W_NCHUNKS = 0, W_NNEW = 1, W_RESULT = 2, W_COUNTS = 4, W_VERDICT = 8, W_REC_COUNT = 9, W_STATS = 16, W_WORDS = 24 };
+// (W_COUNTS: four on the device, five on the host, where the fifth takes W_ENDS, the verdict on a piece's stream ends)
+enum { W_NCHUNKS = 0, W_NNEW = 1, W_RESULT = 2, W_COUNTS = 4, W_VERDICT = 9, W_REC_COUNT = 10, W_ENDS = 11, W_STATS = 16, W_WORDS = 24 };
 
 int check_store(const cw_store *st)
 {
@@ -162,6 +167,139 @@ struct Ingest {
     }
 };
 
+
+// cw_store_ingest_streams: Ingest over the concatenation of many spans.  A piece takes the stream ends not yet taken that lie at or
+// before its end; when the last of them is not the piece's end, the piece's own length is one more end and its last stream is open.
+struct IngestStreams {
+    cw_dedupe_t *x; const cw_cdc_params *p; int comp_alg; const cw_store *st;
+    const uint8_t *const *srcs; const uint64_t *lens; size_t nstreams; uint64_t total, base;
+    StoreCtx *c; hipStream_t s, s_h2d;
+    size_t piece, front, cap, slots_bytes, rec_cap, most; // as Ingest's; most = the largest stream count of a piece
+    size_t k_total = 0; uint64_t done = 0;            // chunks and bytes of the pieces that went in
+    size_t taken = 0; uint64_t taken_end = 0;         // the streams whose end a piece has taken, and the last of those ends
+    bool open = false;                                // the last piece that went in left its last stream open (its entry is written)
+    size_t up_f = 0; uint64_t up_at = 0;              // the upload's cursor: the span of the next fresh byte and the byte's place in it
+
+    size_t pieces() const { return (size_t)((total + piece - 1) / piece); }
+    uint64_t piece_end(size_t i) const { return total - i * piece < piece ? total : (uint64_t)(i + 1) * piece; }
+
+    // the largest stream count of any piece: the ends a piece takes do not depend on the carries
+    size_t most_streams() const
+    {
+        size_t f = 0, most_ = 1;
+        uint64_t cum = 0;
+        for (size_t i = 0, n = pieces(); i < n; i++) {
+            const uint64_t end = piece_end(i);
+            size_t t = 0;
+            while (f < nstreams && cum + lens[f] <= end) { cum += lens[f++]; t++; }
+            const size_t ns = t + (t && cum == end ? 0 : 1);
+            if (ns > most_) most_ = ns;
+        }
+        return most_;
+    }
+
+    int upload(size_t i)
+    {
+        const int b = (int)(i & 1);
+        const size_t take = (size_t)(piece_end(i) - (uint64_t)i * piece);
+        // the span parts behind the fresh bytes: in place when they lie back to back in page-locked memory
+        size_t f = up_f;
+        uint64_t at = up_at;
+        const uint8_t *first = nullptr, *next = nullptr;
+        bool in_place = true;
+        for (size_t left = take; left;) {
+            while (at == lens[f]) { f++; at = 0; }
+            const size_t n = lens[f] - at < left ? (size_t)(lens[f] - at) : left;
+            const uint8_t *q = srcs[f] + at;
+            if (!first) first = q;
+            else if (q != next) in_place = false;
+            if (in_place && at == 0 && !is_pinned(q)) in_place = false;
+            next = q + n; at += n; left -= n;
+        }
+        if (in_place && first && !is_pinned(first)) in_place = false; // (the first part may start inside its span)
+        const void *from = first;
+        if (!in_place) {
+            int rc = c->stage[b].reserve(piece);
+            if (rc != CW_OK) return rc;
+            if (i >= 2) HIP_TRY(hipEventSynchronize(c->ev_up[b])); // the staging buffer's last copy has left it
+            uint8_t *to = (uint8_t *)c->stage[b].p;
+            f = up_f; at = up_at;
+            for (size_t left = take; left;) {
+                while (at == lens[f]) { f++; at = 0; }
+                const size_t n = lens[f] - at < left ? (size_t)(lens[f] - at) : left;
+                memcpy(to, srcs[f] + at, n);
+                to += n; at += n; left -= n;
+            }
+            from = c->stage[b].p;
+        }
+        up_f = f; up_at = at;
+        if (i >= 2) HIP_TRY(hipStreamWaitEvent(s_h2d, c->ev_done[b], 0));
+        HIP_TRY(hipMemcpyAsync((uint8_t *)c->src[b].p + front, from, take, hipMemcpyHostToDevice, s_h2d));
+        HIP_TRY(hipEventRecord(c->ev_up[b], s_h2d));
+        return CW_OK;
+    }
+
+    // CW_OK with *refused set: the piece did not go in and nothing changed
+    int run(bool *refused)
+    {
+        uint64_t *w = (uint64_t *)c->words.p, *h = (uint64_t *)c->h_words.p, *h_ends = (uint64_t *)c->h_ends.p;
+        const size_t n = pieces();
+        size_t carry = 0;
+        int rc = upload(0);
+        for (size_t i = 0; rc == CW_OK && i < n; i++) {
+            const int b = (int)(i & 1);
+            if (i + 1 < n && (rc = upload(i + 1)) != CW_OK) return rc;
+            const uint64_t end = piece_end(i);
+            const size_t take = (size_t)(end - (uint64_t)i * piece), len = carry + take;
+            if (done + len != end) return fail(CW_ERR_STATE, "cw_store_ingest_streams: piece %zu does not start where the last one stopped", i);
+            // the piece's streams: the ends it takes, rebased to its origin (= done), and its own length when its last stream stays open
+            size_t t = 0;
+            uint64_t cum = taken_end;
+            while (taken + t < nstreams && cum + lens[taken + t] <= end) { cum += lens[taken + t]; h_ends[t++] = cum - done; }
+            const bool final_ = t && cum == end;
+            if (!final_) h_ends[t] = len;
+            const size_t ns = t + (final_ ? 0 : 1);
+            if (ns > most) return fail(CW_ERR_STATE, "cw_store_ingest_streams: %zu streams in a piece sized for %zu", ns, most);
+            HIP_TRY(hipMemcpyAsync(c->ends.p, h_ends, ns * 8, hipMemcpyHostToDevice, s)); // (the last piece's copy left h_ends before its synchronise)
+            uint8_t *d_piece = (uint8_t *)c->src[b].p + front - carry;
+            HIP_TRY(hipStreamWaitEvent(s, c->ev_up[b], 0));
+            Admission a{st, base + k_total};
+            bool inserted = false;
+            PieceAdmit hook{st->d_used, w + W_VERDICT, w + W_COUNTS, h + W_COUNTS, admit_piece, &a, &inserted};
+            const StreamList sl{(const uint64_t *)c->ends.p, ns, (uint64_t *)c->first.p, w + W_ENDS, final_ ? 1 : 0};
+            size_t k = 0;
+            rc = dev_cdc_dedupe_compress(x, p, comp_alg, d_piece, len, 1, a.base_k, (uint64_t *)c->off.p, cap, w + W_NCHUNKS, c->dig.p,
+                                         (uint64_t *)c->ref.p, (uint32_t *)c->new_idx.p, w + W_NNEW, c->slots.p, slots_bytes, (uint32_t *)c->sizes.p, &k,
+                                         s, &hook, &sl);
+            if (rc == CW_ERR_NOMEM && !inserted) { *refused = true; return CW_OK; }
+            if (rc == CW_ERR_NOMEM) return fail(CW_ERR_STATE, "cw_store_ingest_streams: device memory ran out behind an admitted piece");
+            if (rc == CW_ERR_BAD_ARG) return fail(CW_ERR_STATE, "cw_store_ingest_streams: the ends of piece %zu were refused", i);
+            if (rc != CW_OK) return rc;
+            rc = cw_dev_store_chunks(comp_alg, d_piece, len, (uint64_t *)c->off.p, w + W_NCHUNKS, cap - 1, (uint32_t *)c->new_idx.p, w + W_NNEW,
+                                     c->slots.p, (uint32_t *)c->sizes.p, a.base_k, st->d_store, st->store_bytes, st->d_used, st->d_dir, st->dir_base,
+                                     st->dir_entries, w + W_RESULT, s);
+            if (rc == CW_OK)
+                rc = cw_dev_ingest_commit_streams((uint64_t *)c->ref.p, (uint64_t *)c->off.p, w + W_NCHUNKS, cap - 1, w + W_NNEW, w + W_RESULT, done,
+                                                  (uint64_t *)c->rec_ref.p, (uint64_t *)c->rec_off.p, w + W_REC_COUNT, rec_cap, w + W_STATS,
+                                                  w + W_VERDICT, (const uint64_t *)c->first.p, ns, taken, open ? 1 : 0, (uint64_t *)c->rec_first.p,
+                                                  nstreams + 1, s);
+            if (rc != CW_OK) return rc == CW_ERR_NOMEM ? fail(CW_ERR_STATE, "cw_store_ingest_streams: no scratch behind an admitted piece") : rc;
+            const size_t consumed = (size_t)h[W_COUNTS + 1];
+            if (final_ && consumed != len) return fail(CW_ERR_STATE, "cw_store_ingest_streams: a closed piece of %zu bytes consumed %zu", len, consumed);
+            if (i + 1 < n) { // the bytes behind the last cut (< max_size) go in front of the next piece's fresh bytes
+                carry = len - consumed;
+                if (carry > front) return fail(CW_ERR_STATE, "cw_store_ingest_streams: a carry of %zu bytes", carry);
+                if (carry) HIP_TRY(hipMemcpyAsync((uint8_t *)c->src[b ^ 1].p + front - carry, d_piece + consumed, carry, hipMemcpyDeviceToDevice, s));
+            }
+            HIP_TRY(hipEventRecord(c->ev_done[b], s));
+            k_total += k;
+            done += consumed;
+            taken += t; taken_end = cum; open = !final_;
+        }
+        return rc;
+    }
+};
+
 } // namespace
 
 extern "C" {
@@ -248,6 +386,115 @@ int cw_store_ingest(cw_dedupe_t *x, const cw_cdc_params *p, int comp_alg, const 
     if (stats) memcpy(stats, h + W_STATS, 5 * sizeof(uint64_t));
     if (refused) return CW_ERR_NOMEM; // (the message is the admission's)
     return *consumed == nbytes ? CW_OK : fail(CW_ERR_STATE, "cw_store_ingest: %zu of %zu bytes went in", *consumed, nbytes);
+}
+
+int cw_dev_ingest_commit_streams(const uint64_t *d_ref, const uint64_t *d_offsets, const uint64_t *d_nchunks, size_t max_chunks,
+                                 const uint64_t *d_n_new, const uint64_t *d_store_result, uint64_t stream_off, uint64_t *d_rec_ref,
+                                 uint64_t *d_rec_off, uint64_t *d_rec_count, size_t rec_cap, uint64_t *d_stats, uint64_t *d_verdict,
+                                 const uint64_t *d_stream_first, size_t nstreams_piece, uint64_t first_stream, int skip_first,
+                                 uint64_t *d_rec_first, size_t first_cap, void *stream)
+{
+    int rc = check_count("max_chunks", max_chunks);
+    if (rc != CW_OK || (rc = check_count("nstreams_piece", nstreams_piece)) != CW_OK) return rc;
+    if (!d_ref || !d_offsets || !d_nchunks || !d_n_new || !d_rec_ref || !d_rec_off || !d_rec_count || !d_verdict || !d_stream_first || !d_rec_first)
+        return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    if (((uintptr_t)d_ref | (uintptr_t)d_offsets | (uintptr_t)d_nchunks | (uintptr_t)d_n_new | (uintptr_t)d_store_result | (uintptr_t)d_rec_ref |
+         (uintptr_t)d_rec_off | (uintptr_t)d_rec_count | (uintptr_t)d_stats | (uintptr_t)d_verdict | (uintptr_t)d_stream_first | (uintptr_t)d_rec_first) & 7)
+        return fail(CW_ERR_BAD_ARG, "a pointer is not 8-byte aligned");
+    if (skip_first != 0 && skip_first != 1) return fail(CW_ERR_BAD_ARG, "skip_first is %d, not 0 or 1", skip_first);
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    const cw::CommitStreams cs{d_stream_first, nstreams_piece, first_stream, (uint64_t)skip_first, d_rec_first, first_cap};
+    return launched(cw::ingest_commit_streams_launch(d_ref, d_offsets, d_nchunks, max_chunks, d_n_new, d_store_result, stream_off, d_rec_ref, d_rec_off,
+                                                     d_rec_count, rec_cap, d_stats, d_verdict, cs, (hipStream_t)stream),
+                    "ingest commit streams launch");
+}
+
+int cw_store_ingest_streams(cw_dedupe_t *x, const cw_cdc_params *p, int comp_alg, const cw_store *st, const void *const *srcs, const uint64_t *lens,
+                            size_t nstreams, uint64_t base, uint64_t *refs, uint64_t *offsets, size_t max_offsets, uint64_t *stream_first,
+                            size_t *nchunks, uint64_t *consumed, size_t *streams_done, cw_ingest_stats *stats)
+{
+    if (nchunks) *nchunks = 0;
+    if (consumed) *consumed = 0;
+    if (streams_done) *streams_done = 0;
+    if (stats) memset(stats, 0, sizeof *stats);
+    cw::CdcParams cp;
+    int rc = cdc_params(p, &cp);
+    if (rc != CW_OK || (rc = check_codec(comp_alg)) != CW_OK) return rc;
+    if (!x || !refs || !offsets || !stream_first || !nchunks || !consumed || !streams_done || (nstreams && (!srcs || !lens)))
+        return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    if (cp.max_size > CW_MAX_BLOCK_BYTES) return fail(CW_ERR_BAD_ARG, "max_size %u > %u: such a chunk cannot be stored", cp.max_size, CW_MAX_BLOCK_BYTES);
+    if ((rc = check_count("nstreams", nstreams)) != CW_OK) return rc;
+    uint64_t total = 0;
+    for (size_t f = 0; f < nstreams; f++) {
+        if (lens[f] && !srcs[f]) return fail(CW_ERR_BAD_ARG, "span %zu is NULL and %llu bytes long", f, (unsigned long long)lens[f]);
+        if (lens[f] > UINT64_MAX - total) return fail(CW_ERR_BAD_ARG, "the sum of lens wraps at span %zu", f);
+        total += lens[f];
+    }
+    if (max_offsets < total / cp.min_size + nstreams + 1)
+        return fail(CW_ERR_BAD_ARG, "max_offsets %zu < nbytes / min_size + nstreams + 1 = %llu", max_offsets,
+                    (unsigned long long)(total / cp.min_size + nstreams + 1));
+    if ((rc = check_store(st)) != CW_OK) return rc;
+    if (base > UINT64_MAX - (total / cp.min_size + nstreams)) return fail(CW_ERR_BAD_ARG, "base + nbytes / min_size + nstreams wraps");
+    IngestStreams g{x, p, comp_alg, st, (const uint8_t *const *)srcs, lens, nstreams, total, base};
+    hipStream_t s_d2h;
+    if ((rc = ctx_store(&g.c, &g.s, &g.s_h2d, &s_d2h)) != CW_OK) return rc;
+    offsets[0] = 0;
+    for (size_t f = 0; f <= nstreams; f++) stream_first[f] = 0;
+    *streams_done = nstreams;
+    if (total == 0) return CW_OK; // (no stream, or empty ones only: no chunk, no piece)
+    *streams_done = 0;
+
+    const long knob = cw::knobs().store_piece;
+    size_t piece = knob ? (size_t)knob : kDefaultPiece;
+    if (piece < cp.max_size) piece = cp.max_size;
+    if (piece > total) piece = total > cp.max_size ? (size_t)total : cp.max_size; // one piece: no more than it needs
+    g.piece = piece;
+    g.front = ((size_t)cp.max_size + 255) & ~(size_t)255;
+    g.most = g.most_streams();
+    g.cap = (cp.max_size + piece) / cp.min_size + g.most + 1;
+    g.slots_bytes = cw_chunk_slots_bytes(comp_alg, cp.max_size + piece, g.cap - 1);
+    g.rec_cap = (size_t)(total / cp.min_size) + nstreams + 1;
+    StoreCtx &c = *g.c;
+    const size_t two = g.pieces() > 1 ? 2 : 1;
+    for (size_t b = 0; b < two; b++)
+        if ((rc = c.src[b].reserve(g.front + piece + 16)) != CW_OK) return rc; // (+16: the scan loads whole granules)
+    if ((rc = c.off.reserve(g.cap * 8)) != CW_OK || (rc = c.dig.reserve(g.cap * 64)) != CW_OK || (rc = c.ref.reserve(g.cap * 8)) != CW_OK ||
+        (rc = c.new_idx.reserve(g.cap * 4)) != CW_OK || (rc = c.sizes.reserve(g.cap * 4)) != CW_OK || (rc = c.slots.reserve(g.slots_bytes)) != CW_OK ||
+        (rc = c.rec_ref.reserve(g.rec_cap * 8)) != CW_OK || (rc = c.rec_off.reserve(g.rec_cap * 8)) != CW_OK ||
+        (rc = c.ends.reserve(g.most * 8)) != CW_OK || (rc = c.first.reserve((g.most + 1) * 8)) != CW_OK || (rc = c.h_ends.reserve(g.most * 8)) != CW_OK ||
+        (rc = c.rec_first.reserve((nstreams + 1) * 8)) != CW_OK || (rc = c.words.reserve(W_WORDS * 8)) != CW_OK ||
+        (rc = c.h_words.reserve(W_WORDS * 8)) != CW_OK)
+        return rc;
+    HIP_TRY(hipMemsetAsync(c.words.p, 0, W_WORDS * 8, g.s));
+    HIP_TRY(hipMemsetAsync(c.rec_off.p, 0, 8, g.s));
+
+    bool refused = false;
+    rc = g.run(&refused);
+    uint64_t *h = (uint64_t *)c.h_words.p;
+    if (rc == CW_OK) {
+        const hipError_t e = hipMemcpyAsync(h + W_VERDICT, (uint64_t *)c.words.p + W_VERDICT, (W_WORDS - W_VERDICT) * 8, hipMemcpyDeviceToHost, g.s);
+        rc = launched(e, "cw_store_ingest_streams: the counts");
+    }
+    drain(g.s, g.s_h2d);
+    if (rc != CW_OK) return rc;
+    const size_t k = (size_t)h[W_REC_COUNT];
+    if (h[W_VERDICT] || k != g.k_total || k + 1 > max_offsets)
+        return fail(CW_ERR_STATE, "cw_store_ingest_streams: an admitted piece was not committed (verdict %llu, %zu of %zu chunks)",
+                    (unsigned long long)h[W_VERDICT], k, g.k_total);
+    if (k) HIP_TRY(hipMemcpy(refs, c.rec_ref.p, k * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(offsets, c.rec_off.p, (k + 1) * 8, hipMemcpyDeviceToHost));
+    // the stream index: the entries the pieces wrote, then the stream that was not begun (or the end) and the entry behind it
+    const size_t written = g.taken + (g.open ? 1 : 0);
+    if (written) HIP_TRY(hipMemcpy(stream_first, c.rec_first.p, written * 8, hipMemcpyDeviceToHost));
+    for (size_t f = written; f <= nstreams && f <= g.taken + 1; f++) stream_first[f] = k;
+    *nchunks = k;
+    *consumed = offsets[k];
+    *streams_done = g.taken;
+    if (stats) memcpy(stats, h + W_STATS, 5 * sizeof(uint64_t));
+    if (refused) return CW_ERR_NOMEM; // (the message is the admission's)
+    return *consumed == total && g.taken == nstreams ? CW_OK
+                                                     : fail(CW_ERR_STATE, "cw_store_ingest_streams: %llu of %llu bytes went in",
+                                                            (unsigned long long)*consumed, (unsigned long long)total);
 }
 
 int cw_store_restore(int comp_alg, const cw_store *st, const uint64_t *refs, const uint64_t *offsets, size_t nchunks, void *dst, size_t dst_bytes,

@@ -379,6 +379,23 @@ class DedupeIndex:
             raise err
         return int(k.value)
 
+    def dev_cdc_streams_part_dedupe_compress(self, params: "CdcParams", comp_alg, d_src: int, nbytes: int, d_ends: int, nstreams: int,
+                                             final: bool, base: int, d_offsets: int, max_offsets: int, d_nchunks: int, d_stream_first: int,
+                                             d_result: int, d_digests: int, d_ref: int, d_new_idx: int, d_n_new: int, d_dst: int,
+                                             dst_bytes: int, d_sizes: int, stream: int = 0) -> int:
+        """``dev_cdc_streams_dedupe_compress`` with ``dev_cdc_streams_part`` as its chunker (``final`` behind nstreams): with final =
+        False only the chunks in front of the bytes consumed are hashed, inserted and compressed.  Raises as that call does."""
+        k = C.c_size_t(0)
+        rc = lib().cw_dev_cdc_streams_part_dedupe_compress(self._x(), C.byref(params), _comp_id(comp_alg), d_src or None, nbytes, d_ends or None,
+                                                           nstreams, 1 if final else 0, base, d_offsets, max_offsets, d_nchunks, d_stream_first,
+                                                           d_result, d_digests, d_ref, d_new_idx, d_n_new, d_dst, dst_bytes, d_sizes,
+                                                           C.byref(k), stream)
+        if rc != 0:
+            err = _lib.CwError(rc, lib().cw_last_error().decode(errors="replace"))
+            err.nchunks = int(k.value)
+            raise err
+        return int(k.value)
+
     def dev_lookup(self, d_digests: int, n: int, d_ref: int, d_n_found: int, stream: int = 0) -> None:
         """Read-only: ref[i] = the stored value of digest i or ``MISS``; *d_n_found = hits (u64).  The index is unchanged."""
         check(lib().cw_dev_dedupe_lookup(self._x(), d_digests, n, d_ref, d_n_found, stream))
@@ -604,6 +621,15 @@ def dev_cdc_streams(params: CdcParams, d_src: int, nbytes: int, d_ends: int, nst
                                    d_stream_first, d_result, stream))
 
 
+def dev_cdc_streams_part(params: CdcParams, d_src: int, nbytes: int, d_ends: int, nstreams: int, final: bool, d_offsets: int, max_offsets: int,
+                         d_nchunks: int, d_stream_first: int, d_result: int, stream: int = 0) -> None:
+    """``dev_cdc_streams`` over a piece of a longer run: final = True is ``dev_cdc_streams``; final = False leaves the last stream
+    [ends[nstreams - 2], nbytes) open, cut as ``dev_cdc(final=False)`` cuts it alone: d_offsets[K] = the bytes consumed, and
+    d_stream_first[nstreams - 1] = K when nothing of the open stream was consumed.  Queued on `stream`, not synchronised."""
+    check(lib().cw_dev_cdc_streams_part(C.byref(params), d_src or None, nbytes, d_ends or None, nstreams, 1 if final else 0, d_offsets,
+                                        max_offsets, d_nchunks, d_stream_first, d_result, stream))
+
+
 def dev_hash_chunks(hash_alg, d_src: int, src_bytes: int, d_offsets: int, d_nchunks: int, max_chunks: int, d_digests: int,
                     stream: int = 0) -> None:
     """Digest of every chunk [offsets[i], offsets[i+1]) for i < min(*d_nchunks, max_chunks), at d_digests + i * digest size."""
@@ -785,6 +811,37 @@ def dev_ingest_commit(d_ref: int, d_offsets: int, d_nchunks: int, max_chunks: in
                                      d_rec_count, rec_cap, d_stats or None, d_verdict, stream))
 
 
+def dev_ingest_commit_streams(d_ref: int, d_offsets: int, d_nchunks: int, max_chunks: int, d_n_new: int, d_store_result: int, stream_off: int,
+                              d_rec_ref: int, d_rec_off: int, d_rec_count: int, rec_cap: int, d_stats: int, d_verdict: int, d_stream_first: int,
+                              nstreams_piece: int, first_stream: int, skip_first: bool, d_rec_first: int, first_cap: int, stream: int = 0) -> None:
+    """``dev_ingest_commit`` for a piece of many streams: also d_rec_first[first_stream + f] = the recipe's count before the call +
+    d_stream_first[f] for skip_first <= f < nstreams_piece; *d_verdict = 3 when first_stream + nstreams_piece > first_cap.  With any
+    verdict other than 0 nothing changes.  Not synchronised."""
+    check(lib().cw_dev_ingest_commit_streams(d_ref, d_offsets, d_nchunks, max_chunks, d_n_new, d_store_result or None, stream_off, d_rec_ref,
+                                             d_rec_off, d_rec_count, rec_cap, d_stats or None, d_verdict, d_stream_first, nstreams_piece,
+                                             first_stream, 1 if skip_first else 0, d_rec_first, first_cap, stream))
+
+
+def store_ingest_streams(index: "DedupeIndex", params: "CdcParams", comp_alg, store: Store, srcs, lens, base: int):
+    """cw_store_ingest_streams of the host spans at the addresses ``srcs`` with the lengths ``lens``: (rc, refs, offsets, stream_first,
+    consumed, streams_done, stats as a dict), in the coordinates of the spans' concatenation.  rc is 0, or -5 when a piece was refused:
+    everything then covers the pieces before it, and stream_first has streams_done + 2 entries (all of them when no stream is left).
+    Any other failure raises."""
+    lens = np.ascontiguousarray(lens, np.uint64).reshape(-1)
+    nf = len(lens)
+    ptrs = (C.c_void_p * max(nf, 1))(*[int(a) or None for a in srcs])
+    cap = params.max_offsets_streams(int(lens.sum(dtype=np.uint64)), nf)
+    refs, offs, first = np.zeros(cap, np.uint64), np.zeros(cap, np.uint64), np.zeros(nf + 1, np.uint64)
+    k, consumed, done, stats = C.c_size_t(0), C.c_uint64(0), C.c_size_t(0), IngestStats()
+    rc = lib().cw_store_ingest_streams(index._x(), C.byref(params), _comp_id(comp_alg), C.byref(store), ptrs if nf else None,
+                                       lens.ctypes.data if nf else None, nf, base, refs.ctypes.data, offs.ctypes.data, cap, first.ctypes.data,
+                                       C.byref(k), C.byref(consumed), C.byref(done), C.byref(stats))
+    if rc not in (0, -5):
+        check(rc)
+    k, done = int(k.value), int(done.value)
+    return rc, refs[:k].copy(), offs[:k + 1].copy(), first[:min(done + 2, nf + 1)].copy(), int(consumed.value), done, stats.as_dict()
+
+
 class Recipe:
     """What restores one ingested stream: refs[j] = the value of chunk j's first occurrence, offsets[0..k] = its cuts."""
 
@@ -851,7 +908,8 @@ class ChunkStore:
     chunk values count up from ``dir_base`` over the ingests.
     ``ingest`` is one device call: the whole buffer has to fit on the device next to its slots.  ``ingest_stream`` and
     ``restore_stream`` take and give host buffers of any size, streamed through the device in pieces (cw_store_ingest /
-    cw_store_restore); ``last_stats`` holds the last streamed ingest's statistics."""
+    cw_store_restore), ``ingest_many_stream`` and ``restore_many_stream`` many of them in one pipelined run; ``last_stats`` holds the
+    last streamed ingest's statistics."""
     last_stats = None
 
     def __init__(self, index: DedupeIndex, comp_alg, params: CdcParams, store_bytes: int, dir_entries: int, dir_base: int = 0):
@@ -967,6 +1025,42 @@ class ChunkStore:
             err.consumed, err.nchunks, err.recipe = consumed, len(refs), recipe
             raise err
         return recipe
+
+    def ingest_many_stream(self, datas) -> list:
+        """``ingest_many`` for host buffers of any number and total size, piece by piece as ``ingest_stream`` (cw_store_ingest_streams):
+        every buffer is chunked as if alone and may span pieces; the recipes, the store and the index are what ``ingest_many`` or a loop
+        of ``ingest`` leaves.  Buffers that lie back to back in page-locked memory are read in place.  When a piece is refused, raises
+        CwError (-5) with ``e.recipes`` (the complete streams), ``e.partial`` (the recipe of the stream that was cut, or None),
+        ``e.streams_done``, ``e.consumed`` and ``e.nchunks``; ``base`` has advanced by ``e.nchunks``.  Make room, then go on with the
+        buffers from ``e.streams_done``, the first shortened by ``e.partial.nbytes``."""
+        import torch
+        parts = [_np_u8(d) for d in datas]
+        torch.cuda.synchronize()
+        lens = np.array([a.size for a in parts], np.uint64)
+        rc, refs, offs, first, consumed, done, stats = store_ingest_streams(self.index, self.params, self.comp_alg, self._triple(),
+                                                                            [a.ctypes.data if a.size else 0 for a in parts], lens, self.base)
+        self.base += len(refs)
+        self.last_stats = stats
+        lo = first.tolist()
+        cut = lambda a, b: Recipe(refs[a:b], offs[a:b + 1] - offs[a]) if b > a else Recipe([], [0])  # noqa: E731
+        recipes = [cut(a, b) for a, b in zip(lo[:done], lo[1:done + 1])]
+        if rc:
+            err = _lib.CwError(rc, lib().cw_last_error().decode(errors="replace"))
+            err.recipes, err.streams_done, err.consumed, err.nchunks = recipes, done, consumed, len(refs)
+            err.partial = cut(lo[done], lo[done + 1]) if done + 1 < len(lo) and lo[done + 1] > lo[done] else None
+            raise err
+        return recipes
+
+    def restore_many_stream(self, recipes) -> list:
+        """``restore_stream`` of many recipes in one pipelined run: the recipes are joined into one with the offsets shifted, restored
+        by one cw_store_restore, and the bytes split again.  Raises as ``restore`` does."""
+        recipes = list(recipes)
+        sizes = [r.nbytes for r in recipes]
+        starts = np.concatenate([np.zeros(1, np.uint64), np.cumsum(sizes, dtype=np.uint64)])
+        refs = np.concatenate([r.refs for r in recipes]) if recipes else np.zeros(0, np.uint64)
+        offs = np.concatenate([np.zeros(1, np.uint64)] + [r.offsets[1:] - r.offsets[0] + starts[i] for i, r in enumerate(recipes)])
+        whole = self.restore_stream(Recipe(refs, offs))
+        return [whole[int(a):int(a) + n] for a, n in zip(starts[:-1], sizes)]
 
     def restore_stream(self, recipe: Recipe) -> bytes:
         """``restore`` into host memory, window by window with downloads beside the kernels.  Raises as ``restore`` does."""

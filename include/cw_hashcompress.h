@@ -323,7 +323,7 @@ int cw_cdc_hash(const cw_cdc_params *p, int hash_alg, const void *src, size_t nb
                 uint64_t *offsets, size_t max_offsets, size_t *nchunks, void *digests);
 /* Many streams in one device buffer, each cut as if alone.  Stream f is d_src[d_ends[f-1] .. d_ends[f]) with
  * d_ends[-1] = 0: d_ends[nstreams] (u64, device memory) is non-decreasing and its last entry is nbytes; equal neighbours are empty
- * streams; nstreams is a host count.  Every stream is complete: there is no final = 0 form.
+ * streams; nstreams is a host count.  Every stream is complete (an open last stream: cw_dev_cdc_streams_part).
  *   d_offsets[0..K]   the cuts of every non-empty stream as cw_dev_cdc(final = 1) over that stream alone gives them, shifted by the
  *                     stream's start, in order: strictly ascending, d_offsets[0] = 0, d_offsets[K] = nbytes.  An empty stream gives no
  *                     chunk.  *d_nchunks = K <= nbytes / min_size + nstreams (a stream of L bytes has at most L / min_size + 1 chunks).
@@ -345,6 +345,20 @@ int cw_cdc_hash(const cw_cdc_params *p, int hash_alg, const void *src, size_t nb
 int cw_dev_cdc_streams(const cw_cdc_params *p, const void *d_src, size_t nbytes, const uint64_t *d_ends, size_t nstreams,
                        uint64_t *d_offsets, size_t max_offsets, uint64_t *d_nchunks,
                        uint64_t *d_stream_first /* [nstreams + 1] */, uint64_t *d_result, void *stream);
+/* cw_dev_cdc_streams over a piece of a longer run of streams: the last stream may be open.  final = 1 is
+ * cw_dev_cdc_streams exactly: the same outputs byte for byte, the same refusals, the same verdict rule.  final = 0: streams
+ * 0 .. nstreams - 2 are complete and chunked to their ends; stream nstreams - 1 = [s, nbytes), s = d_ends[nstreams - 2] (0 when nstreams
+ * is 1), is the part seen so far of a stream that goes on, and its cuts are what cw_dev_cdc(final = 0) over d_src[s .. nbytes) alone
+ * gives, shifted by s: the chain stops at the first cut c >= s with c + max_size > nbytes.  A cut inside a complete stream is never
+ * terminal for that reason.  d_offsets[K] = the bytes consumed, at least s and less than max_size below nbytes; d_stream_first[nstreams]
+ * = K; d_stream_first[nstreams - 1] = the index of the open stream's first chunk, K when nothing of it was consumed.  The caller
+ * carries d_src[d_offsets[K] .. nbytes) in front of the next piece, whose stream 0 then continues the open stream: every cut is a
+ * restart point (cw_dev_cdc's final = 0 contract).  nstreams == 1 gives cw_dev_cdc(final = 0)'s cuts; nbytes == 0 gives K = 0.
+ * d_ends' last entry is nbytes in both forms.  The bound K <= nbytes / min_size + nstreams, the verdict on d_ends, the memory-safety
+ * sentence, CW_ERR_BAD_ARG and the scratch are those of cw_dev_cdc_streams.  Queued on `stream`, not synchronised.                 */
+int cw_dev_cdc_streams_part(const cw_cdc_params *p, const void *d_src, size_t nbytes, const uint64_t *d_ends, size_t nstreams, int final,
+                            uint64_t *d_offsets, size_t max_offsets, uint64_t *d_nchunks,
+                            uint64_t *d_stream_first /* [nstreams + 1] */, uint64_t *d_result, void *stream);
 
 /* ---- codecs over chunks ----------------------------------------------------------------------
  * The codec calls above take one block size per call; these take an offset list as cw_dev_cdc writes it, every chunk
@@ -427,6 +441,15 @@ int cw_dev_cdc_streams_dedupe_compress(cw_dedupe_t *x, const cw_cdc_params *p, i
                                        void *d_digests, uint64_t *d_ref, uint32_t *d_new_idx, uint64_t *d_n_new,
                                        void *d_dst, size_t dst_bytes, uint32_t *d_sizes,
                                        size_t *nchunks, void *stream);
+/* cw_dev_cdc_streams_dedupe_compress with cw_dev_cdc_streams_part as its chunker: `final` behind nstreams, everything else as there.
+ * final = 0: d_offsets[*nchunks] = the bytes consumed, and only the chunks in front of it are hashed, inserted and compressed.       */
+int cw_dev_cdc_streams_part_dedupe_compress(cw_dedupe_t *x, const cw_cdc_params *p, int comp_alg,
+                                            const void *d_src, size_t nbytes, const uint64_t *d_ends, size_t nstreams, int final,
+                                            uint64_t base, uint64_t *d_offsets, size_t max_offsets, uint64_t *d_nchunks,
+                                            uint64_t *d_stream_first, uint64_t *d_result,
+                                            void *d_digests, uint64_t *d_ref, uint32_t *d_new_idx, uint64_t *d_n_new,
+                                            void *d_dst, size_t dst_bytes, uint32_t *d_sizes,
+                                            size_t *nchunks, void *stream);
 
 /* ---- chunk store: keep the new chunks, restore deduplicated streams ---------------------------------
  * The read side of the dedupe path.  The library keeps no state: the CALLER owns three plain device buffers, and all three
@@ -583,6 +606,56 @@ int cw_dev_ingest_commit(const uint64_t *d_ref, const uint64_t *d_offsets, const
                          const uint64_t *d_n_new, const uint64_t *d_store_result /* may be NULL */, uint64_t stream_off,
                          uint64_t *d_rec_ref, uint64_t *d_rec_off, uint64_t *d_rec_count, size_t rec_cap,
                          uint64_t *d_stats /* [8], may be NULL */, uint64_t *d_verdict, void *stream);
+/* cw_dev_ingest_commit for a piece of many streams (cw_dev_cdc_streams_part): the same arguments, rules and verdicts, and the
+ * recipe's stream index on the device.  d_stream_first is the piece's own (d_stream_first[0..nstreams_piece) is read), first_stream
+ * the index, in the whole run, of the piece's stream 0, and skip_first (0 or 1) is 1 when the piece's stream 0 continues a stream
+ * whose entry an earlier piece wrote.  With c = *d_rec_count before the call: d_rec_first[first_stream + f] = c + d_stream_first[f]
+ * for skip_first <= f < nstreams_piece.  An open stream's entry is written by the piece in which the stream first appears, also when
+ * nothing of it was consumed: its first chunk is then the next piece's first.  The caller writes the entry behind the last stream
+ * when the run ends.  *d_verdict = 1 and 2 as cw_dev_ingest_commit, else 3 when first_stream + nstreams_piece > first_cap, else 0;
+ * when it is not 0 nothing changes.  Every count is read on the device, nothing synchronises, and no load or store leaves the arrays:
+ * cw_dev_ingest_commit's, d_stream_first[0..nstreams_piece) and d_rec_first[0..first_cap).  CW_ERR_BAD_ARG before anything is
+ * launched: what cw_dev_ingest_commit refuses, a NULL or misaligned d_stream_first or d_rec_first, nstreams_piece > 2^32 - 256, a
+ * skip_first other than 0 and 1.  No scratch.                                                                                     */
+int cw_dev_ingest_commit_streams(const uint64_t *d_ref, const uint64_t *d_offsets, const uint64_t *d_nchunks, size_t max_chunks,
+                                 const uint64_t *d_n_new, const uint64_t *d_store_result /* may be NULL */, uint64_t stream_off,
+                                 uint64_t *d_rec_ref, uint64_t *d_rec_off, uint64_t *d_rec_count, size_t rec_cap,
+                                 uint64_t *d_stats /* [8], may be NULL */, uint64_t *d_verdict,
+                                 const uint64_t *d_stream_first, size_t nstreams_piece, uint64_t first_stream, int skip_first,
+                                 uint64_t *d_rec_first, size_t first_cap, void *stream);
+/* cw_store_ingest for many host streams of any number and total size: stream f is srcs[f][0..lens[f]), every
+ * stream is cut as if alone, and a stream may span pieces.  Synchronous; host pointers except inside *st.
+ *   result        Coordinates are those of the concatenation of the spans.  refs, offsets, stream_first, the store bytes [0, *d_used),
+ *                 the directory and the index are byte for byte what ONE cw_dev_cdc_streams_dedupe_compress + cw_dev_store_chunks over
+ *                 the concatenation leaves, and what a loop of cw_store_ingest over the spans with base advancing leaves.  Chunk i of
+ *                 the whole run has value base + i; stream f's recipe is positions [stream_first[f], stream_first[f+1]) with the cuts
+ *                 rebased; stream_first[nstreams] = *nchunks.
+ *   pieces        The concatenation is cut as cw_store_ingest cuts one stream: CW_STORE_PIECE fresh bytes plus the carry in front.  A
+ *                 piece takes every stream end not yet taken that lies at or before its last byte's end, leading empty streams and
+ *                 repeated ends included.  When the last taken end is not the piece's end, the piece gets its own length as a further
+ *                 end and is chunked with final = 0 (cw_dev_cdc_streams_part), else with final = 1.  The piece's ends go to the device
+ *                 rebased to the piece's origin; a pass over lens before the first piece finds the largest stream count of any piece,
+ *                 which sizes the per-piece arrays: a piece's max_offsets is (max_size + piece) / min_size + streams_in_piece + 1.
+ *   source        The fresh bytes of a piece are read in place when every span that contributes to them is page-locked and the spans
+ *                 lie back to back in memory (srcs[f + 1] == srcs[f] + lens[f]); otherwise they are gathered into the two pinned
+ *                 staging buffers with one memcpy per span part.
+ *   admission     cw_store_ingest's, per piece, before anything is inserted.
+ *   refusal       CW_ERR_NOMEM: *nchunks, *consumed and *streams_done cover the pieces that went in; *streams_done = the number of
+ *                 streams whose end is at or below *consumed; stream_first[0 .. *streams_done] is valid and stream_first[*streams_done
+ *                 + 1] = *nchunks (the stream that was cut, if any, is positions [stream_first[*streams_done], *nchunks)).  Everything
+ *                 is what ingesting that prefix gives.  Resume with the spans from *streams_done on, the first shortened by what was
+ *                 consumed of it, and base + *nchunks: *consumed is a cut, so the cuts are the uninterrupted run's.
+ *   CW_ERR_BAD_ARG, before the device is touched: what cw_store_ingest refuses, a NULL srcs or lens with nstreams != 0, a NULL span
+ *                 with a non-zero length, a sum of lens that wraps, nstreams > 2^32 - 256, max_offsets < nbytes / min_size + nstreams
+ *                 + 1 (nbytes = the sum of lens).  nstreams == 0: CW_OK with nothing done.  stats->pieces counts pieces.
+ * Events and buffers are cw_store_ingest's, except that a piece's ends are copied on the kernel stream in front of its kernels: their
+ * rebasing needs the carry, which the previous piece's synchronise brings.  Scratch: cw_store_ingest's with c = (M + P) / m + S + 1
+ * for the largest stream count S of a piece, 16 bytes per S for the ends and the piece's stream index, 8 bytes per stream for the
+ * recipe's, and 16 bytes per nbytes / m + nstreams + 1 for the recipe.                                                             */
+int cw_store_ingest_streams(cw_dedupe_t *x, const cw_cdc_params *p, int comp_alg, const cw_store *st,
+                            const void *const *srcs, const uint64_t *lens, size_t nstreams, uint64_t base,
+                            uint64_t *refs, uint64_t *offsets, size_t max_offsets, uint64_t *stream_first /* [nstreams + 1] */,
+                            size_t *nchunks, uint64_t *consumed, size_t *streams_done, cw_ingest_stats *stats /* may be NULL */);
 /* Rebuilds the stream of a recipe into host memory: stream byte x goes to dst[x - offsets[0]].  Synchronous.  The recipe is cut into
  * windows of whole positions whose raw bytes fit a piece (CW_STORE_PIECE, raised to 65536); each window's offsets are rebased and
  * uploaded, cw_dev_restore_chunks writes into one of two device buffers, and a window's download runs beside the next window's
