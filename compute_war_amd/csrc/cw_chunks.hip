@@ -370,6 +370,26 @@ int cw_dev_store_import_chunks(const void *d_in, size_t in_bytes, const cw_chunk
                           "store import launch");
 }
 
+int cw_dev_store_replace_chunks(const void *d_in, size_t in_bytes, const cw_chunk_loc *d_in_loc, const uint64_t *d_values, const uint64_t *d_count,
+                                size_t max_count, void *d_store, size_t store_bytes, uint64_t *d_used, cw_chunk_loc *d_dir, uint64_t dir_base,
+                                size_t dir_entries, uint64_t *d_result, void *stream)
+{
+    int rc = check_count("max_count", max_count);
+    if (rc != CW_OK) return rc;
+    if (!d_in_loc || !d_values || !d_count || !d_used || !d_dir || !d_result || (in_bytes && !d_in) || (store_bytes && !d_store))
+        return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    if (dir_entries == 0) return fail(CW_ERR_BAD_ARG, "dir_entries is 0");
+    if ((rc = check_dir_aligned((uintptr_t)d_in_loc | (uintptr_t)d_dir, "d_in_loc / d_dir")) != CW_OK) return rc;
+    if ((rc = check_word_aligned((uintptr_t)d_values | (uintptr_t)d_count | (uintptr_t)d_used | (uintptr_t)d_result,
+                                 "d_values / d_count / d_used / d_result")) != CW_OK)
+        return rc;
+    if (ranges_overlap(d_in, in_bytes, d_store, store_bytes)) return fail(CW_ERR_BAD_ARG, "d_in overlaps d_store");
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    return launched_nomem(cw::store_replace_launch((const uint8_t *)d_in, in_bytes, d_in_loc, d_values, d_count, max_count, (uint8_t *)d_store,
+                                                   store_bytes, d_used, d_dir, dir_base, dir_entries, d_result, (hipStream_t)stream),
+                          "store replace launch");
+}
+
 int cw_dev_translate_refs(const uint64_t *d_ref, const uint64_t *d_count, size_t max_count, const uint64_t *d_from, const uint64_t *d_to,
                           const uint64_t *d_npairs, size_t max_pairs, uint64_t *d_out, uint64_t *d_n_missing, void *stream)
 {

@@ -326,6 +326,45 @@ int cw_dev_dedupe_export_live(cw_dedupe_t *x, const uint32_t *d_live, uint64_t d
     });
 }
 
+// One window of a scrub: the plan, the restore and the finish are scrub_kernels.hip's; between restore and finish the index judges --
+// the hash of the window's chunks, then one sweep of the table.  Read-only for the index, serialised with its other calls.
+int cw_dev_store_verify(cw_dedupe_t *x, int comp_alg, const void *d_store, size_t store_bytes, const cw_chunk_loc *d_dir, uint64_t dir_base,
+                        size_t dir_entries, const uint32_t *d_live, uint64_t *d_cursor, void *d_work, size_t work_bytes, uint32_t *d_status,
+                        uint64_t *d_totals, void *stream)
+{
+    int rc;
+    if (!x || !d_dir || !d_cursor || !d_work || !d_status || !d_totals || (store_bytes && !d_store))
+        return fail(CW_ERR_BAD_ARG, "NULL %s", x ? "pointer" : "dedupe index");
+    if ((rc = check_codec(comp_alg)) != CW_OK) return rc;
+    if (dir_entries == 0) return fail(CW_ERR_BAD_ARG, "dir_entries is 0");
+    if ((rc = check_count("dir_entries", dir_entries)) != CW_OK) return rc;
+    if (work_bytes < CW_MAX_BLOCK_BYTES) return fail(CW_ERR_BAD_ARG, "work_bytes %zu < %u", work_bytes, CW_MAX_BLOCK_BYTES);
+    if ((uintptr_t)d_dir % 16) return fail(CW_ERR_BAD_ARG, "d_dir is not 16-byte aligned");
+    if (((uintptr_t)d_cursor | (uintptr_t)d_totals) % 8) return fail(CW_ERR_BAD_ARG, "d_cursor / d_totals not 8-byte aligned");
+    if ((rc = dedupe_args(x, 0, 0)) != CW_OK) return rc;
+    const hipStream_t s = (hipStream_t)stream;
+    const size_t window = cw::store_verify_window(dir_entries, cw::knobs().scrub_entries);
+    return dedupe_on_stream(x, s, [&]() -> int {
+        struct Judge { cw_dedupe *x; uint8_t *work; size_t work_bytes; uint64_t dir_base; hipStream_t s; int rc; };
+        Judge j{x, (uint8_t *)d_work, work_bytes, dir_base, s, CW_OK};
+        const cw::ScrubJudge judge{[](void *ctx, const cw::ScrubWindow &w) {
+                                       Judge &j = *static_cast<Judge *>(ctx);
+                                       j.rc = dev_hash_chunks(j.x->hash_alg, j.work, j.work_bytes, w.raw_off, w.d_count, w.max_entries, w.digests, j.s);
+                                       if (j.rc != CW_OK) return hipErrorUnknown; // (the message is recorded)
+                                       const DedupeTable &t = j.x->t;
+                                       return cw::dedupe_verify_launch(j.x->words, t.state, t.value, t.key, j.x->cap, j.dir_base, w.head, w.decoded,
+                                                                       (const uint64_t *)w.digests, w.verdict, j.s);
+                                   },
+                                   &j};
+        const hipError_t e = cw::store_verify_launch(comp_alg == CW_COMP_LZF, (const uint8_t *)d_store, store_bytes, d_dir, dir_base, dir_entries, d_live,
+                                                     d_cursor, (uint8_t *)d_work, work_bytes, window, x->words * 8, d_status, d_totals, judge, s);
+        if (j.rc != CW_OK) return j.rc;
+        if (e == hipErrorOutOfMemory)
+            return fail(CW_ERR_NOMEM, "scrub scratch (%zu bytes): %s", cw::store_verify_scratch_bytes(window, x->words * 8), hipGetErrorString(e));
+        return launched(e, "store verify launch");
+    });
+}
+
 int cw_dedupe_export(cw_dedupe_t *x, void *digests, uint64_t *values, size_t max_out, size_t *n)
 {
     int rc = dedupe_args(x, 0, 0);

@@ -272,6 +272,32 @@ hipError_t store_import_launch(const uint8_t *in, size_t in_bytes, const void *i
                                void *dir, uint64_t dir_base, size_t dir_entries, uint64_t *result, hipStream_t stream);
 hipError_t translate_refs_launch(const uint64_t *ref, const uint64_t *d_count, size_t max_count, const uint64_t *from, const uint64_t *to,
                                  const uint64_t *d_npairs, size_t max_pairs, uint64_t *out, uint64_t *n_missing, hipStream_t stream);
+// cw_dev_store_replace_chunks: the import with the values given (position k carries values[k]) and no selection
+hipError_t store_replace_launch(const uint8_t *in, size_t in_bytes, const void *in_loc, const uint64_t *values, const uint64_t *d_count,
+                                size_t max_count, uint8_t *store, size_t store_bytes, uint64_t *d_used, void *dir, uint64_t dir_base,
+                                size_t dir_entries, uint64_t *result, hipStream_t stream);
+
+// one window of a scrub (scrub_kernels.hip; semantics: the public header's cw_dev_store_verify).  The window in the stream's scratch,
+// as the judge sees it behind the restore: head[0] = c, head[1] = e - c (= *d_count); raw_off[0 .. e - c] the decoded chunks' extents
+// in the work buffer; decoded[k] = the restore's status; verdict[k] = CW_SCRUB_ORPHAN for the entries that were decoded
+struct ScrubWindow {
+    const uint64_t *head, *raw_off, *d_count;
+    size_t max_entries;
+    const uint32_t *decoded;
+    uint8_t *digests;   // of the window's chunks, for the judge to fill
+    uint32_t *verdict;  // for the judge to lower
+};
+// queues the hash of the window's chunks and the sweep of the table that compares: called once, under the scratch's launch lock
+struct ScrubJudge { hipError_t (*fn)(void *ctx, const ScrubWindow &w); void *ctx; };
+size_t store_verify_window(size_t dir_entries, long knob); // W = min(CW_SCRUB_ENTRIES (default 2^20, at least 64), dir_entries)
+size_t store_verify_scratch_bytes(size_t window, unsigned digest_bytes);
+hipError_t store_verify_launch(int lzf, const uint8_t *store, size_t store_bytes, const void *dir, uint64_t dir_base, size_t dir_entries,
+                               const uint32_t *live, uint64_t *d_cursor, uint8_t *work, size_t work_bytes, size_t window, unsigned digest_bytes,
+                               uint32_t *status, uint64_t *totals, const ScrubJudge &judge, hipStream_t stream);
+// the table sweep of a scrub window (dedupe_kernels.hip): a committed slot whose value names a decoded entry of the window lowers
+// verdict[k] to 0 when its key is digests[k], else to 3
+hipError_t dedupe_verify_launch(unsigned words, const uint64_t *state, const uint64_t *value, const uint64_t *key, uint64_t cap, uint64_t dir_base,
+                                const uint64_t *head, const uint32_t *decoded, const uint64_t *digests, uint32_t *verdict, hipStream_t s);
 
 hipError_t sum_sizes_launch(const uint32_t *sizes, size_t n, uint32_t raw_bytes, uint64_t *totals, hipStream_t stream);
 hipError_t gen_random_launch(uint64_t seed, uint64_t first_block, size_t nblocks, size_t block_bytes, uint8_t *dst,

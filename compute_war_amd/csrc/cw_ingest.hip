@@ -585,4 +585,45 @@ int cw_store_restore(int comp_alg, const cw_store *st, const uint64_t *refs, con
     return rc;
 }
 
+// The whole directory through cw_dev_store_verify, window by window: the work buffer is the context's first
+// source buffer, cursor and totals are nine words of its first meta buffer, the statuses its first status buffer.  One synchronise per
+// window brings the cursor back; nothing else crosses the bus until the end.
+int cw_store_scrub(cw_dedupe_t *x, int comp_alg, const cw_store *st, const uint32_t *d_live, uint32_t *status, cw_scrub_stats *stats)
+{
+    int rc = check_codec(comp_alg);
+    if (rc != CW_OK || (rc = check_store(st)) != CW_OK) return rc;
+    if (!x) return fail(CW_ERR_BAD_ARG, "NULL dedupe index");
+    if ((rc = check_count("dir_entries", st->dir_entries)) != CW_OK) return rc;
+    const long knob = cw::knobs().store_piece;
+    size_t piece = knob ? (size_t)knob : kDefaultPiece;
+    if (piece < CW_MAX_BLOCK_BYTES) piece = CW_MAX_BLOCK_BYTES;
+    StoreCtx *cp;
+    hipStream_t s, s_h2d, s_d2h;
+    if ((rc = ctx_store(&cp, &s, &s_h2d, &s_d2h)) != CW_OK) return rc;
+    StoreCtx &c = *cp;
+    const size_t n = st->dir_entries;
+    if ((rc = c.src[0].reserve(piece)) != CW_OK || (rc = c.status[0].reserve(n * 4)) != CW_OK || (rc = c.meta[0].reserve(9 * 8)) != CW_OK) return rc;
+    uint64_t *d_words = (uint64_t *)c.meta[0].p, h_words[9] = {0}; // the cursor, then the totals
+    auto run = [&]() -> int {
+        HIP_TRY(hipMemsetAsync(d_words, 0, sizeof h_words, s));
+        for (uint64_t cursor = 0; cursor < n;) {
+            const int rc = cw_dev_store_verify(x, comp_alg, st->d_store, st->store_bytes, st->d_dir, st->dir_base, n, d_live, d_words, c.src[0].p, piece,
+                                               (uint32_t *)c.status[0].p, d_words + 1, s);
+            if (rc != CW_OK) return rc;
+            HIP_TRY(hipMemcpyAsync(h_words, d_words, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            if (h_words[0] <= cursor) return fail(CW_ERR_STATE, "cw_store_scrub: the cursor stays at %llu", (unsigned long long)cursor);
+            cursor = h_words[0];
+        }
+        HIP_TRY(hipMemcpyAsync(h_words, d_words, sizeof h_words, hipMemcpyDeviceToHost, s));
+        if (status) HIP_TRY(hipMemcpyAsync(status, c.status[0].p, n * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return CW_OK;
+    };
+    rc = run();
+    (void)hipStreamSynchronize(s);
+    if (rc == CW_OK && stats) memcpy(stats, h_words + 1, sizeof *stats);
+    return rc;
+}
+
 } // extern "C"

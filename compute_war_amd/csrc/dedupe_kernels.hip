@@ -410,6 +410,29 @@ dedupe_live_sweep_kernel(const uint64_t *__restrict__ state, const uint64_t *__r
     }
 }
 
+// ---- the compare of a scrub window (cw_dev_store_verify) ------------------------------------------------
+// One lane per slot, plain loads as above.  head = {c, n}: the window is the directory entries [c, c + n).  A committed slot whose
+// value names entry c + k of the window, decoded (decoded[k] == 0), compares its key with the digest computed from the stored bytes
+// and lowers verdict[k] -- ORPHAN (4) when the sweep starts -- with one atomic min: 0 on equality, else 3.  Of several slots that
+// carry one value, a match by any of them leaves 0 whatever the order.  The table is only read.
+template <int W>
+__global__ void __launch_bounds__(kThreads)
+dedupe_verify_sweep_kernel(const uint64_t *__restrict__ state, const uint64_t *__restrict__ value, const uint64_t *__restrict__ key, uint64_t cap,
+                           uint64_t dir_base, const uint64_t *__restrict__ head, const uint32_t *__restrict__ decoded,
+                           const uint64_t *__restrict__ dig, uint32_t *__restrict__ verdict)
+{
+    const uint64_t c = head[0], n = head[1];
+    if (n == 0) return;
+    for (uint64_t o = (uint64_t)blockIdx.x * kThreads + threadIdx.x; o < cap; o += (uint64_t)gridDim.x * kThreads) {
+        if (state[o] != kCommitted) continue;
+        const uint64_t idx = value[o] - dir_base, k = idx - c; // a value below the base, or an entry below the window, wraps out of range
+        if (idx < c || k >= n || decoded[k] != 0) continue;
+        bool eq = true;
+        for (int w = 0; w < W; w++) eq &= key[o * W + w] == dig[k * W + w];
+        __hip_atomic_fetch_min(verdict + k, eq ? 0u : 3u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 unsigned grid_of(uint32_t n) { return (n + kThreads - 1) / kThreads; }
 // grid-stride kernels over `tiles` tiles of kThreads slots
 unsigned grid_stride_of(uint64_t tiles) { return (unsigned)(tiles < (1u << 20) ? tiles : (1u << 20)); }
@@ -527,6 +550,19 @@ hipError_t dedupe_export_live_launch(unsigned words, const uint64_t *state, cons
     default: return hipErrorInvalidValue;
     }
 #undef CW_LIVE
+    return hipGetLastError();
+}
+
+hipError_t dedupe_verify_launch(unsigned words, const uint64_t *state, const uint64_t *value, const uint64_t *key, uint64_t cap, uint64_t dir_base,
+                                const uint64_t *head, const uint32_t *decoded, const uint64_t *digests, uint32_t *verdict, hipStream_t s)
+{
+    const dim3 g(grid_stride_of(dedupe_export_tiles(cap))), b(kThreads);
+    switch (words) {
+    case 2: hipLaunchKernelGGL(dedupe_verify_sweep_kernel<2>, g, b, 0, s, state, value, key, cap, dir_base, head, decoded, digests, verdict); break;
+    case 4: hipLaunchKernelGGL(dedupe_verify_sweep_kernel<4>, g, b, 0, s, state, value, key, cap, dir_base, head, decoded, digests, verdict); break;
+    case 8: hipLaunchKernelGGL(dedupe_verify_sweep_kernel<8>, g, b, 0, s, state, value, key, cap, dir_base, head, decoded, digests, verdict); break;
+    default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

@@ -1,7 +1,9 @@
 // replicate_kernels.hip -- chunk bundles between stores: cw_dev_store_export_chunks takes the stored bytes of
 // the entries a list of values names out of a store, back to back and with a cw_chunk_loc each; cw_dev_store_import_chunks appends
 // such extents to another store under new values; cw_dev_translate_refs rewrites a recipe from the sender's values to the
-// receiver's.  Nothing decodes: extents move in their stored form.  Nothing here keeps state between calls.
+// receiver's; cw_dev_store_replace_chunks is the import with the values given instead of counted up from a
+// base, for chunks that come back under the values they had.  Nothing decodes: extents move in their stored form.  Nothing here keeps
+// state between calls.
 //
 // Export and import mirror the append of restore_kernels.hip: per position its stored size (0 when the position is refused) with
 // the refusal flags; the index-only pack scan over those sizes; a wavefront-per-position copy that also writes the position's entry;
@@ -28,7 +30,7 @@ namespace {
 
 constexpr unsigned kThreads = 256;
 constexpr uint32_t kRawFlag = 0x80000000u, kLenMask = 0x1FFFFu; // cw_chunk_loc::raw (CW_CHUNK_RAW; bits 17..30 stay 0)
-constexpr uint32_t kUnsound = 1u, kOutside = 2u;                // the head's flag word
+constexpr uint32_t kUnsound = 1u, kOutside = 2u, kLength = 4u;  // the head's flag word
 
 struct Entry {
     uint64_t pos;
@@ -115,20 +117,29 @@ struct Selection {
     __device__ __forceinline__ uint64_t chunk(uint64_t j) const { return sel ? sel[j] : j; }
 };
 
-// directory entry of the chunk with value base + k (restore_kernels.hip's rule: neither sum may wrap)
+// directory entry of the chunk with value base + k (restore_kernels.hip's rule: neither sum may wrap), or, for the replace, with
+// value values[k]
 struct Directory {
     uint4 *entries;
     uint64_t base, dir_base, dir_entries;
+    const uint64_t *values; // NULL: the import
     __device__ __forceinline__ bool index(uint64_t k, uint64_t &idx) const
     {
-        const uint64_t v = base + k;
+        const uint64_t v = values ? values[k] : base + k;
         idx = v - dir_base;
-        return v >= base && v >= dir_base && idx < dir_entries;
+        return (values || v >= base) && v >= dir_base && idx < dir_entries;
+    }
+    // the replace keeps a chunk's length: an entry whose own length field is sound (1..65536) takes no other length
+    __device__ __forceinline__ bool keeps_length(uint64_t idx, uint32_t word) const
+    {
+        const uint32_t len = entries[idx].w & kLenMask;
+        return len == 0 || len > kMaxChunkBytes || len == (word & kLenMask);
     }
 };
 
 // sizes[j] = the stored bytes of position j's chunk, 0 and kUnsound when the bundle has no such chunk or its entry is unsound or
-// leaves in_bytes; kOutside when a sound position's value has no directory entry
+// leaves in_bytes; kOutside when a sound position's value has no directory entry; kLength when the replace would change the length
+// of the entry it names
 __global__ void __launch_bounds__(kThreads)
 import_sizes_kernel(const uint4 *__restrict__ in_loc, uint64_t in_bytes, Selection c, Directory d, uint32_t *__restrict__ sizes,
                     uint32_t *__restrict__ flags)
@@ -137,14 +148,17 @@ import_sizes_kernel(const uint4 *__restrict__ in_loc, uint64_t in_bytes, Selecti
     uint32_t mine = 0;
     for (uint64_t j = (uint64_t)blockIdx.x * kThreads + threadIdx.x; j < npos; j += threads) {
         const uint64_t k = c.chunk(j);
-        uint32_t s = 0;
+        uint32_t s = 0, word = 0;
         if (k < n) {
             const Entry e(in_loc[k]);
             if (e.sound(in_bytes)) s = e.stored;
+            word = e.word;
         }
         sizes[j] = s;
         uint64_t idx;
-        mine |= s == 0 ? kUnsound : d.index(k, idx) ? 0u : kOutside;
+        if (s == 0) mine |= kUnsound;
+        else if (!d.index(k, idx)) mine |= kOutside;
+        else if (d.values && !d.keeps_length(idx, word)) mine |= kLength;
     }
     if (mine) atomicOr(flags, mine);
 }
@@ -153,7 +167,7 @@ __device__ __forceinline__ uint32_t import_verdict(uint32_t flags, uint64_t used
 {
     if (flags & kUnsound) return 3u;
     if (used > store_bytes || total > store_bytes - used) return 1u;
-    return flags & kOutside ? 2u : 0u;
+    return flags & kOutside ? 2u : flags & kLength ? 4u : 0u;
 }
 
 // a wavefront per position: the chunk's stored bytes to store + *d_used + off[j], then its directory entry
@@ -258,9 +272,11 @@ hipError_t store_export_launch(const uint8_t *store, size_t store_bytes, const v
     return hipGetLastError();
 }
 
-hipError_t store_import_launch(const uint8_t *in, size_t in_bytes, const void *in_loc, const uint64_t *d_count, size_t max_count,
-                               const uint32_t *sel, const uint64_t *d_nsel, uint64_t base, uint8_t *store, size_t store_bytes, uint64_t *d_used,
-                               void *dir, uint64_t dir_base, size_t dir_entries, uint64_t *result, hipStream_t stream)
+namespace {
+// values == NULL: the import (chunk k carries base + k); else the replace (position k carries values[k], no selection)
+hipError_t import_launch(const uint8_t *in, size_t in_bytes, const void *in_loc, const uint64_t *d_count, size_t max_count, const uint32_t *sel,
+                         const uint64_t *d_nsel, uint64_t base, const uint64_t *values, uint8_t *store, size_t store_bytes, uint64_t *d_used, void *dir,
+                         uint64_t dir_base, size_t dir_entries, uint64_t *result, hipStream_t stream)
 {
     auto &w = replicate_spaces.at(stream);
     LaunchLock sequence(w.launch); // flags, sizes and offsets are shared by the launches below
@@ -272,7 +288,7 @@ hipError_t store_import_launch(const uint8_t *in, size_t in_bytes, const void *i
     if ((e = hipMemsetAsync(flags, 0, kHead, stream)) != hipSuccess) return e;
     const uint4 *locs = static_cast<const uint4 *>(in_loc);
     const Selection c{d_count, sel, d_nsel, (uint64_t)max_count};
-    const Directory d{static_cast<uint4 *>(dir), base, dir_base, (uint64_t)dir_entries};
+    const Directory d{static_cast<uint4 *>(dir), base, dir_base, (uint64_t)dir_entries, values};
     if (max_count)
         hipLaunchKernelGGL(import_sizes_kernel, dim3(lane_grid(max_count)), dim3(kThreads), 0, stream, locs, (uint64_t)in_bytes, c, d, sizes, flags);
     if ((e = chunk_pack_launch(0, nullptr, nullptr, nullptr, sel ? d_nsel : d_count, max_count, sizes, nullptr, off, stream)) != hipSuccess) return e;
@@ -282,6 +298,23 @@ hipError_t store_import_launch(const uint8_t *in, size_t in_bytes, const void *i
                            d_used);
     hipLaunchKernelGGL(import_finish_kernel, dim3(1), dim3(64), 0, stream, c, o, flags, (uint64_t)store_bytes, d_used, result);
     return hipGetLastError();
+}
+} // namespace
+
+hipError_t store_import_launch(const uint8_t *in, size_t in_bytes, const void *in_loc, const uint64_t *d_count, size_t max_count,
+                               const uint32_t *sel, const uint64_t *d_nsel, uint64_t base, uint8_t *store, size_t store_bytes, uint64_t *d_used,
+                               void *dir, uint64_t dir_base, size_t dir_entries, uint64_t *result, hipStream_t stream)
+{
+    return import_launch(in, in_bytes, in_loc, d_count, max_count, sel, d_nsel, base, nullptr, store, store_bytes, d_used, dir, dir_base, dir_entries,
+                         result, stream);
+}
+
+hipError_t store_replace_launch(const uint8_t *in, size_t in_bytes, const void *in_loc, const uint64_t *values, const uint64_t *d_count,
+                                size_t max_count, uint8_t *store, size_t store_bytes, uint64_t *d_used, void *dir, uint64_t dir_base,
+                                size_t dir_entries, uint64_t *result, hipStream_t stream)
+{
+    return import_launch(in, in_bytes, in_loc, d_count, max_count, nullptr, nullptr, 0, values, store, store_bytes, d_used, dir, dir_base, dir_entries,
+                         result, stream);
 }
 
 hipError_t translate_refs_launch(const uint64_t *ref, const uint64_t *d_count, size_t max_count, const uint64_t *from, const uint64_t *to,

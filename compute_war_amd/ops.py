@@ -763,6 +763,26 @@ def dev_translate_refs(d_ref: int, d_count: int, max_count: int, d_from: int, d_
     check(lib().cw_dev_translate_refs(d_ref, d_count, max_count, d_from, d_to, d_npairs, max_pairs, d_out, d_n_missing, stream))
 
 
+def dev_store_verify(index: "DedupeIndex", comp_alg, d_store: int, store_bytes: int, d_dir: int, dir_base: int, dir_entries: int, d_live: int,
+                     d_cursor: int, d_work: int, work_bytes: int, d_status: int, d_totals: int, stream: int = 0) -> None:
+    """One window of a scrub: the directory entries from *d_cursor (u64) on whose decoded chunks fit d_work, at
+    most CW_SCRUB_ENTRIES of them, are decoded, hashed and compared with the digests ``index`` holds for their values.  d_status[idx]
+    (u32) = 0 good, 1 malformed, 2 unsound entry, 3 digest mismatch, 4 no index entry carries the value, 5 not selected (all zero, or
+    d_live[idx] == 0 when d_live is given); d_totals[0..8) (u64) += checked, ok, malformed, unsound, mismatch, orphan, raw bytes,
+    windows; *d_cursor moves to the window's end.  A cursor at or past dir_entries writes nothing.  Not synchronised."""
+    check(lib().cw_dev_store_verify(index._x(), _comp_id(comp_alg), d_store or None, store_bytes, d_dir, dir_base, dir_entries, d_live or None,
+                                    d_cursor, d_work, work_bytes, d_status, d_totals, stream))
+
+
+def dev_store_replace_chunks(d_in: int, in_bytes: int, d_in_loc: int, d_values: int, d_count: int, max_count: int, d_store: int,
+                             store_bytes: int, d_used: int, d_dir: int, dir_base: int, dir_entries: int, d_result: int, stream: int = 0) -> None:
+    """``dev_store_import_chunks`` with explicit values and no selection: position k's stored bytes go behind *d_used and
+    d_dir[d_values[k] - dir_base] points at them.  d_result[0] = 0, or 3 (an incoming entry is unsound) / 1 (does not fit) / 2 (a value
+    outside the directory) / 4 (the entry named has another length) with nothing changed; d_result[1] = the bytes.  Not synchronised."""
+    check(lib().cw_dev_store_replace_chunks(d_in or None, in_bytes, d_in_loc, d_values, d_count, max_count, d_store or None, store_bytes,
+                                            d_used, d_dir, dir_base, dir_entries, d_result, stream))
+
+
 class Store(C.Structure):
     """cw_store: the caller-owned triple of the chunk store (bytes, cursor, directory) as one argument."""
     _fields_ = [("d_store", C.c_void_p), ("store_bytes", C.c_size_t), ("d_used", C.c_void_p), ("d_dir", C.c_void_p),
@@ -801,6 +821,22 @@ def store_restore(comp_alg, store: Store, refs, offsets, dst: int, dst_bytes: in
     status = status[:len(refs)]
     assert int(n_bad.value) == int((status != 0).sum())
     return status
+
+
+class ScrubStats(C.Structure):
+    """cw_scrub_stats: what a scrub checked and found, the decoded bytes it hashed and the windows it took."""
+    _fields_ = [(k, C.c_uint64) for k in ("checked", "ok", "malformed", "unsound", "mismatch", "orphan", "raw_bytes", "windows")]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+def store_scrub(index: "DedupeIndex", comp_alg, store: Store, d_live: int = 0):
+    """cw_store_scrub: every directory entry (d_live = 0), or the entries the device flags d_live (u32[dir_entries]) select, checked
+    against ``index`` in windows of CW_STORE_PIECE decoded bytes.  Returns (status u32 array, one per entry; stats as a dict)."""
+    status, stats = np.zeros(store.dir_entries, np.uint32), ScrubStats()
+    check(lib().cw_store_scrub(index._x(), _comp_id(comp_alg), C.byref(store), d_live or None, status.ctypes.data, C.byref(stats)))
+    return status, stats.as_dict()
 
 
 def dev_ingest_commit(d_ref: int, d_offsets: int, d_nchunks: int, max_chunks: int, d_n_new: int, d_store_result: int, stream_off: int,
@@ -858,6 +894,30 @@ class Recipe:
 
 LOC_DTYPE = np.dtype([("pos", "<u8"), ("stored", "<u4"), ("raw", "<u4")])  # cw_chunk_loc as a numpy record
 _MISS = np.uint64(DedupeIndex.MISS)
+
+
+def _locs_sound(locs, in_bytes: int) -> np.ndarray:
+    """bool per LOC_DTYPE record: sound by cw_dev_store_compact's entry checks against a buffer of in_bytes bytes."""
+    pos, stored, word = locs["pos"], locs["stored"].astype(np.int64), locs["raw"].astype(np.int64)
+    length, is_raw = word & 0x1FFFF, (word & ChunkLoc.RAW) != 0
+    return ((word & ~(ChunkLoc.RAW | 0x1FFFF)) == 0) & (length >= 1) & (length <= 65536) & (stored != 0) & (~is_raw | (stored == length)) & \
+        (pos <= in_bytes) & (stored <= in_bytes - np.minimum(pos, np.uint64(in_bytes)).astype(np.int64))
+
+
+class ScrubReport:
+    """What ``ChunkStore.scrub`` found: ``status`` (uint32, one per directory entry: 0 good, 1 malformed, 2 unsound entry, 3 digest
+    mismatch, 4 orphan, 5 not selected), ``stats`` (cw_scrub_stats as a dict), ``damaged`` (the values with status 1, 2 or 3,
+    ascending) and ``orphans`` (the values with status 4: they decode, but the index holds no digest to judge them by)."""
+
+    def __init__(self, status, stats: dict, dir_base: int):
+        self.status, self.stats = np.ascontiguousarray(status, dtype=np.uint32), stats
+        at = lambda mask: (np.nonzero(mask)[0].astype(np.uint64) + np.uint64(dir_base))  # noqa: E731
+        self.damaged = at((self.status >= 1) & (self.status <= 3))
+        self.orphans = at(self.status == 4)
+
+    @property
+    def clean(self) -> bool:
+        return len(self.damaged) == 0
 
 
 class Bundle:
@@ -1291,10 +1351,7 @@ class ChunkStore:
         lacks, carried, locs = found.cpu().numpy().view(np.uint64) == _MISS, bundle.carried, bundle.locs
         if (lacks & ~carried).any():
             raise _lib.CwError(-2, f"chunk bundle: {int((lacks & ~carried).sum())} chunks this store lacks are listed but not carried")
-        pos, stored, word = locs["pos"], locs["stored"].astype(np.int64), locs["raw"].astype(np.int64)
-        length, is_raw = word & 0x1FFFF, (word & ChunkLoc.RAW) != 0
-        sound = ((word & ~(ChunkLoc.RAW | 0x1FFFF)) == 0) & (length >= 1) & (length <= 65536) & (stored != 0) & (~is_raw | (stored == length)) & \
-            (pos <= in_bytes) & (stored <= in_bytes - np.minimum(pos, np.uint64(in_bytes)).astype(np.int64))
+        stored, length, sound = locs["stored"].astype(np.int64), locs["raw"].astype(np.int64) & 0x1FFFF, _locs_sound(locs, in_bytes)
         if (lacks & ~sound).any():
             raise _lib.CwError(-2, f"chunk bundle: chunk {int(np.nonzero(lacks & ~sound)[0][0])}'s place in the payload is unsound")
         n_lacks, need, count, used = int(lacks.sum()), int(stored[lacks].sum()), self.index.count(), self.used()
@@ -1313,21 +1370,13 @@ class ChunkStore:
         if verify and len(which):
             if not sound[which].all():
                 raise _lib.CwError(-2, f"chunk bundle: chunk {int(which[~sound[which]][0])}'s place in the payload is unsound")
-            cuts = np.concatenate([[0], np.cumsum(length[which])]).astype(np.uint64)
-            k, total = len(which), int(cuts[-1])
-            d_ref, d_raw, d_count = up(which), up(cuts), up([k])
-            out, status, dig2 = z(total, torch.uint8), z(k, torch.int32), z(k * db, torch.uint8)
-            torch.cuda.synchronize()
-            dev_restore_chunks(self.comp_alg, d_in.data_ptr(), in_bytes, d_loc.data_ptr(), 0, n, d_ref.data_ptr(), d_raw.data_ptr(),
-                               d_count.data_ptr(), k, out.data_ptr(), total, status.data_ptr(), s)
-            dev_hash_chunks(self.index.hash_alg, out.data_ptr(), total, d_raw.data_ptr(), d_count.data_ptr(), k, dig2.data_ptr(), s)
-            torch.cuda.synchronize()
-            st = status.cpu().numpy()[:k]
+            k = len(which)
+            st, dig2 = self._restored_digests(d_in.data_ptr(), in_bytes, d_loc.data_ptr(), n, which, length[which])
             if st.any():
                 j = int(np.nonzero(st)[0][0])
                 raise _lib.CwError(-2, f"chunk bundle: {int((st != 0).sum())} of {k} carried chunks do not restore; chunk {int(which[j])} has "
                                        f"status {int(st[j])}")
-            bad = np.nonzero((dig2.cpu().numpy()[:k * db].reshape(k, db) != bundle.digests[which]).any(axis=1))[0]
+            bad = np.nonzero((dig2 != bundle.digests[which]).any(axis=1))[0]
             if len(bad):
                 raise _lib.CwError(-2, f"chunk bundle: {len(bad)} carried chunks do not hash to their manifest digest; the first is chunk "
                                        f"{int(which[bad[0]])}")
@@ -1352,10 +1401,152 @@ class ChunkStore:
         self.base += n
         return [Recipe(d_r.cpu().numpy().view(np.uint64)[:k], r.offsets) for (d_r, _, k), r in zip(outs, bundle.recipes)]
 
+    def _restored_digests(self, d_in: int, in_bytes: int, d_loc: int, n_loc: int, which, lengths):
+        """The chunks ``which`` (positions of the n_loc cw_chunk_loc entries at d_loc, each sound, with the given lengths) restored from
+        the payload d_in[0..in_bytes) -- the payload as the store, the locs as its directory -- and hashed with this index's algorithm:
+        (cw_dev_restore_chunks' statuses, the digests as uint8[k, digest bytes])."""
+        import torch
+        s, db = self._stream(), digest_bytes(self.index.hash_alg)
+        z = lambda k, dt: torch.zeros(max(k, 1), dtype=dt, device="cuda")  # noqa: E731
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64).copy()).cuda()  # noqa: E731
+        cuts = np.concatenate([[0], np.cumsum(lengths)]).astype(np.uint64)
+        k, total = len(which), int(cuts[-1])
+        d_ref, d_raw, d_count = up(which), up(cuts), up([k])
+        out, status, dig2 = z(total, torch.uint8), z(k, torch.int32), z(k * db, torch.uint8)
+        torch.cuda.synchronize()
+        dev_restore_chunks(self.comp_alg, d_in, in_bytes, d_loc, 0, n_loc, d_ref.data_ptr(), d_raw.data_ptr(), d_count.data_ptr(), k,
+                           out.data_ptr(), total, status.data_ptr(), s)
+        dev_hash_chunks(self.index.hash_alg, out.data_ptr(), total, d_raw.data_ptr(), d_count.data_ptr(), k, dig2.data_ptr(), s)
+        torch.cuda.synchronize()
+        return status.cpu().numpy()[:k], dig2.cpu().numpy()[:k * db].reshape(k, db)
+
     def replicate_to(self, other: "ChunkStore", recipes, verify: bool = True) -> list:
         """``other.import_bundle(self.export_bundle(recipes, known=other.index), verify)``: only the chunks ``other`` lacks travel, in
         their stored form, and ``other`` gets recipes of its own for the same streams."""
         return other.import_bundle(self.export_bundle(recipes, known=other.index), verify)
+
+    def scrub(self, keep=None) -> ScrubReport:
+        """Check every stored chunk once against the digest the index holds for its value (cw_store_scrub), in
+        windows of CW_STORE_PIECE decoded bytes.  ``keep`` is a list of recipes: only the entries they name are checked, and a named
+        entry that is missing shows as status 2; None checks every entry that is not all zero.  Raises CwError (-2) when a kept
+        recipe names a value outside the directory."""
+        import torch
+        d_live = 0
+        if keep is not None:
+            s, n = self._stream(), self.dir_entries
+            live, n_out = torch.zeros(n, dtype=torch.int32, device="cuda"), torch.zeros(1, dtype=torch.int64, device="cuda")
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64).copy()).cuda()  # noqa: E731
+            marks = [(up(r.refs), up([len(r.refs)]), len(r.refs)) for r in keep if len(r.refs)]
+            torch.cuda.synchronize()  # (torch zeroed and copied on its own stream)
+            for d_ref, d_count, k in marks:
+                dev_store_mark(d_ref.data_ptr(), d_count.data_ptr(), k, self.dir_base, n, live.data_ptr(), n_out.data_ptr(), s)
+            torch.cuda.synchronize()
+            outside = int(n_out.item())
+            if outside:
+                raise _lib.CwError(-2, f"chunk store: {outside} positions of the kept recipes name no entry of the directory [{self.dir_base}, "
+                                       f"{self.dir_base + n})")
+            d_live = live.data_ptr()
+        torch.cuda.synchronize()  # (the store was written on torch's stream)
+        status, stats = store_scrub(self.index, self.comp_alg, self._triple(), d_live)
+        return ScrubReport(status, stats, self.dir_base)
+
+    def repair_from(self, other: "ChunkStore", report: ScrubReport, verify: bool = True) -> dict:
+        """Put the chunks ``report.damaged`` names back from ``other``, a store that holds them (one the streams were replicated to),
+        in stored form and under their own values, so that every recipe stays valid.  The damaged values' digests come from this
+        store's index, ``other``'s index finds them there, ``dev_store_export_chunks`` takes ``other``'s stored bytes out, and one
+        ``dev_store_replace_chunks`` appends them here and repoints the entries; the old bytes stay until the next ``compact``.  A
+        chunk is left out -- not a reason to refuse the rest -- when ``other`` lacks it, when its entry there is unsound or has
+        another length than the entry here, or, with ``verify``, when it does not restore from the exported bytes or does not hash
+        to the digest this index holds.  Returns dict(repaired, unavailable, no_digest): lists of values; no_digest are the damaged
+        values this index holds no digest for.  ValueError when codec or hash algorithm differ; CwError (-5) with ``e.needed`` (the
+        bytes wanted) when they do not fit behind ``used()``, nothing changed: ``compact`` makes room.  The index is never written."""
+        import torch
+        if other.comp_alg != self.comp_alg or other.index.hash_alg != self.index.hash_alg:
+            raise ValueError(f"peer of codec {other.comp_alg} / hash {other.index.hash_alg}, store of codec {self.comp_alg} / hash "
+                             f"{self.index.hash_alg}")
+        damaged = np.unique(np.ascontiguousarray(report.damaged, dtype=np.uint64))
+        out = dict(repaired=[], unavailable=[], no_digest=[])
+        if len(damaged) == 0:
+            return out
+        idx = damaged - np.uint64(self.dir_base)
+        if (damaged < np.uint64(self.dir_base)).any() or (idx >= np.uint64(self.dir_entries)).any():
+            raise _lib.CwError(-2, f"chunk store: the report names values outside the directory [{self.dir_base}, {self.dir_base + self.dir_entries})")
+        idx = idx.astype(np.int64)
+        s, n, db, m = self._stream(), self.dir_entries, digest_bytes(self.index.hash_alg), len(damaged)
+        z = lambda k, dt: torch.zeros(max(k, 1), dtype=dt, device="cuda")  # noqa: E731
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64).copy()).cuda()  # noqa: E731
+        raw = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()  # noqa: E731
+        # 1. the digests this index holds for the damaged values, in ascending value
+        live, dig, val, res = z(n, torch.int32), z(m * db, torch.uint8), z(m, torch.int64), z(3, torch.int64)
+        live[torch.from_numpy(idx).cuda()] = 1
+        torch.cuda.synchronize()
+        self.index.dev_export_live(live.data_ptr(), self.dir_base, n, dig.data_ptr(), val.data_ptr(), m, res.data_ptr(), s)
+        torch.cuda.synchronize()
+        has = val.cpu().numpy().view(np.uint64)[:m] != _MISS
+        out["no_digest"] = damaged[~has].tolist()
+        # 2. where the peer keeps them
+        found, n_found = z(m, torch.int64), z(1, torch.int64)
+        torch.cuda.synchronize()
+        other.index.dev_lookup(dig.data_ptr(), m, found.data_ptr(), n_found.data_ptr(), s)
+        torch.cuda.synchronize()
+        there = found.cpu().numpy().view(np.uint64)[:m].copy()
+        o_idx = there - np.uint64(other.dir_base)
+        ok = has & (there != _MISS) & (there >= np.uint64(other.dir_base)) & (o_idx < np.uint64(other.dir_entries))
+        o_idx = o_idx.astype(np.int64)
+        entries = lambda cs, at: cs.d_dir.view(-1, 2)[torch.from_numpy(at).cuda()].cpu().numpy().reshape(-1).view(LOC_DTYPE)  # noqa: E731
+        peer, mine = np.zeros(m, LOC_DTYPE), entries(self, idx)
+        if ok.any():
+            peer[ok] = entries(other, o_idx[ok])
+        ok &= _locs_sound(peer, other.store_bytes)
+        # (a replacement keeps the chunk's length, unless the entry here has no sound length of its own)
+        len_here, len_there = mine["raw"].astype(np.int64) & 0x1FFFF, peer["raw"].astype(np.int64) & 0x1FFFF
+        ok &= (len_here < 1) | (len_here > 65536) | (len_here == len_there)
+        which = np.nonzero(ok)[0]
+        nc = len(which)
+        if nc:
+            # 3. the peer's stored bytes, sized by a dry run
+            d_val, d_count, d_loc = up(there[which]), up([nc]), z(nc * 2, torch.int64)
+            torch.cuda.synchronize()
+
+            def run(d_out: int, out_bytes: int):
+                dev_store_export_chunks(other.d_store.data_ptr(), other.store_bytes, other.d_dir.data_ptr(), other.dir_base, other.dir_entries,
+                                        d_val.data_ptr(), d_count.data_ptr(), nc, d_out, out_bytes, d_loc.data_ptr(), res.data_ptr(), s)
+                torch.cuda.synchronize()
+                return tuple(int(v) for v in res.cpu().numpy().view(np.uint64)[:2])
+
+            _, total = run(0, 0)
+            payload = z(total, torch.uint8)
+            torch.cuda.synchronize()
+            verdict, _ = run(payload.data_ptr(), total)
+            if verdict:
+                raise _lib.CwError(-4, f"chunk store: the export of {total} bytes from the peer was refused with verdict {verdict} after its dry run")
+            locs = d_loc.cpu().numpy().view(LOC_DTYPE)[:nc].copy()
+            good = np.ones(nc, bool)
+            if verify:
+                st, dig2 = self._restored_digests(payload.data_ptr(), total, d_loc.data_ptr(), nc, np.arange(nc), len_there[which])
+                good = (st == 0) & (dig2 == dig.cpu().numpy()[:m * db].reshape(m, db)[which]).all(axis=1)
+            ok[which[~good]] = False
+            which, locs = which[good], locs[good]
+        out["unavailable"] = damaged[has & ~ok].tolist()
+        if len(which) == 0:
+            return out
+        # 4. room, then one replace
+        need, used = int(locs["stored"].astype(np.int64).sum()), self.used()
+        if used + need > self.store_bytes:
+            err = _lib.CwError(-5, f"chunk store: the repair's {need} bytes do not fit behind {used} of {self.store_bytes}")
+            err.needed = need
+            raise err
+        d_loc2, d_val2, d_k, result = raw(locs), up(damaged[which]), up([len(which)]), z(2, torch.int64)
+        torch.cuda.synchronize()
+        dev_store_replace_chunks(payload.data_ptr(), total, d_loc2.data_ptr(), d_val2.data_ptr(), d_k.data_ptr(), len(which), self.d_store.data_ptr(),
+                                 self.store_bytes, self.d_used.data_ptr(), self.d_dir.data_ptr(), self.dir_base, self.dir_entries,
+                                 result.data_ptr(), s)
+        torch.cuda.synchronize()
+        verdict, total = (int(v) for v in result.cpu().numpy().view(np.uint64))
+        if verdict:
+            raise _lib.CwError(-4, f"chunk store: admitted, yet the replace was refused with verdict {verdict} ({total} bytes)")
+        out["repaired"] = damaged[which].tolist()
+        return out
 
     def save(self, path) -> None:
         """One ``.npz``: the index's export, the store bytes [0, used), the directory, base and the parameters."""

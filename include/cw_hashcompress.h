@@ -764,6 +764,75 @@ int cw_dev_translate_refs(const uint64_t *d_ref, const uint64_t *d_count, size_t
                           const uint64_t *d_from, const uint64_t *d_to, const uint64_t *d_npairs, size_t max_pairs,
                           uint64_t *d_out, uint64_t *d_n_missing, void *stream);
 
+/* ---- scrub and repair: is what the store holds still good? ---------------------------------------------
+ * A scrub walks the directory and checks every stored chunk once, in bounded memory, against the digest the index holds for its
+ * value; a chunk found damaged can be put back, in stored form and under its own value, from a peer that holds it (a store the
+ * streams were replicated to).  The calls follow the store's conventions: device pointers, counts read on the device, queued on
+ * `stream`, nothing synchronises.                                                                                               */
+#define CW_SCRUB_OK 0         /* sound, decodes to its length, hashes to a digest the index holds for this value */
+#define CW_SCRUB_MALFORMED 1  /* the decoder's verdict on the stored bytes (cw_dev_restore_chunks' status 1) */
+#define CW_SCRUB_UNSOUND 2    /* the entry fails cw_dev_store_compact's entry checks, or is all zero while d_live flags it */
+#define CW_SCRUB_MISMATCH 3   /* decodes, the index holds the value, none of its digests for it equals the computed one */
+#define CW_SCRUB_ORPHAN 4     /* decodes, but no index entry carries this value: cannot be judged */
+#define CW_SCRUB_SKIPPED 5    /* not selected: all zero with d_live == NULL, or d_live[idx] == 0 */
+/* One window of a scrub.  The hash algorithm is the index's; the call is serialised with the index's other calls and leaves the
+ * index unchanged, as cw_dev_dedupe_lookup and cw_dev_dedupe_export_live do.
+ *   window        Let c = *d_cursor.  If c >= dir_entries the call writes nothing at all.  Otherwise E = min(dir_entries, c +
+ *                 entry_cap), entry_cap = CW_SCRUB_ENTRIES (default 2^20, at least 64).  Entry idx is SELECTED iff, with d_live ==
+ *                 NULL, it is not all zero, or, with d_live given, d_live[idx] != 0.  It is DECODABLE iff it is selected and sound
+ *                 by cw_dev_store_compact's entry checks (length 1..65536, bits 17..30 zero, stored != 0, a raw entry has stored ==
+ *                 length, pos + stored <= store_bytes).  need(idx) = its length when decodable, else 0.  e is the largest index in
+ *                 (c, E] with the sum of need over [c, e) <= work_bytes; work_bytes >= 65536, so e > c.  Then *d_cursor = e.
+ *   statuses      Every d_status[idx] with c <= idx < e is written, nothing outside [c, e) is.  A decodable entry goes through
+ *                 cw_dev_restore_chunks' own checks and decoder into d_work, back to back from byte 0, and is hashed there; one sweep
+ *                 of the index's table then compares: of the index entries that carry the value dir_base + idx, a match by any gives
+ *                 0, none matching gives 3, no such entry gives 4.  A decodable entry whose stored bytes are malformed gets 1; a
+ *                 selected entry that is not decodable 2; an entry that is not selected 5.  An entry's status is a property of the
+ *                 store, the directory, the flags and the index: it does not depend on work_bytes, CW_SCRUB_ENTRIES or where a
+ *                 window starts.
+ *   totals        d_totals[8] (u64) += {checked, ok, malformed, unsound, mismatch, orphan, raw bytes hashed, windows}, so that a loop
+ *                 of windows sums as cw_dev_store_mark's counter does: checked = the sum of the five counts behind it (skipped
+ *                 entries are not counted), raw bytes hashed = the sum of need over [c, e), windows += 1.
+ * Whatever the store, the directory and the flags hold, no load leaves d_store[0..store_bytes), d_dir[0..dir_entries),
+ * d_live[0..dir_entries) or the table, and no store leaves d_work[0..work_bytes), d_status[c..e), the cursor, the totals or the
+ * scratch.  The bytes of d_work are unspecified afterwards.
+ * CW_ERR_BAD_ARG before anything is launched: a NULL pointer (d_live may be NULL; d_store when store_bytes is 0), an unknown codec,
+ * dir_entries == 0 or above 2^32 - 256, work_bytes < 65536, a d_dir that is not 16-byte aligned, a d_cursor or d_totals that is not
+ * 8-byte aligned, an index of another device.  Scratch, per stream: 72 + (28 + digest bytes) * W bytes, W = min(entry_cap,
+ * dir_entries) (92 MiB at the default for 64-byte digests and 2^20 entries or more), plus cw_dev_hash_chunks' 4 bytes per window
+ * entry.  Not synchronised.                                                                                                      */
+int cw_dev_store_verify(cw_dedupe_t *x, int comp_alg,
+                        const void *d_store, size_t store_bytes, const cw_chunk_loc *d_dir, uint64_t dir_base, size_t dir_entries,
+                        const uint32_t *d_live /* may be NULL */, uint64_t *d_cursor /* in/out */,
+                        void *d_work, size_t work_bytes,
+                        uint32_t *d_status /* [dir_entries] */, uint64_t *d_totals /* [8], accumulates */, void *stream);
+typedef struct cw_scrub_stats { uint64_t checked, ok, malformed, unsound, mismatch, orphan, raw_bytes, windows; } cw_scrub_stats;
+/* The whole directory, synchronous: a work buffer of CW_STORE_PIECE bytes (default 256 MiB, raised to 65536) from the calling
+ * thread's context scratch (grows only), a zeroed cursor and totals, cw_dev_store_verify until the cursor reaches dir_entries with
+ * one synchronise per window, then the statuses (host, may be NULL) and the totals (may be NULL) come down.  d_live is device
+ * memory and must be complete when the call is made.  CW_OK whatever the statuses are, like cw_store_restore.  CW_ERR_BAD_ARG: a
+ * NULL index or store, what cw_dev_store_verify refuses.                                                                         */
+int cw_store_scrub(cw_dedupe_t *x, int comp_alg, const cw_store *st, const uint32_t *d_live /* device, may be NULL */,
+                   uint32_t *status /* host, [dir_entries], may be NULL */, cw_scrub_stats *stats /* may be NULL */);
+/* cw_dev_store_import_chunks with explicit values and no selection: puts stored chunks back under their own values.  For position
+ * k < n = min(*d_count, max_count): its bytes d_in[loc.pos .. + loc.stored), loc = d_in_loc[k], are appended at *d_used + the stored
+ * bytes of the positions before it, d_dir[d_values[k] - dir_base] = {new pos, stored, raw word}, then *d_used grows by the total.
+ * d_result[2] = {verdict, the total}: verdict 3 when an incoming entry is all zero, unsound by cw_dev_store_compact's checks or
+ * leaves in_bytes (the total then counts the other positions); else 1 when *d_used + total > store_bytes; else 2 when a value lies
+ * outside [dir_base, dir_base + dir_entries); else 4 when the entry a position names has, in the length field of its raw word, a
+ * length in 1..65536 that differs from the incoming length -- a replacement keeps the chunk's length, or every recipe's offsets
+ * would lie; an all-zero entry, or one whose own length field is unsound, takes any length; else 0.  With a verdict other than 0,
+ * no store byte, no directory entry and not *d_used change.  The replaced chunk's old bytes stay where they are until the next
+ * compaction.  A value named twice is stored twice, and either entry stays.  No load leaves d_in[0..in_bytes), d_in_loc[0..n),
+ * d_values[0..n) or d_dir[0..dir_entries).  CW_ERR_BAD_ARG before anything is launched: a NULL pointer (d_in when in_bytes is 0
+ * and d_store when store_bytes is 0 may be), max_count > 2^32 - 256, dir_entries == 0, a d_in_loc or d_dir that is not 16-byte
+ * aligned, a d_values, d_count, d_used or d_result that is not 8-byte aligned, [d_in, +in_bytes) overlapping [d_store,
+ * +store_bytes).  Scratch, per stream: 72 + 12 * max_count bytes.                                                                */
+int cw_dev_store_replace_chunks(const void *d_in, size_t in_bytes, const cw_chunk_loc *d_in_loc, const uint64_t *d_values,
+                                const uint64_t *d_count, size_t max_count,
+                                void *d_store, size_t store_bytes, uint64_t *d_used,
+                                cw_chunk_loc *d_dir, uint64_t dir_base, size_t dir_entries, uint64_t *d_result /* [2] */, void *stream);
+
 /* plain device memory on the calling thread's device, for C callers of cw_dev_* (the host programs link no HIP runtime) */
 void *cw_dev_alloc(size_t bytes);                                   /* NULL on failure */
 void  cw_dev_free(void *d_p);
