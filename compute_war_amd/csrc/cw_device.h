@@ -236,15 +236,16 @@ hipError_t chunk_store_launch(int lzf, const uint8_t *src, size_t src_bytes, con
 hipError_t chunk_restore_launch(int lzf, const uint8_t *store, size_t store_bytes, const void *dir, uint64_t dir_base, size_t dir_entries,
                                 const uint64_t *ref, const uint64_t *raw_offsets, const uint64_t *d_count, size_t max_count, uint8_t *dst,
                                 size_t dst_bytes, uint32_t *status, hipStream_t stream);
-// a streamed ingest (ingest_kernels.hip; semantics: the public header's cw_dev_ingest_commit).  piece_counts_launch: counts[0..4) =
-// min(*d_nchunks, max_chunks), the bytes those chunks cover, *d_used, *d_verdict
+// a streamed ingest (ingest_kernels.hip; semantics: the public header's cw_dev_ingest_commit and cw_dev_ingest_commit_streams).  One
+// pair of kernels and one launch mutex per stream serve both commits: ingest_commit_launch is ingest_commit_streams_launch with the
+// empty list {nullptr, 0, 0, 0, nullptr, 0}.  piece_counts_launch: counts[0..4) = min(*d_nchunks, max_chunks), the bytes those chunks
+// cover, *d_used, *d_verdict
+struct CommitStreams { const uint64_t *first; uint64_t nstreams, first_stream, skip_first; uint64_t *rec_first; uint64_t first_cap; };
 hipError_t ingest_commit_launch(const uint64_t *ref, const uint64_t *offsets, const uint64_t *d_nchunks, size_t max_chunks, const uint64_t *d_n_new,
                                 const uint64_t *store_result, uint64_t stream_off, uint64_t *rec_ref, uint64_t *rec_off, uint64_t *d_rec_count,
                                 size_t rec_cap, uint64_t *stats, uint64_t *d_verdict, hipStream_t stream);
 hipError_t piece_counts_launch(const uint64_t *offsets, const uint64_t *d_nchunks, size_t max_chunks, const uint64_t *d_used,
                                const uint64_t *d_verdict, uint64_t *counts, hipStream_t stream);
-// the commit of a piece of many streams (commit_streams_kernels.hip; semantics: the public header's cw_dev_ingest_commit_streams)
-struct CommitStreams { const uint64_t *first; uint64_t nstreams, first_stream, skip_first; uint64_t *rec_first; uint64_t first_cap; };
 hipError_t ingest_commit_streams_launch(const uint64_t *ref, const uint64_t *offsets, const uint64_t *d_nchunks, size_t max_chunks,
                                         const uint64_t *d_n_new, const uint64_t *store_result, uint64_t stream_off, uint64_t *rec_ref,
                                         uint64_t *rec_off, uint64_t *d_rec_count, size_t rec_cap, uint64_t *stats, uint64_t *d_verdict,

@@ -69,7 +69,8 @@ struct PinnedBuf { // page-locked host staging: the only kind of host memory a c
 };
 bool is_pinned(const void *p); // page-locked host memory (cw_host_alloc / cw_host_register): the copy engines use it in place
 
-// What cw_store_ingest / cw_store_restore keep per calling thread and device (cw_ingest.hip); grows only, freed with the context.
+// What cw_store_ingest / cw_store_ingest_streams (one piece loop, cw_ingest.hip's struct Ingest) and cw_store_restore keep per calling
+// thread and device; grows only, freed with the context.
 // Index 0 / 1: the two buffers the pieces (windows) alternate between.
 struct StoreCtx {
     DevBuf src[2];                                   // ingest: a piece's carry + fresh bytes; restore: a window's bytes

@@ -1,13 +1,16 @@
-// cw_ingest.hip -- the chunk store's host-buffer calls (semantics: the public header): cw_store_ingest streams a
-// host buffer of any size through the device in pieces, cw_store_restore streams a recipe back in windows, and cw_dev_ingest_commit is
-// the device step that assembles a recipe piece by piece (kernels: ingest_kernels.hip).  cw_store_ingest_streams (section 21) is the
-// ingest over many host streams: the same pieces, buffers and events, each piece chunked by cw_dev_cdc_streams_part with the stream
-// ends that fall into it and committed by cw_dev_ingest_commit_streams (commit_streams_kernels.hip); a piece's ends are copied on the
-// kernel stream in front of its kernels, since their rebasing needs the carry.
+// cw_ingest.hip -- the chunk store's host-buffer calls (DESIGN.md sections 18 and 21; semantics: the public header): cw_store_ingest
+// streams a host buffer of any size through the device in pieces, cw_store_ingest_streams does the same over many host streams,
+// cw_store_restore streams a recipe back in windows, and cw_dev_ingest_commit / cw_dev_ingest_commit_streams are the device step that
+// assembles a recipe piece by piece (kernels: ingest_kernels.hip).
+//
+// Both ingests are one loop (struct Ingest) over a list of host spans; cw_store_ingest's one buffer is a single span.  With the stream
+// index (cw_store_ingest_streams) a piece is chunked by cw_dev_cdc_streams_part with the stream ends that fall into it and committed by
+// cw_dev_ingest_commit_streams, and its ends are copied on the kernel stream in front of its kernels, since their rebasing needs the
+// carry; without it a piece is chunked by cw_dev_cdc and committed by cw_dev_ingest_commit.
 //
 // Ingest, piece i in buffer b = i & 1 (F = max_size rounded up to 256, P = the fresh bytes per piece):
 //     s_h2d    wait ev_done[b] (piece i-2 has left the buffer) | fresh bytes -> buf[b] + F | record ev_up[b]
-//     stream   wait ev_up[b] | cdc, hash, counts | SYNCHRONISE, admit | dedupe, codec, append, commit
+//     stream   [ends -> device] | wait ev_up[b] | cdc, hash, counts | SYNCHRONISE, admit | dedupe, codec, append, commit
 //              | carry -> buf[b^1] + F - carry | record ev_done[b]
 // The upload of piece i+1 is queued before piece i's kernels, so it runs beside them; its address does not depend on any count.
 // Restore, window w in buffer b = w & 1:
@@ -59,6 +62,14 @@ const size_t kWindowPositions = (size_t)1 << 24; // positions per restore window
 // (W_COUNTS: four on the device, five on the host, where the fifth takes W_ENDS, the verdict on a piece's stream ends)
 enum { W_NCHUNKS = 0, W_NNEW = 1, W_RESULT = 2, W_COUNTS = 4, W_VERDICT = 9, W_REC_COUNT = 10, W_ENDS = 11, W_STATS = 16, W_WORDS = 24 };
 
+// the bytes of a piece (ingest) or a window (restore, scrub): CW_STORE_PIECE or the default, and no less than `floor`
+size_t piece_bytes(size_t floor)
+{
+    const long knob = cw::knobs().store_piece;
+    const size_t piece = knob ? (size_t)knob : kDefaultPiece;
+    return piece < floor ? floor : piece;
+}
+
 int check_store(const cw_store *st)
 {
     if (!st) return fail(CW_ERR_BAD_ARG, "NULL store");
@@ -97,87 +108,21 @@ int admit_piece(void *self, size_t k, const uint64_t *h)
     return CW_OK;
 }
 
+// The pipelined ingest of the concatenation of host spans.  indexed (cw_store_ingest_streams): every span is a stream with an entry in
+// the recipe's stream index.  A piece then takes the stream ends not yet taken that lie at or before its end; when the last of them is
+// not the piece's end, the piece's own length is one more end and its last stream is open.  Not indexed (cw_store_ingest): the spans are
+// one stream, no ends, the plain chunker and the plain commit.
 struct Ingest {
+    const char *name;                                 // the public call: the prefix of its CW_ERR_STATE messages
     cw_dedupe_t *x; const cw_cdc_params *p; int comp_alg; const cw_store *st;
-    const uint8_t *src; size_t nbytes; uint64_t base;
-    StoreCtx *c; hipStream_t s, s_h2d;
-    size_t piece, front, cap, slots_bytes, rec_cap; // P, F, a piece's max_offsets, its slot bytes, the recipe's entries
-    bool pinned;
-    size_t k_total = 0, done = 0;                    // chunks and stream bytes of the pieces that went in
-
-    size_t pieces() const { return (nbytes + piece - 1) / piece; }
-
-    int upload(size_t i)
-    {
-        const int b = (int)(i & 1);
-        const size_t first = i * piece, take = nbytes - first < piece ? nbytes - first : piece;
-        const void *from = src + first;
-        if (!pinned) {
-            if (i >= 2) HIP_TRY(hipEventSynchronize(c->ev_up[b])); // the staging buffer's last copy has left it
-            memcpy(c->stage[b].p, from, take);
-            from = c->stage[b].p;
-        }
-        if (i >= 2) HIP_TRY(hipStreamWaitEvent(s_h2d, c->ev_done[b], 0));
-        HIP_TRY(hipMemcpyAsync((uint8_t *)c->src[b].p + front, from, take, hipMemcpyHostToDevice, s_h2d));
-        HIP_TRY(hipEventRecord(c->ev_up[b], s_h2d));
-        return CW_OK;
-    }
-
-    // CW_OK with *refused set: the piece did not go in and nothing changed
-    int run(bool *refused)
-    {
-        uint64_t *w = (uint64_t *)c->words.p, *h = (uint64_t *)c->h_words.p;
-        const size_t n = pieces();
-        size_t carry = 0;
-        int rc = upload(0);
-        for (size_t i = 0; rc == CW_OK && i < n; i++) {
-            const int b = (int)(i & 1);
-            if (i + 1 < n && (rc = upload(i + 1)) != CW_OK) return rc;
-            const size_t take = nbytes - i * piece < piece ? nbytes - i * piece : piece, len = carry + take;
-            uint8_t *d_piece = (uint8_t *)c->src[b].p + front - carry;
-            HIP_TRY(hipStreamWaitEvent(s, c->ev_up[b], 0));
-            Admission a{st, base + k_total};
-            bool inserted = false;
-            PieceAdmit hook{st->d_used, w + W_VERDICT, w + W_COUNTS, h + W_COUNTS, admit_piece, &a, &inserted};
-            size_t k = 0;
-            rc = dev_cdc_dedupe_compress(x, p, comp_alg, d_piece, len, i + 1 == n, a.base_k, (uint64_t *)c->off.p, cap, w + W_NCHUNKS, c->dig.p,
-                                         (uint64_t *)c->ref.p, (uint32_t *)c->new_idx.p, w + W_NNEW, c->slots.p, slots_bytes, (uint32_t *)c->sizes.p, &k,
-                                         s, &hook);
-            if (rc == CW_ERR_NOMEM && !inserted) { *refused = true; return CW_OK; }
-            if (rc == CW_ERR_NOMEM) return fail(CW_ERR_STATE, "cw_store_ingest: device memory ran out behind an admitted piece");
-            if (rc != CW_OK) return rc;
-            rc = cw_dev_store_chunks(comp_alg, d_piece, len, (uint64_t *)c->off.p, w + W_NCHUNKS, cap - 1, (uint32_t *)c->new_idx.p, w + W_NNEW,
-                                     c->slots.p, (uint32_t *)c->sizes.p, a.base_k, st->d_store, st->store_bytes, st->d_used, st->d_dir, st->dir_base,
-                                     st->dir_entries, w + W_RESULT, s);
-            if (rc == CW_OK)
-                rc = cw_dev_ingest_commit((uint64_t *)c->ref.p, (uint64_t *)c->off.p, w + W_NCHUNKS, cap - 1, w + W_NNEW, w + W_RESULT, done,
-                                          (uint64_t *)c->rec_ref.p, (uint64_t *)c->rec_off.p, w + W_REC_COUNT, rec_cap, w + W_STATS, w + W_VERDICT, s);
-            if (rc != CW_OK) return rc == CW_ERR_NOMEM ? fail(CW_ERR_STATE, "cw_store_ingest: no scratch behind an admitted piece") : rc;
-            const size_t consumed = (size_t)h[W_COUNTS + 1];
-            if (i + 1 < n) { // the bytes behind the last cut (< max_size) go in front of the next piece's fresh bytes
-                carry = len - consumed;
-                if (carry > front) return fail(CW_ERR_STATE, "cw_store_ingest: a carry of %zu bytes", carry);
-                if (carry) HIP_TRY(hipMemcpyAsync((uint8_t *)c->src[b ^ 1].p + front - carry, d_piece + consumed, carry, hipMemcpyDeviceToDevice, s));
-            }
-            HIP_TRY(hipEventRecord(c->ev_done[b], s));
-            k_total += k;
-            done += consumed;
-        }
-        return rc;
-    }
-};
-
-
-// cw_store_ingest_streams: Ingest over the concatenation of many spans.  A piece takes the stream ends not yet taken that lie at or
-// before its end; when the last of them is not the piece's end, the piece's own length is one more end and its last stream is open.
-struct IngestStreams {
-    cw_dedupe_t *x; const cw_cdc_params *p; int comp_alg; const cw_store *st;
-    const uint8_t *const *srcs; const uint64_t *lens; size_t nstreams; uint64_t total, base;
-    StoreCtx *c; hipStream_t s, s_h2d;
-    size_t piece, front, cap, slots_bytes, rec_cap, most; // as Ingest's; most = the largest stream count of a piece
+    const uint8_t *const *srcs; const uint64_t *lens; size_t nspans; uint64_t total, base;
+    bool indexed;
+    StoreCtx *c = nullptr; hipStream_t s = nullptr, s_h2d = nullptr;
+    size_t piece = 0, front = 0, cap = 0, slots_bytes = 0, rec_cap = 0; // P, F, a piece's max_offsets, its slot bytes, the recipe's entries
+    size_t most = 1;                                  // the largest stream count of a piece
     size_t k_total = 0; uint64_t done = 0;            // chunks and bytes of the pieces that went in
-    size_t taken = 0; uint64_t taken_end = 0;         // the streams whose end a piece has taken, and the last of those ends
-    bool open = false;                                // the last piece that went in left its last stream open (its entry is written)
+    size_t taken = 0; uint64_t taken_end = 0;         // indexed: the streams whose end a piece has taken, and the last of those ends
+    bool open = false;                                // indexed: the last piece that went in left its last stream open (its entry is written)
     size_t up_f = 0; uint64_t up_at = 0;              // the upload's cursor: the span of the next fresh byte and the byte's place in it
 
     size_t pieces() const { return (size_t)((total + piece - 1) / piece); }
@@ -191,18 +136,50 @@ struct IngestStreams {
         for (size_t i = 0, n = pieces(); i < n; i++) {
             const uint64_t end = piece_end(i);
             size_t t = 0;
-            while (f < nstreams && cum + lens[f] <= end) { cum += lens[f++]; t++; }
+            while (f < nspans && cum + lens[f] <= end) { cum += lens[f++]; t++; }
             const size_t ns = t + (t && cum == end ? 0 : 1);
             if (ns > most_) most_ = ns;
         }
         return most_;
     }
 
+    // The pieces' size and everything they need on the device (total > 0).  With one stream most = 1, and cap, rec_cap and slots_bytes
+    // are cw_store_ingest's (max_size + P) / min_size + 2 and nbytes / min_size + 2; with many they are cw_store_ingest_streams'.
+    int prepare(const cw::CdcParams &cp)
+    {
+        piece = piece_bytes(cp.max_size);
+        if (piece > total) piece = total > cp.max_size ? (size_t)total : cp.max_size; // one piece: no more than it needs
+        front = ((size_t)cp.max_size + 255) & ~(size_t)255;
+        most = indexed ? most_streams() : 1;
+        cap = (cp.max_size + piece) / cp.min_size + most + 1;
+        slots_bytes = cw_chunk_slots_bytes(comp_alg, cp.max_size + piece, cap - 1);
+        rec_cap = (size_t)(total / cp.min_size) + nspans + 1;
+        // one pageable buffer is staged piece by piece: both staging buffers before the first piece is queued, so that running out of
+        // page-locked memory fails the call with nothing ingested (the streams of an indexed call reserve theirs when a piece needs it)
+        const bool stage_now = !indexed && !is_pinned(srcs[0]);
+        int rc;
+        for (size_t b = 0, two = pieces() > 1 ? 2 : 1; b < two; b++) {
+            if ((rc = c->src[b].reserve(front + piece + 16)) != CW_OK) return rc; // (+16: the scan loads whole granules)
+            if (stage_now && (rc = c->stage[b].reserve(piece)) != CW_OK) return rc;
+        }
+        if ((rc = c->off.reserve(cap * 8)) != CW_OK || (rc = c->dig.reserve(cap * 64)) != CW_OK || (rc = c->ref.reserve(cap * 8)) != CW_OK ||
+            (rc = c->new_idx.reserve(cap * 4)) != CW_OK || (rc = c->sizes.reserve(cap * 4)) != CW_OK || (rc = c->slots.reserve(slots_bytes)) != CW_OK ||
+            (rc = c->rec_ref.reserve(rec_cap * 8)) != CW_OK || (rc = c->rec_off.reserve(rec_cap * 8)) != CW_OK)
+            return rc;
+        if (indexed && ((rc = c->ends.reserve(most * 8)) != CW_OK || (rc = c->first.reserve((most + 1) * 8)) != CW_OK ||
+                        (rc = c->h_ends.reserve(most * 8)) != CW_OK || (rc = c->rec_first.reserve((nspans + 1) * 8)) != CW_OK))
+            return rc;
+        if ((rc = c->words.reserve(W_WORDS * 8)) != CW_OK || (rc = c->h_words.reserve(W_WORDS * 8)) != CW_OK) return rc;
+        HIP_TRY(hipMemsetAsync(c->words.p, 0, W_WORDS * 8, s));
+        HIP_TRY(hipMemsetAsync(c->rec_off.p, 0, 8, s));
+        return CW_OK;
+    }
+
     int upload(size_t i)
     {
         const int b = (int)(i & 1);
         const size_t take = (size_t)(piece_end(i) - (uint64_t)i * piece);
-        // the span parts behind the fresh bytes: in place when they lie back to back in page-locked memory
+        // the span parts behind the fresh bytes: in place when they lie back to back in page-locked memory (one span: when it is page-locked)
         size_t f = up_f;
         uint64_t at = up_at;
         const uint8_t *first = nullptr, *next = nullptr;
@@ -251,52 +228,81 @@ struct IngestStreams {
             if (i + 1 < n && (rc = upload(i + 1)) != CW_OK) return rc;
             const uint64_t end = piece_end(i);
             const size_t take = (size_t)(end - (uint64_t)i * piece), len = carry + take;
-            if (done + len != end) return fail(CW_ERR_STATE, "cw_store_ingest_streams: piece %zu does not start where the last one stopped", i);
-            // the piece's streams: the ends it takes, rebased to its origin (= done), and its own length when its last stream stays open
-            size_t t = 0;
+            // indexed, the piece's streams: the ends it takes, rebased to its origin (= done), and its own length when its last stream
+            // stays open.  closed: the chunker cuts at the piece's end
+            size_t t = 0, ns = 0;
             uint64_t cum = taken_end;
-            while (taken + t < nstreams && cum + lens[taken + t] <= end) { cum += lens[taken + t]; h_ends[t++] = cum - done; }
-            const bool final_ = t && cum == end;
-            if (!final_) h_ends[t] = len;
-            const size_t ns = t + (final_ ? 0 : 1);
-            if (ns > most) return fail(CW_ERR_STATE, "cw_store_ingest_streams: %zu streams in a piece sized for %zu", ns, most);
-            HIP_TRY(hipMemcpyAsync(c->ends.p, h_ends, ns * 8, hipMemcpyHostToDevice, s)); // (the last piece's copy left h_ends before its synchronise)
+            bool closed = i + 1 == n;
+            if (indexed) {
+                if (done + len != end) return fail(CW_ERR_STATE, "%s: piece %zu does not start where the last one stopped", name, i);
+                while (taken + t < nspans && cum + lens[taken + t] <= end) { cum += lens[taken + t]; h_ends[t++] = cum - done; }
+                closed = t && cum == end;
+                if (!closed) h_ends[t] = len;
+                ns = t + (closed ? 0 : 1);
+                if (ns > most) return fail(CW_ERR_STATE, "%s: %zu streams in a piece sized for %zu", name, ns, most);
+                HIP_TRY(hipMemcpyAsync(c->ends.p, h_ends, ns * 8, hipMemcpyHostToDevice, s)); // (the last piece's copy left h_ends before its synchronise)
+            }
             uint8_t *d_piece = (uint8_t *)c->src[b].p + front - carry;
             HIP_TRY(hipStreamWaitEvent(s, c->ev_up[b], 0));
             Admission a{st, base + k_total};
             bool inserted = false;
             PieceAdmit hook{st->d_used, w + W_VERDICT, w + W_COUNTS, h + W_COUNTS, admit_piece, &a, &inserted};
-            const StreamList sl{(const uint64_t *)c->ends.p, ns, (uint64_t *)c->first.p, w + W_ENDS, final_ ? 1 : 0};
+            const StreamList sl{(const uint64_t *)c->ends.p, ns, (uint64_t *)c->first.p, w + W_ENDS, closed ? 1 : 0};
             size_t k = 0;
-            rc = dev_cdc_dedupe_compress(x, p, comp_alg, d_piece, len, 1, a.base_k, (uint64_t *)c->off.p, cap, w + W_NCHUNKS, c->dig.p,
+            rc = dev_cdc_dedupe_compress(x, p, comp_alg, d_piece, len, closed, a.base_k, (uint64_t *)c->off.p, cap, w + W_NCHUNKS, c->dig.p,
                                          (uint64_t *)c->ref.p, (uint32_t *)c->new_idx.p, w + W_NNEW, c->slots.p, slots_bytes, (uint32_t *)c->sizes.p, &k,
-                                         s, &hook, &sl);
+                                         s, &hook, indexed ? &sl : nullptr);
             if (rc == CW_ERR_NOMEM && !inserted) { *refused = true; return CW_OK; }
-            if (rc == CW_ERR_NOMEM) return fail(CW_ERR_STATE, "cw_store_ingest_streams: device memory ran out behind an admitted piece");
-            if (rc == CW_ERR_BAD_ARG) return fail(CW_ERR_STATE, "cw_store_ingest_streams: the ends of piece %zu were refused", i);
+            if (rc == CW_ERR_NOMEM) return fail(CW_ERR_STATE, "%s: device memory ran out behind an admitted piece", name);
+            if (indexed && rc == CW_ERR_BAD_ARG) return fail(CW_ERR_STATE, "%s: the ends of piece %zu were refused", name, i);
             if (rc != CW_OK) return rc;
             rc = cw_dev_store_chunks(comp_alg, d_piece, len, (uint64_t *)c->off.p, w + W_NCHUNKS, cap - 1, (uint32_t *)c->new_idx.p, w + W_NNEW,
                                      c->slots.p, (uint32_t *)c->sizes.p, a.base_k, st->d_store, st->store_bytes, st->d_used, st->d_dir, st->dir_base,
                                      st->dir_entries, w + W_RESULT, s);
-            if (rc == CW_OK)
+            if (rc == CW_OK && indexed)
                 rc = cw_dev_ingest_commit_streams((uint64_t *)c->ref.p, (uint64_t *)c->off.p, w + W_NCHUNKS, cap - 1, w + W_NNEW, w + W_RESULT, done,
                                                   (uint64_t *)c->rec_ref.p, (uint64_t *)c->rec_off.p, w + W_REC_COUNT, rec_cap, w + W_STATS,
                                                   w + W_VERDICT, (const uint64_t *)c->first.p, ns, taken, open ? 1 : 0, (uint64_t *)c->rec_first.p,
-                                                  nstreams + 1, s);
-            if (rc != CW_OK) return rc == CW_ERR_NOMEM ? fail(CW_ERR_STATE, "cw_store_ingest_streams: no scratch behind an admitted piece") : rc;
+                                                  nspans + 1, s);
+            else if (rc == CW_OK)
+                rc = cw_dev_ingest_commit((uint64_t *)c->ref.p, (uint64_t *)c->off.p, w + W_NCHUNKS, cap - 1, w + W_NNEW, w + W_RESULT, done,
+                                          (uint64_t *)c->rec_ref.p, (uint64_t *)c->rec_off.p, w + W_REC_COUNT, rec_cap, w + W_STATS, w + W_VERDICT, s);
+            if (rc != CW_OK) return rc == CW_ERR_NOMEM ? fail(CW_ERR_STATE, "%s: no scratch behind an admitted piece", name) : rc;
             const size_t consumed = (size_t)h[W_COUNTS + 1];
-            if (final_ && consumed != len) return fail(CW_ERR_STATE, "cw_store_ingest_streams: a closed piece of %zu bytes consumed %zu", len, consumed);
+            if (indexed && closed && consumed != len) return fail(CW_ERR_STATE, "%s: a closed piece of %zu bytes consumed %zu", name, len, consumed);
             if (i + 1 < n) { // the bytes behind the last cut (< max_size) go in front of the next piece's fresh bytes
                 carry = len - consumed;
-                if (carry > front) return fail(CW_ERR_STATE, "cw_store_ingest_streams: a carry of %zu bytes", carry);
+                if (carry > front) return fail(CW_ERR_STATE, "%s: a carry of %zu bytes", name, carry);
                 if (carry) HIP_TRY(hipMemcpyAsync((uint8_t *)c->src[b ^ 1].p + front - carry, d_piece + consumed, carry, hipMemcpyDeviceToDevice, s));
             }
             HIP_TRY(hipEventRecord(c->ev_done[b], s));
             k_total += k;
             done += consumed;
-            taken += t; taken_end = cum; open = !final_;
+            if (indexed) { taken += t; taken_end = cum; open = !closed; }
         }
         return rc;
+    }
+
+    // The pieces, and what they left: *k chunks, their refs and offsets[0 .. *k] and the statistics, with nothing of the call in flight.
+    // CW_OK with *refused set: a piece was refused, and the recipe is that of the pieces before it
+    int run_and_collect(uint64_t *refs, uint64_t *offsets, size_t max_offsets, cw_ingest_stats *stats, size_t *k, bool *refused)
+    {
+        int rc = run(refused);
+        uint64_t *h = (uint64_t *)c->h_words.p;
+        if (rc == CW_OK) {
+            const hipError_t e = hipMemcpyAsync(h + W_VERDICT, (uint64_t *)c->words.p + W_VERDICT, (W_WORDS - W_VERDICT) * 8, hipMemcpyDeviceToHost, s);
+            if (e != hipSuccess) rc = fail(CW_ERR_HIP, "%s: the counts: %s", name, hipGetErrorString(e));
+        }
+        drain(s, s_h2d);
+        if (rc != CW_OK) return rc;
+        *k = (size_t)h[W_REC_COUNT];
+        if (h[W_VERDICT] || *k != k_total || *k + 1 > max_offsets)
+            return fail(CW_ERR_STATE, "%s: an admitted piece was not committed (verdict %llu, %zu of %zu chunks)", name, (unsigned long long)h[W_VERDICT],
+                        *k, k_total);
+        if (*k) HIP_TRY(hipMemcpy(refs, c->rec_ref.p, *k * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(offsets, c->rec_off.p, (*k + 1) * 8, hipMemcpyDeviceToHost));
+        if (stats) memcpy(stats, h + W_STATS, 5 * sizeof(uint64_t));
+        return CW_OK;
     }
 };
 
@@ -336,54 +342,19 @@ int cw_store_ingest(cw_dedupe_t *x, const cw_cdc_params *p, int comp_alg, const 
         return fail(CW_ERR_BAD_ARG, "max_offsets %zu < nbytes / min_size + 2 = %zu", max_offsets, nbytes / cp.min_size + 2);
     if ((rc = check_store(st)) != CW_OK) return rc;
     if (base > UINT64_MAX - (nbytes / cp.min_size + 1)) return fail(CW_ERR_BAD_ARG, "base + nbytes / min_size + 1 wraps");
-    Ingest g{x, p, comp_alg, st, (const uint8_t *)src, nbytes, base};
+    const uint8_t *const span = (const uint8_t *)src;
+    const uint64_t len = nbytes;
+    Ingest g{"cw_store_ingest", x, p, comp_alg, st, &span, &len, 1, len, base, false};
     hipStream_t s_d2h;
     if ((rc = ctx_store(&g.c, &g.s, &g.s_h2d, &s_d2h)) != CW_OK) return rc;
     offsets[0] = 0;
     if (nbytes == 0) return CW_OK;
 
-    const long knob = cw::knobs().store_piece;
-    size_t piece = knob ? (size_t)knob : kDefaultPiece;
-    if (piece < cp.max_size) piece = cp.max_size;
-    if (piece > nbytes) piece = nbytes > cp.max_size ? nbytes : cp.max_size; // one piece: no more than it needs
-    g.piece = piece;
-    g.front = ((size_t)cp.max_size + 255) & ~(size_t)255;
-    g.cap = (cp.max_size + piece) / cp.min_size + 2;
-    g.slots_bytes = cw_chunk_slots_bytes(comp_alg, cp.max_size + piece, g.cap - 1);
-    g.rec_cap = nbytes / cp.min_size + 2;
-    g.pinned = is_pinned(src);
-    StoreCtx &c = *g.c;
-    const size_t two = g.pieces() > 1 ? 2 : 1;
-    for (size_t b = 0; b < two; b++) {
-        if ((rc = c.src[b].reserve(g.front + piece + 16)) != CW_OK) return rc; // (+16: the scan loads whole granules)
-        if (!g.pinned && (rc = c.stage[b].reserve(piece)) != CW_OK) return rc;
-    }
-    if ((rc = c.off.reserve(g.cap * 8)) != CW_OK || (rc = c.dig.reserve(g.cap * 64)) != CW_OK || (rc = c.ref.reserve(g.cap * 8)) != CW_OK ||
-        (rc = c.new_idx.reserve(g.cap * 4)) != CW_OK || (rc = c.sizes.reserve(g.cap * 4)) != CW_OK || (rc = c.slots.reserve(g.slots_bytes)) != CW_OK ||
-        (rc = c.rec_ref.reserve(g.rec_cap * 8)) != CW_OK || (rc = c.rec_off.reserve(g.rec_cap * 8)) != CW_OK ||
-        (rc = c.words.reserve(W_WORDS * 8)) != CW_OK || (rc = c.h_words.reserve(W_WORDS * 8)) != CW_OK)
-        return rc;
-    HIP_TRY(hipMemsetAsync(c.words.p, 0, W_WORDS * 8, g.s));
-    HIP_TRY(hipMemsetAsync(c.rec_off.p, 0, 8, g.s));
-
+    size_t k = 0;
     bool refused = false;
-    rc = g.run(&refused);
-    uint64_t *h = (uint64_t *)c.h_words.p;
-    if (rc == CW_OK) {
-        const hipError_t e = hipMemcpyAsync(h + W_VERDICT, (uint64_t *)c.words.p + W_VERDICT, (W_WORDS - W_VERDICT) * 8, hipMemcpyDeviceToHost, g.s);
-        rc = launched(e, "cw_store_ingest: the counts");
-    }
-    drain(g.s, g.s_h2d);
-    if (rc != CW_OK) return rc;
-    const size_t k = (size_t)h[W_REC_COUNT];
-    if (h[W_VERDICT] || k != g.k_total || k + 1 > max_offsets)
-        return fail(CW_ERR_STATE, "cw_store_ingest: an admitted piece was not committed (verdict %llu, %zu of %zu chunks)", (unsigned long long)h[W_VERDICT],
-                    k, g.k_total);
-    if (k) HIP_TRY(hipMemcpy(refs, c.rec_ref.p, k * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(offsets, c.rec_off.p, (k + 1) * 8, hipMemcpyDeviceToHost));
+    if ((rc = g.prepare(cp)) != CW_OK || (rc = g.run_and_collect(refs, offsets, max_offsets, stats, &k, &refused)) != CW_OK) return rc;
     *nchunks = k;
     *consumed = (size_t)offsets[k];
-    if (stats) memcpy(stats, h + W_STATS, 5 * sizeof(uint64_t));
     if (refused) return CW_ERR_NOMEM; // (the message is the admission's)
     return *consumed == nbytes ? CW_OK : fail(CW_ERR_STATE, "cw_store_ingest: %zu of %zu bytes went in", *consumed, nbytes);
 }
@@ -435,7 +406,7 @@ int cw_store_ingest_streams(cw_dedupe_t *x, const cw_cdc_params *p, int comp_alg
                     (unsigned long long)(total / cp.min_size + nstreams + 1));
     if ((rc = check_store(st)) != CW_OK) return rc;
     if (base > UINT64_MAX - (total / cp.min_size + nstreams)) return fail(CW_ERR_BAD_ARG, "base + nbytes / min_size + nstreams wraps");
-    IngestStreams g{x, p, comp_alg, st, (const uint8_t *const *)srcs, lens, nstreams, total, base};
+    Ingest g{"cw_store_ingest_streams", x, p, comp_alg, st, (const uint8_t *const *)srcs, lens, nstreams, total, base, true};
     hipStream_t s_d2h;
     if ((rc = ctx_store(&g.c, &g.s, &g.s_h2d, &s_d2h)) != CW_OK) return rc;
     offsets[0] = 0;
@@ -444,53 +415,16 @@ int cw_store_ingest_streams(cw_dedupe_t *x, const cw_cdc_params *p, int comp_alg
     if (total == 0) return CW_OK; // (no stream, or empty ones only: no chunk, no piece)
     *streams_done = 0;
 
-    const long knob = cw::knobs().store_piece;
-    size_t piece = knob ? (size_t)knob : kDefaultPiece;
-    if (piece < cp.max_size) piece = cp.max_size;
-    if (piece > total) piece = total > cp.max_size ? (size_t)total : cp.max_size; // one piece: no more than it needs
-    g.piece = piece;
-    g.front = ((size_t)cp.max_size + 255) & ~(size_t)255;
-    g.most = g.most_streams();
-    g.cap = (cp.max_size + piece) / cp.min_size + g.most + 1;
-    g.slots_bytes = cw_chunk_slots_bytes(comp_alg, cp.max_size + piece, g.cap - 1);
-    g.rec_cap = (size_t)(total / cp.min_size) + nstreams + 1;
-    StoreCtx &c = *g.c;
-    const size_t two = g.pieces() > 1 ? 2 : 1;
-    for (size_t b = 0; b < two; b++)
-        if ((rc = c.src[b].reserve(g.front + piece + 16)) != CW_OK) return rc; // (+16: the scan loads whole granules)
-    if ((rc = c.off.reserve(g.cap * 8)) != CW_OK || (rc = c.dig.reserve(g.cap * 64)) != CW_OK || (rc = c.ref.reserve(g.cap * 8)) != CW_OK ||
-        (rc = c.new_idx.reserve(g.cap * 4)) != CW_OK || (rc = c.sizes.reserve(g.cap * 4)) != CW_OK || (rc = c.slots.reserve(g.slots_bytes)) != CW_OK ||
-        (rc = c.rec_ref.reserve(g.rec_cap * 8)) != CW_OK || (rc = c.rec_off.reserve(g.rec_cap * 8)) != CW_OK ||
-        (rc = c.ends.reserve(g.most * 8)) != CW_OK || (rc = c.first.reserve((g.most + 1) * 8)) != CW_OK || (rc = c.h_ends.reserve(g.most * 8)) != CW_OK ||
-        (rc = c.rec_first.reserve((nstreams + 1) * 8)) != CW_OK || (rc = c.words.reserve(W_WORDS * 8)) != CW_OK ||
-        (rc = c.h_words.reserve(W_WORDS * 8)) != CW_OK)
-        return rc;
-    HIP_TRY(hipMemsetAsync(c.words.p, 0, W_WORDS * 8, g.s));
-    HIP_TRY(hipMemsetAsync(c.rec_off.p, 0, 8, g.s));
-
+    size_t k = 0;
     bool refused = false;
-    rc = g.run(&refused);
-    uint64_t *h = (uint64_t *)c.h_words.p;
-    if (rc == CW_OK) {
-        const hipError_t e = hipMemcpyAsync(h + W_VERDICT, (uint64_t *)c.words.p + W_VERDICT, (W_WORDS - W_VERDICT) * 8, hipMemcpyDeviceToHost, g.s);
-        rc = launched(e, "cw_store_ingest_streams: the counts");
-    }
-    drain(g.s, g.s_h2d);
-    if (rc != CW_OK) return rc;
-    const size_t k = (size_t)h[W_REC_COUNT];
-    if (h[W_VERDICT] || k != g.k_total || k + 1 > max_offsets)
-        return fail(CW_ERR_STATE, "cw_store_ingest_streams: an admitted piece was not committed (verdict %llu, %zu of %zu chunks)",
-                    (unsigned long long)h[W_VERDICT], k, g.k_total);
-    if (k) HIP_TRY(hipMemcpy(refs, c.rec_ref.p, k * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(offsets, c.rec_off.p, (k + 1) * 8, hipMemcpyDeviceToHost));
+    if ((rc = g.prepare(cp)) != CW_OK || (rc = g.run_and_collect(refs, offsets, max_offsets, stats, &k, &refused)) != CW_OK) return rc;
     // the stream index: the entries the pieces wrote, then the stream that was not begun (or the end) and the entry behind it
     const size_t written = g.taken + (g.open ? 1 : 0);
-    if (written) HIP_TRY(hipMemcpy(stream_first, c.rec_first.p, written * 8, hipMemcpyDeviceToHost));
+    if (written) HIP_TRY(hipMemcpy(stream_first, g.c->rec_first.p, written * 8, hipMemcpyDeviceToHost));
     for (size_t f = written; f <= nstreams && f <= g.taken + 1; f++) stream_first[f] = k;
     *nchunks = k;
     *consumed = offsets[k];
     *streams_done = g.taken;
-    if (stats) memcpy(stats, h + W_STATS, 5 * sizeof(uint64_t));
     if (refused) return CW_ERR_NOMEM; // (the message is the admission's)
     return *consumed == total && g.taken == nstreams ? CW_OK
                                                      : fail(CW_ERR_STATE, "cw_store_ingest_streams: %llu of %llu bytes went in",
@@ -505,9 +439,7 @@ int cw_store_restore(int comp_alg, const cw_store *st, const uint64_t *refs, con
     if (rc != CW_OK || (rc = check_store(st)) != CW_OK) return rc;
     if (!offsets || !n_bad || (nchunks && !refs)) return fail(CW_ERR_BAD_ARG, "NULL pointer");
     // the windows: whole positions whose raw bytes fit a piece
-    const long knob = cw::knobs().store_piece;
-    size_t piece = knob ? (size_t)knob : kDefaultPiece;
-    if (piece < CW_MAX_BLOCK_BYTES) piece = CW_MAX_BLOCK_BYTES;
+    const size_t piece = piece_bytes(CW_MAX_BLOCK_BYTES);
     std::vector<size_t> first; // first position of every window, and the end
     size_t in_window = 0, most = 0, widest = 0;
     for (size_t j = 0; j < nchunks; j++) {
@@ -594,9 +526,7 @@ int cw_store_scrub(cw_dedupe_t *x, int comp_alg, const cw_store *st, const uint3
     if (rc != CW_OK || (rc = check_store(st)) != CW_OK) return rc;
     if (!x) return fail(CW_ERR_BAD_ARG, "NULL dedupe index");
     if ((rc = check_count("dir_entries", st->dir_entries)) != CW_OK) return rc;
-    const long knob = cw::knobs().store_piece;
-    size_t piece = knob ? (size_t)knob : kDefaultPiece;
-    if (piece < CW_MAX_BLOCK_BYTES) piece = CW_MAX_BLOCK_BYTES;
+    const size_t piece = piece_bytes(CW_MAX_BLOCK_BYTES);
     StoreCtx *cp;
     hipStream_t s, s_h2d, s_d2h;
     if ((rc = ctx_store(&cp, &s, &s_h2d, &s_d2h)) != CW_OK) return rc;

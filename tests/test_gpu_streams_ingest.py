@@ -13,7 +13,8 @@ import pytest
 import ingest_model as IM
 import restore_model as RM
 import streams_ingest_model as XM
-from test_streams_ingest_abi import ALGS, BIG, CASES, REFUSED, expected, refusal, streams_of
+from test_ingest_abi import dups
+from test_streams_ingest_abi import ALGS, BIG, CASES, P1K, REFUSED, expected, refusal, streams_of
 
 pytestmark = pytest.mark.gpu
 NOMEM = -5
@@ -293,3 +294,59 @@ def test_commit_streams_that_is_refused_leaves_every_byte_as_it_was(cw, why):
     assert r.commit(cw, *piece, [0, 9], 0, [0, 2], 2, False) == 0
     r.check(0)
     assert r.x_ref[:3] == [7, 8, 9] and r.x_first[:4] == [0, 1, 3, 5]
+
+
+def commit_plain(cw, r: Growing, refs, offsets, n_dev, max_chunks, n_new, result, stream_off):
+    """cw_dev_ingest_commit into the recipe of a Growing, on the stream its commit() uses; ingest_model's call on the image."""
+    import torch
+    pad = [CANARY] * 3
+    r.keep = [_dev_u64(list(refs) + pad), _dev_u64(list(offsets) + pad), _dev_u64([n_dev, CANARY]), _dev_u64([n_new, CANARY]),
+              _dev_u64(list(result) + pad) if result is not None else None]
+    d_ref, d_off, d_n, d_new, d_res = r.keep
+    torch.cuda.synchronize()
+    cw.dev_ingest_commit(d_ref.data_ptr(), d_off.data_ptr(), d_n.data_ptr(), max_chunks, d_new.data_ptr(), d_res.data_ptr() if result is not None else 0,
+                         stream_off, r.ref.data_ptr(), r.off.data_ptr(), r.count.data_ptr(), r.rec_cap, r.stats.data_ptr(), r.verdict.data_ptr(),
+                         _stream())
+    verdict, r.x_count = IM.commit(refs, offsets, min(n_dev, max_chunks), n_new, result, stream_off, r.x_ref, r.x_off, r.x_count, r.rec_cap, r.x_stats)
+    return verdict
+
+
+def test_plain_and_streams_commits_interleave_on_one_stream_into_one_recipe(cw):
+    """One pair of kernels and one launch sequence behind both entry points: plain, streams, plain into one recipe is the two models
+    applied in that order, and the plain commits leave the stream index alone."""
+    r = Growing(rec_cap=20, first_cap=8)
+    assert commit_plain(cw, r, [7, 8, 9], [0, 10, 30, 60], 3, 3, 2, [0, 55], 0) == 0
+    r.check(0)
+    assert r.x_count == 3 and r.x_first == [CANARY] * 12
+    assert r.commit(cw, [70, 80, 90, 91], [5, 15, 35, 65, 66], 4000, 4, 0, [0, 0], (1 << 40) - 3, [0, 1, 4], 2, True) == 0
+    r.check(0)
+    assert r.x_count == 7 and r.x_first[:5] == [CANARY, CANARY, CANARY, 4, 7]
+    assert commit_plain(cw, r, list(range(12)), list(range(0, 130, 10)), 5000, 12, 1, [0, 3], 100) == 0   # exactly full: 7 + 12 + 1 = 20
+    r.check(0)
+    assert r.x_count == 19 and r.x_off[7:20] == list(range(100, 230, 10)) and r.x_ref[7:19] == list(range(12))
+    assert r.x_first[:5] == [CANARY, CANARY, CANARY, 4, 7] and r.x_stats == [60 + 61 + 120, 19, 3, 58, 3]
+    # a refused plain commit behind them (19 + 1 + 1 > 20) changes nothing, in the recipe or in the stream index
+    assert commit_plain(cw, r, [1], [0, 1], 1, 1, 1, [0, 1], 0) == 2
+    r.check(2)
+
+
+# ---- one stream through both entry points ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("alg", ALGS)
+def test_both_entry_points_leave_the_same_for_one_stream(cw, alg):
+    """cw_store_ingest and cw_store_ingest_streams of one pageable buffer in five pieces of an odd size, with carries: the one piece
+    loop with and without the stream index."""
+    data = dups()[100000:400000]    # text, a block repeated at short distances, noise, text
+    assert len(data) == 300000
+    with Pair(cw, alg, P1K) as a, Pair(cw, alg, P1K) as b:
+        with cw.tuned(CW_STORE_PIECE=70001):
+            ra = a.ingest_stream(data)
+            rb, = b.ingest_many_stream([data])
+        assert a.last_stats["pieces"] == 5 and 0 < a.last_stats["new_chunks"] < a.last_stats["chunks"] == len(ra.refs)
+        assert a.last_stats == b.last_stats
+        assert ra.refs.tolist() == rb.refs.tolist() and ra.offsets.tolist() == rb.offsets.tolist() and int(ra.offsets[-1]) == len(data)
+        assert a.used() == b.used() > 0 and a.base == b.base == 5 + len(ra.refs)
+        assert a.d_dir.cpu().numpy().tobytes() == b.d_dir.cpu().numpy().tobytes()
+        assert a.d_store[:a.used()].cpu().numpy().tobytes() == b.d_store[:b.used()].cpu().numpy().tobytes()
+        assert a.index.count() == b.index.count()
+        with cw.tuned(CW_STORE_PIECE=70001):
+            assert a.restore_stream(ra) == data and b.restore_stream(rb) == data

@@ -312,17 +312,21 @@ def _meta(asm):
 def test_commit_streams_kernels_have_no_private_segment_or_spills(tmp_path):
     out = str(tmp_path / "k.s")
     subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-S", "--cuda-device-only", "--offload-arch=gfx950",
-                    os.path.join(ROOT, "compute_war_amd", "csrc", "commit_streams_kernels.hip"), "-o", out], check=True, capture_output=True)
+                    os.path.join(ROOT, "compute_war_amd", "csrc", "ingest_kernels.hip"), "-o", out], check=True, capture_output=True)
     meta = _meta(open(out).read())
-    assert len(meta) == 2, sorted(meta)
-    for kernel in ("commit_streams_copy_kernel", "commit_streams_finish_kernel"):
+    # the one pair of commit kernels serves both commits (tests/test_ingest_abi.py counts the file's kernels): each takes the stream list
+    for kernel in ("commit_copy_kernel", "commit_finish_kernel"):
         assert sum(kernel in k for k in meta) == 1, kernel
+        assert sum(kernel in k and "CommitStreams" in k for k in meta) == 1, kernel
+    assert not any("commit_streams" in k for k in meta), sorted(meta)
     for name, e in meta.items():
         assert re.search(r"\.private_segment_fixed_size:\s+0\b", e), name
         assert re.search(r"\.vgpr_spill_count:\s+0\b", e), name
         assert re.search(r"\.sgpr_spill_count:\s+0\b", e), name
     makefile = open(os.path.join(ROOT, "compute_war_amd", "csrc", "Makefile")).read()
-    assert "commit_streams_kernels.hip" in re.search(r"^SRCS\s*:=(.*)$", makefile, flags=re.M).group(1)
+    srcs = re.search(r"^SRCS\s*:=(.*)$", makefile, flags=re.M).group(1)
+    assert "ingest_kernels.hip" in srcs and "commit_streams_kernels.hip" not in srcs
+    assert not os.path.exists(os.path.join(ROOT, "compute_war_amd", "csrc", "commit_streams_kernels.hip"))
 
 
 # ---- the model ---------------------------------------------------------------------------------------------------------------
