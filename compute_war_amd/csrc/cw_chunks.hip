@@ -1,6 +1,6 @@
 // cw_chunks.hip -- host side of the device-resident calls over content-defined chunks: the cut (kernels: cdc_kernels.hip), the per-chunk
 // hash, the chunk codecs and their pack (chunk_codec_kernels.hip, pack_kernels.hip), the chunk store (restore_kernels.hip), its ranged reads (read_kernels.hip),
-// its mark and compact (store_gc_kernels.hip) and its chunk bundles (replicate_kernels.hip).  Semantics: the public header.  Every refusal here comes before the device is touched.
+// its mark and compact (store_gc_kernels.hip), its renumbering (renumber_kernels.hip) and its chunk bundles (replicate_kernels.hip).  Semantics: the public header.  Every refusal here comes before the device is touched.
 
 #include "cw_host.h"
 
@@ -329,6 +329,28 @@ int cw_dev_store_compact(const void *d_store, size_t store_bytes, const cw_chunk
     return launched_nomem(cw::store_compact_launch((const uint8_t *)d_store, store_bytes, d_dir, dir_entries, d_live, (uint8_t *)d_new_store,
                                                    new_store_bytes, d_new_used, d_new_dir, d_result, (hipStream_t)stream),
                           "store compact launch");
+}
+
+// ---- the directory gives slots back: renumber (kernels: renumber_kernels.hip) --------------------------------------------------
+int cw_dev_store_renumber(const cw_chunk_loc *d_dir, uint64_t dir_base, size_t dir_entries, const uint32_t *d_live, uint64_t new_base,
+                          cw_chunk_loc *d_new_dir, uint64_t new_dir_base, size_t new_dir_entries, uint64_t *d_from, uint64_t *d_to, size_t max_pairs,
+                          uint64_t *d_result, void *stream)
+{
+    int rc;
+    if (!d_dir || !d_result || (new_dir_entries && !d_new_dir) || (max_pairs && (!d_from || !d_to))) return fail(CW_ERR_BAD_ARG, "NULL pointer");
+    if (dir_entries == 0) return fail(CW_ERR_BAD_ARG, "dir_entries is 0");
+    if ((rc = check_count("dir_entries", dir_entries)) != CW_OK || (rc = check_count("new_dir_entries", new_dir_entries)) != CW_OK ||
+        (rc = check_count("max_pairs", max_pairs)) != CW_OK)
+        return rc;
+    if ((rc = check_dir_aligned((uintptr_t)d_dir | (uintptr_t)d_new_dir, "d_dir / d_new_dir")) != CW_OK) return rc;
+    if ((rc = check_word_aligned((uintptr_t)d_from | (uintptr_t)d_to | (uintptr_t)d_result, "d_from / d_to / d_result")) != CW_OK) return rc;
+    if (ranges_overlap(d_dir, dir_entries * sizeof(cw_chunk_loc), d_new_dir, new_dir_entries * sizeof(cw_chunk_loc)))
+        return fail(CW_ERR_BAD_ARG, "d_new_dir overlaps d_dir");
+    if (new_dir_base > UINT64_MAX - new_dir_entries) return fail(CW_ERR_BAD_ARG, "new_dir_base + new_dir_entries wraps");
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    return launched_nomem(cw::store_renumber_launch(d_dir, dir_base, dir_entries, d_live, new_base, d_new_dir, new_dir_base, new_dir_entries, d_from,
+                                                    d_to, max_pairs, d_result, (hipStream_t)stream),
+                          "store renumber launch");
 }
 
 // ---- chunk bundles between stores: export, import, translate (kernels: replicate_kernels.hip) ----------------------------------

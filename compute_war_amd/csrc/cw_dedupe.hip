@@ -326,6 +326,28 @@ int cw_dev_dedupe_export_live(cw_dedupe_t *x, const uint32_t *d_live, uint64_t d
     });
 }
 
+// The index's side of a renumbering: values change in place (value[] lies apart from the keys), so there is no rebuild and the count
+// bound stays.  The two counters go into the index's scratch (rec).
+int cw_dev_dedupe_revalue(cw_dedupe_t *x, const uint64_t *d_from, const uint64_t *d_to, const uint64_t *d_npairs, size_t max_pairs,
+                          uint64_t range_base, uint64_t range_entries, uint64_t *d_result, void *stream)
+{
+    int rc;
+    if (!x || !d_from || !d_to || !d_npairs || !d_result) return fail(CW_ERR_BAD_ARG, "NULL %s", x ? "pointer" : "dedupe index");
+    if (((uintptr_t)d_from | (uintptr_t)d_to | (uintptr_t)d_npairs | (uintptr_t)d_result) % 8)
+        return fail(CW_ERR_BAD_ARG, "d_from / d_to / d_npairs / d_result not 8-byte aligned");
+    if ((rc = check_count("max_pairs", max_pairs)) != CW_OK) return rc;
+    if (range_base > UINT64_MAX - range_entries) return fail(CW_ERR_BAD_ARG, "range_base + range_entries wraps");
+    if ((rc = dedupe_args(x, 0, 0)) != CW_OK) return rc;
+    const hipStream_t s = (hipStream_t)stream;
+    return dedupe_on_stream(x, s, [&]() -> int {
+        const int ok = dedupe_scratch(x, x->rec, 64);
+        if (ok != CW_OK) return ok;
+        return launched(cw::dedupe_revalue_launch(x->t.state, x->t.value, x->cap, d_from, d_to, d_npairs, max_pairs, range_base, range_entries,
+                                                  (uint64_t *)x->rec.p, d_result, s),
+                        "dedupe revalue launch");
+    });
+}
+
 // One window of a scrub: the plan, the restore and the finish are scrub_kernels.hip's; between restore and finish the index judges --
 // the hash of the window's chunks, then one sweep of the table.  Read-only for the index, serialised with its other calls.
 int cw_dev_store_verify(cw_dedupe_t *x, int comp_alg, const void *d_store, size_t store_bytes, const cw_chunk_loc *d_dir, uint64_t dir_base,

@@ -124,6 +124,11 @@ hipError_t dedupe_rehash_launch(unsigned words, const uint64_t *old_state, const
 hipError_t dedupe_retain_launch(unsigned words, const uint64_t *old_state, const uint64_t *old_value, const uint64_t *old_key, uint64_t old_cap,
                                 const uint32_t *live, uint64_t dir_base, uint64_t dir_entries, uint64_t *state, uint64_t *value, uint64_t *key,
                                 uint64_t mask, unsigned long long *n_kept, unsigned long long *err, hipStream_t s);
+// values through the ascending pairs from[0..min(*d_npairs, max_pairs)) -> to (cw_dev_dedupe_revalue): head[2] is the caller's scratch
+// (hits, stale); result[3] = {verdict, hits, stale}; value[] changes only when no committed entry is stale
+hipError_t dedupe_revalue_launch(const uint64_t *state, uint64_t *value, uint64_t cap, const uint64_t *from, const uint64_t *to,
+                                 const uint64_t *d_npairs, uint64_t max_pairs, uint64_t range_base, uint64_t range_entries, uint64_t *head,
+                                 uint64_t *result, hipStream_t s);
 // block new_idx[j] (src_stride apart in src) -> dst + j * block_bytes, for j < n_new
 hipError_t dedupe_gather_launch(const uint8_t *src, size_t block_bytes, size_t src_stride, const uint32_t *new_idx, size_t n_new,
                                 uint8_t *dst, hipStream_t s);
@@ -263,6 +268,11 @@ hipError_t store_mark_launch(const uint64_t *ref, const uint64_t *d_count, size_
 hipError_t store_compact_launch(const uint8_t *store, size_t store_bytes, const void *dir, size_t dir_entries, const uint32_t *live,
                                 uint8_t *new_store, size_t new_store_bytes, uint64_t *new_used, void *new_dir, uint64_t *result,
                                 hipStream_t stream);
+
+// renumber (renumber_kernels.hip; semantics: the public header).  live may be NULL; new_dir, from and to may be when their counts are 0
+hipError_t store_renumber_launch(const void *dir, uint64_t dir_base, size_t dir_entries, const uint32_t *live, uint64_t new_base, void *new_dir,
+                                 uint64_t new_dir_base, size_t new_dir_entries, uint64_t *from, uint64_t *to, size_t max_pairs, uint64_t *result,
+                                 hipStream_t stream);
 
 // chunk bundles between stores (replicate_kernels.hip; semantics: the public header).  loc / dir: cw_chunk_loc entries, 16-byte aligned
 hipError_t store_export_launch(const uint8_t *store, size_t store_bytes, const void *dir, uint64_t dir_base, size_t dir_entries,

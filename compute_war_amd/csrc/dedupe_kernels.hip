@@ -1,6 +1,7 @@
 // dedupe_kernels.hip -- device-resident fingerprint index (cw_dedupe_*, cw_dev_dedupe*): batched lookup-or-insert of full
 // digests in an open-addressed table with linear probing, on gfx950, and the index's lifecycle: read-only lookup, export, the export of
-// a directory's flagged entries in value order (cw_dev_dedupe_export_live), the rehash of cw_dedupe_resize and the filtered rehash of cw_dedupe_retain.  The reference has no counterpart: HashAndCompress.cpp computes the digests and drops them (:257,
+// a directory's flagged entries in value order (cw_dev_dedupe_export_live), the rehash of cw_dedupe_resize, the filtered rehash of cw_dedupe_retain and the
+// values rewritten in place by cw_dev_dedupe_revalue.  The reference has no counterpart: HashAndCompress.cpp computes the digests and drops them (:257,
 // SURVEY.md D3).
 //
 // Table (allocated by cw_dedupe_create and again by cw_dedupe_resize; capacity a power of two >= 2 x max_entries, so the load stays <= 0.5):
@@ -433,6 +434,78 @@ dedupe_verify_sweep_kernel(const uint64_t *__restrict__ state, const uint64_t *_
     }
 }
 
+// ---- values through a list of pairs (cw_dev_dedupe_revalue) ---------------------------------------------
+// What translate_refs_kernel does to a recipe, done to value[]: the keys, the states and the count stay, so nothing is rehashed.  Two
+// sweeps, one lane per slot, plain loads of state and value as in the lookup.  The count sweep looks every committed value up in the
+// ascending from[0..np) with a binary search: a hit is a translation, a miss inside [range_base, range_base + range_entries) is
+// stale; both are counted per workgroup as the retain counts.  Behind the kernel boundary the apply sweep does nothing when an entry
+// is stale, else repeats the search and stores to[k] over the value -- plain stores: each slot is read and written by one lane, once,
+// and the index serialises its calls.  Block 0's first thread reports.
+// the pair that from[k] == v names, or np
+__device__ __forceinline__ uint64_t revalue_find(const uint64_t *__restrict__ from, uint64_t np, uint64_t v)
+{
+    uint64_t lo = 0, hi = np; // the first pair with from >= v
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (from[mid] < v) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < np && from[lo] == v ? lo : np;
+}
+
+__global__ void __launch_bounds__(kThreads)
+dedupe_revalue_count_kernel(const uint64_t *__restrict__ state, const uint64_t *__restrict__ value, uint64_t cap,
+                            const uint64_t *__restrict__ from, const uint64_t *__restrict__ d_npairs, uint64_t max_pairs, uint64_t range_base,
+                            uint64_t range_entries, unsigned long long *__restrict__ head)
+{
+    const uint64_t np = umin64(*d_npairs, max_pairs);
+    uint32_t hits = 0, stale = 0; // (a lane sees at most cap / (gridDim.x * kThreads) + 1 < 2^32 slots)
+    for (uint64_t o = (uint64_t)blockIdx.x * kThreads + threadIdx.x; o < cap; o += (uint64_t)gridDim.x * kThreads) {
+        if (state[o] != kCommitted) continue;
+        const uint64_t v = value[o];
+        if (revalue_find(from, np, v) < np) hits++;
+        else if (v - range_base < range_entries) stale++; // a value below the base wraps out of range
+    }
+    __shared__ uint32_t whits[kThreads / 64], wstale[kThreads / 64];
+    for (int off = 32; off > 0; off >>= 1) {
+        hits += __shfl_down(hits, off, 64);
+        stale += __shfl_down(stale, off, 64);
+    }
+    if ((threadIdx.x & 63u) == 0) {
+        whits[threadIdx.x >> 6] = hits;
+        wstale[threadIdx.x >> 6] = stale;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    uint32_t h = 0, s = 0;
+    for (uint32_t w = 0; w < kThreads / 64; w++) {
+        h += whits[w];
+        s += wstale[w];
+    }
+    if (h) __hip_atomic_fetch_add(head, (unsigned long long)h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (s) __hip_atomic_fetch_add(head + 1, (unsigned long long)s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ void __launch_bounds__(kThreads)
+dedupe_revalue_apply_kernel(const uint64_t *__restrict__ state, uint64_t *__restrict__ value, uint64_t cap, const uint64_t *__restrict__ from,
+                            const uint64_t *__restrict__ to, const uint64_t *__restrict__ d_npairs, uint64_t max_pairs,
+                            const unsigned long long *__restrict__ head, uint64_t *__restrict__ result)
+{
+    const uint64_t n_hits = head[0], n_stale = head[1];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        result[0] = n_stale != 0;
+        result[1] = n_hits;
+        result[2] = n_stale;
+    }
+    if (n_stale != 0 || n_hits == 0) return;
+    const uint64_t np = umin64(*d_npairs, max_pairs);
+    for (uint64_t o = (uint64_t)blockIdx.x * kThreads + threadIdx.x; o < cap; o += (uint64_t)gridDim.x * kThreads) {
+        if (state[o] != kCommitted) continue;
+        const uint64_t k = revalue_find(from, np, value[o]);
+        if (k < np) value[o] = to[k];
+    }
+}
+
 unsigned grid_of(uint32_t n) { return (n + kThreads - 1) / kThreads; }
 // grid-stride kernels over `tiles` tiles of kThreads slots
 unsigned grid_stride_of(uint64_t tiles) { return (unsigned)(tiles < (1u << 20) ? tiles : (1u << 20)); }
@@ -593,6 +666,19 @@ hipError_t dedupe_retain_launch(unsigned words, const uint64_t *old_state, const
     default: return hipErrorInvalidValue;
     }
 #undef CW_RETAIN
+    return hipGetLastError();
+}
+
+hipError_t dedupe_revalue_launch(const uint64_t *state, uint64_t *value, uint64_t cap, const uint64_t *from, const uint64_t *to,
+                                 const uint64_t *d_npairs, uint64_t max_pairs, uint64_t range_base, uint64_t range_entries, uint64_t *head,
+                                 uint64_t *result, hipStream_t s)
+{
+    const hipError_t e = hipMemsetAsync(head, 0, 2 * sizeof(uint64_t), s);
+    if (e != hipSuccess) return e;
+    const dim3 g(grid_stride_of(dedupe_export_tiles(cap))), b(kThreads);
+    unsigned long long *h = reinterpret_cast<unsigned long long *>(head);
+    hipLaunchKernelGGL(dedupe_revalue_count_kernel, g, b, 0, s, state, value, cap, from, d_npairs, max_pairs, range_base, range_entries, h);
+    hipLaunchKernelGGL(dedupe_revalue_apply_kernel, g, b, 0, s, state, value, cap, from, to, d_npairs, max_pairs, h, result);
     return hipGetLastError();
 }
 

@@ -417,6 +417,14 @@ class DedupeIndex:
         check(lib().cw_dev_dedupe_export_live(self._x(), d_live, dir_base, dir_entries, d_digests or None, d_values or None, max_out, d_result,
                                               stream))
 
+    def dev_revalue(self, d_from: int, d_to: int, d_npairs: int, max_pairs: int, range_base: int, range_entries: int, d_result: int,
+                    stream: int = 0) -> None:
+        """Every entry whose value is d_from[k] (ascending, k < min(*d_npairs, max_pairs)) gets the value d_to[k], in place: no
+        rehash, the count and the keys stay.  An entry with a value of [range_base, range_base + range_entries) that no pair names is
+        stale.  d_result[0..3) = verdict (1: an entry is stale, no value changed), entries translated, stale entries.  Not
+        synchronised."""
+        check(lib().cw_dev_dedupe_revalue(self._x(), d_from, d_to, d_npairs, max_pairs, range_base, range_entries, d_result, stream))
+
     def resize(self, max_entries: int) -> None:
         """Rebuild the table for ``max_entries`` (synchronous; at least ``count()``).  Every lookup answers as before."""
         check(lib().cw_dedupe_resize(self._x(), max_entries))
@@ -737,6 +745,17 @@ def dev_store_compact(d_store: int, store_bytes: int, d_dir: int, dir_entries: i
                                      d_new_used, d_new_dir, d_result, stream))
 
 
+def dev_store_renumber(d_dir: int, dir_base: int, dir_entries: int, d_live: int, new_base: int, d_new_dir: int, new_dir_base: int,
+                       new_dir_entries: int, d_from: int, d_to: int, max_pairs: int, d_result: int, stream: int = 0) -> None:
+    """The kept entries of d_dir (not all zero, and flagged by d_live unless that is 0) move bit for bit to the dense values
+    [new_base, new_base + K) of d_new_dir, whose other entries become zero; d_from[k] / d_to[k] = the k-th kept entry's old / new
+    value, ascending.  d_result[0..4) = verdict (2: the values leave the new directory or wrap, 1: K > max_pairs; nothing written
+    then), K, new_base + K, non-zero entries not kept.  d_new_dir = 0 with new_dir_entries = 0 and d_from = d_to = 0 with
+    max_pairs = 0 is a dry run.  Not synchronised."""
+    check(lib().cw_dev_store_renumber(d_dir, dir_base, dir_entries, d_live or None, new_base, d_new_dir or None, new_dir_base, new_dir_entries,
+                                      d_from or None, d_to or None, max_pairs, d_result, stream))
+
+
 def dev_store_export_chunks(d_store: int, store_bytes: int, d_dir: int, dir_base: int, dir_entries: int, d_values: int, d_count: int,
                             max_count: int, d_out: int, out_bytes: int, d_out_loc: int, d_result: int, stream: int = 0) -> None:
     """The stored bytes of the entries d_values[k], k < min(*d_count, max_count), back to back into d_out with d_out_loc[k] = where.
@@ -963,7 +982,8 @@ class Bundle:
 
 class ChunkStore:
     """A dedupe index with the bytes behind it: ``ingest`` chunks, dedupes and compresses a buffer and appends its new chunks to a
-    device-resident store, ``restore`` turns a recipe back into bytes, ``read`` / ``read_ranges`` give byte ranges of it, ``compact`` forgets every stream but the ones named.
+    device-resident store, ``restore`` turns a recipe back into bytes, ``read`` / ``read_ranges`` give byte ranges of it, ``compact`` forgets every stream but the ones named,
+    ``renumber`` gives the directory slots of forgotten and duplicate chunks back.
     The store is three torch buffers this object owns (bytes, cursor, directory: the caller-owned triple of cw_dev_store_chunks);
     chunk values count up from ``dir_base`` over the ingests.
     ``ingest`` is one device call: the whole buffer has to fit on the device next to its slots.  ``ingest_stream`` and
@@ -1253,6 +1273,72 @@ class ChunkStore:
         removed = self.index.retain(live.data_ptr(), self.dir_base, n)
         self.d_store, self.d_used, self.d_dir, self.store_bytes = new_store, new_used, new_dir, store_bytes
         return dict(kept=kept, dropped=dropped, bytes_before=bytes_before, bytes_after=needed, removed=removed)
+
+    def renumber(self, recipes, dir_entries: int | None = None, dir_base: int | None = None) -> list:
+        """Give directory slots back: the K non-zero directory entries get the dense values [dir_base, dir_base + K) of a new
+        directory of ``dir_entries`` entries (default: as many as now; ``dir_base`` default: as now), ``recipes`` are translated
+        and the index's values change in place; ``base`` becomes dir_base + K.  No stored byte moves.  Renumbering never forgets --
+        that is ``compact``'s job -- so the full rotation is ``store.compact(keep)`` then ``keep = store.renumber(keep)``.
+        Returns the translated recipes in the order given, offsets unchanged; the ones passed in are not modified and are stale
+        afterwards, as is every recipe of this store that was not passed, a ``ScrubReport`` and any list of values taken before
+        the call.  A ``Bundle`` carries its own values and is not; ``save`` / ``load`` keep ``dir_base`` and ``base`` as they are.
+        Everything that can refuse comes before anything shared changes, so a refusal leaves store, index and recipes as they
+        were: CwError (-5) with ``e.needed`` = K when ``dir_entries`` < K; CwError (-2) when a recipe names no stored chunk (a
+        dropped one, say); CwError (-2) with ``e.stale`` when the index holds that many values of this directory that no entry
+        carries -- chunks dropped from the directory but not from the index: compact first."""
+        import torch
+        recipes = list(recipes)
+        s, n, old_base = self._stream(), self.dir_entries, self.dir_base
+        new_base = old_base if dir_base is None else int(dir_base)
+        z = lambda k, dt=torch.int64: torch.zeros(max(k, 1), dtype=dt, device="cuda")  # noqa: E731
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64).copy()).cuda()  # noqa: E731
+        res = z(4)
+        torch.cuda.synchronize()  # (torch zeroed on its own stream)
+        # 1. the dry run: K
+        dev_store_renumber(self.d_dir.data_ptr(), old_base, n, 0, new_base, 0, new_base, 0, 0, 0, 0, res.data_ptr(), s)
+        torch.cuda.synchronize()
+        K = int(res.cpu().numpy().view(np.uint64)[1])
+        new_entries = max(n, K) if dir_entries is None else int(dir_entries)
+        if new_entries < max(K, 1):
+            err = _lib.CwError(-5, f"chunk store: {K} stored chunks do not fit a directory of {new_entries} entries")
+            err.needed = K
+            raise err
+        # 2. the new directory and the pairs, into fresh buffers
+        new_dir, d_from, d_to, d_np = z(new_entries * 2), z(K), z(K), up([K])
+        torch.cuda.synchronize()
+        dev_store_renumber(self.d_dir.data_ptr(), old_base, n, 0, new_base, new_dir.data_ptr(), new_base, new_entries,
+                           d_from.data_ptr() if K else 0, d_to.data_ptr() if K else 0, K, res.data_ptr(), s)
+        # 3. every recipe into a new array
+        n_missing = z(1)
+        work = [(up(r.refs), up([len(r.refs)]), z(len(r.refs))) if len(r.refs) else None for r in recipes]
+        torch.cuda.synchronize()
+        for r, w in zip(recipes, work):
+            if w is not None:
+                dev_translate_refs(w[0].data_ptr(), w[1].data_ptr(), len(r.refs), d_from.data_ptr(), d_to.data_ptr(), d_np.data_ptr(), K,
+                                   w[2].data_ptr(), n_missing.data_ptr(), s)
+        torch.cuda.synchronize()
+        verdict, kept, next_base = (int(v) for v in res.cpu().numpy().view(np.uint64)[:3])
+        if verdict or kept != K:
+            raise _lib.CwError(-4, f"chunk store: the renumbering of {K} entries was refused with verdict {verdict} after its dry run")
+        missing = int(n_missing.item())
+        if missing:
+            raise _lib.CwError(-2, f"chunk store: {missing} positions of the recipes name no stored chunk of the directory [{old_base}, "
+                                   f"{old_base + n})")
+        # 4. the index: refuses, unchanged, when it holds a value of the old range that no entry carries
+        res3 = z(3)
+        torch.cuda.synchronize()
+        self.index.dev_revalue(d_from.data_ptr(), d_to.data_ptr(), d_np.data_ptr(), K, old_base, n, res3.data_ptr(), s)
+        torch.cuda.synchronize()
+        verdict, _, stale = (int(v) for v in res3.cpu().numpy().view(np.uint64))
+        if verdict:
+            err = _lib.CwError(-2, f"chunk store: the index holds {stale} values of the directory [{old_base}, {old_base + n}) that no "
+                                   "entry carries (chunks dropped from the directory only): compact first")
+            err.stale = stale
+            raise err
+        # 5. nothing can refuse any more
+        self.d_dir, self.dir_entries, self.dir_base, self.base = new_dir, new_entries, new_base, next_base
+        return [Recipe(w[2].cpu().numpy().view(np.uint64)[:len(r.refs)], r.offsets.copy()) if w is not None else Recipe([], r.offsets.copy())
+                for r, w in zip(recipes, work)]
 
     def export_bundle(self, recipes, known=None) -> Bundle:
         """The chunks ``recipes`` name as a Bundle: their digests and values in ascending value (``dev_store_mark`` of every recipe,

@@ -713,6 +713,54 @@ int cw_dev_store_compact(const void *d_store, size_t store_bytes, const cw_chunk
 int cw_dedupe_retain(cw_dedupe_t *x, const uint32_t *d_live, uint64_t dir_base, size_t dir_entries,
                      size_t new_max_entries /* 0 = as it is */, uint64_t *n_removed);
 
+/* ---- the directory gives slots back: renumber, and the index's revalue ---------------------------------
+ * Compaction leaves a dropped chunk's directory entry zero and base counting upward; a duplicate chunk takes a value and no entry.
+ * Renumbering moves the kept entries to the dense values [new_base, new_base + K) of a new directory, which can be as small as K
+ * plus headroom.  Three things name a value and change together: the directory (cw_dev_store_renumber), every kept recipe
+ * (cw_dev_translate_refs with the pairs that call wrote) and the index (cw_dev_dedupe_revalue with the same pairs).  Both calls
+ * follow the store's conventions: device pointers, queued on `stream`, nothing synchronises, every decision made on the device,
+ * all or nothing.                                                                                                                */
+/* Moves directory entries to dense values.  No stored byte moves and no entry is judged: an unsound entry moves as it is.
+ *   kept          entry idx is kept iff it is not all zero and (d_live == NULL or d_live[idx] != 0): cw_dev_store_compact's rule,
+ *                 with cw_dev_store_verify's "d_live == NULL selects every non-zero entry".  K = the kept entries, r(idx) = the
+ *                 kept entries below idx.
+ *   placement     for a kept idx with k = r(idx): d_from[k] = dir_base + idx and d_to[k] = new_base + k, both strictly ascending
+ *                 (the pairs cw_dev_translate_refs and cw_dev_dedupe_revalue take), and d_new_dir[new_base + k - new_dir_base] =
+ *                 d_dir[idx] bit for bit.  Every other entry of d_new_dir[0..new_dir_entries) is written all zero.
+ *   d_result[4]   {verdict, K, new_base + K (the next base), the count of non-zero entries not kept}; the last three are written
+ *                 whatever the verdict is.
+ *   verdict       2 when new_base + K wraps or [new_base, new_base + K) is not inside [new_dir_base, new_dir_base +
+ *                 new_dir_entries) (with K == 0 the range is empty and inside); else 1 when K > max_pairs; else 0.  When it is
+ *                 not 0, no byte of d_new_dir, d_from and d_to changes: max_pairs == 0 with d_from == d_to == NULL and
+ *                 new_dir_entries == 0 with d_new_dir == NULL is a dry run, and d_result[1] says how much room to provide.
+ * d_dir is never written; there is no in-place form.  No load leaves d_dir[0..dir_entries) or d_live[0..dir_entries) whatever
+ * they hold; no store leaves d_new_dir[0..new_dir_entries), d_from / d_to[0..max_pairs), d_result and the scratch.
+ * CW_ERR_BAD_ARG before anything is launched: a NULL pointer (d_live may be NULL; d_new_dir when new_dir_entries is 0 and d_from,
+ * d_to when max_pairs is 0 may be), dir_entries == 0, a dir_entries, new_dir_entries or max_pairs above 2^32 - 256, a directory
+ * that is not 16-byte aligned, a d_from, d_to or d_result that is not 8-byte aligned, d_new_dir[0..new_dir_entries) overlapping
+ * d_dir[0..dir_entries), new_dir_base + new_dir_entries wrapping.  Scratch, per stream: 72 + 12 * dir_entries bytes.
+ * Not synchronised.                                                                                                             */
+int cw_dev_store_renumber(const cw_chunk_loc *d_dir, uint64_t dir_base, size_t dir_entries,
+                          const uint32_t *d_live /* may be NULL */, uint64_t new_base,
+                          cw_chunk_loc *d_new_dir, uint64_t new_dir_base, size_t new_dir_entries,
+                          uint64_t *d_from, uint64_t *d_to, size_t max_pairs,
+                          uint64_t *d_result /* [4] */, void *stream);
+/* Does to the index what cw_dev_translate_refs does to a recipe, in place: the table keeps its values apart from its keys, so a
+ * value changes without a rehash.  The count, the keys, the slot states and max_entries do not change, and a full index is fine.
+ * Serialised with the index's other calls.  p = min(*d_npairs, max_pairs), read on the device; d_from[0..p) is ascending (for any
+ * other list, which pair a value hits is unspecified and only memory safety holds).  For every entry with value v: a binary-search
+ * hit d_from[k] == v is a translation to d_to[k]; otherwise, when v - range_base < range_entries (in u64), the entry is STALE -- it
+ * carries a value of the range that no pair names and would collide with renumbered values later; any other entry is left alone
+ * (values outside the range belong to other directories).  d_result[3] = {verdict, entries translated, stale entries}: verdict 1
+ * when an entry is stale, and then no value changes; else 0, and every translation is applied.  range_entries == 0: nothing is
+ * stale.  p == 0: counts only.  Two entries that carry one value are both translated.  Every slot is read once and written at most
+ * once, so the old and the new values may overlap (dense values [dir_base, dir_base + K) out of [dir_base, dir_base +
+ * dir_entries)).  No load leaves d_from / d_to[0..p) or the table.  CW_ERR_BAD_ARG before anything is launched: a NULL pointer, a
+ * pointer that is not 8-byte aligned, max_pairs > 2^32 - 256, range_base + range_entries wrapping, an index of another device.
+ * Scratch: 64 bytes of the index.  Not synchronised.                                                                            */
+int cw_dev_dedupe_revalue(cw_dedupe_t *x, const uint64_t *d_from, const uint64_t *d_to, const uint64_t *d_npairs, size_t max_pairs,
+                          uint64_t range_base, uint64_t range_entries, uint64_t *d_result /* [3] */, void *stream);
+
 /* ---- chunk bundles: stored chunks from one store to another -------------------------------------------
  * A bundle is a manifest and a payload.  The manifest lists the n distinct chunks a set of recipes names, in ascending value of
  * the sending store: digest[k], value[k] and loc[k] (a cw_chunk_loc whose pos is relative to the payload; all zero = listed but
