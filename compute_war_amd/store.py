@@ -1,0 +1,769 @@
+"""The chunk store: ``ChunkStore`` and what travels with it (``Recipe``, ``Bundle``, ``ScrubReport``) over the ``dev_*`` and
+``store_*`` wrappers of ``ops``.
+
+``ops`` takes raw device pointers and never touches torch; this is the one place in the package that owns torch buffers: it
+allocates and fills them, synchronises torch's stream around the ABI calls and reads their result words back.  torch is imported
+when a method first needs it, so importing the package does not import it.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from ._lib import CwError, lib
+from .ops import (CdcParams, ChunkLoc, DedupeIndex, Store, _comp_id, _hash_id, _np_u8, chunk_slots_bytes, dev_hash_chunks, dev_read_ranges,
+                  dev_restore_chunks, dev_store_chunks, dev_store_compact, dev_store_export_chunks, dev_store_import_chunks, dev_store_mark,
+                  dev_store_renumber, dev_store_replace_chunks, dev_translate_refs, device_count, digest_bytes, init, store_ingest,
+                  store_ingest_streams, store_restore, store_scrub)
+
+
+class Recipe:
+    """What restores one ingested stream: refs[j] = the value of chunk j's first occurrence, offsets[0..k] = its cuts."""
+
+    def __init__(self, refs, offsets):
+        self.refs = np.ascontiguousarray(refs, dtype=np.uint64)
+        self.offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if len(self.offsets) != len(self.refs) + 1:
+            raise ValueError(f"{len(self.refs)} refs need {len(self.refs) + 1} offsets, not {len(self.offsets)}")
+
+    @property
+    def nbytes(self) -> int:
+        return int(self.offsets[-1] - self.offsets[0])
+
+
+LOC_DTYPE = np.dtype([("pos", "<u8"), ("stored", "<u4"), ("raw", "<u4")])  # cw_chunk_loc as a numpy record
+_MISS = np.uint64(DedupeIndex.MISS)
+
+
+def _locs_sound(locs, in_bytes: int) -> np.ndarray:
+    """bool per LOC_DTYPE record: sound by cw_dev_store_compact's entry checks against a buffer of in_bytes bytes."""
+    pos, stored, word = locs["pos"], locs["stored"].astype(np.int64), locs["raw"].astype(np.int64)
+    length, is_raw = word & 0x1FFFF, (word & ChunkLoc.RAW) != 0
+    return ((word & ~(ChunkLoc.RAW | 0x1FFFF)) == 0) & (length >= 1) & (length <= 65536) & (stored != 0) & (~is_raw | (stored == length)) & \
+        (pos <= in_bytes) & (stored <= in_bytes - np.minimum(pos, np.uint64(in_bytes)).astype(np.int64))
+
+
+# Device buffers: max(k, 1) zeroed elements (int64 unless told otherwise), ``a`` as uint64 words (an int64 tensor), the bytes of the
+# array ``a``.  None of them synchronises: torch fills them on its own stream, so a caller synchronises before an ABI call reads them.
+def _zeros(k: int, dtype=None):
+    import torch
+    return torch.zeros(max(k, 1), dtype=dtype or torch.int64, device="cuda")
+
+
+def _u64(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64).copy()).cuda()
+
+
+def _u8(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
+
+
+def _words(t, n=None) -> tuple:
+    """The first n (default: all) uint64 words of a small device tensor as Python ints.  Does not synchronise."""
+    return tuple(int(v) for v in t.cpu().numpy().view(np.uint64)[:n])
+
+
+def _refuse_unrestored(st, refs) -> None:
+    """CwError (-2) unless every status of a restore is 0."""
+    if st.any():
+        j = int(np.nonzero(st)[0][0])
+        raise CwError(-2, f"chunk store: {int((st != 0).sum())} of {len(st)} positions not restored; position {j} (ref {int(refs[j])}) has "
+                          f"status {int(st[j])}")
+
+
+def _export_chunks(cs: "ChunkStore", d_val, nc: int, s: int, damaged: str | None = None, whence: str = ""):
+    """The stored bytes of the nc values d_val (a device tensor) of ``cs``: ``dev_store_export_chunks`` twice, a dry run that sizes the
+    payload and the run that fills it.  Returns (payload tensor, total bytes, cw_chunk_loc tensor).  With ``damaged``, verdict 2 in
+    either run raises CwError (-2) with that text; any verdict of the second run raises CwError (-4), worded with ``whence``."""
+    import torch
+    d_count, d_loc, res, out, total = _u64([nc]), _zeros(nc * 2), _zeros(3), None, 0
+    for dry in (True, False):
+        torch.cuda.synchronize()
+        dev_store_export_chunks(cs.d_store.data_ptr(), cs.store_bytes, cs.d_dir.data_ptr(), cs.dir_base, cs.dir_entries, d_val.data_ptr(),
+                                d_count.data_ptr(), nc, 0 if dry else out.data_ptr(), total, d_loc.data_ptr(), res.data_ptr(), s)
+        torch.cuda.synchronize()
+        verdict, needed = _words(res, 2)
+        if verdict == 2 and damaged:
+            raise CwError(-2, damaged)
+        if dry:  # (verdict 1 with the bytes needed)
+            total, out = needed, _zeros(needed, torch.uint8)
+        elif verdict:
+            raise CwError(-4, f"chunk store: the export of {total} bytes{whence} was refused with verdict {verdict} after its dry run")
+    return out, total, d_loc
+
+
+class ScrubReport:
+    """What ``ChunkStore.scrub`` found: ``status`` (uint32, one per directory entry: 0 good, 1 malformed, 2 unsound entry, 3 digest
+    mismatch, 4 orphan, 5 not selected), ``stats`` (cw_scrub_stats as a dict), ``damaged`` (the values with status 1, 2 or 3,
+    ascending) and ``orphans`` (the values with status 4: they decode, but the index holds no digest to judge them by)."""
+
+    def __init__(self, status, stats: dict, dir_base: int):
+        self.status, self.stats = np.ascontiguousarray(status, dtype=np.uint32), stats
+        at = lambda mask: (np.nonzero(mask)[0].astype(np.uint64) + np.uint64(dir_base))  # noqa: E731
+        self.damaged = at((self.status >= 1) & (self.status <= 3))
+        self.orphans = at(self.status == 4)
+
+    @property
+    def clean(self) -> bool:
+        return len(self.damaged) == 0
+
+
+class Bundle:
+    """Chunks on their way from one ChunkStore to another, as plain host data.  The manifest lists the n
+    distinct chunks ``recipes`` name in ascending sender value: ``digests`` uint8[n, digest bytes], ``values`` uint64[n] (the
+    sender's), ``locs`` LOC_DTYPE[n] (where the chunk lies in ``payload``; all zero = listed, not carried).  ``payload`` uint8 holds
+    the carried chunks' stored bytes back to back, in the sender's stored form: sender and receiver share ``hash_alg`` and
+    ``comp_alg``."""
+
+    def __init__(self, digests, values, locs, payload, hash_alg, comp_alg, recipes):
+        self.hash_alg, self.comp_alg = _hash_id(hash_alg), _comp_id(comp_alg)
+        self.values = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1)
+        self.digests = np.ascontiguousarray(digests, dtype=np.uint8).reshape(len(self.values), digest_bytes(self.hash_alg))
+        self.locs = np.ascontiguousarray(locs, dtype=LOC_DTYPE).reshape(-1)
+        self.payload = np.ascontiguousarray(payload, dtype=np.uint8).reshape(-1)
+        self.recipes = list(recipes)
+        if len(self.locs) != len(self.values):
+            raise ValueError(f"{len(self.values)} values, {len(self.locs)} locs")
+
+    @property
+    def carried(self) -> np.ndarray:
+        """bool[n]: the chunks whose stored bytes the payload holds."""
+        return (self.locs["pos"] != 0) | (self.locs["stored"] != 0) | (self.locs["raw"] != 0)
+
+    def save(self, path) -> None:
+        """One ``.npz``: manifest, payload, the algorithm ids and the recipes (refs and offsets concatenated, with their lengths)."""
+        cat = lambda arrays: np.concatenate(arrays) if arrays else np.zeros(0, np.uint64)  # noqa: E731
+        with open(path, "wb") as f:
+            np.savez(f, hash_alg=np.int64(self.hash_alg), comp_alg=np.int64(self.comp_alg), digests=self.digests, values=self.values,
+                     locs=self.locs, payload=self.payload, recipe_lens=np.array([len(r.refs) for r in self.recipes], np.uint64),
+                     recipe_refs=cat([r.refs for r in self.recipes]), recipe_offsets=cat([r.offsets for r in self.recipes]))
+
+    @classmethod
+    def load(cls, path) -> "Bundle":
+        with np.load(path) as z:
+            lens, refs, offs = z["recipe_lens"].tolist(), z["recipe_refs"], z["recipe_offsets"]
+            recipes, a = [], 0
+            for i, k in enumerate(lens):
+                recipes.append(Recipe(refs[a:a + k], offs[a + i:a + i + k + 1]))
+                a += k
+            return cls(z["digests"], z["values"], z["locs"], z["payload"], int(z["hash_alg"]), int(z["comp_alg"]), recipes)
+
+
+class ChunkStore:
+    """A dedupe index with the bytes behind it: ``ingest`` chunks, dedupes and compresses a buffer and appends its new chunks to a
+    device-resident store, ``restore`` turns a recipe back into bytes, ``read`` / ``read_ranges`` give byte ranges of it, ``compact`` forgets every stream but the ones named,
+    ``renumber`` gives the directory slots of forgotten and duplicate chunks back.
+    The store is three torch buffers this object owns (bytes, cursor, directory: the caller-owned triple of cw_dev_store_chunks);
+    chunk values count up from ``dir_base`` over the ingests.
+    ``ingest`` is one device call: the whole buffer has to fit on the device next to its slots.  ``ingest_stream`` and
+    ``restore_stream`` take and give host buffers of any size, streamed through the device in pieces (cw_store_ingest /
+    cw_store_restore), ``ingest_many_stream`` and ``restore_many_stream`` many of them in one pipelined run; ``last_stats`` holds the
+    last streamed ingest's statistics."""
+    last_stats = None
+
+    def __init__(self, index: DedupeIndex, comp_alg, params: CdcParams, store_bytes: int, dir_entries: int, dir_base: int = 0):
+        import torch
+        self.index, self.comp_alg, self.params = index, _comp_id(comp_alg), params
+        self.store_bytes, self.dir_entries, self.dir_base = store_bytes, dir_entries, dir_base
+        self.base = dir_base
+        self.d_store = torch.zeros(max(store_bytes, 1), dtype=torch.uint8, device="cuda")
+        self.d_used = torch.zeros(1, dtype=torch.int64, device="cuda")
+        self.d_dir = torch.zeros(dir_entries * 2, dtype=torch.int64, device="cuda")  # 16 bytes per entry
+        torch.cuda.synchronize()
+
+    @staticmethod
+    def _stream() -> int:
+        import torch
+        return torch.cuda.current_stream().cuda_stream
+
+    def used(self) -> int:
+        return int(self.d_used.item())
+
+    def _no_room(self, what: str, needed: int, used: int) -> CwError:
+        err = CwError(-5, f"{what}: {needed} bytes do not fit behind {used} of {self.store_bytes}")
+        err.needed = needed
+        return err
+
+    def _off_directory(self, what: str, k: int) -> CwError:
+        return CwError(-5, f"{what}: values {self.base} .. {self.base + k} leave the directory [{self.dir_base}, {self.dir_base + self.dir_entries})")
+
+    def _append(self, k: int, src, n: int, off, k_dev, cap: int, slots, sizes, new_idx, n_new, result, s: int) -> None:
+        """``dev_store_chunks`` of the outputs of a fused call that found k chunks; ``base`` advances by k, or CwError (-5)."""
+        import torch
+        dev_store_chunks(self.comp_alg, src.data_ptr(), n, off.data_ptr(), k_dev.data_ptr(), cap - 1, slots.data_ptr(), sizes.data_ptr(),
+                         self.base, self.d_store.data_ptr(), self.store_bytes, self.d_used.data_ptr(), self.d_dir.data_ptr(), self.dir_base,
+                         self.dir_entries, result.data_ptr(), s, new_idx.data_ptr(), n_new.data_ptr())
+        torch.cuda.synchronize()
+        verdict, needed = _words(result)
+        if verdict:
+            # the index holds the call's new chunks already, the store does not: the caller starts over or grows the store
+            err = self._no_room("chunk store", needed, self.used()) if verdict == 1 else self._off_directory("chunk store", k)
+            err.needed = needed
+            raise err
+        self.base += k
+
+    def ingest(self, data) -> Recipe:
+        """Chunk, hash, dedupe and compress ``data`` in one device call, then append its new chunks.  Raises CwError (-5) when the
+        store or the directory cannot take them (``e.needed`` = the bytes the call wanted); the store is then unchanged."""
+        import torch
+        a = _np_u8(data)
+        n, s = a.size, self._stream()
+        src = torch.from_numpy(a.copy() if n else np.zeros(1, np.uint8)).cuda()
+        cap = self.params.max_offsets(n)
+        total = chunk_slots_bytes(self.comp_alg, n, cap - 1)
+        off, k_dev, dig = _zeros(cap), _zeros(1), _zeros(cap * digest_bytes(self.index.hash_alg), torch.uint8)
+        ref, new_idx, n_new = _zeros(cap), _zeros(cap, torch.int32), _zeros(1)
+        slots, sizes, result = torch.empty(total, dtype=torch.uint8, device="cuda"), _zeros(cap, torch.int32), _zeros(2)
+        torch.cuda.synchronize()
+        k = self.index.dev_cdc_dedupe_compress(self.params, self.comp_alg, src.data_ptr(), n, True, self.base, off.data_ptr(), cap,
+                                               k_dev.data_ptr(), dig.data_ptr(), ref.data_ptr(), new_idx.data_ptr(), n_new.data_ptr(),
+                                               slots.data_ptr(), total, sizes.data_ptr(), s)
+        self._append(k, src, n, off, k_dev, cap, slots, sizes, new_idx, n_new, result, s)
+        return Recipe(ref.cpu().numpy().view(np.uint64)[:k], off.cpu().numpy().view(np.uint64)[:k + 1])
+
+    def ingest_many(self, datas) -> list:
+        """``ingest`` of many buffers at once: one upload of their concatenation, one fused call (``dev_cdc_streams_dedupe_compress``)
+        and one ``dev_store_chunks``.  Every buffer is chunked as if alone, so the recipes, the store and the index are what a loop of
+        ``ingest`` over ``datas`` leaves.  Returns one Recipe per buffer, its offsets starting at 0.  Raises as ``ingest`` does."""
+        import torch
+        parts = [_np_u8(d) for d in datas]
+        if not parts:
+            return []
+        ends = np.cumsum([a.size for a in parts], dtype=np.uint64)
+        n, nf, s = int(ends[-1]), len(parts), self._stream()
+        src = torch.from_numpy(np.concatenate(parts) if n else np.zeros(1, np.uint8)).cuda()
+        d_ends = torch.from_numpy(ends.view(np.int64)).cuda()
+        cap = self.params.max_offsets_streams(n, nf)
+        total = chunk_slots_bytes(self.comp_alg, n, cap - 1)
+        off, k_dev, dig = _zeros(cap), _zeros(1), _zeros(cap * digest_bytes(self.index.hash_alg), torch.uint8)
+        ref, new_idx, n_new = _zeros(cap), _zeros(cap, torch.int32), _zeros(1)
+        slots, sizes, result = torch.empty(total, dtype=torch.uint8, device="cuda"), _zeros(cap, torch.int32), _zeros(2)
+        first, ends_ok = _zeros(nf + 1), _zeros(1)
+        torch.cuda.synchronize()
+        k = self.index.dev_cdc_streams_dedupe_compress(self.params, self.comp_alg, src.data_ptr(), n, d_ends.data_ptr(), nf, self.base,
+                                                       off.data_ptr(), cap, k_dev.data_ptr(), first.data_ptr(), ends_ok.data_ptr(),
+                                                       dig.data_ptr(), ref.data_ptr(), new_idx.data_ptr(), n_new.data_ptr(), slots.data_ptr(),
+                                                       total, sizes.data_ptr(), s)
+        self._append(k, src, n, off, k_dev, cap, slots, sizes, new_idx, n_new, result, s)
+        refs, offs = ref.cpu().numpy().view(np.uint64)[:k], off.cpu().numpy().view(np.uint64)[:k + 1]
+        lo = first.cpu().numpy().view(np.uint64)
+        starts = np.concatenate([np.zeros(1, np.uint64), ends[:-1]])
+        return [Recipe(refs[a:b], offs[a:b + 1] - starts[f]) if b > a else Recipe([], [0])
+                for f, (a, b) in enumerate(zip(lo[:-1].tolist(), lo[1:].tolist()))]
+
+    def _triple(self) -> Store:
+        return Store(self.d_store.data_ptr(), self.store_bytes, self.d_used.data_ptr(), self.d_dir.data_ptr(), self.dir_base, self.dir_entries)
+
+    def ingest_stream(self, data) -> Recipe:
+        """``ingest`` for host data of any size, piece by piece with uploads beside the kernels.  When the index, the directory or
+        the store cannot take a piece, raises CwError (-5) with ``e.consumed`` and ``e.nchunks`` (the bytes and chunks of the pieces that
+        went in; ``base`` has advanced by them) and ``e.recipe``, which restores ``data[:e.consumed]``: make room, then ingest
+        ``data[e.consumed:]``."""
+        import torch
+        a = _np_u8(data)
+        torch.cuda.synchronize()  # (the buffers were filled on torch's stream)
+        rc, refs, offs, consumed, stats = store_ingest(self.index, self.params, self.comp_alg, self._triple(), a.ctypes.data if a.size else 0,
+                                                       a.size, self.base)
+        self.base += len(refs)
+        self.last_stats = stats
+        recipe = Recipe(refs, offs)
+        if rc:
+            err = CwError(rc, lib().cw_last_error().decode(errors="replace"))
+            err.consumed, err.nchunks, err.recipe = consumed, len(refs), recipe
+            raise err
+        return recipe
+
+    def ingest_many_stream(self, datas) -> list:
+        """``ingest_many`` for host buffers of any number and total size, piece by piece as ``ingest_stream`` (cw_store_ingest_streams):
+        every buffer is chunked as if alone and may span pieces; the recipes, the store and the index are what ``ingest_many`` or a loop
+        of ``ingest`` leaves.  Buffers that lie back to back in page-locked memory are read in place.  When a piece is refused, raises
+        CwError (-5) with ``e.recipes`` (the complete streams), ``e.partial`` (the recipe of the stream that was cut, or None),
+        ``e.streams_done``, ``e.consumed`` and ``e.nchunks``; ``base`` has advanced by ``e.nchunks``.  Make room, then go on with the
+        buffers from ``e.streams_done``, the first shortened by ``e.partial.nbytes``."""
+        import torch
+        parts = [_np_u8(d) for d in datas]
+        torch.cuda.synchronize()
+        lens = np.array([a.size for a in parts], np.uint64)
+        rc, refs, offs, first, consumed, done, stats = store_ingest_streams(self.index, self.params, self.comp_alg, self._triple(),
+                                                                            [a.ctypes.data if a.size else 0 for a in parts], lens, self.base)
+        self.base += len(refs)
+        self.last_stats = stats
+        lo = first.tolist()
+        cut = lambda a, b: Recipe(refs[a:b], offs[a:b + 1] - offs[a]) if b > a else Recipe([], [0])  # noqa: E731
+        recipes = [cut(a, b) for a, b in zip(lo[:done], lo[1:done + 1])]
+        if rc:
+            err = CwError(rc, lib().cw_last_error().decode(errors="replace"))
+            err.recipes, err.streams_done, err.consumed, err.nchunks = recipes, done, consumed, len(refs)
+            err.partial = cut(lo[done], lo[done + 1]) if done + 1 < len(lo) and lo[done + 1] > lo[done] else None
+            raise err
+        return recipes
+
+    def restore_many_stream(self, recipes) -> list:
+        """``restore_stream`` of many recipes in one pipelined run: the recipes are joined into one with the offsets shifted, restored
+        by one cw_store_restore, and the bytes split again.  Raises as ``restore`` does."""
+        recipes = list(recipes)
+        sizes = [r.nbytes for r in recipes]
+        starts = np.concatenate([np.zeros(1, np.uint64), np.cumsum(sizes, dtype=np.uint64)])
+        refs = np.concatenate([r.refs for r in recipes]) if recipes else np.zeros(0, np.uint64)
+        offs = np.concatenate([np.zeros(1, np.uint64)] + [r.offsets[1:] - r.offsets[0] + starts[i] for i, r in enumerate(recipes)])
+        whole = self.restore_stream(Recipe(refs, offs))
+        return [whole[int(a):int(a) + n] for a, n in zip(starts[:-1], sizes)]
+
+    def restore_stream(self, recipe: Recipe) -> bytes:
+        """``restore`` into host memory, window by window with downloads beside the kernels.  Raises as ``restore`` does."""
+        import torch
+        out = np.zeros(max(recipe.nbytes, 1), np.uint8)
+        torch.cuda.synchronize()
+        _refuse_unrestored(store_restore(self.comp_alg, self._triple(), recipe.refs, recipe.offsets, out.ctypes.data, recipe.nbytes), recipe.refs)
+        return out[:recipe.nbytes].tobytes()
+
+    def restore(self, recipe: Recipe, verify: bool = False) -> bytes:
+        """The bytes of an ingested stream.  Raises CwError (-2) unless every position restores.  verify: the restored chunks are
+        hashed again and looked up in the index, and every answer has to be the recipe's ref."""
+        import torch
+        k, n, s = len(recipe.refs), recipe.nbytes, self._stream()
+        d_ref, d_raw, d_count = _u64(recipe.refs if k else [0]), _u64(recipe.offsets - recipe.offsets[0]), _u64([k])
+        out, status = _zeros(n, torch.uint8), _zeros(k, torch.int32)
+        torch.cuda.synchronize()
+        dev_restore_chunks(self.comp_alg, self.d_store.data_ptr(), self.store_bytes, self.d_dir.data_ptr(), self.dir_base, self.dir_entries,
+                           d_ref.data_ptr(), d_raw.data_ptr(), d_count.data_ptr(), k, out.data_ptr(), n, status.data_ptr(), s)
+        if verify and k:
+            dig, found, n_found = _zeros(k * digest_bytes(self.index.hash_alg), torch.uint8), _zeros(k), _zeros(1)
+            torch.cuda.synchronize()  # (torch zeroed them on its own stream)
+            dev_hash_chunks(self.index.hash_alg, out.data_ptr(), n, d_raw.data_ptr(), d_count.data_ptr(), k, dig.data_ptr(), s)
+            self.index.dev_lookup(dig.data_ptr(), k, found.data_ptr(), n_found.data_ptr(), s)
+        torch.cuda.synchronize()
+        _refuse_unrestored(status.cpu().numpy()[:k], recipe.refs)
+        if verify and k:
+            got = found.cpu().numpy().view(np.uint64)
+            bad = np.nonzero(got != recipe.refs)[0]
+            if len(bad):
+                raise CwError(-2, f"chunk store: verify failed at position {int(bad[0])}: the index answers {int(got[bad[0]])}, "
+                                  f"the recipe says {int(recipe.refs[bad[0]])} ({len(bad)} positions differ)")
+        return out.cpu().numpy()[:n].tobytes()
+
+    def read_ranges(self, recipe: Recipe, ranges) -> list:
+        """The bytes of the ranges ``(offset, length)`` of an ingested stream, in the recipe's own zero-based coordinates, without
+        restoring the stream: one device call, the destinations packed back to back.  Raises CwError (-2) naming the first range
+        with a status other than 0."""
+        if device_count() <= 0:
+            init()  # (raises: no device)
+        import torch
+        ranges = [(int(o), int(l)) for o, l in ranges]
+        k, m, s = len(recipe.refs), len(ranges), self._stream()
+        if m == 0:
+            return []
+        if any(o < 0 or l < 0 or o + l >= 1 << 64 for o, l in ranges):
+            raise ValueError("ranges are (offset, length) with 0 <= offset, 0 <= length and offset + length < 2^64")
+        lens = np.array([l for _, l in ranges], np.uint64)
+        dsts = np.concatenate([[0], np.cumsum(lens, dtype=np.uint64)]).astype(np.uint64)
+        total = int(dsts[-1])
+        d_ref, d_raw, d_count = _u64(recipe.refs if k else [0]), _u64(recipe.offsets - recipe.offsets[0]), _u64([k])
+        d_off, d_len, d_to, d_m = _u64([o for o, _ in ranges]), _u64(lens), _u64(dsts[:-1]), _u64([m])
+        out, status = _zeros(total, torch.uint8), _zeros(m, torch.int32)
+        torch.cuda.synchronize()
+        dev_read_ranges(self.comp_alg, self.d_store.data_ptr(), self.store_bytes, self.d_dir.data_ptr(), self.dir_base, self.dir_entries,
+                        d_ref.data_ptr(), d_raw.data_ptr(), d_count.data_ptr(), k, d_off.data_ptr(), d_len.data_ptr(), d_to.data_ptr(),
+                        d_m.data_ptr(), m, out.data_ptr(), total, status.data_ptr(), s)
+        torch.cuda.synchronize()
+        st = status.cpu().numpy()
+        if st.any():
+            j = int(np.nonzero(st)[0][0])
+            raise CwError(-2, f"chunk store: {int((st != 0).sum())} of {m} ranges not read; range {j} (offset {ranges[j][0]}, length "
+                              f"{ranges[j][1]}) has status {int(st[j])}")
+        host = out.cpu().numpy()
+        return [host[int(dsts[i]):int(dsts[i + 1])].tobytes() for i in range(m)]
+
+    def read(self, recipe: Recipe, offset: int, length: int) -> bytes:
+        """Bytes [offset, offset + length) of an ingested stream: ``read_ranges`` with one range."""
+        return self.read_ranges(recipe, [(offset, length)])[0]
+
+    def _mark(self, recipes, s: int):
+        """(live: a u32 flag per directory entry; n_outside: the positions that name none) after ``dev_store_mark`` of every recipe."""
+        import torch
+        live, n_out = _zeros(self.dir_entries, torch.int32), _zeros(1)
+        marks = [(_u64(r.refs), _u64([len(r.refs)]), len(r.refs)) for r in recipes if len(r.refs)]
+        torch.cuda.synchronize()  # (torch zeroed and copied on its own stream)
+        for d_ref, d_count, k in marks:
+            dev_store_mark(d_ref.data_ptr(), d_count.data_ptr(), k, self.dir_base, self.dir_entries, live.data_ptr(), n_out.data_ptr(), s)
+        return live, n_out
+
+    def _refuse_outside(self, n_out, whose: str) -> None:
+        """CwError (-2) when ``_mark`` counted positions outside the directory; the caller has synchronised."""
+        outside = int(n_out.item())
+        if outside:
+            raise CwError(-2, f"chunk store: {outside} positions of the {whose} name no entry of the directory [{self.dir_base}, "
+                              f"{self.dir_base + self.dir_entries})")
+
+    def compact(self, keep, store_bytes: int | None = None) -> dict:
+        """Forget every stream but the recipes in ``keep``: mark their chunks, move the marked chunks' stored bytes into a new store
+        of ``store_bytes`` (default: as large as the old one, after a dry run) with a new directory, and drop the other chunks' digests
+        from the index.  Values are not renumbered.  Returns dict(kept, dropped, bytes_before, bytes_after, removed).  Raises CwError
+        with ``e.needed`` (the bytes the kept chunks take) when the new store is too small (-5) or a kept chunk's entry is damaged
+        (-2), and CwError -2 when a recipe names a value outside the directory; the store and the index are then unchanged, as they
+        are when the index's retain fails."""
+        import torch
+        s, n = self._stream(), self.dir_entries
+        new_dir, new_used, result = _zeros(n * 2), _zeros(1), _zeros(4)
+        live, n_out = self._mark(keep, s)
+
+        def run(d_new_store: int, new_bytes: int):
+            dev_store_compact(self.d_store.data_ptr(), self.store_bytes, self.d_dir.data_ptr(), n, live.data_ptr(), d_new_store, new_bytes,
+                              new_used.data_ptr(), new_dir.data_ptr(), result.data_ptr(), s)
+            torch.cuda.synchronize()
+            verdict, needed, kept, dropped = _words(result)
+            if verdict:
+                err = CwError(-5 if verdict == 1 else -2, f"chunk store: the kept chunks' {needed} bytes do not fit into {new_bytes}"
+                              if verdict == 1 else "chunk store: a kept chunk's directory entry is damaged")
+                err.needed = needed
+                raise err
+            return needed, kept, dropped
+
+        if store_bytes is None:
+            try:
+                run(0, 0)  # the dry run: verdict 1 with the bytes needed, unless nothing is kept
+            except CwError as e:
+                if e.code != -5:
+                    raise
+            store_bytes = self.store_bytes
+        self._refuse_outside(n_out, "kept recipes")  # (only now: a damaged kept entry wins over an outside position)
+        new_store = _zeros(store_bytes, torch.uint8)
+        torch.cuda.synchronize()
+        bytes_before = self.used()
+        needed, kept, dropped = run(new_store.data_ptr(), store_bytes)
+        removed = self.index.retain(live.data_ptr(), self.dir_base, n)
+        self.d_store, self.d_used, self.d_dir, self.store_bytes = new_store, new_used, new_dir, store_bytes
+        return dict(kept=kept, dropped=dropped, bytes_before=bytes_before, bytes_after=needed, removed=removed)
+
+    def renumber(self, recipes, dir_entries: int | None = None, dir_base: int | None = None) -> list:
+        """Give directory slots back: the K non-zero directory entries get the dense values [dir_base, dir_base + K) of a new
+        directory of ``dir_entries`` entries (default: as many as now; ``dir_base`` default: as now), ``recipes`` are translated
+        and the index's values change in place; ``base`` becomes dir_base + K.  No stored byte moves.  Renumbering never forgets --
+        that is ``compact``'s job -- so the full rotation is ``store.compact(keep)`` then ``keep = store.renumber(keep)``.
+        Returns the translated recipes in the order given, offsets unchanged; the ones passed in are not modified and are stale
+        afterwards, as is every recipe of this store that was not passed, a ``ScrubReport`` and any list of values taken before
+        the call.  A ``Bundle`` carries its own values and is not; ``save`` / ``load`` keep ``dir_base`` and ``base`` as they are.
+        Everything that can refuse comes before anything shared changes, so a refusal leaves store, index and recipes as they
+        were: CwError (-5) with ``e.needed`` = K when ``dir_entries`` < K; CwError (-2) when a recipe names no stored chunk (a
+        dropped one, say); CwError (-2) with ``e.stale`` when the index holds that many values of this directory that no entry
+        carries -- chunks dropped from the directory but not from the index: compact first."""
+        import torch
+        recipes = list(recipes)
+        s, n, old_base = self._stream(), self.dir_entries, self.dir_base
+        new_base = old_base if dir_base is None else int(dir_base)
+        res = _zeros(4)
+        torch.cuda.synchronize()  # (torch zeroed on its own stream)
+        # 1. the dry run: K
+        dev_store_renumber(self.d_dir.data_ptr(), old_base, n, 0, new_base, 0, new_base, 0, 0, 0, 0, res.data_ptr(), s)
+        torch.cuda.synchronize()
+        K = _words(res)[1]
+        new_entries = max(n, K) if dir_entries is None else int(dir_entries)
+        if new_entries < max(K, 1):
+            err = CwError(-5, f"chunk store: {K} stored chunks do not fit a directory of {new_entries} entries")
+            err.needed = K
+            raise err
+        # 2. the new directory and the pairs, into fresh buffers
+        new_dir, d_from, d_to, d_np = _zeros(new_entries * 2), _zeros(K), _zeros(K), _u64([K])
+        torch.cuda.synchronize()
+        dev_store_renumber(self.d_dir.data_ptr(), old_base, n, 0, new_base, new_dir.data_ptr(), new_base, new_entries,
+                           d_from.data_ptr() if K else 0, d_to.data_ptr() if K else 0, K, res.data_ptr(), s)
+        # 3. every recipe into a new array
+        n_missing = _zeros(1)
+        work = [(_u64(r.refs), _u64([len(r.refs)]), _zeros(len(r.refs))) if len(r.refs) else None for r in recipes]
+        torch.cuda.synchronize()
+        for r, w in zip(recipes, work):
+            if w is not None:
+                dev_translate_refs(w[0].data_ptr(), w[1].data_ptr(), len(r.refs), d_from.data_ptr(), d_to.data_ptr(), d_np.data_ptr(), K,
+                                   w[2].data_ptr(), n_missing.data_ptr(), s)
+        torch.cuda.synchronize()
+        verdict, kept, next_base = _words(res, 3)
+        if verdict or kept != K:
+            raise CwError(-4, f"chunk store: the renumbering of {K} entries was refused with verdict {verdict} after its dry run")
+        missing = int(n_missing.item())
+        if missing:
+            raise CwError(-2, f"chunk store: {missing} positions of the recipes name no stored chunk of the directory [{old_base}, "
+                              f"{old_base + n})")
+        # 4. the index: refuses, unchanged, when it holds a value of the old range that no entry carries
+        res3 = _zeros(3)
+        torch.cuda.synchronize()
+        self.index.dev_revalue(d_from.data_ptr(), d_to.data_ptr(), d_np.data_ptr(), K, old_base, n, res3.data_ptr(), s)
+        torch.cuda.synchronize()
+        verdict, _, stale = _words(res3)
+        if verdict:
+            err = CwError(-2, f"chunk store: the index holds {stale} values of the directory [{old_base}, {old_base + n}) that no "
+                              "entry carries (chunks dropped from the directory only): compact first")
+            err.stale = stale
+            raise err
+        # 5. nothing can refuse any more
+        self.d_dir, self.dir_entries, self.dir_base, self.base = new_dir, new_entries, new_base, next_base
+        return [Recipe(w[2].cpu().numpy().view(np.uint64)[:len(r.refs)], r.offsets.copy()) if w is not None else Recipe([], r.offsets.copy())
+                for r, w in zip(recipes, work)]
+
+    def export_bundle(self, recipes, known=None) -> Bundle:
+        """The chunks ``recipes`` name as a Bundle: their digests and values in ascending value (``dev_store_mark`` of every recipe,
+        then ``dev_export_live``) and their stored bytes (``dev_store_export_chunks``, sized by a dry run).  ``known`` is a DedupeIndex
+        on this device, or a ChunkStore standing for its index, typically the receiver's: chunks it holds are listed in the manifest
+        but not carried.  Raises CwError (-2), the store untouched, when a recipe names a value outside the directory, when the
+        index and the store disagree about a named value, or when a named chunk's entry is damaged."""
+        import torch
+        recipes = list(recipes)
+        known = known.index if isinstance(known, ChunkStore) else known
+        if known is not None and known.hash_alg != self.index.hash_alg:
+            raise ValueError(f"known index hashes with algorithm {known.hash_alg}, this store with {self.index.hash_alg}")
+        s, n, db = self._stream(), self.dir_entries, digest_bytes(self.index.hash_alg)
+        live, n_out = self._mark(recipes, s)
+        torch.cuda.synchronize()
+        self._refuse_outside(n_out, "recipes")
+        flagged = int(torch.count_nonzero(live).item())
+        dig, val, res = _zeros(flagged * db, torch.uint8), _zeros(flagged), _zeros(3)
+        torch.cuda.synchronize()
+        self.index.dev_export_live(live.data_ptr(), self.dir_base, n, dig.data_ptr(), val.data_ptr(), flagged, res.data_ptr(), s)
+        torch.cuda.synchronize()
+        count, hits = _words(res, 2)
+        values = val.cpu().numpy().view(np.uint64)[:flagged]
+        if count != flagged or hits != flagged or (values == _MISS).any():
+            raise CwError(-2, f"chunk store: the recipes name {flagged} chunks, the index holds {hits} entries with their values "
+                              f"({int((values == _MISS).sum())} values have none): store and index disagree")
+        carry = np.ones(flagged, bool)
+        if known is not None and flagged:
+            found, n_found = _zeros(flagged), _zeros(1)
+            torch.cuda.synchronize()
+            known.dev_lookup(dig.data_ptr(), flagged, found.data_ptr(), n_found.data_ptr(), s)
+            torch.cuda.synchronize()
+            carry = found.cpu().numpy().view(np.uint64)[:flagged] == _MISS
+        locs, payload, nc = np.zeros(flagged, LOC_DTYPE), np.zeros(0, np.uint8), int(carry.sum())
+        if nc:
+            out, total, d_loc = _export_chunks(self, _u64(values[carry]), nc, s, damaged="chunk store: a named chunk's directory entry is damaged")
+            locs[carry] = d_loc.cpu().numpy().view(LOC_DTYPE)[:nc]
+            payload = out.cpu().numpy()[:total]
+        return Bundle(dig.cpu().numpy()[:flagged * db], values, locs, payload, self.index.hash_alg, self.comp_alg, recipes)
+
+    def import_bundle(self, bundle: Bundle, verify: bool = True) -> list:
+        """Take a Bundle's chunks into this store and return its recipes in this store's values (offsets unchanged).  Chunks this
+        store's index already holds keep their value here; the others are appended in manifest order under the values ``base`` + k,
+        and ``base`` grows by the manifest's length.  Everything that can refuse comes before the index is touched, so a refusal
+        leaves index, store, directory and ``base`` as they were: ValueError when codec or hash algorithm differ; CwError (-2) when
+        the bundle lacks a chunk this store needs, when a needed chunk's place in the payload is unsound, when a recipe names a
+        value the manifest lacks or -- with ``verify`` -- when a carried chunk does not restore from the bundle or does not hash to
+        its manifest digest; CwError (-5) when the index, the directory or the store cannot take the new chunks."""
+        import torch
+        if bundle.comp_alg != self.comp_alg or bundle.hash_alg != self.index.hash_alg:
+            raise ValueError(f"bundle of codec {bundle.comp_alg} / hash {bundle.hash_alg}, store of codec {self.comp_alg} / hash "
+                             f"{self.index.hash_alg}")
+        n, s, db = len(bundle.values), self._stream(), digest_bytes(self.index.hash_alg)
+        if bundle.digests.shape != (n, db):
+            raise ValueError(f"{n} values need digests of shape ({n}, {db}), not {bundle.digests.shape}")
+        for r in bundle.recipes:
+            if not np.isin(r.refs, bundle.values).all():
+                raise CwError(-2, "chunk bundle: a recipe names a value the manifest lacks")
+        if n == 0:
+            return [Recipe(r.refs, r.offsets) for r in bundle.recipes]
+        in_bytes = len(bundle.payload)
+        d_dig, d_loc, d_in = _u8(bundle.digests), _u8(bundle.locs), _u8(bundle.payload if in_bytes else np.zeros(1, np.uint8))
+        found, n_found = _zeros(n), _zeros(1)
+        torch.cuda.synchronize()
+        # 2. what this store lacks, read-only; every such chunk is carried, soundly, and there is room for all of them
+        self.index.dev_lookup(d_dig.data_ptr(), n, found.data_ptr(), n_found.data_ptr(), s)
+        torch.cuda.synchronize()
+        lacks, carried, locs = found.cpu().numpy().view(np.uint64) == _MISS, bundle.carried, bundle.locs
+        if (lacks & ~carried).any():
+            raise CwError(-2, f"chunk bundle: {int((lacks & ~carried).sum())} chunks this store lacks are listed but not carried")
+        stored, length, sound = locs["stored"].astype(np.int64), locs["raw"].astype(np.int64) & 0x1FFFF, _locs_sound(locs, in_bytes)
+        if (lacks & ~sound).any():
+            raise CwError(-2, f"chunk bundle: chunk {int(np.nonzero(lacks & ~sound)[0][0])}'s place in the payload is unsound")
+        n_lacks, need, count, used = int(lacks.sum()), int(stored[lacks].sum()), self.index.count(), self.used()
+        if count + n_lacks > self.index.max_entries:
+            raise CwError(-5, f"chunk bundle: {count} entries + {n_lacks} new chunks > max_entries {self.index.max_entries}")
+        if self.base + n > self.dir_base + self.dir_entries:
+            raise self._off_directory("chunk bundle", n)
+        if used + need > self.store_bytes:
+            raise self._no_room("chunk bundle", need, used)
+        # 3. the carried chunks restore from the bundle itself (the payload as the store, the locs as its directory) and hash to
+        # the manifest's digests
+        which = np.nonzero(carried)[0]
+        if verify and len(which):
+            if not sound[which].all():
+                raise CwError(-2, f"chunk bundle: chunk {int(which[~sound[which]][0])}'s place in the payload is unsound")
+            k = len(which)
+            st, dig2 = self._restored_digests(d_in.data_ptr(), in_bytes, d_loc.data_ptr(), n, which, length[which])
+            if st.any():
+                j = int(np.nonzero(st)[0][0])
+                raise CwError(-2, f"chunk bundle: {int((st != 0).sum())} of {k} carried chunks do not restore; chunk {int(which[j])} has "
+                                  f"status {int(st[j])}")
+            bad = np.nonzero((dig2 != bundle.digests[which]).any(axis=1))[0]
+            if len(bad):
+                raise CwError(-2, f"chunk bundle: {len(bad)} carried chunks do not hash to their manifest digest; the first is chunk "
+                                  f"{int(which[bad[0]])}")
+        # 4. the index, the store, the recipes
+        ref, new_idx, n_new = _zeros(n), _zeros(n, torch.int32), _zeros(1)
+        d_n, d_from, result, n_missing = _u64([n]), _u64(bundle.values), _zeros(2), _zeros(1)
+        outs = [(_u64(r.refs), _u64([len(r.refs)]), len(r.refs)) for r in bundle.recipes]
+        torch.cuda.synchronize()
+        self.index.dev_dedupe(d_dig.data_ptr(), n, self.base, ref.data_ptr(), new_idx.data_ptr(), n_new.data_ptr(), s)
+        dev_store_import_chunks(d_in.data_ptr(), in_bytes, d_loc.data_ptr(), d_n.data_ptr(), n, self.base, self.d_store.data_ptr(), self.store_bytes,
+                                self.d_used.data_ptr(), self.d_dir.data_ptr(), self.dir_base, self.dir_entries, result.data_ptr(), s,
+                                new_idx.data_ptr(), n_new.data_ptr())
+        for d_r, d_k, k in outs:
+            if k:
+                dev_translate_refs(d_r.data_ptr(), d_k.data_ptr(), k, d_from.data_ptr(), ref.data_ptr(), d_n.data_ptr(), n, d_r.data_ptr(),
+                                   n_missing.data_ptr(), s)
+        torch.cuda.synchronize()
+        verdict, total = _words(result)
+        if verdict or int(n_missing.item()):
+            raise CwError(-4, f"chunk bundle: admitted, yet the append was refused with verdict {verdict} ({total} bytes) or "
+                              f"{int(n_missing.item())} recipe positions found no value")
+        self.base += n
+        return [Recipe(d_r.cpu().numpy().view(np.uint64)[:k], r.offsets) for (d_r, _, k), r in zip(outs, bundle.recipes)]
+
+    def _restored_digests(self, d_in: int, in_bytes: int, d_loc: int, n_loc: int, which, lengths):
+        """The chunks ``which`` (positions of the n_loc cw_chunk_loc entries at d_loc, each sound, with the given lengths) restored from
+        the payload d_in[0..in_bytes) -- the payload as the store, the locs as its directory -- and hashed with this index's algorithm:
+        (cw_dev_restore_chunks' statuses, the digests as uint8[k, digest bytes])."""
+        import torch
+        s, db = self._stream(), digest_bytes(self.index.hash_alg)
+        cuts = np.concatenate([[0], np.cumsum(lengths)]).astype(np.uint64)
+        k, total = len(which), int(cuts[-1])
+        d_ref, d_raw, d_count = _u64(which), _u64(cuts), _u64([k])
+        out, status, dig2 = _zeros(total, torch.uint8), _zeros(k, torch.int32), _zeros(k * db, torch.uint8)
+        torch.cuda.synchronize()
+        dev_restore_chunks(self.comp_alg, d_in, in_bytes, d_loc, 0, n_loc, d_ref.data_ptr(), d_raw.data_ptr(), d_count.data_ptr(), k,
+                           out.data_ptr(), total, status.data_ptr(), s)
+        dev_hash_chunks(self.index.hash_alg, out.data_ptr(), total, d_raw.data_ptr(), d_count.data_ptr(), k, dig2.data_ptr(), s)
+        torch.cuda.synchronize()
+        return status.cpu().numpy()[:k], dig2.cpu().numpy()[:k * db].reshape(k, db)
+
+    def replicate_to(self, other: "ChunkStore", recipes, verify: bool = True) -> list:
+        """``other.import_bundle(self.export_bundle(recipes, known=other.index), verify)``: only the chunks ``other`` lacks travel, in
+        their stored form, and ``other`` gets recipes of its own for the same streams."""
+        return other.import_bundle(self.export_bundle(recipes, known=other.index), verify)
+
+    def scrub(self, keep=None) -> ScrubReport:
+        """Check every stored chunk once against the digest the index holds for its value (cw_store_scrub), in
+        windows of CW_STORE_PIECE decoded bytes.  ``keep`` is a list of recipes: only the entries they name are checked, and a named
+        entry that is missing shows as status 2; None checks every entry that is not all zero.  Raises CwError (-2) when a kept
+        recipe names a value outside the directory."""
+        import torch
+        d_live = 0
+        if keep is not None:
+            live, n_out = self._mark(keep, self._stream())
+            torch.cuda.synchronize()
+            self._refuse_outside(n_out, "kept recipes")
+            d_live = live.data_ptr()
+        torch.cuda.synchronize()  # (the store was written on torch's stream)
+        status, stats = store_scrub(self.index, self.comp_alg, self._triple(), d_live)
+        return ScrubReport(status, stats, self.dir_base)
+
+    def repair_from(self, other: "ChunkStore", report: ScrubReport, verify: bool = True) -> dict:
+        """Put the chunks ``report.damaged`` names back from ``other``, a store that holds them (one the streams were replicated to),
+        in stored form and under their own values, so that every recipe stays valid.  The damaged values' digests come from this
+        store's index, ``other``'s index finds them there, ``dev_store_export_chunks`` takes ``other``'s stored bytes out, and one
+        ``dev_store_replace_chunks`` appends them here and repoints the entries; the old bytes stay until the next ``compact``.  A
+        chunk is left out -- not a reason to refuse the rest -- when ``other`` lacks it, when its entry there is unsound or has
+        another length than the entry here, or, with ``verify``, when it does not restore from the exported bytes or does not hash
+        to the digest this index holds.  Returns dict(repaired, unavailable, no_digest): lists of values; no_digest are the damaged
+        values this index holds no digest for.  ValueError when codec or hash algorithm differ; CwError (-5) with ``e.needed`` (the
+        bytes wanted) when they do not fit behind ``used()``, nothing changed: ``compact`` makes room.  The index is never written."""
+        import torch
+        if other.comp_alg != self.comp_alg or other.index.hash_alg != self.index.hash_alg:
+            raise ValueError(f"peer of codec {other.comp_alg} / hash {other.index.hash_alg}, store of codec {self.comp_alg} / hash "
+                             f"{self.index.hash_alg}")
+        damaged = np.unique(np.ascontiguousarray(report.damaged, dtype=np.uint64))
+        out = dict(repaired=[], unavailable=[], no_digest=[])
+        if len(damaged) == 0:
+            return out
+        idx = damaged - np.uint64(self.dir_base)
+        if (damaged < np.uint64(self.dir_base)).any() or (idx >= np.uint64(self.dir_entries)).any():
+            raise CwError(-2, f"chunk store: the report names values outside the directory [{self.dir_base}, {self.dir_base + self.dir_entries})")
+        idx = idx.astype(np.int64)
+        s, n, db, m = self._stream(), self.dir_entries, digest_bytes(self.index.hash_alg), len(damaged)
+        # 1. the digests this index holds for the damaged values, in ascending value
+        live, dig, val, res = _zeros(n, torch.int32), _zeros(m * db, torch.uint8), _zeros(m), _zeros(3)
+        live[torch.from_numpy(idx).cuda()] = 1
+        torch.cuda.synchronize()
+        self.index.dev_export_live(live.data_ptr(), self.dir_base, n, dig.data_ptr(), val.data_ptr(), m, res.data_ptr(), s)
+        torch.cuda.synchronize()
+        has = val.cpu().numpy().view(np.uint64)[:m] != _MISS
+        out["no_digest"] = damaged[~has].tolist()
+        # 2. where the peer keeps them
+        found, n_found = _zeros(m), _zeros(1)
+        torch.cuda.synchronize()
+        other.index.dev_lookup(dig.data_ptr(), m, found.data_ptr(), n_found.data_ptr(), s)
+        torch.cuda.synchronize()
+        there = found.cpu().numpy().view(np.uint64)[:m].copy()
+        o_idx = there - np.uint64(other.dir_base)
+        ok = has & (there != _MISS) & (there >= np.uint64(other.dir_base)) & (o_idx < np.uint64(other.dir_entries))
+        o_idx = o_idx.astype(np.int64)
+        entries = lambda cs, at: cs.d_dir.view(-1, 2)[torch.from_numpy(at).cuda()].cpu().numpy().reshape(-1).view(LOC_DTYPE)  # noqa: E731
+        peer, mine = np.zeros(m, LOC_DTYPE), entries(self, idx)
+        if ok.any():
+            peer[ok] = entries(other, o_idx[ok])
+        ok &= _locs_sound(peer, other.store_bytes)
+        # (a replacement keeps the chunk's length, unless the entry here has no sound length of its own)
+        len_here, len_there = mine["raw"].astype(np.int64) & 0x1FFFF, peer["raw"].astype(np.int64) & 0x1FFFF
+        ok &= (len_here < 1) | (len_here > 65536) | (len_here == len_there)
+        which = np.nonzero(ok)[0]
+        nc = len(which)
+        if nc:
+            # 3. the peer's stored bytes, sized by a dry run
+            payload, total, d_loc = _export_chunks(other, _u64(there[which]), nc, s, whence=" from the peer")
+            locs = d_loc.cpu().numpy().view(LOC_DTYPE)[:nc].copy()
+            good = np.ones(nc, bool)
+            if verify:
+                st, dig2 = self._restored_digests(payload.data_ptr(), total, d_loc.data_ptr(), nc, np.arange(nc), len_there[which])
+                good = (st == 0) & (dig2 == dig.cpu().numpy()[:m * db].reshape(m, db)[which]).all(axis=1)
+            ok[which[~good]] = False
+            which, locs = which[good], locs[good]
+        out["unavailable"] = damaged[has & ~ok].tolist()
+        if len(which) == 0:
+            return out
+        # 4. room, then one replace
+        need, used = int(locs["stored"].astype(np.int64).sum()), self.used()
+        if used + need > self.store_bytes:
+            err = CwError(-5, f"chunk store: the repair's {need} bytes do not fit behind {used} of {self.store_bytes}")
+            err.needed = need
+            raise err
+        d_loc2, d_val2, d_k, result = _u8(locs), _u64(damaged[which]), _u64([len(which)]), _zeros(2)
+        torch.cuda.synchronize()
+        dev_store_replace_chunks(payload.data_ptr(), total, d_loc2.data_ptr(), d_val2.data_ptr(), d_k.data_ptr(), len(which), self.d_store.data_ptr(),
+                                 self.store_bytes, self.d_used.data_ptr(), self.d_dir.data_ptr(), self.dir_base, self.dir_entries,
+                                 result.data_ptr(), s)
+        torch.cuda.synchronize()
+        verdict, total = _words(result)
+        if verdict:
+            raise CwError(-4, f"chunk store: admitted, yet the replace was refused with verdict {verdict} ({total} bytes)")
+        out["repaired"] = damaged[which].tolist()
+        return out
+
+    def save(self, path) -> None:
+        """One ``.npz``: the index's export, the store bytes [0, used), the directory, base and the parameters."""
+        dig, val = self.index.export()
+        p = self.params
+        gear = p._gear if getattr(p, "_gear", None) is not None else np.zeros(0, np.uint64)
+        with open(path, "wb") as f:
+            np.savez(f, hash_alg=np.int64(self.index.hash_alg), max_entries=np.int64(self.index.max_entries), digests=dig, values=val,
+                     comp_alg=np.int64(self.comp_alg), store=self.d_store[:self.used()].cpu().numpy(), store_bytes=np.int64(self.store_bytes),
+                     directory=self.d_dir.cpu().numpy(), dir_base=np.uint64(self.dir_base), base=np.uint64(self.base),
+                     cdc=np.array([p.min_size, p.normal_size, p.max_size, p.mask_s, p.mask_l], np.uint64), gear=gear)
+
+    @classmethod
+    def load(cls, path) -> "ChunkStore":
+        """A new index and fresh device buffers from a snapshot."""
+        import torch
+        with np.load(path) as z:
+            cdc, gear = [int(v) for v in z["cdc"]], z["gear"]
+            params = CdcParams(cdc[0], cdc[1], cdc[2], cdc[3], cdc[4], gear if len(gear) else None)
+            index = DedupeIndex(int(z["hash_alg"]), int(z["max_entries"]))
+            try:
+                index.import_(z["digests"], z["values"])
+                directory, store = z["directory"], z["store"]
+                cs = cls(index, int(z["comp_alg"]), params, int(z["store_bytes"]), len(directory) // 2, int(z["dir_base"]))
+                cs.base = int(z["base"])
+                cs.d_store[:len(store)] = torch.from_numpy(store).cuda()
+                cs.d_dir.copy_(torch.from_numpy(directory).cuda())
+                cs.d_used.fill_(len(store))
+                torch.cuda.synchronize()
+            except Exception:
+                index.close()
+                raise
+        return cs
