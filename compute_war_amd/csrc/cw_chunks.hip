@@ -1,6 +1,6 @@
 // cw_chunks.hip -- host side of the device-resident calls over content-defined chunks: the cut (kernels: cdc_kernels.hip), the per-chunk
 // hash, the chunk codecs and their pack (chunk_codec_kernels.hip, pack_kernels.hip), the chunk store (restore_kernels.hip), its ranged reads (read_kernels.hip),
-// its mark and compact (store_gc_kernels.hip), its renumbering (renumber_kernels.hip) and its chunk bundles (replicate_kernels.hip).  Semantics: the public header.  Every refusal here comes before the device is touched.
+// its mark and compact (store_gc_kernels.hip), its renumbering (renumber_kernels.hip), its accounting (account_kernels.hip) and its chunk bundles (replicate_kernels.hip).  Semantics: the public header.  Every refusal here comes before the device is touched.
 
 #include "cw_host.h"
 
@@ -351,6 +351,28 @@ int cw_dev_store_renumber(const cw_chunk_loc *d_dir, uint64_t dir_base, size_t d
     return launched_nomem(cw::store_renumber_launch(d_dir, dir_base, dir_entries, d_live, new_base, d_new_dir, new_dir_base, new_dir_entries, d_from,
                                                     d_to, max_pairs, d_result, (hipStream_t)stream),
                           "store renumber launch");
+}
+
+// ---- per-stream accounting and reverse references: account (kernels: account_kernels.hip) --------------------------------------
+int cw_dev_store_account(const uint64_t *d_ref, const uint64_t *d_first, size_t nstreams, size_t max_positions, const cw_chunk_loc *d_dir,
+                         uint64_t dir_base, size_t dir_entries, const uint32_t *d_flag, cw_stream_account *d_acct, uint32_t *d_refcount,
+                         uint32_t *d_owner, uint64_t *d_totals, void *stream)
+{
+    int rc;
+    const char *null = !d_first ? "d_first" : !d_dir ? "d_dir" : !d_acct ? "d_acct" : !d_totals ? "d_totals" : max_positions && !d_ref ? "d_ref" : NULL;
+    if (null) return fail(CW_ERR_BAD_ARG, "NULL pointer: %s", null);
+    if (nstreams == 0) return fail(CW_ERR_BAD_ARG, "nstreams is 0");
+    if (nstreams > ((size_t)1 << 32) - 258) return fail(CW_ERR_BAD_ARG, "nstreams %zu > 2^32 - 258", nstreams); // (CW_OWNER_SHARED, CW_OWNER_NONE)
+    if (dir_entries == 0) return fail(CW_ERR_BAD_ARG, "dir_entries is 0");
+    if ((rc = check_count("max_positions", max_positions)) != CW_OK || (rc = check_count("dir_entries", dir_entries)) != CW_OK) return rc;
+    if ((rc = check_dir_aligned((uintptr_t)d_dir, "d_dir")) != CW_OK) return rc;
+    if ((rc = check_word_aligned((uintptr_t)d_ref | (uintptr_t)d_first | (uintptr_t)d_acct | (uintptr_t)d_totals,
+                                 "d_ref / d_first / d_acct / d_totals")) != CW_OK)
+        return rc;
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    return launched_nomem(cw::store_account_launch(d_ref, d_first, nstreams, max_positions, d_dir, dir_base, dir_entries, d_flag, d_acct, d_refcount,
+                                                   d_owner, d_totals, (hipStream_t)stream),
+                          "store account launch");
 }
 
 // ---- chunk bundles between stores: export, import, translate (kernels: replicate_kernels.hip) ----------------------------------

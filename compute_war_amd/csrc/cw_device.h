@@ -274,6 +274,12 @@ hipError_t store_renumber_launch(const void *dir, uint64_t dir_base, size_t dir_
                                  uint64_t new_dir_base, size_t new_dir_entries, uint64_t *from, uint64_t *to, size_t max_pairs, uint64_t *result,
                                  hipStream_t stream);
 
+// account (account_kernels.hip; semantics: the public header).  acct: cw_stream_account[nstreams]; flag, refcount and owner may be
+// NULL, ref may be when max_positions is 0
+hipError_t store_account_launch(const uint64_t *ref, const uint64_t *first, size_t nstreams, size_t max_positions, const void *dir,
+                                uint64_t dir_base, size_t dir_entries, const uint32_t *flag, void *acct, uint32_t *refcount, uint32_t *owner,
+                                uint64_t *totals, hipStream_t stream);
+
 // chunk bundles between stores (replicate_kernels.hip; semantics: the public header).  loc / dir: cw_chunk_loc entries, 16-byte aligned
 hipError_t store_export_launch(const uint8_t *store, size_t store_bytes, const void *dir, uint64_t dir_base, size_t dir_entries,
                                const uint64_t *values, const uint64_t *d_count, size_t max_count, uint8_t *out, size_t out_bytes, void *out_loc,

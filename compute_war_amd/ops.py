@@ -756,6 +756,27 @@ def dev_store_renumber(d_dir: int, dir_base: int, dir_entries: int, d_live: int,
                                       d_from or None, d_to or None, max_pairs, d_result, stream))
 
 
+class StreamAccount(C.Structure):
+    """cw_stream_account: what one stream of a ``dev_store_account`` call names, shares with no other stream and has in flagged chunks."""
+    _fields_ = [(k, C.c_uint64) for k in ("positions", "missing", "logical_bytes", "unique_chunks", "unique_stored", "unique_raw",
+                                          "flagged_positions", "flagged_bytes")]
+    OWNER_NONE, OWNER_SHARED = 0xFFFFFFFF, 0xFFFFFFFE  # CW_OWNER_NONE, CW_OWNER_SHARED
+
+
+ACCOUNT_DTYPE = np.dtype([(k, "<u8") for k, _ in StreamAccount._fields_])  # cw_stream_account as a numpy record
+
+
+def dev_store_account(d_ref: int, d_first: int, nstreams: int, max_positions: int, d_dir: int, dir_base: int, dir_entries: int, d_flag: int,
+                      d_acct: int, d_refcount: int, d_owner: int, d_totals: int, stream: int = 0) -> None:
+    """Stream f = positions [d_first[f], d_first[f + 1]) of d_ref: d_acct[f] (cw_stream_account) = what it names, what no other
+    stream of the call names and what lies in entries flagged by d_flag (u32 per entry, or 0); d_refcount[idx] / d_owner[idx] (u32,
+    or 0) = the positions that name entry idx and the one stream that does (or OWNER_NONE / OWNER_SHARED).  d_totals[0..8) = verdict
+    (1: d_first does not start at 0, decreases or ends above max_positions; nothing else written then), non-zero entries and their
+    stored bytes, referenced entries and theirs, shared entries and theirs, missing positions.  Not synchronised."""
+    check(lib().cw_dev_store_account(d_ref or None, d_first, nstreams, max_positions, d_dir, dir_base, dir_entries, d_flag or None, d_acct,
+                                     d_refcount or None, d_owner or None, d_totals, stream))
+
+
 def dev_store_export_chunks(d_store: int, store_bytes: int, d_dir: int, dir_base: int, dir_entries: int, d_values: int, d_count: int,
                             max_count: int, d_out: int, out_bytes: int, d_out_loc: int, d_result: int, stream: int = 0) -> None:
     """The stored bytes of the entries d_values[k], k < min(*d_count, max_count), back to back into d_out with d_out_loc[k] = where.

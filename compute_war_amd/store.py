@@ -10,14 +10,15 @@ from __future__ import annotations
 import numpy as np
 
 from ._lib import CwError, lib
-from .ops import (CdcParams, ChunkLoc, DedupeIndex, Store, _comp_id, _hash_id, _np_u8, chunk_slots_bytes, dev_hash_chunks, dev_read_ranges,
-                  dev_restore_chunks, dev_store_chunks, dev_store_compact, dev_store_export_chunks, dev_store_import_chunks, dev_store_mark,
+from .ops import (ACCOUNT_DTYPE, CdcParams, ChunkLoc, DedupeIndex, Store, _comp_id, _hash_id, _np_u8, chunk_slots_bytes, dev_hash_chunks,
+                  dev_read_ranges, dev_restore_chunks, dev_store_account, dev_store_chunks, dev_store_compact, dev_store_export_chunks, dev_store_import_chunks, dev_store_mark,
                   dev_store_renumber, dev_store_replace_chunks, dev_translate_refs, device_count, digest_bytes, init, store_ingest,
                   store_ingest_streams, store_restore, store_scrub)
 
 
 class Recipe:
-    """What restores one ingested stream: refs[j] = the value of chunk j's first occurrence, offsets[0..k] = its cuts."""
+    """What restores one ingested stream: refs[j] = the value of chunk j's first occurrence, offsets[0..k] = its cuts.  Stale after
+    ``ChunkStore.renumber`` unless it was passed to it: use the translated recipe that call returns."""
 
     def __init__(self, refs, offsets):
         self.refs = np.ascontiguousarray(refs, dtype=np.uint64)
@@ -96,7 +97,8 @@ def _export_chunks(cs: "ChunkStore", d_val, nc: int, s: int, damaged: str | None
 class ScrubReport:
     """What ``ChunkStore.scrub`` found: ``status`` (uint32, one per directory entry: 0 good, 1 malformed, 2 unsound entry, 3 digest
     mismatch, 4 orphan, 5 not selected), ``stats`` (cw_scrub_stats as a dict), ``damaged`` (the values with status 1, 2 or 3,
-    ascending) and ``orphans`` (the values with status 4: they decode, but the index holds no digest to judge them by)."""
+    ascending) and ``orphans`` (the values with status 4: they decode, but the index holds no digest to judge them by).  Stale after
+    ``ChunkStore.renumber``: status is per directory entry and the values are the old ones."""
 
     def __init__(self, status, stats: dict, dir_base: int):
         self.status, self.stats = np.ascontiguousarray(status, dtype=np.uint32), stats
@@ -107,6 +109,26 @@ class ScrubReport:
     @property
     def clean(self) -> bool:
         return len(self.damaged) == 0
+
+
+TOTALS = ("nonzero", "nonzero_stored", "referenced", "referenced_stored", "shared", "shared_stored", "missing")  # d_totals[1..7]
+
+
+class Account:
+    """What ``ChunkStore.account`` computed for the recipes of one call: ``streams`` (an ACCOUNT_DTYPE record per recipe, in the order
+    given), ``refcount`` (uint32 per directory entry: the positions that name it) and ``owner`` (uint32 per directory entry: the
+    index of the one recipe that names it, ``Account.NONE`` or ``Account.SHARED``), ``totals`` (a dict: the words of d_totals under
+    the names of ``TOTALS``, plus ``unreferenced_entries`` and ``unreferenced_stored``: what a ``compact`` that keeps these recipes
+    drops).  Exact for the recipes passed and for the store as it was; stale after ``ChunkStore.renumber``, like a ScrubReport:
+    ``refcount`` and ``owner`` are per directory entry."""
+    NONE, SHARED = 0xFFFFFFFF, 0xFFFFFFFE
+
+    def __init__(self, streams, refcount, owner, totals):
+        self.streams = np.ascontiguousarray(streams, dtype=ACCOUNT_DTYPE)
+        self.refcount, self.owner = np.ascontiguousarray(refcount, dtype=np.uint32), np.ascontiguousarray(owner, dtype=np.uint32)
+        self.totals = dict(zip(TOTALS, (int(v) for v in totals)))
+        self.totals["unreferenced_entries"] = self.totals["nonzero"] - self.totals["referenced"]
+        self.totals["unreferenced_stored"] = self.totals["nonzero_stored"] - self.totals["referenced_stored"]
 
 
 class Bundle:
@@ -153,7 +175,9 @@ class Bundle:
 class ChunkStore:
     """A dedupe index with the bytes behind it: ``ingest`` chunks, dedupes and compresses a buffer and appends its new chunks to a
     device-resident store, ``restore`` turns a recipe back into bytes, ``read`` / ``read_ranges`` give byte ranges of it, ``compact`` forgets every stream but the ones named,
-    ``renumber`` gives the directory slots of forgotten and duplicate chunks back.
+    ``renumber`` gives the directory slots of forgotten and duplicate chunks back, ``account`` says what each stream names alone
+    (what dropping it gives back) and ``affected`` which streams a scrub's damaged chunks hurt.  ``renumber`` changes every value:
+    recipes not passed to it, a ``ScrubReport`` and an ``Account`` taken before it are stale afterwards.
     The store is three torch buffers this object owns (bytes, cursor, directory: the caller-owned triple of cw_dev_store_chunks);
     chunk values count up from ``dir_base`` over the ingests.
     ``ingest`` is one device call: the whole buffer has to fit on the device next to its slots.  ``ingest_stream`` and
@@ -499,6 +523,46 @@ class ChunkStore:
         self.d_dir, self.dir_entries, self.dir_base, self.base = new_dir, new_entries, new_base, next_base
         return [Recipe(w[2].cpu().numpy().view(np.uint64)[:len(r.refs)], r.offsets.copy()) if w is not None else Recipe([], r.offsets.copy())
                 for r, w in zip(recipes, work)]
+
+    def account(self, recipes, flagged=None) -> Account:
+        """Per-stream accounting and reverse references for ``recipes`` (``dev_store_account``): one upload of
+        the concatenated refs with their stream index, one call, one synchronise.  ``streams[i].unique_stored`` is what dropping
+        recipe i alone lets ``compact`` give back, given that the other recipes passed are all that is kept.  ``flagged`` is None, a
+        ``ScrubReport`` (its damaged entries are flagged) or a uint32 array with one element per directory entry (any non-zero
+        value is a flag); ``flagged_positions`` / ``flagged_bytes`` say how much of each stream sits in flagged chunks.  The distinct
+        entries a stream names among the shared ones are not counted: ``account([r])`` alone gives them as ``unique_chunks``.  No
+        recipes: an empty Account, the device untouched."""
+        recipes = list(recipes)
+        n = self.dir_entries
+        if not recipes:
+            return Account(np.zeros(0, ACCOUNT_DTYPE), np.zeros(n, np.uint32), np.full(n, Account.NONE, np.uint32), [0] * len(TOTALS))
+        import torch
+        if isinstance(flagged, ScrubReport):
+            flagged = ((flagged.status >= 1) & (flagged.status <= 3)).astype(np.uint32)
+        if flagged is not None:
+            flagged = np.ascontiguousarray(flagged, dtype=np.uint32).reshape(-1)
+            if len(flagged) != n:
+                raise ValueError(f"flagged has {len(flagged)} elements, the directory {n} entries")
+        first = np.concatenate([[0], np.cumsum([len(r.refs) for r in recipes])]).astype(np.uint64)
+        k, nf, s = int(first[-1]), len(recipes), self._stream()
+        d_ref, d_first = _u64(np.concatenate([r.refs for r in recipes]) if k else [0]), _u64(first)
+        d_flag = None if flagged is None else _u8(flagged)
+        acct, refcount, owner, totals = _zeros(nf * 8), _zeros(n, torch.int32), _zeros(n, torch.int32), _zeros(8)
+        torch.cuda.synchronize()  # (torch zeroed and copied on its own stream)
+        dev_store_account(d_ref.data_ptr(), d_first.data_ptr(), nf, k, self.d_dir.data_ptr(), self.dir_base, n,
+                          0 if d_flag is None else d_flag.data_ptr(), acct.data_ptr(), refcount.data_ptr(), owner.data_ptr(), totals.data_ptr(), s)
+        torch.cuda.synchronize()
+        t = _words(totals)
+        if t[0]:
+            raise CwError(-4, f"chunk store: the account of {nf} recipes was refused with verdict {t[0]}")
+        return Account(acct.cpu().numpy().view(ACCOUNT_DTYPE)[:nf], refcount.cpu().numpy().view(np.uint32)[:n],
+                       owner.cpu().numpy().view(np.uint32)[:n], t[1:])
+
+    def affected(self, recipes, report: ScrubReport) -> list:
+        """The recipes that a scrub's damaged chunks hurt: ``(index, flagged_positions, flagged_bytes)`` for every recipe of
+        ``account(recipes, flagged=report)`` with a position in a damaged chunk, in the order given."""
+        streams = self.account(recipes, flagged=report).streams
+        return [(i, int(a["flagged_positions"]), int(a["flagged_bytes"])) for i, a in enumerate(streams) if a["flagged_positions"] > 0]
 
     def export_bundle(self, recipes, known=None) -> Bundle:
         """The chunks ``recipes`` name as a Bundle: their digests and values in ascending value (``dev_store_mark`` of every recipe,

@@ -761,6 +761,54 @@ int cw_dev_store_renumber(const cw_chunk_loc *d_dir, uint64_t dir_base, size_t d
 int cw_dev_dedupe_revalue(cw_dedupe_t *x, const uint64_t *d_from, const uint64_t *d_to, const uint64_t *d_npairs, size_t max_pairs,
                           uint64_t range_base, uint64_t range_entries, uint64_t *d_result /* [3] */, void *stream);
 
+/* ---- per-stream accounting and reverse references ------------------------------------------------------
+ * "What does dropping this stream give back?" and "which streams do these damaged chunks hurt?" are one computation: reverse
+ * references from directory entries to the streams that name them.  The store keeps no reference counts (section 15: mark and
+ * sweep); these are computed on demand from the recipes the caller passes, exact for that set, and nothing is kept between calls.
+ * The call follows the store's conventions: device pointers, counts read on the device, queued on `stream`, nothing synchronises,
+ * every decision made on the device.  Everything summed is an integer, so the result is bit for bit a function of the arguments. */
+typedef struct cw_stream_account {   /* 64 bytes, one per stream of the call */
+    uint64_t positions;          /* positions of the stream: d_first[f+1] - d_first[f] */
+    uint64_t missing;            /* positions that name no stored chunk: d_ref - dir_base outside [0, dir_entries) in u64
+                                    (so CW_DEDUPE_MISS and values below the base), or an all-zero entry */
+    uint64_t logical_bytes;      /* the entry's length (bits 0..16 of raw) summed over the other positions */
+    uint64_t unique_chunks;      /* entries this stream names and no other stream of the call does */
+    uint64_t unique_stored;      /* their `stored` summed: what dropping this stream alone lets compact give back */
+    uint64_t unique_raw;         /* their lengths summed, each entry once */
+    uint64_t flagged_positions;  /* non-missing positions whose entry idx has d_flag[idx] != 0; 0 when d_flag == NULL */
+    uint64_t flagged_bytes;      /* those positions' lengths summed: the stream bytes that sit in flagged chunks */
+} cw_stream_account;
+#define CW_OWNER_NONE   0xFFFFFFFFu   /* no position names the entry (every all-zero entry) */
+#define CW_OWNER_SHARED 0xFFFFFFFEu   /* positions of at least two different streams name it */
+/* Accounts the streams of one call against a directory.
+ *   streams       d_ref is the concatenation of the recipes' refs, d_first[nstreams + 1] the index of each stream's first position
+ *                 (what cw_dev_ingest_commit_streams and cw_dev_cdc_streams write): stream f is positions [d_first[f],
+ *                 d_first[f+1]), equal neighbours are an empty stream, and n = d_first[nstreams] is read on the device.
+ *   verdict       d_totals[0], decided on the device before anything else is written: 1 when d_first[0] != 0, when a pair
+ *                 decreases or when n > max_positions, and then not a byte of d_acct, d_refcount, d_owner or d_totals[1..7]
+ *                 changes; else 0.
+ *   rules         no entry is judged (cw_dev_store_renumber's rule: a non-zero entry counts with its fields as they are).  A
+ *                 position that names an all-zero entry is missing and enters no count of that entry.  d_refcount[idx] = the
+ *                 non-missing positions of all streams that name idx; d_owner[idx] = the one stream that names idx, or
+ *                 CW_OWNER_NONE / CW_OWNER_SHARED.  d_flag has the shape of d_live and of cw_store_scrub's status: one u32 per
+ *                 entry, any non-zero value is a flag.
+ *   d_totals[8]   {verdict, the non-zero entries, their stored summed, the referenced entries, their stored summed, the shared
+ *                 entries, their stored summed, the missing positions of all streams}.  [1] - [3] entries are unreferenced: what
+ *                 a compact that keeps these recipes drops.  Every output is written whole, not accumulated.
+ * A stream's count of distinct entries among the shared ones is not computed; a call over that stream alone gives it as
+ * unique_chunks.  Whatever the buffers hold, no load leaves d_ref[0..min(n, max_positions)), d_first[0..nstreams],
+ * d_dir[0..dir_entries) or d_flag[0..dir_entries), and no store leaves the outputs and the scratch.  CW_ERR_BAD_ARG before anything
+ * is launched: a NULL pointer (d_flag, d_refcount and d_owner may be NULL; d_ref may be when max_positions is 0), nstreams == 0 or
+ * > 2^32 - 258 (the two sentinels), max_positions > 2^32 - 256, dir_entries == 0 or > 2^32 - 256, a directory that is not 16-byte
+ * aligned, a d_ref, d_first, d_acct or d_totals that is not 8-byte aligned.  Scratch, per stream: at most 72 + 12 * dir_entries
+ * bytes.  Not synchronised.                                                                                                       */
+int cw_dev_store_account(const uint64_t *d_ref, const uint64_t *d_first, size_t nstreams, size_t max_positions,
+                         const cw_chunk_loc *d_dir, uint64_t dir_base, size_t dir_entries,
+                         const uint32_t *d_flag /* may be NULL */,
+                         cw_stream_account *d_acct /* [nstreams] */,
+                         uint32_t *d_refcount /* [dir_entries], may be NULL */, uint32_t *d_owner /* [dir_entries], may be NULL */,
+                         uint64_t *d_totals /* [8] */, void *stream);
+
 /* ---- chunk bundles: stored chunks from one store to another -------------------------------------------
  * A bundle is a manifest and a payload.  The manifest lists the n distinct chunks a set of recipes names, in ascending value of
  * the sending store: digest[k], value[k] and loc[k] (a cw_chunk_loc whose pos is relative to the payload; all zero = listed but
