@@ -15,14 +15,14 @@
 #include <stdint.h>
 
 #include "cw_device.h"
-#include "stream_scratch.h"
+#include "store_device.h"
 
 namespace cw {
 
 namespace {
 
-constexpr unsigned kThreads = 256;
-constexpr uint32_t kLenMask = 0x1FFFFu;                               // cw_chunk_loc::raw, bits 0..16: the chunk's length
+using namespace chunkstore;
+
 constexpr uint32_t kOwnerNone = 0xFFFFFFFFu, kOwnerShared = 0xFFFFFFFEu; // CW_OWNER_NONE, CW_OWNER_SHARED
 typedef unsigned long long u64;
 
@@ -32,25 +32,6 @@ enum { kPositions, kMissing, kLogicalBytes, kUniqueChunks, kUniqueStored, kUniqu
 __device__ __forceinline__ void add64(u64 *p, u64 v)
 {
     if (v) __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// the wavefront's sum of v in lane 0 (every lane calls)
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
-// the workgroup's sum of v in thread 0 (kThreads threads, every one of them calls)
-__device__ __forceinline__ u64 group_sum(u64 v, u64 *wsum)
-{
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if ((threadIdx.x & 63u) == 0) wsum[threadIdx.x >> 6] = v;
-    __syncthreads();
-    u64 all = 0;
-    for (uint32_t w = 0; w < kThreads / 64; w++) all += wsum[w];
-    __syncthreads(); // the next sum writes wsum again
-    return all;
 }
 
 // ---- 1. the check ------------------------------------------------------------------------------------------------------------------
@@ -124,13 +105,13 @@ account_positions_kernel(const uint32_t *__restrict__ verdict, const uint64_t *_
 
         uint32_t missing = 0, len = 0, flagged = 0;
         if (active) {
-            const uint64_t idx = ref[p] - dir_base; // a value below the base wraps out of range
+            uint64_t idx;
             missing = 1;
-            if (idx < dir_entries) {
-                const uint4 e = dir[idx];
-                if ((e.x | e.y | e.z | e.w) != 0) {
+            if (names_entry(ref[p], dir_base, dir_entries, idx)) {
+                const Entry e(dir[idx]);
+                if (e.nonzero) {
                     missing = 0;
-                    len = e.w & kLenMask;
+                    len = e.len();
                     flagged = flag && flag[idx] != 0;
                     atomicAdd(&count[idx], 1u);
                     atomicMin(&lowest[idx], f);
@@ -184,11 +165,11 @@ account_entries_kernel(const uint32_t *__restrict__ verdict, const uint4 *__rest
         const uint64_t idx = i0 + lane;
         uint32_t own = kOwnerNone, stored = 0, len = 0;
         if (idx < dir_entries) {
-            const uint4 e = dir[idx];
+            const Entry e(dir[idx]);
             const uint32_t c = count[idx]; // (c != 0: a position named the entry, which is then not all zero)
-            const bool nz = (e.x | e.y | e.z | e.w) != 0;
-            stored = e.z;
-            len = e.w & kLenMask;
+            const bool nz = e.nonzero;
+            stored = e.stored;
+            len = e.len();
             if (c) own = lowest[idx] == highest[idx] ? lowest[idx] : kOwnerShared;
             if (refcount) refcount[idx] = c;
             if (owner) owner[idx] = own;
@@ -236,13 +217,6 @@ account_entries_kernel(const uint32_t *__restrict__ verdict, const uint4 *__rest
 
 // per stream: the verdict at [0], the counts, the lowest and the highest streams (u32, dir_entries each) from byte 64
 StreamScratch<DeviceBuf> account_spaces;
-constexpr size_t kHead = 64;
-
-unsigned lane_grid(size_t n)
-{
-    const size_t grid = (n + kThreads - 1) / kThreads;
-    return (unsigned)(grid > 256 * 8 ? 256 * 8 : grid);
-}
 
 } // namespace
 
@@ -252,11 +226,11 @@ hipError_t store_account_launch(const uint64_t *ref, const uint64_t *first, size
 {
     auto &w = account_spaces.at(stream);
     LaunchLock sequence(w.launch); // the head and the per-entry words are shared by the launches below
-    hipError_t e = w.reserve(kHead + dir_entries * 12, (size_t)1 << 20);
+    hipError_t e = w.reserve(kScratchHead + dir_entries * 12, (size_t)1 << 20);
     if (e != hipSuccess) return e;
     uint32_t *verdict = w.as<uint32_t>();
-    uint32_t *count = reinterpret_cast<uint32_t *>(w.as<uint8_t>() + kHead), *lowest = count + dir_entries, *highest = lowest + dir_entries;
-    if ((e = hipMemsetAsync(verdict, 0, kHead, stream)) != hipSuccess) return e;
+    uint32_t *count = reinterpret_cast<uint32_t *>(w.as<uint8_t>() + kScratchHead), *lowest = count + dir_entries, *highest = lowest + dir_entries;
+    if ((e = hipMemsetAsync(verdict, 0, kScratchHead, stream)) != hipSuccess) return e;
     const uint4 *entries = static_cast<const uint4 *>(dir);
     u64 *a = static_cast<u64 *>(acct), *t = reinterpret_cast<u64 *>(totals);
     hipLaunchKernelGGL(account_check_kernel, dim3(lane_grid(nstreams)), dim3(kThreads), 0, stream, first, (uint64_t)nstreams,

@@ -5,7 +5,7 @@
 //   plan    a lane per range: the range's own verdict (status 3 or 0), its first touched position and its piece count
 //           (piece = a touched position), found by binary search in the recipe's offsets
 //   scan    the piece counts -> piece offsets and their total (pack_launch, index only)
-//   pieces  a lane per piece, 64 at a time: restore_chunks_kernel's entry checks; a compressed chunk that lies wholly inside its
+//   pieces  a lane per piece, 64 at a time: the entry's soundness (store_device.h); a compressed chunk that lies wholly inside its
 //           range is decoded straight into the destination, raw entries are copied by the whole wavefront clipped to the range
 //   edges   a lane per edge slot (2k: the first piece of range k, 2k + 1: its last): a compressed chunk the range covers only in
 //           part is decoded WHOLE into the lane's own 64 KiB buffer (an LZ chunk decodes only from its start), then the wavefront
@@ -18,16 +18,14 @@
 #include "cw_device.h"
 #include "lane_codec.h"
 #include "lz_device.h"
-#include "stream_scratch.h"
+#include "store_device.h"
 
 namespace cw {
 
 namespace {
 
 using namespace lane;
-
-constexpr unsigned kThreads = 256;
-constexpr uint32_t kRawFlag = 0x80000000u, kLenMask = 0x1FFFFu; // cw_chunk_loc::raw (CW_CHUNK_RAW; bits 17..30 stay 0)
+using namespace chunkstore;
 
 // the store, its directory and the recipe, as cw_dev_restore_chunks takes them
 struct Recipe {
@@ -87,8 +85,8 @@ read_plan_kernel(Recipe c, Ranges r, uint64_t dst_bytes, uint32_t *__restrict__ 
 }
 
 // ---- a piece ------------------------------------------------------------------------------------------------------------------
-// What position j means to range [a, a + len): restore_chunks_kernel's checks of the recipe and of the entry, with the range's
-// destination check (made by the plan) in the place of the chunk's.
+// What position j means to range [a, a + len): restore_chunks_kernel's checks of the recipe and store_device.h's rule for the entry, with
+// the range's destination check (made by the plan) in the place of the chunk's.
 struct Piece {
     bool touched = false; // a non-empty (or decreasing) raw extent: an empty one is touched by no range
     bool refuse = true, raw = false, whole = false;
@@ -103,6 +101,9 @@ struct Piece {
         touched = rs != re;
         if (!touched) return;
         if (r >= c.dir_base && idx < c.dir_entries && rs < re && re - rs <= kMaxChunkBytes) {
+            // Entry::sound (store_device.h) and `len != re - rs`, in this kernel's own spelling: cw_dev_read_ranges measured 1-2 %
+            // slower over 4 KiB ranges with the lookup and the rule taken from the header, in either of two forms
+            // (profiles/r22_store_device_ab.txt); tests/test_gpu_store_entry.py holds the two spellings together
             const uint4 e = c.dir[idx];
             pos = (uint64_t)e.y << 32 | e.x;
             stored = e.z;
@@ -139,13 +140,7 @@ read_pieces_kernel(Recipe c, Ranges r, const uint32_t *__restrict__ first_pos, c
         const bool decode = q.touched && !q.refuse && !q.raw && q.whole, skip = !decode || q.stored > (1u << 24);
         const bool bad = lane_decode<ALG>(c.store + (skip ? 0 : q.pos), skip ? 0u : q.stored, dst + (skip ? 0 : to), skip ? 0u : q.len, skip);
         if (q.touched && (q.refuse || (decode && bad))) atomicMax(status + k, q.refuse ? 2u : 1u);
-        unsigned long long copies = __ballot(q.touched && !q.refuse && q.raw && q.n != 0);
-        while (copies) {
-            const int l = __ffsll((long long)copies) - 1;
-            copies &= copies - 1;
-            const uint64_t from = __shfl((unsigned long long)(q.pos + q.lo), l, 64), at = __shfl((unsigned long long)(to + q.lo), l, 64);
-            lz::copy_g2g(dst + at, c.store + from, (uint32_t)__shfl((int)q.n, l, 64), threadIdx.x);
-        }
+        wave_copy(q.touched && !q.refuse && q.raw && q.n != 0, c.store, q.pos + q.lo, dst, to + q.lo, q.n);
     }
 }
 
@@ -154,6 +149,7 @@ read_pieces_kernel(Recipe c, Ranges r, const uint32_t *__restrict__ first_pos, c
 // Only the first kEdgeLanes lanes of a wavefront are edge lanes (the copies use all 64): the buffers bound the number of decoders, and
 // 16,384 of them as whole wavefronts would be one wavefront per compute unit, three of its four SIMDs idle.
 constexpr uint32_t kEdgeLanes = 16;
+static_assert(kEdgeLanes <= 64, "an edge lane's buffer is found by its index in the wavefront (wave_copy's from_slot)");
 template <int ALG>
 __global__ void __launch_bounds__(64)
 read_edges_kernel(Recipe c, Ranges r, const uint32_t *__restrict__ first_pos, const uint32_t *__restrict__ pieces, uint8_t *__restrict__ bufs,
@@ -179,15 +175,8 @@ read_edges_kernel(Recipe c, Ranges r, const uint32_t *__restrict__ first_pos, co
         if (decode && bad) atomicMax(status + k, 1u);
         // (a wavefront's own vector memory operations are performed in order: the fence only keeps the compiler from moving them)
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        unsigned long long copies = __ballot(decode && !bad && q.n != 0);
-        while (copies) {
-            const int l = __ffsll((long long)copies) - 1;
-            copies &= copies - 1;
-            const uint64_t owner = (uint64_t)blockIdx.x * kEdgeLanes + (uint64_t)l;
-            const uint32_t lo = (uint32_t)__shfl((int)q.lo, l, 64);
-            const uint64_t at = __shfl((unsigned long long)(to + q.lo), l, 64);
-            lz::copy_g2g(dst + at, bufs + owner * (uint64_t)kMaxChunkBytes + lo, (uint32_t)__shfl((int)q.n, l, 64), threadIdx.x);
-        }
+        // (a decoding lane is an edge lane: its buffer is the threadIdx.x-th of the wavefront's)
+        wave_copy(decode && !bad && q.n != 0, bufs + (uint64_t)blockIdx.x * kEdgeLanes * kMaxChunkBytes, q.lo, dst, to + q.lo, q.n, kMaxChunkBytes);
     }
 }
 
@@ -204,7 +193,6 @@ struct ReadSpace {
     }
 };
 StreamScratch<ReadSpace> read_spaces;
-constexpr size_t kReadHead = 64;
 // 16,384 edge lanes (1 GiB of buffers): an eighth of the lanes the restore's grid keeps decoding (256 * 8 wavefronts of 64), spread
 // over 1,024 wavefronts, one on every SIMD.  The restore's lane count would take 8 GiB of scratch per stream for the edges alone.
 constexpr size_t kMaxEdgeLanes = 16384, kMinEdgeLanes = 64;
@@ -220,7 +208,7 @@ hipError_t read_ranges_launch(int lzf, const uint8_t *store, size_t store_bytes,
     auto &w = read_spaces.at(stream);
     LaunchLock sequence(w.launch); // plan and buffers are shared by the launches below
     hipError_t e;
-    const size_t plan_bytes = kReadHead + (max_ranges + 1) * 8 + max_ranges * 8;
+    const size_t plan_bytes = kScratchHead + (max_ranges + 1) * 8 + max_ranges * 8;
     // (a buffer is only replaced by a larger one: the queued launches of this stream that use the old one have to finish first)
     if (w.plan.bytes() && w.plan.bytes() < plan_bytes && (e = hipStreamSynchronize(stream)) != hipSuccess) return e;
     if ((e = w.plan.reserve(plan_bytes, 4096)) != hipSuccess) return e;
@@ -237,28 +225,25 @@ hipError_t read_ranges_launch(int lzf, const uint8_t *store, size_t store_bytes,
             w.lane_limit = nbuf;
         }
     }
-    unsigned long long *off = reinterpret_cast<unsigned long long *>(w.plan.as<uint8_t>() + kReadHead);
+    unsigned long long *off = reinterpret_cast<unsigned long long *>(w.plan.as<uint8_t>() + kScratchHead);
     uint32_t *first = reinterpret_cast<uint32_t *>(off + max_ranges + 1), *pieces = first + max_ranges;
     const Recipe c{store, (uint64_t)store_bytes, static_cast<const uint4 *>(dir), dir_base, (uint64_t)dir_entries, ref, raw_offsets, d_count,
                    (uint64_t)max_count};
     const Ranges r{range_off, range_len, range_dst, d_nranges, (uint64_t)max_ranges};
 
-    size_t grid = (max_ranges + kThreads - 1) / kThreads;
-    if (grid > 256 * 8) grid = 256 * 8;
-    hipLaunchKernelGGL(read_plan_kernel, dim3((unsigned)grid), dim3(kThreads), 0, stream, c, r, (uint64_t)dst_bytes, first, pieces, status);
+    hipLaunchKernelGGL(read_plan_kernel, dim3(lane_grid(max_ranges)), dim3(kThreads), 0, stream, c, r, (uint64_t)dst_bytes, first, pieces, status);
     // off[k] = sum of pieces[0..k) for k <= max_ranges
     if ((e = pack_launch(nullptr, 0, pieces, max_ranges, nullptr, reinterpret_cast<uint64_t *>(off), stream)) != hipSuccess) return e;
     // at most max_count pieces per range
     const size_t most = max_count && max_ranges > ((size_t)1 << 40) / max_count ? (size_t)1 << 40 : max_ranges * max_count;
-    grid = (most + 63) / 64;
-    if (grid > 256 * 8) grid = 256 * 8;
+    const unsigned grid = decode_grid(most);
     const size_t edge_grid = (nbuf + kEdgeLanes - 1) / kEdgeLanes;
     if (grid && lzf) {
-        hipLaunchKernelGGL(read_pieces_kernel<1>, dim3((unsigned)grid), dim3(64), 0, stream, c, r, first, off, dst, status);
+        hipLaunchKernelGGL(read_pieces_kernel<1>, dim3(grid), dim3(64), 0, stream, c, r, first, off, dst, status);
         hipLaunchKernelGGL(read_edges_kernel<1>, dim3((unsigned)edge_grid), dim3(64), 0, stream, c, r, first, pieces, w.bufs.as<uint8_t>(),
                            (uint64_t)nbuf, dst, status);
     } else if (grid) {
-        hipLaunchKernelGGL(read_pieces_kernel<0>, dim3((unsigned)grid), dim3(64), 0, stream, c, r, first, off, dst, status);
+        hipLaunchKernelGGL(read_pieces_kernel<0>, dim3(grid), dim3(64), 0, stream, c, r, first, off, dst, status);
         hipLaunchKernelGGL(read_edges_kernel<0>, dim3((unsigned)edge_grid), dim3(64), 0, stream, c, r, first, pieces, w.bufs.as<uint8_t>(),
                            (uint64_t)nbuf, dst, status);
     }
@@ -268,7 +253,7 @@ hipError_t read_ranges_launch(int lzf, const uint8_t *store, size_t store_bytes,
 size_t read_ranges_scratch_bytes(size_t max_ranges)
 {
     const size_t nbuf = 2 * max_ranges < kMaxEdgeLanes ? 2 * max_ranges : kMaxEdgeLanes;
-    return max_ranges ? kReadHead + 8 + 16 * max_ranges + nbuf * kMaxChunkBytes : 0;
+    return max_ranges ? kScratchHead + 8 + 16 * max_ranges + nbuf * kMaxChunkBytes : 0;
 }
 
 } // namespace cw

@@ -15,13 +15,13 @@
 #include <stdint.h>
 
 #include "cw_device.h"
-#include "stream_scratch.h"
+#include "store_device.h"
 
 namespace cw {
 
 namespace {
 
-constexpr unsigned kThreads = 256;
+using namespace chunkstore;
 
 // flags[idx] = 1 for a kept entry (not all zero, and flagged when live is given), else 0; *n_dropped += the non-zero entries not kept
 __global__ void __launch_bounds__(kThreads)
@@ -32,19 +32,13 @@ renumber_flags_kernel(const uint4 *__restrict__ dir, uint64_t dir_entries, const
     const uint64_t threads = (uint64_t)gridDim.x * kThreads;
     uint32_t dropped = 0; // (a thread sees at most dir_entries / threads + 1 < 2^32 entries)
     for (uint64_t idx = (uint64_t)blockIdx.x * kThreads + threadIdx.x; idx < dir_entries; idx += threads) {
-        const uint4 e = dir[idx];
-        const bool nonzero = (e.x | e.y | e.z | e.w) != 0;
-        const bool keep = nonzero && (!live || live[idx] != 0);
+        const Entry e(dir[idx]);
+        const bool keep = e.nonzero && (!live || live[idx] != 0);
         flags[idx] = keep;
-        dropped += nonzero && !keep;
+        dropped += e.nonzero && !keep;
     }
-    for (int off = 32; off > 0; off >>= 1) dropped += __shfl_down(dropped, off, 64);
-    if ((threadIdx.x & 63u) == 0) wsum[threadIdx.x >> 6] = dropped;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    uint32_t all = 0;
-    for (uint32_t w = 0; w < kThreads / 64; w++) all += wsum[w];
-    if (all) __hip_atomic_fetch_add(n_dropped, (unsigned long long)all, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t all = group_sum(dropped, wsum);
+    if (threadIdx.x == 0 && all) __hip_atomic_fetch_add(n_dropped, (unsigned long long)all, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // where the K kept entries go, and what fill, scatter and finish are gated on
@@ -103,13 +97,6 @@ renumber_finish_kernel(const unsigned long long *__restrict__ rank, uint64_t dir
 
 // per stream: the dropped count at [0], the ranks (u64, dir_entries + 1) from byte 64, the flags (u32) behind them
 StreamScratch<DeviceBuf> renumber_spaces;
-constexpr size_t kHead = 64;
-
-unsigned lane_grid(size_t n)
-{
-    const size_t grid = (n + kThreads - 1) / kThreads;
-    return (unsigned)(grid > 256 * 8 ? 256 * 8 : grid);
-}
 
 } // namespace
 
@@ -119,18 +106,17 @@ hipError_t store_renumber_launch(const void *dir, uint64_t dir_base, size_t dir_
 {
     auto &w = renumber_spaces.at(stream);
     LaunchLock sequence(w.launch); // head, ranks and flags are shared by the launches below
-    hipError_t e = w.reserve(kHead + (dir_entries + 1) * 8 + dir_entries * 4, (size_t)1 << 20);
+    ScanScratch s;
+    hipError_t e = scan_scratch(w, dir_entries, stream, s);
     if (e != hipSuccess) return e;
-    unsigned long long *head = w.as<unsigned long long>();
-    uint64_t *rank = reinterpret_cast<uint64_t *>(w.as<uint8_t>() + kHead);
-    uint32_t *flags = reinterpret_cast<uint32_t *>(rank + dir_entries + 1);
-    if ((e = hipMemsetAsync(head, 0, kHead, stream)) != hipSuccess) return e;
+    unsigned long long *head = s.head_as<unsigned long long>();
+    uint32_t *flags = s.sizes;
     const uint4 *entries = static_cast<const uint4 *>(dir);
     hipLaunchKernelGGL(renumber_flags_kernel, dim3(lane_grid(dir_entries)), dim3(kThreads), 0, stream, entries, (uint64_t)dir_entries, live, flags,
                        head);
     // rank[idx] = the kept entries below idx, for idx <= dir_entries
-    if ((e = pack_launch(nullptr, 0, flags, dir_entries, nullptr, rank, stream)) != hipSuccess) return e;
-    const unsigned long long *r = reinterpret_cast<const unsigned long long *>(rank);
+    if ((e = pack_launch(nullptr, 0, flags, dir_entries, nullptr, s.off, stream)) != hipSuccess) return e;
+    const unsigned long long *r = s.offsets();
     const Placement p{new_base, new_dir_base, (uint64_t)new_dir_entries, (uint64_t)max_pairs};
     if (new_dir_entries)
         hipLaunchKernelGGL(renumber_fill_kernel, dim3(lane_grid(new_dir_entries)), dim3(kThreads), 0, stream, r, (uint64_t)dir_entries, p,

@@ -21,32 +21,15 @@
 #include <stdint.h>
 
 #include "cw_device.h"
-#include "lz_device.h"
-#include "stream_scratch.h"
+#include "store_device.h"
 
 namespace cw {
 
 namespace {
 
-constexpr unsigned kThreads = 256;
-constexpr uint32_t kRawFlag = 0x80000000u, kLenMask = 0x1FFFFu; // cw_chunk_loc::raw (CW_CHUNK_RAW; bits 17..30 stay 0)
-constexpr uint32_t kUnsound = 1u, kOutside = 2u, kLength = 4u;  // the head's flag word
+using namespace chunkstore;
 
-struct Entry {
-    uint64_t pos;
-    uint32_t stored, word;
-    bool nonzero;
-    __device__ __forceinline__ explicit Entry(const uint4 e) : pos((uint64_t)e.y << 32 | e.x), stored(e.z), word(e.w), nonzero((e.x | e.y | e.z | e.w) != 0) {}
-    // cw_dev_store_compact's entry checks, against the buffer of `bytes` bytes the entry points into
-    __device__ __forceinline__ bool sound(uint64_t bytes) const
-    {
-        const uint32_t len = word & kLenMask;
-        const bool raw = (word & kRawFlag) != 0;
-        return nonzero && (word & ~(kRawFlag | kLenMask)) == 0 && len != 0 && len <= kMaxChunkBytes && stored != 0 && (!raw || stored == len) &&
-               pos <= bytes && stored <= bytes - pos;
-    }
-    __device__ __forceinline__ uint4 at(uint64_t to) const { return make_uint4((uint32_t)to, (uint32_t)(to >> 32), stored, word); }
-};
+constexpr uint32_t kUnsound = 1u, kOutside = 2u, kLength = 4u; // the head's flag word
 
 // ---- export ------------------------------------------------------------------------------------------------------------------
 // sizes[k] = the stored bytes of the entry values[k] names, 0 and the flag when it names none or an unsound one
@@ -57,9 +40,9 @@ export_sizes_kernel(const uint4 *__restrict__ dir, uint64_t dir_base, uint64_t d
     const uint64_t n = umin64(*d_count, max_count), threads = (uint64_t)gridDim.x * kThreads;
     bool bad = false;
     for (uint64_t k = (uint64_t)blockIdx.x * kThreads + threadIdx.x; k < n; k += threads) {
-        const uint64_t idx = values[k] - dir_base; // a value below the base wraps out of range, CW_DEDUPE_MISS with it
+        uint64_t idx;
         uint32_t s = 0;
-        if (idx < dir_entries) {
+        if (names_entry(values[k], dir_base, dir_entries, idx)) {
             const Entry e(dir[idx]);
             if (e.sound(store_bytes)) s = e.stored;
         }
@@ -85,8 +68,8 @@ export_copy_kernel(const uint8_t *__restrict__ store, const uint4 *__restrict__ 
     const uint64_t n = umin64(*d_count, max_count);
     if (export_verdict(*flags, off[n], out_bytes)) return;
     for (uint64_t k = blockIdx.x; k < n; k += gridDim.x) {
-        const uint64_t idx = values[k] - dir_base;
-        if (idx >= dir_entries) continue; // (no flag: every position names a sound entry)
+        uint64_t idx;
+        if (!names_entry(values[k], dir_base, dir_entries, idx)) continue; // (no flag: every position names a sound entry)
         const Entry e(dir[idx]);
         const uint64_t to = off[k];
         lz::copy_g2g(out + to, store + e.pos, e.stored, threadIdx.x);
@@ -117,26 +100,7 @@ struct Selection {
     __device__ __forceinline__ uint64_t chunk(uint64_t j) const { return sel ? sel[j] : j; }
 };
 
-// directory entry of the chunk with value base + k (restore_kernels.hip's rule: neither sum may wrap), or, for the replace, with
-// value values[k]
-struct Directory {
-    uint4 *entries;
-    uint64_t base, dir_base, dir_entries;
-    const uint64_t *values; // NULL: the import
-    __device__ __forceinline__ bool index(uint64_t k, uint64_t &idx) const
-    {
-        const uint64_t v = values ? values[k] : base + k;
-        idx = v - dir_base;
-        return (values || v >= base) && v >= dir_base && idx < dir_entries;
-    }
-    // the replace keeps a chunk's length: an entry whose own length field is sound (1..65536) takes no other length
-    __device__ __forceinline__ bool keeps_length(uint64_t idx, uint32_t word) const
-    {
-        const uint32_t len = entries[idx].w & kLenMask;
-        return len == 0 || len > kMaxChunkBytes || len == (word & kLenMask);
-    }
-};
-
+// (Directory d: values == NULL is the import, chunk k carries base + k; else the replace, position k carries values[k])
 // sizes[j] = the stored bytes of position j's chunk, 0 and kUnsound when the bundle has no such chunk or its entry is unsound or
 // leaves in_bytes; kOutside when a sound position's value has no directory entry; kLength when the replace would change the length
 // of the entry it names
@@ -224,25 +188,12 @@ translate_refs_kernel(const uint64_t *ref, const uint64_t *__restrict__ d_count,
         out[j] = hit ? to[lo] : UINT64_MAX;
         missing += !hit;
     }
-    for (int off = 32; off > 0; off >>= 1) missing += __shfl_down(missing, off, 64);
-    if ((threadIdx.x & 63u) == 0) wsum[threadIdx.x >> 6] = missing;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    uint32_t all = 0;
-    for (uint32_t w = 0; w < kThreads / 64; w++) all += wsum[w];
-    if (all) __hip_atomic_fetch_add(n_missing, (unsigned long long)all, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t all = group_sum(missing, wsum);
+    if (threadIdx.x == 0 && all) __hip_atomic_fetch_add(n_missing, (unsigned long long)all, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // per stream: the flag word at [0], the scan's offsets (u64, max_count + 1) from byte 64, the sizes (u32) behind them
 StreamScratch<DeviceBuf> replicate_spaces;
-constexpr size_t kHead = 64;
-
-unsigned lane_grid(size_t n)
-{
-    const size_t grid = (n + kThreads - 1) / kThreads;
-    return (unsigned)(grid < 256 * 8 ? grid : 256 * 8);
-}
-unsigned wave_grid(size_t n) { return (unsigned)(n < 256 * 32 ? n : 256 * 32); }
 
 } // namespace
 
@@ -252,19 +203,17 @@ hipError_t store_export_launch(const uint8_t *store, size_t store_bytes, const v
 {
     auto &w = replicate_spaces.at(stream);
     LaunchLock sequence(w.launch); // flags, sizes and offsets are shared by the launches below
-    hipError_t e = w.reserve(kHead + (max_count + 1) * 8 + max_count * 4, (size_t)1 << 20);
+    ScanScratch s;
+    hipError_t e = scan_scratch(w, max_count, stream, s);
     if (e != hipSuccess) return e;
-    uint32_t *flags = w.as<uint32_t>();
-    uint64_t *off = reinterpret_cast<uint64_t *>(w.as<uint8_t>() + kHead);
-    uint32_t *sizes = reinterpret_cast<uint32_t *>(off + max_count + 1);
-    if ((e = hipMemsetAsync(flags, 0, kHead, stream)) != hipSuccess) return e;
+    uint32_t *flags = s.head_as<uint32_t>();
     const uint4 *entries = static_cast<const uint4 *>(dir);
     if (max_count)
         hipLaunchKernelGGL(export_sizes_kernel, dim3(lane_grid(max_count)), dim3(kThreads), 0, stream, entries, dir_base, (uint64_t)dir_entries,
-                           (uint64_t)store_bytes, values, d_count, (uint64_t)max_count, sizes, flags);
+                           (uint64_t)store_bytes, values, d_count, (uint64_t)max_count, s.sizes, flags);
     // off[k] = sum of sizes[0..k) for k <= n (max_count == 0: off[0] = 0)
-    if ((e = chunk_pack_launch(0, nullptr, nullptr, nullptr, d_count, max_count, sizes, nullptr, off, stream)) != hipSuccess) return e;
-    const unsigned long long *o = reinterpret_cast<const unsigned long long *>(off);
+    if ((e = chunk_pack_launch(0, nullptr, nullptr, nullptr, d_count, max_count, s.sizes, nullptr, s.off, stream)) != hipSuccess) return e;
+    const unsigned long long *o = s.offsets();
     if (max_count)
         hipLaunchKernelGGL(export_copy_kernel, dim3(wave_grid(max_count)), dim3(64), 0, stream, store, entries, dir_base, (uint64_t)dir_entries, values,
                            d_count, (uint64_t)max_count, o, flags, out, (uint64_t)out_bytes, static_cast<uint4 *>(out_loc));
@@ -280,19 +229,17 @@ hipError_t import_launch(const uint8_t *in, size_t in_bytes, const void *in_loc,
 {
     auto &w = replicate_spaces.at(stream);
     LaunchLock sequence(w.launch); // flags, sizes and offsets are shared by the launches below
-    hipError_t e = w.reserve(kHead + (max_count + 1) * 8 + max_count * 4, (size_t)1 << 20);
+    ScanScratch s;
+    hipError_t e = scan_scratch(w, max_count, stream, s);
     if (e != hipSuccess) return e;
-    uint32_t *flags = w.as<uint32_t>();
-    uint64_t *off = reinterpret_cast<uint64_t *>(w.as<uint8_t>() + kHead);
-    uint32_t *sizes = reinterpret_cast<uint32_t *>(off + max_count + 1);
-    if ((e = hipMemsetAsync(flags, 0, kHead, stream)) != hipSuccess) return e;
+    uint32_t *flags = s.head_as<uint32_t>();
     const uint4 *locs = static_cast<const uint4 *>(in_loc);
     const Selection c{d_count, sel, d_nsel, (uint64_t)max_count};
     const Directory d{static_cast<uint4 *>(dir), base, dir_base, (uint64_t)dir_entries, values};
     if (max_count)
-        hipLaunchKernelGGL(import_sizes_kernel, dim3(lane_grid(max_count)), dim3(kThreads), 0, stream, locs, (uint64_t)in_bytes, c, d, sizes, flags);
-    if ((e = chunk_pack_launch(0, nullptr, nullptr, nullptr, sel ? d_nsel : d_count, max_count, sizes, nullptr, off, stream)) != hipSuccess) return e;
-    const unsigned long long *o = reinterpret_cast<const unsigned long long *>(off);
+        hipLaunchKernelGGL(import_sizes_kernel, dim3(lane_grid(max_count)), dim3(kThreads), 0, stream, locs, (uint64_t)in_bytes, c, d, s.sizes, flags);
+    if ((e = chunk_pack_launch(0, nullptr, nullptr, nullptr, sel ? d_nsel : d_count, max_count, s.sizes, nullptr, s.off, stream)) != hipSuccess) return e;
+    const unsigned long long *o = s.offsets();
     if (max_count)
         hipLaunchKernelGGL(import_copy_kernel, dim3(wave_grid(max_count)), dim3(64), 0, stream, in, locs, c, d, o, flags, store, (uint64_t)store_bytes,
                            d_used);

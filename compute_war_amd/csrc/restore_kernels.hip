@@ -18,28 +18,14 @@
 #include "cw_device.h"
 #include "lane_codec.h"
 #include "lz_device.h"
-#include "stream_scratch.h"
+#include "store_device.h"
 
 namespace cw {
 
 namespace {
 
 using namespace lane;
-
-constexpr unsigned kThreads = 256;
-constexpr uint32_t kRawFlag = 0x80000000u, kLenMask = 0x1FFFFu; // cw_chunk_loc::raw (CW_CHUNK_RAW; bits 17..30 stay 0)
-
-// directory entry of the chunk with value base + i
-struct Directory {
-    uint4 *entries;
-    uint64_t base, dir_base, dir_entries;
-    __device__ __forceinline__ bool index(uint64_t i, uint64_t &idx) const
-    {
-        const uint64_t v = base + i;
-        idx = v - dir_base;
-        return v >= base && v >= dir_base && idx < dir_entries;
-    }
-};
+using namespace chunkstore;
 
 // ---- append ------------------------------------------------------------------------------------------------------------------
 // eff[j] = bytes position j occupies in the store (0: out of contract); *flags |= 1 if an in-contract chunk has no directory entry
@@ -55,7 +41,7 @@ store_sizes_kernel(ChunkList c, const uint32_t *__restrict__ sizes, Directory d,
         if (l) {
             const uint32_t s = sizes[j];
             e = s > 0 && s < l ? s : l;
-            outside |= !d.index(i, idx);
+            outside |= !d.index<false>(i, idx); // (the append has no list of values: chunk i carries base + i)
         }
         eff[j] = e;
     }
@@ -84,7 +70,7 @@ store_copy_kernel(const uint8_t *__restrict__ src, ChunkList c, const uint8_t *_
         if (e == 0) continue;
         uint64_t i, start, idx;
         const uint32_t l = c.chunk(j, count, i, start);
-        if (!d.index(i, idx)) continue; // (no flag: every in-contract chunk has an entry)
+        if (!d.index<false>(i, idx)) continue; // (no flag: every in-contract chunk has an entry)
         const bool raw = e == l;
         const uint64_t pos = used + off[j];
         lz::copy_g2g(store + pos, raw ? src + start : slots + chunk_slot_offset(lz4, start, i), e, lane);
@@ -122,35 +108,30 @@ restore_chunks_kernel(const uint8_t *__restrict__ store, uint64_t store_bytes, c
         uint64_t pos = 0, rs = 0;
         uint32_t stored = 0, len = 0;
         if (j < total) {
-            const uint64_t r = ref[j], re = raw_off[j + 1], idx = r - dir_base;
+            const uint64_t r = ref[j], re = raw_off[j + 1];
+            uint64_t idx;
+            const bool named = names_entry(r, dir_base, dir_entries, idx); // (in front of the condition: no branch of its own)
             rs = raw_off[j];
-            if (r >= dir_base && idx < dir_entries && rs <= re && re - rs <= kMaxChunkBytes && re <= dst_bytes) {
-                const uint4 e = dir[idx];
-                pos = (uint64_t)e.y << 32 | e.x;
-                stored = e.z;
-                len = e.w & kLenMask;
-                raw = (e.w & kRawFlag) != 0;
-                refuse = (e.w & ~(kRawFlag | kLenMask)) != 0 || len == 0 || len > kMaxChunkBytes || len != re - rs || stored == 0 ||
-                         (raw && stored != len) || pos > store_bytes || stored > store_bytes - pos;
+            // (r >= dir_base: a directory whose values wrap has no entry for a value below its base)
+            if (r >= dir_base && named && rs <= re && re - rs <= kMaxChunkBytes && re <= dst_bytes) {
+                const Entry e(dir[idx]);
+                pos = e.pos;
+                stored = e.stored;
+                len = e.len();
+                raw = e.raw();
+                refuse = !e.sound(store_bytes) || len != re - rs;
             }
         }
         // (cw_dev_decompress_chunks skips a compressed extent above 2^24 bytes with status 1: the same verdict here)
         const bool skip = refuse || raw || stored > (1u << 24);
         const bool bad = lane_decode<ALG>(store + (skip ? 0 : pos), skip ? 0u : stored, dst + (skip ? 0 : rs), skip ? 0u : len, skip);
         if (j < total) status[j] = refuse ? 2u : raw ? 0u : bad ? 1u : 0u;
-        unsigned long long copies = __ballot(!refuse && raw);
-        while (copies) {
-            const int k = __ffsll((long long)copies) - 1;
-            copies &= copies - 1;
-            const uint64_t from = __shfl((unsigned long long)pos, k, 64), to = __shfl((unsigned long long)rs, k, 64);
-            lz::copy_g2g(dst + to, store + from, (uint32_t)__shfl((int)len, k, 64), threadIdx.x);
-        }
+        wave_copy(!refuse && raw, store, pos, dst, rs, len);
     }
 }
 
 // per stream: the flags word at [0], the scan's offsets (u64, max_chunks + 1) from byte 64, the effective sizes (u32) behind them
 StreamScratch<DeviceBuf> store_spaces;
-constexpr size_t kStoreHead = 64;
 
 } // namespace
 
@@ -161,28 +142,21 @@ hipError_t chunk_store_launch(int lzf, const uint8_t *src, size_t src_bytes, con
 {
     auto &w = store_spaces.at(stream);
     LaunchLock sequence(w.launch); // flags, sizes and offsets are shared by the launches below
-    hipError_t e = w.reserve(kStoreHead + (max_chunks + 1) * 8 + max_chunks * 4, (size_t)1 << 20);
+    ScanScratch s;
+    hipError_t e = scan_scratch(w, max_chunks, stream, s);
     if (e != hipSuccess) return e;
-    uint32_t *flags = w.as<uint32_t>();
-    uint64_t *off = reinterpret_cast<uint64_t *>(w.as<uint8_t>() + kStoreHead);
-    uint32_t *eff = reinterpret_cast<uint32_t *>(off + max_chunks + 1);
-    if ((e = hipMemsetAsync(flags, 0, kStoreHead, stream)) != hipSuccess) return e;
+    uint32_t *flags = s.head_as<uint32_t>(), *eff = s.sizes;
     const ChunkList c{offsets, d_nchunks, sel, d_nsel, (uint64_t)max_chunks, (uint64_t)src_bytes};
-    const Directory d{static_cast<uint4 *>(dir), base, dir_base, (uint64_t)dir_entries};
-    if (max_chunks) {
-        size_t grid = (max_chunks + kThreads - 1) / kThreads;
-        if (grid > 256 * 8) grid = 256 * 8;
-        hipLaunchKernelGGL(store_sizes_kernel, dim3((unsigned)grid), dim3(kThreads), 0, stream, c, sizes, d, eff, flags);
-    }
+    const Directory d{static_cast<uint4 *>(dir), base, dir_base, (uint64_t)dir_entries, nullptr};
+    if (max_chunks)
+        hipLaunchKernelGGL(store_sizes_kernel, dim3(lane_grid(max_chunks)), dim3(kThreads), 0, stream, c, sizes, d, eff, flags);
     // off[j] = sum of eff[0..j) for j <= n, n = the number of positions (max_chunks == 0: off[0] = 0)
-    if ((e = chunk_pack_launch(lzf, nullptr, nullptr, nullptr, sel ? d_nsel : d_nchunks, max_chunks, eff, nullptr, off, stream)) != hipSuccess)
+    if ((e = chunk_pack_launch(lzf, nullptr, nullptr, nullptr, sel ? d_nsel : d_nchunks, max_chunks, eff, nullptr, s.off, stream)) != hipSuccess)
         return e;
-    const unsigned long long *o = reinterpret_cast<const unsigned long long *>(off);
-    if (max_chunks) {
-        const size_t grid = max_chunks < 256 * 32 ? max_chunks : 256 * 32;
-        hipLaunchKernelGGL(store_copy_kernel, dim3((unsigned)grid), dim3(64), 0, stream, src, c, slots, lzf == 0, eff, o, flags, d, store,
+    const unsigned long long *o = s.offsets();
+    if (max_chunks)
+        hipLaunchKernelGGL(store_copy_kernel, dim3(wave_grid(max_chunks)), dim3(64), 0, stream, src, c, slots, lzf == 0, eff, o, flags, d, store,
                            (uint64_t)store_bytes, d_used);
-    }
     hipLaunchKernelGGL(store_finish_kernel, dim3(1), dim3(64), 0, stream, c, o, flags, (uint64_t)store_bytes, d_used, result);
     return hipGetLastError();
 }
@@ -192,14 +166,13 @@ hipError_t chunk_restore_launch(int lzf, const uint8_t *store, size_t store_byte
                                 size_t dst_bytes, uint32_t *status, hipStream_t stream)
 {
     if (max_count == 0) return hipSuccess;
-    size_t grid = (max_count + 63) / 64;
-    if (grid > 256 * 8) grid = 256 * 8;
+    const unsigned grid = decode_grid(max_count);
     const uint4 *entries = static_cast<const uint4 *>(dir);
     if (lzf)
-        hipLaunchKernelGGL(restore_chunks_kernel<1>, dim3((unsigned)grid), dim3(64), 0, stream, store, (uint64_t)store_bytes, entries, dir_base,
+        hipLaunchKernelGGL(restore_chunks_kernel<1>, dim3(grid), dim3(64), 0, stream, store, (uint64_t)store_bytes, entries, dir_base,
                            (uint64_t)dir_entries, ref, raw_offsets, d_count, (uint64_t)max_count, dst, (uint64_t)dst_bytes, status);
     else
-        hipLaunchKernelGGL(restore_chunks_kernel<0>, dim3((unsigned)grid), dim3(64), 0, stream, store, (uint64_t)store_bytes, entries, dir_base,
+        hipLaunchKernelGGL(restore_chunks_kernel<0>, dim3(grid), dim3(64), 0, stream, store, (uint64_t)store_bytes, entries, dir_base,
                            (uint64_t)dir_entries, ref, raw_offsets, d_count, (uint64_t)max_count, dst, (uint64_t)dst_bytes, status);
     return hipGetLastError();
 }

@@ -4,7 +4,7 @@
 // of the index's table (dedupe_kernels.hip).  This file plans the window in front of them and merges the verdicts behind them.
 //
 // Plan: classify the entries [c, E), E = min(dir_entries, c + entry_cap): need[k] = the length of a selected entry that is sound by
-// cw_dev_store_compact's entry checks (it will be decoded), else 0, and verdict[k] = SKIPPED, UNSOUND or -- for an entry that will be
+// store_device.h's rule (it will be decoded), else 0, and verdict[k] = SKIPPED, UNSOUND or -- for an entry that will be
 // decoded -- ORPHAN, which the table sweep lowers.  The index-only pack scan over need gives raw_off; the window ends at the largest
 // e with raw_off[e - c] <= work_bytes (raw_off does not decrease, so exactly one lane finds it).  The window's recipe names the
 // entries that will be decoded by their own values and every other one by CW_DEDUPE_MISS, which the restore refuses without a load.
@@ -20,46 +20,19 @@
 #include <stdint.h>
 
 #include "cw_device.h"
-#include "stream_scratch.h"
+#include "store_device.h"
 
 namespace cw {
 
 namespace {
 
-constexpr unsigned kThreads = 256;
-constexpr uint32_t kRawFlag = 0x80000000u, kLenMask = 0x1FFFFu; // cw_chunk_loc::raw (CW_CHUNK_RAW; bits 17..30 stay 0)
-constexpr uint32_t kOk = 0, kMalformed = 1, kUnsound = 2, kMismatch = 3, kOrphan = 4, kSkipped = 5; // CW_SCRUB_*
+using namespace chunkstore;
 
-struct Entry {
-    uint64_t pos;
-    uint32_t stored, word;
-    bool nonzero;
-    __device__ __forceinline__ explicit Entry(const uint4 e) : pos((uint64_t)e.y << 32 | e.x), stored(e.z), word(e.w), nonzero((e.x | e.y | e.z | e.w) != 0) {}
-    // cw_dev_store_compact's entry checks (an all-zero entry fails them: its length is 0)
-    __device__ __forceinline__ bool sound(uint64_t store_bytes) const
-    {
-        const uint32_t len = word & kLenMask;
-        const bool raw = (word & kRawFlag) != 0;
-        return (word & ~(kRawFlag | kLenMask)) == 0 && len != 0 && len <= kMaxChunkBytes && stored != 0 && (!raw || stored == len) &&
-               pos <= store_bytes && stored <= store_bytes - pos;
-    }
-};
+constexpr uint32_t kOk = 0, kMalformed = 1, kUnsound = 2, kMismatch = 3, kOrphan = 4, kSkipped = 5; // CW_SCRUB_*
 
 struct ScrubHead { // the first 24 of the scratch's 64 head bytes
     unsigned long long c, n, m; // the cursor as the call found it, e - c, E - c
 };
-
-// the workgroup's sum of v in thread 0 (kThreads threads, every one of them calls)
-__device__ __forceinline__ uint32_t group_sum(uint32_t v, uint32_t *wsum)
-{
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if ((threadIdx.x & 63u) == 0) wsum[threadIdx.x >> 6] = v;
-    __syncthreads();
-    uint32_t all = 0;
-    for (uint32_t w = 0; w < kThreads / 64; w++) all += wsum[w];
-    __syncthreads(); // the next sum writes wsum again
-    return all;
-}
 
 // need and verdict of the entries [c, E); the head
 __global__ void __launch_bounds__(kThreads)
@@ -72,7 +45,7 @@ scrub_classify_kernel(const uint4 *__restrict__ dir, uint64_t dir_entries, uint6
         const uint64_t idx = c + k;
         const Entry e(dir[idx]);
         const bool selected = live ? live[idx] != 0 : e.nonzero, decode = selected && e.sound(store_bytes);
-        need[k] = decode ? e.word & kLenMask : 0u;
+        need[k] = decode ? e.len() : 0u;
         verdict[k] = !selected ? kSkipped : decode ? kOrphan : kUnsound;
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -131,14 +104,7 @@ scrub_finish_kernel(const ScrubHead *__restrict__ head, const unsigned long long
 
 // per stream: the layout of the header comment
 StreamScratch<DeviceBuf> scrub_spaces;
-constexpr size_t kHead = 64;
-static_assert(sizeof(ScrubHead) <= kHead, "the head holds the cursor and both counts");
-
-unsigned lane_grid(size_t n)
-{
-    const size_t grid = (n + kThreads - 1) / kThreads;
-    return (unsigned)(grid < 256 * 8 ? grid : 256 * 8);
-}
+static_assert(sizeof(ScrubHead) <= kScratchHead, "the head holds the cursor and both counts");
 
 } // namespace
 
@@ -149,7 +115,7 @@ size_t store_verify_window(size_t dir_entries, long knob)
     return cap < dir_entries ? cap : dir_entries;
 }
 
-size_t store_verify_scratch_bytes(size_t window, unsigned digest_bytes) { return kHead + 8 + (28 + (size_t)digest_bytes) * window; }
+size_t store_verify_scratch_bytes(size_t window, unsigned digest_bytes) { return kScratchHead + 8 + (28 + (size_t)digest_bytes) * window; }
 
 hipError_t store_verify_launch(int lzf, const uint8_t *store, size_t store_bytes, const void *dir, uint64_t dir_base, size_t dir_entries,
                                const uint32_t *live, uint64_t *d_cursor, uint8_t *work, size_t work_bytes, size_t window, unsigned digest_bytes,
@@ -160,7 +126,7 @@ hipError_t store_verify_launch(int lzf, const uint8_t *store, size_t store_bytes
     hipError_t e = w.reserve(store_verify_scratch_bytes(window, digest_bytes), (size_t)1 << 20);
     if (e != hipSuccess) return e;
     ScrubHead *head = w.as<ScrubHead>();
-    uint8_t *dig = w.as<uint8_t>() + kHead;
+    uint8_t *dig = w.as<uint8_t>() + kScratchHead;
     uint64_t *raw_off = reinterpret_cast<uint64_t *>(dig + (size_t)digest_bytes * window), *ref = raw_off + window + 1;
     uint32_t *need = reinterpret_cast<uint32_t *>(ref + window), *decoded = need + window, *verdict = decoded + window;
     const uint4 *entries = static_cast<const uint4 *>(dir);

@@ -18,27 +18,13 @@
 #include <stdint.h>
 
 #include "cw_device.h"
-#include "lz_device.h"
-#include "stream_scratch.h"
+#include "store_device.h"
 
 namespace cw {
 
 namespace {
 
-constexpr unsigned kThreads = 256;
-constexpr uint32_t kRawFlag = 0x80000000u, kLenMask = 0x1FFFFu; // cw_chunk_loc::raw (CW_CHUNK_RAW; bits 17..30 stay 0)
-
-// the workgroup's sum of v in thread 0 (kThreads threads, every one of them calls)
-__device__ __forceinline__ uint32_t group_sum(uint32_t v, uint32_t *wsum)
-{
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if ((threadIdx.x & 63u) == 0) wsum[threadIdx.x >> 6] = v;
-    __syncthreads();
-    uint32_t all = 0;
-    for (uint32_t w = 0; w < kThreads / 64; w++) all += wsum[w];
-    __syncthreads(); // the next sum writes wsum again
-    return all;
-}
+using namespace chunkstore;
 
 // ---- mark --------------------------------------------------------------------------------------------------------------------
 // live[ref[j] - dir_base] = 1 for every position j < min(*d_count, max_count) that names an entry; the others are counted
@@ -50,8 +36,8 @@ store_mark_kernel(const uint64_t *__restrict__ ref, const uint64_t *__restrict__
     const uint64_t n = umin64(*d_count, max_count), threads = (uint64_t)gridDim.x * kThreads;
     uint32_t outside = 0; // (a thread sees at most max_count / threads + 1 < 2^32 positions)
     for (uint64_t j = (uint64_t)blockIdx.x * kThreads + threadIdx.x; j < n; j += threads) {
-        const uint64_t idx = ref[j] - dir_base; // a value below the base wraps out of range
-        if (idx < dir_entries) live[idx] = 1u;  // racing stores of the same value
+        uint64_t idx;
+        if (names_entry(ref[j], dir_base, dir_entries, idx)) live[idx] = 1u; // racing stores of the same value
         else outside++;
     }
     const uint32_t all = group_sum(outside, wsum);
@@ -59,21 +45,6 @@ store_mark_kernel(const uint64_t *__restrict__ ref, const uint64_t *__restrict__
 }
 
 // ---- compact -----------------------------------------------------------------------------------------------------------------
-struct Entry {
-    uint64_t pos;
-    uint32_t stored, word;
-    bool nonzero;
-    __device__ __forceinline__ explicit Entry(const uint4 e) : pos((uint64_t)e.y << 32 | e.x), stored(e.z), word(e.w), nonzero((e.x | e.y | e.z | e.w) != 0) {}
-    // the entry checks of cw_dev_restore_chunks that need no recipe
-    __device__ __forceinline__ bool sound(uint64_t store_bytes) const
-    {
-        const uint32_t len = word & kLenMask;
-        const bool raw = (word & kRawFlag) != 0;
-        return (word & ~(kRawFlag | kLenMask)) == 0 && len != 0 && len <= kMaxChunkBytes && stored != 0 && (!raw || stored == len) &&
-               pos <= store_bytes && stored <= store_bytes - pos;
-    }
-};
-
 struct GcHead { // the first 24 of the scratch's 64 head bytes
     uint32_t unsound, pad;
     unsigned long long kept, dropped;
@@ -134,13 +105,7 @@ gc_copy_kernel(const uint8_t *__restrict__ store, uint64_t store_bytes, const ui
             word = e.word;
             to = off[idx];
         }
-        unsigned long long copies = __ballot(keep);
-        while (copies) {
-            const int k = __ffsll((long long)copies) - 1;
-            copies &= copies - 1;
-            const uint64_t f = __shfl((unsigned long long)from, k, 64), t = __shfl((unsigned long long)to, k, 64);
-            lz::copy_g2g(new_store + t, store + f, (uint32_t)__shfl((int)stored, k, 64), threadIdx.x);
-        }
+        wave_copy(keep, store, from, new_store, to, stored);
         if (idx < dir_entries) new_dir[idx] = keep ? make_uint4((uint32_t)to, (uint32_t)(to >> 32), stored, word) : make_uint4(0u, 0u, 0u, 0u);
     }
 }
@@ -162,8 +127,7 @@ gc_finish_kernel(const unsigned long long *__restrict__ off, uint64_t dir_entrie
 
 // per stream: the head at [0], the scan's offsets (u64, dir_entries + 1) from byte 64, the sizes (u32) behind them
 StreamScratch<DeviceBuf> gc_spaces;
-constexpr size_t kGcHead = 64;
-static_assert(sizeof(GcHead) <= kGcHead, "the head holds the flag and both counts");
+static_assert(sizeof(GcHead) <= kScratchHead, "the head holds the flag and both counts");
 
 } // namespace
 
@@ -171,9 +135,7 @@ hipError_t store_mark_launch(const uint64_t *ref, const uint64_t *d_count, size_
                              uint32_t *live, uint64_t *n_outside, hipStream_t stream)
 {
     if (max_count == 0) return hipSuccess;
-    size_t grid = (max_count + kThreads - 1) / kThreads;
-    if (grid > 256 * 8) grid = 256 * 8;
-    hipLaunchKernelGGL(store_mark_kernel, dim3((unsigned)grid), dim3(kThreads), 0, stream, ref, d_count, (uint64_t)max_count, dir_base,
+    hipLaunchKernelGGL(store_mark_kernel, dim3(lane_grid(max_count)), dim3(kThreads), 0, stream, ref, d_count, (uint64_t)max_count, dir_base,
                        (uint64_t)dir_entries, live, reinterpret_cast<unsigned long long *>(n_outside));
     return hipGetLastError();
 }
@@ -184,23 +146,18 @@ hipError_t store_compact_launch(const uint8_t *store, size_t store_bytes, const 
 {
     auto &w = gc_spaces.at(stream);
     LaunchLock sequence(w.launch); // head, sizes and offsets are shared by the launches below
-    hipError_t e = w.reserve(kGcHead + (dir_entries + 1) * 8 + dir_entries * 4, (size_t)1 << 20);
+    ScanScratch s;
+    hipError_t e = scan_scratch(w, dir_entries, stream, s);
     if (e != hipSuccess) return e;
-    GcHead *head = w.as<GcHead>();
-    uint64_t *off = reinterpret_cast<uint64_t *>(w.as<uint8_t>() + kGcHead);
-    uint32_t *sizes = reinterpret_cast<uint32_t *>(off + dir_entries + 1);
-    if ((e = hipMemsetAsync(head, 0, kGcHead, stream)) != hipSuccess) return e;
+    GcHead *head = s.head_as<GcHead>();
     const uint4 *entries = static_cast<const uint4 *>(dir);
-    size_t grid = (dir_entries + kThreads - 1) / kThreads;
-    if (grid > 256 * 8) grid = 256 * 8;
-    hipLaunchKernelGGL(gc_sizes_kernel, dim3((unsigned)grid), dim3(kThreads), 0, stream, entries, (uint64_t)dir_entries, live,
-                       (uint64_t)store_bytes, sizes, head);
+    hipLaunchKernelGGL(gc_sizes_kernel, dim3(lane_grid(dir_entries)), dim3(kThreads), 0, stream, entries, (uint64_t)dir_entries, live,
+                       (uint64_t)store_bytes, s.sizes, head);
     // off[idx] = sum of sizes[0..idx) for idx <= dir_entries
-    if ((e = pack_launch(nullptr, 0, sizes, dir_entries, nullptr, off, stream)) != hipSuccess) return e;
-    const unsigned long long *o = reinterpret_cast<const unsigned long long *>(off);
-    grid = (dir_entries + 63) / 64;
-    if (grid > 256 * 32) grid = 256 * 32;
-    hipLaunchKernelGGL(gc_copy_kernel, dim3((unsigned)grid), dim3(64), 0, stream, store, (uint64_t)store_bytes, entries, (uint64_t)dir_entries, live,
+    if ((e = pack_launch(nullptr, 0, s.sizes, dir_entries, nullptr, s.off, stream)) != hipSuccess) return e;
+    const unsigned long long *o = s.offsets();
+    // a wavefront per 64 entries
+    hipLaunchKernelGGL(gc_copy_kernel, dim3(wave_grid((dir_entries + 63) / 64)), dim3(64), 0, stream, store, (uint64_t)store_bytes, entries, (uint64_t)dir_entries, live,
                        o, head, new_store, (uint64_t)new_store_bytes, static_cast<uint4 *>(new_dir));
     hipLaunchKernelGGL(gc_finish_kernel, dim3(1), dim3(64), 0, stream, o, (uint64_t)dir_entries, head, (uint64_t)new_store_bytes, new_used,
                        result);
