@@ -590,6 +590,7 @@ int cw::host::dev_cdc_dedupe_compress(cw_dedupe_t *x, const cw_cdc_params *p, in
     return dedupe_on_stream(x, s, [&]() -> int {
         int rc = streams ? dev_cdc_streams(cp, src, nbytes, *streams, d_offsets, max_offsets, d_nchunks, s)
                          : dev_cdc(cp, src, nbytes, final_ ? 1 : 0, d_offsets, max_offsets, d_nchunks, s);
+        if (rc == CW_OK && hook && hook->after_cdc) rc = hook->after_cdc(hook->self, s);
         if (rc == CW_OK) rc = dev_hash_chunks(x->hash_alg, src, nbytes, d_offsets, d_nchunks, max_chunks, (uint8_t *)d_digests, s);
         if (rc != CW_OK) return rc;
         uint64_t *h_counts = hook ? hook->h_counts : x->h_ctrl;

@@ -147,6 +147,10 @@ struct CdcStreams { const uint64_t *ends; size_t nstreams; uint64_t *first, *res
 size_t cdc_streams_workspace_bytes(size_t nbytes, size_t nstreams, uint32_t min_size, uint64_t seg);
 hipError_t cdc_streams_launch(const CdcParams &p, const uint8_t *src, size_t nbytes, const CdcStreams &st, uint64_t *offsets, size_t max_offsets,
                               uint64_t *nchunks, uint64_t seg, hipStream_t stream);
+// the resync of an edit's window (patch_kernels.hip; semantics: the public header's cw_dev_cdc_resync)
+hipError_t cdc_resync_launch(const uint64_t *new_offsets, uint64_t *d_new_count, size_t max_new, const uint64_t *old_offsets,
+                             const uint64_t *d_old_count, size_t max_old, uint64_t new_from, uint64_t shift, int keep_all, uint64_t *result,
+                             hipStream_t stream);
 // orders the chunks i < min(*d_n, max_chunks) by (length >> step_shift), longest first, into a permutation in the stream's
 // workspace, and calls hash.fn(hash.ctx, perm) to queue the hash that reads it -- both under the workspace's launch lock
 struct ChunkHash { hipError_t (*fn)(void *ctx, const uint32_t *perm); void *ctx; };

@@ -130,6 +130,9 @@ struct PieceAdmit {
     int (*admit)(void *self, size_t k, const uint64_t *h_counts);
     void *self;
     bool *inserted; // set once the piece's chunks are queued for the index: a failure behind that point is no refusal
+    // cw_store_patch: called between the chunker and the hash, for what shortens *d_nchunks on the device (cw_dev_cdc_resync) and for
+    // the copies that ride on the piece's one synchronise; whatever it returns other than CW_OK ends the call there
+    int (*after_cdc)(void *self, hipStream_t s) = nullptr;
 };
 // cw_dev_cdc_dedupe_compress is this with hook == nullptr and streams == nullptr; cw_dev_cdc_streams_dedupe_compress gives `streams`
 // (the chunker is then cw_dev_cdc_streams_part with streams->final_, final_ is not read, and the verdict on d_ends comes back with the

@@ -1,7 +1,9 @@
 // cw_ingest.hip -- the chunk store's host-buffer calls (DESIGN.md sections 18 and 21; semantics: the public header): cw_store_ingest
 // streams a host buffer of any size through the device in pieces, cw_store_ingest_streams does the same over many host streams,
 // cw_store_restore streams a recipe back in windows, and cw_dev_ingest_commit / cw_dev_ingest_commit_streams are the device step that
-// assembles a recipe piece by piece (kernels: ingest_kernels.hip).
+// assembles a recipe piece by piece (kernels: ingest_kernels.hip).  cw_store_patch edits a stored stream in place (DESIGN.md section 25;
+// struct Patch, one piece of the same kind over a window rebuilt on the device), with cw_dev_cdc_resync as its device step (kernels:
+// patch_kernels.hip).
 //
 // Both ingests are one loop (struct Ingest) over a list of host spans; cw_store_ingest's one buffer is a single span.  With the stream
 // index (cw_store_ingest_streams) a piece is chunked by cw_dev_cdc_streams_part with the stream ends that fall into it and committed by
@@ -60,7 +62,8 @@ const size_t kWindowPositions = (size_t)1 << 24; // positions per restore window
 
 // u64 words of StoreCtx::words (device) and h_words (pinned)
 // (W_COUNTS: four on the device, five on the host, where the fifth takes W_ENDS, the verdict on a piece's stream ends)
-enum { W_NCHUNKS = 0, W_NNEW = 1, W_RESULT = 2, W_COUNTS = 4, W_VERDICT = 9, W_REC_COUNT = 10, W_ENDS = 11, W_STATS = 16, W_WORDS = 24 };
+// (W_RESYNC: cw_store_patch's four words of cw_dev_cdc_resync)
+enum { W_NCHUNKS = 0, W_NNEW = 1, W_RESULT = 2, W_COUNTS = 4, W_VERDICT = 9, W_REC_COUNT = 10, W_ENDS = 11, W_RESYNC = 12, W_STATS = 16, W_WORDS = 24 };
 
 // the bytes of a piece (ingest) or a window (restore, scrub): CW_STORE_PIECE or the default, and no less than `floor`
 size_t piece_bytes(size_t floor)
@@ -306,6 +309,173 @@ struct Ingest {
     }
 };
 
+// One edit of a stored stream (cw_store_patch).  An attempt is one piece of Ingest's kind -- the same fused call
+// with the same admission -- over a window rebuilt on the device instead of uploaded, with cw_dev_cdc_resync behind the chunker:
+//     stream   count | ranges | refs | rebased cuts -> meta[0] | read ranges into src[0] around the insert | insert -> src[0] + head
+//              | cdc, resync, hash, counts | SYNCHRONISE: statuses, verdict, admit | dedupe, codec, append | refs, cuts -> host
+// Everything is queued on the context's kernel stream.  meta[0], in u64 words: the count of uploaded positions, the range count (2),
+// the ranges' offsets, lengths and destinations, the refs of positions [j, e) and the cuts of [j, e] rebased to c_j.
+struct Patch {
+    enum { M_COUNT = 0, M_NRANGES = 1, M_ROFF = 2, M_RLEN = 4, M_RDST = 6, M_REFS = 8 };
+    cw_dedupe_t *x; const cw_cdc_params *p; int comp_alg; const cw_store *st;
+    const uint64_t *refs, *offsets; size_t K;
+    uint64_t a, remove; const uint8_t *insert; size_t ins; uint64_t base; size_t max_out;
+    StoreCtx *c = nullptr; hipStream_t s = nullptr;
+    size_t j = 0, e = 0, cap = 0;                    // the attempt: old positions [j, e) lie in the window; its max_offsets
+    uint64_t head = 0, tail = 0, wb = 0;             // the old bytes in front of and behind the insert, and the window's bytes
+    bool final_ = false, retry = false, unrestored = false;
+    size_t k = 0, resume = 0;                        // what the attempt keeps: k window chunks, then old positions [resume, K)
+
+    uint64_t cut(size_t i) const { return offsets[i] - offsets[0]; }
+    uint64_t *meta() const { return (uint64_t *)c->meta[0].p; }
+
+    // j and e for a lookahead: c_j <= a (the last chunk when a is the end), c_e = W >= b.  CW_ERR_BAD_ARG when [j, e] does not ascend
+    int locate(uint64_t look)
+    {
+        const uint64_t n = cut(K), b = a + remove;
+        size_t lo = 0, hi = K; // the last i in [0, K] with cut(i) <= a
+        while (lo < hi) {
+            const size_t mid = lo + (hi - lo + 1) / 2;
+            if (cut(mid) <= a) lo = mid;
+            else hi = mid - 1;
+        }
+        j = K && lo == K ? K - 1 : lo;
+        lo = j; hi = K; // the first i in [j, K] with cut(i) >= b + look, or K
+        if (look <= n - b)
+            while (lo < hi) {
+                const size_t mid = lo + (hi - lo) / 2;
+                if (cut(mid) >= b + look) hi = mid;
+                else lo = mid + 1;
+            }
+        e = hi;
+        for (size_t i = j; i < e; i++)
+            if (offsets[i + 1] < offsets[i]) return fail(CW_ERR_BAD_ARG, "offsets decrease at position %zu", i);
+        if (cut(j) > a || cut(e) < b || (K && e <= j)) return fail(CW_ERR_BAD_ARG, "offsets do not ascend around position %zu", j);
+        final_ = e == K;
+        head = a - cut(j); tail = cut(e) - b; wb = head + ins + tail;
+        return CW_OK;
+    }
+
+    static int after_cdc(void *self, hipStream_t s)
+    {
+        Patch &t = *static_cast<Patch *>(self);
+        uint64_t *w = (uint64_t *)t.c->words.p, *h = (uint64_t *)t.c->h_words.p, *m = t.meta();
+        const size_t np = t.e - t.j;
+        int rc = cw_dev_cdc_resync((uint64_t *)t.c->off.p, w + W_NCHUNKS, t.cap - 1, m + M_REFS + np, m + M_COUNT, np, t.head + t.ins,
+                                   t.remove - (uint64_t)t.ins, t.final_ ? 1 : 0, w + W_RESYNC, s);
+        if (rc != CW_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(h + W_RESYNC, w + W_RESYNC, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(t.c->h_status[0].p, t.c->status[0].p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        return CW_OK;
+    }
+
+    // behind the attempt's synchronise, before anything is inserted: the window was read, it ends (a resync, or the stream's end), the
+    // recipe fits, and the kept chunks are admitted as a piece of cw_store_ingest is
+    static int admit(void *self, size_t k, const uint64_t *hc)
+    {
+        Patch &t = *static_cast<Patch *>(self);
+        const uint64_t *r = (const uint64_t *)t.c->h_words.p + W_RESYNC;
+        const uint32_t *got = (const uint32_t *)t.c->h_status[0].p;
+        if (got[0] || got[1]) {
+            t.unrestored = true;
+            return fail(CW_ERR_BAD_ARG, "cw_store_patch: the window's old bytes were not read (statuses %u, %u)", got[0], got[1]);
+        }
+        if (r[0] && !t.final_) {
+            t.retry = true;
+            return k ? fail(CW_ERR_STATE, "cw_store_patch: %zu chunks kept without a resync", k) : CW_OK;
+        }
+        if (!r[0] && (r[1] != k || r[2] > t.e - t.j)) return fail(CW_ERR_STATE, "cw_store_patch: resync at %llu, %zu chunks kept", (unsigned long long)r[1], k);
+        t.k = k;
+        t.resume = r[0] ? t.K : t.j + (size_t)r[2];
+        if (t.j + k + (t.K - t.resume) + 1 > t.max_out) return fail(CW_ERR_STATE, "cw_store_patch: %zu chunks do not fit max_out %zu", t.j + k + (t.K - t.resume), t.max_out);
+        Admission adm{t.st, t.base};
+        return admit_piece(&adm, k, hc);
+    }
+
+    // the first position of the window that does not restore, for the message: the window's positions once more, whole
+    int diagnose()
+    {
+        const size_t np = e - j;
+        const uint64_t bytes = cut(e) - cut(j);
+        uint64_t *m = meta();
+        if (c->src[1].reserve(bytes + 16) == CW_OK && c->status[1].reserve(np * 4) == CW_OK && c->h_status[1].reserve(np * 4) == CW_OK &&
+            cw_dev_restore_chunks(comp_alg, st->d_store, st->store_bytes, st->d_dir, st->dir_base, st->dir_entries, m + M_REFS, m + M_REFS + np,
+                                  m + M_COUNT, np, c->src[1].p, bytes, (uint32_t *)c->status[1].p, s) == CW_OK &&
+            hipMemcpyAsync(c->h_status[1].p, c->status[1].p, np * 4, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess) {
+            const uint32_t *got = (const uint32_t *)c->h_status[1].p;
+            for (size_t i = 0; i < np; i++)
+                if (got[i] && (cut(j + i) < a || cut(j + i + 1) > a + remove))
+                    return fail(CW_ERR_BAD_ARG, "cw_store_patch: position %zu (ref %llu) does not restore: status %u", j + i,
+                                (unsigned long long)refs[j + i], got[i]);
+        }
+        const uint32_t *got = (const uint32_t *)c->h_status[0].p;
+        return fail(CW_ERR_BAD_ARG, "cw_store_patch: a position in [%zu, %zu) does not restore (which one could not be determined): statuses %u, %u of "
+                                    "the bytes in front of and behind the edit", j, e, got[0], got[1]);
+    }
+
+    // one attempt: CW_OK with retry set = no resync in a window that is not final, nothing changed
+    int attempt(const cw::CdcParams &cp, uint64_t *out_refs, uint64_t *out_offsets, cw_patch_stats *stats)
+    {
+        const size_t np = e - j;
+        int rc;
+        if (wb / cp.min_size > SIZE_MAX - 2) return fail(CW_ERR_NOMEM, "cw_store_patch: a window of %llu bytes", (unsigned long long)wb);
+        cap = (size_t)(wb / cp.min_size) + 2;
+        if (check_count("window chunks", cap) != CW_OK || check_count("window positions", np) != CW_OK)
+            return fail(CW_ERR_NOMEM, "cw_store_patch: a window of %llu bytes and %zu positions", (unsigned long long)wb, np);
+        const size_t slots_bytes = cw_chunk_slots_bytes(comp_alg, wb, cap - 1), meta_words = M_REFS + 2 * np + 1;
+        if ((rc = c->src[0].reserve(wb + 16)) != CW_OK || (rc = c->off.reserve(cap * 8)) != CW_OK || (rc = c->dig.reserve(cap * 64)) != CW_OK ||
+            (rc = c->ref.reserve(cap * 8)) != CW_OK || (rc = c->new_idx.reserve(cap * 4)) != CW_OK || (rc = c->sizes.reserve(cap * 4)) != CW_OK ||
+            (rc = c->slots.reserve(slots_bytes)) != CW_OK || (rc = c->meta[0].reserve(meta_words * 8)) != CW_OK ||
+            (rc = c->h_meta[0].reserve(meta_words * 8)) != CW_OK || (rc = c->h_meta[1].reserve(2 * cap * 8)) != CW_OK || (rc = c->status[0].reserve(8)) != CW_OK || (rc = c->h_status[0].reserve(8)) != CW_OK ||
+            (rc = c->words.reserve(W_WORDS * 8)) != CW_OK || (rc = c->h_words.reserve(W_WORDS * 8)) != CW_OK)
+            return rc;
+        uint64_t *w = (uint64_t *)c->words.p, *h = (uint64_t *)c->h_words.p, *m = (uint64_t *)c->h_meta[0].p, *d_m = meta();
+        uint8_t *window = (uint8_t *)c->src[0].p;
+        const uint64_t cj = cut(j);
+        m[M_COUNT] = np; m[M_NRANGES] = 2;
+        m[M_ROFF] = 0; m[M_RLEN] = head; m[M_RDST] = 0;
+        m[M_ROFF + 1] = a + remove - cj; m[M_RLEN + 1] = tail; m[M_RDST + 1] = head + ins;
+        if (np) memcpy(m + M_REFS, refs + j, np * 8);
+        for (size_t i = 0; i <= np; i++) m[M_REFS + np + i] = cut(j + i) - cj;
+        HIP_TRY(hipMemsetAsync(w, 0, W_WORDS * 8, s));
+        HIP_TRY(hipMemsetAsync(c->status[0].p, 0, 8, s));
+        HIP_TRY(hipMemcpyAsync(d_m, m, meta_words * 8, hipMemcpyHostToDevice, s));
+        if (np && (head || tail) &&
+            (rc = cw_dev_read_ranges(comp_alg, st->d_store, st->store_bytes, st->d_dir, st->dir_base, st->dir_entries, d_m + M_REFS, d_m + M_REFS + np,
+                                     d_m + M_COUNT, np, d_m + M_ROFF, d_m + M_RLEN, d_m + M_RDST, d_m + M_NRANGES, 2, window, wb,
+                                     (uint32_t *)c->status[0].p, s)) != CW_OK)
+            return rc;
+        if (ins) HIP_TRY(hipMemcpyAsync(window + head, insert, ins, hipMemcpyHostToDevice, s));
+        bool inserted = false;
+        retry = unrestored = false;
+        PieceAdmit hook{st->d_used, w + W_VERDICT, w + W_COUNTS, h + W_COUNTS, admit, this, &inserted, after_cdc};
+        size_t found = 0;
+        rc = dev_cdc_dedupe_compress(x, p, comp_alg, window, wb, final_ ? 1 : 0, base, (uint64_t *)c->off.p, cap, w + W_NCHUNKS, c->dig.p,
+                                     (uint64_t *)c->ref.p, (uint32_t *)c->new_idx.p, w + W_NNEW, c->slots.p, slots_bytes, (uint32_t *)c->sizes.p, &found,
+                                     s, &hook);
+        if (unrestored) return diagnose();
+        if (rc == CW_ERR_NOMEM && inserted) return fail(CW_ERR_STATE, "cw_store_patch: device memory ran out behind an admitted window");
+        if (rc != CW_OK || retry) return rc;
+        rc = cw_dev_store_chunks(comp_alg, window, wb, (uint64_t *)c->off.p, w + W_NCHUNKS, cap - 1, (uint32_t *)c->new_idx.p, w + W_NNEW, c->slots.p,
+                                 (uint32_t *)c->sizes.p, base, st->d_store, st->store_bytes, st->d_used, st->d_dir, st->dir_base, st->dir_entries,
+                                 w + W_RESULT, s);
+        if (rc != CW_OK) return rc == CW_ERR_NOMEM ? fail(CW_ERR_STATE, "cw_store_patch: no scratch behind an admitted window") : rc;
+        // the kept refs and cuts come down on the same stream into pinned memory (k <= cap - 1 is known since the admission): one more
+        // synchronise, and no copy on the null stream, which would wait for every other thread's stream
+        uint64_t *h_ref = (uint64_t *)c->h_meta[1].p, *h_off = h_ref + cap;
+        HIP_TRY(hipMemcpyAsync(h + W_NNEW, w + W_NNEW, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, s)); // (W_NNEW, W_RESULT[2])
+        if (k) HIP_TRY(hipMemcpyAsync(h_ref, c->ref.p, k * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(h_off, c->off.p, (k + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (h[W_RESULT]) return fail(CW_ERR_STATE, "cw_store_patch: an admitted window was not stored (verdict %llu)", (unsigned long long)h[W_RESULT]);
+        // the splice: old positions [0, j), the window's k chunks, old positions [resume, K) shifted by delta
+        if (k) memcpy(out_refs + j, h_ref, k * 8);
+        for (size_t i = 0; i <= k; i++) out_offsets[j + i] = h_off[i] + cj;
+        stats->window_bytes = wb; stats->window_chunks = k; stats->new_chunks = h[W_NNEW]; stats->stored_bytes = h[W_RESULT + 1];
+        return CW_OK;
+    }
+};
+
 } // namespace
 
 extern "C" {
@@ -515,6 +685,86 @@ int cw_store_restore(int comp_alg, const cw_store *st, const uint64_t *refs, con
     (void)hipStreamSynchronize(s_d2h);
     if (rc == CW_OK) *n_bad = bad;
     return rc;
+}
+
+int cw_dev_cdc_resync(const uint64_t *d_new_offsets, uint64_t *d_new_count, size_t max_new, const uint64_t *d_old_offsets,
+                      const uint64_t *d_old_count, size_t max_old, uint64_t new_from, uint64_t shift, int keep_all, uint64_t *d_result, void *stream)
+{
+    int rc = check_count("max_new", max_new);
+    if (rc != CW_OK || (rc = check_count("max_old", max_old)) != CW_OK) return rc;
+    if (!d_new_offsets) return fail(CW_ERR_BAD_ARG, "NULL d_new_offsets");
+    if (!d_new_count) return fail(CW_ERR_BAD_ARG, "NULL d_new_count");
+    if (!d_old_offsets) return fail(CW_ERR_BAD_ARG, "NULL d_old_offsets");
+    if (!d_old_count) return fail(CW_ERR_BAD_ARG, "NULL d_old_count");
+    if (!d_result) return fail(CW_ERR_BAD_ARG, "NULL d_result");
+    if (((uintptr_t)d_new_offsets | (uintptr_t)d_new_count | (uintptr_t)d_old_offsets | (uintptr_t)d_old_count | (uintptr_t)d_result) & 7)
+        return fail(CW_ERR_BAD_ARG, "a pointer is not 8-byte aligned");
+    if (keep_all != 0 && keep_all != 1) return fail(CW_ERR_BAD_ARG, "keep_all is %d, not 0 or 1", keep_all);
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    return launched_nomem(cw::cdc_resync_launch(d_new_offsets, d_new_count, max_new, d_old_offsets, d_old_count, max_old, new_from, shift, keep_all,
+                                                d_result, (hipStream_t)stream),
+                          "cdc resync launch");
+}
+
+int cw_store_patch(cw_dedupe_t *x, const cw_cdc_params *p, int comp_alg, const cw_store *st, const uint64_t *refs, const uint64_t *offsets,
+                   size_t nchunks, uint64_t edit_off, uint64_t remove_bytes, const void *insert, size_t insert_bytes, uint64_t base, size_t lookahead,
+                   uint64_t *out_refs, uint64_t *out_offsets, size_t max_out, size_t *out_nchunks, cw_patch_stats *stats)
+{
+    if (out_nchunks) *out_nchunks = 0;
+    cw_patch_stats local;
+    if (!stats) stats = &local;
+    memset(stats, 0, sizeof *stats);
+    cw::CdcParams cp;
+    int rc = cdc_params(p, &cp);
+    if (rc != CW_OK || (rc = check_codec(comp_alg)) != CW_OK) return rc;
+    if (!x) return fail(CW_ERR_BAD_ARG, "NULL dedupe index");
+    if (!offsets || (nchunks && !refs)) return fail(CW_ERR_BAD_ARG, "NULL recipe (refs / offsets)");
+    if (!out_refs || !out_offsets || !out_nchunks) return fail(CW_ERR_BAD_ARG, "NULL out_refs / out_offsets / out_nchunks");
+    if (insert_bytes && !insert) return fail(CW_ERR_BAD_ARG, "NULL insert with insert_bytes %zu", insert_bytes);
+    if (cp.max_size > CW_MAX_BLOCK_BYTES) return fail(CW_ERR_BAD_ARG, "max_size %u > %u: such a chunk cannot be stored", cp.max_size, CW_MAX_BLOCK_BYTES);
+    if (offsets[nchunks] < offsets[0]) return fail(CW_ERR_BAD_ARG, "offsets end below their start");
+    const uint64_t n = offsets[nchunks] - offsets[0];
+    if (edit_off > n || remove_bytes > n - edit_off)
+        return fail(CW_ERR_BAD_ARG, "edit_off %llu + remove_bytes %llu leaves the stream's %llu bytes", (unsigned long long)edit_off,
+                    (unsigned long long)remove_bytes, (unsigned long long)n);
+    if (insert_bytes > UINT64_MAX - (n - remove_bytes)) return fail(CW_ERR_BAD_ARG, "insert_bytes %zu: the edited stream's length wraps", insert_bytes);
+    const uint64_t edited = n - remove_bytes + insert_bytes;
+    if (max_out < edited / cp.min_size + 2)
+        return fail(CW_ERR_BAD_ARG, "max_out %zu < edited bytes / min_size + 2 = %llu", max_out, (unsigned long long)(edited / cp.min_size + 2));
+    if ((rc = check_store(st)) != CW_OK) return rc;
+    if (base > UINT64_MAX - (edited / cp.min_size + 1)) return fail(CW_ERR_BAD_ARG, "base + edited bytes / min_size + 1 wraps");
+    Patch t{x, p, comp_alg, st, refs, offsets, nchunks, edit_off, remove_bytes, (const uint8_t *)insert, insert_bytes, base, max_out};
+    uint64_t look = lookahead ? lookahead : (uint64_t)4 * cp.max_size;
+    if (look < (uint64_t)2 * cp.max_size) look = (uint64_t)2 * cp.max_size;
+    if ((rc = t.locate(look)) != CW_OK) return rc;
+    hipStream_t s_h2d, s_d2h;
+    if ((rc = ctx_store(&t.c, &t.s, &s_h2d, &s_d2h)) != CW_OK) return rc;
+
+    for (;;) {
+        stats->attempts++;
+        if (t.wb == 0) { // the stream ends at c_j and nothing is put behind it: no window, no device
+            t.k = 0; t.resume = t.K; t.retry = false;
+            out_offsets[t.j] = t.cut(t.j);
+        } else {
+            rc = t.attempt(cp, out_refs, out_offsets, stats);
+            if (rc != CW_OK) (void)hipStreamSynchronize(t.s); // nothing of the call is in flight when it returns
+            if (rc != CW_OK) return rc;
+        }
+        if (!t.retry) break;
+        look = look > UINT64_MAX / 2 ? UINT64_MAX : look * 2;
+        if ((rc = t.locate(look)) != CW_OK) return rc;
+    }
+    const int64_t delta = (int64_t)(insert_bytes - remove_bytes);
+    if (t.j) memcpy(out_refs, refs, t.j * 8);
+    for (size_t i = 0; i < t.j; i++) out_offsets[i] = t.cut(i);
+    const size_t at = t.j + t.k, rest = nchunks - t.resume;
+    if (out_offsets[at] != (t.resume == nchunks ? edited : t.cut(t.resume) + (uint64_t)delta))
+        return fail(CW_ERR_STATE, "cw_store_patch: the window ends at %llu, not where old position %zu begins", (unsigned long long)out_offsets[at], t.resume);
+    if (rest) memcpy(out_refs + at, refs + t.resume, rest * 8);
+    for (size_t i = 1; i <= rest; i++) out_offsets[at + i] = t.cut(t.resume + i) + (uint64_t)delta;
+    *out_nchunks = at + rest;
+    stats->first_position = t.j; stats->resume_position = t.resume; stats->reused_positions = t.j + rest;
+    return CW_OK;
 }
 
 // The whole directory through cw_dev_store_verify, window by window: the work buffer is the context's first

@@ -852,6 +852,48 @@ def store_ingest(index: "DedupeIndex", params: "CdcParams", comp_alg, store: Sto
     return rc, refs[:k].copy(), offs[:k + 1].copy(), int(consumed.value), stats.as_dict()
 
 
+def dev_cdc_resync(d_new_offsets: int, d_new_count: int, max_new: int, d_old_offsets: int, d_old_count: int, max_old: int, new_from: int,
+                   shift: int, keep_all: bool, d_result: int, stream: int = 0) -> None:
+    """The device step of an edit: the smallest t in [1, N] with new[t] >= new_from and new[t] + shift (mod 2^64) an old cut old[s];
+    d_result[0..4) = (0, t, s, new[t]) and *d_new_count = t, or (1, 0, 0, 0) with *d_new_count kept (keep_all) or zeroed.  Both
+    counts are read on the device (N = min(*d_new_count, max_new), O = min(*d_old_count, max_old)).  Not synchronised."""
+    check(lib().cw_dev_cdc_resync(d_new_offsets, d_new_count, max_new, d_old_offsets, d_old_count, max_old, new_from % (1 << 64),
+                                  shift % (1 << 64), 1 if keep_all else 0, d_result, stream))
+
+
+class PatchStats(C.Structure):
+    """cw_patch_stats: one store_patch call's last window (bytes, kept chunks, new chunks, stored bytes), its attempts, and the old
+    positions around the window: the first re-chunked one, the one the new recipe resumes at, and how many were reused."""
+    _fields_ = [(k, C.c_uint64) for k in ("window_bytes", "window_chunks", "new_chunks", "stored_bytes", "attempts", "first_position",
+                                          "resume_position", "reused_positions")]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+PATCH_DTYPE = np.dtype([(k, "<u8") for k, _ in PatchStats._fields_])  # cw_patch_stats as a numpy record
+
+
+def store_patch(index: "DedupeIndex", params: "CdcParams", comp_alg, store: Store, refs, offsets, edit_off: int, remove_bytes: int, insert,
+                base: int, lookahead: int = 0):
+    """cw_store_patch: bytes [edit_off, edit_off + remove_bytes) of the stream of the recipe (refs, offsets) replaced by ``insert``.
+    Returns (refs, offsets, stats as a dict) of the edited stream, offsets starting at 0; raises CwError (-5: not admitted, -2: a
+    refused argument or a position that does not restore) with index, store and directory unchanged."""
+    refs, offsets = np.ascontiguousarray(refs, np.uint64), np.ascontiguousarray(offsets, np.uint64)
+    if len(offsets) != len(refs) + 1:
+        raise ValueError(f"{len(refs)} refs need {len(refs) + 1} offsets, not {len(offsets)}")
+    ins = _np_u8(insert)
+    edited = int(offsets[-1] - offsets[0]) - remove_bytes + ins.size
+    cap = params.max_offsets(max(edited, 0))
+    out_refs, out_offs = np.zeros(cap, np.uint64), np.zeros(cap, np.uint64)
+    k, stats = C.c_size_t(0), PatchStats()
+    check(lib().cw_store_patch(index._x(), C.byref(params), _comp_id(comp_alg), C.byref(store), refs.ctypes.data if len(refs) else None,
+                               offsets.ctypes.data, len(refs), edit_off, remove_bytes, ins.ctypes.data if ins.size else None, ins.size, base,
+                               lookahead, out_refs.ctypes.data, out_offs.ctypes.data, cap, C.byref(k), C.byref(stats)))
+    k = int(k.value)
+    return out_refs[:k].copy(), out_offs[:k + 1].copy(), stats.as_dict()
+
+
 def store_restore(comp_alg, store: Store, refs, offsets, dst: int, dst_bytes: int):
     """cw_store_restore into the host memory at address ``dst``: the status of every position (u32 array)."""
     refs, offsets = np.ascontiguousarray(refs, np.uint64), np.ascontiguousarray(offsets, np.uint64)

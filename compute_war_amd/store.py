@@ -13,7 +13,7 @@ from ._lib import CwError, lib
 from .ops import (ACCOUNT_DTYPE, CdcParams, ChunkLoc, DedupeIndex, Store, _comp_id, _hash_id, _np_u8, chunk_slots_bytes, dev_hash_chunks,
                   dev_read_ranges, dev_restore_chunks, dev_store_account, dev_store_chunks, dev_store_compact, dev_store_export_chunks, dev_store_import_chunks, dev_store_mark,
                   dev_store_renumber, dev_store_replace_chunks, dev_translate_refs, device_count, digest_bytes, init, store_ingest,
-                  store_ingest_streams, store_restore, store_scrub)
+                  store_ingest_streams, store_patch, store_restore, store_scrub)
 
 
 class Recipe:
@@ -183,8 +183,10 @@ class ChunkStore:
     ``ingest`` is one device call: the whole buffer has to fit on the device next to its slots.  ``ingest_stream`` and
     ``restore_stream`` take and give host buffers of any size, streamed through the device in pieces (cw_store_ingest /
     cw_store_restore), ``ingest_many_stream`` and ``restore_many_stream`` many of them in one pipelined run; ``last_stats`` holds the
-    last streamed ingest's statistics."""
+    last streamed ingest's statistics.  ``patch`` edits a stored stream in place -- ``write``, ``append``, ``truncate`` and
+    ``patch_many`` are thin forms of it -- and ``last_patch`` holds the last edit's statistics (cw_patch_stats as a dict)."""
     last_stats = None
+    last_patch = None
 
     def __init__(self, index: DedupeIndex, comp_alg, params: CdcParams, store_bytes: int, dir_entries: int, dir_base: int = 0):
         import torch
@@ -402,6 +404,55 @@ class ChunkStore:
     def read(self, recipe: Recipe, offset: int, length: int) -> bytes:
         """Bytes [offset, offset + length) of an ingested stream: ``read_ranges`` with one range."""
         return self.read_ranges(recipe, [(offset, length)])[0]
+
+    def patch(self, recipe: Recipe, offset: int, remove: int, data, lookahead: int = 0) -> Recipe:
+        """The recipe of the stream with bytes [offset, offset + remove) replaced by ``data`` (cw_store_patch):
+        only the chunks around the edit are rebuilt, re-chunked and stored, yet recipe, store and index are exactly what ingesting
+        the whole edited stream leaves.  ``recipe`` stays valid: the store only appends, and the two versions share their chunks.
+        ``base`` advances by the window's chunks and ``last_patch`` holds the call's statistics.  ``lookahead`` (0 = 4 * max_size)
+        is how far behind the edit the first window reaches; it doubles until the cuts resynchronise.  Raises CwError (-5) when the
+        index, the directory, the store or the device's memory cannot take the window, and CwError (-2) when a position of the
+        window does not restore or the edit leaves the stream; store, index and ``base`` are then unchanged."""
+        if device_count() <= 0:
+            init()  # (raises: no device)
+        import torch
+        offset, remove = int(offset), int(remove)
+        if offset < 0 or remove < 0:
+            raise ValueError("offset and remove are not negative")
+        torch.cuda.synchronize()  # (the store was written on torch's stream)
+        refs, offs, stats = store_patch(self.index, self.params, self.comp_alg, self._triple(), recipe.refs, recipe.offsets, offset, remove, data,
+                                        self.base, lookahead)
+        self.base += stats["window_chunks"]
+        self.last_patch = stats
+        return Recipe(refs, offs)
+
+    def write(self, recipe: Recipe, offset: int, data) -> Recipe:
+        """Overwrite: ``data`` replaces as many bytes from ``offset`` on as the stream has, so a write past the end extends it."""
+        n = len(_np_u8(data))
+        return self.patch(recipe, offset, max(min(n, recipe.nbytes - int(offset)), 0), data)
+
+    def append(self, recipe: Recipe, data) -> Recipe:
+        """``data`` behind the stream's last byte."""
+        return self.patch(recipe, recipe.nbytes, 0, data)
+
+    def truncate(self, recipe: Recipe, nbytes: int) -> Recipe:
+        """The first ``nbytes`` bytes of the stream (no more than it has)."""
+        nbytes = min(int(nbytes), recipe.nbytes)
+        return self.patch(recipe, nbytes, recipe.nbytes - nbytes, b"")
+
+    def patch_many(self, recipe: Recipe, edits) -> Recipe:
+        """``patch`` for several edits ``(offset, remove, data)``, all in the coordinates of the stream as it is now: they must not
+        overlap or share an offset with an insert (ValueError, before any of them runs) and are applied from the highest offset
+        down, one ``patch`` each.  ``last_patch`` is the last applied edit's, the one with the lowest offset."""
+        edits = sorted(((int(o), int(r), d) for o, r, d in edits), key=lambda e: (e[0], e[1]))
+        for (o, r, _), (o2, _, _) in zip(edits, edits[1:]):
+            if o + r > o2 or (o == o2 and r == 0):
+                raise ValueError(f"edits overlap: ({o}, {r}) and the one at {o2}")
+        if any(o < 0 or r < 0 or o + r > recipe.nbytes for o, r, _ in edits):
+            raise ValueError(f"an edit leaves the stream's {recipe.nbytes} bytes")
+        for o, r, d in reversed(edits):
+            recipe = self.patch(recipe, o, r, d)
+        return recipe
 
     def _mark(self, recipes, s: int):
         """(live: a u32 flag per directory entry; n_outside: the positions that name none) after ``dev_store_mark`` of every recipe."""

@@ -666,6 +666,64 @@ int cw_store_ingest_streams(cw_dedupe_t *x, const cw_cdc_params *p, int comp_alg
 int cw_store_restore(int comp_alg, const cw_store *st, const uint64_t *refs, const uint64_t *offsets, size_t nchunks,
                      void *dst, size_t dst_bytes, uint32_t *status /* [nchunks], may be NULL */, size_t *n_bad);
 
+/* ---- the chunk store edits a stream in place: patch, append, truncate -----------------------------------
+ * The device step of an edit: which of the cuts of a re-chunked window lands on a cut of the old stream.  Both counts are read on the
+ * device: N = min(*d_new_count, max_new), O = min(*d_old_count, max_old); d_new_offsets[0 .. N] and d_old_offsets[0 .. O] are cuts as
+ * cw_dev_cdc writes them, the old ones ascending.  The call finds the smallest t in [1, N] with d_new_offsets[t] >= new_from and
+ * d_new_offsets[t] + shift (mod 2^64) == d_old_offsets[s] for some s in [0, O] (the lowest such s), and writes
+ * d_result[0 .. 4) = {verdict, t, s, d_new_offsets[t]}: verdict 0 = found, and *d_new_count becomes t; verdict 1 = not found,
+ * d_result[1 .. 4) = 0, and *d_new_count stays as it is when keep_all is set and becomes 0 otherwise.  Index 0 of the new cuts never
+ * matches.  Every call queued behind this one on `stream` reads its count on the device: cw_dev_hash_chunks, the dedupe and
+ * cw_dev_compress_chunks then work on exactly the kept chunks and cw_dev_store_chunks stores exactly their new ones; with none kept each
+ * is a no-op, without a host round trip.  No load leaves d_new_offsets[0 .. max_new] or d_old_offsets[0 .. max_old]; nothing else is
+ * written.  Scratch, per stream: 64 bytes.  Not synchronised.
+ * CW_ERR_BAD_ARG before the device is touched: a NULL pointer, a pointer that is not 8-byte aligned, max_new or max_old > 2^32 - 256,
+ * a keep_all other than 0 and 1.                                                                                                    */
+int cw_dev_cdc_resync(const uint64_t *d_new_offsets, uint64_t *d_new_count /* in, out */, size_t max_new,
+                      const uint64_t *d_old_offsets, const uint64_t *d_old_count, size_t max_old,
+                      uint64_t new_from, uint64_t shift, int keep_all, uint64_t *d_result /* [4] */, void *stream);
+typedef struct cw_patch_stats {   /* of one cw_store_patch call; the window is the last attempt's */
+    uint64_t window_bytes, window_chunks, new_chunks, stored_bytes, attempts, first_position, resume_position, reused_positions;
+} cw_patch_stats;
+/* Replaces bytes [edit_off, edit_off + remove_bytes) of a stored stream by insert[0 .. insert_bytes) and gives the edited stream's
+ * recipe, without restoring or re-ingesting the stream.  Synchronous; host pointers except inside *st.  The old recipe is refs[nchunks]
+ * and offsets[nchunks + 1]; coordinates are zero-based: the stream is offsets[nchunks] - offsets[0] bytes long and the new offsets
+ * start at 0.  out_refs / out_offsets must not overlap refs / offsets.
+ *   result        *out_nchunks, out_refs, out_offsets, the store bytes [0, *d_used), the directory and the index are exactly what
+ *                 cw_store_ingest of the whole edited stream with the same base leaves, given that the index still holds every chunk of
+ *                 the old recipe: the cuts bit for bit, a new chunk's value base + i for window chunk i.  The store only appends, so
+ *                 the OLD recipe stays valid: versions of a stream share their chunks.
+ *   rule          With cuts c_0 .. c_K of the old stream, a = edit_off, b = a + remove_bytes, delta = insert_bytes - remove_bytes:
+ *                 j = the chunk that holds byte a (the last chunk when a is the stream's end, 0 when K is 0).  The window is the edited
+ *                 stream from c_j to W + delta, W = the first old cut >= b + lookahead, or the end; it is chunked with final = (W is
+ *                 the end).  The first window cut x_t, t >= 1, at or behind b + delta for which x_t - delta is an old cut c_s ends the
+ *                 window's part: the new recipe is old positions [0, j), window chunks [0, t), old positions [s, K) with their cuts
+ *                 shifted by delta.  A final window without such a cut is kept whole and no tail follows; any other window without one
+ *                 inserts nothing anywhere, the lookahead doubles and the attempt is repeated.  lookahead 0 = 4 * max_size; a smaller
+ *                 value is raised to 2 * max_size.
+ *   attempt       Only positions [j, e] of the old recipe (c_e = W) are uploaded; their bytes [c_j, a) and [b, W) are rebuilt on the
+ *                 device around the uploaded insert (cw_dev_read_ranges); then cw_dev_cdc, cw_dev_cdc_resync, the hash, ONE synchronise
+ *                 (the kept count, the resync result, the store cursor and the read statuses), admission, the dedupe of the kept chunks,
+ *                 the codec over the new ones and cw_dev_store_chunks: cw_store_ingest's piece with the resync behind the chunker.
+ *   all or nothing  Nothing is inserted into index, directory or store before the window's old bytes were all read with status 0, a
+ *                 resync was found or the window was final, and the kept chunks were admitted exactly as a piece of cw_store_ingest
+ *                 is (index room for t, the directory for [base, base + t), the store conservatively against the kept bytes).
+ *                 CW_ERR_NOMEM (not admitted, or the window and its lists do not fit on the device: fall back to restore + ingest)
+ *                 and CW_ERR_BAD_ARG naming the first position that did not restore and its status (found by restoring the window's
+ *                 positions once more, whole; when that restore cannot get its buffers the message gives the window's positions and
+ *                 the two read statuses and says so) both leave index, store, directory and the old recipe as they were.
+ *   CW_ERR_BAD_ARG, before the device is touched: what cw_store_ingest refuses (max_size > CW_MAX_BLOCK_BYTES included), edit_off +
+ *                 remove_bytes wrapping or beyond the stream, a NULL insert with insert_bytes != 0, max_out < (stream bytes -
+ *                 remove_bytes + insert_bytes) / min_size + 2, offsets that decrease in the located window.
+ * The window and its lists live in the calling thread's context scratch (grows only): a stream that never resynchronises (all zero, or
+ * periodic) grows the window by doubling until it reaches the end of the stream.                                                     */
+int cw_store_patch(cw_dedupe_t *x, const cw_cdc_params *p, int comp_alg, const cw_store *st,
+                   const uint64_t *refs, const uint64_t *offsets, size_t nchunks,
+                   uint64_t edit_off, uint64_t remove_bytes, const void *insert, size_t insert_bytes,
+                   uint64_t base, size_t lookahead /* 0 = default */,
+                   uint64_t *out_refs, uint64_t *out_offsets, size_t max_out, size_t *out_nchunks,
+                   cw_patch_stats *stats /* may be NULL */);
+
 /* ---- the store forgets: mark, compact, and the index's retain ----------------------------------------
  * Mark and sweep over the same caller-owned buffers, plus one more the caller owns: d_live[dir_entries] (u32), a flag per
  * directory entry.  To drop streams: zero d_live and *d_n_outside, mark every recipe that stays, compact, retain.  Marking is
