@@ -317,6 +317,7 @@ const KnobDef kKnobTable[] = {
     {"CW_CDC_SEGMENT", [](Knobs &k, const char *v) { positive(k.cdc_segment, v); }},
     {"CW_STORE_PIECE", [](Knobs &k, const char *v) { positive(k.store_piece, v); }},
     {"CW_SCRUB_ENTRIES", [](Knobs &k, const char *v) { positive(k.scrub_entries, v); }},
+    {"CW_DELTA_TILE", [](Knobs &k, const char *v) { positive(k.delta_tile, v); }},
     {"CW_LZ_FORCE_REDO", [](Knobs &k, const char *v) { k.force_redo = atoi(v) > 0; }},
     {"CW_LZF_SHARE_GIVE_UP", [](Knobs &k, const char *v) { k.lzf_share_give_up = atoi(v) > 0; }},
     {"CW_LZ4_LANES", [](Knobs &k, const char *v) { k.lz4_lanes = atoi(v); }},

@@ -1,6 +1,6 @@
 // cw_chunks.hip -- host side of the device-resident calls over content-defined chunks: the cut (kernels: cdc_kernels.hip), the per-chunk
 // hash, the chunk codecs and their pack (chunk_codec_kernels.hip, pack_kernels.hip), the chunk store (restore_kernels.hip), its ranged reads (read_kernels.hip),
-// its mark and compact (store_gc_kernels.hip), its renumbering (renumber_kernels.hip), its accounting (account_kernels.hip) and its chunk bundles (replicate_kernels.hip).  Semantics: the public header.  Every refusal here comes before the device is touched.
+// its mark and compact (store_gc_kernels.hip), its renumbering (renumber_kernels.hip), its accounting (account_kernels.hip), its chunk bundles (replicate_kernels.hip) and its recipe diff and delta (delta_kernels.hip).  Semantics: the public header.  Every refusal here comes before the device is touched.
 
 #include "cw_host.h"
 
@@ -373,6 +373,59 @@ int cw_dev_store_account(const uint64_t *d_ref, const uint64_t *d_first, size_t 
     return launched_nomem(cw::store_account_launch(d_ref, d_first, nstreams, max_positions, d_dir, dir_base, dir_entries, d_flag, d_acct, d_refcount,
                                                    d_owner, d_totals, (hipStream_t)stream),
                           "store account launch");
+}
+
+// ---- what changed between two recipes, and a version as a delta (kernels: delta_kernels.hip) -------------------------------------
+static_assert(sizeof(cw_delta_op) == 32, "cw_delta_op is four u64 words");
+
+int cw_dev_recipe_diff(const uint64_t *d_ref_a, const uint64_t *d_off_a, const uint64_t *d_na, size_t max_a, const uint64_t *d_ref_b,
+                       const uint64_t *d_off_b, const uint64_t *d_nb, size_t max_b, uint64_t dir_base, size_t dir_entries, cw_delta_op *d_ops,
+                       size_t max_ops, uint64_t *d_nops, uint64_t *d_src, uint64_t *d_new_off, uint64_t *d_new_len, uint64_t *d_new_dst,
+                       uint64_t *d_nnew, uint64_t *d_totals, void *stream)
+{
+    int rc;
+    const char *null = !d_ref_a ? "d_ref_a" : !d_off_a ? "d_off_a" : !d_na ? "d_na" : !d_ref_b ? "d_ref_b" : !d_off_b ? "d_off_b" : !d_nb ? "d_nb"
+                     : !d_nops ? "d_nops" : !d_totals ? "d_totals" : max_ops && !d_ops ? "d_ops" : NULL;
+    if (null) return fail(CW_ERR_BAD_ARG, "NULL pointer: %s", null);
+    const int ranges = !!d_new_off + !!d_new_len + !!d_new_dst + !!d_nnew;
+    if (ranges != 0 && ranges != 4) return fail(CW_ERR_BAD_ARG, "NULL pointer: d_new_off, d_new_len, d_new_dst and d_nnew go together");
+    if (dir_entries == 0) return fail(CW_ERR_BAD_ARG, "dir_entries is 0");
+    if ((rc = check_count("max_a", max_a)) != CW_OK || (rc = check_count("max_b", max_b)) != CW_OK ||
+        (rc = check_count("dir_entries", dir_entries)) != CW_OK)
+        return rc;
+    const struct { const void *p; const char *name; } words[] = {
+        {d_ref_a, "d_ref_a"}, {d_off_a, "d_off_a"}, {d_na, "d_na"}, {d_ref_b, "d_ref_b"}, {d_off_b, "d_off_b"}, {d_nb, "d_nb"}, {d_ops, "d_ops"},
+        {d_nops, "d_nops"}, {d_src, "d_src"}, {d_new_off, "d_new_off"}, {d_new_len, "d_new_len"}, {d_new_dst, "d_new_dst"}, {d_nnew, "d_nnew"},
+        {d_totals, "d_totals"}};
+    for (const auto &w : words)
+        if ((rc = check_word_aligned((uintptr_t)w.p, w.name)) != CW_OK) return rc;
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    const hipError_t e = cw::recipe_diff_launch(d_ref_a, d_off_a, d_na, max_a, d_ref_b, d_off_b, d_nb, max_b, dir_base, dir_entries, d_ops, max_ops,
+                                                d_nops, d_src, d_new_off, d_new_len, d_new_dst, d_nnew, d_totals, (hipStream_t)stream);
+    if (e == hipErrorOutOfMemory)
+        return fail(CW_ERR_NOMEM, "recipe diff scratch (%zu bytes): %s", cw::recipe_diff_scratch_bytes(max_b, dir_entries), hipGetErrorString(e));
+    return launched(e, "recipe diff launch");
+}
+
+int cw_dev_apply_delta(const void *d_old, size_t old_bytes, const void *d_payload, size_t payload_bytes, const cw_delta_op *d_ops,
+                       const uint64_t *d_nops, size_t max_ops, void *d_dst, size_t dst_bytes, uint64_t *d_result, void *stream)
+{
+    int rc;
+    const char *null = !d_nops ? "d_nops" : !d_result ? "d_result" : max_ops && !d_ops ? "d_ops" : old_bytes && !d_old ? "d_old"
+                     : payload_bytes && !d_payload ? "d_payload" : dst_bytes && !d_dst ? "d_dst" : NULL;
+    if (null) return fail(CW_ERR_BAD_ARG, "NULL pointer: %s", null);
+    if ((rc = check_count("max_ops", max_ops)) != CW_OK) return rc;
+    if ((rc = check_word_aligned((uintptr_t)d_ops, "d_ops")) != CW_OK || (rc = check_word_aligned((uintptr_t)d_nops, "d_nops")) != CW_OK ||
+        (rc = check_word_aligned((uintptr_t)d_result, "d_result")) != CW_OK)
+        return rc;
+    if (ranges_overlap(d_dst, dst_bytes, d_old, old_bytes)) return fail(CW_ERR_BAD_ARG, "d_dst overlaps d_old");
+    if (ranges_overlap(d_dst, dst_bytes, d_payload, payload_bytes)) return fail(CW_ERR_BAD_ARG, "d_dst overlaps d_payload");
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    ProfScope prof(PROF_CODEC, (hipStream_t)stream);
+    return launched(cw::apply_delta_launch((const uint8_t *)d_old, old_bytes, (const uint8_t *)d_payload, payload_bytes, d_ops, d_nops, max_ops,
+                                           (uint8_t *)d_dst, dst_bytes, cw::apply_delta_tile_shift(cw::knobs().delta_tile), d_result,
+                                           (hipStream_t)stream),
+                    "apply delta launch");
 }
 
 // ---- chunk bundles between stores: export, import, translate (kernels: replicate_kernels.hip) ----------------------------------

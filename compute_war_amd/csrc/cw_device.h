@@ -284,6 +284,18 @@ hipError_t store_account_launch(const uint64_t *ref, const uint64_t *first, size
                                 uint64_t dir_base, size_t dir_entries, const uint32_t *flag, void *acct, uint32_t *refcount, uint32_t *owner,
                                 uint64_t *totals, hipStream_t stream);
 
+// recipe diff and delta apply (delta_kernels.hip; semantics: the public header).  ops: cw_delta_op entries; src and the four range
+// arrays may be NULL
+hipError_t recipe_diff_launch(const uint64_t *ref_a, const uint64_t *off_a, const uint64_t *d_na, size_t max_a, const uint64_t *ref_b,
+                              const uint64_t *off_b, const uint64_t *d_nb, size_t max_b, uint64_t dir_base, size_t dir_entries, void *ops,
+                              size_t max_ops, uint64_t *nops, uint64_t *src, uint64_t *new_off, uint64_t *new_len, uint64_t *new_dst,
+                              uint64_t *nnew, uint64_t *totals, hipStream_t stream);
+size_t recipe_diff_scratch_bytes(size_t max_b, size_t dir_entries);
+unsigned apply_delta_tile_shift(long knob_kib); // CW_DELTA_TILE: 16, 64 or 256 (KiB); anything else is the default
+hipError_t apply_delta_launch(const uint8_t *old, size_t old_bytes, const uint8_t *payload, size_t payload_bytes, const void *ops,
+                              const uint64_t *d_nops, size_t max_ops, uint8_t *dst, size_t dst_bytes, unsigned tile_shift, uint64_t *result,
+                              hipStream_t stream);
+
 // chunk bundles between stores (replicate_kernels.hip; semantics: the public header).  loc / dir: cw_chunk_loc entries, 16-byte aligned
 hipError_t store_export_launch(const uint8_t *store, size_t store_bytes, const void *dir, uint64_t dir_base, size_t dir_entries,
                                const uint64_t *values, const uint64_t *d_count, size_t max_count, uint8_t *out, size_t out_bytes, void *out_loc,

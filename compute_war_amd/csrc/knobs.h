@@ -32,7 +32,7 @@ struct Knobs {
     // > 0
     int scan_wpc = 0, parse_wpc = 0, lanes_wpc = 0, lanes_reserve = 0, vtab_wpc = 0, lzf_st_wpc = 0, lzf_round = 0, lzf_lds_max = 0,
         skein_nslices = 0;
-    long host_chunk_mb = 0, host_big_chunk_mb = 0, cdc_segment = 0, store_piece = 0, scrub_entries = 0;
+    long host_chunk_mb = 0, host_big_chunk_mb = 0, cdc_segment = 0, store_piece = 0, scrub_entries = 0, delta_tile = 0;
     bool force_redo = false, lzf_share_give_up = false; // CW_LZ_FORCE_REDO, CW_LZF_SHARE_GIVE_UP
     // set: atoi of the value ("" = 0)
     std::optional<int> lz4_lanes, lzf_lanes, decode_lanes, lanes_leave, vtab_min, vtab_max, vtab_reserve, lz4_vtab, lz4_lanes_ring,

@@ -894,6 +894,39 @@ def store_patch(index: "DedupeIndex", params: "CdcParams", comp_alg, store: Stor
     return out_refs[:k].copy(), out_offs[:k + 1].copy(), stats.as_dict()
 
 
+# ---- recipe diff and deltas (cw_dev_recipe_diff / cw_dev_apply_delta) ------------------------------------
+class DeltaOp(C.Structure):
+    """cw_delta_op: B's bytes [b_off, b_off + len) are A's from a_off on (a copy) or the payload's from payload_off on (a new op);
+    the other of the two is ``NONE``.  Offsets are zero-based."""
+    _fields_ = [(k, C.c_uint64) for k in ("b_off", "len", "a_off", "payload_off")]
+    NONE = (1 << 64) - 1  # CW_DELTA_NONE
+
+
+DELTA_OP_DTYPE = np.dtype([(k, "<u8") for k, _ in DeltaOp._fields_])  # cw_delta_op as a numpy record
+
+
+def dev_recipe_diff(d_ref_a: int, d_off_a: int, d_na: int, max_a: int, d_ref_b: int, d_off_b: int, d_nb: int, max_b: int, dir_base: int,
+                    dir_entries: int, d_ops: int, max_ops: int, d_nops: int, d_totals: int, stream: int = 0, d_src: int = 0, d_new_off: int = 0,
+                    d_new_len: int = 0, d_new_dst: int = 0, d_nnew: int = 0) -> None:
+    """The ops that turn the stream of recipe A (d_ref_a, d_off_a, min(*d_na, max_a) positions) into that of recipe B, from the
+    recipes alone: d_ops[0..*d_nops) (cw_delta_op), d_src[i] (or 0) = where B position i's bytes lie in A or DeltaOp.NONE, the new ops
+    as ranges for dev_read_ranges over recipe B (all four or none).  d_totals[0..8) = verdict (1: an offset list does not ascend in
+    extents of 1..65536, nothing else written; 2: more ops than max_ops, no op written), ops, new ops, in-place / moved / new bytes,
+    matched positions, B positions.  max_ops = 0 with d_ops = 0 is a dry run.  Not synchronised."""
+    check(lib().cw_dev_recipe_diff(d_ref_a, d_off_a, d_na, max_a, d_ref_b, d_off_b, d_nb, max_b, dir_base, dir_entries, d_ops or None, max_ops,
+                                   d_nops, d_src or None, d_new_off or None, d_new_len or None, d_new_dst or None, d_nnew or None, d_totals,
+                                   stream))
+
+
+def dev_apply_delta(d_old: int, old_bytes: int, d_payload: int, payload_bytes: int, d_ops: int, d_nops: int, max_ops: int, d_dst: int,
+                    dst_bytes: int, d_result: int, stream: int = 0) -> None:
+    """d_dst[0..total) = the stream the min(*d_nops, max_ops) ops build from d_old and d_payload.  d_result[0..4) = verdict (1: the
+    list is malformed, 2: total > dst_bytes; nothing written then), total, the lowest malformed op or DeltaOp.NONE, the op count.
+    Not synchronised."""
+    check(lib().cw_dev_apply_delta(d_old or None, old_bytes, d_payload or None, payload_bytes, d_ops or None, d_nops, max_ops, d_dst or None,
+                                   dst_bytes, d_result, stream))
+
+
 def store_restore(comp_alg, store: Store, refs, offsets, dst: int, dst_bytes: int):
     """cw_store_restore into the host memory at address ``dst``: the status of every position (u32 array)."""
     refs, offsets = np.ascontiguousarray(refs, np.uint64), np.ascontiguousarray(offsets, np.uint64)

@@ -1,4 +1,4 @@
-"""The chunk store: ``ChunkStore`` and what travels with it (``Recipe``, ``Bundle``, ``ScrubReport``) over the ``dev_*`` and
+"""The chunk store: ``ChunkStore`` and what travels with it (``Recipe``, ``Bundle``, ``ScrubReport``, ``Diff``, ``Delta``) over the ``dev_*`` and
 ``store_*`` wrappers of ``ops``.
 
 ``ops`` takes raw device pointers and never touches torch; this is the one place in the package that owns torch buffers: it
@@ -10,8 +10,8 @@ from __future__ import annotations
 import numpy as np
 
 from ._lib import CwError, lib
-from .ops import (ACCOUNT_DTYPE, CdcParams, ChunkLoc, DedupeIndex, Store, _comp_id, _hash_id, _np_u8, chunk_slots_bytes, dev_hash_chunks,
-                  dev_read_ranges, dev_restore_chunks, dev_store_account, dev_store_chunks, dev_store_compact, dev_store_export_chunks, dev_store_import_chunks, dev_store_mark,
+from .ops import (ACCOUNT_DTYPE, DELTA_OP_DTYPE, CdcParams, ChunkLoc, DedupeIndex, DeltaOp, Store, _comp_id, _hash_id, _np_u8, chunk_slots_bytes,
+                  dev_apply_delta, dev_hash_chunks, dev_read_ranges, dev_recipe_diff, dev_restore_chunks, dev_store_account, dev_store_chunks, dev_store_compact, dev_store_export_chunks, dev_store_import_chunks, dev_store_mark,
                   dev_store_renumber, dev_store_replace_chunks, dev_translate_refs, device_count, digest_bytes, init, store_ingest,
                   store_ingest_streams, store_patch, store_restore, store_scrub)
 
@@ -131,6 +131,74 @@ class Account:
         self.totals["unreferenced_stored"] = self.totals["nonzero_stored"] - self.totals["referenced_stored"]
 
 
+class Diff:
+    """What ``ChunkStore.diff(old, new)`` found, from the recipes alone: ``ops`` (a DELTA_OP_DTYPE record per op; the ops tile the new
+    stream back to back, each a copy out of the old stream or a run of new bytes), ``src`` (uint64 per position of ``new``: where its
+    bytes lie in the old stream, or ``DeltaOp.NONE``) and ``totals`` (a dict under the names of ``DIFF_TOTALS``).  Offsets are
+    zero-based.  Values only enter through equality, so a Diff is unchanged by ``renumber`` of both recipes and by ``compact``."""
+
+    def __init__(self, ops, src, totals):
+        self.ops = np.ascontiguousarray(ops, dtype=DELTA_OP_DTYPE).reshape(-1)
+        self.src = np.ascontiguousarray(src, dtype=np.uint64).reshape(-1)
+        self.totals = dict(zip(DIFF_TOTALS, (int(v) for v in totals)))
+
+    def changed_ranges(self) -> list:
+        """The new ops as ``(offset, length)`` in the new stream: what ``read_ranges(new, ...)`` takes."""
+        new = self.ops[self.ops["a_off"] == np.uint64(DeltaOp.NONE)]
+        return [(int(o), int(n)) for o, n in zip(new["b_off"], new["len"])]
+
+
+DIFF_TOTALS = ("ops", "new_ops", "in_place_bytes", "moved_bytes", "new_bytes", "matched_positions", "positions")  # d_totals[1..7]
+
+
+class Delta:
+    """Version B for someone who holds version A as plain bytes (``ChunkStore.delta(old, new)``): ``ops`` as in a ``Diff``, ``payload``
+    (uint8: the new ops' bytes back to back), ``old_bytes`` and ``new_bytes`` (the sizes of the two streams).  Plain host data:
+    ``save`` / ``load`` use one ``.npz``; ``apply_delta(old, delta)`` needs no store and no index."""
+
+    def __init__(self, ops, payload, old_bytes: int, new_bytes: int):
+        self.ops = np.ascontiguousarray(ops, dtype=DELTA_OP_DTYPE).reshape(-1)
+        self.payload = _np_u8(payload)
+        self.old_bytes, self.new_bytes = int(old_bytes), int(new_bytes)
+
+    def save(self, path) -> None:
+        with open(path, "wb") as f:
+            np.savez(f, ops=self.ops, payload=self.payload, old_bytes=np.uint64(self.old_bytes), new_bytes=np.uint64(self.new_bytes))
+
+    @classmethod
+    def load(cls, path) -> "Delta":
+        with np.load(path) as z:
+            return cls(z["ops"], z["payload"], int(z["old_bytes"]), int(z["new_bytes"]))
+
+
+def apply_delta(old, delta: Delta) -> bytes:
+    """The new stream's bytes from the old stream's and a ``Delta`` (``dev_apply_delta``): one upload, one call, one download.
+    Nothing of the delta is trusted: raises CwError (-2) naming the first malformed op, or when the ops build another size than
+    ``delta.new_bytes`` or ``old`` is not of ``delta.old_bytes`` bytes."""
+    if device_count() <= 0:
+        init()  # (raises: no device)
+    import torch
+    a = _np_u8(old)
+    if a.size != delta.old_bytes:
+        raise CwError(-2, f"delta: made against an old stream of {delta.old_bytes} bytes, not {a.size}")
+    n, s = len(delta.ops), torch.cuda.current_stream().cuda_stream
+    d_old, d_payload = _u8(a if a.size else np.zeros(1, np.uint8)), _u8(delta.payload if delta.payload.size else np.zeros(1, np.uint8))
+    d_ops, d_n = _u8(delta.ops if n else np.zeros(1, DELTA_OP_DTYPE)), _u64([n])
+    out, result = _zeros(delta.new_bytes, torch.uint8), _zeros(4)
+    torch.cuda.synchronize()
+    dev_apply_delta(d_old.data_ptr(), a.size, d_payload.data_ptr(), delta.payload.size, d_ops.data_ptr(), d_n.data_ptr(), n, out.data_ptr(),
+                    delta.new_bytes, result.data_ptr(), s)
+    torch.cuda.synchronize()
+    verdict, total, bad, _ = _words(result)
+    if verdict == 1:
+        err = CwError(-2, f"delta: op {bad} of {n} is malformed")
+        err.op = bad
+        raise err
+    if verdict or total != delta.new_bytes:
+        raise CwError(-2, f"delta: the ops build {total} bytes, the delta says {delta.new_bytes}")
+    return out.cpu().numpy()[:total].tobytes()
+
+
 class Bundle:
     """Chunks on their way from one ChunkStore to another, as plain host data.  The manifest lists the n
     distinct chunks ``recipes`` name in ascending sender value: ``digests`` uint8[n, digest bytes], ``values`` uint64[n] (the
@@ -184,7 +252,9 @@ class ChunkStore:
     ``restore_stream`` take and give host buffers of any size, streamed through the device in pieces (cw_store_ingest /
     cw_store_restore), ``ingest_many_stream`` and ``restore_many_stream`` many of them in one pipelined run; ``last_stats`` holds the
     last streamed ingest's statistics.  ``patch`` edits a stored stream in place -- ``write``, ``append``, ``truncate`` and
-    ``patch_many`` are thin forms of it -- and ``last_patch`` holds the last edit's statistics (cw_patch_stats as a dict)."""
+    ``patch_many`` are thin forms of it -- and ``last_patch`` holds the last edit's statistics (cw_patch_stats as a dict).  ``diff``
+    says what changed between two recipes from the recipes alone, and ``delta`` packs the new version's new bytes with those ops for
+    someone who holds the old version as plain bytes (``apply_delta``)."""
     last_stats = None
     last_patch = None
 
@@ -453,6 +523,74 @@ class ChunkStore:
         for o, r, d in reversed(edits):
             recipe = self.patch(recipe, o, r, d)
         return recipe
+
+    def _diff_call(self, old: Recipe, new: Recipe, max_ops: int, ranges: bool):
+        """One queued ``dev_recipe_diff`` of the two recipes with room for max_ops ops: the device buffers as a dict.  The caller
+        synchronises."""
+        import torch
+        ka, kb, s = len(old.refs), len(new.refs), self._stream()
+        t = dict(ref_a=_u64(old.refs if ka else [0]), off_a=_u64(old.offsets), na=_u64([ka]), ref_b=_u64(new.refs if kb else [0]),
+                 off_b=_u64(new.offsets), nb=_u64([kb]), ops=_zeros(max_ops * 4), nops=_zeros(1), src=_zeros(kb), totals=_zeros(8))
+        if ranges:
+            t.update(new_off=_zeros(max_ops), new_len=_zeros(max_ops), new_dst=_zeros(max_ops), nnew=_zeros(1))
+        torch.cuda.synchronize()  # (torch zeroed and copied on its own stream)
+        ptr = lambda k: t[k].data_ptr() if k in t else 0  # noqa: E731
+        dev_recipe_diff(ptr("ref_a"), ptr("off_a"), ptr("na"), ka, ptr("ref_b"), ptr("off_b"), ptr("nb"), kb, self.dir_base, self.dir_entries,
+                        ptr("ops") if max_ops else 0, max_ops, ptr("nops"), ptr("totals"), s, ptr("src"), ptr("new_off"), ptr("new_len"),
+                        ptr("new_dst"), ptr("nnew"))
+        return t
+
+    @staticmethod
+    def _refuse_recipes(verdict: int) -> None:
+        if verdict == 1:
+            raise CwError(-2, "chunk store: a recipe's offsets do not ascend in extents of 1 to 65536 bytes")
+
+    def diff(self, old: Recipe, new: Recipe, max_ops: int = 4096) -> Diff:
+        """What changed between two recipes of this store (``dev_recipe_diff``): no data is read, equal refs
+        mean equal bytes.  One call with room for ``max_ops`` ops, and a second one with the room the first reported when that was too
+        little.  Raises CwError (-2) when a recipe's offsets are not what the library writes."""
+        if device_count() <= 0:
+            init()  # (raises: no device)
+        import torch
+        for attempt in range(2):
+            t = self._diff_call(old, new, max_ops, False)
+            torch.cuda.synchronize()
+            totals = _words(t["totals"])
+            self._refuse_recipes(totals[0])
+            if totals[0] == 0:
+                return Diff(t["ops"].cpu().numpy().view(DELTA_OP_DTYPE)[:totals[1]], t["src"].cpu().numpy().view(np.uint64)[:len(new.refs)],
+                            totals[1:])
+            max_ops = totals[1]  # (verdict 2: the dry run that sized the buffer)
+        raise CwError(-4, f"chunk store: the diff was refused with verdict {totals[0]} after its dry run")
+
+    def delta(self, old: Recipe, new: Recipe) -> Delta:
+        """``new`` as a ``Delta`` against ``old``: the diff and, queued directly behind it, ``dev_read_ranges`` of the new ops' bytes
+        over ``new``, with one synchronise (room for one op per position and for every byte of ``new``).  Raises CwError (-2) naming
+        the first range whose status is not 0 (a damaged stored chunk, say), or when a recipe's offsets are not what the library
+        writes."""
+        if device_count() <= 0:
+            init()  # (raises: no device)
+        import torch
+        kb, nbytes, s = len(new.refs), new.nbytes, self._stream()
+        cap = max(kb, 1)
+        payload, status = _zeros(nbytes, torch.uint8), _zeros(cap, torch.int32)
+        t = self._diff_call(old, new, cap, True)
+        dev_read_ranges(self.comp_alg, self.d_store.data_ptr(), self.store_bytes, self.d_dir.data_ptr(), self.dir_base, self.dir_entries,
+                        t["ref_b"].data_ptr(), t["off_b"].data_ptr(), t["nb"].data_ptr(), kb, t["new_off"].data_ptr(), t["new_len"].data_ptr(),
+                        t["new_dst"].data_ptr(), t["nnew"].data_ptr(), cap, payload.data_ptr(), nbytes, status.data_ptr(), s)
+        torch.cuda.synchronize()
+        totals = _words(t["totals"])
+        self._refuse_recipes(totals[0])
+        if totals[0]:
+            raise CwError(-4, f"chunk store: the diff of {kb} positions was refused with verdict {totals[0]}")
+        ops = t["ops"].cpu().numpy().view(DELTA_OP_DTYPE)[:totals[1]]
+        st = status.cpu().numpy()[:totals[2]]
+        if st.any():
+            j = int(np.nonzero(st)[0][0])
+            off, length = int(t["new_off"][j].item()), int(t["new_len"][j].item())
+            raise CwError(-2, f"chunk store: {int((st != 0).sum())} of {len(st)} new ranges not read; range {j} (offset "
+                              f"{off - int(new.offsets[0])}, length {length}) has status {int(st[j])}")
+        return Delta(ops, payload.cpu().numpy()[:totals[5]], old.nbytes, nbytes)
 
     def _mark(self, recipes, s: int):
         """(live: a u32 flag per directory entry; n_outside: the positions that name none) after ``dev_store_mark`` of every recipe."""

@@ -867,6 +867,65 @@ int cw_dev_store_account(const uint64_t *d_ref, const uint64_t *d_first, size_t 
                          uint32_t *d_refcount /* [dir_entries], may be NULL */, uint32_t *d_owner /* [dir_entries], may be NULL */,
                          uint64_t *d_totals /* [8] */, void *stream);
 
+/* ---- what changed between two recipes, and a version shipped as a delta ---------------------------------
+ * A patched stream and its parent share every chunk but the few around the edit.  Equal refs mean equal bytes, so what changed
+ * between two recipes is decided from the recipes alone, and handing version B to someone who holds version A as plain bytes takes
+ * only the bytes of the chunks that are new.  A delta is a list of ops that tile B back to back, each either a copy out of A or a
+ * run of new bytes out of a payload, and the payload.  Both calls follow the store's conventions: device pointers, counts read on
+ * the device, queued on `stream`, nothing synchronises, every decision made on the device and all or nothing.                     */
+#define CW_DELTA_NONE UINT64_MAX
+typedef struct cw_delta_op {   /* 32 bytes; offsets are zero-based (x - off[0] on each side) */
+    uint64_t b_off;              /* where the op starts in B; the ops tile B back to back from 0 */
+    uint64_t len;                /* its bytes, at least 1 */
+    uint64_t a_off;              /* a copy: where its bytes lie in A; a new op: CW_DELTA_NONE */
+    uint64_t payload_off;        /* a new op: where its bytes lie in the payload; a copy: CW_DELTA_NONE */
+} cw_delta_op;
+/* The ops that turn stream A into stream B, from their recipes alone.
+ *   recipes       A is d_ref_a[0..na), d_off_a[0..na] with na = min(*d_na, max_a), B likewise: what the ingests, cw_store_patch and
+ *                 cw_dev_translate_refs write, in any coordinates (cw_dev_restore_chunks' d_raw_offsets).  dir_base and dir_entries
+ *                 are the value range of the directory: they bound a per-entry table, the directory itself is not read.
+ *   verdict       d_totals[0], decided on the device before anything else is written: 1 unless both offset lists ascend strictly in
+ *                 extents of 1..65536 bytes (what the library writes), and then no other byte of any output changes.
+ *   source        of B position i, in zero-based offsets.  IN PLACE: an A position starts at the same offset with the same ref and
+ *                 the same length; the source is that offset.  Else MOVED: the lowest A position that names the same ref, if its
+ *                 length is that of i; the source is its offset.  Else NEW: CW_DELTA_NONE.  A ref outside [dir_base, dir_base +
+ *                 dir_entries), CW_DEDUPE_MISS among them, names no chunk: such a position of A is no source and such a position of
+ *                 B is new.  d_src[i] (optional) = the source of i < nb.
+ *   ops           position i starts an op unless it continues the one before: both are new, or both are copies and source(i) ==
+ *                 source(i-1) + length(i-1).  The new ops' bytes are numbered back to back in op order: payload_off.  d_ops[0..ops)
+ *                 and *d_nops = ops.  More ops than max_ops: verdict 2, *d_nops = *d_nnew = 0, no op and no range is written, the
+ *                 totals are complete -- max_ops == 0 (d_ops may then be NULL) is the dry run that sizes the buffers.
+ *   ranges        optional, all four or none: the new ops as d_new_off / d_new_len / d_new_dst [0..*d_nnew) (room for max_ops each),
+ *                 offsets in B's own coordinates and destinations equal to payload_off, so cw_dev_read_ranges over recipe B queues
+ *                 directly behind this call and its d_dst is the payload.
+ *   d_totals[8]   {verdict, ops, new ops, in-place bytes, moved bytes, new bytes, matched positions, nb}.
+ * Everything is an integer and the table is built with atomicMin, which does not depend on order: every output is bit for bit a
+ * function of the arguments.  A run of one repeated chunk that shifts costs one op per chunk (the lowest position wins); in place
+ * it is one op.  Whatever the buffers hold, no load leaves d_ref_x[0..max_x), d_off_x[0..max_x] or the scratch, and no store leaves
+ * the outputs and the scratch.  CW_ERR_BAD_ARG before anything is launched: a NULL pointer (d_src may be NULL, the four range
+ * pointers may be together, d_ops may be when max_ops is 0), a pointer that is not 8-byte aligned, max_a, max_b or dir_entries
+ * above 2^32 - 256, dir_entries == 0.  Scratch, per stream: at most 96 + 4 * dir_entries + 44 * max_b bytes.  Not synchronised.  */
+int cw_dev_recipe_diff(const uint64_t *d_ref_a, const uint64_t *d_off_a, const uint64_t *d_na, size_t max_a,
+                       const uint64_t *d_ref_b, const uint64_t *d_off_b, const uint64_t *d_nb, size_t max_b,
+                       uint64_t dir_base, size_t dir_entries,
+                       cw_delta_op *d_ops /* [max_ops] */, size_t max_ops, uint64_t *d_nops,
+                       uint64_t *d_src /* [max_b], may be NULL */,
+                       uint64_t *d_new_off, uint64_t *d_new_len, uint64_t *d_new_dst /* [max_ops] each */, uint64_t *d_nnew /* may be NULL together */,
+                       uint64_t *d_totals /* [8] */, void *stream);
+/* Rebuilds B's bytes from A's plain bytes d_old[0..old_bytes), a payload and n = min(*d_nops, max_ops) ops.  A delta may come from
+ * a file, so nothing of the list is trusted.  d_result[4] = {verdict, total, the lowest bad op or CW_DELTA_NONE, n}.  Verdict 1, a
+ * malformed list (total is then 0): an op that does not start where the one before ends (op 0: at 0), has len 0 or an end that
+ * wraps, has both or neither of a_off and payload_off equal to CW_DELTA_NONE, or has a_off + len > old_bytes or payload_off + len >
+ * payload_bytes.  Else verdict 2 when total = the end of the last op > dst_bytes.  Else 0, and d_dst[0..total) is B.  With a verdict
+ * other than 0 not a byte of d_dst changes.  Whatever the ops hold, no load leaves d_old, d_payload or d_ops[0..n) and no store
+ * leaves d_dst[0..total) and d_result.  The copy is tiled by output (CW_DELTA_TILE KiB per wavefront), so an op of one byte and one
+ * of gigabytes cost what their bytes cost.  CW_ERR_BAD_ARG before anything is launched: a NULL pointer (d_old, d_payload, d_dst and
+ * d_ops may be when their size is 0), a d_ops, d_nops or d_result that is not 8-byte aligned, max_ops > 2^32 - 256, [d_dst,
+ * +dst_bytes) overlapping [d_old, +old_bytes) or [d_payload, +payload_bytes).  No scratch.  Not synchronised.                     */
+int cw_dev_apply_delta(const void *d_old, size_t old_bytes, const void *d_payload, size_t payload_bytes,
+                       const cw_delta_op *d_ops, const uint64_t *d_nops, size_t max_ops,
+                       void *d_dst, size_t dst_bytes, uint64_t *d_result /* [4] */, void *stream);
+
 /* ---- chunk bundles: stored chunks from one store to another -------------------------------------------
  * A bundle is a manifest and a payload.  The manifest lists the n distinct chunks a set of recipes names, in ascending value of
  * the sending store: digest[k], value[k] and loc[k] (a cw_chunk_loc whose pos is relative to the payload; all zero = listed but
