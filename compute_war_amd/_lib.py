@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "cw_dev_store_verify", "cw_store_scrub", "cw_dev_store_replace_chunks",
     "cw_dev_store_renumber", "cw_dev_dedupe_revalue", "cw_dev_store_account",
     "cw_dev_cdc_resync", "cw_store_patch", "cw_dev_recipe_diff", "cw_dev_apply_delta",
+    "cw_dev_cdc_resync_windows", "cw_dev_scatter_extents", "cw_store_compose",
     "cw_shard_range", "cw_mgpu_create", "cw_mgpu_destroy", "cw_mgpu_ndev", "cw_mgpu_device", "cw_mgpu_last_error", "cw_mgpu_gather",
 ]
 
@@ -188,6 +189,9 @@ def lib() -> C.CDLL:
         "cw_store_patch": ([vp, vp, C.c_int, vp, vp, vp, sz, C.c_uint64, C.c_uint64, vp, sz, C.c_uint64, sz, vp, vp, sz, vp, vp], C.c_int),
         "cw_dev_recipe_diff": ([vp, vp, vp, sz, vp, vp, vp, sz, C.c_uint64, sz, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
         "cw_dev_apply_delta": ([vp, sz, vp, sz, vp, vp, sz, vp, sz, vp, vp], C.c_int),
+        "cw_dev_cdc_resync_windows": ([vp, vp, sz, vp, vp, sz, vp, sz, vp, vp], C.c_int),
+        "cw_dev_scatter_extents": ([vp, sz, vp, vp, sz, vp, sz, vp, vp], C.c_int),
+        "cw_store_compose": ([vp, vp, C.c_int, vp, vp, vp, sz, vp, sz, vp, sz, vp, sz, C.c_uint64, sz, vp, vp, sz, vp, vp], C.c_int),
         "cw_shard_range": ([sz, C.c_int, C.c_int, vp, vp], None),
         "cw_mgpu_create": ([vp, C.c_int], vp), "cw_mgpu_destroy": ([vp], None), "cw_mgpu_ndev": ([vp], C.c_int),
         "cw_mgpu_device": ([vp, C.c_int], C.c_int), "cw_mgpu_last_error": ([], C.c_char_p),

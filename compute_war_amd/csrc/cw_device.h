@@ -296,6 +296,13 @@ hipError_t apply_delta_launch(const uint8_t *old, size_t old_bytes, const uint8_
                               const uint64_t *d_nops, size_t max_ops, uint8_t *dst, size_t dst_bytes, unsigned tile_shift, uint64_t *result,
                               hipStream_t stream);
 
+// the device steps of a compose (compose_kernels.hip; semantics: the public header).  win: cw_resync_window entries; ext: three words
+// per extent (src_off, dst_off, len)
+hipError_t cdc_resync_windows_launch(const uint64_t *new_offsets, const uint64_t *d_new_count, size_t max_new, const uint64_t *stream_first,
+                                     const void *win, size_t nwin, const uint64_t *old_offsets, size_t max_old, uint64_t *result, hipStream_t stream);
+hipError_t scatter_extents_launch(const uint8_t *src, size_t src_bytes, const uint64_t *ext, const uint64_t *d_n, size_t max_n, uint8_t *dst,
+                                  size_t dst_bytes, uint64_t *result, hipStream_t stream);
+
 // chunk bundles between stores (replicate_kernels.hip; semantics: the public header).  loc / dir: cw_chunk_loc entries, 16-byte aligned
 hipError_t store_export_launch(const uint8_t *store, size_t store_bytes, const void *dir, uint64_t dir_base, size_t dir_entries,
                                const uint64_t *values, const uint64_t *d_count, size_t max_count, uint8_t *out, size_t out_bytes, void *out_loc,

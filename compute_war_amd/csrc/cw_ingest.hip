@@ -3,7 +3,9 @@
 // cw_store_restore streams a recipe back in windows, and cw_dev_ingest_commit / cw_dev_ingest_commit_streams are the device step that
 // assembles a recipe piece by piece (kernels: ingest_kernels.hip).  cw_store_patch edits a stored stream in place (DESIGN.md section 25;
 // struct Patch, one piece of the same kind over a window rebuilt on the device), with cw_dev_cdc_resync as its device step (kernels:
-// patch_kernels.hip).
+// patch_kernels.hip).  cw_store_compose builds a stream from ranges of stored streams and new bytes (struct
+// Compose: rounds that only chunk the windows between the kept ranges, then one piece over everything rebuilt), with
+// cw_dev_cdc_resync_windows and cw_dev_scatter_extents as its device steps (kernels: compose_kernels.hip).
 //
 // Both ingests are one loop (struct Ingest) over a list of host spans; cw_store_ingest's one buffer is a single span.  With the stream
 // index (cw_store_ingest_streams) a piece is chunked by cw_dev_cdc_streams_part with the stream ends that fall into it and committed by
@@ -476,6 +478,394 @@ struct Patch {
     }
 };
 
+// A stream composed from ranges of stored streams and new bytes (cw_store_compose).  The plan is the host's:
+// the copies merged and split at A's stream ends, the anchors [p, q) by binary search, a window in front of every anchor and a final
+// one behind the last.  A round materialises the unresolved windows back to back in src[0] and only chunks them:
+//     stream   lists -> meta[1] | read ranges of A into src[0] | scatter the new bytes out of src[1] | cdc_streams | resync_windows
+//              | statuses, results, words -> host | SYNCHRONISE
+// and the commit is one piece of Ingest's kind over the rebuilt extents of all windows, each a stream of its own:
+//     stream   lists | read ranges | scatter | cdc_streams, hash, counts | SYNCHRONISE: statuses, stream index, admit | dedupe, codec,
+//              append | refs, cuts -> host | SYNCHRONISE
+// src[1] holds the payload and meta[0] the recipe of A (count | refs | zero-based cuts), both uploaded once.
+struct Compose {
+    struct Anchor { uint64_t b, d; size_t p, q; };   // a copy piece at b of B with keepable positions [p, q) of A; d = a - b (mod 2^64)
+    struct Window {
+        uint64_t start; long anchor;                 // where it starts in B; the anchor it runs into, -1 for the final window
+        uint64_t look;
+        bool resolved = false, discard = false, ran = false, exhausted = false;
+        uint64_t t = 0, end = 0; size_t s = 0;       // resolved: t chunks in [start, end), then positions [s, q) of the anchor
+        uint64_t at = 0, tried = 0; size_t slot = 0; // the round: where it lies in src[0], where it ends in B, its index among the round's
+    };
+    struct Span { uint64_t start, end; };            // a stretch of B to materialise
+    cw_dedupe_t *x; const cw_cdc_params *p; int comp_alg; const cw_store *st;
+    const uint64_t *refs; size_t K; const uint64_t *stream_first; size_t nstreams;
+    const cw_delta_op *ops; size_t nops; const uint8_t *payload; size_t payload_bytes;
+    uint64_t base, nb, look0; size_t max_out;
+    cw_compose_stats *stats;
+    StoreCtx *c = nullptr; hipStream_t s = nullptr;
+    std::vector<uint64_t> cuts, lists;               // A's zero-based cuts; a round's lists on their way up
+    std::vector<Anchor> anchors;
+    std::vector<Window> wins;
+    std::vector<Span> spans;
+    size_t nranges = 0, next = 0, cap = 0, slots_bytes = 0; uint64_t total = 0; // of the spans materialised last
+    bool uploaded = false, unread = false;
+
+    uint64_t in_b(const Anchor &a, size_t i) const { return cuts[i] - a.d; } // cut i of A in B's coordinates, through anchor a
+    // the first i in [lo, hi) with v[i] >= x, hi when there is none
+    static size_t lower(const std::vector<uint64_t> &v, size_t lo, size_t hi, uint64_t x)
+    {
+        while (lo < hi) {
+            const size_t mid = lo + (hi - lo) / 2;
+            if (v[mid] < x) lo = mid + 1;
+            else hi = mid;
+        }
+        return lo;
+    }
+    bool ends_stream(size_t q) const // position q - 1 is the last of its stream
+    {
+        if (!stream_first) return q == K;
+        size_t lo = 1, hi = nstreams + 1;
+        while (lo < hi) {
+            const size_t mid = lo + (hi - lo) / 2;
+            if (stream_first[mid] < q) lo = mid + 1;
+            else hi = mid;
+        }
+        return lo <= nstreams && stream_first[lo] == q;
+    }
+
+    void add_piece(uint64_t b, uint64_t n, uint64_t a)
+    {
+        size_t pp = lower(cuts, 0, K + 1, a), q = lower(cuts, 0, K + 1, a + n); // (a + n <= cuts[K]: the ops were checked)
+        if (cuts[q] != a + n) q--;                                               // the last cut at or below a + n
+        if (q > pp && ends_stream(q) && cuts[q] - a + b != nb) q--;
+        if (q > pp) anchors.push_back(Anchor{b, a - b, pp, q});
+    }
+
+    // merged copies, split at the stream ends of A that lie inside them
+    void add_copy(uint64_t b, uint64_t n, uint64_t a)
+    {
+        uint64_t lo = a;
+        for (size_t f = 1; stream_first && f < nstreams; f++) { // (the ends ascend with f)
+            const uint64_t e = cuts[stream_first[f]];
+            if (e <= lo) continue;
+            if (e >= a + n) break;
+            add_piece(b + (lo - a), e - lo, lo);
+            lo = e;
+        }
+        add_piece(b + (lo - a), a + n - lo, lo);
+    }
+
+    void plan()
+    {
+        bool open = false;
+        uint64_t mb = 0, mn = 0, ma = 0;
+        for (size_t k = 0; k < nops; k++) {
+            const cw_delta_op &o = ops[k];
+            if (o.a_off == CW_DELTA_NONE) continue;
+            if (open && mb + mn == o.b_off && ma + mn == o.a_off) { mn += o.len; continue; }
+            if (open) add_copy(mb, mn, ma);
+            open = true; mb = o.b_off; mn = o.len; ma = o.a_off;
+        }
+        if (open) add_copy(mb, mn, ma);
+        uint64_t start = 0;
+        for (size_t i = 0; i < anchors.size(); i++) {
+            const Anchor &a = anchors[i];
+            Window w{start, (long)i, look0};
+            if (in_b(a, a.p) == start) { w.resolved = true; w.s = a.p; w.end = start; } // kept from where the region starts: no window
+            else stats->windows++;
+            wins.push_back(w);
+            start = in_b(a, a.q);
+        }
+        if (start < nb) { wins.push_back(Window{start, -1, look0}); stats->windows++; }
+    }
+
+    // the recipe of A and the payload, once, in front of the first device work
+    int upload()
+    {
+        if (uploaded) return CW_OK;
+        int rc;
+        if ((rc = check_count("nchunks", K)) != CW_OK) return fail(CW_ERR_NOMEM, "cw_store_compose: a source of %zu positions", K);
+        if ((rc = c->meta[0].reserve((2 * K + 2) * 8)) != CW_OK || (rc = c->src[1].reserve(payload_bytes + 16)) != CW_OK ||
+            (rc = c->words.reserve(W_WORDS * 8)) != CW_OK || (rc = c->h_words.reserve(W_WORDS * 8)) != CW_OK)
+            return rc;
+        uint64_t *m = (uint64_t *)c->meta[0].p;
+        const uint64_t count = K;
+        HIP_TRY(hipMemcpyAsync(m, &count, 8, hipMemcpyHostToDevice, s));
+        if (K) HIP_TRY(hipMemcpyAsync(m + 1, refs, K * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(m + 1 + K, cuts.data(), (K + 1) * 8, hipMemcpyHostToDevice, s));
+        if (payload_bytes) HIP_TRY(hipMemcpyAsync(c->src[1].p, payload, payload_bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s)); // (`count` leaves the stack)
+        uploaded = true;
+        return CW_OK;
+    }
+
+    // Queues what fills src[0] with the spans' bytes back to back, and reserves what a chunker over them needs.  lists, in u64 words:
+    // nranges | next | range offsets, lengths, destinations [nranges each] | extents [3 * next] | the spans' ends [n] | `extra` words
+    int materialise(size_t extra, uint64_t **d_ends, uint64_t **d_extra, std::vector<uint64_t> **host)
+    {
+        const size_t n = spans.size();
+        std::vector<uint64_t> roff, rlen, rdst, ext, ends;
+        total = 0;
+        for (const Span &sp : spans) {
+            size_t lo = 0, hi = nops; // the op that holds byte sp.start
+            while (hi - lo > 1) {
+                const size_t mid = lo + (hi - lo) / 2;
+                if (ops[mid].b_off <= sp.start) lo = mid;
+                else hi = mid;
+            }
+            for (size_t k = lo; k < nops && ops[k].b_off < sp.end; k++) {
+                const cw_delta_op &o = ops[k];
+                const uint64_t from = o.b_off > sp.start ? o.b_off : sp.start, to = o.b_off + o.len < sp.end ? o.b_off + o.len : sp.end;
+                if (from >= to) continue;
+                const uint64_t dst = total + (from - sp.start);
+                if (o.a_off != CW_DELTA_NONE) { roff.push_back(o.a_off + (from - o.b_off)); rlen.push_back(to - from); rdst.push_back(dst); }
+                else { ext.push_back(o.payload_off + (from - o.b_off)); ext.push_back(dst); ext.push_back(to - from); }
+            }
+            total += sp.end - sp.start;
+            ends.push_back(total);
+        }
+        nranges = roff.size(); next = ext.size() / 3;
+        const cw::CdcParams cp = params();
+        if (total / cp.min_size > SIZE_MAX - n - 1) return fail(CW_ERR_NOMEM, "cw_store_compose: windows of %llu bytes", (unsigned long long)total);
+        cap = (size_t)(total / cp.min_size) + n + 1;
+        if (check_count("window chunks", cap) != CW_OK || check_count("windows", n) != CW_OK || check_count("ranges", nranges) != CW_OK ||
+            check_count("extents", next) != CW_OK)
+            return fail(CW_ERR_NOMEM, "cw_store_compose: %zu windows of %llu bytes in %zu ranges and %zu extents", n, (unsigned long long)total, nranges, next);
+        lists.clear();
+        lists.push_back(nranges); lists.push_back(next);
+        lists.insert(lists.end(), roff.begin(), roff.end()); lists.insert(lists.end(), rlen.begin(), rlen.end());
+        lists.insert(lists.end(), rdst.begin(), rdst.end()); lists.insert(lists.end(), ext.begin(), ext.end());
+        const size_t at_ends = lists.size();
+        lists.insert(lists.end(), ends.begin(), ends.end());
+        const size_t at_extra = lists.size();
+        lists.resize(at_extra + extra, 0);
+        int rc;
+        if ((rc = upload()) != CW_OK) return rc;
+        if ((rc = c->src[0].reserve(total + 16)) != CW_OK || (rc = c->meta[1].reserve(lists.size() * 8)) != CW_OK ||
+            (rc = c->h_meta[1].reserve(lists.size() * 8)) != CW_OK || (rc = c->off.reserve(cap * 8)) != CW_OK ||
+            (rc = c->first.reserve((n + 1) * 8)) != CW_OK || (rc = c->status[0].reserve((nranges + 1) * 4)) != CW_OK ||
+            (rc = c->h_status[0].reserve((nranges + 1) * 4)) != CW_OK)
+            return rc;
+        uint64_t *d = (uint64_t *)c->meta[1].p;
+        *d_ends = d + at_ends; *d_extra = d + at_extra; *host = &lists;
+        return CW_OK;
+    }
+
+    // behind materialise, once the caller has filled the extra words: the lists go up, the bytes are rebuilt
+    int fill()
+    {
+        uint64_t *d = (uint64_t *)c->meta[1].p, *w = (uint64_t *)c->words.p, *m = (uint64_t *)c->meta[0].p;
+        memcpy(c->h_meta[1].p, lists.data(), lists.size() * 8);
+        HIP_TRY(hipMemsetAsync(w, 0, W_WORDS * 8, s));
+        HIP_TRY(hipMemsetAsync(c->status[0].p, 0, (nranges + 1) * 4, s));
+        HIP_TRY(hipMemcpyAsync(d, c->h_meta[1].p, lists.size() * 8, hipMemcpyHostToDevice, s));
+        int rc;
+        if (nranges && (rc = cw_dev_read_ranges(comp_alg, st->d_store, st->store_bytes, st->d_dir, st->dir_base, st->dir_entries, m + 1, m + 1 + K, m, K,
+                                                d + 2, d + 2 + nranges, d + 2 + 2 * nranges, d, nranges, c->src[0].p, (size_t)total,
+                                                (uint32_t *)c->status[0].p, s)) != CW_OK)
+            return rc;
+        if (next && (rc = cw_dev_scatter_extents(c->src[1].p, payload_bytes, d + 2 + 3 * nranges, d + 1, next, c->src[0].p, (size_t)total, w + W_RESYNC, s)) != CW_OK)
+            return rc;
+        return CW_OK;
+    }
+
+    // behind the synchronise that brought statuses and words down
+    int check_filled()
+    {
+        const uint64_t *h = (const uint64_t *)c->h_words.p;
+        const uint32_t *got = (const uint32_t *)c->h_status[0].p;
+        if (next && h[W_RESYNC]) return fail(CW_ERR_STATE, "cw_store_compose: extent %llu of the new bytes was refused", (unsigned long long)h[W_RESYNC + 2]);
+        for (size_t r = 0; r < nranges; r++)
+            if (got[r]) {
+                unread = true;
+                return fail(CW_ERR_BAD_ARG, "cw_store_compose: %llu bytes of the source at offset %llu were not read: status %u (a position there does not restore)",
+                            (unsigned long long)lists[2 + nranges + r], (unsigned long long)lists[2 + r], got[r]);
+            }
+        return CW_OK;
+    }
+
+    cw::CdcParams params() const { cw::CdcParams cp; (void)cdc_params(p, &cp); return cp; }
+
+    // one round over the unresolved windows; the windows' state afterwards is the model's (tests/compose_model.py)
+    int round()
+    {
+        spans.clear();
+        for (Window &w : wins) {
+            w.ran = false;
+            if (w.resolved) continue;
+            if (w.anchor < 0) { w.tried = nb; w.exhausted = false; }
+            else {
+                const Anchor &a = anchors[(size_t)w.anchor];
+                const uint64_t from = (a.b > w.start ? a.b : w.start) - a.b + (a.b + a.d), target = w.look > UINT64_MAX - from ? UINT64_MAX : from + w.look;
+                size_t e = lower(cuts, a.p, a.q + 1, target);
+                if (e > a.q) e = a.q;
+                w.tried = in_b(a, e); w.exhausted = e == a.q;
+            }
+            w.ran = true; w.slot = spans.size();
+            spans.push_back(Span{w.start, w.tried});
+        }
+        const size_t n = spans.size();
+        uint64_t *d_ends, *d_win;
+        std::vector<uint64_t> *l;
+        int rc = materialise(5 * n, &d_ends, &d_win, &l);
+        if (rc != CW_OK) return rc;
+        uint64_t *spec = l->data() + (l->size() - 5 * n), at = 0;
+        for (Window &w : wins) {
+            if (!w.ran) continue;
+            w.at = at;
+            uint64_t *q = spec + 5 * w.slot;
+            if (w.anchor < 0) { q[0] = q[1] = q[2] = q[3] = 0; q[4] = 1; }
+            else {
+                const Anchor &a = anchors[(size_t)w.anchor];
+                q[0] = (a.b > w.start ? a.b : w.start) - w.start + at; q[1] = a.d + w.start - at; q[2] = a.p; q[3] = a.q - a.p; q[4] = w.tried == nb;
+            }
+            at += w.tried - w.start;
+        }
+        if ((rc = c->rec_ref.reserve(4 * n * 8)) != CW_OK || (rc = c->h_meta[0].reserve((5 * n + 1) * 8)) != CW_OK || (rc = fill()) != CW_OK) return rc;
+        uint64_t *w = (uint64_t *)c->words.p, *h = (uint64_t *)c->h_words.p, *m = (uint64_t *)c->meta[0].p;
+        const StreamList sl{d_ends, n, (uint64_t *)c->first.p, w + W_ENDS};
+        const cw::CdcParams cp = params();
+        if ((rc = cdc_streams_args(cp, c->src[0].p, (size_t)total, sl, (uint64_t *)c->off.p, cap, w + W_NCHUNKS)) != CW_OK) return fail(CW_ERR_STATE, "cw_store_compose: the chunker refused the windows");
+        if ((rc = dev_cdc_streams(cp, (const uint8_t *)c->src[0].p, (size_t)total, sl, (uint64_t *)c->off.p, cap, w + W_NCHUNKS, s)) != CW_OK) return rc;
+        if ((rc = cw_dev_cdc_resync_windows((uint64_t *)c->off.p, w + W_NCHUNKS, cap - 1, (uint64_t *)c->first.p, (const cw_resync_window *)d_win, n,
+                                            m + 1 + K, K + 1, (uint64_t *)c->rec_ref.p, s)) != CW_OK)
+            return rc;
+        HIP_TRY(hipMemcpyAsync(c->h_meta[0].p, c->rec_ref.p, 4 * n * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync((uint64_t *)c->h_meta[0].p + 4 * n, c->first.p, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(c->h_status[0].p, c->status[0].p, (nranges + 1) * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(h, w, W_WORDS * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if ((rc = check_filled()) != CW_OK) return rc;
+        if (h[W_ENDS]) return fail(CW_ERR_STATE, "cw_store_compose: the windows' ends were refused");
+        stats->rounds++;
+
+        const uint64_t *res = (const uint64_t *)c->h_meta[0].p, *first = res + 4 * n;
+        bool settled = true; // every window in front of this one is resolved
+        for (size_t i = 0; i < wins.size();) {
+            Window &v = wins[i++];
+            if (v.discard) { v.discard = false; settled = false; continue; }
+            if (!v.ran) { settled = settled && v.resolved; continue; }
+            const uint64_t *r = res + 4 * v.slot;
+            if (v.anchor < 0) { v.resolved = true; v.end = nb; v.t = first[v.slot + 1] - first[v.slot]; } // kept whole
+            else if (r[0] == 0) {
+                const Anchor &a = anchors[(size_t)v.anchor];
+                if (r[2] < a.p || r[2] >= a.q) return fail(CW_ERR_STATE, "cw_store_compose: a landing at position %llu outside [%zu, %zu)", (unsigned long long)r[2], a.p, a.q);
+                v.resolved = true; v.t = r[1]; v.s = (size_t)r[2]; v.end = r[3] - v.at + v.start;
+            } else if (!v.exhausted) {
+                v.look = v.look > UINT64_MAX / 2 ? UINT64_MAX : v.look * 2;
+                settled = false;
+            } else if (!settled) {
+                settled = false; // its start is not known to be a true cut yet: it waits
+            } else { // the anchor is dropped: the window merges into the next one
+                stats->merged_windows++;
+                const uint64_t start = v.start;
+                if (i == wins.size()) wins.push_back(Window{start, -1, look0});
+                Window &nxt = wins[i];
+                nxt.start = start; nxt.resolved = false; nxt.discard = nxt.ran;
+                wins.erase(wins.begin() + (long)(i - 1));
+                i--;
+            }
+        }
+        return CW_OK;
+    }
+
+    // the commit's hooks: the statuses and the stream index ride on the piece's one synchronise
+    static int after_cdc(void *self, hipStream_t s)
+    {
+        Compose &t = *static_cast<Compose *>(self);
+        const size_t n = t.spans.size();
+        HIP_TRY(hipMemcpyAsync(t.c->h_status[0].p, t.c->status[0].p, (t.nranges + 1) * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(t.c->h_meta[0].p, t.c->first.p, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync((uint64_t *)t.c->h_words.p + W_RESYNC, (uint64_t *)t.c->words.p + W_RESYNC, 4 * 8, hipMemcpyDeviceToHost, s));
+        return CW_OK;
+    }
+    static int admit(void *self, size_t k, const uint64_t *hc)
+    {
+        Compose &t = *static_cast<Compose *>(self);
+        int rc = t.check_filled();
+        if (rc != CW_OK) return rc;
+        const uint64_t *first = (const uint64_t *)t.c->h_meta[0].p;
+        size_t e = 0;
+        for (const Window &w : t.wins) {
+            if (w.end <= w.start) continue;
+            if (first[e + 1] - first[e] != w.t)
+                return fail(CW_ERR_STATE, "cw_store_compose: the extent at %llu chunked into %llu chunks, its round found %llu", (unsigned long long)w.start,
+                            (unsigned long long)(first[e + 1] - first[e]), (unsigned long long)w.t);
+            e++;
+        }
+        if (k != t.stats->rebuilt_chunks) return fail(CW_ERR_STATE, "cw_store_compose: %zu rebuilt chunks, the rounds found %llu", k, (unsigned long long)t.stats->rebuilt_chunks);
+        if (k + t.stats->kept_positions + 1 > t.max_out) return fail(CW_ERR_STATE, "cw_store_compose: %llu chunks do not fit max_out %zu", (unsigned long long)(k + t.stats->kept_positions), t.max_out);
+        Admission adm{t.st, t.base};
+        return admit_piece(&adm, k, hc);
+    }
+
+    int commit(uint64_t *out_refs, uint64_t *out_offsets, size_t *out_n)
+    {
+        spans.clear();
+        stats->rebuilt_chunks = stats->rebuilt_bytes = stats->kept_positions = 0;
+        for (const Window &w : wins) {
+            if (w.end > w.start) { spans.push_back(Span{w.start, w.end}); stats->rebuilt_chunks += w.t; stats->rebuilt_bytes += w.end - w.start; }
+            if (w.anchor >= 0) stats->kept_positions += anchors[(size_t)w.anchor].q - w.s;
+        }
+        const size_t n = spans.size();
+        uint64_t *h = (uint64_t *)c->h_words.p;
+        const uint64_t *h_ref = nullptr, *h_off = nullptr, *first = nullptr;
+        if (n) {
+            uint64_t *d_ends, *d_extra;
+            std::vector<uint64_t> *l;
+            int rc = materialise(0, &d_ends, &d_extra, &l);
+            if (rc != CW_OK) return rc;
+            slots_bytes = cw_chunk_slots_bytes(comp_alg, (size_t)total, cap - 1);
+            if ((rc = c->dig.reserve(cap * 64)) != CW_OK || (rc = c->ref.reserve(cap * 8)) != CW_OK || (rc = c->new_idx.reserve(cap * 4)) != CW_OK ||
+                (rc = c->sizes.reserve(cap * 4)) != CW_OK || (rc = c->slots.reserve(slots_bytes)) != CW_OK || (rc = c->h_meta[0].reserve((n + 1 + 2 * cap) * 8)) != CW_OK ||
+                (rc = fill()) != CW_OK)
+                return rc;
+            uint64_t *w = (uint64_t *)c->words.p;
+            bool inserted = false;
+            PieceAdmit hook{st->d_used, w + W_VERDICT, w + W_COUNTS, h + W_COUNTS, admit, this, &inserted, after_cdc};
+            const StreamList sl{d_ends, n, (uint64_t *)c->first.p, w + W_ENDS};
+            size_t k = 0;
+            rc = dev_cdc_dedupe_compress(x, p, comp_alg, c->src[0].p, (size_t)total, 1, base, (uint64_t *)c->off.p, cap, w + W_NCHUNKS, c->dig.p,
+                                         (uint64_t *)c->ref.p, (uint32_t *)c->new_idx.p, w + W_NNEW, c->slots.p, slots_bytes, (uint32_t *)c->sizes.p, &k, s,
+                                         &hook, &sl);
+            if (rc == CW_ERR_NOMEM && inserted) return fail(CW_ERR_STATE, "cw_store_compose: device memory ran out behind the admitted extents");
+            if (rc == CW_ERR_BAD_ARG && !unread) return fail(CW_ERR_STATE, "cw_store_compose: the extents' ends were refused");
+            if (rc != CW_OK) return rc;
+            rc = cw_dev_store_chunks(comp_alg, c->src[0].p, (size_t)total, (uint64_t *)c->off.p, w + W_NCHUNKS, cap - 1, (uint32_t *)c->new_idx.p, w + W_NNEW,
+                                     c->slots.p, (uint32_t *)c->sizes.p, base, st->d_store, st->store_bytes, st->d_used, st->d_dir, st->dir_base,
+                                     st->dir_entries, w + W_RESULT, s);
+            if (rc != CW_OK) return rc == CW_ERR_NOMEM ? fail(CW_ERR_STATE, "cw_store_compose: no scratch behind the admitted extents") : rc;
+            uint64_t *down = (uint64_t *)c->h_meta[0].p + n + 1;
+            HIP_TRY(hipMemcpyAsync(h + W_NNEW, w + W_NNEW, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, s)); // (W_NNEW, W_RESULT[2])
+            if (k) HIP_TRY(hipMemcpyAsync(down, c->ref.p, k * 8, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(down + cap, c->off.p, (k + 1) * 8, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            if (h[W_RESULT]) return fail(CW_ERR_STATE, "cw_store_compose: the admitted extents were not stored (verdict %llu)", (unsigned long long)h[W_RESULT]);
+            stats->new_chunks = h[W_NNEW]; stats->stored_bytes = h[W_RESULT + 1];
+            first = (const uint64_t *)c->h_meta[0].p; h_ref = down; h_off = down + cap;
+        } else if (stats->kept_positions + 1 > max_out) {
+            return fail(CW_ERR_STATE, "cw_store_compose: %llu chunks do not fit max_out %zu", (unsigned long long)stats->kept_positions, max_out);
+        }
+        // the splice, window by window: its extent's chunks, then the kept positions shifted into B
+        size_t at = 0, e = 0;
+        uint64_t lay = 0; // where the extent lies in src[0]
+        out_offsets[0] = 0;
+        for (const Window &w : wins) {
+            if (out_offsets[at] != w.start) return fail(CW_ERR_STATE, "cw_store_compose: the recipe reaches %llu where a window starts at %llu", (unsigned long long)out_offsets[at], (unsigned long long)w.start);
+            if (w.end > w.start) {
+                for (uint64_t g = first[e]; g < first[e + 1]; g++, at++) { out_refs[at] = h_ref[g]; out_offsets[at + 1] = h_off[g + 1] - lay + w.start; }
+                lay += w.end - w.start; e++;
+            }
+            if (w.anchor < 0) continue;
+            const Anchor &a = anchors[(size_t)w.anchor];
+            for (size_t i = w.s; i < a.q; i++, at++) { out_refs[at] = refs[i]; out_offsets[at + 1] = in_b(a, i + 1); }
+        }
+        if (out_offsets[at] != nb) return fail(CW_ERR_STATE, "cw_store_compose: the recipe ends at %llu of %llu bytes", (unsigned long long)out_offsets[at], (unsigned long long)nb);
+        *out_n = at;
+        return CW_OK;
+    }
+};
+
 } // namespace
 
 extern "C" {
@@ -765,6 +1155,119 @@ int cw_store_patch(cw_dedupe_t *x, const cw_cdc_params *p, int comp_alg, const c
     *out_nchunks = at + rest;
     stats->first_position = t.j; stats->resume_position = t.resume; stats->reused_positions = t.j + rest;
     return CW_OK;
+}
+
+static_assert(sizeof(cw_resync_window) == 40 && sizeof(cw_compose_stats) == 64, "five and eight u64 words");
+
+int cw_dev_cdc_resync_windows(const uint64_t *d_new_offsets, const uint64_t *d_new_count, size_t max_new, const uint64_t *d_stream_first,
+                              const cw_resync_window *d_win, size_t nwin, const uint64_t *d_old_offsets, size_t max_old, uint64_t *d_result,
+                              void *stream)
+{
+    int rc = check_count("max_new", max_new);
+    if (rc != CW_OK || (rc = check_count("max_old", max_old)) != CW_OK || (rc = check_count("nwin", nwin)) != CW_OK) return rc;
+    if (!d_new_offsets) return fail(CW_ERR_BAD_ARG, "NULL d_new_offsets");
+    if (!d_new_count) return fail(CW_ERR_BAD_ARG, "NULL d_new_count");
+    if (!d_stream_first) return fail(CW_ERR_BAD_ARG, "NULL d_stream_first");
+    if (!d_win) return fail(CW_ERR_BAD_ARG, "NULL d_win");
+    if (!d_old_offsets && max_old) return fail(CW_ERR_BAD_ARG, "NULL d_old_offsets");
+    if (!d_result) return fail(CW_ERR_BAD_ARG, "NULL d_result");
+    if (((uintptr_t)d_new_offsets | (uintptr_t)d_new_count | (uintptr_t)d_stream_first | (uintptr_t)d_win | (uintptr_t)d_old_offsets | (uintptr_t)d_result) & 7)
+        return fail(CW_ERR_BAD_ARG, "a pointer is not 8-byte aligned");
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    return launched_nomem(cw::cdc_resync_windows_launch(d_new_offsets, d_new_count, max_new, d_stream_first, d_win, nwin, d_old_offsets, max_old, d_result,
+                                                        (hipStream_t)stream),
+                          "cdc resync windows launch");
+}
+
+int cw_dev_scatter_extents(const void *d_src, size_t src_bytes, const uint64_t *d_ext, const uint64_t *d_n, size_t max_n, void *d_dst, size_t dst_bytes,
+                           uint64_t *d_result, void *stream)
+{
+    int rc = check_count("max_n", max_n);
+    if (rc != CW_OK) return rc;
+    const char *null = !d_n ? "d_n" : !d_result ? "d_result" : max_n && !d_ext ? "d_ext" : src_bytes && !d_src ? "d_src" : dst_bytes && !d_dst ? "d_dst" : NULL;
+    if (null) return fail(CW_ERR_BAD_ARG, "NULL pointer: %s", null);
+    if (((uintptr_t)d_ext | (uintptr_t)d_n | (uintptr_t)d_result) & 7) return fail(CW_ERR_BAD_ARG, "d_ext, d_n or d_result is not 8-byte aligned");
+    const uintptr_t a = (uintptr_t)d_src, b = (uintptr_t)d_dst;
+    if (src_bytes && dst_bytes && a < b + dst_bytes && b < a + src_bytes) return fail(CW_ERR_BAD_ARG, "d_dst overlaps d_src");
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    ProfScope prof(PROF_CODEC, (hipStream_t)stream);
+    return launched(cw::scatter_extents_launch((const uint8_t *)d_src, src_bytes, d_ext, d_n, max_n, (uint8_t *)d_dst, dst_bytes, d_result,
+                                               (hipStream_t)stream),
+                    "scatter extents launch");
+}
+
+int cw_store_compose(cw_dedupe_t *x, const cw_cdc_params *p, int comp_alg, const cw_store *st, const uint64_t *refs, const uint64_t *offsets,
+                     size_t nchunks, const uint64_t *stream_first, size_t nstreams, const cw_delta_op *ops, size_t nops, const void *payload,
+                     size_t payload_bytes, uint64_t base, size_t lookahead, uint64_t *out_refs, uint64_t *out_offsets, size_t max_out,
+                     size_t *out_nchunks, cw_compose_stats *stats)
+{
+    if (out_nchunks) *out_nchunks = 0;
+    cw_compose_stats local;
+    if (!stats) stats = &local;
+    memset(stats, 0, sizeof *stats);
+    cw::CdcParams cp;
+    int rc = cdc_params(p, &cp);
+    if (rc != CW_OK || (rc = check_codec(comp_alg)) != CW_OK) return rc;
+    if (!x) return fail(CW_ERR_BAD_ARG, "NULL dedupe index");
+    if (!offsets || (nchunks && !refs)) return fail(CW_ERR_BAD_ARG, "NULL recipe (refs / offsets)");
+    if (nops && !ops) return fail(CW_ERR_BAD_ARG, "NULL ops with nops %zu", nops);
+    if (!out_refs || !out_offsets || !out_nchunks) return fail(CW_ERR_BAD_ARG, "NULL out_refs / out_offsets / out_nchunks");
+    if (payload_bytes && !payload) return fail(CW_ERR_BAD_ARG, "NULL payload with payload_bytes %zu", payload_bytes);
+    if (cp.max_size > CW_MAX_BLOCK_BYTES) return fail(CW_ERR_BAD_ARG, "max_size %u > %u: such a chunk cannot be stored", cp.max_size, CW_MAX_BLOCK_BYTES);
+    if (offsets[nchunks] < offsets[0]) return fail(CW_ERR_BAD_ARG, "offsets end below their start");
+    const uint64_t na = offsets[nchunks] - offsets[0];
+    if (stream_first) {
+        if (stream_first[0] != 0) return fail(CW_ERR_BAD_ARG, "stream_first starts at %llu, not 0", (unsigned long long)stream_first[0]);
+        for (size_t f = 0; f < nstreams; f++)
+            if (stream_first[f + 1] < stream_first[f]) return fail(CW_ERR_BAD_ARG, "stream_first decreases at stream %zu", f);
+        if (stream_first[nstreams] != nchunks)
+            return fail(CW_ERR_BAD_ARG, "stream_first ends at %llu, not at nchunks %zu", (unsigned long long)stream_first[nstreams], nchunks);
+    }
+    // the op list, by cw_dev_apply_delta's rule over A's bytes and the payload
+    uint64_t nb = 0;
+    bool copies = false;
+    for (size_t k = 0; k < nops; k++) {
+        const cw_delta_op &o = ops[k];
+        const bool copy = o.a_off != CW_DELTA_NONE, fresh = o.payload_off != CW_DELTA_NONE;
+        const uint64_t room = copy ? na : (uint64_t)payload_bytes, from = copy ? o.a_off : o.payload_off;
+        const char *why = o.b_off != nb ? "does not start where the one before ends" : o.len == 0 ? "has len 0" : o.b_off + o.len < o.b_off ? "wraps"
+                        : copy == fresh ? "names both sources or neither" : o.len > room || from > room - o.len ? (copy ? "leaves the source's bytes" : "leaves the payload") : NULL;
+        if (why) return fail(CW_ERR_BAD_ARG, "op %zu of %zu %s", k, nops, why);
+        nb = o.b_off + o.len;
+        copies = copies || copy;
+    }
+    if (max_out < nb / cp.min_size + 2)
+        return fail(CW_ERR_BAD_ARG, "max_out %zu < composed bytes / min_size + 2 = %llu", max_out, (unsigned long long)(nb / cp.min_size + 2));
+    if ((rc = check_store(st)) != CW_OK) return rc;
+    if (base > UINT64_MAX - (nb / cp.min_size + 1)) return fail(CW_ERR_BAD_ARG, "base + composed bytes / min_size + 1 wraps");
+    if (copies) // (the plan searches the whole list)
+        for (size_t i = 0; i < nchunks; i++)
+            if (offsets[i + 1] < offsets[i]) return fail(CW_ERR_BAD_ARG, "offsets decrease at position %zu", i);
+    uint64_t look = lookahead ? lookahead : (uint64_t)4 * cp.max_size;
+    if (look < (uint64_t)2 * cp.max_size) look = (uint64_t)2 * cp.max_size;
+    Compose t{x, p, comp_alg, st, refs, nchunks, stream_first, stream_first ? nstreams : 1, ops, nops, (const uint8_t *)payload, payload_bytes, base, nb, look, max_out, stats};
+    out_offsets[0] = 0;
+    if (nops == 0) return CW_OK; // the empty stream: no device
+    hipStream_t s_h2d, s_d2h;
+    if ((rc = ctx_store(&t.c, &t.s, &s_h2d, &s_d2h)) != CW_OK) return rc;
+    t.cuts.resize(nchunks + 1);
+    for (size_t i = 0; i <= nchunks; i++) t.cuts[i] = offsets[i] - offsets[0];
+    t.plan();
+    auto run = [&]() -> int {
+        for (;;) {
+            bool open = false;
+            for (const Compose::Window &w : t.wins) open = open || !w.resolved;
+            if (!open) break;
+            if (int rc = t.round()) return rc;
+        }
+        size_t k = 0;
+        if (int rc = t.commit(out_refs, out_offsets, &k)) return rc;
+        *out_nchunks = k;
+        return CW_OK;
+    };
+    rc = run();
+    if (rc != CW_OK) (void)hipStreamSynchronize(t.s); // nothing of the call is in flight when it returns
+    return rc;
 }
 
 // The whole directory through cw_dev_store_verify, window by window: the work buffer is the context's first

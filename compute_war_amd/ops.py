@@ -927,6 +927,70 @@ def dev_apply_delta(d_old: int, old_bytes: int, d_payload: int, payload_bytes: i
                                    dst_bytes, d_result, stream))
 
 
+# ---- compose a stream from stored ranges and new bytes (cw_store_compose) --------------------------------
+class ResyncWindow(C.Structure):
+    """cw_resync_window: a window's cuts at or behind ``new_from`` are looked up, shifted by ``shift`` (mod 2^64), among the old cuts
+    [old_first, old_first + old_count); ``final``: the window's last cut counts as well."""
+    _fields_ = [(k, C.c_uint64) for k in ("new_from", "shift", "old_first", "old_count", "final")]
+
+
+RESYNC_WINDOW_DTYPE = np.dtype([(k, "<u8") for k, _ in ResyncWindow._fields_])  # cw_resync_window as a numpy record
+
+
+def dev_cdc_resync_windows(d_new_offsets: int, d_new_count: int, max_new: int, d_stream_first: int, d_win: int, nwin: int, d_old_offsets: int,
+                           max_old: int, d_result: int, stream: int = 0) -> None:
+    """``dev_cdc_resync`` for the nwin windows one ``dev_cdc_streams`` call chunked: d_result[4 * w ..] = (0, t, s, x) for the smallest
+    t >= 1 whose cut x of window w lies at or behind the window's new_from with x + shift an old cut of the window's own range (s: its
+    index in d_old_offsets), or (1, 0, 0, 0).  A window's last cut counts only when it is final.  No count changes.  Not synchronised."""
+    check(lib().cw_dev_cdc_resync_windows(d_new_offsets, d_new_count, max_new, d_stream_first, d_win, nwin, d_old_offsets or None, max_old, d_result,
+                                          stream))
+
+
+def dev_scatter_extents(d_src: int, src_bytes: int, d_ext: int, d_n: int, max_n: int, d_dst: int, dst_bytes: int, d_result: int,
+                        stream: int = 0) -> None:
+    """Copies min(*d_n, max_n) extents (src_off, dst_off, len: three uint64 words each) from d_src to d_dst.  d_result[0..4) = verdict
+    (1: an extent is empty, leaves a buffer, wraps or starts in front of the end of the one before; nothing is written then), the end
+    of the last extent, the lowest bad extent or DeltaOp.NONE, the extent count.  Not synchronised."""
+    check(lib().cw_dev_scatter_extents(d_src or None, src_bytes, d_ext or None, d_n, max_n, d_dst or None, dst_bytes, d_result, stream))
+
+
+class ComposeStats(C.Structure):
+    """cw_compose_stats: one store_compose call's windows, rounds and merges, what it rebuilt (bytes, chunks, the new chunks among them
+    and their stored bytes) and the positions it kept."""
+    _fields_ = [(k, C.c_uint64) for k in ("windows", "rounds", "merged_windows", "rebuilt_bytes", "rebuilt_chunks", "new_chunks", "stored_bytes",
+                                          "kept_positions")]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+COMPOSE_DTYPE = np.dtype([(k, "<u8") for k, _ in ComposeStats._fields_])  # cw_compose_stats as a numpy record
+
+
+def store_compose(index: "DedupeIndex", params: "CdcParams", comp_alg, store: Store, refs, offsets, ops, payload, base: int, lookahead: int = 0,
+                  stream_first=None):
+    """cw_store_compose: the stream the ``ops`` (DELTA_OP_DTYPE records, tiling it from 0) build from the bytes of the stored source
+    (refs, offsets; with ``stream_first`` the concatenation of several stored streams) and ``payload``.  Returns (refs, offsets, stats as
+    a dict) of the new stream; raises CwError (-5: not admitted, -2: a refused argument or a source range that does not restore) with
+    index, store and directory unchanged."""
+    refs, offsets = np.ascontiguousarray(refs, np.uint64), np.ascontiguousarray(offsets, np.uint64)
+    if len(offsets) != len(refs) + 1:
+        raise ValueError(f"{len(refs)} refs need {len(refs) + 1} offsets, not {len(offsets)}")
+    ops = np.ascontiguousarray(ops, dtype=DELTA_OP_DTYPE).reshape(-1)
+    pay = _np_u8(payload)
+    first = None if stream_first is None else np.ascontiguousarray(stream_first, np.uint64)
+    total = int(ops["len"].sum(dtype=np.uint64)) if len(ops) else 0
+    cap = params.max_offsets(total)
+    out_refs, out_offs = np.zeros(cap, np.uint64), np.zeros(cap, np.uint64)
+    k, stats = C.c_size_t(0), ComposeStats()
+    check(lib().cw_store_compose(index._x(), C.byref(params), _comp_id(comp_alg), C.byref(store), refs.ctypes.data if len(refs) else None,
+                                 offsets.ctypes.data, len(refs), None if first is None else first.ctypes.data, 0 if first is None else len(first) - 1,
+                                 ops.ctypes.data if len(ops) else None, len(ops), pay.ctypes.data if pay.size else None, pay.size, base, lookahead,
+                                 out_refs.ctypes.data, out_offs.ctypes.data, cap, C.byref(k), C.byref(stats)))
+    k = int(k.value)
+    return out_refs[:k].copy(), out_offs[:k + 1].copy(), stats.as_dict()
+
+
 def store_restore(comp_alg, store: Store, refs, offsets, dst: int, dst_bytes: int):
     """cw_store_restore into the host memory at address ``dst``: the status of every position (u32 array)."""
     refs, offsets = np.ascontiguousarray(refs, np.uint64), np.ascontiguousarray(offsets, np.uint64)

@@ -13,7 +13,7 @@ from ._lib import CwError, lib
 from .ops import (ACCOUNT_DTYPE, DELTA_OP_DTYPE, CdcParams, ChunkLoc, DedupeIndex, DeltaOp, Store, _comp_id, _hash_id, _np_u8, chunk_slots_bytes,
                   dev_apply_delta, dev_hash_chunks, dev_read_ranges, dev_recipe_diff, dev_restore_chunks, dev_store_account, dev_store_chunks, dev_store_compact, dev_store_export_chunks, dev_store_import_chunks, dev_store_mark,
                   dev_store_renumber, dev_store_replace_chunks, dev_translate_refs, device_count, digest_bytes, init, store_ingest,
-                  store_ingest_streams, store_patch, store_restore, store_scrub)
+                  store_compose, store_ingest_streams, store_patch, store_restore, store_scrub)
 
 
 class Recipe:
@@ -254,9 +254,12 @@ class ChunkStore:
     last streamed ingest's statistics.  ``patch`` edits a stored stream in place -- ``write``, ``append``, ``truncate`` and
     ``patch_many`` are thin forms of it -- and ``last_patch`` holds the last edit's statistics (cw_patch_stats as a dict).  ``diff``
     says what changed between two recipes from the recipes alone, and ``delta`` packs the new version's new bytes with those ops for
-    someone who holds the old version as plain bytes (``apply_delta``)."""
+    someone who holds the old version as plain bytes (``apply_delta``).  ``compose`` builds a new stored stream from ranges of stored
+    streams and new bytes in one call -- ``apply_delta`` (a ``Delta`` applied inside the store), ``concat`` and ``edit`` (``patch_many``
+    in one call) are thin forms of it -- and ``last_compose`` holds its statistics (cw_compose_stats as a dict)."""
     last_stats = None
     last_patch = None
+    last_compose = None
 
     def __init__(self, index: DedupeIndex, comp_alg, params: CdcParams, store_bytes: int, dir_entries: int, dir_base: int = 0):
         import torch
@@ -523,6 +526,90 @@ class ChunkStore:
         for o, r, d in reversed(edits):
             recipe = self.patch(recipe, o, r, d)
         return recipe
+
+    @staticmethod
+    def _sorted_edits(recipe: Recipe, edits) -> list:
+        """``patch_many``'s edits in ascending order, or its ValueError."""
+        edits = sorted(((int(o), int(r), d) for o, r, d in edits), key=lambda e: (e[0], e[1]))
+        for (o, r, _), (o2, _, _) in zip(edits, edits[1:]):
+            if o + r > o2 or (o == o2 and r == 0):
+                raise ValueError(f"edits overlap: ({o}, {r}) and the one at {o2}")
+        if any(o < 0 or r < 0 or o + r > recipe.nbytes for o, r, _ in edits):
+            raise ValueError(f"an edit leaves the stream's {recipe.nbytes} bytes")
+        return edits
+
+    def _compose_call(self, sources, ops, payload, lookahead: int) -> Recipe:
+        """One ``store_compose`` over the recipes ``sources`` joined as ``restore_many_stream`` joins them, with their stream index."""
+        if device_count() <= 0:
+            init()  # (raises: no device)
+        import torch
+        refs = np.concatenate([r.refs for r in sources]) if sources else np.zeros(0, np.uint64)
+        starts = np.concatenate([np.zeros(1, np.uint64), np.cumsum([r.nbytes for r in sources], dtype=np.uint64)])
+        offs = np.concatenate([np.zeros(1, np.uint64)] + [r.offsets[1:] - r.offsets[0] + starts[i] for i, r in enumerate(sources)])
+        first = np.concatenate([np.zeros(1, np.uint64), np.cumsum([len(r.refs) for r in sources], dtype=np.uint64)])
+        torch.cuda.synchronize()  # (the store was written on torch's stream)
+        out_refs, out_offs, stats = store_compose(self.index, self.params, self.comp_alg, self._triple(), refs, offs, ops, payload, self.base, lookahead,
+                                                  first if len(sources) > 1 else None)
+        self.base += stats["rebuilt_chunks"]
+        self.last_compose = stats
+        return Recipe(out_refs, out_offs)
+
+    def compose(self, parts, lookahead: int = 0) -> Recipe:
+        """The recipe of the stream that ``parts`` build, back to back: a part is ``(recipe, offset, length)`` -- bytes [offset, offset +
+        length) of a stream this store holds -- or a bytes-like of new bytes (cw_store_compose).  Nothing is
+        restored or re-ingested: chunks that a copied range holds whole keep their refs, only what lies between them is read back,
+        re-chunked and stored, yet recipe, store and index are what ingesting the composed bytes leaves.  ``base`` advances by the rebuilt
+        chunks and ``last_compose`` holds the call's statistics (cw_compose_stats as a dict).  Raises CwError (-5) when the index, the
+        directory, the store or the device's memory cannot take the rebuilt chunks and CwError (-2) when a source range does not
+        restore; store, index and ``base`` are then unchanged."""
+        sources, where, ops, payload, b = [], {}, [], [], 0
+        for part in parts:
+            if isinstance(part, tuple) and len(part) == 3 and isinstance(part[0], Recipe):
+                r, off, n = part[0], int(part[1]), int(part[2])
+                if off < 0 or n < 0 or off + n > r.nbytes:
+                    raise ValueError(f"a part ({off}, {n}) leaves its stream's {r.nbytes} bytes")
+                if id(r) not in where:
+                    where[id(r)] = sum(s.nbytes for s in sources)
+                    sources.append(r)
+                if n:
+                    ops.append((b, n, where[id(r)] + off, DeltaOp.NONE))
+                    b += n
+            else:
+                a = _np_u8(part)
+                if a.size:
+                    ops.append((b, a.size, DeltaOp.NONE, sum(p.size for p in payload)))
+                    payload.append(a)
+                    b += a.size
+        return self._compose_call(sources, np.array(ops, dtype=DELTA_OP_DTYPE), np.concatenate(payload) if payload else np.zeros(0, np.uint8), lookahead)
+
+    def apply_delta(self, old: Recipe, delta: Delta) -> Recipe:
+        """Version B inside the store from version A's recipe and a ``Delta`` made against A: ``compose`` with the delta's ops and
+        payload.  Nothing of the delta is trusted: raises CwError (-2) when it was made against another size than ``old.nbytes``, when
+        its ops build another size than ``delta.new_bytes``, or naming the first malformed op."""
+        if device_count() <= 0:
+            init()  # (raises: no device)
+        if delta.old_bytes != old.nbytes:
+            raise CwError(-2, f"delta: made against an old stream of {delta.old_bytes} bytes, not {old.nbytes}")
+        total = int(delta.ops["len"].sum(dtype=np.uint64)) if len(delta.ops) else 0
+        if total != delta.new_bytes:
+            raise CwError(-2, f"delta: the ops build {total} bytes, the delta says {delta.new_bytes}")
+        new = self._compose_call([old], delta.ops, delta.payload, 0)
+        if new.nbytes != delta.new_bytes:
+            raise CwError(-4, f"delta: composed {new.nbytes} bytes, the delta says {delta.new_bytes}")
+        return new
+
+    def concat(self, recipes) -> Recipe:
+        """The stored streams back to back as one stream: ``compose`` of their whole ranges."""
+        return self.compose([(r, 0, r.nbytes) for r in recipes])
+
+    def edit(self, recipe: Recipe, edits) -> Recipe:
+        """``patch_many`` in one ``compose``: the same edits ``(offset, remove, data)``, the same refusals and the same result, without a
+        device call and two synchronises per edit."""
+        parts, at = [], 0
+        for o, r, d in self._sorted_edits(recipe, edits):
+            parts += [(recipe, at, o - at), d]
+            at = o + r
+        return self.compose(parts + [(recipe, at, recipe.nbytes - at)])
 
     def _diff_call(self, old: Recipe, new: Recipe, max_ops: int, ranges: bool):
         """One queued ``dev_recipe_diff`` of the two recipes with room for max_ops ops: the device buffers as a dict.  The caller

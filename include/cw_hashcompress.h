@@ -926,6 +926,78 @@ int cw_dev_apply_delta(const void *d_old, size_t old_bytes, const void *d_payloa
                        const cw_delta_op *d_ops, const uint64_t *d_nops, size_t max_ops,
                        void *d_dst, size_t dst_bytes, uint64_t *d_result /* [4] */, void *stream);
 
+/* ---- compose a stored stream from stored ranges and new bytes --------------------------------------------
+ * cw_dev_cdc_resync for many windows chunked by one cw_dev_cdc_streams call.  N = min(*d_new_count, max_new) is read on the device;
+ * window w's cuts are d_new_offsets[first[w] .. first[w+1]], first = d_stream_first[0 .. nwin].  For every window the call finds the
+ * smallest t >= 1 whose cut x = d_new_offsets[first[w] + t] has x >= new_from and x + shift (mod 2^64) equal to one of the old cuts
+ * d_old_offsets[old_first .. old_first + old_count) (ascending; the range is clamped into [0, max_old)).  The window's last cut, which
+ * the window's end forced, is not tested unless `final` is set.  d_result[4 * w ..] = {0, t, s, x} with s the index of the old cut in
+ * d_old_offsets, or {1, 0, 0, 0}.  A cut never matches through another window's old range.  No count changes and nothing else is
+ * written; no load leaves d_new_offsets[0 .. max_new], d_stream_first[0 .. nwin], d_win[0 .. nwin) or d_old_offsets[0 .. max_old),
+ * whatever they hold.  nwin == 0 is a no-op.  Scratch, per stream: 64 + 8 * nwin bytes.  Not synchronised.
+ * CW_ERR_BAD_ARG before the device is touched: a NULL pointer (d_old_offsets may be NULL when max_old is 0), a pointer that is not
+ * 8-byte aligned, max_new, max_old or nwin > 2^32 - 256.                                                                            */
+typedef struct cw_resync_window {   /* 40 bytes */
+    uint64_t new_from, shift, old_first, old_count, final;
+} cw_resync_window;
+int cw_dev_cdc_resync_windows(const uint64_t *d_new_offsets, const uint64_t *d_new_count, size_t max_new,
+                              const uint64_t *d_stream_first /* [nwin + 1] */, const cw_resync_window *d_win, size_t nwin,
+                              const uint64_t *d_old_offsets, size_t max_old, uint64_t *d_result /* [4 * nwin] */, void *stream);
+/* Copies n = min(*d_n, max_n) extents from d_src to d_dst; extent k is the three words d_ext[3 * k ..] = {src_off, dst_off, len}.
+ * Nothing of the list is trusted.  d_result[4] = {verdict, the end of the last extent in d_dst, the lowest bad extent or CW_DELTA_NONE,
+ * n}.  Verdict 1 (the end is then 0): an extent with len 0, one that leaves d_src[0 .. src_bytes) or d_dst[0 .. dst_bytes) or wraps,
+ * or one whose dst_off lies in front of the end of the extent before it (the destinations ascend without overlap); then not a byte of
+ * d_dst changes.  The copy is tiled by the bytes of d_dst (16 KiB per wavefront), so an extent of one byte and one of gigabytes cost
+ * what their bytes cost.  Whatever the list holds, no load leaves d_src or d_ext[0 .. 3 * max_n) and no store leaves the extents'
+ * destinations and d_result.  CW_ERR_BAD_ARG before anything is launched: a NULL pointer (d_src, d_dst and d_ext may be when their
+ * size is 0), a d_ext, d_n or d_result that is not 8-byte aligned, max_n > 2^32 - 256, d_dst overlapping d_src.  No scratch.  Not
+ * synchronised.                                                                                                                     */
+int cw_dev_scatter_extents(const void *d_src, size_t src_bytes, const uint64_t *d_ext /* [3 * max_n] */, const uint64_t *d_n, size_t max_n,
+                           void *d_dst, size_t dst_bytes, uint64_t *d_result /* [4] */, void *stream);
+typedef struct cw_compose_stats {   /* of one cw_store_compose call */
+    uint64_t windows, rounds, merged_windows, rebuilt_bytes, rebuilt_chunks, new_chunks, stored_bytes, kept_positions;
+} cw_compose_stats;
+/* Builds a new stored stream B from ranges of streams the store already holds and new bytes, without restoring or re-ingesting
+ * anything.  Synchronous; host pointers except inside *st.
+ *   source        A is the recipe refs[nchunks], offsets[nchunks + 1] (zero-based: A is offsets[nchunks] - offsets[0] bytes).  With
+ *                 stream_first[nstreams + 1] (as cw_dev_store_account takes it) A is the concatenation of nstreams stored streams,
+ *                 stream f being positions [stream_first[f], stream_first[f + 1]); NULL means one stream.
+ *   ops           ops[nops] tile B from 0 as cw_dev_apply_delta's do: each a copy of A's bytes [a_off, a_off + len) or len new bytes
+ *                 at payload_off of payload[0 .. payload_bytes).
+ *   result        *out_nchunks, out_refs, out_offsets, the store bytes, the directory and the index are what cw_store_ingest of B's
+ *                 bytes leaves, given that the index still holds every chunk of A: the cuts bit for bit.  A chunk of B is KEPT -- it
+ *                 takes A's ref and is not read, hashed or stored -- exactly when a copy holds it whole as position s of A, it starts
+ *                 at or behind the copy's start in B, and s is not the last position of its stream (whose end the stream's end
+ *                 forced) unless it ends B as well; adjacent copies that continue each other count as one, and a copy is split at
+ *                 the stream ends of A inside it.  Every other chunk is REBUILT: read back or taken from the payload, hashed,
+ *                 deduplicated, compressed and appended, rebuilt chunk i of the call in B order with value base + i.  The caller
+ *                 advances base by stats->rebuilt_chunks.  The store only appends, so A stays valid.
+ *   procedure     A copy with kept candidates is an anchor.  Between two anchors lies a window: it starts where the candidates of
+ *                 the anchor before end and reaches lookahead bytes (0 = 4 * max_size, at least 2 * max_size) into its own anchor.
+ *                 A round materialises all unresolved windows on the device (cw_dev_read_ranges, cw_dev_scatter_extents), chunks
+ *                 them in one cw_dev_cdc_streams call and looks for each window's landing (cw_dev_cdc_resync_windows): one
+ *                 synchronise.  A window without a landing doubles its lookahead; one that has covered its whole anchor drops the
+ *                 anchor and merges into the next window, once every window in front of it is resolved.  Behind the last anchor a
+ *                 final window runs to B's end.  Then ONE commit: the rebuilt extents of all windows through
+ *                 cw_dev_cdc_streams_dedupe_compress and cw_dev_store_chunks.
+ *   all or nothing  Nothing is inserted into index, directory or store before every range was read with status 0, each extent chunked
+ *                 into exactly the chunks its round found (else CW_ERR_STATE), and the rebuilt chunks were admitted exactly as a piece
+ *                 of cw_store_ingest is.  CW_ERR_NOMEM (not admitted, or the windows do not fit on the device) and CW_ERR_BAD_ARG (a
+ *                 range that does not restore) leave index, store, directory and A as they were.
+ *   CW_ERR_BAD_ARG, before the device is touched: what cw_store_patch refuses of index, parameters, codec and store; a NULL among
+ *                 refs (nchunks != 0), offsets, ops (nops != 0), out_refs, out_offsets, out_nchunks; a NULL payload with payload_bytes
+ *                 != 0; an op list cw_dev_apply_delta would call malformed over A's bytes and the payload, naming the lowest bad op; a
+ *                 stream_first that does not start at 0, decreases or does not end at nchunks; max_out < B's bytes / min_size + 2; base
+ *                 + that bound wrapping; offsets that decrease, when an op copies (the plan searches the whole list).
+ * nops == 0 gives the empty recipe (*out_nchunks = 0, out_offsets[0] = 0) with no device work.                                      */
+int cw_store_compose(cw_dedupe_t *x, const cw_cdc_params *p, int comp_alg, const cw_store *st,
+                     const uint64_t *refs, const uint64_t *offsets, size_t nchunks,
+                     const uint64_t *stream_first /* may be NULL */, size_t nstreams,
+                     const cw_delta_op *ops, size_t nops, const void *payload, size_t payload_bytes,
+                     uint64_t base, size_t lookahead /* 0 = default */,
+                     uint64_t *out_refs, uint64_t *out_offsets, size_t max_out, size_t *out_nchunks,
+                     cw_compose_stats *stats /* may be NULL */);
+
 /* ---- chunk bundles: stored chunks from one store to another -------------------------------------------
  * A bundle is a manifest and a payload.  The manifest lists the n distinct chunks a set of recipes names, in ascending value of
  * the sending store: digest[k], value[k] and loc[k] (a cw_chunk_loc whose pos is relative to the payload; all zero = listed but
