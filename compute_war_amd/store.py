@@ -288,7 +288,8 @@ class ChunkStore:
         return CwError(-5, f"{what}: values {self.base} .. {self.base + k} leave the directory [{self.dir_base}, {self.dir_base + self.dir_entries})")
 
     def _append(self, k: int, src, n: int, off, k_dev, cap: int, slots, sizes, new_idx, n_new, result, s: int) -> None:
-        """``dev_store_chunks`` of the outputs of a fused call that found k chunks; ``base`` advances by k, or CwError (-5)."""
+        """``dev_store_chunks`` of the outputs of a fused call that found k chunks; ``base`` advances by k, or CwError (-5) with the
+        index as it was before the fused call."""
         import torch
         dev_store_chunks(self.comp_alg, src.data_ptr(), n, off.data_ptr(), k_dev.data_ptr(), cap - 1, slots.data_ptr(), sizes.data_ptr(),
                          self.base, self.d_store.data_ptr(), self.store_bytes, self.d_used.data_ptr(), self.d_dir.data_ptr(), self.dir_base,
@@ -296,7 +297,13 @@ class ChunkStore:
         torch.cuda.synchronize()
         verdict, needed = _words(result)
         if verdict:
-            # the index holds the call's new chunks already, the store does not: the caller starts over or grows the store
+            # the fused call put the call's new chunks into the index and the store took none of them: they are exactly the entries
+            # with values in [base, base + k) -- base never advanced over them -- so one retain over that range with no flag set
+            # takes them out again, and a later ingest does not find them "known" under values that name nothing
+            if k:
+                none_live = _zeros(k, torch.int32)
+                torch.cuda.synchronize()
+                self.index.retain(none_live.data_ptr(), self.base, k)
             err = self._no_room("chunk store", needed, self.used()) if verdict == 1 else self._off_directory("chunk store", k)
             err.needed = needed
             raise err
@@ -304,7 +311,9 @@ class ChunkStore:
 
     def ingest(self, data) -> Recipe:
         """Chunk, hash, dedupe and compress ``data`` in one device call, then append its new chunks.  Raises CwError (-5) when the
-        store or the directory cannot take them (``e.needed`` = the bytes the call wanted); the store is then unchanged."""
+        store or the directory cannot take them (``e.needed`` = the bytes the call wanted); store, directory, index and ``base``
+        are then as they were: the digests the fused call inserted are taken out of the index again (one ``index.retain`` over the
+        call's values, a rebuild of the table), so the same or another buffer can be ingested once there is room."""
         import torch
         a = _np_u8(data)
         n, s = a.size, self._stream()
