@@ -502,4 +502,82 @@ int cw_dev_translate_refs(const uint64_t *d_ref, const uint64_t *d_count, size_t
                     "translate refs launch");
 }
 
+// ---- XOR guard stripes over the store's bytes: update, check, rebuild (kernels: guard_kernels.hip) ------------------------------
+size_t cw_store_guard_bytes(size_t store_bytes, size_t stripe, unsigned group)
+{
+    if (stripe < CW_GUARD_MIN_STRIPE || stripe > CW_GUARD_MAX_STRIPE || (stripe & (stripe - 1)) || group < 1 || group > CW_GUARD_MAX_GROUP) return 0;
+    return cw::store_guard_groups(store_bytes, stripe, group) * stripe;
+}
+
+// what the three calls refuse of store, geometry and guard
+static int guard_args(const void *d_store, size_t store_bytes, size_t stripe, unsigned group, const void *d_guard, size_t guard_bytes)
+{
+    int rc;
+    if (!d_guard || (store_bytes && !d_store)) return fail(CW_ERR_BAD_ARG, "NULL pointer: %s", !d_guard ? "d_guard" : "d_store");
+    if (cw_store_guard_bytes(1, stripe, group) == 0)
+        return fail(CW_ERR_BAD_ARG, "stripe %zu is no power of two in [65536, 2^30] or group %u is not in [1, 256]", stripe, group);
+    if (guard_bytes < cw_store_guard_bytes(store_bytes, stripe, group))
+        return fail(CW_ERR_BAD_ARG, "guard_bytes %zu < %zu, what a store of %zu bytes needs", guard_bytes, cw_store_guard_bytes(store_bytes, stripe, group),
+                    store_bytes);
+    if ((rc = check_count("the groups of store_bytes", cw::store_guard_groups(store_bytes, stripe, group))) != CW_OK) return rc;
+    if ((rc = check_dir_aligned((uintptr_t)d_store | (uintptr_t)d_guard, "d_store / d_guard")) != CW_OK) return rc;
+    if (ranges_overlap(d_store, store_bytes, d_guard, guard_bytes)) return fail(CW_ERR_BAD_ARG, "d_guard overlaps d_store");
+    return CW_OK;
+}
+
+int cw_dev_store_guard_update(const void *d_store, size_t store_bytes, const uint64_t *d_used, uint64_t *d_covered, size_t stripe, unsigned group,
+                              void *d_guard, size_t guard_bytes, uint64_t *d_result, void *stream)
+{
+    int rc;
+    const char *null = !d_used ? "d_used" : !d_covered ? "d_covered" : !d_result ? "d_result" : NULL;
+    if (null) return fail(CW_ERR_BAD_ARG, "NULL pointer: %s", null);
+    if ((rc = guard_args(d_store, store_bytes, stripe, group, d_guard, guard_bytes)) != CW_OK) return rc;
+    if ((rc = check_word_aligned((uintptr_t)d_used | (uintptr_t)d_covered | (uintptr_t)d_result, "d_used / d_covered / d_result")) != CW_OK) return rc;
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    return launched(cw::store_guard_update_launch((const uint8_t *)d_store, store_bytes, d_used, d_covered, stripe, group, d_guard, d_result,
+                                                  (hipStream_t)stream),
+                    "store guard update launch");
+}
+
+int cw_dev_store_guard_check(const void *d_store, size_t store_bytes, const uint64_t *d_covered, size_t stripe, unsigned group, const void *d_guard,
+                             size_t guard_bytes, uint32_t *d_group_bad, uint64_t *d_result, void *stream)
+{
+    int rc;
+    const char *null = !d_covered ? "d_covered" : !d_result ? "d_result" : NULL;
+    if (null) return fail(CW_ERR_BAD_ARG, "NULL pointer: %s", null);
+    if ((rc = guard_args(d_store, store_bytes, stripe, group, d_guard, guard_bytes)) != CW_OK) return rc;
+    if ((rc = check_word_aligned((uintptr_t)d_covered | (uintptr_t)d_result, "d_covered / d_result")) != CW_OK) return rc;
+    if ((uintptr_t)d_group_bad & 3) return fail(CW_ERR_BAD_ARG, "d_group_bad is not 4-byte aligned");
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    return launched_nomem(cw::store_guard_check_launch((const uint8_t *)d_store, store_bytes, d_covered, stripe, group, d_guard, d_group_bad, d_result,
+                                                       (hipStream_t)stream),
+                          "store guard check launch");
+}
+
+int cw_dev_store_guard_rebuild(const void *d_store, size_t store_bytes, const cw_chunk_loc *d_dir, uint64_t dir_base, size_t dir_entries,
+                               const uint64_t *d_covered, size_t stripe, unsigned group, const void *d_guard, size_t guard_bytes,
+                               const uint64_t *d_values, const uint64_t *d_count, size_t max_count, void *d_out, size_t out_bytes,
+                               cw_chunk_loc *d_out_loc, uint32_t *d_status, uint64_t *d_result, void *stream)
+{
+    int rc = check_count("max_count", max_count);
+    if (rc != CW_OK) return rc;
+    const char *null = !d_dir ? "d_dir" : !d_covered ? "d_covered" : !d_values ? "d_values" : !d_count ? "d_count" : !d_out_loc ? "d_out_loc"
+                     : !d_status ? "d_status" : !d_result ? "d_result" : out_bytes && !d_out ? "d_out" : NULL;
+    if (null) return fail(CW_ERR_BAD_ARG, "NULL pointer: %s", null);
+    if (dir_entries == 0) return fail(CW_ERR_BAD_ARG, "dir_entries is 0");
+    if ((rc = guard_args(d_store, store_bytes, stripe, group, d_guard, guard_bytes)) != CW_OK) return rc;
+    if ((rc = check_dir_aligned((uintptr_t)d_dir | (uintptr_t)d_out_loc, "d_dir / d_out_loc")) != CW_OK) return rc;
+    if ((rc = check_word_aligned((uintptr_t)d_covered | (uintptr_t)d_values | (uintptr_t)d_count | (uintptr_t)d_result,
+                                 "d_covered / d_values / d_count / d_result")) != CW_OK)
+        return rc;
+    if ((uintptr_t)d_status & 3) return fail(CW_ERR_BAD_ARG, "d_status is not 4-byte aligned");
+    if (ranges_overlap(d_store, store_bytes, d_out, out_bytes)) return fail(CW_ERR_BAD_ARG, "d_out overlaps d_store");
+    if (ranges_overlap(d_guard, guard_bytes, d_out, out_bytes)) return fail(CW_ERR_BAD_ARG, "d_out overlaps d_guard");
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    return launched_nomem(cw::store_guard_rebuild_launch((const uint8_t *)d_store, store_bytes, d_dir, dir_base, dir_entries, d_covered, stripe, group,
+                                                         d_guard, d_values, d_count, max_count, (uint8_t *)d_out, out_bytes, d_out_loc, d_status, d_result,
+                                                         (hipStream_t)stream),
+                          "store guard rebuild launch");
+}
+
 } // extern "C"

@@ -823,6 +823,42 @@ def dev_store_replace_chunks(d_in: int, in_bytes: int, d_in_loc: int, d_values: 
                                             d_used, d_dir, dir_base, dir_entries, d_result, stream))
 
 
+# ---- XOR guard stripes over the store's bytes (cw_dev_store_guard_*) --------------------------------------
+def store_guard_bytes(store_bytes: int, stripe: int, group: int) -> int:
+    """The guard bytes a store of store_bytes bytes needs: ceil(store_bytes / (group * stripe)) * stripe, or 0 when stripe is no power of
+    two in [65536, 2^30] or group is not in [1, 256].  Host only."""
+    if store_bytes < 0 or stripe < 0 or not 0 <= group < 1 << 32:
+        return 0
+    return int(lib().cw_store_guard_bytes(store_bytes, stripe, group))
+
+
+def dev_store_guard_update(d_store: int, store_bytes: int, d_used: int, d_covered: int, stripe: int, group: int, d_guard: int, guard_bytes: int,
+                           d_result: int, stream: int = 0) -> None:
+    """Folds the store bytes [*d_covered, *d_used) into the guard, then *d_covered = *d_used.  d_result[0..4) = verdict (1: the cursors
+    are inconsistent, nothing changed), from, to, the bytes folded.  Not synchronised."""
+    check(lib().cw_dev_store_guard_update(d_store or None, store_bytes, d_used, d_covered, stripe, group, d_guard, guard_bytes, d_result, stream))
+
+
+def dev_store_guard_check(d_store: int, store_bytes: int, d_covered: int, stripe: int, group: int, d_guard: int, guard_bytes: int, d_group_bad: int,
+                          d_result: int, stream: int = 0) -> None:
+    """Recomputes the guard over the store bytes [0, *d_covered) and compares.  d_result[0..4) = verdict (1: the cursor lies above
+    store_bytes), the groups checked, the groups that differ, the lowest of them or 2^64 - 1; d_group_bad (u32 per group, or 0) gets a
+    flag for every group checked.  Not synchronised."""
+    check(lib().cw_dev_store_guard_check(d_store or None, store_bytes, d_covered, stripe, group, d_guard, guard_bytes, d_group_bad or None, d_result,
+                                         stream))
+
+
+def dev_store_guard_rebuild(d_store: int, store_bytes: int, d_dir: int, dir_base: int, dir_entries: int, d_covered: int, stripe: int, group: int,
+                            d_guard: int, guard_bytes: int, d_values: int, d_count: int, max_count: int, d_out: int, out_bytes: int,
+                            d_out_loc: int, d_status: int, d_result: int, stream: int = 0) -> None:
+    """The stored bytes of the entries d_values[k], k < min(*d_count, max_count), rebuilt from the guard and the other bytes of their
+    groups, back to back into d_out with d_out_loc[k] = where (all zero: not rebuilt).  d_status[k] (u32) = 0 rebuilt, 1 collides with
+    another listed extent, 2 unprotected.  d_result[0..4) = verdict (1: does not fit, 2: the cursor lies above store_bytes; d_out and
+    d_out_loc untouched then), total bytes, positions, positions rebuilt.  d_out = 0 with out_bytes = 0 is a dry run.  Not synchronised."""
+    check(lib().cw_dev_store_guard_rebuild(d_store or None, store_bytes, d_dir, dir_base, dir_entries, d_covered, stripe, group, d_guard, guard_bytes,
+                                           d_values, d_count, max_count, d_out or None, out_bytes, d_out_loc, d_status, d_result, stream))
+
+
 class Store(C.Structure):
     """cw_store: the caller-owned triple of the chunk store (bytes, cursor, directory) as one argument."""
     _fields_ = [("d_store", C.c_void_p), ("store_bytes", C.c_size_t), ("d_used", C.c_void_p), ("d_dir", C.c_void_p),

@@ -7,12 +7,14 @@ when a method first needs it, so importing the package does not import it.
 """
 from __future__ import annotations
 
+import functools
+
 import numpy as np
 
 from ._lib import CwError, lib
 from .ops import (ACCOUNT_DTYPE, DELTA_OP_DTYPE, CdcParams, ChunkLoc, DedupeIndex, DeltaOp, Store, _comp_id, _hash_id, _np_u8, chunk_slots_bytes,
-                  dev_apply_delta, dev_hash_chunks, dev_read_ranges, dev_recipe_diff, dev_restore_chunks, dev_store_account, dev_store_chunks, dev_store_compact, dev_store_export_chunks, dev_store_import_chunks, dev_store_mark,
-                  dev_store_renumber, dev_store_replace_chunks, dev_translate_refs, device_count, digest_bytes, init, store_ingest,
+                  dev_apply_delta, dev_hash_chunks, dev_read_ranges, dev_recipe_diff, dev_restore_chunks, dev_store_account, dev_store_chunks, dev_store_compact, dev_store_export_chunks, dev_store_guard_check, dev_store_guard_rebuild, dev_store_guard_update, dev_store_import_chunks, dev_store_mark,
+                  dev_store_renumber, dev_store_replace_chunks, dev_scatter_extents, dev_translate_refs, device_count, digest_bytes, init, store_guard_bytes, store_ingest,
                   store_compose, store_ingest_streams, store_patch, store_restore, store_scrub)
 
 
@@ -240,6 +242,17 @@ class Bundle:
             return cls(z["digests"], z["values"], z["locs"], z["payload"], int(z["hash_alg"]), int(z["comp_alg"]), recipes)
 
 
+def _folds(method):
+    """A ChunkStore method that appends: while the store is protected it ends, refused or not, with one queued guard update."""
+    @functools.wraps(method)
+    def appending(self, *args, **kwargs):
+        try:
+            return method(self, *args, **kwargs)
+        finally:
+            self._fold()
+    return appending
+
+
 class ChunkStore:
     """A dedupe index with the bytes behind it: ``ingest`` chunks, dedupes and compresses a buffer and appends its new chunks to a
     device-resident store, ``restore`` turns a recipe back into bytes, ``read`` / ``read_ranges`` give byte ranges of it, ``compact`` forgets every stream but the ones named,
@@ -256,10 +269,14 @@ class ChunkStore:
     says what changed between two recipes from the recipes alone, and ``delta`` packs the new version's new bytes with those ops for
     someone who holds the old version as plain bytes (``apply_delta``).  ``compose`` builds a new stored stream from ranges of stored
     streams and new bytes in one call -- ``apply_delta`` (a ``Delta`` applied inside the store), ``concat`` and ``edit`` (``patch_many``
-    in one call) are thin forms of it -- and ``last_compose`` holds its statistics (cw_compose_stats as a dict)."""
+    in one call) are thin forms of it -- and ``last_compose`` holds its statistics (cw_compose_stats as a dict).
+    ``protect`` puts XOR guard stripes over the stored bytes: every method that appends then ends with one
+    queued guard update, ``guard_check`` says which groups of stripes no longer match, and ``repair_local`` rebuilds the chunks a scrub
+    found damaged from the guard, in place and without a peer."""
     last_stats = None
     last_patch = None
     last_compose = None
+    d_guard = None  # the guard, with its cursor (d_covered) and its geometry (stripe, group), while the store is protected
 
     def __init__(self, index: DedupeIndex, comp_alg, params: CdcParams, store_bytes: int, dir_entries: int, dir_base: int = 0):
         import torch
@@ -278,6 +295,51 @@ class ChunkStore:
 
     def used(self) -> int:
         return int(self.d_used.item())
+
+    def protect(self, stripe: int = 65536, group: int = 16) -> None:
+        """Put guard stripes over the store: a guard of store_bytes / group bytes and its cursor, then one
+        update that folds in the bytes [0, used()).  ``stripe`` is a power of two in [65536, 2^30], ``group`` in [1, 256].  A store
+        that is protected already gets a fresh guard of the new geometry."""
+        import torch
+        size = store_guard_bytes(max(self.store_bytes, 1), stripe, group)
+        if size == 0:
+            raise ValueError(f"stripe {stripe} is no power of two in [65536, 2^30] or group {group} is not in [1, 256]")
+        self.stripe, self.group = int(stripe), int(group)
+        self.d_guard, self.d_covered, self._fold_result = _zeros(size, torch.uint8), _zeros(1), _zeros(4)
+        torch.cuda.synchronize()  # (torch zeroed them on its own stream)
+        self._fold()
+
+    def _fold(self) -> None:
+        """The one guard update: queued, not synchronised.  Nothing when the store is not protected."""
+        if self.d_guard is not None:
+            dev_store_guard_update(self.d_store.data_ptr(), self.store_bytes, self.d_used.data_ptr(), self.d_covered.data_ptr(), self.stripe,
+                                   self.group, self.d_guard.data_ptr(), self.d_guard.numel(), self._fold_result.data_ptr(), self._stream())
+
+    def protected_bytes(self) -> int:
+        """The guard's cursor: the stored bytes [0, protected_bytes()) are folded in.  Equal to ``used()`` whenever a method has
+        returned; 0 for a store that is not protected."""
+        return 0 if self.d_guard is None else int(self.d_covered.item())
+
+    def guard_check(self) -> tuple:
+        """(count, groups): how many groups of stripes below the cursor differ from the guard, and which (``dev_store_guard_check``).
+        A group differs when a stored byte in it changed, live or not, or a byte of the guard itself."""
+        import torch
+        self._need_guard()
+        groups = self.d_guard.numel() // self.stripe
+        bad, result = _zeros(groups, torch.int32), _zeros(4)
+        torch.cuda.synchronize()
+        dev_store_guard_check(self.d_store.data_ptr(), self.store_bytes, self.d_covered.data_ptr(), self.stripe, self.group, self.d_guard.data_ptr(),
+                              self.d_guard.numel(), bad.data_ptr(), result.data_ptr(), self._stream())
+        torch.cuda.synchronize()
+        verdict, checked, differ, _ = _words(result)
+        if verdict:
+            raise CwError(-4, f"chunk store: the guard's cursor {self.protected_bytes()} lies above the store's {self.store_bytes} bytes")
+        which = np.nonzero(bad.cpu().numpy()[:checked])[0].tolist()
+        return differ, which
+
+    def _need_guard(self) -> None:
+        if self.d_guard is None:
+            raise CwError(-4, "chunk store: not protected (ChunkStore.protect comes first)")
 
     def _no_room(self, what: str, needed: int, used: int) -> CwError:
         err = CwError(-5, f"{what}: {needed} bytes do not fit behind {used} of {self.store_bytes}")
@@ -309,6 +371,7 @@ class ChunkStore:
             raise err
         self.base += k
 
+    @_folds
     def ingest(self, data) -> Recipe:
         """Chunk, hash, dedupe and compress ``data`` in one device call, then append its new chunks.  Raises CwError (-5) when the
         store or the directory cannot take them (``e.needed`` = the bytes the call wanted); store, directory, index and ``base``
@@ -330,6 +393,7 @@ class ChunkStore:
         self._append(k, src, n, off, k_dev, cap, slots, sizes, new_idx, n_new, result, s)
         return Recipe(ref.cpu().numpy().view(np.uint64)[:k], off.cpu().numpy().view(np.uint64)[:k + 1])
 
+    @_folds
     def ingest_many(self, datas) -> list:
         """``ingest`` of many buffers at once: one upload of their concatenation, one fused call (``dev_cdc_streams_dedupe_compress``)
         and one ``dev_store_chunks``.  Every buffer is chunked as if alone, so the recipes, the store and the index are what a loop of
@@ -363,6 +427,7 @@ class ChunkStore:
     def _triple(self) -> Store:
         return Store(self.d_store.data_ptr(), self.store_bytes, self.d_used.data_ptr(), self.d_dir.data_ptr(), self.dir_base, self.dir_entries)
 
+    @_folds
     def ingest_stream(self, data) -> Recipe:
         """``ingest`` for host data of any size, piece by piece with uploads beside the kernels.  When the index, the directory or
         the store cannot take a piece, raises CwError (-5) with ``e.consumed`` and ``e.nchunks`` (the bytes and chunks of the pieces that
@@ -382,6 +447,7 @@ class ChunkStore:
             raise err
         return recipe
 
+    @_folds
     def ingest_many_stream(self, datas) -> list:
         """``ingest_many`` for host buffers of any number and total size, piece by piece as ``ingest_stream`` (cw_store_ingest_streams):
         every buffer is chunked as if alone and may span pieces; the recipes, the store and the index are what ``ingest_many`` or a loop
@@ -487,6 +553,7 @@ class ChunkStore:
         """Bytes [offset, offset + length) of an ingested stream: ``read_ranges`` with one range."""
         return self.read_ranges(recipe, [(offset, length)])[0]
 
+    @_folds
     def patch(self, recipe: Recipe, offset: int, remove: int, data, lookahead: int = 0) -> Recipe:
         """The recipe of the stream with bytes [offset, offset + remove) replaced by ``data`` (cw_store_patch):
         only the chunks around the edit are rebuilt, re-chunked and stored, yet recipe, store and index are exactly what ingesting
@@ -547,6 +614,7 @@ class ChunkStore:
             raise ValueError(f"an edit leaves the stream's {recipe.nbytes} bytes")
         return edits
 
+    @_folds
     def _compose_call(self, sources, ops, payload, lookahead: int) -> Recipe:
         """One ``store_compose`` over the recipes ``sources`` joined as ``restore_many_stream`` joins them, with their stream index."""
         if device_count() <= 0:
@@ -708,7 +776,7 @@ class ChunkStore:
     def compact(self, keep, store_bytes: int | None = None) -> dict:
         """Forget every stream but the recipes in ``keep``: mark their chunks, move the marked chunks' stored bytes into a new store
         of ``store_bytes`` (default: as large as the old one, after a dry run) with a new directory, and drop the other chunks' digests
-        from the index.  Values are not renumbered.  Returns dict(kept, dropped, bytes_before, bytes_after, removed).  Raises CwError
+        from the index.  Values are not renumbered; a protected store gets a fresh guard over the new bytes.  Returns dict(kept, dropped, bytes_before, bytes_after, removed).  Raises CwError
         with ``e.needed`` (the bytes the kept chunks take) when the new store is too small (-5) or a kept chunk's entry is damaged
         (-2), and CwError -2 when a recipe names a value outside the directory; the store and the index are then unchanged, as they
         are when the index's retain fails."""
@@ -743,6 +811,8 @@ class ChunkStore:
         needed, kept, dropped = run(new_store.data_ptr(), store_bytes)
         removed = self.index.retain(live.data_ptr(), self.dir_base, n)
         self.d_store, self.d_used, self.d_dir, self.store_bytes = new_store, new_used, new_dir, store_bytes
+        if self.d_guard is not None:
+            self.protect(self.stripe, self.group)  # every kept byte moved: a fresh guard over the new store
         return dict(kept=kept, dropped=dropped, bytes_before=bytes_before, bytes_after=needed, removed=removed)
 
     def renumber(self, recipes, dir_entries: int | None = None, dir_base: int | None = None) -> list:
@@ -888,6 +958,7 @@ class ChunkStore:
             payload = out.cpu().numpy()[:total]
         return Bundle(dig.cpu().numpy()[:flagged * db], values, locs, payload, self.index.hash_alg, self.comp_alg, recipes)
 
+    @_folds
     def import_bundle(self, bundle: Bundle, verify: bool = True) -> list:
         """Take a Bundle's chunks into this store and return its recipes in this store's values (offsets unchanged).  Chunks this
         store's index already holds keep their value here; the others are appended in manifest order under the values ``base`` + k,
@@ -1003,6 +1074,7 @@ class ChunkStore:
         status, stats = store_scrub(self.index, self.comp_alg, self._triple(), d_live)
         return ScrubReport(status, stats, self.dir_base)
 
+    @_folds
     def repair_from(self, other: "ChunkStore", report: ScrubReport, verify: bool = True) -> dict:
         """Put the chunks ``report.damaged`` names back from ``other``, a store that holds them (one the streams were replicated to),
         in stored form and under their own values, so that every recipe stays valid.  The damaged values' digests come from this
@@ -1084,20 +1156,106 @@ class ChunkStore:
         out["repaired"] = damaged[which].tolist()
         return out
 
+    def repair_local(self, report: ScrubReport, verify: bool = True) -> dict:
+        """Rebuild the chunks ``report.damaged`` names from the guard and the other stored bytes of their groups, and write them back
+        in place, at their own ``pos``: no room is needed, the directory and every recipe stay as they are, and the guard stays
+        exact.  The damaged values' digests come from this store's index, ``dev_store_guard_rebuild`` (sized by a dry run) rebuilds
+        their stored bytes, and one ``dev_scatter_extents`` puts the good ones back.  A chunk is left out -- not a reason to refuse
+        the rest -- when its extent shares a guard byte with another damaged chunk's (``collided``: neither can be told from the
+        other), when its entry is missing, unsound or ends above ``protected_bytes()`` (``unprotected``), or, with ``verify``, when
+        the rebuilt bytes do not decode or do not hash to the digest this index holds (``failed``: damage the report does not name,
+        in the guard or in another chunk of the group).  Returns dict(repaired, collided, unprotected, failed, no_digest): lists of
+        values; no_digest are the damaged values this index holds no digest for, which are skipped.  The index is never written."""
+        import torch
+        self._need_guard()
+        damaged = np.unique(np.ascontiguousarray(report.damaged, dtype=np.uint64))
+        out = dict(repaired=[], collided=[], unprotected=[], failed=[], no_digest=[])
+        if len(damaged) == 0:
+            return out
+        idx = damaged - np.uint64(self.dir_base)
+        if (damaged < np.uint64(self.dir_base)).any() or (idx >= np.uint64(self.dir_entries)).any():
+            raise CwError(-2, f"chunk store: the report names values outside the directory [{self.dir_base}, {self.dir_base + self.dir_entries})")
+        idx = idx.astype(np.int64)
+        s, n, db, m = self._stream(), self.dir_entries, digest_bytes(self.index.hash_alg), len(damaged)
+        # 1. the digests this index holds for the damaged values, in ascending value
+        live, dig, val, res = _zeros(n, torch.int32), _zeros(m * db, torch.uint8), _zeros(m), _zeros(3)
+        live[torch.from_numpy(idx).cuda()] = 1
+        torch.cuda.synchronize()
+        self.index.dev_export_live(live.data_ptr(), self.dir_base, n, dig.data_ptr(), val.data_ptr(), m, res.data_ptr(), s)
+        torch.cuda.synchronize()
+        has = val.cpu().numpy().view(np.uint64)[:m] != _MISS
+        out["no_digest"] = damaged[~has].tolist()
+        # 2. the rebuild: a dry run that sizes the payload, then the run that fills it
+        d_val, d_count, d_loc, d_status, result = _u64(damaged), _u64([m]), _zeros(m * 2), _zeros(m, torch.int32), _zeros(4)
+        payload, total = None, 0
+        for dry in (True, False):
+            torch.cuda.synchronize()
+            dev_store_guard_rebuild(self.d_store.data_ptr(), self.store_bytes, self.d_dir.data_ptr(), self.dir_base, n, self.d_covered.data_ptr(),
+                                    self.stripe, self.group, self.d_guard.data_ptr(), self.d_guard.numel(), d_val.data_ptr(), d_count.data_ptr(), m,
+                                    0 if dry else payload.data_ptr(), total, d_loc.data_ptr(), d_status.data_ptr(), result.data_ptr(), s)
+            torch.cuda.synchronize()
+            verdict, needed = _words(result, 2)
+            if verdict == 2:
+                raise CwError(-4, f"chunk store: the guard's cursor lies above the store's {self.store_bytes} bytes")
+            if dry:  # (verdict 1 with the bytes needed, unless nothing can be rebuilt)
+                payload, total = _zeros(needed, torch.uint8), needed
+            elif verdict:
+                raise CwError(-4, f"chunk store: the rebuild of {total} bytes was refused with verdict {verdict} after its dry run")
+        status = d_status.cpu().numpy().view(np.uint32)[:m]
+        out["collided"], out["unprotected"] = damaged[has & (status == 1)].tolist(), damaged[has & (status == 2)].tolist()
+        which = np.nonzero(has & (status == 0))[0]
+        if len(which) == 0:
+            return out
+        locs = d_loc.cpu().numpy().view(LOC_DTYPE)[:m]
+        good = np.ones(len(which), bool)
+        if verify:
+            # 3. the rebuilt chunks restore from the payload and hash to the digests this index holds
+            st, dig2 = self._restored_digests(payload.data_ptr(), total, d_loc.data_ptr(), m, which, locs["raw"][which].astype(np.int64) & 0x1FFFF)
+            good = (st == 0) & (dig2 == dig.cpu().numpy()[:m * db].reshape(m, db)[which]).all(axis=1)
+        # 4. back in place, in ascending pos: an extent that starts in front of the end of the one before it is left out
+        mine = self.d_dir.view(-1, 2)[torch.from_numpy(idx[which]).cuda()].cpu().numpy().reshape(-1).view(LOC_DTYPE)
+        ext, end = [], 0
+        for j in np.argsort(mine["pos"], kind="stable"):
+            pos, stored = int(mine["pos"][j]), int(mine["stored"][j])
+            if good[j] and pos >= end:
+                ext.append((int(locs["pos"][which[j]]), pos, stored))
+                end = pos + stored
+            else:
+                good[j] = False
+        out["failed"] = damaged[which[~good]].tolist()
+        if ext:
+            d_ext, d_n, result = _u64(np.array(ext, np.uint64)), _u64([len(ext)]), _zeros(4)
+            torch.cuda.synchronize()
+            dev_scatter_extents(payload.data_ptr(), total, d_ext.data_ptr(), d_n.data_ptr(), len(ext), self.d_store.data_ptr(), self.store_bytes,
+                                result.data_ptr(), s)
+            torch.cuda.synchronize()
+            verdict = _words(result, 1)[0]
+            if verdict:
+                raise CwError(-4, f"chunk store: checked, yet the write-back of {len(ext)} extents was refused with verdict {verdict}")
+        out["repaired"] = damaged[which[good]].tolist()
+        return out
+
     def save(self, path) -> None:
-        """One ``.npz``: the index's export, the store bytes [0, used), the directory, base and the parameters."""
+        """One ``.npz``: the index's export, the store bytes [0, used), the directory, base and the parameters; of a protected store
+        also the guard (the groups below its cursor), the cursor and the geometry."""
         dig, val = self.index.export()
+        guard = {}
+        if self.d_guard is not None:
+            covered = self.protected_bytes()
+            held = -(-covered // (self.stripe * self.group)) * self.stripe
+            guard = dict(guard=self.d_guard[:held].cpu().numpy(), guard_covered=np.uint64(covered),
+                         guard_geometry=np.array([self.stripe, self.group], np.uint64))
         p = self.params
         gear = p._gear if getattr(p, "_gear", None) is not None else np.zeros(0, np.uint64)
         with open(path, "wb") as f:
             np.savez(f, hash_alg=np.int64(self.index.hash_alg), max_entries=np.int64(self.index.max_entries), digests=dig, values=val,
                      comp_alg=np.int64(self.comp_alg), store=self.d_store[:self.used()].cpu().numpy(), store_bytes=np.int64(self.store_bytes),
                      directory=self.d_dir.cpu().numpy(), dir_base=np.uint64(self.dir_base), base=np.uint64(self.base),
-                     cdc=np.array([p.min_size, p.normal_size, p.max_size, p.mask_s, p.mask_l], np.uint64), gear=gear)
+                     cdc=np.array([p.min_size, p.normal_size, p.max_size, p.mask_s, p.mask_l], np.uint64), gear=gear, **guard)
 
     @classmethod
     def load(cls, path) -> "ChunkStore":
-        """A new index and fresh device buffers from a snapshot."""
+        """A new index and fresh device buffers from a snapshot; protected when the snapshot holds a guard."""
         import torch
         with np.load(path) as z:
             cdc, gear = [int(v) for v in z["cdc"]], z["gear"]
@@ -1111,6 +1269,15 @@ class ChunkStore:
                 cs.d_store[:len(store)] = torch.from_numpy(store).cuda()
                 cs.d_dir.copy_(torch.from_numpy(directory).cuda())
                 cs.d_used.fill_(len(store))
+                if "guard" in z.files:
+                    held, (stripe, group) = z["guard"], (int(v) for v in z["guard_geometry"])
+                    size = store_guard_bytes(max(cs.store_bytes, 1), stripe, group)
+                    if size == 0 or len(held) > size:
+                        raise CwError(-2, f"chunk store: the snapshot's guard ({len(held)} bytes, stripe {stripe}, group {group}) does not fit "
+                                          f"a store of {cs.store_bytes} bytes")
+                    cs.stripe, cs.group = stripe, group
+                    cs.d_guard, cs.d_covered, cs._fold_result = _zeros(size, torch.uint8), _u64([int(z["guard_covered"])]), _zeros(4)
+                    cs.d_guard[:len(held)] = torch.from_numpy(held).cuda()
                 torch.cuda.synchronize()
             except Exception:
                 index.close()

@@ -1118,6 +1118,67 @@ int cw_dev_store_replace_chunks(const void *d_in, size_t in_bytes, const cw_chun
                                 void *d_store, size_t store_bytes, uint64_t *d_used,
                                 cw_chunk_loc *d_dir, uint64_t dir_base, size_t dir_entries, uint64_t *d_result /* [2] */, void *stream);
 
+/* ---- guard stripes: XOR redundancy over the stored bytes, repair without a peer --------------------------
+ * Two parameters: `stripe` = S, a power of two with 65536 <= S <= 2^30, and `group` = G, 1 <= G <= 256; W = G * S.  Store byte p
+ * belongs to group p / W and column p % S.  The guard is a caller-owned device buffer like the store's triple, with a u64 cursor
+ * `covered` beside it: for every group g and column c
+ *     d_guard[g * S + c] = the XOR of d_store[p] over all p < covered with p / W == g and p % S == c.
+ * A zeroed guard with covered == 0 guards an empty store; the guard is 1 / G of the store.  The store only appends, so the bytes
+ * below `covered` never change and an update folds in only what was appended.  A stored extent is at most 65536 <= S bytes, so it
+ * never meets one of its own bytes in a column, whatever boundaries it straddles: any one extent can be rebuilt from the guard and
+ * the other bytes of its groups.  The calls follow the store's conventions: device pointers, counts and cursors read on the device,
+ * queued on `stream`, nothing synchronises, every decision made on the device and all or nothing.  All three refuse with
+ * CW_ERR_BAD_ARG before anything is launched: a NULL pointer (d_store may be NULL when store_bytes is 0, and what each call names), a
+ * stripe or group outside the bounds above, guard_bytes < cw_store_guard_bytes(store_bytes, stripe, group), more than 2^32 - 256
+ * groups, a d_store or d_guard that is not 16-byte aligned, [d_guard, +guard_bytes) overlapping [d_store, +store_bytes).           */
+#define CW_GUARD_MIN_STRIPE 65536u
+#define CW_GUARD_MAX_STRIPE (1u << 30)
+#define CW_GUARD_MAX_GROUP 256u
+/* The guard bytes a store of store_bytes bytes needs: ceil(store_bytes / W) * S; 0 for a geometry that is not allowed.  Host only. */
+size_t cw_store_guard_bytes(size_t store_bytes, size_t stripe, unsigned group);
+/* Folds d_store[from, to), from = *d_covered and to = *d_used, into the guard, then sets *d_covered = to.  d_result[4] = {verdict,
+ * from, to, the bytes folded}.  Verdict 1 when from > to or to > store_bytes: then no guard byte and not the cursor change and the
+ * bytes folded are 0.  Every byte of the range is folded exactly once, and the cursor is written by a second kernel, behind every
+ * guard byte: the call can be queued directly behind any call that appends, and a second call behind it folds nothing.  One lane
+ * owns each 16-byte guard word the range touches, loads the at most G store words behind it, masks the bytes outside the range and
+ * does one read-modify-write; there are no atomics.  Whatever the cursors hold, no load leaves d_store[from, to) or the guard words
+ * of the groups of [from, to), and no store leaves those guard words, *d_covered and d_result.  CW_ERR_BAD_ARG also for: a NULL
+ * d_used, d_covered or d_result, or one that is not 8-byte aligned.  No scratch.                                                 */
+int cw_dev_store_guard_update(const void *d_store, size_t store_bytes, const uint64_t *d_used, uint64_t *d_covered /* in/out */,
+                              size_t stripe, unsigned group, void *d_guard, size_t guard_bytes, uint64_t *d_result /* [4] */, void *stream);
+/* Recomputes the XOR over d_store[0, *d_covered) and compares it with the guard, every column of the N = ceil(*d_covered / W) groups
+ * below the cursor: a group differs when a store byte below the cursor changed -- whether or not a live entry names it -- or a
+ * guard byte did.  d_result[4] = {verdict, N, the groups that differ, the lowest such group or ~0}; d_group_bad (u32 per group, may be
+ * NULL) gets 1 or 0 for each group below N.  Verdict 1 when *d_covered > store_bytes: N is then 0.  Nothing else is written, and no
+ * load leaves d_store[0, *d_covered) or the guard bytes of those groups.  CW_ERR_BAD_ARG also for: a NULL d_covered or d_result, or
+ * one that is not 8-byte aligned; a d_group_bad that is not 4-byte aligned.  Scratch, per stream: 64 + 4 * ceil(store_bytes / W).   */
+int cw_dev_store_guard_check(const void *d_store, size_t store_bytes, const uint64_t *d_covered, size_t stripe, unsigned group,
+                             const void *d_guard, size_t guard_bytes, uint32_t *d_group_bad /* may be NULL */, uint64_t *d_result /* [4] */,
+                             void *stream);
+/* Rebuilds stored chunks from the guard and the other bytes of their groups.  n = min(*d_count, max_count); position k < n names the
+ * directory entry of value d_values[k], as cw_dev_store_export_chunks' positions do.  d_status[k] (u32) =
+ *   2 (unprotected)  the value names no entry, or the entry is all zero, unsound by cw_dev_store_compact's entry checks, or ends above
+ *                    *d_covered.  An unprotected position has no extent and takes no part in what follows.
+ *   1 (collides)     with E the SET of bytes in the extents of all other positions: some byte p of the extent has a byte p' != p in E
+ *                    with the same group and the same column.  A value named twice does not collide with itself (those are the same
+ *                    bytes).  The test is a symmetric "exists": the statuses are a function of the arguments alone.
+ *   0 (rebuilt)      every byte is the guard byte XOR the other members' bytes of its column below *d_covered.
+ * The rebuilt extents go to d_out back to back in position order, d_out_loc[k] = {pos in d_out, stored, raw word}, all zero for a
+ * position that was not rebuilt.  d_result[4] = {verdict, the total bytes, n, the positions rebuilt}.  Verdict 2 when *d_covered >
+ * store_bytes: every position is then unprotected.  Else verdict 1 when the total > out_bytes.  With a verdict other than 0 no byte of
+ * d_out and no d_out_loc changes, while d_status and d_result are written: out_bytes == 0 with d_out == NULL is the dry run.  The
+ * rebuild trusts the bytes of the other members: damage there that the list does not name gives wrong bytes, so the caller verifies
+ * the result by digest.  The work is linear in n plus, per position, the listed extents that share one of its at most two groups.
+ * Whatever the buffers hold, no load leaves d_store[0, *d_covered), the guard, d_dir[0..dir_entries) or d_values[0..n), and no store
+ * leaves the rebuilt extents' places in d_out, d_out_loc[0..n), d_status[0..n) and d_result.  CW_ERR_BAD_ARG also for: a NULL pointer
+ * (d_out may be NULL when out_bytes is 0), max_count > 2^32 - 256, dir_entries == 0, a d_dir or d_out_loc that is not 16-byte
+ * aligned, a d_covered, d_values, d_count or d_result that is not 8-byte aligned, a d_status that is not 4-byte aligned, [d_out,
+ * +out_bytes) overlapping the store or the guard.  Scratch, per stream: 80 + 28 * max_count + 16 * ceil(store_bytes / W) bytes.    */
+int cw_dev_store_guard_rebuild(const void *d_store, size_t store_bytes, const cw_chunk_loc *d_dir, uint64_t dir_base, size_t dir_entries,
+                               const uint64_t *d_covered, size_t stripe, unsigned group, const void *d_guard, size_t guard_bytes,
+                               const uint64_t *d_values, const uint64_t *d_count, size_t max_count, void *d_out, size_t out_bytes,
+                               cw_chunk_loc *d_out_loc, uint32_t *d_status /* [max_count] */, uint64_t *d_result /* [4] */, void *stream);
+
 /* plain device memory on the calling thread's device, for C callers of cw_dev_* (the host programs link no HIP runtime) */
 void *cw_dev_alloc(size_t bytes);                                   /* NULL on failure */
 void  cw_dev_free(void *d_p);
