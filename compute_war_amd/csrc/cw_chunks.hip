@@ -580,4 +580,75 @@ int cw_dev_store_guard_rebuild(const void *d_store, size_t store_bytes, const cw
                           "store guard rebuild launch");
 }
 
+// ---- the dual guard: P and the GF(2^8) syndrome Q (kernels: guard2_kernels.hip) ------------------------------------------------
+// what the three dual calls refuse: guard_args of the store, the geometry and P, then the narrower group and Q
+static int guard2_args(const void *d_store, size_t store_bytes, size_t stripe, unsigned group, const void *d_guard_p, const void *d_guard_q,
+                       size_t guard_bytes)
+{
+    int rc;
+    if (!d_guard_q) return fail(CW_ERR_BAD_ARG, "NULL pointer: d_guard_q");
+    if ((rc = guard_args(d_store, store_bytes, stripe, group, d_guard_p, guard_bytes)) != CW_OK) return rc;
+    if (group > CW_GUARD2_MAX_GROUP) return fail(CW_ERR_BAD_ARG, "group %u is not in [1, 255]: the dual guard's stripe weights 2^m repeat after 255", group);
+    if ((rc = check_dir_aligned((uintptr_t)d_guard_q, "d_guard_q")) != CW_OK) return rc;
+    if (ranges_overlap(d_store, store_bytes, d_guard_q, guard_bytes)) return fail(CW_ERR_BAD_ARG, "d_guard_q overlaps d_store");
+    if (ranges_overlap(d_guard_p, guard_bytes, d_guard_q, guard_bytes)) return fail(CW_ERR_BAD_ARG, "d_guard_q overlaps d_guard_p");
+    return CW_OK;
+}
+
+int cw_dev_store_guard2_update(const void *d_store, size_t store_bytes, const uint64_t *d_used, uint64_t *d_covered, size_t stripe, unsigned group,
+                               void *d_guard_p, void *d_guard_q, size_t guard_bytes, uint64_t *d_result, void *stream)
+{
+    int rc;
+    const char *null = !d_used ? "d_used" : !d_covered ? "d_covered" : !d_result ? "d_result" : NULL;
+    if (null) return fail(CW_ERR_BAD_ARG, "NULL pointer: %s", null);
+    if ((rc = guard2_args(d_store, store_bytes, stripe, group, d_guard_p, d_guard_q, guard_bytes)) != CW_OK) return rc;
+    if ((rc = check_word_aligned((uintptr_t)d_used | (uintptr_t)d_covered | (uintptr_t)d_result, "d_used / d_covered / d_result")) != CW_OK) return rc;
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    return launched(cw::store_guard2_update_launch((const uint8_t *)d_store, store_bytes, d_used, d_covered, stripe, group, d_guard_p, d_guard_q,
+                                                   d_result, (hipStream_t)stream),
+                    "store guard2 update launch");
+}
+
+int cw_dev_store_guard2_check(const void *d_store, size_t store_bytes, const uint64_t *d_covered, size_t stripe, unsigned group,
+                              const void *d_guard_p, const void *d_guard_q, size_t guard_bytes, uint32_t *d_group_bad, uint64_t *d_result, void *stream)
+{
+    int rc;
+    const char *null = !d_covered ? "d_covered" : !d_result ? "d_result" : NULL;
+    if (null) return fail(CW_ERR_BAD_ARG, "NULL pointer: %s", null);
+    if ((rc = guard2_args(d_store, store_bytes, stripe, group, d_guard_p, d_guard_q, guard_bytes)) != CW_OK) return rc;
+    if ((rc = check_word_aligned((uintptr_t)d_covered | (uintptr_t)d_result, "d_covered / d_result")) != CW_OK) return rc;
+    if ((uintptr_t)d_group_bad & 3) return fail(CW_ERR_BAD_ARG, "d_group_bad is not 4-byte aligned");
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    return launched_nomem(cw::store_guard2_check_launch((const uint8_t *)d_store, store_bytes, d_covered, stripe, group, d_guard_p, d_guard_q,
+                                                        d_group_bad, d_result, (hipStream_t)stream),
+                          "store guard2 check launch");
+}
+
+int cw_dev_store_guard2_rebuild(const void *d_store, size_t store_bytes, const cw_chunk_loc *d_dir, uint64_t dir_base, size_t dir_entries,
+                                const uint64_t *d_covered, size_t stripe, unsigned group, const void *d_guard_p, const void *d_guard_q,
+                                size_t guard_bytes, const uint64_t *d_values, const uint64_t *d_count, size_t max_count, void *d_out, size_t out_bytes,
+                                cw_chunk_loc *d_out_loc, uint32_t *d_status, uint64_t *d_result, void *stream)
+{
+    int rc = check_count("max_count", max_count);
+    if (rc != CW_OK) return rc;
+    const char *null = !d_dir ? "d_dir" : !d_covered ? "d_covered" : !d_values ? "d_values" : !d_count ? "d_count" : !d_out_loc ? "d_out_loc"
+                     : !d_status ? "d_status" : !d_result ? "d_result" : out_bytes && !d_out ? "d_out" : NULL;
+    if (null) return fail(CW_ERR_BAD_ARG, "NULL pointer: %s", null);
+    if (dir_entries == 0) return fail(CW_ERR_BAD_ARG, "dir_entries is 0");
+    if ((rc = guard2_args(d_store, store_bytes, stripe, group, d_guard_p, d_guard_q, guard_bytes)) != CW_OK) return rc;
+    if ((rc = check_dir_aligned((uintptr_t)d_dir | (uintptr_t)d_out_loc, "d_dir / d_out_loc")) != CW_OK) return rc;
+    if ((rc = check_word_aligned((uintptr_t)d_covered | (uintptr_t)d_values | (uintptr_t)d_count | (uintptr_t)d_result,
+                                 "d_covered / d_values / d_count / d_result")) != CW_OK)
+        return rc;
+    if ((uintptr_t)d_status & 3) return fail(CW_ERR_BAD_ARG, "d_status is not 4-byte aligned");
+    if (ranges_overlap(d_store, store_bytes, d_out, out_bytes)) return fail(CW_ERR_BAD_ARG, "d_out overlaps d_store");
+    if (ranges_overlap(d_guard_p, guard_bytes, d_out, out_bytes)) return fail(CW_ERR_BAD_ARG, "d_out overlaps d_guard_p");
+    if (ranges_overlap(d_guard_q, guard_bytes, d_out, out_bytes)) return fail(CW_ERR_BAD_ARG, "d_out overlaps d_guard_q");
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    return launched_nomem(cw::store_guard2_rebuild_launch((const uint8_t *)d_store, store_bytes, d_dir, dir_base, dir_entries, d_covered, stripe, group,
+                                                          d_guard_p, d_guard_q, d_values, d_count, max_count, (uint8_t *)d_out, out_bytes, d_out_loc,
+                                                          d_status, d_result, (hipStream_t)stream),
+                          "store guard2 rebuild launch");
+}
+
 } // extern "C"

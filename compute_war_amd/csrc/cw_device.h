@@ -352,6 +352,17 @@ hipError_t store_guard_rebuild_launch(const uint8_t *store, size_t store_bytes, 
                                       const uint64_t *d_covered, size_t stripe, unsigned group, const void *guard, const uint64_t *values,
                                       const uint64_t *d_count, size_t max_count, uint8_t *out, size_t out_bytes, void *out_loc, uint32_t *status,
                                       uint64_t *result, hipStream_t stream);
+// The dual guard: P as above and the GF(2^8) syndrome Q beside it (guard2_kernels.hip), group <= 255; result is [4], the rebuild's [5].
+// The rebuild's scratch is store_guard_rebuild_scratch_bytes
+size_t store_guard2_check_scratch_bytes(size_t groups);
+hipError_t store_guard2_update_launch(const uint8_t *store, size_t store_bytes, const uint64_t *d_used, uint64_t *d_covered, size_t stripe,
+                                      unsigned group, void *guard_p, void *guard_q, uint64_t *result, hipStream_t stream);
+hipError_t store_guard2_check_launch(const uint8_t *store, size_t store_bytes, const uint64_t *d_covered, size_t stripe, unsigned group,
+                                     const void *guard_p, const void *guard_q, uint32_t *group_bad, uint64_t *result, hipStream_t stream);
+hipError_t store_guard2_rebuild_launch(const uint8_t *store, size_t store_bytes, const void *dir, uint64_t dir_base, size_t dir_entries,
+                                       const uint64_t *d_covered, size_t stripe, unsigned group, const void *guard_p, const void *guard_q,
+                                       const uint64_t *values, const uint64_t *d_count, size_t max_count, uint8_t *out, size_t out_bytes, void *out_loc,
+                                       uint32_t *status, uint64_t *result, hipStream_t stream);
 
 hipError_t sum_sizes_launch(const uint32_t *sizes, size_t n, uint32_t raw_bytes, uint64_t *totals, hipStream_t stream);
 hipError_t gen_random_launch(uint64_t seed, uint64_t first_block, size_t nblocks, size_t block_bytes, uint8_t *dst,

@@ -859,6 +859,33 @@ def dev_store_guard_rebuild(d_store: int, store_bytes: int, d_dir: int, dir_base
                                            d_values, d_count, max_count, d_out or None, out_bytes, d_out_loc, d_status, d_result, stream))
 
 
+# ---- the dual guard: P and the GF(2^8) syndrome Q beside it (cw_dev_store_guard2_*); group <= 255 ---------
+def dev_store_guard2_update(d_store: int, store_bytes: int, d_used: int, d_covered: int, stripe: int, group: int, d_guard_p: int, d_guard_q: int,
+                            guard_bytes: int, d_result: int, stream: int = 0) -> None:
+    """``dev_store_guard_update`` for both syndromes: folds the store bytes [*d_covered, *d_used) into P and Q, then *d_covered =
+    *d_used.  d_result[0..4) as there; the P bytes are what that call writes.  Not synchronised."""
+    check(lib().cw_dev_store_guard2_update(d_store or None, store_bytes, d_used, d_covered, stripe, group, d_guard_p, d_guard_q, guard_bytes,
+                                           d_result, stream))
+
+
+def dev_store_guard2_check(d_store: int, store_bytes: int, d_covered: int, stripe: int, group: int, d_guard_p: int, d_guard_q: int, guard_bytes: int,
+                           d_group_bad: int, d_result: int, stream: int = 0) -> None:
+    """``dev_store_guard_check`` for both syndromes: d_group_bad (u32 per group, or 0) gets bit 0 when P differs and bit 1 when Q does;
+    d_result[0..4) = verdict, the groups checked, the groups with any bit, the lowest of them or 2^64 - 1.  Not synchronised."""
+    check(lib().cw_dev_store_guard2_check(d_store or None, store_bytes, d_covered, stripe, group, d_guard_p, d_guard_q, guard_bytes,
+                                          d_group_bad or None, d_result, stream))
+
+
+def dev_store_guard2_rebuild(d_store: int, store_bytes: int, d_dir: int, dir_base: int, dir_entries: int, d_covered: int, stripe: int, group: int,
+                             d_guard_p: int, d_guard_q: int, guard_bytes: int, d_values: int, d_count: int, max_count: int, d_out: int,
+                             out_bytes: int, d_out_loc: int, d_status: int, d_result: int, stream: int = 0) -> None:
+    """``dev_store_guard_rebuild`` with the second syndrome: two listed extents that meet in a guard byte are both rebuilt, and
+    d_status[k] = 1 only when three different listed bytes meet in one.  d_result[0..5) = verdict, total bytes, positions, positions
+    rebuilt, the rebuilt positions that needed Q.  Not synchronised."""
+    check(lib().cw_dev_store_guard2_rebuild(d_store or None, store_bytes, d_dir, dir_base, dir_entries, d_covered, stripe, group, d_guard_p, d_guard_q,
+                                            guard_bytes, d_values, d_count, max_count, d_out or None, out_bytes, d_out_loc, d_status, d_result, stream))
+
+
 class Store(C.Structure):
     """cw_store: the caller-owned triple of the chunk store (bytes, cursor, directory) as one argument."""
     _fields_ = [("d_store", C.c_void_p), ("store_bytes", C.c_size_t), ("d_used", C.c_void_p), ("d_dir", C.c_void_p),

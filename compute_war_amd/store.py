@@ -13,7 +13,7 @@ import numpy as np
 
 from ._lib import CwError, lib
 from .ops import (ACCOUNT_DTYPE, DELTA_OP_DTYPE, CdcParams, ChunkLoc, DedupeIndex, DeltaOp, Store, _comp_id, _hash_id, _np_u8, chunk_slots_bytes,
-                  dev_apply_delta, dev_hash_chunks, dev_read_ranges, dev_recipe_diff, dev_restore_chunks, dev_store_account, dev_store_chunks, dev_store_compact, dev_store_export_chunks, dev_store_guard_check, dev_store_guard_rebuild, dev_store_guard_update, dev_store_import_chunks, dev_store_mark,
+                  dev_apply_delta, dev_hash_chunks, dev_read_ranges, dev_recipe_diff, dev_restore_chunks, dev_store_account, dev_store_chunks, dev_store_compact, dev_store_export_chunks, dev_store_guard_check, dev_store_guard_rebuild, dev_store_guard_update, dev_store_guard2_check, dev_store_guard2_rebuild, dev_store_guard2_update, dev_store_import_chunks, dev_store_mark,
                   dev_store_renumber, dev_store_replace_chunks, dev_scatter_extents, dev_translate_refs, device_count, digest_bytes, init, store_guard_bytes, store_ingest,
                   store_compose, store_ingest_streams, store_patch, store_restore, store_scrub)
 
@@ -272,11 +272,15 @@ class ChunkStore:
     in one call) are thin forms of it -- and ``last_compose`` holds its statistics (cw_compose_stats as a dict).
     ``protect`` puts XOR guard stripes over the stored bytes: every method that appends then ends with one
     queued guard update, ``guard_check`` says which groups of stripes no longer match, and ``repair_local`` rebuilds the chunks a scrub
-    found damaged from the guard, in place and without a peer."""
+    found damaged from the guard, in place and without a peer.  ``protect(parity=2)`` keeps a second, GF(2^8)-weighted syndrome beside
+    the XOR one (section 29): two damaged chunks that meet in a guard byte are then both rebuilt, and ``last_repair`` says how many
+    chunks of the last ``repair_local`` needed it."""
     last_stats = None
     last_patch = None
     last_compose = None
+    last_repair = None
     d_guard = None  # the guard, with its cursor (d_covered) and its geometry (stripe, group), while the store is protected
+    d_guard_q = None  # the second syndrome of a parity-2 store, as large as d_guard
 
     def __init__(self, index: DedupeIndex, comp_alg, params: CdcParams, store_bytes: int, dir_entries: int, dir_base: int = 0):
         import torch
@@ -296,22 +300,32 @@ class ChunkStore:
     def used(self) -> int:
         return int(self.d_used.item())
 
-    def protect(self, stripe: int = 65536, group: int = 16) -> None:
+    def protect(self, stripe: int = 65536, group: int = 16, parity: int = 1) -> None:
         """Put guard stripes over the store: a guard of store_bytes / group bytes and its cursor, then one
         update that folds in the bytes [0, used()).  ``stripe`` is a power of two in [65536, 2^30], ``group`` in [1, 256].  A store
-        that is protected already gets a fresh guard of the new geometry."""
+        that is protected already gets a fresh guard of the new geometry.  ``parity=2`` adds the second syndrome (section 29): a
+        second buffer of the same size, and ``group`` in [1, 255]."""
         import torch
         size = store_guard_bytes(max(self.store_bytes, 1), stripe, group)
         if size == 0:
             raise ValueError(f"stripe {stripe} is no power of two in [65536, 2^30] or group {group} is not in [1, 256]")
+        if parity not in (1, 2):
+            raise ValueError(f"parity {parity} is neither 1 nor 2")
+        if parity == 2 and group > 255:
+            raise ValueError(f"group {group} is not in [1, 255], the dual guard's bound")
         self.stripe, self.group = int(stripe), int(group)
         self.d_guard, self.d_covered, self._fold_result = _zeros(size, torch.uint8), _zeros(1), _zeros(4)
+        self.d_guard_q = _zeros(size, torch.uint8) if parity == 2 else None
         torch.cuda.synchronize()  # (torch zeroed them on its own stream)
         self._fold()
 
     def _fold(self) -> None:
         """The one guard update: queued, not synchronised.  Nothing when the store is not protected."""
-        if self.d_guard is not None:
+        if self.d_guard_q is not None:
+            dev_store_guard2_update(self.d_store.data_ptr(), self.store_bytes, self.d_used.data_ptr(), self.d_covered.data_ptr(), self.stripe,
+                                    self.group, self.d_guard.data_ptr(), self.d_guard_q.data_ptr(), self.d_guard.numel(),
+                                    self._fold_result.data_ptr(), self._stream())
+        elif self.d_guard is not None:
             dev_store_guard_update(self.d_store.data_ptr(), self.store_bytes, self.d_used.data_ptr(), self.d_covered.data_ptr(), self.stripe,
                                    self.group, self.d_guard.data_ptr(), self.d_guard.numel(), self._fold_result.data_ptr(), self._stream())
 
@@ -320,22 +334,30 @@ class ChunkStore:
         returned; 0 for a store that is not protected."""
         return 0 if self.d_guard is None else int(self.d_covered.item())
 
-    def guard_check(self) -> tuple:
+    def guard_check(self, detail: bool = False) -> tuple:
         """(count, groups): how many groups of stripes below the cursor differ from the guard, and which (``dev_store_guard_check``).
-        A group differs when a stored byte in it changed, live or not, or a byte of the guard itself."""
+        A group differs when a stored byte in it changed, live or not, or a byte of the guard itself.  With ``detail``, a third
+        element: for each of those groups, bit 0 when the XOR guard differs and bit 1 when the second syndrome of a parity-2 store
+        does -- a changed stored byte sets both, a changed guard byte its own."""
         import torch
         self._need_guard()
         groups = self.d_guard.numel() // self.stripe
         bad, result = _zeros(groups, torch.int32), _zeros(4)
         torch.cuda.synchronize()
-        dev_store_guard_check(self.d_store.data_ptr(), self.store_bytes, self.d_covered.data_ptr(), self.stripe, self.group, self.d_guard.data_ptr(),
-                              self.d_guard.numel(), bad.data_ptr(), result.data_ptr(), self._stream())
+        if self.d_guard_q is not None:
+            dev_store_guard2_check(self.d_store.data_ptr(), self.store_bytes, self.d_covered.data_ptr(), self.stripe, self.group,
+                                   self.d_guard.data_ptr(), self.d_guard_q.data_ptr(), self.d_guard.numel(), bad.data_ptr(), result.data_ptr(),
+                                   self._stream())
+        else:
+            dev_store_guard_check(self.d_store.data_ptr(), self.store_bytes, self.d_covered.data_ptr(), self.stripe, self.group,
+                                  self.d_guard.data_ptr(), self.d_guard.numel(), bad.data_ptr(), result.data_ptr(), self._stream())
         torch.cuda.synchronize()
         verdict, checked, differ, _ = _words(result)
         if verdict:
             raise CwError(-4, f"chunk store: the guard's cursor {self.protected_bytes()} lies above the store's {self.store_bytes} bytes")
-        which = np.nonzero(bad.cpu().numpy()[:checked])[0].tolist()
-        return differ, which
+        bits = bad.cpu().numpy()[:checked]
+        which = np.nonzero(bits)[0].tolist()
+        return (differ, which, bits[which].tolist()) if detail else (differ, which)
 
     def _need_guard(self) -> None:
         if self.d_guard is None:
@@ -812,7 +834,7 @@ class ChunkStore:
         removed = self.index.retain(live.data_ptr(), self.dir_base, n)
         self.d_store, self.d_used, self.d_dir, self.store_bytes = new_store, new_used, new_dir, store_bytes
         if self.d_guard is not None:
-            self.protect(self.stripe, self.group)  # every kept byte moved: a fresh guard over the new store
+            self.protect(self.stripe, self.group, 2 if self.d_guard_q is not None else 1)  # every kept byte moved: a fresh guard over the new store
         return dict(kept=kept, dropped=dropped, bytes_before=bytes_before, bytes_after=needed, removed=removed)
 
     def renumber(self, recipes, dir_entries: int | None = None, dir_base: int | None = None) -> list:
@@ -1165,9 +1187,12 @@ class ChunkStore:
         other), when its entry is missing, unsound or ends above ``protected_bytes()`` (``unprotected``), or, with ``verify``, when
         the rebuilt bytes do not decode or do not hash to the digest this index holds (``failed``: damage the report does not name,
         in the guard or in another chunk of the group).  Returns dict(repaired, collided, unprotected, failed, no_digest): lists of
-        values; no_digest are the damaged values this index holds no digest for, which are skipped.  The index is never written."""
+        values; no_digest are the damaged values this index holds no digest for, which are skipped.  The index is never written.
+        On a parity-2 store (``dev_store_guard2_rebuild``) two damaged chunks that meet in a guard byte are both rebuilt, and
+        ``collided`` means three or more in one; ``last_repair`` = dict(paired): how many rebuilt chunks had such a partner."""
         import torch
         self._need_guard()
+        self.last_repair = dict(paired=0)
         damaged = np.unique(np.ascontiguousarray(report.damaged, dtype=np.uint64))
         out = dict(repaired=[], collided=[], unprotected=[], failed=[], no_digest=[])
         if len(damaged) == 0:
@@ -1186,13 +1211,20 @@ class ChunkStore:
         has = val.cpu().numpy().view(np.uint64)[:m] != _MISS
         out["no_digest"] = damaged[~has].tolist()
         # 2. the rebuild: a dry run that sizes the payload, then the run that fills it
-        d_val, d_count, d_loc, d_status, result = _u64(damaged), _u64([m]), _zeros(m * 2), _zeros(m, torch.int32), _zeros(4)
+        d_val, d_count, d_loc, d_status, result = _u64(damaged), _u64([m]), _zeros(m * 2), _zeros(m, torch.int32), _zeros(5)
         payload, total = None, 0
         for dry in (True, False):
             torch.cuda.synchronize()
-            dev_store_guard_rebuild(self.d_store.data_ptr(), self.store_bytes, self.d_dir.data_ptr(), self.dir_base, n, self.d_covered.data_ptr(),
-                                    self.stripe, self.group, self.d_guard.data_ptr(), self.d_guard.numel(), d_val.data_ptr(), d_count.data_ptr(), m,
-                                    0 if dry else payload.data_ptr(), total, d_loc.data_ptr(), d_status.data_ptr(), result.data_ptr(), s)
+            if self.d_guard_q is not None:
+                dev_store_guard2_rebuild(self.d_store.data_ptr(), self.store_bytes, self.d_dir.data_ptr(), self.dir_base, n,
+                                         self.d_covered.data_ptr(), self.stripe, self.group, self.d_guard.data_ptr(), self.d_guard_q.data_ptr(),
+                                         self.d_guard.numel(), d_val.data_ptr(), d_count.data_ptr(), m, 0 if dry else payload.data_ptr(), total,
+                                         d_loc.data_ptr(), d_status.data_ptr(), result.data_ptr(), s)
+            else:
+                dev_store_guard_rebuild(self.d_store.data_ptr(), self.store_bytes, self.d_dir.data_ptr(), self.dir_base, n,
+                                        self.d_covered.data_ptr(), self.stripe, self.group, self.d_guard.data_ptr(), self.d_guard.numel(),
+                                        d_val.data_ptr(), d_count.data_ptr(), m, 0 if dry else payload.data_ptr(), total, d_loc.data_ptr(),
+                                        d_status.data_ptr(), result.data_ptr(), s)
             torch.cuda.synchronize()
             verdict, needed = _words(result, 2)
             if verdict == 2:
@@ -1201,6 +1233,7 @@ class ChunkStore:
                 payload, total = _zeros(needed, torch.uint8), needed
             elif verdict:
                 raise CwError(-4, f"chunk store: the rebuild of {total} bytes was refused with verdict {verdict} after its dry run")
+        self.last_repair = dict(paired=_words(result, 5)[4])
         status = d_status.cpu().numpy().view(np.uint32)[:m]
         out["collided"], out["unprotected"] = damaged[has & (status == 1)].tolist(), damaged[has & (status == 2)].tolist()
         which = np.nonzero(has & (status == 0))[0]
@@ -1237,7 +1270,7 @@ class ChunkStore:
 
     def save(self, path) -> None:
         """One ``.npz``: the index's export, the store bytes [0, used), the directory, base and the parameters; of a protected store
-        also the guard (the groups below its cursor), the cursor and the geometry."""
+        also the guard (the groups below its cursor), the cursor and the geometry, and of a parity-2 store the second syndrome."""
         dig, val = self.index.export()
         guard = {}
         if self.d_guard is not None:
@@ -1245,6 +1278,8 @@ class ChunkStore:
             held = -(-covered // (self.stripe * self.group)) * self.stripe
             guard = dict(guard=self.d_guard[:held].cpu().numpy(), guard_covered=np.uint64(covered),
                          guard_geometry=np.array([self.stripe, self.group], np.uint64))
+            if self.d_guard_q is not None:
+                guard["guard_q"] = self.d_guard_q[:held].cpu().numpy()
         p = self.params
         gear = p._gear if getattr(p, "_gear", None) is not None else np.zeros(0, np.uint64)
         with open(path, "wb") as f:
@@ -1278,6 +1313,12 @@ class ChunkStore:
                     cs.stripe, cs.group = stripe, group
                     cs.d_guard, cs.d_covered, cs._fold_result = _zeros(size, torch.uint8), _u64([int(z["guard_covered"])]), _zeros(4)
                     cs.d_guard[:len(held)] = torch.from_numpy(held).cuda()
+                    if "guard_q" in z.files:
+                        if len(z["guard_q"]) != len(held) or group > 255:
+                            raise CwError(-2, f"chunk store: the snapshot's second syndrome ({len(z['guard_q'])} bytes, group {group}) does not "
+                                              f"match its guard of {len(held)} bytes")
+                        cs.d_guard_q = _zeros(size, torch.uint8)
+                        cs.d_guard_q[:len(held)] = torch.from_numpy(z["guard_q"]).cuda()
                 torch.cuda.synchronize()
             except Exception:
                 index.close()

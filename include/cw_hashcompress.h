@@ -1179,6 +1179,57 @@ int cw_dev_store_guard_rebuild(const void *d_store, size_t store_bytes, const cw
                                const uint64_t *d_values, const uint64_t *d_count, size_t max_count, void *d_out, size_t out_bytes,
                                cw_chunk_loc *d_out_loc, uint32_t *d_status /* [max_count] */, uint64_t *d_result /* [4] */, void *stream);
 
+/* ---- the dual guard: a second syndrome, so two damaged chunks that meet in a guard byte are both rebuilt ----
+ * Beside the XOR guard P = d_guard_p, which is exactly the d_guard of the calls above, a second buffer Q = d_guard_q of the same
+ * size, cw_store_guard_bytes.  The field is GF(2^8) with the polynomial x^8 + x^4 + x^3 + x^2 + 1 (0x11D) and the generator 2; with
+ * m = (p / S) % G the member of store byte p,
+ *     d_guard_q[g * S + c] = the XOR of 2^m (x) d_store[p] over all p < covered with p / W == g and p % S == c.
+ * 2 has order 255, so the members' weights differ only for G <= 255: the dual calls refuse group = 256.  A guard cell then gives
+ * back two unknown bytes: with the unknown bytes of a cell in members m and o, and P', Q' the cell's guard bytes less every known
+ * member's byte below the cursor,  D_m = (Q' ^ 2^o (x) P') (x) inv(2^m ^ 2^o);  with one unknown, D_m = P'.  One cursor serves both
+ * buffers.  The three calls follow the conventions of the guard calls above and refuse what they refuse (d_guard_p in d_guard's
+ * place, reported under d_guard's name); also, with CW_ERR_BAD_ARG before anything is launched: group > 255, a NULL d_guard_q, one
+ * that is not 16-byte aligned, [d_guard_q, +guard_bytes) overlapping the store or [d_guard_p, +guard_bytes).                       */
+#define CW_GUARD2_MAX_GROUP 255u
+/* cw_dev_store_guard_update for both buffers: folds d_store[from, to), from = *d_covered and to = *d_used, into P and Q, then sets
+ * *d_covered = to.  d_result[4] and the verdict are cw_dev_store_guard_update's, and the P bytes written are bit for bit what that
+ * call writes for the same arguments.  One lane owns the two 16-byte guard words of a (group, column word) the range touches, loads
+ * the at most G store words behind them from the highest member down, masks the bytes outside the range, accumulates Q by Horner's
+ * rule with the doubling done on packed dwords, and does two read-modify-writes; there are no tables and no atomics, and the cursor is
+ * written by a second kernel.  Whatever the cursors hold, no load leaves d_store[from, to) or the P and Q words of the groups of
+ * [from, to), and no store leaves those words, *d_covered and d_result.  No scratch.                                              */
+int cw_dev_store_guard2_update(const void *d_store, size_t store_bytes, const uint64_t *d_used, uint64_t *d_covered /* in/out */,
+                               size_t stripe, unsigned group, void *d_guard_p, void *d_guard_q, size_t guard_bytes,
+                               uint64_t *d_result /* [4] */, void *stream);
+/* cw_dev_store_guard_check for both buffers.  d_group_bad[g] (u32 per group below N, may be NULL) = bit 0 when a P word of the group
+ * differs, bit 1 when a Q word does: a changed store byte sets both, a changed guard byte its own.  d_result[4] = {verdict, N, the
+ * groups with any bit, the lowest such group or ~0}.  Nothing else is written, and no load leaves d_store[0, *d_covered) or the P and
+ * Q bytes of those groups.  Scratch, per stream: 64 + 8 * ceil(store_bytes / W).                                                  */
+int cw_dev_store_guard2_check(const void *d_store, size_t store_bytes, const uint64_t *d_covered, size_t stripe, unsigned group,
+                              const void *d_guard_p, const void *d_guard_q, size_t guard_bytes, uint32_t *d_group_bad /* may be NULL */,
+                              uint64_t *d_result /* [4] */, void *stream);
+/* cw_dev_store_guard_rebuild with the second syndrome: positions, the statuses' meaning, d_out, d_out_loc and the verdicts are that
+ * call's, except that
+ *   1 (collides)     some guard cell of the extent holds three or more DIFFERENT store bytes of the protected listed extents (its own
+ *                    among them): three different members cover that column of that group.  A value named twice and overlapping
+ *                    entries of one stripe are the same member and never count against each other.  Still a symmetric "exists".
+ *   0 (rebuilt)      every byte by the formula above: every other protected listed byte of its cell counts as unknown, whether or not
+ *                    that other position is itself rebuilt, and every other member's byte below *d_covered as known.
+ * d_result[5] = {verdict, the total bytes, n, the positions rebuilt, the rebuilt positions that have a partner in some cell -- those
+ * that needed Q}; the fifth word is counted whatever the verdict is.  While it runs, a rebuilt position's place in d_out holds a
+ * byte per byte of working state; with a verdict other than 0 no byte of d_out and no d_out_loc changes.  The work is linear in n and
+ * in the rebuilt bytes plus, per piece of a position (at most two), its group's listed pieces once, once more for each of them that
+ * overlaps it, and the overlapped columns once per overlapping piece.  Whatever the buffers hold, no load leaves
+ * d_store[0, *d_covered), the two guards, d_dir[0..dir_entries), d_values[0..n) or the rebuilt extents' places in d_out, and no store
+ * leaves those places, d_out_loc[0..n), d_status[0..n) and d_result.  CW_ERR_BAD_ARG also for what cw_dev_store_guard_rebuild refuses,
+ * and [d_out, +out_bytes) overlapping either guard.  Scratch, per stream: 80 + 28 * max_count + 16 * ceil(store_bytes / W) bytes,
+ * as for the single guard.                                                                                                        */
+int cw_dev_store_guard2_rebuild(const void *d_store, size_t store_bytes, const cw_chunk_loc *d_dir, uint64_t dir_base, size_t dir_entries,
+                                const uint64_t *d_covered, size_t stripe, unsigned group, const void *d_guard_p, const void *d_guard_q,
+                                size_t guard_bytes, const uint64_t *d_values, const uint64_t *d_count, size_t max_count, void *d_out,
+                                size_t out_bytes, cw_chunk_loc *d_out_loc, uint32_t *d_status /* [max_count] */, uint64_t *d_result /* [5] */,
+                                void *stream);
+
 /* plain device memory on the calling thread's device, for C callers of cw_dev_* (the host programs link no HIP runtime) */
 void *cw_dev_alloc(size_t bytes);                                   /* NULL on failure */
 void  cw_dev_free(void *d_p);
