@@ -106,7 +106,7 @@ def rebuild(store, store_bytes: int, directory, dir_base: int, covered: int, S: 
     lc = cells(lb, S, G)
     cell, count = np.unique(lc, return_counts=True)
     hot = cell[count > 2]
-    out, locs, paired = [], np.zeros(n, RM.LOC), 0
+    out, locs, paired, at = [], np.zeros(n, RM.LOC), 0, 0
     for k, e in enumerate(ext):
         if e is None:
             continue
@@ -130,9 +130,10 @@ def rebuild(store, store_bytes: int, directory, dir_base: int, covered: int, S: 
         wm, wo = POW[members(p[two], S, G)], POW[members(other[two], S, G)]
         v[two] = MUL[qq[two] ^ MUL[wo, pp[two]], INV[wm ^ wo]]
         paired += bool(two.any())
-        locs[k] = (sum(len(o) for o in out), e[1], int(directory[values[k] - dir_base]["raw"]))
+        locs[k] = (at, e[1], int(directory[values[k] - dir_base]["raw"]))
         out.append(v)
-    total, rebuilt = sum(len(o) for o in out), int((status == REBUILT).sum())
+        at += len(v)
+    total, rebuilt = at, int((status == REBUILT).sum())
     if total > out_bytes:
         return [1, total, n, rebuilt, paired], status, None, None
     return [0, total, n, rebuilt, paired], status, np.concatenate(out) if out else np.zeros(0, np.uint8), locs
@@ -147,14 +148,15 @@ def update_range_255():
     return 255 * S - 4099, 255 * S + 5003
 
 
-def rebuild_cases(G: int, store_bytes: int = STORE_BYTES):
+def rebuild_cases(G: int, store_bytes: int = STORE_BYTES, S: int = S, single: bool = None):
     """{name: (directory entries, values, covered, the statuses wanted, the positions that need Q)}: guard_model's cases -- "one shared
     column" now rebuilds all three -- and the ones the second syndrome adds.  dir_base 0; statuses and the need for Q are the cases'
-    own claims, which the tests hold against the two brute-force rebuilds."""
+    own claims, which the tests hold against the two brute-force rebuilds.  ``single`` says whether guard_model's cases are among them:
+    by default, over the store of 6 stripes and 37 bytes only."""
     W, full = G * S, store_bytes
     c = {}
-    if store_bytes == STORE_BYTES:
-        for name, (entries, values, covered, wanted) in GM.rebuild_cases(G).items():
+    if store_bytes == STORE_BYTES and S == GM.S if single is None else single:
+        for name, (entries, values, covered, wanted) in GM.rebuild_cases(G, S, store_bytes).items():
             c[name] = (entries, values, covered, wanted, [])
         if G > 1:
             e, v, cov, _, _ = c["one shared column"]

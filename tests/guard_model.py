@@ -97,7 +97,7 @@ def rebuild(store, store_bytes: int, directory, dir_base: int, covered: int, S: 
     if listed:
         cell, count = np.unique(cells(np.unique(np.concatenate(listed)), S, G), return_counts=True)
         hot = cell[count > 1]
-    out, locs = [], np.zeros(n, RM.LOC)
+    out, locs, at = [], np.zeros(n, RM.LOC), 0
     for k, e in enumerate(ext):
         if e is None:
             continue
@@ -111,9 +111,10 @@ def rebuild(store, store_bytes: int, directory, dir_base: int, covered: int, S: 
             q = p // W * W + m * S + p % S
             take = (q < covered) & (q != p)
             v[take] ^= store[q[take]]
-        locs[k] = (sum(len(o) for o in out), e[1], int(directory[values[k] - dir_base]["raw"]))
+        locs[k] = (at, e[1], int(directory[values[k] - dir_base]["raw"]))
         out.append(v)
-    total, rebuilt = sum(len(o) for o in out), int((status == REBUILT).sum())
+        at += len(v)
+    total, rebuilt = at, int((status == REBUILT).sum())
     if total > out_bytes:
         return [1, total, n, rebuilt], status, None, None
     return [0, total, n, rebuilt], status, np.concatenate(out) if out else np.zeros(0, np.uint8), locs
@@ -128,9 +129,9 @@ def entry(pos: int, stored: int):
     return (pos, stored, RM.RAW | (stored & RM.LEN_MASK))
 
 
-def update_ranges(G: int):
-    """{name: (covered, used)} over a store of 6 stripes and 37 bytes."""
-    W = G * S
+def update_ranges(G: int, S: int = S, store_bytes: int = None):
+    """{name: (covered, used)} over a store of 6 stripes and 37 bytes, or of ``store_bytes`` >= 2 * S + 1002."""
+    W, store_bytes = G * S, 6 * S + 37 if store_bytes is None else store_bytes
     r = {}
     for n in (1, 15, 16, 17):
         for at in (0, 1, 15):
@@ -139,8 +140,9 @@ def update_ranges(G: int):
     r["across a stripe boundary"] = (S - 1000, S + 1001)
     r["across a group boundary"] = (W - 77, W + 33)
     r["W bytes"] = (S // 2 + 5, S // 2 + 5 + W)
-    r["more than W bytes"] = (3, W + S + 900)
-    r["everything"] = (0, STORE_BYTES)
+    r["more than W bytes"] = (3, min(W + S + 900, store_bytes))
+    r["everything"] = (0, store_bytes)
+    assert all(a <= b <= store_bytes for a, b in r.values()), (G, S, store_bytes)
     r["nothing"] = (S + 7, S + 7)
     return r
 
@@ -148,14 +150,17 @@ def update_ranges(G: int):
 STORE_BYTES = 6 * S + 37
 
 
-def rebuild_cases(G: int):
-    """{name: (directory entries, values, covered, the statuses wanted)} over a store of 6 stripes and 37 bytes, dir_base 0; the
-    statuses are the cases' own claim, which the tests hold against the brute-force rebuild."""
+def rebuild_cases(G: int, S: int = S, store_bytes: int = None):
+    """{name: (directory entries, values, covered, the statuses wanted)} over a store of 6 stripes and 37 bytes, or of ``store_bytes``
+    >= max(6 * S, G * S + S); dir_base 0; the statuses are the cases' own claim, which the tests hold against the brute-force rebuild."""
     W = G * S
-    full = STORE_BYTES
+    full = 6 * S + 37 if store_bytes is None else store_bytes
+    assert full >= max(6 * S, W + S), (G, S, full)
     c = {}
     c["one byte"] = ([entry(S + 5, 1)], [0], full, [0])
-    c["S bytes from mid-stripe"] = ([entry(S // 2 + 3, S)], [0], full, [0])
+    c["S bytes from mid-stripe"] = ([entry(S // 2 + 3, min(S, 65536))], [0], full, [0])
+    if S > 65536:
+        c["65536 bytes from the last column"] = ([entry(S - 1, 65536)], [0], full, [0])
     c["across a stripe boundary"] = ([entry(S - 700, 1500)], [0], full, [0])
     c["across a group boundary"] = ([entry(W - 901, 2000)], [0], full, [0])
     # two extents of one group, in different stripes, whose columns touch but do not overlap
@@ -167,4 +172,10 @@ def rebuild_cases(G: int):
     c["ends at covered"] = ([entry(4 * S + 10, 990)], [0], 4 * S + 1000, [0])
     c["ends above covered"] = ([entry(4 * S + 10, 991)], [0], 4 * S + 1000, [2])
     c["unprotected"] = ([(0, 0, 0), (S, 0, RM.RAW | 5), entry(5 * S, 100)], [0, 1, 7, RM.MISS, 2], full, [2, 2, 2, 2, 0])
+    if G == G_MAX:
+        # the two highest members at disjoint columns, then with columns in common; the last member into the next group beside member 254
+        c["members 254 and 255"] = ([entry(254 * S + 70, 4000), entry(255 * S + 5000, 4000)], [0, 1], full, [0, 0])
+        c["members 254 and 255 collide"] = ([entry(254 * S + 70, 4000), entry(255 * S + 2000, 4000)], [0, 1], full, [1, 1])
+        c["from member 255 into the next group"] = ([entry(W - 600, 1500), entry(254 * S + 62000, 500)], [0, 1], full, [0, 0])
+        c["from member 255 into the next group, colliding"] = ([entry(W - 600, 1500), entry(255 * S - 300, 200)], [0, 1], full, [1, 1])
     return c

@@ -1,7 +1,9 @@
 """The whole chunk store in plain Python, and the life-cycle scripts that run on it and on ``cw.ChunkStore``.
 
 ``Store`` is ``restore_model.Model`` (blob, directory, ``values`` keyed by content) with what ``ChunkStore`` keeps beside its buffers:
-``base``, ``dir_base``, the directory's size, ``store_bytes``, ``max_entries`` and the live named streams (name -> bytes, refs, cuts).
+``base``, ``dir_base``, the directory's size, ``store_bytes``, ``max_entries``, the live named streams (name -> bytes, refs, cuts) and,
+once ``protect`` has been called, the guard: (stripe, group, parity, P, Q or None, covered), kept by guard_model / guard2_model's
+``update``, read by their ``check`` and ``rebuild``.
 Every method mirrors a ``ChunkStore`` call and composes the model of that call -- it restates none of them -- and returns a dict with
 ``code``: 0, or the CwError code of a refusal, after which nothing has changed where the header says nothing changes.  A refused
 one-shot ``ingest`` / ``ingest_many`` leaves the index as it was, too.  The module never imports the package under test.
@@ -13,6 +15,7 @@ GPU test share.  A recipe is either current or wholly stale in these scripts (``
 model refuses a call on a stale recipe by restoring the whole recipe, not only the positions the call reads."""
 from __future__ import annotations
 
+import functools
 import os
 
 import numpy as np
@@ -21,6 +24,8 @@ import account_model as AM
 import cdc_model as CM
 import compose_model as XM
 import delta_model as DM
+import guard2_model as G2
+import guard_model as G1
 import ingest_model as IM
 import patch_model as PM
 import read_model as RD
@@ -49,6 +54,30 @@ def ok(**kw):
     return dict(code=0, **kw)
 
 
+class Guard:
+    """What ``protect`` keeps: (stripe, group, parity, P, Q or None, covered).  A fresh one is all zero with its cursor at 0."""
+
+    def __init__(self, stripe, group, parity, store_bytes):
+        size = G1.guard_bytes(max(store_bytes, 1), stripe, group)
+        assert size and parity in (1, 2) and (parity == 1 or G2.geometry_ok(stripe, group)), (stripe, group, parity)
+        self.stripe, self.group, self.parity, self.covered = stripe, group, parity, 0
+        self.P, self.Q = np.zeros(size, np.uint8), np.zeros(size, np.uint8) if parity == 2 else None
+
+    def state(self):
+        return self.stripe, self.group, self.parity, self.P.tobytes(), None if self.Q is None else self.Q.tobytes(), self.covered
+
+
+def _folds(method):
+    """A Store method that mirrors an appending ChunkStore method: it ends, refused or not, with one guard update."""
+    @functools.wraps(method)
+    def appending(self, *args, **kwargs):
+        try:
+            return method(self, *args, **kwargs)
+        finally:
+            self._fold()
+    return appending
+
+
 class Store:
     def __init__(self, oracle, alg, store_bytes, dir_entries, dir_base=0, max_entries=1 << 14, p=P):
         self.m = RM.Model(oracle, alg, store_bytes, dir_entries, dir_base)
@@ -56,7 +85,10 @@ class Store:
         self.streams, self.stale = {}, {}
         self.made = set()                        # the contents of every stream made since the last compact, and of the kept ones
         self.hurt = set()                        # the values ``corrupt`` has flipped a byte of and no repair has replaced
-        self.last_patch = self.last_compose = None
+        self.last_patch = self.last_compose = self.last_repair = None
+        self.guard = None                        # a Guard while the store is protected
+        self.flipped = set()                     # what has been flipped since the last ``protect`` and not put back: stored positions, and
+        #                                          (which, at) of the guard -- while it is empty, the guard is exact
 
     # ---- state ------------------------------------------------------------------------------------------------------------------
     @property
@@ -84,7 +116,8 @@ class Store:
 
     def snapshot(self):
         return (bytes(self.m.blob), self.m.directory.tobytes(), tuple(sorted(self.m.values.items())), self.base, self.dir_base, self.dir_entries,
-                self.store_bytes, tuple(sorted((n, tuple(s.refs), tuple(s.cuts)) for n, s in self.streams.items())))
+                self.store_bytes, tuple(sorted((n, tuple(s.refs), tuple(s.cuts)) for n, s in self.streams.items())),
+                None if self.guard is None else self.guard.state())
 
     def _get(self, name):
         return self.streams[name] if name in self.streams else self.stale[name]
@@ -108,6 +141,86 @@ class Store:
             return dict(code=-5, why="store")
         return None
 
+    # ---- the guard --------------------------------------------------------------------------------------------------------------
+    def _stored(self):
+        return np.frombuffer(bytes(self.m.blob), np.uint8)
+
+    def protect(self, stripe=65536, group=16, parity=1):
+        """a fresh guard, also over one that is there, and one fold of [0, used)"""
+        self.guard = Guard(stripe, group, parity, self.store_bytes)
+        self.flipped = set()
+        self._fold()
+        return ok()
+
+    def _fold(self):
+        g = self.guard
+        if g is None:
+            return
+        if g.Q is None:
+            result, g.covered = G1.update(g.P, self._stored(), self.store_bytes, self.used, g.covered, g.stripe, g.group)
+        else:
+            result, g.covered = G2.update(g.P, g.Q, self._stored(), self.store_bytes, self.used, g.covered, g.stripe, g.group)
+        assert result[0] == 0 and g.covered == self.used, result
+
+    def guard_check(self, detail=True):
+        g = self.guard
+        if g.Q is None:
+            result, bits = G1.check(g.P, self._stored(), self.store_bytes, g.covered, g.stripe, g.group)
+        else:
+            result, bits = G2.check(g.P, g.Q, self._stored(), self.store_bytes, g.covered, g.stripe, g.group)
+        assert result[0] == 0
+        which = np.nonzero(bits)[0].tolist()
+        return ok(count=result[2], groups=which, bits=bits[which].tolist())
+
+    def corrupt_guard(self, which, at):
+        """not a ChunkStore call: byte ``at`` of P (which = 0) or Q (1) is flipped"""
+        (self.guard.P, self.guard.Q)[which][at] ^= 0xFF
+        self.flipped ^= {(which, at)}
+        return ok(at=at)
+
+    def repair_local(self, damaged, verify=True):
+        g = self.guard
+        damaged = sorted(set(int(v) for v in damaged))
+        self.last_repair = dict(paired=0)
+        out = dict(repaired=[], collided=[], unprotected=[], failed=[], no_digest=[])
+        if not damaged:
+            return ok(**out, paired=0)
+        if damaged[0] < self.dir_base or damaged[-1] >= self.dir_base + self.dir_entries:
+            return dict(code=-2)
+        by_value = {v: c for c, v in self.m.values.items()}
+        out["no_digest"] = [v for v in damaged if v not in by_value]
+        if g.Q is None:
+            result, status, payload, locs = G1.rebuild(self._stored(), self.store_bytes, self.m.directory, self.dir_base, g.covered, g.stripe, g.group,
+                                                       g.P, damaged, 1 << 62)
+        else:
+            result, status, payload, locs = G2.rebuild(self._stored(), self.store_bytes, self.m.directory, self.dir_base, g.covered, g.stripe, g.group,
+                                                       g.P, g.Q, damaged, 1 << 62)
+            self.last_repair = dict(paired=result[4])
+        assert result[0] == 0
+        held = [(k, v) for k, v in enumerate(damaged) if v in by_value]
+        out["collided"] = [v for k, v in held if status[k] == G1.COLLIDES]
+        out["unprotected"] = [v for k, v in held if status[k] == G1.UNPROTECTED]
+        # the rebuilt ones in ascending pos: good when the payload decodes to the content the index holds, and not in front of the end
+        # of the good one before it
+        rebuilt = sorted((int(self.m.directory[v - self.dir_base]["pos"]), k, v) for k, v in held if status[k] == G1.REBUILT)
+        end = 0
+        for pos, k, v in rebuilt:
+            at, stored, word = (int(x) for x in locs[k])
+            good = pos >= end
+            if good and verify:
+                want = by_value[v]
+                (st, piece), = RM.restore(payload, len(payload), locs, 0, [k], [0, len(want)], len(want), self.m.decode())
+                good = st == 0 and piece == want
+            if good:
+                self.m.blob[pos:pos + stored] = payload[at:at + stored].tobytes()
+                self.flipped -= set(range(pos, pos + stored))
+                end = pos + stored
+            out["repaired" if good else "failed"].append(v)
+        out["repaired"].sort()
+        out["failed"].sort()
+        self.hurt -= set(out["repaired"])
+        return ok(**out, paired=self.last_repair["paired"])
+
     # ---- ingest -----------------------------------------------------------------------------------------------------------------
     def _one_shot(self, data: bytes, cuts):
         """ONE fused call and ONE cw_dev_store_chunks: (refs, new, stored bytes), or the refusal with the index put back"""
@@ -120,6 +233,7 @@ class Store:
         self.base += len(cuts) - 1
         return refs, new, total
 
+    @_folds
     def ingest(self, name, data):
         cuts = CM.chunk(data, self.p) if len(data) else [0]
         got = self._one_shot(data, cuts)
@@ -128,6 +242,7 @@ class Store:
         self._make(name, data, got[0], cuts)
         return ok(new_chunks=len(got[1]), stored_bytes=got[2])
 
+    @_folds
     def ingest_many(self, names, datas):
         data, cuts, first = XM.join([bytes(d) for d in datas], self.p)
         got = self._one_shot(data, cuts)
@@ -138,12 +253,14 @@ class Store:
             self._make(name, d, got[0][a:b], [c - cuts[a] for c in cuts[a:b + 1]])
         return ok(new_chunks=len(got[1]), stored_bytes=got[2])
 
+    @_folds
     def ingest_stream(self, name, data, piece):
         r = IM.ingest(self.m, data, self.p, piece, self.base, self.max_entries)
         self.base += r.nchunks
         self._make(name, data[:r.consumed], r.refs, r.offsets)
         return dict(code=-5 if r.refused else 0, why=r.refused, run=r, stats=r.stats)
 
+    @_folds
     def ingest_many_stream(self, names, datas, piece):
         r = SIM.ingest_streams(self.m, [bytes(d) for d in datas], self.p, piece, self.base, self.max_entries)
         self.base += r.nchunks
@@ -155,6 +272,7 @@ class Store:
         return dict(code=-5 if r.refused else 0, why=r.refused, run=r, stats=r.stats)
 
     # ---- edits ------------------------------------------------------------------------------------------------------------------
+    @_folds
     def patch(self, src, dst, a, r, ins, lookahead=0, dry=False):
         """``dry``: only the plan (j, t, s, cuts), nothing changes"""
         old = self._get(src)
@@ -174,6 +292,7 @@ class Store:
         self.last_patch = dict(window_chunks=t, new_chunks=len(fresh), stored_bytes=total)
         return ok(**plan, **self.last_patch)
 
+    @_folds
     def _compose(self, dst, sources, ops, payload, lookahead=0):
         srcs = [self._get(n) for n in sources]
         if not all(self._restores(s) for s in srcs):
@@ -263,6 +382,8 @@ class Store:
         self.streams = {n: s for n, s in self.streams.items() if n in keep}
         self.stale = {}
         self.made = {c for s in self.streams.values() for c in s.chunks()}
+        if self.guard is not None:                                         # every kept byte moved: a fresh guard over the new store
+            self.protect(self.guard.stripe, self.guard.group, self.guard.parity)
         return ok(kept=result[2], dropped=result[3], bytes_before=before, bytes_after=result[1], removed=count - len(self.m.values),
                   dropped_contents=dropped)
 
@@ -333,14 +454,21 @@ class Store:
         pos, stored, _ = (int(v) for v in self.m.directory[value - self.dir_base])
         assert 0 <= at < stored
         self.m.blob[pos + at] ^= 0xFF
+        self.flipped ^= {pos + at}
         self.hurt.add(value)
         return ok(pos=pos + at)
+
+    def corrupt_unlisted(self, value, at, keep):
+        """``corrupt`` of a chunk that none of the streams ``keep`` names, so a ``scrub(keep=keep)`` does not report it"""
+        assert all(value not in self._get(n).refs for n in keep), value
+        return self.corrupt(value, at)
 
     def scrub(self, keep=None):
         live = None if keep is None else self._mark(keep)[0]
         held = SM.digests_by_value((c, v) for c, v in self.m.values.items())       # in a Model the digest of a chunk is its content
         status = SM.statuses(self.m.blob, self.store_bytes, self.m.directory, self.dir_base, live, held, self.m.decode(), lambda piece: piece)
         damaged = [self.dir_base + int(i) for i in np.nonzero((status >= 1) & (status <= 3))[0]]
+        self.last_scrub = damaged
         return ok(status=status, damaged=damaged)
 
     def affected(self, names, status):
@@ -348,6 +476,7 @@ class Store:
         streams = self.account(names, flag)["streams"]
         return ok(affected=[(i, int(a["flagged_positions"]), int(a["flagged_bytes"])) for i, a in enumerate(streams) if a["flagged_positions"] > 0])
 
+    @_folds
     def repair_from(self, peer: "Store", damaged):
         by_value = {v: c for c, v in self.m.values.items()}
         out = dict(repaired=[], unavailable=[], no_digest=[])
@@ -384,6 +513,12 @@ class Store:
 
     # ---- bundles ----------------------------------------------------------------------------------------------------------------
     def replicate_to(self, other: "Store", names, as_names, negotiate=True):
+        try:
+            return self._replicate_to(other, names, as_names, negotiate)
+        finally:
+            other._fold()                                                  # import_bundle appends on the receiving store
+
+    def _replicate_to(self, other: "Store", names, as_names, negotiate):
         recipes = [self._get(n).refs for n in names]
         bundle = RP.export_bundle(self.m, recipes, other.m.values if negotiate else None)
         lacks = [k for k, d in enumerate(bundle["digests"]) if d not in other.m.values]
@@ -411,6 +546,8 @@ def run(stores: dict, op: str, args: dict):
         return s.replicate_to(stores[args.pop("to")], **args)
     if op == "repair_from":
         return s.repair_from(stores[args.pop("peer")], s.scrub()["damaged"])
+    if op == "repair_local":                                             # of the store's last scrub, which may have had a ``keep``
+        return s.repair_local(s.last_scrub, **args)
     if op == "affected":
         return s.affected(args["names"], s.scrub()["status"])
     if op == "delta_round_trip":
@@ -650,10 +787,292 @@ def cut_in_carry(data, piece) -> bool:
     return any(len(q["cuts"]) > 1 and q["cuts"][1] < carry for carry, q in zip(r.carries, r.log))
 
 
-BUILDERS = (_edit_after_compact, _edit_after_renumber, lambda O, alg: _refused_ingest(O, alg, False), lambda O, alg: _refused_ingest(O, alg, True),
-            _duplicates, _peers, _repair_then_edit, _streamed_and_reloaded)
+# ---- the guarded scripts ---------------------------------------------------------------------------------------------------------
+S = G1.S                                                                   # 65536
+GUARDED = dict(store_bytes=1 << 20, dir_entries=4096, dir_base=7, max_entries=1 << 13)
+PARTIAL = ("ingest_stream", "ingest_many_stream")                          # a refusal of these may leave a prefix behind
+
+
+def _fill(s, store, names, seed, G, n=60000):
+    """Noise streams, stored raw, until ``used`` has passed G * S."""
+    for k, name in enumerate(names):
+        s.do("ingest", store=store, name=name, data=noise(seed + k, n))
+    m = s.stores[store]
+    assert m.used > G * S and m.used == n * len(names), (s.name, m.used)
+
+
+def _extents(m):
+    """(pos, stored, value) of every stored chunk, in ascending pos"""
+    d = m.m.directory
+    return sorted((int(d[i]["pos"]), int(d[i]["stored"]), m.dir_base + int(i)) for i in np.nonzero(RN.nonzero(d))[0])
+
+
+def _chunk_at(ext, p):
+    return next((v for pos, stored, v in ext if pos <= p < pos + stored), None)
+
+
+def _kind(pos, stored, G, S=S):
+    """where an extent lies: inside one stripe, across a stripe boundary inside a group, or across a group boundary"""
+    if pos // (G * S) != (pos + stored - 1) // (G * S):
+        return "group"
+    return "stripe" if pos // S != (pos + stored - 1) // S else "inside"
+
+
+def _pairs(m, G, kinds, S=S, spread=20000):
+    """One pair (a, b, q) per kind: a of that kind, b the chunk over the column of a's first byte in the next member of a's group
+    (in the one before it, from the last member), q that byte of b.  The pairs share no chunk, and the inside ones lie apart."""
+    ext, out, taken, last = _extents(m), [], set(), -spread
+    for kind in kinds:
+        for pos, stored, a in ext:
+            q = pos + S if pos // S % G < G - 1 else pos - S
+            b = _chunk_at(ext, q) if 0 <= q < m.used else None
+            if _kind(pos, stored, G, S) != kind or b is None or {a, b} & taken or a == b or (kind == "inside" and pos < last + spread):
+                continue
+            out.append((a, b, q))
+            taken |= {a, b}
+            last = pos if kind == "inside" else last
+            break
+        else:
+            raise AssertionError(f"no {kind} pair in the built store")
+    return out
+
+
+def _owner(m, value):
+    """(stream, position) of a live recipe that names the value"""
+    return next((n, st.refs.index(value)) for n, st in sorted(m.streams.items()) if value in st.refs)
+
+
+def _damage(s, store, pairs):
+    """a's middle byte and b's byte over the column of a's first one, of every pair"""
+    m = s.stores[store]
+    for a, b, q in pairs:
+        pa, na = (int(v) for v in m.m.directory[a - m.dir_base][["pos", "stored"]])
+        s.do("corrupt", store=store, value=a, at=na // 2)
+        s.do("corrupt", store=store, value=b, at=q - int(m.m.directory[b - m.dir_base]["pos"]))
+    return sorted(v for a, b, _ in pairs for v in (a, b))
+
+
+def _scrub_and_repair(s, store, victims, keep=None):
+    s.do("scrub", store=store, keep=keep)
+    s.note("reports", victims)
+    return s.do("repair_local", store=store)
+
+
+def _guarded_pairs(O, alg):
+    G = 2
+    s = Script("guarded_pairs", O, alg, P=dict(GUARDED, store_bytes=5 * G * S))
+    s.do("protect", stripe=S, group=G, parity=2)
+    names = ["N0", "N1", "N2", "N3", "N4"]
+    _fill(s, "P", names, 100, G)
+    m = s.stores["P"]
+    pairs = _pairs(m, G, ["stripe", "group", "inside", "inside", "inside"])
+    assert len(pairs) >= 4 and len({v for a, b, _ in pairs for v in (a, b)}) == 2 * len(pairs)
+    victims = _damage(s, "P", pairs)
+    _scrub_and_repair(s, "P", victims)
+    s.note("all_paired", len(pairs))
+    s.do("scrub")
+    s.note("clean")
+    s.do("guard_check")
+    name, j = _owner(m, pairs[0][0])                                       # the window begins with a repaired chunk
+    st = m.streams[name]
+    s.do("patch", src=name, dst="E", a=st.cuts[j] + 5, r=3, ins=noise(110, 200))
+    s.note("window_reads", (st.cuts[j], st.cuts[j + 1]))
+    before = m.guard.state()[:3] + (len(m.guard.P),)
+    s.do("compact", keep=names[1:] + ["E"], store_bytes=1 << 20)           # N0 goes: every kept byte moves, into 8 groups
+    s.note("fresh_guard", before)
+    for keep in (None, names[1:] + ["E"]):
+        if keep:
+            s.do("renumber", keep=keep, dir_base=3000)
+        again = _pairs(m, G, ["inside", "group"] if keep else ["stripe", "inside"])
+        victims = _damage(s, "P", again)
+        _scrub_and_repair(s, "P", victims)
+        s.note("all_paired", len(again))
+        s.do("scrub")
+        s.note("clean")
+    s.do("restore_many_stream", names=names[1:] + ["E"])
+    return s.done()
+
+
+def _guarded_triple(O, alg):
+    G = 3
+    s = Script("guarded_triple", O, alg, P=GUARDED, Q=dict(GUARDED, dir_base=1000))
+    s.do("protect", stripe=S, group=G, parity=2)
+    s.do("protect", store="Q")                                             # the peer under ChunkStore.protect()'s own geometry
+    names = ["N0", "N1", "N2", "N3"]
+    _fill(s, "P", names, 200, G)
+    s.do("replicate_to", to="Q", names=names, as_names=names)
+    m, W = s.stores["P"], G * S
+    ext = _extents(m)
+    a, three = next((v, [v, _chunk_at(ext, pos + S), _chunk_at(ext, pos + 2 * S)]) for pos, n, v in ext if pos > 3000 and _kind(pos, n, G) == "inside")
+    assert len(set(three)) == 3 and None not in three
+    pa = int(m.m.directory[a - m.dir_base]["pos"])
+    alone = next(v for pos, n, v in ext if pos > W + 1000 and _kind(pos, n, G) == "inside")
+    for k, v in enumerate(three):                                          # one column of group 0, in members 0, 1 and 2
+        s.do("corrupt", value=v, at=pa + k * S - int(m.m.directory[v - m.dir_base]["pos"]))
+    s.do("corrupt", value=alone, at=0)
+    s.do("scrub")
+    s.note("reports", sorted(three + [alone]))
+    s.do("repair_local")
+    s.note("repair", dict(repaired=[alone], collided=sorted(three), unprotected=[], failed=[], no_digest=[], paired=0))
+    s.do("scrub")
+    s.note("reports", sorted(three))
+    s.do("repair_from", peer="Q")
+    s.do("scrub")
+    s.note("clean")
+    s.do("guard_check")                                                    # the old bytes stay, damaged, until a compact
+    s.note("guard_check", dict(count=1, groups=[0], bits=[3]))
+    s.do("compact", keep=names)
+    s.do("guard_check")
+    s.note("guard_check", dict(count=0, groups=[], bits=[]))
+    s.do("restore_many_stream", names=names)
+    return s.done()
+
+
+def _guard_is_damaged(O, alg):
+    G = 2
+    s = Script("guard_is_damaged", O, alg, A=GUARDED, B=dict(GUARDED, dir_base=500))
+    names = ["N0", "N1", "N2"]
+    for store, parity in (("A", 1), ("B", 2)):
+        s.do("protect", store=store, stripe=S, group=G, parity=parity)
+        _fill(s, store, names, 300, G)
+        m = s.stores[store]
+        (a, b, q), = _pairs(m, G, ["inside"])
+        pa, na = (int(v) for v in m.m.directory[a - m.dir_base][["pos", "stored"]])
+        assert pa + na <= S and q == pa + S
+        column = pa + 1                                                    # group 0: the guard byte of a's second byte
+        # 1. a alone, and a P byte of its column
+        s.do("corrupt", store=store, value=a, at=na // 2)
+        s.do("corrupt_guard", store=store, which=0, at=column)
+        _scrub_and_repair(s, store, [a])
+        s.note("repair", dict(repaired=[], collided=[], unprotected=[], failed=[a], no_digest=[], paired=0))
+        s.note("nothing_changed")
+        s.do("guard_check", store=store)
+        s.note("guard_check", dict(count=1, groups=[0], bits=[1 if parity == 1 else 3]))
+        s.do("corrupt_guard", store=store, which=0, at=column)             # the guard byte put back: now it rebuilds
+        got = s.do("repair_local", store=store)
+        assert got["repaired"] == [a]
+        # 2. a pair, and a Q byte of the column where it meets
+        if parity == 2:
+            victims = _damage(s, store, [(a, b, q)])
+            s.do("corrupt_guard", store=store, which=1, at=q % S)
+            got = _scrub_and_repair(s, store, victims)
+            s.note("some_failed", victims)
+            if len(got["failed"]) == 2:
+                s.note("nothing_changed")
+            s.do("corrupt_guard", store=store, which=1, at=q % S)
+            s.do("scrub", store=store)
+            s.do("repair_local", store=store)
+            s.do("scrub", store=store)
+            s.note("clean")
+        # 3. a, and a chunk of its column that the scrub was not asked about: N1 is not kept
+        assert _owner(m, a)[0] == "N0" and _owner(m, b)[0] == "N1"
+        s.do("corrupt", store=store, value=a, at=na // 2)
+        s.do("corrupt_unlisted", store=store, value=b, at=q - int(m.m.directory[b - m.dir_base]["pos"]), keep=["N0", "N2"])
+        _scrub_and_repair(s, store, [a], keep=["N0", "N2"])
+        s.note("repair", dict(repaired=[], collided=[], unprotected=[], failed=[a], no_digest=[], paired=0))
+        s.note("nothing_changed")
+        _scrub_and_repair(s, store, sorted([a, b]))                         # a whole scrub names both: two in one column
+        s.note("repair", dict(repaired=[a, b], collided=[], unprotected=[], failed=[], no_digest=[], paired=2) if parity == 2 else
+               dict(repaired=[], collided=sorted([a, b]), unprotected=[], failed=[], no_digest=[], paired=0))
+    return s.done()
+
+
+def _protect_over_damage(O, alg):
+    G = 2
+    s = Script("protect_over_damage", O, alg, P=GUARDED, Q=dict(GUARDED, dir_base=1000))
+    names = ["N0", "N1", "N2"]
+    _fill(s, "P", names, 400, G)
+    s.do("replicate_to", to="Q", names=names, as_names=names)
+    s.do("protect", stripe=S, group=G, parity=1)                            # late, on a store that is not empty
+    m = s.stores["P"]
+    pair, = _pairs(m, G, ["inside"])
+    victims = _damage(s, "P", [pair])
+    _scrub_and_repair(s, "P", victims)
+    s.note("repair", dict(repaired=[], collided=victims, unprotected=[], failed=[], no_digest=[], paired=0))
+    s.do("protect", stripe=S, group=G, parity=2)                            # over the damage: the new guards hold it
+    s.do("guard_check")
+    s.note("guard_check", dict(count=0, groups=[], bits=[]))
+    _scrub_and_repair(s, "P", victims)
+    s.note("repair", dict(repaired=[], collided=[], unprotected=[], failed=victims, no_digest=[], paired=2))
+    s.note("nothing_changed")
+    s.do("repair_from", peer="Q")
+    s.do("scrub")
+    s.note("clean")
+    s.do("protect", stripe=1 << 17, group=G, parity=2)                      # a second geometry
+    s.do("ingest", name="N3", data=noise(410, 60000))
+    pair, = _pairs(m, G, ["inside"], S=1 << 17)
+    victims = _damage(s, "P", [pair])
+    _scrub_and_repair(s, "P", victims)
+    s.note("repair", dict(repaired=victims, collided=[], unprotected=[], failed=[], no_digest=[], paired=2))
+    s.do("scrub")
+    s.note("clean")
+    s.do("restore_many_stream", names=names + ["N3"])
+    return s.done()
+
+
+def _guarded_refusals(O, alg):
+    G = 2
+    names = ["N0", "N1", "N2"]
+    small, large = dict(a=20000, r=1, ins=b"x"), dict(a=30000, r=0, ins=noise(510, 4000))
+    parts = lambda n: [("N0", 100, 3000), noise(511, n), ("N1", 200, 2500)]  # noqa: E731
+
+    def probe():                                                            # a store with all the room, to count on
+        m = Store(O, alg, **GUARDED)
+        for k, name in enumerate(names):
+            m.ingest(name, noise(500 + k, 60000))
+        return m
+    K, used = probe().stored_chunks(), probe().used
+    t = [probe().patch("N0", "X", dry=True, **kw)["t"] for kw in (small, large)] + [probe().compose("X", parts(n))["rebuilt_chunks"] for n in (10, 4000)]
+    few, many = max(t[0], t[2]), min(t[1], t[3])                            # the window chunks of the small calls and of the large ones
+    assert few < many and K == len(probe().m.values), t
+    tight = dict(GUARDED, store_bytes=used + 50000)
+    s = Script("guarded_refusals", O, alg, D=dict(GUARDED, max_entries=K + few), T=tight)
+    # D: the directory, then the index
+    s.do("protect", store="D", stripe=S, group=G, parity=1)
+    _fill(s, "D", names, 500, G)
+    s.do("renumber", store="D", keep=names, dir_entries=K)
+    s.note("full")
+    s.do("patch", expect=-5, store="D", src="N0", dst="X", **small)
+    s.note("refused", "directory")
+    s.do("compose", expect=-5, store="D", dst="X", parts=parts(10))
+    s.note("refused", "directory")
+    s.do("renumber", store="D", keep=names, dir_entries=K + 64)
+    s.do("patch", expect=-5, store="D", src="N0", dst="X", **large)
+    s.note("refused", "index")
+    s.do("compose", expect=-5, store="D", dst="X", parts=parts(4000))
+    s.note("refused", "index")
+    s.do("patch", store="D", src="N0", dst="X", **small)
+    s.do("guard_check", store="D")
+    # T: the store's bytes, one-shot and part-way
+    s.do("protect", store="T", stripe=S, group=G, parity=2)
+    _fill(s, "T", names, 500, G)
+    s.do("ingest", expect=-5, store="T", name="Y", data=noise(520, 55000))
+    s.note("refused", "store")
+    got = s.do("ingest_stream", expect=-5, store="T", name="Y", data=noise(521, 60000), piece=7001)
+    s.note("part_way", got["run"].consumed)
+    got = s.do("ingest_many_stream", expect=-5, store="T", names=["Z0", "Z1", "Z2"], datas=[noise(522 + k, n) for k, n in enumerate((1200, 5000, 2500))], piece=2100)
+    assert got["run"].recipes()[1] is not None, "no stream was cut"
+    s.note("part_way", got["run"].consumed)
+    s.do("guard_check", store="T")
+    m = s.stores["T"]
+    pair, = _pairs(m, G, ["inside"])
+    victims = _damage(s, "T", [pair])
+    s.do("save_load", store="T", names=[])                                  # a snapshot of a damaged store
+    _scrub_and_repair(s, "T", victims)                                       # in the loaded store, from the loaded guards
+    s.note("repair", dict(repaired=victims, collided=[], unprotected=[], failed=[], no_digest=[], paired=2))
+    s.do("scrub", store="T")
+    s.note("clean")
+    s.do("restore_many_stream", store="T", names=names + ["Y", "Z0", "Z1"])
+    return s.done()
+
+
+BUILDERS = (_edit_after_compact,_edit_after_renumber, lambda O, alg: _refused_ingest(O, alg, False), lambda O, alg: _refused_ingest(O, alg, True),
+            _duplicates, _peers, _repair_then_edit, _streamed_and_reloaded, _guarded_pairs, _guarded_triple, _guard_is_damaged, _protect_over_damage,
+            _guarded_refusals)
 NAMES = ("edit_after_compact", "edit_after_renumber", "refused_ingest_then_on[ingest]", "refused_ingest_then_on[ingest_many]", "duplicates", "peers",
-         "repair_then_edit", "streamed_and_reloaded")
+         "repair_then_edit", "streamed_and_reloaded", "guarded_pairs", "guarded_triple", "guard_is_damaged", "protect_over_damage",
+         "guarded_refusals")
+UNGUARDED = NAMES[:8]                                                      # these run once more under ``protected``
 _BUILT = {}
 
 
@@ -666,3 +1085,13 @@ def script(oracle, alg, name):
 
 def scripts(oracle, alg):
     return [script(oracle, alg, name) for name in NAMES]
+
+
+FLAVOUR = dict(lz4=dict(stripe=65536, group=3, parity=1), lzf=dict(stripe=65536, group=2, parity=2))
+
+
+def protected(sc, alg):
+    """The script with ``protect`` as the first step on every store, one flavour per codec; the notes move with their steps."""
+    first = [("protect", dict(store=n, **FLAVOUR[alg]), 0) for n in sc["specs"]]
+    notes = {key: [(i + len(first), value) for i, value in hits] for key, hits in sc["notes"].items()}
+    return dict(name=sc["name"] + "+guard", specs=sc["specs"], steps=first + sc["steps"], notes=notes)

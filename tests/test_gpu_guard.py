@@ -92,7 +92,7 @@ class Guard:
         return int(_u64(self.d_covered)[0])
 
 
-def update(cw, d_store, guard, used, G, store_bytes=BYTES):
+def update(cw, d_store, guard, used, G, store_bytes=BYTES, S=S):
     d_used, result = _dev_u64([used]), _dev_u64([7, 7, 7, 7])
     _sync()
     cw.dev_store_guard_update(d_store.data_ptr(), store_bytes, d_used.data_ptr(), guard.d_covered.data_ptr(), S, G, guard.ptr(), guard.size,
@@ -149,11 +149,11 @@ def test_many_small_updates_equal_one_large(cw, store, guards, G):
 
 
 # ---- 2. check -------------------------------------------------------------------------------------------------------------------------
-def check(cw, d_store, guard, G, flags=True):
+def check(cw, d_store, guard, G, flags=True, store_bytes=BYTES, S=S):
     n = guard.size // S
     bad, result = _dev_bytes(np.full(n + 2, 0xEEEEEEEE, np.uint32)), _dev_u64([7, 7, 7, 7])
     _sync()
-    cw.dev_store_guard_check(d_store.data_ptr(), BYTES, guard.d_covered.data_ptr(), S, G, guard.ptr(), guard.size, bad.data_ptr() + 4 if flags else 0,
+    cw.dev_store_guard_check(d_store.data_ptr(), store_bytes, guard.d_covered.data_ptr(), S, G, guard.ptr(), guard.size, bad.data_ptr() + 4 if flags else 0,
                              result.data_ptr(), _stream())
     _sync()
     return _u64(result).tolist(), bad.cpu().numpy().view(np.uint32)
@@ -198,7 +198,7 @@ def test_check(cw, store, guards, G):
 
 
 # ---- 3. rebuild -----------------------------------------------------------------------------------------------------------------------
-def rebuild(cw, d_store, directory, dir_base, guard, G, values, out_bytes, count=None, max_count=None):
+def rebuild(cw, d_store, directory, dir_base, guard, G, values, out_bytes, count=None, max_count=None, store_bytes=BYTES, S=S):
     """cw_dev_store_guard_rebuild into poisoned buffers: (result[4], statuses with a pad, the out_bytes of d_out, d_out_loc with a pad)."""
     n = len(values)
     max_count = n if max_count is None else max_count
@@ -208,7 +208,7 @@ def rebuild(cw, d_store, directory, dir_base, guard, G, values, out_bytes, count
     loc = _dev_bytes(np.full(2 * (max_count + 2), 0xEEEEEEEEEEEEEEEE, np.uint64))
     status, result = _dev_bytes(np.full(max_count + 2, 0xEEEEEEEE, np.uint32)), _dev_u64([7, 7, 7, 7])
     _sync()
-    cw.dev_store_guard_rebuild(d_store.data_ptr(), BYTES, d_dir.data_ptr(), dir_base, len(directory), guard.d_covered.data_ptr(), S, G, guard.ptr(),
+    cw.dev_store_guard_rebuild(d_store.data_ptr(), store_bytes, d_dir.data_ptr(), dir_base, len(directory), guard.d_covered.data_ptr(), S, G, guard.ptr(),
                                guard.size, d_val.data_ptr(), d_count.data_ptr(), max_count, out.data_ptr() + PAD if out_bytes else 0, out_bytes,
                                loc.data_ptr() + 16, status.data_ptr() + 4, result.data_ptr(), _stream())
     _sync()
@@ -220,15 +220,15 @@ def rebuild(cw, d_store, directory, dir_base, guard, G, values, out_bytes, count
     return _u64(result).tolist(), st[1:-1], h[PAD:PAD + out_bytes], locs[2:-2].view(RM.LOC)
 
 
-def compare(cw, d_store, hurt, directory, dir_base, guard, covered, G, values, original=None):
+def compare(cw, d_store, hurt, directory, dir_base, guard, covered, G, values, original=None, store_bytes=BYTES, S=S):
     """One rebuild with exactly the room it needs, against the model; then the dry run and a buffer one byte too small."""
-    want, wst, wout, wlocs = GM.rebuild(hurt, BYTES, directory, dir_base, covered, S, G, guard.host(), values, BYTES)
+    want, wst, wout, wlocs = GM.rebuild(hurt, store_bytes, directory, dir_base, covered, S, G, guard.host(), values, 1 << 62)
     total = want[1]
-    result, st, out, locs = rebuild(cw, d_store, directory, dir_base, guard, G, values, total)
+    result, st, out, locs = rebuild(cw, d_store, directory, dir_base, guard, G, values, total, store_bytes=store_bytes, S=S)
     assert result == want and st.tolist() == wst.tolist()
     assert (out == wout).all() and (locs == wlocs).all()
     for room in sorted({0, max(total - 1, 0)}) if total else []:
-        result, st, out, locs = rebuild(cw, d_store, directory, dir_base, guard, G, values, room)
+        result, st, out, locs = rebuild(cw, d_store, directory, dir_base, guard, G, values, room, store_bytes=store_bytes, S=S)
         assert result == [1] + want[1:] and st.tolist() == wst.tolist()
         assert (out == 0xEE).all() and (locs.view(np.uint64) == 0xEEEEEEEEEEEEEEEE).all()       # nothing but status and result
     return wst.tolist()

@@ -31,15 +31,15 @@ def cw():
 class Stored:
     """Noise on the host and on the device, neither written, and the model's (P, Q) for the cursors the tests use, each computed once."""
 
-    def __init__(self, n, seed):
-        self.n = n
+    def __init__(self, n, seed, S=S):
+        self.n, self.S = n, S
         self.host = np.random.default_rng(seed).integers(0, 256, n, dtype=np.uint8)
         self.dev = _dev_bytes(self.host)
         self.cache = {}
 
     def guards(self, covered, G):
         if (covered, G) not in self.cache:
-            self.cache[covered, G] = G2.guards_of(self.host, covered, S, G, self.n)
+            self.cache[covered, G] = G2.guards_of(self.host, covered, self.S, G, self.n)
         return self.cache[covered, G]
 
 
@@ -71,7 +71,7 @@ class Guards:
         return (p[:len(pq[0])] == pq[0]).all() and (q[:len(pq[1])] == pq[1]).all() and not p[len(pq[0]):].any() and not q[len(pq[1]):].any()
 
 
-def update(cw, d_store, g, used, G, store_bytes=BYTES):
+def update(cw, d_store, g, used, G, store_bytes=BYTES, S=S):
     d_used, result = _dev_u64([used]), _dev_u64([7, 7, 7, 7, POISON64])
     _sync()
     cw.dev_store_guard2_update(d_store.data_ptr(), store_bytes, d_used.data_ptr(), g.d_covered.data_ptr(), S, G, g.p.ptr(), g.q.ptr(), g.size,
@@ -82,7 +82,7 @@ def update(cw, d_store, g, used, G, store_bytes=BYTES):
     return r[:4]
 
 
-def update_p_only(cw, d_store, guard, used, G, store_bytes=BYTES):
+def update_p_only(cw, d_store, guard, used, G, store_bytes=BYTES, S=S):
     d_used, result = _dev_u64([used]), _dev_u64([7, 7, 7, 7])
     _sync()
     cw.dev_store_guard_update(d_store.data_ptr(), store_bytes, d_used.data_ptr(), guard.d_covered.data_ptr(), S, G, guard.ptr(), guard.size,
@@ -151,7 +151,7 @@ def test_update_with_255_members(cw, store255):
 
 
 # ---- 2. check -------------------------------------------------------------------------------------------------------------------------
-def check(cw, d_store, g, G, flags=True, store_bytes=BYTES):
+def check(cw, d_store, g, G, flags=True, store_bytes=BYTES, S=S):
     n = g.size // S
     bad, result = _dev_bytes(np.full(n + 2, 0xEEEEEEEE, np.uint32)), _dev_u64([7, 7, 7, 7, POISON64])
     _sync()
@@ -215,7 +215,7 @@ def test_check_with_255_members(cw, store255):
 
 
 # ---- 3. rebuild -----------------------------------------------------------------------------------------------------------------------
-def rebuild(cw, d_store, store_bytes, directory, dir_base, g, G, values, out_bytes, count=None, max_count=None):
+def rebuild(cw, d_store, store_bytes, directory, dir_base, g, G, values, out_bytes, count=None, max_count=None, S=S):
     """cw_dev_store_guard2_rebuild into poisoned buffers: (result[5], statuses, the out_bytes of d_out, d_out_loc)."""
     n = len(values)
     max_count = n if max_count is None else max_count
@@ -237,24 +237,24 @@ def rebuild(cw, d_store, store_bytes, directory, dir_base, g, G, values, out_byt
     return r[:5], st[1:-1], h[PAD:PAD + out_bytes], locs[2:-2].view(RM.LOC)
 
 
-def compare(cw, d_store, hurt, store_bytes, directory, dir_base, g, covered, G, values):
+def compare(cw, d_store, hurt, store_bytes, directory, dir_base, g, covered, G, values, S=S):
     """One rebuild with exactly the room it needs, against the model; then the dry run and a buffer one byte too small."""
     p, q = g.host()
-    want, wst, wout, wlocs = G2.rebuild(hurt, store_bytes, directory, dir_base, covered, S, G, p, q, values, store_bytes)
+    want, wst, wout, wlocs = G2.rebuild(hurt, store_bytes, directory, dir_base, covered, S, G, p, q, values, 1 << 62)
     total = want[1]
-    result, st, out, locs = rebuild(cw, d_store, store_bytes, directory, dir_base, g, G, values, total)
+    result, st, out, locs = rebuild(cw, d_store, store_bytes, directory, dir_base, g, G, values, total, S=S)
     assert result == want and st.tolist() == wst.tolist()
     assert (out == wout).all() and (locs == wlocs).all()
     for room in sorted({0, max(total - 1, 0)}) if total else []:
-        result, st, out, locs = rebuild(cw, d_store, store_bytes, directory, dir_base, g, G, values, room)
+        result, st, out, locs = rebuild(cw, d_store, store_bytes, directory, dir_base, g, G, values, room, S=S)
         assert result == [1] + want[1:] and st.tolist() == wst.tolist()
         assert (out == 0xEE).all() and (locs.view(np.uint64) == POISON64).all()                 # nothing but status and result
     return wst.tolist(), want[4], wout, wlocs
 
 
-def run_cases(cw, stored, G):
-    host, n = stored.host, stored.n
-    for name, (entries, values, covered, wanted, need_q) in G2.rebuild_cases(G, n).items():
+def run_cases(cw, stored, G, single=None):
+    host, n, S = stored.host, stored.n, stored.S
+    for name, (entries, values, covered, wanted, need_q) in G2.rebuild_cases(G, n, S, single).items():
         directory = np.array(entries, RM.LOC)
         hurt = host.copy()                                                                      # damaged after the guards were built
         for v in values:
@@ -262,7 +262,7 @@ def run_cases(cw, stored, G):
             if e:
                 hurt[e[0]:e[0] + e[1]] ^= 0xA5
         g = Guards(stored.guards(covered, G), covered)
-        statuses, paired, out, locs = compare(cw, _dev_bytes(hurt), hurt, n, directory, 0, g, covered, G, values)
+        statuses, paired, out, locs = compare(cw, _dev_bytes(hurt), hurt, n, directory, 0, g, covered, G, values, S=S)
         assert statuses == wanted and paired == len(need_q), name
         for k, (v, s) in enumerate(zip(values, wanted)):                                        # and the bytes are the original ones
             if s == 0:

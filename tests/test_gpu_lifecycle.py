@@ -1,8 +1,11 @@
 """The chunk store's life cycle on the GPU: every script of tests/lifecycle_model.py runs step by step on ``cw.ChunkStore`` and on the
 whole-store model, and after every step the whole device state is compared with the model, exactly: ``used()``, the stored bytes, the
 directory, the index as {digest: value}, ``base`` / ``dir_base`` / ``dir_entries``, every live recipe's refs and offsets,
-``restore(recipe, verify=True)`` and the statistics of the last patch and compose.  After a refused step the device state is what it
-was before the step.  What each script has to reach is asserted on the model alone, in tests/test_lifecycle_model.py."""
+``restore(recipe, verify=True)`` and the statistics of the last patch and compose; of a protected store also the guard's geometry, its
+cursor (``protected_bytes() == used()``), the whole of ``d_guard`` and ``d_guard_q`` and ``guard_check(detail=True)``.  After a refused
+step the device state is what it was before the step -- but for the prefix that a streamed ingest leaves, which is the model's.  The
+eight unguarded scripts run once more with ``protect`` as the first step on every store.  What each script has to reach is asserted on
+the model alone, in tests/test_lifecycle_model.py."""
 import numpy as np
 import pytest
 
@@ -30,11 +33,19 @@ def digest(oracle, content: bytes) -> bytes:
     return DIGEST[content]
 
 
+def guard_state(cs):
+    """The guard of a protected store: geometry, cursor, and every byte of P and Q."""
+    if cs.d_guard is None:
+        return None
+    return (cs.stripe, cs.group, cs.d_guard_q is None, cs.protected_bytes(), cs.d_guard.cpu().numpy().tobytes(),
+            None if cs.d_guard_q is None else cs.d_guard_q.cpu().numpy().tobytes())
+
+
 def device_state(cs):
     """Everything of a store that a refused step must leave alone (the index as a set of pairs: a retain rebuilds its table)."""
     dig, val = cs.index.export()
     return (frozenset((bytes(d), int(v)) for d, v in zip(dig, val)), cs.d_dir.cpu().numpy().tobytes(), cs.used(),
-            cs.d_store[:cs.used()].cpu().numpy().tobytes(), cs.base, cs.dir_base, cs.dir_entries, cs.store_bytes)
+            cs.d_store[:cs.used()].cpu().numpy().tobytes(), cs.base, cs.dir_base, cs.dir_entries, cs.store_bytes, guard_state(cs))
 
 
 class Env:
@@ -65,6 +76,13 @@ class Env:
             want = {digest(self.oracle, c): v for c, v in m.m.values.items()}
             assert len(have) == len(val) and have == want, (at, "index", len(have), len(want), sorted(set(have.values()) ^ set(want.values()))[:8])
             assert (cs.base, cs.dir_base, cs.dir_entries, cs.store_bytes) == (m.base, m.dir_base, m.dir_entries, m.store_bytes), at
+            g = m.guard
+            assert (cs.d_guard is None) == (g is None), at
+            if g is not None:
+                assert cs.protected_bytes() == used == g.covered, (at, "cursor", cs.protected_bytes(), g.covered)
+                assert guard_state(cs) == (g.stripe, g.group, g.Q is None, g.covered, g.P.tobytes(), None if g.Q is None else g.Q.tobytes()), (at, "guard")
+                want = m.guard_check()
+                assert cs.guard_check(detail=True) == (want["count"], want["groups"], want["bits"]), (at, "guard_check")
             damaged = m.hurt
             for stream, st in m.streams.items():
                 r = self.recipes[name, stream]
@@ -99,13 +117,20 @@ class Env:
         elif op == "ingest_many":
             for n, r in zip(args["names"], cs.ingest_many(args["datas"])):
                 self.recipes[store, n] = r
-        elif op == "ingest_stream":
-            self.recipes[store, args["name"]] = piece(args["piece"], lambda: cs.ingest_stream(args["data"]))
-            assert {k: cs.last_stats[k] for k in want["stats"]} == want["stats"], cs.last_stats
-        elif op == "ingest_many_stream":
-            for n, r in zip(args["names"], piece(args["piece"], lambda: cs.ingest_many_stream(args["datas"]))):
+        elif op in LM.PARTIAL:                                               # a refusal leaves the recipes of the prefix that went in
+            one = op == "ingest_stream"
+            names, refusal = [args["name"]] if one else args["names"], None
+            try:
+                got = piece(args["piece"], lambda: [cs.ingest_stream(args["data"])] if one else cs.ingest_many_stream(args["datas"]))
+            except cw.CwError as e:
+                refusal = e
+                got = [e.recipe] if one else e.recipes + [e.partial] * (e.partial is not None)
+                assert (e.consumed, e.nchunks) == (want["run"].consumed, want["run"].nchunks), (e.consumed, e.nchunks)
+            for n, r in zip(names, got):
                 self.recipes[store, n] = r
             assert {k: cs.last_stats[k] for k in want["stats"]} == want["stats"], cs.last_stats
+            if refusal is not None:
+                raise refusal
         elif op == "patch":
             self.recipes[store, args["dst"]] = cs.patch(R(args["src"]), args["a"], args["r"], args["ins"], args.get("lookahead", 0))
             assert {k: cs.last_patch[k] for k in ("window_chunks", "new_chunks", "stored_bytes")} == \
@@ -145,8 +170,18 @@ class Env:
                 assert a.streams[k].tolist() == want["streams"][k].tolist(), k
             assert a.refcount.tolist() == want["refcount"].tolist() and a.owner.tolist() == want["owner"].tolist()
             assert [a.totals[k] for k in TOTALS] == want["totals"]
-        elif op == "corrupt":
+        elif op in ("corrupt", "corrupt_unlisted"):
             cs.d_store[want["pos"]:want["pos"] + 1].bitwise_xor_(0xFF)
+        elif op == "corrupt_guard":
+            (cs.d_guard, cs.d_guard_q)[args["which"]][want["at"]:want["at"] + 1].bitwise_xor_(0xFF)
+        elif op == "protect":
+            cs.protect(**args)
+        elif op == "guard_check":
+            assert cs.guard_check(detail=True) == (want["count"], want["groups"], want["bits"])
+        elif op == "repair_local":
+            got = cs.repair_local(self.reports[store], **args)
+            assert got == {k: want[k] for k in ("repaired", "collided", "unprotected", "failed", "no_digest")}, got
+            assert cs.last_repair == dict(paired=want["paired"]), cs.last_repair
         elif op == "scrub":
             rep = cs.scrub(None if args.get("keep") is None else [R(n) for n in args["keep"]])
             assert rep.status.tolist() == want["status"].tolist() and rep.damaged.tolist() == want["damaged"]
@@ -185,7 +220,16 @@ class Env:
 @pytest.mark.parametrize("name", LM.NAMES)
 @pytest.mark.parametrize("alg", ALGS)
 def test_script_leaves_what_the_model_leaves_after_every_step(cw, oracle, tmp_path, alg, name):
-    sc = LM.script(oracle, alg, name)
+    leaves_what_the_model_leaves(cw, oracle, tmp_path, alg, name, LM.script(oracle, alg, name))
+
+
+@pytest.mark.parametrize("name", LM.UNGUARDED)
+@pytest.mark.parametrize("alg", ALGS)
+def test_protected_script_leaves_what_the_model_leaves_after_every_step(cw, oracle, tmp_path, alg, name):
+    leaves_what_the_model_leaves(cw, oracle, tmp_path, alg, name, LM.protected(LM.script(oracle, alg, name), alg))
+
+
+def leaves_what_the_model_leaves(cw, oracle, tmp_path, alg, name, sc):
     models = LM.new_stores(oracle, alg, sc["specs"])
     env = Env(cw, oracle, alg, sc["specs"], tmp_path)
     try:
@@ -198,7 +242,8 @@ def test_script_leaves_what_the_model_leaves_after_every_step(cw, oracle, tmp_pa
                 with pytest.raises(cw.CwError) as e:
                     env.step(op, args, want)
                 assert e.value.code == expect, (where, str(e.value))
-                assert {n: device_state(cs) for n, cs in env.stores.items()} == before, (where, "a refused step changed the device state")
+                if op not in LM.PARTIAL or want["run"].consumed == 0:
+                    assert {n: device_state(cs) for n, cs in env.stores.items()} == before, (where, "a refused step changed the device state")
             else:
                 env.step(op, args, want)
             env.same_as_model(models, where)

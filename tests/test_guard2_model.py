@@ -67,10 +67,10 @@ def test_p_is_the_xor_guard_and_updates_add_up(small, G):
     assert G2.check(p, q, small, G2.STORE_BYTES, cursor, S, G)[1].tolist()[:2] == [1, 2]
 
 
-def _run_cases(store, G, store_bytes):
+def _run_cases(store, G, store_bytes, S=S, single=None):
     """Every case against both models, undamaged and with every protected listed extent damaged."""
     reached, guards = set(), {}
-    for name, (entries, values, covered, wanted, need_q) in G2.rebuild_cases(G, store_bytes).items():
+    for name, (entries, values, covered, wanted, need_q) in G2.rebuild_cases(G, store_bytes, S, single).items():
         directory = np.array(entries, RM.LOC)
         if covered not in guards:
             guards[covered] = G2.guards_of(store, covered, S, G, store_bytes)
@@ -122,3 +122,18 @@ def test_rebuild_cases_of_255_members(big):
     assert e[0][0] // S == 253 and e[1][0] // S == 254
     a, b = G2.update_range_255()
     assert a // S % 255 == 254 and a // (255 * S) == 0 and b // (255 * S) == 1 and (b - 1) // S % 255 == 0 and b <= G2.STORE_BYTES_255
+
+
+@pytest.mark.parametrize("S_, G, stripes", [(S, 1, 6), (S, 16, 33), (1 << 17, 2, 6)])
+def test_rebuild_cases_at_other_geometries(S_, G, stripes):
+    """guard_model's cases and the dual guard's over one member, over ChunkStore.protect()'s default group, and over a larger stripe."""
+    n = stripes * S_ + 37
+    assert _run_cases(_store(n, G), G, n, S_, single=True) == ({0, 2} if G == 1 else {0, 2, "Q"} if G == 2 else {0, 1, 2, "Q"})
+    cases = G2.rebuild_cases(G, n, S_, True)
+    assert set(GM.rebuild_cases(G, S_, n)) <= set(cases) and ("one shared column" in cases) == (G > 1)
+    e = cases["across a group boundary"][0][0]
+    assert e[0] // (G * S_) == 0 and (e[0] + e[1] - 1) // (G * S_) == 1 and cases["across a group boundary"][3] == [0]
+    if S_ > S:
+        assert cases["S bytes from mid-stripe"][0][0][1] == 65536 and cases["65536 bytes from the last column"][0][0][0] % S_ == S_ - 1
+    ranges = GM.update_ranges(G, S_, n)
+    assert ranges["everything"] == (0, n) and ranges["more than W bytes"][1] - ranges["more than W bytes"][0] > G * S_

@@ -173,3 +173,29 @@ def test_a_collision_is_symmetric_and_needs_two_different_bytes(store):
     for values, wanted in (([0, 1], [1, 1]), ([1, 0], [1, 1]), ([0, 2], [0, 0]), ([0, 2, 3], [0, 0, 0]), ([0, 2, 1], [1, 1, 1]), ([4, 5], [1, 1]),
                            ([4], [0]), ([5], [0]), ([0, 0, 1, 1], [1, 1, 1, 1])):
         assert GM.rebuild(store, BYTES, d, 0, BYTES, S, G, guard, values, BYTES)[1].tolist() == wanted, values
+
+
+def test_the_cases_of_256_members():
+    """G = 256, the single guard's maximum, over one group, one stripe of the next and a few bytes: the statuses the cases claim."""
+    G, n = 256, 257 * S + 37
+    big = np.random.default_rng(256).integers(0, 256, n, dtype=np.uint8)
+    cases, guards = GM.rebuild_cases(G, S, n), {}
+    assert {"members 254 and 255", "from member 255 into the next group"} <= set(cases) and "members 254 and 255" not in GM.rebuild_cases(3)
+    for name, (entries, values, covered, wanted) in cases.items():
+        directory = np.array(entries, RM.LOC)
+        if covered not in guards:
+            guards[covered] = GM.guard_of(big, covered, S, G, n)
+        hurt = big.copy()
+        for v in values:
+            e = GM.extent_of(directory, 0, v, n, covered)
+            if e:
+                hurt[e[0]:e[0] + e[1]] ^= 0xA5
+        result, status, out, locs = GM.rebuild(hurt, n, directory, 0, covered, S, G, guards[covered], values, n)
+        assert status.tolist() == wanted and result[0] == 0, name
+        for k, (v, s) in enumerate(zip(values, wanted)):
+            if s == 0:
+                pos, m, at = int(directory[v]["pos"]), int(directory[v]["stored"]), int(locs[k]["pos"])
+                assert (out[at:at + m] == big[pos:pos + m]).all(), (name, k)
+    ranges = GM.update_ranges(G, S, n)
+    a, b = ranges["more than W bytes"]
+    assert b - a > G * S and b == n and ranges["across a group boundary"][0] // (G * S) == 0

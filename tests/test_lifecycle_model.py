@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import cdc_model as CM
+import guard2_model as G2
 import lifecycle_model as LM
 import restore_model as RM
 
@@ -27,6 +28,14 @@ def invariants(s: LM.Store, where):
         assert not 0 <= idx < s.dir_entries or any(int(x) for x in s.m.directory[idx]), (where, v, "a value of the directory names a zero entry")
     assert set(values) == s.made, (where, len(values), len(s.made))
     assert s.dir_base <= s.base and s.used <= s.store_bytes and len(values) <= s.max_entries
+    g = s.guard
+    if g is not None:                                                    # after every step, refused or not: the cursor is ``used``
+        assert g.covered == s.used and len(g.P) == G2.guard_bytes(max(s.store_bytes, 1), g.stripe, g.group), where
+        assert (g.Q is None) == (g.parity == 1) and (g.Q is None or len(g.Q) == len(g.P)), where
+        if not s.flipped:                                                # ... and the guard is exact, zero tail included
+            p, q = G2.guards_of(s._stored(), s.used, g.stripe, g.group, max(s.store_bytes, 1))
+            assert (g.P == p).all() and (g.Q is None or (g.Q == q).all()), (where, "the guard is not exact")
+            assert s.guard_check()["count"] == 0, where
 
 
 def play(sc, oracle, alg):
@@ -36,25 +45,38 @@ def play(sc, oracle, alg):
         before = {n: s.snapshot() for n, s in stores.items()}
         got = LM.run(stores, op, args)
         assert got["code"] == expect, (sc["name"], i, op, got)
-        if expect or op in READ_ONLY:
-            assert {n: s.snapshot() for n, s in stores.items()} == before, (sc["name"], i, op, "changed the state")
+        same = {n: s.snapshot() for n, s in stores.items()} == before
+        if (expect and op not in LM.PARTIAL) or op in READ_ONLY:
+            assert same, (sc["name"], i, op, "changed the state")
         for n, s in stores.items():
             invariants(s, (sc["name"], i, op, n))
-        yield i, op, args, got, stores
+        yield i, op, args, dict(got, same=same), stores
 
 
-READ_ONLY = ("scrub", "account", "affected", "restore", "read_ranges", "diff", "save_load", "restore_many_stream")
+READ_ONLY = ("scrub", "account", "affected", "restore", "read_ranges", "diff", "save_load", "restore_many_stream", "guard_check")
 
 
 @pytest.mark.parametrize("name", LM.NAMES)
 @pytest.mark.parametrize("alg", ALGS)
 def test_script_keeps_the_invariants_and_reaches_its_edge(oracle, alg, name):
-    sc = LM.script(oracle, alg, name)
+    reaches_its_edge(LM.script(oracle, alg, name), oracle, alg, name)
+
+
+@pytest.mark.parametrize("name", LM.UNGUARDED)
+@pytest.mark.parametrize("alg", ALGS)
+def test_protected_script_keeps_the_invariants_and_reaches_its_edge(oracle, alg, name):
+    """The same steps behind a ``protect`` on every store: the same edges, and after every step, refused or not, an exact guard."""
+    sc = LM.protected(LM.script(oracle, alg, name), alg)
+    assert [op for op, _, _ in sc["steps"][:len(sc["specs"])]] == ["protect"] * len(sc["specs"])
+    reaches_its_edge(sc, oracle, alg, name)
+
+
+def reaches_its_edge(sc, oracle, alg, name):
     notes = {(i, key): value for key, hits in sc["notes"].items() for i, value in hits}
     seen, prev = set(), {}
     for i, op, args, got, stores in play(sc, oracle, alg):
         s = stores[args.get("store", "P")]
-        state = dict(base=s.base, K=s.stored_chunks(), holes=s.holes(), contents=set(s.m.values), entries=s.dir_entries)
+        state = dict(base=s.base, K=s.stored_chunks(), holes=s.holes(), contents=set(s.m.values), entries=s.dir_entries, used=s.used)
         was = prev.get(args.get("store", "P"), state)
         for (at, key), value in notes.items():
             if at != i:
@@ -97,6 +119,27 @@ def test_script_keeps_the_invariants_and_reaches_its_edge(oracle, alg, name):
                 assert len(value) >= 3
             elif key == "edits":
                 prev["edits"] = value
+            elif key == "reports":
+                assert got["damaged"] == value and value, (name, i, got["damaged"])
+                prev["reports"] = value
+            elif key == "all_paired":                                    # every damaged chunk has a partner, and all come back
+                assert got["repaired"] == prev["reports"] and got["paired"] == 2 * value == len(got["repaired"]) and value >= 2, (name, i, got)
+                assert not (got["collided"] or got["unprotected"] or got["failed"] or got["no_digest"]) and not s.hurt and not s.flipped
+            elif key == "repair":
+                assert {k: got[k] for k in value} == value, (name, i, got)
+            elif key == "guard_check":
+                assert {k: got[k] for k in value} == value, (name, i, got)
+            elif key == "nothing_changed":                               # the stored bytes, the guards and the cursor among it
+                assert got["same"], (name, i)
+            elif key == "some_failed":
+                assert got["failed"] and sorted(got["failed"] + got["repaired"] + got["collided"]) == value, (name, i, got)
+            elif key == "fresh_guard":
+                g = s.guard
+                assert (g.stripe, g.group, g.parity) == value[:3] and len(g.P) != value[3] and g.covered == s.used and not s.flipped
+            elif key == "part_way":
+                total = sum(len(d) for d in args.get("datas", [args.get("data", b"")]))
+                assert got["code"] == -5 and got["why"] == "store" and 0 < value == got["run"].consumed < total, (name, i, value)
+                assert s.guard.covered == s.used > was["used"] and not got["same"]
         if op == "diff" and "edits" in prev:
             new_ops = [o for o in got["ops"] if o[2] == LM.NONE]
             at, shift = [], 0
