@@ -502,17 +502,20 @@ int cw_dev_translate_refs(const uint64_t *d_ref, const uint64_t *d_count, size_t
                     "translate refs launch");
 }
 
-// ---- XOR guard stripes over the store's bytes: update, check, rebuild (kernels: guard_kernels.hip) ------------------------------
+// ---- guard stripes over the store's bytes, P alone or P and Q: update, check, rebuild (kernels: guard_kernels.hip) ---------------
 size_t cw_store_guard_bytes(size_t store_bytes, size_t stripe, unsigned group)
 {
     if (stripe < CW_GUARD_MIN_STRIPE || stripe > CW_GUARD_MAX_STRIPE || (stripe & (stripe - 1)) || group < 1 || group > CW_GUARD_MAX_GROUP) return 0;
     return cw::store_guard_groups(store_bytes, stripe, group) * stripe;
 }
 
-// what the three calls refuse of store, geometry and guard
-static int guard_args(const void *d_store, size_t store_bytes, size_t stripe, unsigned group, const void *d_guard, size_t guard_bytes)
+// Each operation has a single entry (P alone; d_guard_q is NULL) and a dual one (P and the GF(2^8) syndrome Q): `dual` says which was called.
+// What the three operations refuse of store, geometry and guards; the dual entries refuse a missing Q first and the rest of Q last
+static int guard_args(bool dual, const void *d_store, size_t store_bytes, size_t stripe, unsigned group, const void *d_guard, const void *d_guard_q,
+                      size_t guard_bytes)
 {
     int rc;
+    if (dual && !d_guard_q) return fail(CW_ERR_BAD_ARG, "NULL pointer: d_guard_q");
     if (!d_guard || (store_bytes && !d_store)) return fail(CW_ERR_BAD_ARG, "NULL pointer: %s", !d_guard ? "d_guard" : "d_store");
     if (cw_store_guard_bytes(1, stripe, group) == 0)
         return fail(CW_ERR_BAD_ARG, "stripe %zu is no power of two in [65536, 2^30] or group %u is not in [1, 256]", stripe, group);
@@ -522,36 +525,92 @@ static int guard_args(const void *d_store, size_t store_bytes, size_t stripe, un
     if ((rc = check_count("the groups of store_bytes", cw::store_guard_groups(store_bytes, stripe, group))) != CW_OK) return rc;
     if ((rc = check_dir_aligned((uintptr_t)d_store | (uintptr_t)d_guard, "d_store / d_guard")) != CW_OK) return rc;
     if (ranges_overlap(d_store, store_bytes, d_guard, guard_bytes)) return fail(CW_ERR_BAD_ARG, "d_guard overlaps d_store");
+    if (!dual) return CW_OK;
+    if (group > CW_GUARD2_MAX_GROUP) return fail(CW_ERR_BAD_ARG, "group %u is not in [1, 255]: the dual guard's stripe weights 2^m repeat after 255", group);
+    if ((rc = check_dir_aligned((uintptr_t)d_guard_q, "d_guard_q")) != CW_OK) return rc;
+    if (ranges_overlap(d_store, store_bytes, d_guard_q, guard_bytes)) return fail(CW_ERR_BAD_ARG, "d_guard_q overlaps d_store");
+    if (ranges_overlap(d_guard, guard_bytes, d_guard_q, guard_bytes)) return fail(CW_ERR_BAD_ARG, "d_guard_q overlaps d_guard_p");
     return CW_OK;
+}
+
+static int guard_update(bool dual, const void *d_store, size_t store_bytes, const uint64_t *d_used, uint64_t *d_covered, size_t stripe, unsigned group,
+                        void *d_guard, void *d_guard_q, size_t guard_bytes, uint64_t *d_result, void *stream)
+{
+    int rc;
+    const char *null = !d_used ? "d_used" : !d_covered ? "d_covered" : !d_result ? "d_result" : NULL;
+    if (null) return fail(CW_ERR_BAD_ARG, "NULL pointer: %s", null);
+    if ((rc = guard_args(dual, d_store, store_bytes, stripe, group, d_guard, d_guard_q, guard_bytes)) != CW_OK) return rc;
+    if ((rc = check_word_aligned((uintptr_t)d_used | (uintptr_t)d_covered | (uintptr_t)d_result, "d_used / d_covered / d_result")) != CW_OK) return rc;
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    return launched(cw::store_guard_update_launch((const uint8_t *)d_store, store_bytes, d_used, d_covered, stripe, group, d_guard, d_guard_q, d_result,
+                                                  (hipStream_t)stream),
+                    dual ? "store guard2 update launch" : "store guard update launch");
+}
+
+static int guard_check(bool dual, const void *d_store, size_t store_bytes, const uint64_t *d_covered, size_t stripe, unsigned group, const void *d_guard,
+                       const void *d_guard_q, size_t guard_bytes, uint32_t *d_group_bad, uint64_t *d_result, void *stream)
+{
+    int rc;
+    const char *null = !d_covered ? "d_covered" : !d_result ? "d_result" : NULL;
+    if (null) return fail(CW_ERR_BAD_ARG, "NULL pointer: %s", null);
+    if ((rc = guard_args(dual, d_store, store_bytes, stripe, group, d_guard, d_guard_q, guard_bytes)) != CW_OK) return rc;
+    if ((rc = check_word_aligned((uintptr_t)d_covered | (uintptr_t)d_result, "d_covered / d_result")) != CW_OK) return rc;
+    if ((uintptr_t)d_group_bad & 3) return fail(CW_ERR_BAD_ARG, "d_group_bad is not 4-byte aligned");
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    return launched_nomem(cw::store_guard_check_launch((const uint8_t *)d_store, store_bytes, d_covered, stripe, group, d_guard, d_guard_q, d_group_bad,
+                                                       d_result, (hipStream_t)stream),
+                          dual ? "store guard2 check launch" : "store guard check launch");
+}
+
+static int guard_rebuild(bool dual, const void *d_store, size_t store_bytes, const cw_chunk_loc *d_dir, uint64_t dir_base, size_t dir_entries,
+                         const uint64_t *d_covered, size_t stripe, unsigned group, const void *d_guard, const void *d_guard_q, size_t guard_bytes,
+                         const uint64_t *d_values, const uint64_t *d_count, size_t max_count, void *d_out, size_t out_bytes, cw_chunk_loc *d_out_loc,
+                         uint32_t *d_status, uint64_t *d_result, void *stream)
+{
+    int rc = check_count("max_count", max_count);
+    if (rc != CW_OK) return rc;
+    const char *null = !d_dir ? "d_dir" : !d_covered ? "d_covered" : !d_values ? "d_values" : !d_count ? "d_count" : !d_out_loc ? "d_out_loc"
+                     : !d_status ? "d_status" : !d_result ? "d_result" : out_bytes && !d_out ? "d_out" : NULL;
+    if (null) return fail(CW_ERR_BAD_ARG, "NULL pointer: %s", null);
+    if (dir_entries == 0) return fail(CW_ERR_BAD_ARG, "dir_entries is 0");
+    if ((rc = guard_args(dual, d_store, store_bytes, stripe, group, d_guard, d_guard_q, guard_bytes)) != CW_OK) return rc;
+    if ((rc = check_dir_aligned((uintptr_t)d_dir | (uintptr_t)d_out_loc, "d_dir / d_out_loc")) != CW_OK) return rc;
+    if ((rc = check_word_aligned((uintptr_t)d_covered | (uintptr_t)d_values | (uintptr_t)d_count | (uintptr_t)d_result,
+                                 "d_covered / d_values / d_count / d_result")) != CW_OK)
+        return rc;
+    if ((uintptr_t)d_status & 3) return fail(CW_ERR_BAD_ARG, "d_status is not 4-byte aligned");
+    if (ranges_overlap(d_store, store_bytes, d_out, out_bytes)) return fail(CW_ERR_BAD_ARG, "d_out overlaps d_store");
+    if (ranges_overlap(d_guard, guard_bytes, d_out, out_bytes)) return fail(CW_ERR_BAD_ARG, "d_out overlaps %s", dual ? "d_guard_p" : "d_guard");
+    if (dual && ranges_overlap(d_guard_q, guard_bytes, d_out, out_bytes)) return fail(CW_ERR_BAD_ARG, "d_out overlaps d_guard_q");
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    return launched_nomem(cw::store_guard_rebuild_launch((const uint8_t *)d_store, store_bytes, d_dir, dir_base, dir_entries, d_covered, stripe, group,
+                                                         d_guard, d_guard_q, d_values, d_count, max_count, (uint8_t *)d_out, out_bytes, d_out_loc, d_status,
+                                                         d_result, (hipStream_t)stream),
+                          dual ? "store guard2 rebuild launch" : "store guard rebuild launch");
 }
 
 int cw_dev_store_guard_update(const void *d_store, size_t store_bytes, const uint64_t *d_used, uint64_t *d_covered, size_t stripe, unsigned group,
                               void *d_guard, size_t guard_bytes, uint64_t *d_result, void *stream)
 {
-    int rc;
-    const char *null = !d_used ? "d_used" : !d_covered ? "d_covered" : !d_result ? "d_result" : NULL;
-    if (null) return fail(CW_ERR_BAD_ARG, "NULL pointer: %s", null);
-    if ((rc = guard_args(d_store, store_bytes, stripe, group, d_guard, guard_bytes)) != CW_OK) return rc;
-    if ((rc = check_word_aligned((uintptr_t)d_used | (uintptr_t)d_covered | (uintptr_t)d_result, "d_used / d_covered / d_result")) != CW_OK) return rc;
-    if ((rc = ensure_init()) != CW_OK) return rc;
-    return launched(cw::store_guard_update_launch((const uint8_t *)d_store, store_bytes, d_used, d_covered, stripe, group, d_guard, d_result,
-                                                  (hipStream_t)stream),
-                    "store guard update launch");
+    return guard_update(false, d_store, store_bytes, d_used, d_covered, stripe, group, d_guard, NULL, guard_bytes, d_result, stream);
+}
+
+int cw_dev_store_guard2_update(const void *d_store, size_t store_bytes, const uint64_t *d_used, uint64_t *d_covered, size_t stripe, unsigned group,
+                               void *d_guard_p, void *d_guard_q, size_t guard_bytes, uint64_t *d_result, void *stream)
+{
+    return guard_update(true, d_store, store_bytes, d_used, d_covered, stripe, group, d_guard_p, d_guard_q, guard_bytes, d_result, stream);
 }
 
 int cw_dev_store_guard_check(const void *d_store, size_t store_bytes, const uint64_t *d_covered, size_t stripe, unsigned group, const void *d_guard,
                              size_t guard_bytes, uint32_t *d_group_bad, uint64_t *d_result, void *stream)
 {
-    int rc;
-    const char *null = !d_covered ? "d_covered" : !d_result ? "d_result" : NULL;
-    if (null) return fail(CW_ERR_BAD_ARG, "NULL pointer: %s", null);
-    if ((rc = guard_args(d_store, store_bytes, stripe, group, d_guard, guard_bytes)) != CW_OK) return rc;
-    if ((rc = check_word_aligned((uintptr_t)d_covered | (uintptr_t)d_result, "d_covered / d_result")) != CW_OK) return rc;
-    if ((uintptr_t)d_group_bad & 3) return fail(CW_ERR_BAD_ARG, "d_group_bad is not 4-byte aligned");
-    if ((rc = ensure_init()) != CW_OK) return rc;
-    return launched_nomem(cw::store_guard_check_launch((const uint8_t *)d_store, store_bytes, d_covered, stripe, group, d_guard, d_group_bad, d_result,
-                                                       (hipStream_t)stream),
-                          "store guard check launch");
+    return guard_check(false, d_store, store_bytes, d_covered, stripe, group, d_guard, NULL, guard_bytes, d_group_bad, d_result, stream);
+}
+
+int cw_dev_store_guard2_check(const void *d_store, size_t store_bytes, const uint64_t *d_covered, size_t stripe, unsigned group,
+                              const void *d_guard_p, const void *d_guard_q, size_t guard_bytes, uint32_t *d_group_bad, uint64_t *d_result, void *stream)
+{
+    return guard_check(true, d_store, store_bytes, d_covered, stripe, group, d_guard_p, d_guard_q, guard_bytes, d_group_bad, d_result, stream);
 }
 
 int cw_dev_store_guard_rebuild(const void *d_store, size_t store_bytes, const cw_chunk_loc *d_dir, uint64_t dir_base, size_t dir_entries,
@@ -559,69 +618,8 @@ int cw_dev_store_guard_rebuild(const void *d_store, size_t store_bytes, const cw
                                const uint64_t *d_values, const uint64_t *d_count, size_t max_count, void *d_out, size_t out_bytes,
                                cw_chunk_loc *d_out_loc, uint32_t *d_status, uint64_t *d_result, void *stream)
 {
-    int rc = check_count("max_count", max_count);
-    if (rc != CW_OK) return rc;
-    const char *null = !d_dir ? "d_dir" : !d_covered ? "d_covered" : !d_values ? "d_values" : !d_count ? "d_count" : !d_out_loc ? "d_out_loc"
-                     : !d_status ? "d_status" : !d_result ? "d_result" : out_bytes && !d_out ? "d_out" : NULL;
-    if (null) return fail(CW_ERR_BAD_ARG, "NULL pointer: %s", null);
-    if (dir_entries == 0) return fail(CW_ERR_BAD_ARG, "dir_entries is 0");
-    if ((rc = guard_args(d_store, store_bytes, stripe, group, d_guard, guard_bytes)) != CW_OK) return rc;
-    if ((rc = check_dir_aligned((uintptr_t)d_dir | (uintptr_t)d_out_loc, "d_dir / d_out_loc")) != CW_OK) return rc;
-    if ((rc = check_word_aligned((uintptr_t)d_covered | (uintptr_t)d_values | (uintptr_t)d_count | (uintptr_t)d_result,
-                                 "d_covered / d_values / d_count / d_result")) != CW_OK)
-        return rc;
-    if ((uintptr_t)d_status & 3) return fail(CW_ERR_BAD_ARG, "d_status is not 4-byte aligned");
-    if (ranges_overlap(d_store, store_bytes, d_out, out_bytes)) return fail(CW_ERR_BAD_ARG, "d_out overlaps d_store");
-    if (ranges_overlap(d_guard, guard_bytes, d_out, out_bytes)) return fail(CW_ERR_BAD_ARG, "d_out overlaps d_guard");
-    if ((rc = ensure_init()) != CW_OK) return rc;
-    return launched_nomem(cw::store_guard_rebuild_launch((const uint8_t *)d_store, store_bytes, d_dir, dir_base, dir_entries, d_covered, stripe, group,
-                                                         d_guard, d_values, d_count, max_count, (uint8_t *)d_out, out_bytes, d_out_loc, d_status, d_result,
-                                                         (hipStream_t)stream),
-                          "store guard rebuild launch");
-}
-
-// ---- the dual guard: P and the GF(2^8) syndrome Q (kernels: guard2_kernels.hip) ------------------------------------------------
-// what the three dual calls refuse: guard_args of the store, the geometry and P, then the narrower group and Q
-static int guard2_args(const void *d_store, size_t store_bytes, size_t stripe, unsigned group, const void *d_guard_p, const void *d_guard_q,
-                       size_t guard_bytes)
-{
-    int rc;
-    if (!d_guard_q) return fail(CW_ERR_BAD_ARG, "NULL pointer: d_guard_q");
-    if ((rc = guard_args(d_store, store_bytes, stripe, group, d_guard_p, guard_bytes)) != CW_OK) return rc;
-    if (group > CW_GUARD2_MAX_GROUP) return fail(CW_ERR_BAD_ARG, "group %u is not in [1, 255]: the dual guard's stripe weights 2^m repeat after 255", group);
-    if ((rc = check_dir_aligned((uintptr_t)d_guard_q, "d_guard_q")) != CW_OK) return rc;
-    if (ranges_overlap(d_store, store_bytes, d_guard_q, guard_bytes)) return fail(CW_ERR_BAD_ARG, "d_guard_q overlaps d_store");
-    if (ranges_overlap(d_guard_p, guard_bytes, d_guard_q, guard_bytes)) return fail(CW_ERR_BAD_ARG, "d_guard_q overlaps d_guard_p");
-    return CW_OK;
-}
-
-int cw_dev_store_guard2_update(const void *d_store, size_t store_bytes, const uint64_t *d_used, uint64_t *d_covered, size_t stripe, unsigned group,
-                               void *d_guard_p, void *d_guard_q, size_t guard_bytes, uint64_t *d_result, void *stream)
-{
-    int rc;
-    const char *null = !d_used ? "d_used" : !d_covered ? "d_covered" : !d_result ? "d_result" : NULL;
-    if (null) return fail(CW_ERR_BAD_ARG, "NULL pointer: %s", null);
-    if ((rc = guard2_args(d_store, store_bytes, stripe, group, d_guard_p, d_guard_q, guard_bytes)) != CW_OK) return rc;
-    if ((rc = check_word_aligned((uintptr_t)d_used | (uintptr_t)d_covered | (uintptr_t)d_result, "d_used / d_covered / d_result")) != CW_OK) return rc;
-    if ((rc = ensure_init()) != CW_OK) return rc;
-    return launched(cw::store_guard2_update_launch((const uint8_t *)d_store, store_bytes, d_used, d_covered, stripe, group, d_guard_p, d_guard_q,
-                                                   d_result, (hipStream_t)stream),
-                    "store guard2 update launch");
-}
-
-int cw_dev_store_guard2_check(const void *d_store, size_t store_bytes, const uint64_t *d_covered, size_t stripe, unsigned group,
-                              const void *d_guard_p, const void *d_guard_q, size_t guard_bytes, uint32_t *d_group_bad, uint64_t *d_result, void *stream)
-{
-    int rc;
-    const char *null = !d_covered ? "d_covered" : !d_result ? "d_result" : NULL;
-    if (null) return fail(CW_ERR_BAD_ARG, "NULL pointer: %s", null);
-    if ((rc = guard2_args(d_store, store_bytes, stripe, group, d_guard_p, d_guard_q, guard_bytes)) != CW_OK) return rc;
-    if ((rc = check_word_aligned((uintptr_t)d_covered | (uintptr_t)d_result, "d_covered / d_result")) != CW_OK) return rc;
-    if ((uintptr_t)d_group_bad & 3) return fail(CW_ERR_BAD_ARG, "d_group_bad is not 4-byte aligned");
-    if ((rc = ensure_init()) != CW_OK) return rc;
-    return launched_nomem(cw::store_guard2_check_launch((const uint8_t *)d_store, store_bytes, d_covered, stripe, group, d_guard_p, d_guard_q,
-                                                        d_group_bad, d_result, (hipStream_t)stream),
-                          "store guard2 check launch");
+    return guard_rebuild(false, d_store, store_bytes, d_dir, dir_base, dir_entries, d_covered, stripe, group, d_guard, NULL, guard_bytes, d_values, d_count,
+                         max_count, d_out, out_bytes, d_out_loc, d_status, d_result, stream);
 }
 
 int cw_dev_store_guard2_rebuild(const void *d_store, size_t store_bytes, const cw_chunk_loc *d_dir, uint64_t dir_base, size_t dir_entries,
@@ -629,26 +627,8 @@ int cw_dev_store_guard2_rebuild(const void *d_store, size_t store_bytes, const c
                                 size_t guard_bytes, const uint64_t *d_values, const uint64_t *d_count, size_t max_count, void *d_out, size_t out_bytes,
                                 cw_chunk_loc *d_out_loc, uint32_t *d_status, uint64_t *d_result, void *stream)
 {
-    int rc = check_count("max_count", max_count);
-    if (rc != CW_OK) return rc;
-    const char *null = !d_dir ? "d_dir" : !d_covered ? "d_covered" : !d_values ? "d_values" : !d_count ? "d_count" : !d_out_loc ? "d_out_loc"
-                     : !d_status ? "d_status" : !d_result ? "d_result" : out_bytes && !d_out ? "d_out" : NULL;
-    if (null) return fail(CW_ERR_BAD_ARG, "NULL pointer: %s", null);
-    if (dir_entries == 0) return fail(CW_ERR_BAD_ARG, "dir_entries is 0");
-    if ((rc = guard2_args(d_store, store_bytes, stripe, group, d_guard_p, d_guard_q, guard_bytes)) != CW_OK) return rc;
-    if ((rc = check_dir_aligned((uintptr_t)d_dir | (uintptr_t)d_out_loc, "d_dir / d_out_loc")) != CW_OK) return rc;
-    if ((rc = check_word_aligned((uintptr_t)d_covered | (uintptr_t)d_values | (uintptr_t)d_count | (uintptr_t)d_result,
-                                 "d_covered / d_values / d_count / d_result")) != CW_OK)
-        return rc;
-    if ((uintptr_t)d_status & 3) return fail(CW_ERR_BAD_ARG, "d_status is not 4-byte aligned");
-    if (ranges_overlap(d_store, store_bytes, d_out, out_bytes)) return fail(CW_ERR_BAD_ARG, "d_out overlaps d_store");
-    if (ranges_overlap(d_guard_p, guard_bytes, d_out, out_bytes)) return fail(CW_ERR_BAD_ARG, "d_out overlaps d_guard_p");
-    if (ranges_overlap(d_guard_q, guard_bytes, d_out, out_bytes)) return fail(CW_ERR_BAD_ARG, "d_out overlaps d_guard_q");
-    if ((rc = ensure_init()) != CW_OK) return rc;
-    return launched_nomem(cw::store_guard2_rebuild_launch((const uint8_t *)d_store, store_bytes, d_dir, dir_base, dir_entries, d_covered, stripe, group,
-                                                          d_guard_p, d_guard_q, d_values, d_count, max_count, (uint8_t *)d_out, out_bytes, d_out_loc,
-                                                          d_status, d_result, (hipStream_t)stream),
-                          "store guard2 rebuild launch");
+    return guard_rebuild(true, d_store, store_bytes, d_dir, dir_base, dir_entries, d_covered, stripe, group, d_guard_p, d_guard_q, guard_bytes, d_values,
+                         d_count, max_count, d_out, out_bytes, d_out_loc, d_status, d_result, stream);
 }
 
 } // extern "C"

@@ -339,30 +339,21 @@ hipError_t store_verify_launch(int lzf, const uint8_t *store, size_t store_bytes
 hipError_t dedupe_verify_launch(unsigned words, const uint64_t *state, const uint64_t *value, const uint64_t *key, uint64_t cap, uint64_t dir_base,
                                 const uint64_t *head, const uint32_t *decoded, const uint64_t *digests, uint32_t *verdict, hipStream_t s);
 
-// XOR guard stripes over the store's bytes (guard_kernels.hip; semantics: the public header).  The geometry is checked by the caller;
-// groups = the groups of store_bytes, ceil(store_bytes / (stripe * group)); group_bad, out and out_loc may be NULL as the header says
+// Guard stripes over the store's bytes (guard_kernels.hip; semantics: the public header): the XOR guard P and, when guard_q is not
+// NULL, the GF(2^8) syndrome Q beside it (the dual guard, group <= 255).  The geometry is checked by the caller; groups = the groups
+// of store_bytes, ceil(store_bytes / (stripe * group)); group_bad, out and out_loc may be NULL as the header says.  result is [4],
+// the dual rebuild's [5]
 size_t store_guard_groups(size_t store_bytes, size_t stripe, unsigned group);
-size_t store_guard_check_scratch_bytes(size_t groups);
+size_t store_guard_check_scratch_bytes(size_t groups, bool dual);
 size_t store_guard_rebuild_scratch_bytes(size_t max_count, size_t groups);
 hipError_t store_guard_update_launch(const uint8_t *store, size_t store_bytes, const uint64_t *d_used, uint64_t *d_covered, size_t stripe,
-                                     unsigned group, void *guard, uint64_t *result, hipStream_t stream);
+                                     unsigned group, void *guard_p, void *guard_q, uint64_t *result, hipStream_t stream);
 hipError_t store_guard_check_launch(const uint8_t *store, size_t store_bytes, const uint64_t *d_covered, size_t stripe, unsigned group,
-                                    const void *guard, uint32_t *group_bad, uint64_t *result, hipStream_t stream);
+                                    const void *guard_p, const void *guard_q, uint32_t *group_bad, uint64_t *result, hipStream_t stream);
 hipError_t store_guard_rebuild_launch(const uint8_t *store, size_t store_bytes, const void *dir, uint64_t dir_base, size_t dir_entries,
-                                      const uint64_t *d_covered, size_t stripe, unsigned group, const void *guard, const uint64_t *values,
-                                      const uint64_t *d_count, size_t max_count, uint8_t *out, size_t out_bytes, void *out_loc, uint32_t *status,
-                                      uint64_t *result, hipStream_t stream);
-// The dual guard: P as above and the GF(2^8) syndrome Q beside it (guard2_kernels.hip), group <= 255; result is [4], the rebuild's [5].
-// The rebuild's scratch is store_guard_rebuild_scratch_bytes
-size_t store_guard2_check_scratch_bytes(size_t groups);
-hipError_t store_guard2_update_launch(const uint8_t *store, size_t store_bytes, const uint64_t *d_used, uint64_t *d_covered, size_t stripe,
-                                      unsigned group, void *guard_p, void *guard_q, uint64_t *result, hipStream_t stream);
-hipError_t store_guard2_check_launch(const uint8_t *store, size_t store_bytes, const uint64_t *d_covered, size_t stripe, unsigned group,
-                                     const void *guard_p, const void *guard_q, uint32_t *group_bad, uint64_t *result, hipStream_t stream);
-hipError_t store_guard2_rebuild_launch(const uint8_t *store, size_t store_bytes, const void *dir, uint64_t dir_base, size_t dir_entries,
-                                       const uint64_t *d_covered, size_t stripe, unsigned group, const void *guard_p, const void *guard_q,
-                                       const uint64_t *values, const uint64_t *d_count, size_t max_count, uint8_t *out, size_t out_bytes, void *out_loc,
-                                       uint32_t *status, uint64_t *result, hipStream_t stream);
+                                      const uint64_t *d_covered, size_t stripe, unsigned group, const void *guard_p, const void *guard_q,
+                                      const uint64_t *values, const uint64_t *d_count, size_t max_count, uint8_t *out, size_t out_bytes, void *out_loc,
+                                      uint32_t *status, uint64_t *result, hipStream_t stream);
 
 hipError_t sum_sizes_launch(const uint32_t *sizes, size_t n, uint32_t raw_bytes, uint64_t *totals, hipStream_t stream);
 hipError_t gen_random_launch(uint64_t seed, uint64_t first_block, size_t nblocks, size_t block_bytes, uint8_t *dst,

@@ -319,15 +319,18 @@ class ChunkStore:
         torch.cuda.synchronize()  # (torch zeroed them on its own stream)
         self._fold()
 
+    def _guard_call(self, single, dual, front: tuple, back: tuple) -> None:
+        """One guard call of ops.py on this store's stream, ``single`` or ``dual`` by the store's parity: the store's bytes, ``front``
+        (the call's arguments between them and the geometry), the geometry, the guard or guards and their size, ``back`` (the rest)."""
+        guards = [self.d_guard.data_ptr()] + ([] if self.d_guard_q is None else [self.d_guard_q.data_ptr()])
+        (single if self.d_guard_q is None else dual)(self.d_store.data_ptr(), self.store_bytes, *front, self.stripe, self.group, *guards,
+                                                     self.d_guard.numel(), *back, self._stream())
+
     def _fold(self) -> None:
         """The one guard update: queued, not synchronised.  Nothing when the store is not protected."""
-        if self.d_guard_q is not None:
-            dev_store_guard2_update(self.d_store.data_ptr(), self.store_bytes, self.d_used.data_ptr(), self.d_covered.data_ptr(), self.stripe,
-                                    self.group, self.d_guard.data_ptr(), self.d_guard_q.data_ptr(), self.d_guard.numel(),
-                                    self._fold_result.data_ptr(), self._stream())
-        elif self.d_guard is not None:
-            dev_store_guard_update(self.d_store.data_ptr(), self.store_bytes, self.d_used.data_ptr(), self.d_covered.data_ptr(), self.stripe,
-                                   self.group, self.d_guard.data_ptr(), self.d_guard.numel(), self._fold_result.data_ptr(), self._stream())
+        if self.d_guard is not None:
+            self._guard_call(dev_store_guard_update, dev_store_guard2_update, (self.d_used.data_ptr(), self.d_covered.data_ptr()),
+                             (self._fold_result.data_ptr(),))
 
     def protected_bytes(self) -> int:
         """The guard's cursor: the stored bytes [0, protected_bytes()) are folded in.  Equal to ``used()`` whenever a method has
@@ -344,13 +347,7 @@ class ChunkStore:
         groups = self.d_guard.numel() // self.stripe
         bad, result = _zeros(groups, torch.int32), _zeros(4)
         torch.cuda.synchronize()
-        if self.d_guard_q is not None:
-            dev_store_guard2_check(self.d_store.data_ptr(), self.store_bytes, self.d_covered.data_ptr(), self.stripe, self.group,
-                                   self.d_guard.data_ptr(), self.d_guard_q.data_ptr(), self.d_guard.numel(), bad.data_ptr(), result.data_ptr(),
-                                   self._stream())
-        else:
-            dev_store_guard_check(self.d_store.data_ptr(), self.store_bytes, self.d_covered.data_ptr(), self.stripe, self.group,
-                                  self.d_guard.data_ptr(), self.d_guard.numel(), bad.data_ptr(), result.data_ptr(), self._stream())
+        self._guard_call(dev_store_guard_check, dev_store_guard2_check, (self.d_covered.data_ptr(),), (bad.data_ptr(), result.data_ptr()))
         torch.cuda.synchronize()
         verdict, checked, differ, _ = _words(result)
         if verdict:
@@ -1215,16 +1212,9 @@ class ChunkStore:
         payload, total = None, 0
         for dry in (True, False):
             torch.cuda.synchronize()
-            if self.d_guard_q is not None:
-                dev_store_guard2_rebuild(self.d_store.data_ptr(), self.store_bytes, self.d_dir.data_ptr(), self.dir_base, n,
-                                         self.d_covered.data_ptr(), self.stripe, self.group, self.d_guard.data_ptr(), self.d_guard_q.data_ptr(),
-                                         self.d_guard.numel(), d_val.data_ptr(), d_count.data_ptr(), m, 0 if dry else payload.data_ptr(), total,
-                                         d_loc.data_ptr(), d_status.data_ptr(), result.data_ptr(), s)
-            else:
-                dev_store_guard_rebuild(self.d_store.data_ptr(), self.store_bytes, self.d_dir.data_ptr(), self.dir_base, n,
-                                        self.d_covered.data_ptr(), self.stripe, self.group, self.d_guard.data_ptr(), self.d_guard.numel(),
-                                        d_val.data_ptr(), d_count.data_ptr(), m, 0 if dry else payload.data_ptr(), total, d_loc.data_ptr(),
-                                        d_status.data_ptr(), result.data_ptr(), s)
+            self._guard_call(dev_store_guard_rebuild, dev_store_guard2_rebuild, (self.d_dir.data_ptr(), self.dir_base, n, self.d_covered.data_ptr()),
+                             (d_val.data_ptr(), d_count.data_ptr(), m, 0 if dry else payload.data_ptr(), total, d_loc.data_ptr(),
+                              d_status.data_ptr(), result.data_ptr()))
             torch.cuda.synchronize()
             verdict, needed = _words(result, 2)
             if verdict == 2:

@@ -283,3 +283,125 @@ def test_rebuild_of_more_positions_than_workgroups(cw, parity):
             if s == 0:
                 pos, m, to = entries[v][0], entries[v][1], int(locs[k]["pos"])
                 assert (out[to:to + m] == noise.host[pos:pos + m]).all(), k
+
+
+# ---- 3. both parities on the scratch they share ------------------------------------------------------------------------------------------
+class Mixed:
+    """Three whole groups of two stripes and 5000 bytes, both guards folded to the end, then four damaged extents: two that meet in
+    guard bytes (members 0 and 1 of group 0, columns 2500 .. 4000) -- collided for the single guard, rebuilt with Q by the dual one --,
+    one of 65536 bytes across a stripe boundary of group 1 and one of a single byte in the last, partial group.  Listed: the four,
+    the first once more and a value that names no entry.  The model's answers for the single (1) and the dual (2) guard, each once."""
+    S, G, n = S16, 2, 3 * 2 * S16 + 5000
+
+    def __init__(self):
+        S, G, n = self.S, self.G, self.n
+        rng = np.random.default_rng(2830)
+        self.host = rng.integers(0, 256, n, dtype=np.uint8)
+        hurt_extents = [(1000, 3000), (S + 2500, 2000), (3 * S - 700, 65536), (6 * S + 4000, 1)]
+        entries, taken = [GM.entry(at, m) for at, m in hurt_extents], sorted(hurt_extents)
+        for lo, hi in zip([0] + [at + m for at, m in taken], [at for at, _ in taken] + [n]):   # other extents in the room between them
+            at = lo + int(rng.integers(0, 3000))
+            while len(entries) < 40:
+                m = int(rng.integers(1, 9000))
+                if at + m > hi:
+                    break
+                entries.append(GM.entry(at, m))
+                at += m + int(rng.integers(0, 6000))
+        assert 36 <= len(entries) <= 40 and n == 398216
+        self.directory = np.array(entries, RM.LOC)
+        self.values = [0, 1, 2, 3, 0, len(entries) + 3]
+        self.hurt = self.host.copy()
+        for at, m in hurt_extents:
+            self.hurt[at:at + m] ^= 0x5A
+        self.pq = G2.guards_of(self.host, n, S, G, n)
+        self.groups = len(self.pq[0]) // S
+        p, q = self.pq
+        self.want = {("check", 1): GM.check(p, self.hurt, n, n, S, G), ("check", 2): G2.check(p, q, self.hurt, n, n, S, G),
+                     ("rebuild", 1): GM.rebuild(self.hurt, n, self.directory, 0, n, S, G, p, self.values, 1 << 62),
+                     ("rebuild", 2): G2.rebuild(self.hurt, n, self.directory, 0, n, S, G, p, q, self.values, 1 << 62)}
+        # what the case is for: the two parities disagree on the first two extents
+        assert self.want["rebuild", 1][1].tolist() == [1, 1, 0, 0, 1, 2] and self.want["rebuild", 1][0] == [0, 65537, 6, 2]
+        assert self.want["rebuild", 2][1].tolist() == [0, 0, 0, 0, 0, 2] and self.want["rebuild", 2][0] == [0, 65537 + 3000 + 2000 + 3000, 6, 5, 3]
+        assert self.want["check", 1][1].tolist() == [1, 1, 0, 1] and self.want["check", 2][1].tolist() == [3, 3, 0, 3]
+        self.d_hurt, self.d_dir = _dev_bytes(self.hurt), _dev_bytes(self.directory)
+        self.d_val, self.d_count = _dev_u64(self.values + [0]), _dev_u64([len(self.values)])
+        self.g = Guards(self.pq, n)
+
+
+@pytest.fixture(scope="module")
+def mixed(cw):
+    return Mixed()
+
+
+class Call:
+    """One check or rebuild of ``Mixed`` at one parity: poisoned outputs of its own, made before anything is queued; ``launch`` queues
+    the call and synchronises nothing; ``outputs`` reads what it wrote."""
+
+    def __init__(self, cw, c, op, parity):
+        self.cw, self.c, self.op, self.parity = cw, c, op, parity
+        words = 5 if (op, parity) == ("rebuild", 2) else 4                   # (only the dual rebuild reports a fifth word)
+        self.result = _dev_u64([7] * words + [T2.POISON64])
+        if op == "check":
+            self.bad = _dev_bytes(np.full(c.groups + 2, 0xEEEEEEEE, np.uint32))
+        else:
+            self.m, self.total = len(c.values), c.want[op, parity][0][1]
+            self.out = _dev_bytes(np.full(self.total + 2 * T1.PAD, 0xEE, np.uint8))
+            self.loc = _dev_bytes(np.full(2 * (self.m + 2), T2.POISON64, np.uint64))
+            self.status = _dev_bytes(np.full(self.m + 2, 0xEEEEEEEE, np.uint32))
+
+    def launch(self, stream):
+        c, g, cw = self.c, self.c.g, self.cw
+        guards = (g.p.ptr(),) if self.parity == 1 else (g.p.ptr(), g.q.ptr())
+        if self.op == "check":
+            fn = cw.dev_store_guard_check if self.parity == 1 else cw.dev_store_guard2_check
+            fn(c.d_hurt.data_ptr(), c.n, g.d_covered.data_ptr(), c.S, c.G, *guards, g.size, self.bad.data_ptr() + 4, self.result.data_ptr(), stream)
+        else:
+            fn = cw.dev_store_guard_rebuild if self.parity == 1 else cw.dev_store_guard2_rebuild
+            fn(c.d_hurt.data_ptr(), c.n, c.d_dir.data_ptr(), 0, len(c.directory), g.d_covered.data_ptr(), c.S, c.G, *guards, g.size,
+               c.d_val.data_ptr(), c.d_count.data_ptr(), self.m, self.out.data_ptr() + T1.PAD, self.total, self.loc.data_ptr() + 16,
+               self.status.data_ptr() + 4, self.result.data_ptr(), stream)
+
+    def outputs(self):
+        r = _u64(self.result).tolist()
+        assert r[-1] == T2.POISON64
+        if self.op == "check":
+            bad = self.bad.cpu().numpy().view(np.uint32)
+            assert bad[0] == bad[-1] == 0xEEEEEEEE
+            return r[:-1], bad[1:-1].tolist()
+        h, locs, st = self.out.cpu().numpy(), self.loc.cpu().numpy().view(np.uint64), self.status.cpu().numpy().view(np.uint32)
+        assert (h[:T1.PAD] == 0xEE).all() and (h[T1.PAD + self.total:] == 0xEE).all(), "a store left d_out"
+        assert (locs[:2] == T2.POISON64).all() and (locs[-2:] == T2.POISON64).all() and st[0] == st[-1] == 0xEEEEEEEE
+        return r[:-1], st[1:-1].tolist(), h[T1.PAD:T1.PAD + self.total].tobytes(), locs[2:-2].tobytes()
+
+    def wanted(self):
+        want = self.c.want[self.op, self.parity]
+        if self.op == "check":
+            return want[0], want[1].tolist()
+        return want[0], want[1].tolist(), want[2].tobytes(), want[3].tobytes()
+
+
+SEQUENCE = [("check", 1), ("check", 2), ("rebuild", 1), ("rebuild", 2), ("check", 1), ("check", 2)]
+
+
+@pytest.mark.parametrize("streams", ["one stream", "a stream per parity"])
+def test_both_parities_queued_on_the_scratch_they_share(cw, mixed, streams):
+    """Single check, dual check, single rebuild, dual rebuild, single check, dual check, queued with nothing synchronised between them
+    -- on one stream, where every call reuses the stream's one guard scratch behind the other parity's, and with the single calls
+    on one stream and the dual calls on another: every result, flag, status, loc and payload byte is the model's, and equals what
+    the same call writes alone on a fresh stream."""
+    import torch
+    queues = [torch.cuda.Stream() for _ in range(1 if streams == "one stream" else 2)]
+    calls = [Call(cw, mixed, op, parity) for op, parity in SEQUENCE]
+    alone = [Call(cw, mixed, op, parity) for op, parity in SEQUENCE]
+    _sync()
+    for call in calls:
+        call.launch(queues[(call.parity - 1) % len(queues)].cuda_stream)
+    _sync()
+    for k, (call, lone) in enumerate(zip(calls, alone)):
+        fresh = torch.cuda.Stream()
+        lone.launch(fresh.cuda_stream)
+        _sync()
+        got = call.outputs()
+        assert got == call.wanted(), (k, call.op, call.parity)
+        assert got == lone.outputs(), (k, call.op, call.parity)
+    mixed.g.host()                                                           # (the guards are only read)

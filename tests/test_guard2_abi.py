@@ -1,6 +1,6 @@
 """CPU-side checks of the dual guard: the three symbols are declared, listed, exported and mirrored, the calls refuse bad arguments
 before the device -- group = 256, a d_guard_q that overlaps each other buffer, misalignments among them -- and fail loudly without a
-device, and guard2_kernels.hip compiles for gfx950 without scratch memory or spills."""
+device, and the dual guard's kernels in guard_kernels.hip compile for gfx950 without scratch memory or spills."""
 import inspect
 import os
 import re
@@ -8,12 +8,12 @@ import subprocess
 
 import pytest
 
+import guard_isa
 import guard_model as GM
 from conftest import ROOT
 
 NEW_SYMBOLS = ["cw_dev_store_guard2_update", "cw_dev_store_guard2_check", "cw_dev_store_guard2_rebuild"]
 NO_DEVICE, BAD_ARG = -1, -2
-HIPCC = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-S", "--cuda-device-only", "--offload-arch=gfx950"]
 TOO_MANY = (1 << 32) - 255
 S = 65536
 BAD_GEOMETRIES = [(32768, 2), (65536 + 16, 2), (3 * 65536, 2), (1 << 31, 2), (0, 2), (S, 0), (S, 257)]
@@ -44,8 +44,8 @@ def test_header_declares_and_binding_lists_the_symbols(cwlib):
     assert "detail" in inspect.signature(cwlib.ChunkStore.guard_check).parameters
     assert cwlib.ChunkStore.last_repair is None and cwlib.ChunkStore.d_guard_q is None
     makefile = open(os.path.join(ROOT, "compute_war_amd", "csrc", "Makefile")).read()
-    assert "guard2_kernels.hip" in re.search(r"^SRCS\s*:=(.*)$", makefile, flags=re.M).group(1)
-    assert "guard_device.h" in re.search(r"^HDRS\s*:=(.*)$", makefile, flags=re.M).group(1)
+    assert "guard_kernels.hip" in re.search(r"^SRCS\s*:=(.*)$", makefile, flags=re.M).group(1)
+    assert "guard2_kernels.hip" not in makefile and "guard_device.h" not in makefile
     for doc in ("README.md", "DESIGN.md", "INTEGRATION.md"):
         assert "cw_dev_store_guard2_rebuild" in open(os.path.join(ROOT, doc)).read(), doc
 
@@ -157,30 +157,10 @@ def test_no_gpu_means_no_guard(cwlib):
     assert e.value.code == NO_DEVICE
 
 
-def _meta(asm):
-    meta = asm[asm.index("amdhsa.kernels"):]
-    out = {}
-    for e in re.split(r"\n  - ", meta):
-        m = re.search(r"\.name:\s+(\S+)", e)
-        if m:
-            out[m.group(1)] = e
-    return out
-
-
 def test_guard2_kernels_have_no_private_segment_or_spills(tmp_path):
-    """guard2_kernels.hip: fold and its finish; compare and its finish; the rebuild's count, scatter, status, fill, pair, copy and finish."""
-    out = str(tmp_path / "guard2_kernels.s")
-    subprocess.run(HIPCC + [os.path.join(ROOT, "compute_war_amd", "csrc", "guard2_kernels.hip"), "-o", out], check=True, capture_output=True)
-    meta = _meta(open(out).read())
-    names = ("guard2_fold", "guard2_update_finish", "guard2_compare", "guard2_check_finish", "rebuild2_count", "rebuild2_scatter", "rebuild2_status",
-             "rebuild2_fill", "rebuild2_pair", "rebuild2_copy", "rebuild2_finish")
-    assert len(meta) == len(names), sorted(meta)
-    for name in names:
-        assert sum(bool(re.search(r"\d%s_kernel" % name, k)) for k in meta) == 1, name
-    for name, e in meta.items():
-        assert re.search(r"\.private_segment_fixed_size:\s+0\b", e), name
-        assert re.search(r"\.vgpr_spill_count:\s+0\b", e), name
-        assert re.search(r"\.sgpr_spill_count:\s+0\b", e), name
+    """guard_kernels.hip, the dual guard: fold and its finish; compare and its finish; the rebuild's count, scatter, status, fill, pair,
+    copy and finish -- the Dual = true instantiations, the kernels that exist once and the two only the dual guard runs.  No kernel of
+    the file has scratch memory or spills."""
+    meta = dict(zip(guard_isa.DUAL, guard_isa.compiled(tmp_path, guard_isa.DUAL)))
     # the update has no tables and no LDS
-    fold = next(e for k, e in meta.items() if "guard2_fold_kernel" in k)
-    assert re.search(r"\.group_segment_fixed_size:\s+0\b", fold)
+    assert guard_isa.lds_bytes(meta["guard_fold_kernelILb1E"]) == 0

@@ -7,12 +7,12 @@ import subprocess
 
 import pytest
 
+import guard_isa
 import guard_model as GM
 from conftest import ROOT
 
 NEW_SYMBOLS = ["cw_store_guard_bytes", "cw_dev_store_guard_update", "cw_dev_store_guard_check", "cw_dev_store_guard_rebuild"]
 NO_DEVICE, BAD_ARG = -1, -2
-HIPCC = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-S", "--cuda-device-only", "--offload-arch=gfx950"]
 TOO_MANY = (1 << 32) - 255
 S = 65536
 BAD_GEOMETRIES = [(32768, 2), (65536 + 16, 2), (3 * 65536, 2), (1 << 31, 2), (0, 2), (S, 0), (S, 257)]
@@ -44,6 +44,7 @@ def test_header_declares_and_binding_lists_the_symbols(cwlib):
         assert hasattr(cwlib.ChunkStore, name)
     makefile = open(os.path.join(ROOT, "compute_war_amd", "csrc", "Makefile")).read()
     assert "guard_kernels.hip" in re.search(r"^SRCS\s*:=(.*)$", makefile, flags=re.M).group(1)
+    assert "guard2_kernels.hip" not in makefile and "guard_device.h" not in makefile
     for doc in ("README.md", "DESIGN.md", "INTEGRATION.md"):
         assert "cw_dev_store_guard_rebuild" in open(os.path.join(ROOT, doc)).read(), doc
 
@@ -159,27 +160,10 @@ def test_no_gpu_means_no_guard(cwlib):
     assert e.value.code == NO_DEVICE
 
 
-def _meta(asm):
-    meta = asm[asm.index("amdhsa.kernels"):]
-    out = {}
-    for e in re.split(r"\n  - ", meta):
-        m = re.search(r"\.name:\s+(\S+)", e)
-        if m:
-            out[m.group(1)] = e
-    return out
-
-
 def test_guard_kernels_have_no_private_segment_or_spills(tmp_path):
-    """guard_kernels.hip: fold and its finish; compare and its finish; the rebuild's count, scatter, status, copy and finish."""
-    out = str(tmp_path / "guard_kernels.s")
-    subprocess.run(HIPCC + [os.path.join(ROOT, "compute_war_amd", "csrc", "guard_kernels.hip"), "-o", out], check=True, capture_output=True)
-    meta = _meta(open(out).read())
-    names = ("guard_fold", "guard_update_finish", "guard_compare", "guard_check_finish", "rebuild_count", "rebuild_scatter", "rebuild_status",
-             "rebuild_copy", "rebuild_finish")
-    assert len(meta) == len(names), sorted(meta)
-    for name in names:
-        assert sum(bool(re.search(r"\d%s_kernel" % name, k)) for k in meta) == 1, name
-    for name, e in meta.items():
-        assert re.search(r"\.private_segment_fixed_size:\s+0\b", e), name
-        assert re.search(r"\.vgpr_spill_count:\s+0\b", e), name
-        assert re.search(r"\.sgpr_spill_count:\s+0\b", e), name
+    """guard_kernels.hip, the single guard: fold and its finish; compare and its finish; the rebuild's count, scatter, status, copy and
+    finish -- the Dual = false instantiations and the kernels that exist once.  No kernel of the file has scratch memory or spills."""
+    meta = dict(zip(guard_isa.SINGLE, guard_isa.compiled(tmp_path, guard_isa.SINGLE)))
+    # the update has no LDS, and the single copy none of the dual copy's field tables
+    assert guard_isa.lds_bytes(meta["guard_fold_kernelILb0E"]) == 0
+    assert guard_isa.lds_bytes(meta["rebuild_copy_kernelILb0E"]) == 0
