@@ -12,13 +12,13 @@ from .ops import (ACCOUNT_DTYPE, COMPOSE_DTYPE, DELTA_OP_DTYPE, CdcParams, Chunk
                   dev_compress, dev_compress_chunks, dev_decompress, dev_decompress_chunks, dev_gen_mixed, dev_gen_random, dev_hash,
                   dev_hash_and_compress, dev_hash_chunks, dev_hash_tree, dev_ingest_commit, dev_ingest_commit_streams, dev_pack,
                   dev_pack_chunks, dev_read_ranges, dev_recipe_diff, dev_restore_chunks, dev_scatter_extents, dev_store_account, dev_store_chunks, dev_store_compact, dev_store_export_chunks, dev_store_guard_check, dev_store_guard_rebuild, dev_store_guard_update,
-                  dev_store_guard2_check, dev_store_guard2_rebuild, dev_store_guard2_update,
+                  dev_store_guard2_check, dev_store_guard2_locate, dev_store_guard2_rebuild, dev_store_guard2_update, dev_store_guard_locate,
                   dev_store_import_chunks, dev_store_mark, dev_store_renumber, dev_store_replace_chunks, dev_store_verify, dev_sum_sizes,
                   dev_translate_refs, device_count, digest_bytes, do_compression, do_decompression, do_hashing, get_device,
                   hash_and_compress_blocks, hash_and_compress_packed, hash_blocks, hash_plan_describe, hash_tree_blocks, init,
                   plan_describe, profile_enable, profile_kernels, profile_read, set_block_size, set_device, shutdown, store_compose, store_guard_bytes, store_ingest,
                   store_ingest_streams, store_patch, store_restore, store_scrub, tune_reset, tune_set, tuned)
-from .store import DIFF_TOTALS, LOC_DTYPE, Account, Bundle, ChunkStore, Delta, Diff, Recipe, ScrubReport, apply_delta
+from .store import DIFF_TOTALS, LOC_DTYPE, Account, Bundle, ChunkStore, Delta, Diff, GuardSuspects, Recipe, ScrubReport, apply_delta
 
 # (the import above also binds the submodule ``store``, which is not an export; ``ops`` has always been listed)
 __all__ = [n for n in dir() if not n.startswith("_") and n != "store"]

@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "cw_dev_store_verify", "cw_store_scrub", "cw_dev_store_replace_chunks",
     "cw_store_guard_bytes", "cw_dev_store_guard_update", "cw_dev_store_guard_check", "cw_dev_store_guard_rebuild",
     "cw_dev_store_guard2_update", "cw_dev_store_guard2_check", "cw_dev_store_guard2_rebuild",
+    "cw_dev_store_guard_locate", "cw_dev_store_guard2_locate",
     "cw_dev_store_renumber", "cw_dev_dedupe_revalue", "cw_dev_store_account",
     "cw_dev_cdc_resync", "cw_store_patch", "cw_dev_recipe_diff", "cw_dev_apply_delta",
     "cw_dev_cdc_resync_windows", "cw_dev_scatter_extents", "cw_store_compose",
@@ -191,6 +192,8 @@ def lib() -> C.CDLL:
         "cw_dev_store_guard2_update": ([vp, sz, vp, vp, sz, C.c_uint, vp, vp, sz, vp, vp], C.c_int),
         "cw_dev_store_guard2_check": ([vp, sz, vp, sz, C.c_uint, vp, vp, sz, u32p, vp, vp], C.c_int),
         "cw_dev_store_guard2_rebuild": ([vp, sz, vp, C.c_uint64, sz, vp, sz, C.c_uint, vp, vp, sz, vp, vp, sz, vp, sz, vp, u32p, vp, vp], C.c_int),
+        "cw_dev_store_guard_locate": ([vp, sz, vp, C.c_uint64, sz, vp, sz, C.c_uint, vp, sz, u32p, vp, vp], C.c_int),
+        "cw_dev_store_guard2_locate": ([vp, sz, vp, C.c_uint64, sz, vp, sz, C.c_uint, vp, vp, sz, u32p, vp, vp], C.c_int),
         "cw_dev_store_renumber": ([vp, C.c_uint64, sz, u32p, C.c_uint64, vp, C.c_uint64, sz, vp, vp, sz, vp, vp], C.c_int),
         "cw_dev_dedupe_revalue": ([vp, vp, vp, vp, sz, C.c_uint64, C.c_uint64, vp, vp], C.c_int),
         "cw_dev_store_account": ([vp, vp, sz, sz, vp, C.c_uint64, sz, u32p, vp, u32p, u32p, vp, vp], C.c_int),

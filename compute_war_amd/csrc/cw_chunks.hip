@@ -502,7 +502,7 @@ int cw_dev_translate_refs(const uint64_t *d_ref, const uint64_t *d_count, size_t
                     "translate refs launch");
 }
 
-// ---- guard stripes over the store's bytes, P alone or P and Q: update, check, rebuild (kernels: guard_kernels.hip) ---------------
+// ---- guard stripes over the store's bytes, P alone or P and Q: update, check, rebuild (kernels: guard_kernels.hip), locate ------
 size_t cw_store_guard_bytes(size_t store_bytes, size_t stripe, unsigned group)
 {
     if (stripe < CW_GUARD_MIN_STRIPE || stripe > CW_GUARD_MAX_STRIPE || (stripe & (stripe - 1)) || group < 1 || group > CW_GUARD_MAX_GROUP) return 0;
@@ -589,6 +589,27 @@ static int guard_rebuild(bool dual, const void *d_store, size_t store_bytes, con
                           dual ? "store guard2 rebuild launch" : "store guard rebuild launch");
 }
 
+// (kernels: guard_locate_kernels.hip; dir_base shifts no entry: the output is per entry, not per value)
+static int guard_locate(bool dual, const void *d_store, size_t store_bytes, const cw_chunk_loc *d_dir, uint64_t dir_base, size_t dir_entries,
+                        const uint64_t *d_covered, size_t stripe, unsigned group, const void *d_guard, const void *d_guard_q, size_t guard_bytes,
+                        uint32_t *d_suspect, uint64_t *d_result, void *stream)
+{
+    (void)dir_base;
+    int rc;
+    const char *null = !d_dir ? "d_dir" : !d_covered ? "d_covered" : !d_suspect ? "d_suspect" : !d_result ? "d_result" : NULL;
+    if (null) return fail(CW_ERR_BAD_ARG, "NULL pointer: %s", null);
+    if (dir_entries == 0) return fail(CW_ERR_BAD_ARG, "dir_entries is 0");
+    if ((rc = check_count("dir_entries", dir_entries)) != CW_OK) return rc;
+    if ((rc = guard_args(dual, d_store, store_bytes, stripe, group, d_guard, d_guard_q, guard_bytes)) != CW_OK) return rc;
+    if ((rc = check_dir_aligned((uintptr_t)d_dir, "d_dir")) != CW_OK) return rc;
+    if ((rc = check_word_aligned((uintptr_t)d_covered | (uintptr_t)d_result, "d_covered / d_result")) != CW_OK) return rc;
+    if ((uintptr_t)d_suspect & 3) return fail(CW_ERR_BAD_ARG, "d_suspect is not 4-byte aligned");
+    if ((rc = ensure_init()) != CW_OK) return rc;
+    return launched_nomem(cw::store_guard_locate_launch((const uint8_t *)d_store, store_bytes, d_dir, dir_entries, d_covered, stripe, group, d_guard,
+                                                        d_guard_q, d_suspect, d_result, (hipStream_t)stream),
+                          dual ? "store guard2 locate launch" : "store guard locate launch");
+}
+
 int cw_dev_store_guard_update(const void *d_store, size_t store_bytes, const uint64_t *d_used, uint64_t *d_covered, size_t stripe, unsigned group,
                               void *d_guard, size_t guard_bytes, uint64_t *d_result, void *stream)
 {
@@ -629,6 +650,22 @@ int cw_dev_store_guard2_rebuild(const void *d_store, size_t store_bytes, const c
 {
     return guard_rebuild(true, d_store, store_bytes, d_dir, dir_base, dir_entries, d_covered, stripe, group, d_guard_p, d_guard_q, guard_bytes, d_values,
                          d_count, max_count, d_out, out_bytes, d_out_loc, d_status, d_result, stream);
+}
+
+int cw_dev_store_guard_locate(const void *d_store, size_t store_bytes, const cw_chunk_loc *d_dir, uint64_t dir_base, size_t dir_entries,
+                              const uint64_t *d_covered, size_t stripe, unsigned group, const void *d_guard, size_t guard_bytes, uint32_t *d_suspect,
+                              uint64_t *d_result, void *stream)
+{
+    return guard_locate(false, d_store, store_bytes, d_dir, dir_base, dir_entries, d_covered, stripe, group, d_guard, NULL, guard_bytes, d_suspect,
+                        d_result, stream);
+}
+
+int cw_dev_store_guard2_locate(const void *d_store, size_t store_bytes, const cw_chunk_loc *d_dir, uint64_t dir_base, size_t dir_entries,
+                               const uint64_t *d_covered, size_t stripe, unsigned group, const void *d_guard_p, const void *d_guard_q,
+                               size_t guard_bytes, uint32_t *d_suspect, uint64_t *d_result, void *stream)
+{
+    return guard_locate(true, d_store, store_bytes, d_dir, dir_base, dir_entries, d_covered, stripe, group, d_guard_p, d_guard_q, guard_bytes, d_suspect,
+                        d_result, stream);
 }
 
 } // extern "C"

@@ -354,6 +354,11 @@ hipError_t store_guard_rebuild_launch(const uint8_t *store, size_t store_bytes, 
                                       const uint64_t *d_covered, size_t stripe, unsigned group, const void *guard_p, const void *guard_q,
                                       const uint64_t *values, const uint64_t *d_count, size_t max_count, uint8_t *out, size_t out_bytes, void *out_loc,
                                       uint32_t *status, uint64_t *result, hipStream_t stream);
+// The entries the syndromes suspect (guard_locate_kernels.hip): suspect is u32[dir_entries], result is [8]; scratch per stream
+size_t store_guard_locate_scratch_bytes(size_t groups, size_t stripe);
+hipError_t store_guard_locate_launch(const uint8_t *store, size_t store_bytes, const void *dir, size_t dir_entries, const uint64_t *d_covered,
+                                     size_t stripe, unsigned group, const void *guard_p, const void *guard_q, uint32_t *suspect, uint64_t *result,
+                                     hipStream_t stream);
 
 hipError_t sum_sizes_launch(const uint32_t *sizes, size_t n, uint32_t raw_bytes, uint64_t *totals, hipStream_t stream);
 hipError_t gen_random_launch(uint64_t seed, uint64_t first_block, size_t nblocks, size_t block_bytes, uint8_t *dst,

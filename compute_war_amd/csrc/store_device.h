@@ -1,5 +1,5 @@
 // store_device.h -- what the chunk store's kernel files share (restore_, read_, store_gc_, renumber_, account_, replicate_, scrub_
-// and guard_kernels.hip): the directory entry and its soundness rule, the value -> index rules of a directory, the workgroup and
+// guard_ and guard_locate_kernels.hip): the directory entry and its soundness rule, the value -> index rules of a directory, the workgroup and
 // wavefront sums, the wavefront's copy of its lanes' extents, and on the host side the scan scratch and the three grid rules.
 // Each file keeps its own StreamScratch registry (launch functions nest on a stream); nothing here holds state.
 #pragma once

@@ -886,6 +886,26 @@ def dev_store_guard2_rebuild(d_store: int, store_bytes: int, d_dir: int, dir_bas
                                             guard_bytes, d_values, d_count, max_count, d_out or None, out_bytes, d_out_loc, d_status, d_result, stream))
 
 
+# ---- which entries the syndromes suspect (cw_dev_store_guard_locate / cw_dev_store_guard2_locate) ---------
+def dev_store_guard_locate(d_store: int, store_bytes: int, d_dir: int, dir_base: int, dir_entries: int, d_covered: int, stripe: int, group: int,
+                           d_guard: int, guard_bytes: int, d_suspect: int, d_result: int, stream: int = 0) -> None:
+    """d_suspect (u32 per directory entry) = 0, bit 1 when a byte of the entry's extent lies in a guard cell that differs (every such
+    cell of the single guard is ambiguous), or exactly 4 for an entry that is not all zero and not protected.  d_result[0..8) =
+    verdict (1: the cursor lies above the store, only d_result is written), the groups below the cursor, dirty cells, located cells
+    (0 here), ambiguous cells, entries with bit 0 or 1, entries with value 4, 0.  d_suspect is d_live-shaped.  Not synchronised."""
+    check(lib().cw_dev_store_guard_locate(d_store or None, store_bytes, d_dir, dir_base, dir_entries, d_covered, stripe, group, d_guard, guard_bytes,
+                                          d_suspect, d_result, stream))
+
+
+def dev_store_guard2_locate(d_store: int, store_bytes: int, d_dir: int, dir_base: int, dir_entries: int, d_covered: int, stripe: int, group: int,
+                            d_guard_p: int, d_guard_q: int, guard_bytes: int, d_suspect: int, d_result: int, stream: int = 0) -> None:
+    """``dev_store_guard_locate`` with both syndromes: a cell whose differences P', Q' are both non-zero with Q' = 2^m (x) P' for a
+    member m below the cursor is LOCATED(m) -- one wrong store byte, in member m -- and sets bit 0 of the entries that hold that very
+    byte; every other dirty cell is ambiguous and sets bit 1 of every entry with a byte in it.  Not synchronised."""
+    check(lib().cw_dev_store_guard2_locate(d_store or None, store_bytes, d_dir, dir_base, dir_entries, d_covered, stripe, group, d_guard_p, d_guard_q,
+                                           guard_bytes, d_suspect, d_result, stream))
+
+
 class Store(C.Structure):
     """cw_store: the caller-owned triple of the chunk store (bytes, cursor, directory) as one argument."""
     _fields_ = [("d_store", C.c_void_p), ("store_bytes", C.c_size_t), ("d_used", C.c_void_p), ("d_dir", C.c_void_p),

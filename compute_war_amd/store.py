@@ -13,7 +13,7 @@ import numpy as np
 
 from ._lib import CwError, lib
 from .ops import (ACCOUNT_DTYPE, DELTA_OP_DTYPE, CdcParams, ChunkLoc, DedupeIndex, DeltaOp, Store, _comp_id, _hash_id, _np_u8, chunk_slots_bytes,
-                  dev_apply_delta, dev_hash_chunks, dev_read_ranges, dev_recipe_diff, dev_restore_chunks, dev_store_account, dev_store_chunks, dev_store_compact, dev_store_export_chunks, dev_store_guard_check, dev_store_guard_rebuild, dev_store_guard_update, dev_store_guard2_check, dev_store_guard2_rebuild, dev_store_guard2_update, dev_store_import_chunks, dev_store_mark,
+                  dev_apply_delta, dev_hash_chunks, dev_read_ranges, dev_recipe_diff, dev_restore_chunks, dev_store_account, dev_store_chunks, dev_store_compact, dev_store_export_chunks, dev_store_guard_check, dev_store_guard_rebuild, dev_store_guard_update, dev_store_guard2_check, dev_store_guard2_locate, dev_store_guard2_rebuild, dev_store_guard2_update, dev_store_guard_locate, dev_store_import_chunks, dev_store_mark,
                   dev_store_renumber, dev_store_replace_chunks, dev_scatter_extents, dev_translate_refs, device_count, digest_bytes, init, store_guard_bytes, store_ingest,
                   store_compose, store_ingest_streams, store_patch, store_restore, store_scrub)
 
@@ -111,6 +111,25 @@ class ScrubReport:
     @property
     def clean(self) -> bool:
         return len(self.damaged) == 0
+
+
+LOCATE_TOTALS = ("groups", "dirty_cells", "located_cells", "ambiguous_cells", "suspects", "unprotected")  # d_result[1..7) of a locate
+
+
+class GuardSuspects:
+    """What ``ChunkStore.guard_locate`` read from the guard's syndromes: ``status`` (uint32, one per directory entry: 0 nothing, bit 0
+    a byte of the entry is the one wrong byte of a located cell, bit 1 a byte of it lies in an ambiguous cell, 4 the entry is not
+    protected and cannot be judged), ``located`` (the values with bit 0), ``ambiguous`` (with bit 1), ``unprotected`` (with 4),
+    ``suspects`` (located or ambiguous), all ascending, and ``totals`` (LOCATE_TOTALS as a dict).  A hint, never a verdict: a scrub of
+    the suspects decides.  Stale after ``ChunkStore.renumber``, like a ``ScrubReport``."""
+
+    def __init__(self, status, totals: dict, dir_base: int):
+        self.status, self.totals = np.ascontiguousarray(status, dtype=np.uint32), totals
+        at = lambda mask: (np.nonzero(mask)[0].astype(np.uint64) + np.uint64(dir_base))  # noqa: E731
+        self.located = at((self.status & 1) != 0)
+        self.ambiguous = at((self.status & 2) != 0)
+        self.unprotected = at(self.status == 4)
+        self.suspects = at((self.status & 3) != 0)
 
 
 TOTALS = ("nonzero", "nonzero_stored", "referenced", "referenced_stored", "shared", "shared_stored", "missing")  # d_totals[1..7]
@@ -274,7 +293,9 @@ class ChunkStore:
     queued guard update, ``guard_check`` says which groups of stripes no longer match, and ``repair_local`` rebuilds the chunks a scrub
     found damaged from the guard, in place and without a peer.  ``protect(parity=2)`` keeps a second, GF(2^8)-weighted syndrome beside
     the XOR one (section 29): two damaged chunks that meet in a guard byte are then both rebuilt, and ``last_repair`` says how many
-    chunks of the last ``repair_local`` needed it."""
+    chunks of the last ``repair_local`` needed it.  ``guard_locate`` reads the suspect chunks off the guard's syndromes in about the
+    time of a ``guard_check`` (section 31), ``scrub(values=...)`` checks only those, and ``heal`` is locate, that scrub,
+    ``repair_local`` and one more check in one call: a store that checks and mends itself without a full scrub."""
     last_stats = None
     last_patch = None
     last_compose = None
@@ -355,6 +376,45 @@ class ChunkStore:
         bits = bad.cpu().numpy()[:checked]
         which = np.nonzero(bits)[0].tolist()
         return (differ, which, bits[which].tolist()) if detail else (differ, which)
+
+    def guard_locate(self) -> GuardSuspects:
+        """Which chunks the guard's syndromes suspect, in about the time of a ``guard_check`` (``dev_store_guard_locate``, DESIGN.md
+        section 31): every entry with a byte in a guard cell that differs.  On a parity-2 store the two syndromes of a cell with one
+        wrong byte name its member, and only the entry that holds that byte is suspected (``located``); everything else -- every
+        cell of a parity-1 store, a damaged guard byte, two wrong bytes in one cell -- suspects every entry with a byte in the cell
+        (``ambiguous``).  Raises CwError (-4) on a store that is not protected."""
+        import torch
+        self._need_guard()
+        status, result = _zeros(self.dir_entries, torch.int32), _zeros(8)
+        torch.cuda.synchronize()
+        self._guard_call(dev_store_guard_locate, dev_store_guard2_locate, (self.d_dir.data_ptr(), self.dir_base, self.dir_entries, self.d_covered.data_ptr()),
+                         (status.data_ptr(), result.data_ptr()))
+        torch.cuda.synchronize()
+        words = _words(result)
+        if words[0]:
+            raise CwError(-4, f"chunk store: the guard's cursor {self.protected_bytes()} lies above the store's {self.store_bytes} bytes")
+        return GuardSuspects(status.cpu().numpy().view(np.uint32)[:self.dir_entries], dict(zip(LOCATE_TOTALS, words[1:7])), self.dir_base)
+
+    def heal(self, verify: bool = True) -> dict:
+        """Check and mend in one call, without a full scrub: ``guard_locate()``, then ``scrub(values=suspects)`` -- the digests decide,
+        the syndromes only say where to look -- then ``repair_local`` of what that scrub found damaged, then one more ``guard_check``.
+        With no suspects it stops after the locate: no scrub window runs.  Returns ``repair_local``'s dict and suspects, located,
+        ambiguous (lists of values), cleared (the suspects the scrub found good: the price of ambiguity), windows (the scrub windows
+        taken) and groups_left (the groups that still differ afterwards).  Groups can still differ for damage in bytes no live entry
+        names, damage in the guard's own bytes, and chunks ``repair_local`` left out: neither the store nor the guard is written for
+        these, and ``protect()`` again folds a fresh guard over the bytes as they are.  No byte is ever written on the syndromes'
+        word alone: two wrong bytes in one cell can look like one wrong byte of a third member."""
+        found = self.guard_locate()
+        out = dict(repaired=[], collided=[], unprotected=[], failed=[], no_digest=[], suspects=found.suspects.tolist(),
+                   located=found.located.tolist(), ambiguous=found.ambiguous.tolist(), cleared=[], windows=0, groups_left=0)
+        if len(found.suspects):
+            report = self.scrub(values=found)
+            out.update(self.repair_local(report, verify))
+            out["cleared"] = np.setdiff1d(found.suspects, report.damaged).tolist()
+            out["windows"] = report.stats["windows"]
+        if len(found.suspects) or found.totals["dirty_cells"]:
+            out["groups_left"] = self.guard_check()[0]
+        return out
 
     def _need_guard(self) -> None:
         if self.d_guard is None:
@@ -1077,13 +1137,26 @@ class ChunkStore:
         their stored form, and ``other`` gets recipes of its own for the same streams."""
         return other.import_bundle(self.export_bundle(recipes, known=other.index), verify)
 
-    def scrub(self, keep=None) -> ScrubReport:
+    def scrub(self, keep=None, values=None) -> ScrubReport:
         """Check every stored chunk once against the digest the index holds for its value (cw_store_scrub), in
         windows of CW_STORE_PIECE decoded bytes.  ``keep`` is a list of recipes: only the entries they name are checked, and a named
         entry that is missing shows as status 2; None checks every entry that is not all zero.  Raises CwError (-2) when a kept
-        recipe names a value outside the directory."""
+        recipe names a value outside the directory.  ``values`` -- a list or array of values, or the ``GuardSuspects`` of
+        ``guard_locate``, whose suspects are meant -- selects entries in the same way: only they are checked; a value outside the
+        directory raises CwError (-2), and ``keep`` together with ``values`` is a ValueError."""
         import torch
+        if keep is not None and values is not None:
+            raise ValueError("scrub takes keep or values, not both")
         d_live = 0
+        if values is not None:
+            vals = np.ascontiguousarray(values.suspects if isinstance(values, GuardSuspects) else values, dtype=np.uint64).reshape(-1)
+            idx = vals - np.uint64(self.dir_base)
+            if (vals < np.uint64(self.dir_base)).any() or (idx >= np.uint64(self.dir_entries)).any():
+                raise CwError(-2, f"chunk store: values outside the directory [{self.dir_base}, {self.dir_base + self.dir_entries})")
+            live = _zeros(self.dir_entries, torch.int32)
+            if len(idx):
+                live[torch.from_numpy(idx.astype(np.int64)).cuda()] = 1
+            d_live = live.data_ptr()
         if keep is not None:
             live, n_out = self._mark(keep, self._stream())
             torch.cuda.synchronize()

@@ -1230,6 +1230,39 @@ int cw_dev_store_guard2_rebuild(const void *d_store, size_t store_bytes, const c
                                 size_t out_bytes, cw_chunk_loc *d_out_loc, uint32_t *d_status /* [max_count] */, uint64_t *d_result /* [5] */,
                                 void *stream);
 
+/* ---- locating damage from the syndromes: which entries to scrub, in the time of a check ---------------------
+ * A CELL is one guard byte: group g < N = ceil(*d_covered / W), column c < S.  Its members below the cursor are the store positions
+ * q_m = g * W + m * S + c < *d_covered, m < G.  P' = the guard byte XOR those store bytes; Q' (dual call only) = the Q byte XOR the
+ * XOR of 2^m (x) d_store[q_m].  A cell is DIRTY when P' != 0, on the dual call when P' != 0 or Q' != 0.  A dirty cell is
+ *   LOCATED(m)   dual call only: P' != 0, Q' != 0 and Q' == 2^m (x) P' for an m with q_m < *d_covered (unique, as G <= 255): what one
+ *                wrong store byte, in member m, leaves behind -- the RAID-6 error-location identity;
+ *   AMBIGUOUS    otherwise: every dirty cell of the single guard; a dual cell where only one syndrome differs (typically a damaged
+ *                guard byte); a dual cell with no such m (two or more wrong bytes).
+ * An entry is PROTECTED as for cw_dev_store_guard_rebuild: not all zero, sound, and pos + stored <= *d_covered.  d_suspect[idx], one u32
+ * per directory entry idx < dir_entries (dir_base shifts none of them):
+ *   0            an all-zero entry, or a protected entry none of whose bytes is flagged;
+ *   bit 0        some byte p of its extent lies in a cell LOCATED(m) with m = the member of p, (p / S) % G;
+ *   bit 1        some byte of its extent lies in an AMBIGUOUS cell;
+ *   4 exactly    the entry is not all zero and not protected: it cannot be judged.
+ * d_result[8] = {verdict, N, the dirty cells, the located cells, the ambiguous cells, the entries with bit 0 or bit 1, the entries
+ * with value 4, 0}.  Verdict 1 when *d_covered > store_bytes: then only d_result is written, {1, 0, 0, 0, 0, 0, 0, 0}.  Every output
+ * is an integer count, so the outputs are bit for bit a function of the arguments.  The syndromes hint, they do not judge: two wrong
+ * bytes of one cell can look like one wrong byte of a third member, so a caller scrubs the suspects before it mends them.  d_suspect
+ * is d_live-shaped: it can be handed as it is to cw_dev_store_verify and cw_store_scrub, where non-zero selects, and to
+ * cw_dev_store_account's d_flag.  Whatever the buffers hold, no load leaves d_store[0, *d_covered), the guard bytes of the N groups or
+ * d_dir[0..dir_entries), and no store leaves d_suspect[0..dir_entries), d_result or the per-stream scratch.  The calls do not
+ * synchronise: they can be queued behind an update.  A lane per 16-byte guard word sums as the check does and a ballot per wavefront
+ * stores its 64 dirty bits; a lane per entry then walks its extent's bits and re-sums only the dirty words.  CW_ERR_BAD_ARG, before
+ * anything is launched, for whatever the check calls refuse, a NULL d_dir, d_covered, d_suspect or d_result, dir_entries == 0 or above
+ * 2^32 - 256, a d_dir that is not 16-byte aligned, a d_suspect that is not 4-byte aligned.  Scratch, per stream:
+ * 64 + ceil(store_bytes / W) * S / 128 bytes.                                                                                      */
+int cw_dev_store_guard_locate(const void *d_store, size_t store_bytes, const cw_chunk_loc *d_dir, uint64_t dir_base, size_t dir_entries,
+                              const uint64_t *d_covered, size_t stripe, unsigned group, const void *d_guard, size_t guard_bytes,
+                              uint32_t *d_suspect /* [dir_entries] */, uint64_t *d_result /* [8] */, void *stream);
+int cw_dev_store_guard2_locate(const void *d_store, size_t store_bytes, const cw_chunk_loc *d_dir, uint64_t dir_base, size_t dir_entries,
+                               const uint64_t *d_covered, size_t stripe, unsigned group, const void *d_guard_p, const void *d_guard_q,
+                               size_t guard_bytes, uint32_t *d_suspect /* [dir_entries] */, uint64_t *d_result /* [8] */, void *stream);
+
 /* plain device memory on the calling thread's device, for C callers of cw_dev_* (the host programs link no HIP runtime) */
 void *cw_dev_alloc(size_t bytes);                                   /* NULL on failure */
 void  cw_dev_free(void *d_p);
