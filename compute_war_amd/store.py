@@ -13,9 +13,12 @@ import numpy as np
 
 from ._lib import CwError, lib
 from .ops import (ACCOUNT_DTYPE, DELTA_OP_DTYPE, CdcParams, ChunkLoc, DedupeIndex, DeltaOp, Store, _comp_id, _hash_id, _np_u8, chunk_slots_bytes,
-                  dev_apply_delta, dev_hash_chunks, dev_read_ranges, dev_recipe_diff, dev_restore_chunks, dev_store_account, dev_store_chunks, dev_store_compact, dev_store_export_chunks, dev_store_guard_check, dev_store_guard_rebuild, dev_store_guard_update, dev_store_guard2_check, dev_store_guard2_locate, dev_store_guard2_rebuild, dev_store_guard2_update, dev_store_guard_locate, dev_store_import_chunks, dev_store_mark,
-                  dev_store_renumber, dev_store_replace_chunks, dev_scatter_extents, dev_translate_refs, device_count, digest_bytes, init, store_guard_bytes, store_ingest,
-                  store_compose, store_ingest_streams, store_patch, store_restore, store_scrub)
+                  dev_apply_delta, dev_hash_chunks, dev_read_ranges, dev_recipe_diff, dev_restore_chunks, dev_scatter_extents, dev_store_account,
+                  dev_store_chunks, dev_store_compact, dev_store_export_chunks, dev_store_guard2_check, dev_store_guard2_locate,
+                  dev_store_guard2_rebuild, dev_store_guard2_update, dev_store_guard_check, dev_store_guard_locate, dev_store_guard_rebuild,
+                  dev_store_guard_update, dev_store_import_chunks, dev_store_mark, dev_store_renumber, dev_store_replace_chunks, dev_translate_refs,
+                  device_count, digest_bytes, init, store_compose, store_guard_bytes, store_ingest, store_ingest_streams, store_patch, store_restore,
+                  store_scrub)
 
 
 class Recipe:
@@ -67,12 +70,45 @@ def _words(t, n=None) -> tuple:
     return tuple(int(v) for v in t.cpu().numpy().view(np.uint64)[:n])
 
 
+def _need_device() -> None:
+    if device_count() <= 0:
+        init()  # (raises: no device)
+
+
 def _refuse_unrestored(st, refs) -> None:
     """CwError (-2) unless every status of a restore is 0."""
     if st.any():
         j = int(np.nonzero(st)[0][0])
         raise CwError(-2, f"chunk store: {int((st != 0).sum())} of {len(st)} positions not restored; position {j} (ref {int(refs[j])}) has "
                           f"status {int(st[j])}")
+
+
+def _entry_index(values, dir_base: int, dir_entries: int, report: bool = False) -> np.ndarray:
+    """The directory entries (int64) of ``values`` (uint64), or CwError (-2), worded for a ``report``'s values or for a caller's."""
+    idx = values - np.uint64(dir_base)
+    if (values < np.uint64(dir_base)).any() or (idx >= np.uint64(dir_entries)).any():
+        raise CwError(-2, f"chunk store: the report names values outside the directory [{dir_base}, {dir_base + dir_entries})" if report else
+                          f"chunk store: values outside the directory [{dir_base}, {dir_base + dir_entries})")
+    return idx.astype(np.int64)
+
+
+def _joined(recipes) -> tuple:
+    """Recipes back to back as one: (refs, offsets from 0, the byte at which each starts, the position at which each starts), uint64."""
+    starts = np.concatenate([np.zeros(1, np.uint64), np.cumsum([r.nbytes for r in recipes], dtype=np.uint64)])
+    first = np.concatenate([np.zeros(1, np.uint64), np.cumsum([len(r.refs) for r in recipes], dtype=np.uint64)])
+    refs = np.concatenate([r.refs for r in recipes]) if recipes else np.zeros(0, np.uint64)
+    offs = np.concatenate([np.zeros(1, np.uint64)] + [r.offsets[1:] - r.offsets[0] + starts[i] for i, r in enumerate(recipes)])
+    return refs, offs, starts, first
+
+
+def _looked_up(index: DedupeIndex, d_dig, k: int, s: int) -> np.ndarray:
+    """What ``index`` answers for the k digests of the device tensor d_dig (``dev_lookup``): their values or MISS, uint64[k]."""
+    import torch
+    found, n_found = _zeros(k), _zeros(1)
+    torch.cuda.synchronize()
+    index.dev_lookup(d_dig.data_ptr(), k, found.data_ptr(), n_found.data_ptr(), s)
+    torch.cuda.synchronize()
+    return found.cpu().numpy().view(np.uint64)[:k]
 
 
 def _export_chunks(cs: "ChunkStore", d_val, nc: int, s: int, damaged: str | None = None, whence: str = ""):
@@ -83,8 +119,8 @@ def _export_chunks(cs: "ChunkStore", d_val, nc: int, s: int, damaged: str | None
     d_count, d_loc, res, out, total = _u64([nc]), _zeros(nc * 2), _zeros(3), None, 0
     for dry in (True, False):
         torch.cuda.synchronize()
-        dev_store_export_chunks(cs.d_store.data_ptr(), cs.store_bytes, cs.d_dir.data_ptr(), cs.dir_base, cs.dir_entries, d_val.data_ptr(),
-                                d_count.data_ptr(), nc, 0 if dry else out.data_ptr(), total, d_loc.data_ptr(), res.data_ptr(), s)
+        dev_store_export_chunks(*cs._bytes_args(), *cs._dir_args(), d_val.data_ptr(), d_count.data_ptr(), nc, 0 if dry else out.data_ptr(),
+                                total, d_loc.data_ptr(), res.data_ptr(), s)
         torch.cuda.synchronize()
         verdict, needed = _words(res, 2)
         if verdict == 2 and damaged:
@@ -196,8 +232,7 @@ def apply_delta(old, delta: Delta) -> bytes:
     """The new stream's bytes from the old stream's and a ``Delta`` (``dev_apply_delta``): one upload, one call, one download.
     Nothing of the delta is trusted: raises CwError (-2) naming the first malformed op, or when the ops build another size than
     ``delta.new_bytes`` or ``old`` is not of ``delta.old_bytes`` bytes."""
-    if device_count() <= 0:
-        init()  # (raises: no device)
+    _need_device()
     import torch
     a = _np_u8(old)
     if a.size != delta.old_bytes:
@@ -321,6 +356,16 @@ class ChunkStore:
     def used(self) -> int:
         return int(self.d_used.item())
 
+    # the stored bytes and the directory as the ABI's calls take them
+    def _bytes_args(self) -> tuple:
+        return self.d_store.data_ptr(), self.store_bytes
+
+    def _dir_args(self) -> tuple:
+        return self.d_dir.data_ptr(), self.dir_base, self.dir_entries
+
+    def _triple(self) -> Store:
+        return Store(*self._bytes_args(), self.d_used.data_ptr(), *self._dir_args())
+
     def protect(self, stripe: int = 65536, group: int = 16, parity: int = 1) -> None:
         """Put guard stripes over the store: a guard of store_bytes / group bytes and its cursor, then one
         update that folds in the bytes [0, used()).  ``stripe`` is a power of two in [65536, 2^30], ``group`` in [1, 256].  A store
@@ -344,8 +389,8 @@ class ChunkStore:
         """One guard call of ops.py on this store's stream, ``single`` or ``dual`` by the store's parity: the store's bytes, ``front``
         (the call's arguments between them and the geometry), the geometry, the guard or guards and their size, ``back`` (the rest)."""
         guards = [self.d_guard.data_ptr()] + ([] if self.d_guard_q is None else [self.d_guard_q.data_ptr()])
-        (single if self.d_guard_q is None else dual)(self.d_store.data_ptr(), self.store_bytes, *front, self.stripe, self.group, *guards,
-                                                     self.d_guard.numel(), *back, self._stream())
+        (single if self.d_guard_q is None else dual)(*self._bytes_args(), *front, self.stripe, self.group, *guards, self.d_guard.numel(), *back,
+                                                     self._stream())
 
     def _fold(self) -> None:
         """The one guard update: queued, not synchronised.  Nothing when the store is not protected."""
@@ -387,7 +432,7 @@ class ChunkStore:
         self._need_guard()
         status, result = _zeros(self.dir_entries, torch.int32), _zeros(8)
         torch.cuda.synchronize()
-        self._guard_call(dev_store_guard_locate, dev_store_guard2_locate, (self.d_dir.data_ptr(), self.dir_base, self.dir_entries, self.d_covered.data_ptr()),
+        self._guard_call(dev_store_guard_locate, dev_store_guard2_locate, (*self._dir_args(), self.d_covered.data_ptr()),
                          (status.data_ptr(), result.data_ptr()))
         torch.cuda.synchronize()
         words = _words(result)
@@ -433,8 +478,8 @@ class ChunkStore:
         index as it was before the fused call."""
         import torch
         dev_store_chunks(self.comp_alg, src.data_ptr(), n, off.data_ptr(), k_dev.data_ptr(), cap - 1, slots.data_ptr(), sizes.data_ptr(),
-                         self.base, self.d_store.data_ptr(), self.store_bytes, self.d_used.data_ptr(), self.d_dir.data_ptr(), self.dir_base,
-                         self.dir_entries, result.data_ptr(), s, new_idx.data_ptr(), n_new.data_ptr())
+                         self.base, *self._bytes_args(), self.d_used.data_ptr(), *self._dir_args(), result.data_ptr(), s, new_idx.data_ptr(),
+                         n_new.data_ptr())
         torch.cuda.synchronize()
         verdict, needed = _words(result)
         if verdict:
@@ -446,9 +491,16 @@ class ChunkStore:
                 torch.cuda.synchronize()
                 self.index.retain(none_live.data_ptr(), self.base, k)
             err = self._no_room("chunk store", needed, self.used()) if verdict == 1 else self._off_directory("chunk store", k)
-            err.needed = needed
+            err.needed = needed  # (for the directory's refusal: _no_room has set it)
             raise err
         self.base += k
+
+    def _fused_buffers(self, n: int, cap: int) -> tuple:
+        """The outputs of a fused call over n bytes with room for cap offsets and of the ``_append`` behind it, unsynchronised."""
+        import torch
+        total = chunk_slots_bytes(self.comp_alg, n, cap - 1)
+        return (total, _zeros(cap), _zeros(1), _zeros(cap * digest_bytes(self.index.hash_alg), torch.uint8), _zeros(cap),
+                _zeros(cap, torch.int32), _zeros(1), torch.empty(total, dtype=torch.uint8, device="cuda"), _zeros(cap, torch.int32), _zeros(2))
 
     @_folds
     def ingest(self, data) -> Recipe:
@@ -461,10 +513,7 @@ class ChunkStore:
         n, s = a.size, self._stream()
         src = torch.from_numpy(a.copy() if n else np.zeros(1, np.uint8)).cuda()
         cap = self.params.max_offsets(n)
-        total = chunk_slots_bytes(self.comp_alg, n, cap - 1)
-        off, k_dev, dig = _zeros(cap), _zeros(1), _zeros(cap * digest_bytes(self.index.hash_alg), torch.uint8)
-        ref, new_idx, n_new = _zeros(cap), _zeros(cap, torch.int32), _zeros(1)
-        slots, sizes, result = torch.empty(total, dtype=torch.uint8, device="cuda"), _zeros(cap, torch.int32), _zeros(2)
+        total, off, k_dev, dig, ref, new_idx, n_new, slots, sizes, result = self._fused_buffers(n, cap)
         torch.cuda.synchronize()
         k = self.index.dev_cdc_dedupe_compress(self.params, self.comp_alg, src.data_ptr(), n, True, self.base, off.data_ptr(), cap,
                                                k_dev.data_ptr(), dig.data_ptr(), ref.data_ptr(), new_idx.data_ptr(), n_new.data_ptr(),
@@ -486,10 +535,7 @@ class ChunkStore:
         src = torch.from_numpy(np.concatenate(parts) if n else np.zeros(1, np.uint8)).cuda()
         d_ends = torch.from_numpy(ends.view(np.int64)).cuda()
         cap = self.params.max_offsets_streams(n, nf)
-        total = chunk_slots_bytes(self.comp_alg, n, cap - 1)
-        off, k_dev, dig = _zeros(cap), _zeros(1), _zeros(cap * digest_bytes(self.index.hash_alg), torch.uint8)
-        ref, new_idx, n_new = _zeros(cap), _zeros(cap, torch.int32), _zeros(1)
-        slots, sizes, result = torch.empty(total, dtype=torch.uint8, device="cuda"), _zeros(cap, torch.int32), _zeros(2)
+        total, off, k_dev, dig, ref, new_idx, n_new, slots, sizes, result = self._fused_buffers(n, cap)
         first, ends_ok = _zeros(nf + 1), _zeros(1)
         torch.cuda.synchronize()
         k = self.index.dev_cdc_streams_dedupe_compress(self.params, self.comp_alg, src.data_ptr(), n, d_ends.data_ptr(), nf, self.base,
@@ -502,9 +548,6 @@ class ChunkStore:
         starts = np.concatenate([np.zeros(1, np.uint64), ends[:-1]])
         return [Recipe(refs[a:b], offs[a:b + 1] - starts[f]) if b > a else Recipe([], [0])
                 for f, (a, b) in enumerate(zip(lo[:-1].tolist(), lo[1:].tolist()))]
-
-    def _triple(self) -> Store:
-        return Store(self.d_store.data_ptr(), self.store_bytes, self.d_used.data_ptr(), self.d_dir.data_ptr(), self.dir_base, self.dir_entries)
 
     @_folds
     def ingest_stream(self, data) -> Recipe:
@@ -555,13 +598,9 @@ class ChunkStore:
     def restore_many_stream(self, recipes) -> list:
         """``restore_stream`` of many recipes in one pipelined run: the recipes are joined into one with the offsets shifted, restored
         by one cw_store_restore, and the bytes split again.  Raises as ``restore`` does."""
-        recipes = list(recipes)
-        sizes = [r.nbytes for r in recipes]
-        starts = np.concatenate([np.zeros(1, np.uint64), np.cumsum(sizes, dtype=np.uint64)])
-        refs = np.concatenate([r.refs for r in recipes]) if recipes else np.zeros(0, np.uint64)
-        offs = np.concatenate([np.zeros(1, np.uint64)] + [r.offsets[1:] - r.offsets[0] + starts[i] for i, r in enumerate(recipes)])
+        refs, offs, starts, _ = _joined(list(recipes))
         whole = self.restore_stream(Recipe(refs, offs))
-        return [whole[int(a):int(a) + n] for a, n in zip(starts[:-1], sizes)]
+        return [whole[int(a):int(b)] for a, b in zip(starts[:-1], starts[1:])]
 
     def restore_stream(self, recipe: Recipe) -> bytes:
         """``restore`` into host memory, window by window with downloads beside the kernels.  Raises as ``restore`` does."""
@@ -579,8 +618,8 @@ class ChunkStore:
         d_ref, d_raw, d_count = _u64(recipe.refs if k else [0]), _u64(recipe.offsets - recipe.offsets[0]), _u64([k])
         out, status = _zeros(n, torch.uint8), _zeros(k, torch.int32)
         torch.cuda.synchronize()
-        dev_restore_chunks(self.comp_alg, self.d_store.data_ptr(), self.store_bytes, self.d_dir.data_ptr(), self.dir_base, self.dir_entries,
-                           d_ref.data_ptr(), d_raw.data_ptr(), d_count.data_ptr(), k, out.data_ptr(), n, status.data_ptr(), s)
+        dev_restore_chunks(self.comp_alg, *self._bytes_args(), *self._dir_args(), d_ref.data_ptr(), d_raw.data_ptr(), d_count.data_ptr(), k,
+                           out.data_ptr(), n, status.data_ptr(), s)
         if verify and k:
             dig, found, n_found = _zeros(k * digest_bytes(self.index.hash_alg), torch.uint8), _zeros(k), _zeros(1)
             torch.cuda.synchronize()  # (torch zeroed them on its own stream)
@@ -600,8 +639,7 @@ class ChunkStore:
         """The bytes of the ranges ``(offset, length)`` of an ingested stream, in the recipe's own zero-based coordinates, without
         restoring the stream: one device call, the destinations packed back to back.  Raises CwError (-2) naming the first range
         with a status other than 0."""
-        if device_count() <= 0:
-            init()  # (raises: no device)
+        _need_device()
         import torch
         ranges = [(int(o), int(l)) for o, l in ranges]
         k, m, s = len(recipe.refs), len(ranges), self._stream()
@@ -616,9 +654,8 @@ class ChunkStore:
         d_off, d_len, d_to, d_m = _u64([o for o, _ in ranges]), _u64(lens), _u64(dsts[:-1]), _u64([m])
         out, status = _zeros(total, torch.uint8), _zeros(m, torch.int32)
         torch.cuda.synchronize()
-        dev_read_ranges(self.comp_alg, self.d_store.data_ptr(), self.store_bytes, self.d_dir.data_ptr(), self.dir_base, self.dir_entries,
-                        d_ref.data_ptr(), d_raw.data_ptr(), d_count.data_ptr(), k, d_off.data_ptr(), d_len.data_ptr(), d_to.data_ptr(),
-                        d_m.data_ptr(), m, out.data_ptr(), total, status.data_ptr(), s)
+        dev_read_ranges(self.comp_alg, *self._bytes_args(), *self._dir_args(), d_ref.data_ptr(), d_raw.data_ptr(), d_count.data_ptr(), k,
+                        d_off.data_ptr(), d_len.data_ptr(), d_to.data_ptr(), d_m.data_ptr(), m, out.data_ptr(), total, status.data_ptr(), s)
         torch.cuda.synchronize()
         st = status.cpu().numpy()
         if st.any():
@@ -641,8 +678,7 @@ class ChunkStore:
         is how far behind the edit the first window reaches; it doubles until the cuts resynchronise.  Raises CwError (-5) when the
         index, the directory, the store or the device's memory cannot take the window, and CwError (-2) when a position of the
         window does not restore or the edit leaves the stream; store, index and ``base`` are then unchanged."""
-        if device_count() <= 0:
-            init()  # (raises: no device)
+        _need_device()
         import torch
         offset, remove = int(offset), int(remove)
         if offset < 0 or remove < 0:
@@ -672,13 +708,7 @@ class ChunkStore:
         """``patch`` for several edits ``(offset, remove, data)``, all in the coordinates of the stream as it is now: they must not
         overlap or share an offset with an insert (ValueError, before any of them runs) and are applied from the highest offset
         down, one ``patch`` each.  ``last_patch`` is the last applied edit's, the one with the lowest offset."""
-        edits = sorted(((int(o), int(r), d) for o, r, d in edits), key=lambda e: (e[0], e[1]))
-        for (o, r, _), (o2, _, _) in zip(edits, edits[1:]):
-            if o + r > o2 or (o == o2 and r == 0):
-                raise ValueError(f"edits overlap: ({o}, {r}) and the one at {o2}")
-        if any(o < 0 or r < 0 or o + r > recipe.nbytes for o, r, _ in edits):
-            raise ValueError(f"an edit leaves the stream's {recipe.nbytes} bytes")
-        for o, r, d in reversed(edits):
+        for o, r, d in reversed(self._sorted_edits(recipe, edits)):
             recipe = self.patch(recipe, o, r, d)
         return recipe
 
@@ -696,13 +726,9 @@ class ChunkStore:
     @_folds
     def _compose_call(self, sources, ops, payload, lookahead: int) -> Recipe:
         """One ``store_compose`` over the recipes ``sources`` joined as ``restore_many_stream`` joins them, with their stream index."""
-        if device_count() <= 0:
-            init()  # (raises: no device)
+        _need_device()
         import torch
-        refs = np.concatenate([r.refs for r in sources]) if sources else np.zeros(0, np.uint64)
-        starts = np.concatenate([np.zeros(1, np.uint64), np.cumsum([r.nbytes for r in sources], dtype=np.uint64)])
-        offs = np.concatenate([np.zeros(1, np.uint64)] + [r.offsets[1:] - r.offsets[0] + starts[i] for i, r in enumerate(sources)])
-        first = np.concatenate([np.zeros(1, np.uint64), np.cumsum([len(r.refs) for r in sources], dtype=np.uint64)])
+        refs, offs, _, first = _joined(sources)
         torch.cuda.synchronize()  # (the store was written on torch's stream)
         out_refs, out_offs, stats = store_compose(self.index, self.params, self.comp_alg, self._triple(), refs, offs, ops, payload, self.base, lookahead,
                                                   first if len(sources) > 1 else None)
@@ -742,8 +768,7 @@ class ChunkStore:
         """Version B inside the store from version A's recipe and a ``Delta`` made against A: ``compose`` with the delta's ops and
         payload.  Nothing of the delta is trusted: raises CwError (-2) when it was made against another size than ``old.nbytes``, when
         its ops build another size than ``delta.new_bytes``, or naming the first malformed op."""
-        if device_count() <= 0:
-            init()  # (raises: no device)
+        _need_device()
         if delta.old_bytes != old.nbytes:
             raise CwError(-2, f"delta: made against an old stream of {delta.old_bytes} bytes, not {old.nbytes}")
         total = int(delta.ops["len"].sum(dtype=np.uint64)) if len(delta.ops) else 0
@@ -792,8 +817,7 @@ class ChunkStore:
         """What changed between two recipes of this store (``dev_recipe_diff``): no data is read, equal refs
         mean equal bytes.  One call with room for ``max_ops`` ops, and a second one with the room the first reported when that was too
         little.  Raises CwError (-2) when a recipe's offsets are not what the library writes."""
-        if device_count() <= 0:
-            init()  # (raises: no device)
+        _need_device()
         import torch
         for attempt in range(2):
             t = self._diff_call(old, new, max_ops, False)
@@ -811,16 +835,15 @@ class ChunkStore:
         over ``new``, with one synchronise (room for one op per position and for every byte of ``new``).  Raises CwError (-2) naming
         the first range whose status is not 0 (a damaged stored chunk, say), or when a recipe's offsets are not what the library
         writes."""
-        if device_count() <= 0:
-            init()  # (raises: no device)
+        _need_device()
         import torch
         kb, nbytes, s = len(new.refs), new.nbytes, self._stream()
         cap = max(kb, 1)
         payload, status = _zeros(nbytes, torch.uint8), _zeros(cap, torch.int32)
         t = self._diff_call(old, new, cap, True)
-        dev_read_ranges(self.comp_alg, self.d_store.data_ptr(), self.store_bytes, self.d_dir.data_ptr(), self.dir_base, self.dir_entries,
-                        t["ref_b"].data_ptr(), t["off_b"].data_ptr(), t["nb"].data_ptr(), kb, t["new_off"].data_ptr(), t["new_len"].data_ptr(),
-                        t["new_dst"].data_ptr(), t["nnew"].data_ptr(), cap, payload.data_ptr(), nbytes, status.data_ptr(), s)
+        dev_read_ranges(self.comp_alg, *self._bytes_args(), *self._dir_args(), t["ref_b"].data_ptr(), t["off_b"].data_ptr(), t["nb"].data_ptr(), kb,
+                        t["new_off"].data_ptr(), t["new_len"].data_ptr(), t["new_dst"].data_ptr(), t["nnew"].data_ptr(), cap, payload.data_ptr(),
+                        nbytes, status.data_ptr(), s)
         torch.cuda.synchronize()
         totals = _words(t["totals"])
         self._refuse_recipes(totals[0])
@@ -865,8 +888,8 @@ class ChunkStore:
         live, n_out = self._mark(keep, s)
 
         def run(d_new_store: int, new_bytes: int):
-            dev_store_compact(self.d_store.data_ptr(), self.store_bytes, self.d_dir.data_ptr(), n, live.data_ptr(), d_new_store, new_bytes,
-                              new_used.data_ptr(), new_dir.data_ptr(), result.data_ptr(), s)
+            dev_store_compact(*self._bytes_args(), self.d_dir.data_ptr(), n, live.data_ptr(), d_new_store, new_bytes, new_used.data_ptr(),
+                              new_dir.data_ptr(), result.data_ptr(), s)
             torch.cuda.synchronize()
             verdict, needed, kept, dropped = _words(result)
             if verdict:
@@ -983,8 +1006,8 @@ class ChunkStore:
         d_flag = None if flagged is None else _u8(flagged)
         acct, refcount, owner, totals = _zeros(nf * 8), _zeros(n, torch.int32), _zeros(n, torch.int32), _zeros(8)
         torch.cuda.synchronize()  # (torch zeroed and copied on its own stream)
-        dev_store_account(d_ref.data_ptr(), d_first.data_ptr(), nf, k, self.d_dir.data_ptr(), self.dir_base, n,
-                          0 if d_flag is None else d_flag.data_ptr(), acct.data_ptr(), refcount.data_ptr(), owner.data_ptr(), totals.data_ptr(), s)
+        dev_store_account(d_ref.data_ptr(), d_first.data_ptr(), nf, k, *self._dir_args(), 0 if d_flag is None else d_flag.data_ptr(),
+                          acct.data_ptr(), refcount.data_ptr(), owner.data_ptr(), totals.data_ptr(), s)
         torch.cuda.synchronize()
         t = _words(totals)
         if t[0]:
@@ -1025,11 +1048,7 @@ class ChunkStore:
                               f"({int((values == _MISS).sum())} values have none): store and index disagree")
         carry = np.ones(flagged, bool)
         if known is not None and flagged:
-            found, n_found = _zeros(flagged), _zeros(1)
-            torch.cuda.synchronize()
-            known.dev_lookup(dig.data_ptr(), flagged, found.data_ptr(), n_found.data_ptr(), s)
-            torch.cuda.synchronize()
-            carry = found.cpu().numpy().view(np.uint64)[:flagged] == _MISS
+            carry = _looked_up(known, dig, flagged, s) == _MISS
         locs, payload, nc = np.zeros(flagged, LOC_DTYPE), np.zeros(0, np.uint8), int(carry.sum())
         if nc:
             out, total, d_loc = _export_chunks(self, _u64(values[carry]), nc, s, damaged="chunk store: a named chunk's directory entry is damaged")
@@ -1060,12 +1079,8 @@ class ChunkStore:
             return [Recipe(r.refs, r.offsets) for r in bundle.recipes]
         in_bytes = len(bundle.payload)
         d_dig, d_loc, d_in = _u8(bundle.digests), _u8(bundle.locs), _u8(bundle.payload if in_bytes else np.zeros(1, np.uint8))
-        found, n_found = _zeros(n), _zeros(1)
-        torch.cuda.synchronize()
         # 2. what this store lacks, read-only; every such chunk is carried, soundly, and there is room for all of them
-        self.index.dev_lookup(d_dig.data_ptr(), n, found.data_ptr(), n_found.data_ptr(), s)
-        torch.cuda.synchronize()
-        lacks, carried, locs = found.cpu().numpy().view(np.uint64) == _MISS, bundle.carried, bundle.locs
+        lacks, carried, locs = _looked_up(self.index, d_dig, n, s) == _MISS, bundle.carried, bundle.locs
         if (lacks & ~carried).any():
             raise CwError(-2, f"chunk bundle: {int((lacks & ~carried).sum())} chunks this store lacks are listed but not carried")
         stored, length, sound = locs["stored"].astype(np.int64), locs["raw"].astype(np.int64) & 0x1FFFF, _locs_sound(locs, in_bytes)
@@ -1100,9 +1115,8 @@ class ChunkStore:
         outs = [(_u64(r.refs), _u64([len(r.refs)]), len(r.refs)) for r in bundle.recipes]
         torch.cuda.synchronize()
         self.index.dev_dedupe(d_dig.data_ptr(), n, self.base, ref.data_ptr(), new_idx.data_ptr(), n_new.data_ptr(), s)
-        dev_store_import_chunks(d_in.data_ptr(), in_bytes, d_loc.data_ptr(), d_n.data_ptr(), n, self.base, self.d_store.data_ptr(), self.store_bytes,
-                                self.d_used.data_ptr(), self.d_dir.data_ptr(), self.dir_base, self.dir_entries, result.data_ptr(), s,
-                                new_idx.data_ptr(), n_new.data_ptr())
+        dev_store_import_chunks(d_in.data_ptr(), in_bytes, d_loc.data_ptr(), d_n.data_ptr(), n, self.base, *self._bytes_args(),
+                                self.d_used.data_ptr(), *self._dir_args(), result.data_ptr(), s, new_idx.data_ptr(), n_new.data_ptr())
         for d_r, d_k, k in outs:
             if k:
                 dev_translate_refs(d_r.data_ptr(), d_k.data_ptr(), k, d_from.data_ptr(), ref.data_ptr(), d_n.data_ptr(), n, d_r.data_ptr(),
@@ -1150,12 +1164,9 @@ class ChunkStore:
         d_live = 0
         if values is not None:
             vals = np.ascontiguousarray(values.suspects if isinstance(values, GuardSuspects) else values, dtype=np.uint64).reshape(-1)
-            idx = vals - np.uint64(self.dir_base)
-            if (vals < np.uint64(self.dir_base)).any() or (idx >= np.uint64(self.dir_entries)).any():
-                raise CwError(-2, f"chunk store: values outside the directory [{self.dir_base}, {self.dir_base + self.dir_entries})")
-            live = _zeros(self.dir_entries, torch.int32)
+            idx, live = _entry_index(vals, self.dir_base, self.dir_entries), _zeros(self.dir_entries, torch.int32)
             if len(idx):
-                live[torch.from_numpy(idx.astype(np.int64)).cuda()] = 1
+                live[torch.from_numpy(idx).cuda()] = 1
             d_live = live.data_ptr()
         if keep is not None:
             live, n_out = self._mark(keep, self._stream())
@@ -1165,6 +1176,17 @@ class ChunkStore:
         torch.cuda.synchronize()  # (the store was written on torch's stream)
         status, stats = store_scrub(self.index, self.comp_alg, self._triple(), d_live)
         return ScrubReport(status, stats, self.dir_base)
+
+    def _held_digests(self, values) -> tuple:
+        """For the ascending values a report names: (their entries, the index's digests for them on the device, bool: it holds one)."""
+        import torch
+        idx, n, m = _entry_index(values, self.dir_base, self.dir_entries, report=True), self.dir_entries, len(values)
+        live, dig, val, res = _zeros(n, torch.int32), _zeros(m * digest_bytes(self.index.hash_alg), torch.uint8), _zeros(m), _zeros(3)
+        live[torch.from_numpy(idx).cuda()] = 1
+        torch.cuda.synchronize()
+        self.index.dev_export_live(live.data_ptr(), self.dir_base, n, dig.data_ptr(), val.data_ptr(), m, res.data_ptr(), self._stream())
+        torch.cuda.synchronize()
+        return idx, dig, val.cpu().numpy().view(np.uint64)[:m] != _MISS
 
     @_folds
     def repair_from(self, other: "ChunkStore", report: ScrubReport, verify: bool = True) -> dict:
@@ -1185,25 +1207,12 @@ class ChunkStore:
         out = dict(repaired=[], unavailable=[], no_digest=[])
         if len(damaged) == 0:
             return out
-        idx = damaged - np.uint64(self.dir_base)
-        if (damaged < np.uint64(self.dir_base)).any() or (idx >= np.uint64(self.dir_entries)).any():
-            raise CwError(-2, f"chunk store: the report names values outside the directory [{self.dir_base}, {self.dir_base + self.dir_entries})")
-        idx = idx.astype(np.int64)
-        s, n, db, m = self._stream(), self.dir_entries, digest_bytes(self.index.hash_alg), len(damaged)
         # 1. the digests this index holds for the damaged values, in ascending value
-        live, dig, val, res = _zeros(n, torch.int32), _zeros(m * db, torch.uint8), _zeros(m), _zeros(3)
-        live[torch.from_numpy(idx).cuda()] = 1
-        torch.cuda.synchronize()
-        self.index.dev_export_live(live.data_ptr(), self.dir_base, n, dig.data_ptr(), val.data_ptr(), m, res.data_ptr(), s)
-        torch.cuda.synchronize()
-        has = val.cpu().numpy().view(np.uint64)[:m] != _MISS
+        idx, dig, has = self._held_digests(damaged)
         out["no_digest"] = damaged[~has].tolist()
         # 2. where the peer keeps them
-        found, n_found = _zeros(m), _zeros(1)
-        torch.cuda.synchronize()
-        other.index.dev_lookup(dig.data_ptr(), m, found.data_ptr(), n_found.data_ptr(), s)
-        torch.cuda.synchronize()
-        there = found.cpu().numpy().view(np.uint64)[:m].copy()
+        s, m = self._stream(), len(damaged)
+        there = _looked_up(other.index, dig, m, s)
         o_idx = there - np.uint64(other.dir_base)
         ok = has & (there != _MISS) & (there >= np.uint64(other.dir_base)) & (o_idx < np.uint64(other.dir_entries))
         o_idx = o_idx.astype(np.int64)
@@ -1224,7 +1233,7 @@ class ChunkStore:
             good = np.ones(nc, bool)
             if verify:
                 st, dig2 = self._restored_digests(payload.data_ptr(), total, d_loc.data_ptr(), nc, np.arange(nc), len_there[which])
-                good = (st == 0) & (dig2 == dig.cpu().numpy()[:m * db].reshape(m, db)[which]).all(axis=1)
+                good = (st == 0) & (dig2 == dig.cpu().numpy().reshape(m, -1)[which]).all(axis=1)
             ok[which[~good]] = False
             which, locs = which[good], locs[good]
         out["unavailable"] = damaged[has & ~ok].tolist()
@@ -1238,9 +1247,8 @@ class ChunkStore:
             raise err
         d_loc2, d_val2, d_k, result = _u8(locs), _u64(damaged[which]), _u64([len(which)]), _zeros(2)
         torch.cuda.synchronize()
-        dev_store_replace_chunks(payload.data_ptr(), total, d_loc2.data_ptr(), d_val2.data_ptr(), d_k.data_ptr(), len(which), self.d_store.data_ptr(),
-                                 self.store_bytes, self.d_used.data_ptr(), self.d_dir.data_ptr(), self.dir_base, self.dir_entries,
-                                 result.data_ptr(), s)
+        dev_store_replace_chunks(payload.data_ptr(), total, d_loc2.data_ptr(), d_val2.data_ptr(), d_k.data_ptr(), len(which), *self._bytes_args(),
+                                 self.d_used.data_ptr(), *self._dir_args(), result.data_ptr(), s)
         torch.cuda.synchronize()
         verdict, total = _words(result)
         if verdict:
@@ -1267,25 +1275,16 @@ class ChunkStore:
         out = dict(repaired=[], collided=[], unprotected=[], failed=[], no_digest=[])
         if len(damaged) == 0:
             return out
-        idx = damaged - np.uint64(self.dir_base)
-        if (damaged < np.uint64(self.dir_base)).any() or (idx >= np.uint64(self.dir_entries)).any():
-            raise CwError(-2, f"chunk store: the report names values outside the directory [{self.dir_base}, {self.dir_base + self.dir_entries})")
-        idx = idx.astype(np.int64)
-        s, n, db, m = self._stream(), self.dir_entries, digest_bytes(self.index.hash_alg), len(damaged)
         # 1. the digests this index holds for the damaged values, in ascending value
-        live, dig, val, res = _zeros(n, torch.int32), _zeros(m * db, torch.uint8), _zeros(m), _zeros(3)
-        live[torch.from_numpy(idx).cuda()] = 1
-        torch.cuda.synchronize()
-        self.index.dev_export_live(live.data_ptr(), self.dir_base, n, dig.data_ptr(), val.data_ptr(), m, res.data_ptr(), s)
-        torch.cuda.synchronize()
-        has = val.cpu().numpy().view(np.uint64)[:m] != _MISS
+        idx, dig, has = self._held_digests(damaged)
         out["no_digest"] = damaged[~has].tolist()
         # 2. the rebuild: a dry run that sizes the payload, then the run that fills it
+        s, m = self._stream(), len(damaged)
         d_val, d_count, d_loc, d_status, result = _u64(damaged), _u64([m]), _zeros(m * 2), _zeros(m, torch.int32), _zeros(5)
         payload, total = None, 0
         for dry in (True, False):
             torch.cuda.synchronize()
-            self._guard_call(dev_store_guard_rebuild, dev_store_guard2_rebuild, (self.d_dir.data_ptr(), self.dir_base, n, self.d_covered.data_ptr()),
+            self._guard_call(dev_store_guard_rebuild, dev_store_guard2_rebuild, (*self._dir_args(), self.d_covered.data_ptr()),
                              (d_val.data_ptr(), d_count.data_ptr(), m, 0 if dry else payload.data_ptr(), total, d_loc.data_ptr(),
                               d_status.data_ptr(), result.data_ptr()))
             torch.cuda.synchronize()
@@ -1307,7 +1306,7 @@ class ChunkStore:
         if verify:
             # 3. the rebuilt chunks restore from the payload and hash to the digests this index holds
             st, dig2 = self._restored_digests(payload.data_ptr(), total, d_loc.data_ptr(), m, which, locs["raw"][which].astype(np.int64) & 0x1FFFF)
-            good = (st == 0) & (dig2 == dig.cpu().numpy()[:m * db].reshape(m, db)[which]).all(axis=1)
+            good = (st == 0) & (dig2 == dig.cpu().numpy().reshape(m, -1)[which]).all(axis=1)
         # 4. back in place, in ascending pos: an extent that starts in front of the end of the one before it is left out
         mine = self.d_dir.view(-1, 2)[torch.from_numpy(idx[which]).cuda()].cpu().numpy().reshape(-1).view(LOC_DTYPE)
         ext, end = [], 0
@@ -1322,8 +1321,7 @@ class ChunkStore:
         if ext:
             d_ext, d_n, result = _u64(np.array(ext, np.uint64)), _u64([len(ext)]), _zeros(4)
             torch.cuda.synchronize()
-            dev_scatter_extents(payload.data_ptr(), total, d_ext.data_ptr(), d_n.data_ptr(), len(ext), self.d_store.data_ptr(), self.store_bytes,
-                                result.data_ptr(), s)
+            dev_scatter_extents(payload.data_ptr(), total, d_ext.data_ptr(), d_n.data_ptr(), len(ext), *self._bytes_args(), result.data_ptr(), s)
             torch.cuda.synchronize()
             verdict = _words(result, 1)[0]
             if verdict:

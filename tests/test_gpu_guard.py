@@ -537,3 +537,56 @@ def test_save_and_load(cw, alg, tmp_path):
         index.close()
         for cs in loaded:
             cs.index.close()
+
+
+def test_both_repairs_select_entries_alike(cw):
+    """repair_local and repair_from take one report: the same value without a digest from both, the same refusal of a value below
+    dir_base.  Two chunks of one small stream are damaged; the one whose digest the index has lost gets a first token without literals,
+    a match at output position 0, so that it cannot decode and a scrub lists it as damaged, not as an orphan."""
+    import torch
+    data, base, entries = corpus_file("alice29.txt")[:65536], 5, 4096
+    ia, ib = cw.DedupeIndex("skein", 4096), cw.DedupeIndex("skein", 4096)
+    try:
+        A, B = (cw.ChunkStore(i, "lz4", cw.CdcParams.default(256), 1 << 20, entries, base) for i in (ia, ib))
+        recipe = A.ingest(data)
+        assert (B.ingest(data).refs == recipe.refs).all()
+        A.protect(65536, 4)
+        d = directory_of(A)
+        full = [i for i in range(entries) if d[i]["stored"]]
+        packed = [i for i in full if not int(d[i]["raw"]) & RM.RAW]
+        lost, hit = base + packed[len(packed) // 2], base + full[3]
+        assert lost != hit
+        token = int(A.d_store[int(d[lost - base]["pos"])].item())
+        assert token & 0xF0
+        flip(A, d, [lost], mask=token & 0xF0, where={lost: int(d[lost - base]["pos"])})
+        flip(A, d, [hit])
+        live = np.ones(entries, np.int32)
+        live[lost - base] = 0
+        d_live = torch.from_numpy(live).cuda()
+        _sync()
+        assert ia.retain(d_live.data_ptr(), base, entries) == 1
+        report = A.scrub()
+        assert report.damaged.tolist() == sorted([lost, hit]) and len(report.orphans) == 0
+        first = A.repair_local(report)
+        assert first == dict(repaired=[hit], collided=[], unprotected=[], failed=[], no_digest=[lost])
+        assert A.repair_from(B, report)["no_digest"] == [lost]
+        # neither call could judge the chunk without a digest, and neither touched it: its positions, and only they, do not restore;
+        # with its own byte put back, the stream is whole again
+        assert directory_of(A)[lost - base] == d[lost - base] and int(A.d_store[int(d[lost - base]["pos"])].item()) == token & 0x0F
+        with pytest.raises(cw.CwError) as e:
+            A.restore(recipe)
+        assert e.value.code == -2 and f": {int((recipe.refs == lost).sum())} of {len(recipe.refs)} positions not restored" in str(e.value)
+        flip(A, d, [lost], mask=token & 0xF0, where={lost: int(d[lost - base]["pos"])})
+        assert A.restore(recipe, verify=False) == data
+        below = cw.ScrubReport(np.array([3], np.uint32), {}, base - 1)
+        assert below.damaged.tolist() == [base - 1]
+        texts = []
+        for repair in (A.repair_local, lambda r: A.repair_from(B, r)):
+            with pytest.raises(cw.CwError) as e:
+                repair(below)
+            assert e.value.code == -2
+            texts.append(str(e.value))
+        assert texts[0] == texts[1] == f"libcwhc error -2: chunk store: the report names values outside the directory [{base}, {base + entries})"
+    finally:
+        ia.close()
+        ib.close()
